@@ -3,6 +3,7 @@
 
     python bench.py --gpus N --steps K --warmup W [--config c2|c3|c4|c5]
     python bench.py --gpus N --launcher inlib     one process, N GPUs behind ONE C call (icikt_pairs_multi_f64)
+    python bench.py ... --dump-outputs DIR        also write the last timed step's results as DIR/*.npy (see dump_outputs)
 
 `python bench.py --gpus N` runs AS TYPED for N = 1, 2, 4, 8: with N > 1 and no WORLD_SIZE in the environment this
 process -- before it imports torch or touches a GPU -- starts `python -m torch.distributed.run --nnodes=1
@@ -217,6 +218,33 @@ def check_against_oracle(got_out, got_cnt, ref_out, ref_cnt):
         chk["counts_bit_exact"] = bool(np.array_equal(got_cnt, ref_cnt[:, :got_cnt.shape[1]]))
     chk["ok"] = bool(chk["max_abs_diff"] <= ATOL and chk["nan_rows"] == 0 and chk.get("counts_bit_exact", True))
     return chk
+
+
+OUT_FIELDS = ("tau", "pvalue", "taumax", "completeness")   # the four doubles of a pair's result, in column order
+DUMP_LIMIT_BYTES = 64_000_000
+
+
+def dump_outputs(outdir: str, results) -> dict:
+    """--dump-outputs: the timed path's results of its last step, {perspective: (pairs, 4) float64 in combn pair order},
+    as outdir/<perspective>_<field>.npy (float64).  Over DUMP_LIMIT_BYTES in all, every file keeps the same fixed,
+    seeded sample of rows (sorted pair indices), so two builds stay comparable array for array."""
+    os.makedirs(outdir, exist_ok=True)
+    P = next(iter(results.values())).shape[0]
+    row_bytes = 8 * len(OUT_FIELDS) * len(results)
+    rows = None
+    if P * row_bytes > DUMP_LIMIT_BYTES:
+        k = (DUMP_LIMIT_BYTES - 4096) // row_bytes          # (4096: room for the .npy headers)
+        rows = np.sort(np.random.default_rng(0).choice(P, size=k, replace=False))
+    files = []
+    for persp, out in results.items():
+        assert out.shape == (P, len(OUT_FIELDS)) and out.dtype == np.float64
+        for c, field in enumerate(OUT_FIELDS):
+            col = out[:, c] if rows is None else out[rows, c]
+            name = f"{persp}_{field}"
+            np.save(os.path.join(outdir, name + ".npy"), np.ascontiguousarray(col))
+            files.append(name)
+    return {"dir": outdir, "files": files, "pairs": P, "rows": P if rows is None else int(len(rows)),
+            "sample": None if rows is None else "np.sort(np.random.default_rng(0).choice(pairs, size=rows, replace=False))"}
 
 
 PMC_RECORDS = os.path.join(ROOT, "profiles", "k1_pmc_records.json")
@@ -480,6 +508,7 @@ def run_inlib(args, cfg):
     for _ in range(args.steps):
         out, _c, _r = m.pairs(X, perspective="global", want_counts=False)
     elapsed = time.perf_counter() - t0
+    dumped = dump_outputs(args.dump_outputs, {"global": out}) if args.dump_outputs else None
     m.pairs(X, perspective="global", want_counts=False, flags=_lib.FLAG_TIMING)
     phases = m.phase_ms()
     ranks = m.rank_phase_ms()[:max(1, m.ranks_used)]
@@ -497,6 +526,8 @@ def run_inlib(args, cfg):
         "phase_ms_synced": phases,
         "rank_phase_ms": spread(ranks, _lib.MULTI_PHASES + ("wait",)),
     }
+    if dumped:
+        line["dump_outputs"] = dumped
     if args.cpu_sample > 0:
         _b, sel, ref_out, ref_cnt = cpu_baseline(X, P_total, min(args.cpu_sample, 2000))
         line["check"] = check_against_oracle(out[sel], cnt[sel] if cnt is not None else None, ref_out, ref_cnt)
@@ -528,9 +559,18 @@ def main(argv=None):
                     help="roofline counters of the pair kernel: taken now by child rocprofv3 --pmc runs (N = 1; falls back "
                          "to the committed record of the same source), from the committed record only, or not at all")
     ap.add_argument("--save-pmc", action="store_true", help="write the live counters to profiles/k1_pmc_records.json")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the results of the last timed step to DIR/<perspective>_<field>.npy (float64, at most "
+                         "64 MB in all: a fixed, seeded sample of the pairs beyond that)")
     args = ap.parse_args(argv)
     if args.gpus < 1:
         raise SystemExit("--gpus must be >= 1")
+    if (args.steps is not None and args.steps < 1) or (args.warmup is not None and args.warmup < 0):
+        raise SystemExit("--steps must be >= 1 and --warmup >= 0")
+    if args.dump_outputs:
+        # the ranks of a self-launch run in ROOT: they get the directory as the caller meant it (the last one given wins)
+        args.dump_outputs = os.path.abspath(args.dump_outputs)
+        argv = argv + ["--dump-outputs", args.dump_outputs]
     # `python bench.py --gpus N` as typed: this process is the parent of the ranks (no torch, no GPU in it)
     if should_spawn(args.gpus, args.launcher, os.environ):
         return spawn_ranks(argv, args.gpus)
@@ -583,7 +623,7 @@ def main(argv=None):
     out_local = torch.full((n_each, 4), float("nan"), dtype=torch.float64, device=dev)
     out_second = torch.empty((n_each, 4), dtype=torch.float64, device=dev) if args.config == "c5" else None
     flags = _lib.FLAG_TIMING
-    gathered = None
+    gathered = gathered_second = None
     both = args.config == "c5"   # BASELINE config 5: perspective = "local" vs "global"
 
     # N > 1: each rank sorts only its S/N columns (K0); order, the bitsets and stats are all-gathered (RCCL over
@@ -612,7 +652,7 @@ def main(argv=None):
         return e
 
     def step(timed=False):
-        nonlocal gathered
+        nonlocal gathered, gathered_second
         evs = [mark()] if timed else None
         if sp is None:
             ctx.prepare_dev(dX.data_ptr(), n, S, n, flags)
@@ -631,7 +671,7 @@ def main(argv=None):
             # every rank's P/N x 4 results to rank 0 (RCCL over xGMI)
             gathered = sharding.gather_blocks(dist, out_local, n_each, dev, via_host, to_all=False)
             if both:
-                sharding.gather_blocks(dist, out_second, n_each, dev, via_host, to_all=False)
+                gathered_second = sharding.gather_blocks(dist, out_second, n_each, dev, via_host, to_all=False)
         if timed:
             evs.append(mark())                   # gather
             ev_pool.append(evs)
@@ -658,6 +698,18 @@ def main(argv=None):
         t = torch.tensor([elapsed], dtype=torch.float64, device="cpu" if via_host else dev)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
+    # --dump-outputs: the last timed step's results as the caller receives them, before the checks below reuse the context
+    dumped = None
+    if args.dump_outputs and rank == 0:
+        if distributed:
+            res = {"global": sharding.assemble(gathered, P_total, n_each)}
+            if both:
+                res["local"] = sharding.assemble(gathered_second, P_total, n_each)
+        else:
+            res = {"global": out_local[:P_local]}
+            if both:
+                res["local"] = out_second[:P_local]
+        dumped = dump_outputs(args.dump_outputs, {k: v.cpu().numpy() for k, v in res.items()})
     # this rank's phases, ms per step (the events are complete: fence() synchronised)
     my_phase = [sum(evs[i].elapsed_time(evs[i + 1]) for evs in ev_pool) / max(1, len(ev_pool)) for i in range(4)]
     rank_rows = [dict(zip(PHASES, my_phase))]
@@ -726,6 +778,8 @@ def main(argv=None):
             # rebuild launches of a step, not the all-gather between them)
             "kernel_ms_per_step": {k: v[0] / args.steps for k, v in k_ms.items()},
         }
+        if dumped:
+            line["dump_outputs"] = dumped
         if world == 1 and args.cpu_sample > 0:
             base, sel, ref_out, ref_cnt = cpu_baseline(X, P_total, args.cpu_sample)
             line["cpu_baseline"] = base

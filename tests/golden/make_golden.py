@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Regenerates tests/golden/*.npz and tests/golden/expected.json.
+"""Regenerates tests/golden/*.npz, tests/golden/yeast_rownames.txt and tests/golden/expected.json.
 
 Run in the BUILD container (needs /root/reference for the yeast data file only):
 
@@ -156,6 +156,9 @@ def main():
         Xy, rn, cn = yeast()
         assert Xy.shape == (6887, 96)
         np.savez_compressed(os.path.join(HERE, "yeast_missing.npz"), X=Xy, colnames=np.array(cn))
+        # the row names, one per line: tests/test_formats.py writes the matrix back in R's formats with its dimnames
+        with open(os.path.join(HERE, "yeast_rownames.txt"), "w") as f:
+            f.write("\n".join(rn) + "\n")
         expected["yeast"] = {"source": "data/yeast_missing.rda", "shape": [6887, 96], "n_zero": int((Xy == 0).sum())}
 
     with open(os.path.join(HERE, "expected.json"), "w") as f:

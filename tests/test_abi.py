@@ -18,6 +18,9 @@ def test_header_functions_are_exported():
     from icikendalltau_amd import _lib
     if _lib.needs_build():
         _lib.build()
+    # loaded as _lib.lib() loads it, after torch's HIP runtime: a first load of the bare library brings the ROCm
+    # installation's runtime in beside torch's, and torch then finds no device for the rest of the session
+    _lib.lib()
     L = ctypes.CDLL(_lib.LIB_PATH)
     names = _declared_functions()
     assert len(names) >= 18

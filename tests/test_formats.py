@@ -1,5 +1,8 @@
 """Input-side formats: R data files and the long data.frame converters."""
+import bz2
+import gzip
 import os
+import struct
 
 import numpy as np
 import pandas as pd
@@ -7,7 +10,7 @@ import pytest
 
 from icikendalltau_amd import formats
 
-REF = "/root/reference"
+GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
 
 
 def test_reshaping_round_trip():
@@ -31,14 +34,59 @@ def test_reshaping_round_trip():
         formats.long_df_2_cor_matrix(short.rename(columns={"cor": "raw"}))
 
 
-@pytest.mark.skipif(not os.path.isdir(REF), reason="reference data files are only in the build container")
-def test_read_reference_data_files():
-    X, rn, cn = formats.read_r_matrix(f"{REF}/data/yeast_missing.rda")
-    gold = np.load("tests/golden/yeast_missing.npz")
+# ---- R's XDR serialisation (R Internals, "Serialization Formats"), only what the reference's data files hold ----------
+def _i32(v):
+    return struct.pack(">i", v)
+
+
+def _charsxp(s):
+    b = s.encode()
+    return _i32(0x40009) + _i32(len(b)) + b            # CHARSXP flagged ASCII, as R writes names
+
+
+def _strsxp(v):
+    return _i32(16) + _i32(len(v)) + b"".join(_charsxp(s) for s in v)
+
+
+def _pairlist(items):
+    """Tagged pairlist of (name, serialised value), closed by NILVALUE_SXP."""
+    return b"".join(_i32(0x402) + _i32(1) + _charsxp(tag) + val for tag, val in items) + _i32(254)
+
+
+def _real_matrix(X, rownames=None, colnames=None):
+    attrs = [("dim", _i32(13) + _i32(2) + struct.pack(">ii", *X.shape))]
+    if rownames is not None:
+        attrs.append(("dimnames", _i32(19) + _i32(2) + _strsxp(rownames) + _strsxp(colnames)))
+    return _i32(0x20e) + _i32(X.size) + np.asarray(X, dtype=">f8").tobytes(order="F") + _pairlist(attrs)
+
+
+def _serialize(obj, version):
+    head = b"X\n" + _i32(version) + _i32(0x040300) + _i32(0x020300 if version == 2 else 0x030500)
+    return head + (_i32(5) + b"UTF-8" if version == 3 else b"") + obj
+
+
+def test_read_reference_data_files(tmp_path):
+    """The reference's data files as R wrote them, rebuilt from the committed yeast fixture: data/yeast_missing.rda
+    (RDX2, version 2, bzip2; a matrix with dimnames), large_test/yeast_data.rds (version 3, gzip; the same matrix) and
+    data/missing_dataset.rda (RDX3, version 3, gzip; a 1000 x 20 matrix with NA cells)."""
+    gold = np.load(os.path.join(GOLDEN, "yeast_missing.npz"))
+    with open(os.path.join(GOLDEN, "yeast_rownames.txt")) as f:
+        rownames = f.read().split()
+    yeast = _real_matrix(gold["X"], rownames, list(gold["colnames"]))
+    (tmp_path / "yeast_missing.rda").write_bytes(bz2.compress(b"RDX2\n" + _serialize(_pairlist([("yeast_missing", yeast)]), 2)))
+    (tmp_path / "yeast_data.rds").write_bytes(gzip.compress(_serialize(yeast, 3)))
+    M = np.random.default_rng(0).standard_normal((1000, 20))
+    na = np.random.default_rng(1).random(M.shape) < 0.1
+    M[na] = struct.unpack(">d", struct.pack(">Q", 0x7FF00000000007A2))[0]   # NA_real_
+    (tmp_path / "missing_dataset.rda").write_bytes(
+        gzip.compress(b"RDX3\n" + _serialize(_pairlist([("missing_dataset", _real_matrix(M))]), 3)))
+
+    X, rn, cn = formats.read_r_matrix(str(tmp_path / "yeast_missing.rda"))
     assert X.shape == (6887, 96) and np.array_equal(X, gold["X"]) and list(cn) == list(gold["colnames"])
-    assert rn[0] == "15S_rRNA"
-    Y, _, cn2 = formats.read_r_matrix(f"{REF}/large_test/yeast_data.rds")
+    assert rn[0] == "15S_rRNA" and list(rn) == rownames
+    Y, _, cn2 = formats.read_r_matrix(str(tmp_path / "yeast_data.rds"))
     assert Y.shape == (6887, 96) and np.array_equal(Y, X)
-    objs = formats.read_r_data(f"{REF}/data/missing_dataset.rda")
+    objs = formats.read_r_data(str(tmp_path / "missing_dataset.rda"))
     (name, obj), = objs.items()
     assert obj["data"].shape == (1000, 20)
+    assert name == "missing_dataset" and np.array_equal(np.isnan(obj["data"]), na)

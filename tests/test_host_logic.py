@@ -1,6 +1,7 @@
 """Host-side mirror of the reference's R front-end (R/kendalltau.R:96-308,357-421,563-629), exercised on
 the CPU with the checker engine (tests/oracle_engine.py).  Expected values are the reference's own test
 assertions and README output (tests/golden/expected.json)."""
+import os
 import warnings
 
 import numpy as np
@@ -10,6 +11,8 @@ import pytest
 from icikendalltau_amd import api
 from tests.oracle_engine import OracleEngine
 
+GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
+
 ENG = OracleEngine()
 
 
@@ -18,7 +21,7 @@ def _names(n):
 
 
 def test_readme_matrix_and_dataframe_outputs(expected):
-    z = np.load("tests/golden/readme_s1_s4.npz")
+    z = np.load(os.path.join(GOLDEN, "readme_s1_s4.npz"))
     e = expected["readme"]
     r1 = api.ici_kendalltau(np.c_[z["s1"], z["s2"]], colnames=["s1", "s2"], engine=ENG)
     assert list(r1.keys()) == ["cor", "raw", "pvalue", "taumax", "completeness", "keep", "run_time"]
@@ -53,7 +56,7 @@ def test_matrix_equals_single_pair():
 
 def test_include_only_semantics(expected):
     # test-kendall-tau.R:102-136
-    X = np.load("tests/golden/include_only_50x100.npz")["X"]
+    X = np.load(os.path.join(GOLDEN, "include_only_50x100.npz"))["X"]
     names = _names(100)
     z = expected["include_only"]["zeros"]
     r = api.ici_kendalltau(X, include_only="s1", colnames=names, engine=ENG)
@@ -77,7 +80,7 @@ def test_include_only_semantics(expected):
 
 def test_completeness_matches_pairwise_completeness(expected):
     # test-kendall-tau.R:138-151
-    X = np.load("tests/golden/completeness_50x100.npz")["X"]
+    X = np.load(os.path.join(GOLDEN, "completeness_50x100.npz"))["X"]
     names = _names(100)
     xc = api.ici_kendalltau(X, perspective="global", return_matrix=False, colnames=names, engine=ENG)["cor"]
     comp = api.pairwise_completeness(X, return_matrix=False, colnames=names, engine=ENG)
@@ -213,7 +216,7 @@ def _sig7(v):
 
 def test_kt_fast_snapshots(expected):
     # tests/testthat/test-kendall-tau.R:153-205 and _snaps/kendall-tau.md:19-88
-    X = np.load("tests/golden/ktfast_100x4.npz")["X"]
+    X = np.load(os.path.join(GOLDEN, "ktfast_100x4.npz"))["X"]
     names = _names(4)
     e = expected["ktfast"]
     from scipy import stats

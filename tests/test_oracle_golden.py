@@ -4,12 +4,16 @@ This is what pins the oracle (and therefore every GPU parity claim) to the refer
 tests/testthat/test-kendall-tau.R, tests/testthat/_snaps/kendall-tau.md, README.md, all reproduced
 without R through the RNG emulation in oracle/rrng.py (inputs committed under tests/golden/).
 """
+import os
+
 import numpy as np
 import pytest
 from scipy import stats
 
 from oracle import oracle as O
 from oracle.rrng import RRandom
+
+GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
 
 
 def test_rrng_matches_r():
@@ -18,7 +22,7 @@ def test_rrng_matches_r():
     assert np.allclose(r.rnorm(5), [-1.2070657, 0.2774292, 1.0844412, -2.3456977, 0.4291247], atol=5e-8)
     # golden arrays are what the emulation produces
     r = RRandom(1234)
-    z = np.load("tests/golden/snapshot_50000.npz")
+    z = np.load(os.path.join(GOLDEN, "snapshot_50000.npz"))
     assert np.array_equal(r.rnorm(50000), z["x"]) and np.array_equal(r.rnorm(50000), z["y"])
 
 
@@ -63,7 +67,7 @@ def test_na_and_error_contract():
 
 
 def test_snapshot_50000(expected):
-    z = np.load("tests/golden/snapshot_50000.npz")
+    z = np.load(os.path.join(GOLDEN, "snapshot_50000.npz"))
     out, cnt, rsn = O.ici_kt(z["x"], z["y"], "global")
     e = expected["snapshot_50000"]
     assert round(out[0], 8) == e["tau"] and round(out[1], 8) == e["pvalue"]
@@ -71,7 +75,7 @@ def test_snapshot_50000(expected):
 
 
 def test_readme_example(expected):
-    z = np.load("tests/golden/readme_s1_s4.npz")
+    z = np.load(os.path.join(GOLDEN, "readme_s1_s4.npz"))
     e = expected["readme"]["r_4"]
     out, cnt, rsn = O.ici_kt(z["s3"], z["s4"], "global")
     assert round(out[0], 7) == e["raw"] and round(out[2], 6) == e["taumax"] and out[3] == pytest.approx(e["completeness"])
@@ -83,7 +87,7 @@ def test_readme_example(expected):
 
 def test_ktfast_snapshots(expected):
     # kt_fast(use = "complete.obs" / "pairwise.complete.obs") reduce to ici_kt on NA-free rows
-    X = np.load("tests/golden/ktfast_100x4.npz")["X"]
+    X = np.load(os.path.join(GOLDEN, "ktfast_100x4.npz"))["X"]
     e = expected["ktfast"]
     keep = np.ones(100, bool)
     keep[e["complete_obs_drop_row"] - 1] = False
@@ -106,7 +110,7 @@ def test_ktfast_snapshots(expected):
 
 
 def test_completeness_snapshot(expected):
-    X = np.load("tests/golden/completeness_50x100.npz")["X"]
+    X = np.load(os.path.join(GOLDEN, "completeness_50x100.npz"))["X"]
     assert np.isnan(X).sum() == 40
     for row in expected["completeness"]["rows_4_6"]:
         i, j = int(row["s1"][1:]) - 1, int(row["s2"][1:]) - 1
