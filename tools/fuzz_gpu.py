@@ -5,12 +5,15 @@ levels, blocks of equal values, constants), a missingness pattern (random, left-
 a K1 launch plan override (pairs per wave, pend placement, half-wave step, joint-tie mode), then compares
 counts bit-exactly and the four doubles within 1e-10 for both perspectives.
 
-    python tools/fuzz_gpu.py [cases] [seed] [big|mid|ext|r4|fam]
+    python tools/fuzz_gpu.py [cases] [seed] [big|mid|ext|r4|fam|wide]
 
 `mid`: 16 000 .. 31 000 rows (both kernel families of 18 337 .. 30 656 rows, the windows of the tie program) with
 two more value models: many small tie groups (n / 2 .. n / 40 distinct values) and a tied region beside a
 continuous one.  `ext`: the default lengths with those two models.  `fam`: 15 200 .. 31 000 rows x 48 columns (a task list
 that fills the chip: the library chooses the kernel family from the columns' tie structure), half of the matrices continuous.
+`wide`: 65 .. 200 columns, one value model before a random split column and another after it, so that the columns the
+library plans from (the first 64, or the first upload chunk) misrepresent the rest; the library's own plan, the oracle on a
+seeded subset of the pairs.
 """
 import os
 import sys
@@ -27,12 +30,14 @@ BIG = False  # set by main(): argv[3] == 'big'
 MID = False  # set by main(): argv[3] == 'mid'
 EXT = False  # set by main(): argv[3] == 'ext' (the default lengths with the two extra value models)
 FAM = False  # set by main(): argv[3] == 'fam'
+WIDE = False  # set by main(): argv[3] == 'wide'
 R4 = False   # set by main(): argv[3] == 'r4': `ext` + values that collide in the pre-pass's one-word sort (its second pass)
              # + the pre-pass shape (plan key k0) drawn at random
 
 
-def make_column(rng, n):
-    kind = rng.integers(0, 12 if R4 else 10 if (MID or EXT) else 8)
+def make_column(rng, n, kind=None):
+    if kind is None:
+        kind = rng.integers(0, 12 if R4 else 10 if (MID or EXT) else 8)
     if kind >= 10:  # values that share the top 48 bits of their sortable keys: distinct low bits, ties among them, either sign
         base = float(rng.choice([1.0, -3.0, 1e-300, 7.5e200]))
         k = rng.integers(0, int(rng.choice([3, 50, 60000])), n)
@@ -80,6 +85,8 @@ def make_column(rng, n):
 
 
 def one_case(ctx, rng, case):
+    if WIDE:
+        return wide_case(ctx, rng, case)
     r = rng.random()
     if FAM:
         n = int(rng.integers(15200, 18337)) if rng.random() < 0.7 else int(rng.integers(18337, 31000))
@@ -157,10 +164,50 @@ def one_case(ctx, rng, case):
     return "ok", desc
 
 
+def wide_case(ctx, rng, case):
+    """`wide`: S = 65 .. 200 columns of n = 2 000 .. 60 000 rows, value model A up to a random split column, B after it."""
+    n = int(rng.integers(2000, 60000)) if rng.random() < 0.3 else int(rng.integers(14000, 31000))
+    S = int(rng.integers(65, 201))
+    split = int(rng.integers(1, S))
+    ka, kb = (int(k) for k in rng.integers(0, 10, 2))
+    X = np.asfortranarray(np.stack([make_column(rng, n, ka if c < split else kb) for c in range(S)], axis=1))
+    ctx.debug_set_plan(None)
+    flags = int(rng.random() < 0.25)
+    persp = rng.choice(["global", "local"])
+    desc = f"case {case}: wide n={n} S={S} split={split} models={ka}/{kb} {persp} flags={flags}"
+    out, cnt, rsn = ctx.pairs(X, None, None, persp, "two.sided", False, flags)
+    iu, ju = np.triu_indices(S, k=1)
+    # the oracle on a seeded subset: pairs at random, and pairs across the split
+    sel = rng.choice(len(iu), 40, replace=False)
+    a = rng.integers(0, split, 8)
+    b = rng.integers(split, S, 8)
+    pi = np.concatenate([iu[sel], a]).astype(np.int64)
+    pj = np.concatenate([ju[sel], b]).astype(np.int64)
+    idx = pi * (2 * S - pi - 1) // 2 + (pj - pi - 1)
+    ref, rcnt, rrsn = O.ici_pairs(X, pi.astype(np.int32), pj.astype(np.int32), persp, int32_compat=not (flags & 1))
+    out, cnt, rsn = out[idx], cnt[idx], rsn[idx]
+    ok = rrsn == 0
+    bad = None
+    if not np.array_equal(rsn, rrsn):
+        bad = f"reasons {rsn} vs {rrsn}"
+    elif not np.array_equal(cnt[ok], rcnt[ok][:, :cnt.shape[1]]):
+        w = np.argwhere(cnt[ok] != rcnt[ok][:, :cnt.shape[1]])[0]
+        bad = f"counts differ at pair ({pi[ok][w[0]]}, {pj[ok][w[0]]}) field {w[1]}: {cnt[ok][w[0]]} vs {rcnt[ok][w[0]]}"
+    elif not np.array_equal(np.isnan(out), np.isnan(ref)):
+        bad = "NaN pattern"
+    elif np.any(~np.isnan(ref)) and np.nanmax(np.abs(out - ref)) > ATOL:
+        bad = f"max abs diff {np.nanmax(np.abs(out - ref))}"
+    if bad:
+        np.save(f"fuzz_wide_fail_{case}.npy", X)   # (in the working directory: the test runs each sweep in a temporary one)
+        return "FAIL", desc + " -> " + bad + f" (input saved as fuzz_wide_fail_{case}.npy)"
+    return "ok", desc
+
+
 def main():
     cases = int(sys.argv[1]) if len(sys.argv) > 1 else 300
     seed = int(sys.argv[2]) if len(sys.argv) > 2 else 1
-    global BIG, MID, EXT, R4, FAM
+    global BIG, MID, EXT, R4, FAM, WIDE
+    WIDE = len(sys.argv) > 3 and sys.argv[3] == "wide"
     FAM = len(sys.argv) > 3 and sys.argv[3] == "fam"
     R4 = len(sys.argv) > 3 and sys.argv[3] == "r4"
     BIG = len(sys.argv) > 3 and sys.argv[3] == "big"
