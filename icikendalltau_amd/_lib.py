@@ -14,9 +14,10 @@ import numpy as np
 _PKG = os.path.dirname(os.path.abspath(__file__))
 _ROOT = os.path.dirname(_PKG)
 LIB_PATH = os.environ.get("ICIKT_LIB") or os.path.join(_PKG, "libicikt_hip.so")  # ICIKT_LIB: A/B of builds (tools)
-SOURCES = [os.path.join(_PKG, "csrc", f) for f in ("icikt_kernels.hip", "icikt_capi.cpp", "icikt_multi.cpp")]
+SOURCES = [os.path.join(_PKG, "csrc", f) for f in ("icikt_kernels.hip", "icikt_capi.cpp", "icikt_multi.cpp",
+                                                       "icikt_transfer.cpp")]
 HEADERS = [os.path.join(_ROOT, "include", "icikt.h"), os.path.join(_PKG, "csrc", "icikt_device.h"),
-           os.path.join(_PKG, "csrc", "icikt_host.h")]
+           os.path.join(_PKG, "csrc", "icikt_host.h"), os.path.join(_PKG, "csrc", "icikt_transfer.h")]
 
 # include/icikt.h
 SUCCESS = 0

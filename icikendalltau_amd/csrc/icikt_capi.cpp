@@ -11,10 +11,6 @@
 #include <cstring>
 #include <functional>
 #include <new>
-#include <atomic>
-#include <mutex>
-#include <condition_variable>
-#include <thread>
 #include <string>
 #include <vector>
 
@@ -508,25 +504,15 @@ int icikt_ctx_create(int device, icikt_ctx** out) {
     return ICIKT_E_HIP;
   }
   c->stream = c->own_stream;
-  if (hipStreamCreateWithFlags(&c->copy_stream, hipStreamNonBlocking) != hipSuccess) {
+  // the pre-pass of a chunk must not queue behind the pair kernel of the chunks before it for longer than that
+  // kernel's workgroups take to retire: the highest priority the device offers
+  int lo_prio = 0, hi_prio = 0;
+  if (hipDeviceGetStreamPriorityRange(&lo_prio, &hi_prio) != hipSuccess) { (void)hipGetLastError(); hi_prio = 0; }
+  if (hipStreamCreateWithFlags(&c->copy_stream, hipStreamNonBlocking) != hipSuccess ||
+      hipStreamCreateWithPriority(&c->prep_stream, hipStreamNonBlocking, hi_prio) != hipSuccess || c->xfer.init() != hipSuccess) {
     icikt_ctx_destroy(c);
     return ICIKT_E_HIP;
   }
-  {
-    // the pre-pass of a chunk must not queue behind the pair kernel of the chunks before it for longer than that
-    // kernel's workgroups take to retire: the highest priority the device offers
-    int lo_prio = 0, hi_prio = 0;
-    if (hipDeviceGetStreamPriorityRange(&lo_prio, &hi_prio) != hipSuccess) { (void)hipGetLastError(); hi_prio = 0; }
-    if (hipStreamCreateWithPriority(&c->prep_stream, hipStreamNonBlocking, hi_prio) != hipSuccess) {
-      icikt_ctx_destroy(c);
-      return ICIKT_E_HIP;
-    }
-  }
-  for (auto& e : c->ev_copy)
-    if (hipEventCreateWithFlags(&e, hipEventDisableTiming) != hipSuccess) {
-      icikt_ctx_destroy(c);
-      return ICIKT_E_HIP;
-    }
   *out = c;
   return ICIKT_SUCCESS;
 }
@@ -536,32 +522,17 @@ void icikt_ctx_destroy(icikt_ctx* c) {
   (void)hipSetDevice(c->device);
   (void)hipStreamSynchronize(c->stream);
   if (c->copy_stream) (void)hipStreamSynchronize(c->copy_stream);
-  c->order.release(); c->hirow.release(); c->girow.release(); c->rec.release(); c->meta.release();
-  c->tgroups.release(); c->tprog.release(); c->smask.release(); c->srow.release(); c->sort_keys.release(); c->sort_idx.release(); c->wide32.release(); c->order_w.release(); c->k0_bits.release();
-  c->d_pi.release(); c->d_pj.release(); c->d_unit_start.release(); c->d_raw.release();
-  c->d_task_ctr.release();
-  c->d_X.release(); c->d_Xp.release(); c->d_out4.release(); c->d_counts.release(); c->d_reasons.release(); c->d_self.release();
-  c->d_out5.release(); c->d_keep.release(); c->d_red.release(); c->d_pi_all.release(); c->d_pj_all.release();
   for (int k = 0; k < ICIKT_K_COUNT; ++k)
     for (auto& p : c->ev_pool[k]) {
       if (p.a) (void)hipEventDestroy(p.a);
       if (p.b) (void)hipEventDestroy(p.b);
     }
-  for (auto& e : c->ev_copy)
-    if (e) (void)hipEventDestroy(e);
-  if (c->pinned) (void)hipHostFree(c->pinned);
-  if (c->pinned_tasks) (void)hipHostFree(c->pinned_tasks);
-  for (auto& ps : c->out_pinned)
-    if (ps.p) (void)hipHostFree(ps.p);
-  if (c->copy_pool) { icikt::host::destroy_copy_pool(c->copy_pool); c->copy_pool = nullptr; }
   for (auto& e : c->ev_chunk)
-    if (e) (void)hipEventDestroy(e);
-  for (auto& e : c->ev_out)
     if (e) (void)hipEventDestroy(e);
   if (c->prep_stream) { (void)hipStreamSynchronize(c->prep_stream); (void)hipStreamDestroy(c->prep_stream); }
   if (c->copy_stream) (void)hipStreamDestroy(c->copy_stream);
   if (c->own_stream) (void)hipStreamDestroy(c->own_stream);
-  delete c;
+  delete c;   // (the device buffers, and the transfers' pinned buffers, threads and events, go with it)
 }
 
 const char* icikt_last_error(const icikt_ctx* c) { return c ? c->err.c_str() : "null context"; }
@@ -788,7 +759,7 @@ int icikt_prepare_cols_f64(icikt_ctx* c, const double* X, int64_t n_feat, int64_
   if (rc) return rc;
   rc = prepare_alloc(c, n_feat, n_samp, alloc_cols, col_end - col_begin);
   if (rc) return rc;
-  const icikt::host::PinnedScope pinned_scope(c, flags);
+  const icikt::host::PinnedScope scope(c, flags);
   rc = icikt::host::upload_and_prepare(c, X, n_feat, n_samp, ld, col_begin, col_end, flags);
   if (rc) return rc;
   c->prepared = true;
@@ -979,125 +950,9 @@ int icikt_reset_timers(icikt_ctx* c) {
 namespace icikt {
 namespace host {
 
-// Host-side copies into / out of the library's pinned buffers, on a few threads: one core moves ~10 GB/s, the c4
-// matrix is 82 MB and PCIe takes it in 1.8 ms.  The threads belong to the context (started on first use, parked on a
-// condition variable between copies: creating and joining seven threads per chunk cost ~0.2 ms a time, a millisecond of
-// a c4 call); a copy is cut into parts that the workers and the calling thread take from a shared counter.
-struct CopyPool {
-  std::vector<std::thread> th;
-  std::mutex m;
-  std::condition_variable cv_work, cv_done;
-  const std::function<void(unsigned)>* job = nullptr;
-  unsigned nparts = 0, done = 0;
-  std::atomic<unsigned> next{0};
-  unsigned long long gen = 0;
-  bool stop = false;
-  unsigned active = 0;   // workers that hold the current job (a copy is over when all parts are done AND nobody holds it)
-  void worker() {
-    unsigned long long seen = 0;
-    for (;;) {
-      const std::function<void(unsigned)>* f;
-      unsigned n;
-      {
-        std::unique_lock<std::mutex> lk(m);
-        cv_work.wait(lk, [&] { return stop || gen != seen; });
-        if (stop) return;
-        seen = gen; f = job; n = nparts;
-        if (!f) continue;          // woke after the copy was over
-        ++active;
-      }
-      unsigned mine = 0;
-      for (unsigned i = next.fetch_add(1); i < n; i = next.fetch_add(1)) { (*f)(i); ++mine; }
-      {
-        std::lock_guard<std::mutex> lk(m);
-        done += mine;
-        --active;
-        if (done == nparts && active == 0) cv_done.notify_one();
-      }
-    }
-  }
-  bool start(unsigned n) {
-    try {
-      while (th.size() < n) th.emplace_back(&CopyPool::worker, this);
-    } catch (...) {}
-    return !th.empty();
-  }
-  void run(unsigned n, const std::function<void(unsigned)>& f) {
-    {
-      std::lock_guard<std::mutex> lk(m);
-      job = &f; nparts = n; done = 0; next.store(0); ++gen;
-    }
-    cv_work.notify_all();
-    unsigned mine = 0;
-    for (unsigned i = next.fetch_add(1); i < n; i = next.fetch_add(1)) { f(i); ++mine; }
-    std::unique_lock<std::mutex> lk(m);
-    done += mine;
-    cv_done.wait(lk, [&] { return done == nparts && active == 0; });
-    job = nullptr;
-  }
-  ~CopyPool() {
-    { std::lock_guard<std::mutex> lk(m); stop = true; }
-    cv_work.notify_all();
-    for (auto& t : th) t.join();
-  }
-};
-void destroy_copy_pool(void* p) { delete static_cast<CopyPool*>(p); }
-
-// `rows` pieces of `row_bytes`, strides in bytes (a contiguous copy: one row)
-static void par_copy2d(icikt_ctx* c, void* dst, size_t dst_stride, const void* src, size_t src_stride, size_t row_bytes, size_t rows) {
-  const size_t total = row_bytes * rows;
-  unsigned nt = (unsigned)std::min<size_t>(8, total / ((size_t)1 << 20));   // (12 threads measured slower than 8 on the pool's boxes)
-  CopyPool* pool = nullptr;
-  if (nt > 1) {
-    if (!c->copy_pool) { try { c->copy_pool = new CopyPool(); } catch (...) { c->copy_pool = nullptr; } }
-    pool = static_cast<CopyPool*>(c->copy_pool);
-    if (!pool || !pool->start(7)) pool = nullptr;
-  }
-  if (!pool) {   // small, or no threads to be had: one core does it all
-    for (size_t r = 0; r < rows; ++r)
-      memcpy(static_cast<char*>(dst) + r * dst_stride, static_cast<const char*>(src) + r * src_stride, row_bytes);
-    return;
-  }
-  if (rows == 1) {   // a contiguous copy: pieces of ~1 MB
-    const size_t piece = (size_t)1 << 20;
-    const unsigned parts = (unsigned)((total + piece - 1) / piece);
-    const std::function<void(unsigned)> f = [=](unsigned i) {
-      const size_t off = (size_t)i * piece;
-      memcpy(static_cast<char*>(dst) + off, static_cast<const char*>(src) + off, std::min(piece, total - off));
-    };
-    pool->run(parts, f);
-    return;
-  }
-  const size_t per = std::max<size_t>(1, ((size_t)1 << 20) / std::max<size_t>(row_bytes, 1));   // rows per part: ~1 MB
-  const unsigned parts = (unsigned)((rows + per - 1) / per);
-  const std::function<void(unsigned)> f = [=](unsigned i) {
-    const size_t r0 = (size_t)i * per, r1 = std::min(rows, r0 + per);
-    for (size_t r = r0; r < r1; ++r)
-      memcpy(static_cast<char*>(dst) + r * dst_stride, static_cast<const char*>(src) + r * src_stride, row_bytes);
-  };
-  pool->run(parts, f);
-}
-static void par_memcpy(icikt_ctx* c, void* dst, const void* src, size_t bytes) { par_copy2d(c, dst, 0, src, 0, bytes, 1); }
-
-int ensure_bounce(icikt_ctx* c, size_t need) {
-  if (c->pinned_bytes >= need) return ICIKT_SUCCESS;
-  if (c->pinned) (void)hipHostFree(c->pinned);
-  c->pinned = nullptr;
-  c->pinned_bytes = 0;
-  // (write-combined memory was tried for this buffer, which the host only ever writes: no difference, round 4)
-  HIPCHK(c, hipHostMalloc(&c->pinned, need, hipHostMallocDefault));
-  c->pinned_bytes = need;
-  return ICIKT_SUCCESS;
-}
-
 // H2D of columns [col_begin, col_end) + K0 over them.  The copies run on the context's copy stream in column
 // chunks and K0 of a chunk waits only for its own chunk (an event per chunk), so the pre-pass of chunk i runs
-// while chunk i + 1 crosses PCIe.  How the caller's matrix is read:
-//   staged (default)  through the library's pinned double buffer (a threaded host memcpy per chunk): the GPU never
-//                     touches the caller's pages, and the library never page-locks them
-//   pinned            ICIKT_FLAG_HOST_PINNED on the call: the caller has page-locked the matrix itself; the copies are
-//                     DMA straight out of it
-//   small             matrices below kLockMin bytes take the runtime's own staging path
+// while chunk i + 1 crosses PCIe.  How the caller's matrix is read: MatrixUpload (icikt_transfer.h).
 // prepass: kPrepassFull = K0; kPrepassMask = missing-row bitsets only (pairwise_completeness); kPrepassNone = the
 // columns are only copied (icikt_pairs_complete_f64 sorts masked copies, not the columns).
 int upload_and_prepare(icikt_ctx* c, const double* X, int64_t n_feat, int64_t n_samp, int64_t ld, int64_t col_begin,
@@ -1125,34 +980,15 @@ int upload_and_prepare(icikt_ctx* c, const double* X, int64_t n_feat, int64_t n_
     // 1.4 ms after the last copy, four chunks of 256 right behind it)
     if (pipelined) chunk = std::max<int64_t>(chunk, std::min<int64_t>(c->prop.multiProcessorCount, (n_samp / 4) & ~(int64_t)1));
     if (prepass == kPrepassFull) chunk = std::min<int64_t>(chunk, std::max(1, c->sort_chunk));
-    const double* src0 = X + col_begin * ld;
     const size_t span = ((size_t)(ncols - 1) * (size_t)ld + (size_t)n_feat) * sizeof(double);
-    const int mode = (span < kLockMin) ? 0 : (c->host_pinned ? 3 : 2);
-    if (mode == 2) {
-      rc = ensure_bounce(c, 2 * (size_t)chunk * col_bytes);
-      if (rc) return rc;
-    }
-    // the copy stream must not overwrite d_X while earlier work on the compute stream still reads it
-    hipError_t e = hipEventRecord(c->ev_copy[0], c->stream);
-    if (e == hipSuccess) e = hipStreamWaitEvent(c->copy_stream, c->ev_copy[0], 0);
-    if (e == hipSuccess && pipelined) e = hipStreamWaitEvent(c->prep_stream, c->ev_copy[0], 0);
+    MatrixUpload up{c, col_bytes, (size_t)ld * sizeof(double), (size_t)chunk * col_bytes};
+    hipError_t e = up.begin(span, pipelined ? c->prep_stream : nullptr);
     int k = 0;
     const int64_t first_chunk = chunk;   // (a short first chunk was measured twice: no gain -- what the last pair-kernel launch waits for is the last chunk's pre-pass, which finds no free CU until the launch before it drains)
     for (int64_t c0 = col_begin, step = first_chunk; c0 < col_end && e == hipSuccess && rc == 0; c0 += step, step = chunk, ++k) {
       const int64_t nc = std::min<int64_t>(step, col_end - c0);
-      double* dst = c->d_X.p + (size_t)c0 * (size_t)n_feat;
-      hipEvent_t ev = c->ev_copy[1 + (k % 3)];
-      if (mode == 2) {
-        char* stage = static_cast<char*>(c->pinned) + (size_t)(k & 1) * (size_t)chunk * col_bytes;
-        if (k >= 2) e = hipEventSynchronize(c->ev_copy[1 + ((k - 2) % 3)]);  // the copy that last used this half
-        if (e != hipSuccess) break;
-        par_copy2d(c, stage, col_bytes, X + c0 * ld, (size_t)ld * sizeof(double), col_bytes, (size_t)nc);
-        e = hipMemcpyAsync(dst, stage, (size_t)nc * col_bytes, hipMemcpyHostToDevice, c->copy_stream);
-      } else {
-        e = hipMemcpy2DAsync(dst, col_bytes, X + c0 * ld, (size_t)ld * sizeof(double), col_bytes, (size_t)nc,
-                             hipMemcpyHostToDevice, c->copy_stream);
-      }
-      if (e == hipSuccess) e = hipEventRecord(ev, c->copy_stream);
+      hipEvent_t ev = nullptr;
+      e = up.copy(k, c->d_X.p + (size_t)c0 * (size_t)n_feat, X + c0 * ld, nc, &ev);
       if (pipelined) {
         // the chunk's pre-pass on the pre-pass stream; an event of its own tells the pair kernel's stream when
         if (e == hipSuccess) e = hipStreamWaitEvent(c->prep_stream, ev, 0);
@@ -1181,9 +1017,9 @@ int upload_and_prepare(icikt_ctx* c, const double* X, int64_t n_feat, int64_t n_
     if (pipelined && (e != hipSuccess || rc)) (void)hipStreamSynchronize(c->prep_stream);
     // The staging buffer serves the later transfers of the call as their bounce buffer, so its last copy is waited for
     // here.  A matrix the caller has page-locked is read in place: the pipelined callers go on with host work (the task
-    // list) and wait for the copy stream themselves before they return (finish_upload) -- no entry point returns while
+    // list) and wait for the copy stream themselves before they return (end_call) -- no entry point returns while
     // a copy still reads the caller's memory.
-    if (!(pipelined && mode == 3) || e != hipSuccess || rc) (void)hipStreamSynchronize(c->copy_stream);
+    if (!(pipelined && up.in_place) || e != hipSuccess || rc) (void)hipStreamSynchronize(c->copy_stream);
     if (e != hipSuccess) return fail(c, ICIKT_E_HIP, std::string("H2D of the matrix: ") + hipGetErrorString(e));
     if (rc) return rc;
   } else if (ncols > 0 && prepass == kPrepassFull) {
@@ -1245,13 +1081,9 @@ int upload_prepare_pairs(icikt_ctx* c, const double* X, int64_t n_feat, int64_t 
     auto pidx = [S](int64_t i, int64_t j) { return (int32_t)(i * (2 * S - i - 1) / 2 + (j - i - 1)); };
     const size_t cap_tasks = (size_t)c->n_pairs + (size_t)S + 8;
     HIPCHK(c, c->d_unit_start.reserve(cap_tasks * 2));
-    if (c->pinned_tasks_bytes < cap_tasks * 2 * sizeof(int32_t)) {
-      if (c->pinned_tasks) (void)hipHostFree(c->pinned_tasks);
-      c->pinned_tasks = nullptr; c->pinned_tasks_bytes = 0;
-      HIPCHK(c, hipHostMalloc(&c->pinned_tasks, cap_tasks * 2 * sizeof(int32_t), hipHostMallocDefault));
-      c->pinned_tasks_bytes = cap_tasks * 2 * sizeof(int32_t);
-    }
-    int32_t* u = static_cast<int32_t*>(c->pinned_tasks);
+    int32_t* u = nullptr;
+    rc = task_staging(c, cap_tasks * 2, &u);
+    if (rc) return rc;
     size_t nt = 0;
     int64_t cb = 0;
     const std::function<int(size_t, int64_t)> on_chunk = [&](size_t q, int64_t ce) -> int {
@@ -1370,85 +1202,6 @@ int upload_prepare_pairs(icikt_ctx* c, const double* X, int64_t n_feat, int64_t 
   return ICIKT_SUCCESS;
 }
 
-int upload_sync(icikt_ctx* c, void* dst, const void* src, size_t bytes) {
-  if (bytes == 0) return ICIKT_SUCCESS;
-  if (bytes >= kLockMin) {
-    // through the library's pinned bounce buffer, a chunk at a time (pair and task lists: the library's own vectors
-    // or the caller's index arrays -- ICIKT_FLAG_HOST_PINNED speaks of the matrix and the result arrays only)
-    const size_t cap = (size_t)8 << 20;
-    int rc = ensure_bounce(c, std::min(bytes, cap));
-    if (rc) return rc;
-    for (size_t off = 0; off < bytes; off += cap) {
-      const size_t m = std::min(cap, bytes - off);
-      par_memcpy(c, c->pinned, static_cast<const char*>(src) + off, m);
-      hipError_t e = hipMemcpyAsync(static_cast<char*>(dst) + off, c->pinned, m, hipMemcpyHostToDevice, c->stream);
-      const hipError_t es = hipStreamSynchronize(c->stream);
-      if (e == hipSuccess) e = es;
-      if (e != hipSuccess) return fail(c, ICIKT_E_HIP, std::string("H2D copy (staged): ") + hipGetErrorString(e));
-    }
-    return ICIKT_SUCCESS;
-  }
-  hipError_t e = hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, c->stream);
-  const hipError_t es = hipStreamSynchronize(c->stream);       // the host range must outlive the copy
-  if (e == hipSuccess) e = es;
-  if (e != hipSuccess) return fail(c, ICIKT_E_HIP, std::string("H2D copy: ") + hipGetErrorString(e));
-  return ICIKT_SUCCESS;
-}
-
-int download(icikt_ctx* c, void* dst, const void* src, size_t bytes) {
-  if (bytes == 0) return ICIKT_SUCCESS;
-  if (bytes >= kLockMin && !c->host_pinned) {
-    // into a pinned buffer of the library's (kept from call to call: slot = position among the call's downloads);
-    // finish_downloads() moves it to the caller's array
-    const size_t slot = c->bounced_out.size();
-    if (slot >= c->out_pinned.size()) c->out_pinned.resize(slot + 1);
-    auto& ps = c->out_pinned[slot];
-    if (ps.bytes < bytes) {
-      if (ps.p) (void)hipHostFree(ps.p);
-      ps.p = nullptr; ps.bytes = 0;
-      HIPCHK(c, hipHostMalloc(&ps.p, bytes, hipHostMallocDefault));
-      ps.bytes = bytes;
-    }
-    // in pieces, an event behind each: finish_stream() moves a piece to the caller's array while the next ones are
-    // still on their way (c4: 19 MB of results, 0.4 ms of PCIe and 0.25 ms of host copy that used to run one after the other)
-    const size_t piece = std::max<size_t>((size_t)4 << 20, (bytes + 3) / 4);
-    for (size_t off = 0; off < bytes; off += piece) {
-      const size_t m = std::min(piece, bytes - off);
-      HIPCHK(c, hipMemcpyAsync(static_cast<char*>(ps.p) + off, static_cast<const char*>(src) + off, m, hipMemcpyDeviceToHost, c->stream));
-      hipEvent_t ev = nullptr;
-      if (c->ev_out_used < c->ev_out.size()) ev = c->ev_out[c->ev_out_used];
-      else if (hipEventCreateWithFlags(&ev, hipEventDisableTiming) == hipSuccess) c->ev_out.push_back(ev);
-      else { (void)hipGetLastError(); ev = nullptr; }
-      if (ev) { c->ev_out_used += 1; HIPCHK(c, hipEventRecord(ev, c->stream)); }
-      c->bounced_out.push_back(icikt_ctx::Bounce{static_cast<char*>(ps.p) + off, static_cast<char*>(dst) + off, m, ev});
-    }
-    return ICIKT_SUCCESS;
-  }
-  HIPCHK(c, hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, c->stream));
-  return ICIKT_SUCCESS;
-}
-
-// (the stream has been synchronised; `ok` = it ended without an error, i.e. the bounced bytes are the results)
-void finish_downloads(icikt_ctx* c, bool ok) {
-  for (auto& b : c->bounced_out)
-    if (ok) par_memcpy(c, b.dst, b.pinned, b.bytes);
-  c->bounced_out.clear();
-  c->ev_out_used = 0;
-}
-
-hipError_t finish_stream(icikt_ctx* c, bool ok) {
-  for (auto& b : c->bounced_out) {
-    if (!ok) break;
-    // (a piece without an event -- none could be created -- waits for everything enqueued so far)
-    const hipError_t e = b.ev ? hipEventSynchronize(b.ev) : hipStreamSynchronize(c->stream);
-    if (e != hipSuccess) { (void)hipGetLastError(); ok = false; break; }
-    par_memcpy(c, b.dst, b.pinned, b.bytes);
-  }
-  c->bounced_out.clear();
-  c->ev_out_used = 0;
-  return hipStreamSynchronize(c->stream);
-}
-
 }  // namespace host
 }  // namespace icikt
 
@@ -1462,6 +1215,33 @@ static int check_pair_list(icikt_ctx* c, const char* who, const int32_t* pi, con
   return ICIKT_SUCCESS;
 }
 
+namespace icikt {
+namespace host {
+
+int check_pair_args(icikt_ctx* c, const char* who, const double* X, int64_t n_feat, int64_t n_samp, int64_t ld,
+                    const int32_t* pi, const int32_t* pj, int64_t* n_pairs, const void* out, bool out5,
+                    int perspective, int alternative) {
+  const std::string w(who);
+  int rc = check_shape(c, who, n_feat, n_samp, ld);
+  if (rc) return rc;
+  if (n_feat > 0 && n_samp > 0 && !X) return fail(c, ICIKT_E_INVALID, w + ": null matrix");
+  if (pi == nullptr) {
+    if (pj != nullptr) return fail(c, ICIKT_E_INVALID, w + ": pi is null but pj is not");
+    *n_pairs = n_samp * (n_samp - 1) / 2;
+  } else {
+    rc = check_pair_list(c, who, pi, pj, *n_pairs, n_samp);
+    if (rc) return rc;
+  }
+  if ((out5 ? n_samp : *n_pairs) > 0 && !out) return fail(c, ICIKT_E_INVALID, w + ": null output");
+  if (perspective != ICIKT_PERSPECTIVE_LOCAL && perspective != ICIKT_PERSPECTIVE_GLOBAL)
+    return fail(c, ICIKT_E_INVALID, w + ": perspective must be local (0) or global (1)");
+  if (alternative < 0 || alternative > ICIKT_ALT_OTHER) return fail(c, ICIKT_E_INVALID, w + ": bad alternative code");
+  return ICIKT_SUCCESS;
+}
+
+}  // namespace host
+}  // namespace icikt
+
 extern "C" {
 
 int icikt_pairs_f64(icikt_ctx* c, const double* X, int64_t n_feat, int64_t n_samp, int64_t ld,
@@ -1469,20 +1249,9 @@ int icikt_pairs_f64(icikt_ctx* c, const double* X, int64_t n_feat, int64_t n_sam
                     int continuity, uint32_t flags, double* out4, int64_t* counts, int32_t* reasons) {
   if (!c) return ICIKT_E_INVALID;
   // every argument is validated before the first asynchronous copy reads the caller's memory
-  int rc = check_shape(c, "pairs", n_feat, n_samp, ld);
+  int rc = icikt::host::check_pair_args(c, "pairs", X, n_feat, n_samp, ld, pi, pj, &n_pairs, out4, false, perspective,
+                                        alternative);
   if (rc) return rc;
-  if (n_feat > 0 && n_samp > 0 && !X) return fail(c, ICIKT_E_INVALID, "pairs: null matrix");
-  if (pi == nullptr) {
-    if (pj != nullptr) return fail(c, ICIKT_E_INVALID, "pairs: pi is null but pj is not");
-    n_pairs = n_samp * (n_samp - 1) / 2;
-  } else {
-    rc = check_pair_list(c, "pairs", pi, pj, n_pairs, n_samp);
-    if (rc) return rc;
-  }
-  if (n_pairs > 0 && !out4) return fail(c, ICIKT_E_INVALID, "pairs: null output");
-  if (perspective != ICIKT_PERSPECTIVE_LOCAL && perspective != ICIKT_PERSPECTIVE_GLOBAL)
-    return fail(c, ICIKT_E_INVALID, "pairs: perspective must be local (0) or global (1)");
-  if (alternative < 0 || alternative > ICIKT_ALT_OTHER) return fail(c, ICIKT_E_INVALID, "pairs: bad alternative code");
   rc = use_device(c);
   if (rc) return rc;
   rc = pi ? icikt_set_pairs(c, pi, pj, n_pairs) : icikt_set_pairs_combn(c, n_samp, 0, n_pairs);
@@ -1491,21 +1260,11 @@ int icikt_pairs_f64(icikt_ctx* c, const double* X, int64_t n_feat, int64_t n_sam
   if (rc) return rc;
   // The copies and the pre-pass are only ENQUEUED here; the host builds the pair kernel's task list while the matrix
   // crosses PCIe (it used to wait for the copies first and build the list afterwards, with the GPU idle: 1.2 ms of
-  // 14.3 on c4).  Nothing may still read the caller's matrix when the call returns: finish_upload.
-  const icikt::host::PinnedScope pinned_scope(c, flags);
+  // 14.3 on c4).  Nothing may still read the caller's matrix when the call returns: end_call.
+  const icikt::host::PinnedScope scope(c, flags);
   rc = icikt::host::upload_prepare_pairs(c, X, n_feat, n_samp, ld, flags);
-  auto finish_upload = [&]() {
-    (void)hipStreamSynchronize(c->prep_stream);
-    (void)hipStreamSynchronize(c->copy_stream);
-  };
-  if (rc) { finish_upload(); return rc; }
   const int64_t P = c->n_pairs;
-  if (P == 0) {
-    const hipError_t e0 = hipStreamSynchronize(c->stream);
-    finish_upload();
-    if (e0 != hipSuccess) return fail(c, ICIKT_E_HIP, std::string("pairs: ") + hipGetErrorString(e0));
-    return ICIKT_SUCCESS;
-  }
+  if (rc || P == 0) return icikt::host::end_call(c, "pairs", rc);
   auto body = [&]() -> int {
     HIPCHK(c, c->d_out4.reserve((size_t)P * 4));
     if (counts) HIPCHK(c, c->d_counts.reserve((size_t)P * ICIKT_CNT_FIELDS));
@@ -1519,13 +1278,8 @@ int icikt_pairs_f64(icikt_ctx* c, const double* X, int64_t n_feat, int64_t n_sam
     if (!r && reasons) r = icikt::host::download(c, reasons, c->d_reasons.p, (size_t)P * sizeof(int32_t));
     return r;
   };
-  rc = body();
   // success or not: nothing may still be reading or writing the caller's buffers when this returns
-  const hipError_t es = icikt::host::finish_stream(c, rc == 0);
-  finish_upload();
-  if (rc) return rc;
-  if (es != hipSuccess) return fail(c, ICIKT_E_HIP, std::string("pairs: ") + hipGetErrorString(es));
-  return ICIKT_SUCCESS;
+  return icikt::host::end_call(c, "pairs", body());
 }
 
 }  // extern "C"
@@ -1565,20 +1319,9 @@ int icikt_matrix_f64(icikt_ctx* c, const double* X, int64_t n_feat, int64_t n_sa
                      int alternative, int continuity, uint32_t flags, int scale_max, int diag_good, double* out5,
                      uint8_t* keep, int64_t* reason_counts) {
   if (!c) return ICIKT_E_INVALID;
-  int rc = check_shape(c, "matrix", n_feat, n_samp, ld);
+  int rc = icikt::host::check_pair_args(c, "matrix", X, n_feat, n_samp, ld, pi, pj, &n_pairs, out5, true, perspective,
+                                        alternative);
   if (rc) return rc;
-  if (n_feat > 0 && n_samp > 0 && !X) return fail(c, ICIKT_E_INVALID, "matrix: null matrix");
-  if (pi == nullptr) {
-    if (pj != nullptr) return fail(c, ICIKT_E_INVALID, "matrix: pi is null but pj is not");
-    n_pairs = n_samp * (n_samp - 1) / 2;
-  } else {
-    rc = check_pair_list(c, "matrix", pi, pj, n_pairs, n_samp);
-    if (rc) return rc;
-  }
-  if (n_samp > 0 && !out5) return fail(c, ICIKT_E_INVALID, "matrix: null output");
-  if (perspective != ICIKT_PERSPECTIVE_LOCAL && perspective != ICIKT_PERSPECTIVE_GLOBAL)
-    return fail(c, ICIKT_E_INVALID, "matrix: perspective must be local (0) or global (1)");
-  if (alternative < 0 || alternative > ICIKT_ALT_OTHER) return fail(c, ICIKT_E_INVALID, "matrix: bad alternative code");
   icikt::MaskSpec ms;
   rc = icikt::host::make_mask_spec(c, global_na, n_global_na, &ms);
   if (rc) return rc;
@@ -1597,17 +1340,13 @@ int icikt_matrix_f64(icikt_ctx* c, const double* X, int64_t n_feat, int64_t n_sa
   HIPCHK(c, c->d_red.reserve(8));
   HIPCHK(c, c->d_out4.reserve(std::max<size_t>(P, 1) * 4));
   HIPCHK(c, c->d_reasons.reserve(std::max<size_t>(P, 1)));
-  const icikt::host::PinnedScope pinned_scope(c, flags);
+  const icikt::host::PinnedScope scope(c, flags);
   c->k0_mask = &ms;
   c->k0_keep = keep_bytes ? c->d_keep.p : nullptr;
   rc = icikt::host::upload_prepare_pairs(c, X, n_feat, n_samp, ld, flags);
   c->k0_mask = nullptr;
   c->k0_keep = nullptr;
-  auto finish_upload = [&]() {
-    (void)hipStreamSynchronize(c->prep_stream);
-    (void)hipStreamSynchronize(c->copy_stream);
-  };
-  if (rc) { finish_upload(); return rc; }
+  if (rc) return icikt::host::end_call(c, "matrix", rc);
   unsigned long long red[8] = {};
   auto body = [&]() -> int {
     int r = icikt_run_dev(c, perspective, alternative, continuity, flags | (c->raw_valid ? ICIKT_FLAG_REUSE_COUNTS : 0u),
@@ -1621,11 +1360,8 @@ int icikt_matrix_f64(icikt_ctx* c, const double* X, int64_t n_feat, int64_t n_sa
     if (!r) r = icikt::host::download(c, red, c->d_red.p, sizeof(red));
     return r;
   };
-  rc = body();
-  const hipError_t es = icikt::host::finish_stream(c, rc == 0);
-  finish_upload();
+  rc = icikt::host::end_call(c, "matrix", body());
   if (rc) return rc;
-  if (es != hipSuccess) return fail(c, ICIKT_E_HIP, std::string("matrix: ") + hipGetErrorString(es));
   if (reason_counts) for (int k = 0; k < 5; ++k) reason_counts[k] = (int64_t)red[1 + k];
   return ICIKT_SUCCESS;
 }
@@ -1654,7 +1390,7 @@ int icikt_pairs_complete_f64(icikt_ctx* c, const double* X, int64_t n_feat, int6
   // the matrix and the pair list, once
   rc = icikt_set_pairs(c, pi, pj, n_pairs);
   if (rc) return rc;
-  const icikt::host::PinnedScope pinned_scope(c, flags);
+  const icikt::host::PinnedScope scope(c, flags);
   DevBuf<int32_t> all_pi, all_pj;  // the caller's list stays on the device while d_pi / d_pj hold a chunk's (2k, 2k+1)
   HIPCHK(c, all_pi.reserve((size_t)n_pairs));
   HIPCHK(c, all_pj.reserve((size_t)n_pairs));
@@ -1690,22 +1426,11 @@ int icikt_pairs_complete_f64(icikt_ctx* c, const double* X, int64_t n_feat, int6
       if (!r && counts) r = icikt::host::download(c, counts + ICIKT_CNT_FIELDS * first, c->d_counts.p, (size_t)m * ICIKT_CNT_FIELDS * sizeof(int64_t));
       if (!r && reasons) r = icikt::host::download(c, reasons + first, c->d_reasons.p, (size_t)m * sizeof(int32_t));
       if (r) return r;
-      {  // the chunk's buffers are reused by the next one
-        const hipError_t ec = hipStreamSynchronize(c->stream);
-        icikt::host::finish_downloads(c, ec == hipSuccess);
-        HIPCHK(c, ec);
-      }
+      HIPCHK(c, icikt::host::finish_stream(c, true));   // the chunk's buffers are reused by the next one
     }
     return ICIKT_SUCCESS;
   };
-  rc = body();
-  const hipError_t es = hipStreamSynchronize(c->stream);
-  icikt::host::finish_downloads(c, rc == 0 && es == hipSuccess);
-  all_pi.release();
-  all_pj.release();
-  if (rc) return rc;
-  if (es != hipSuccess) return fail(c, ICIKT_E_HIP, std::string("pairs_complete: ") + hipGetErrorString(es));
-  return ICIKT_SUCCESS;
+  return icikt::host::end_call(c, "pairs_complete", body());
 }
 
 int icikt_pair_f64(icikt_ctx* c, const double* x, const double* y, int64_t n, int perspective, int alternative,
@@ -1757,12 +1482,7 @@ int icikt_missingness_f64(icikt_ctx* c, const double* X, int64_t n_feat, int64_t
     HIPCHK(c, icikt::launch_missingness(c->pv, c->d_pi.p, c->d_pj.p, n_pairs, c->d_counts.p, c->stream));
     return icikt::host::download(c, missingness, c->d_counts.p, (size_t)n_pairs * sizeof(int64_t));
   };
-  rc = body();
-  const hipError_t es = hipStreamSynchronize(c->stream);
-  icikt::host::finish_downloads(c, rc == 0 && es == hipSuccess);
-  if (rc) return rc;
-  if (es != hipSuccess) return fail(c, ICIKT_E_HIP, std::string("missingness: ") + hipGetErrorString(es));
-  return ICIKT_SUCCESS;
+  return icikt::host::end_call(c, "missingness", body());
 }
 
 // Development / test hook: "key=value,key=value" overrides of the pair kernel's launch plan and of the host

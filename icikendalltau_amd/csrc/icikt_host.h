@@ -12,7 +12,9 @@
 
 #include "icikt.h"
 #include "icikt_device.h"
+#include "icikt_transfer.h"
 
+// a device buffer, grown on demand and kept; freed with its owner (on the device current at that time)
 template <typename T>
 struct DevBuf {
   T* p = nullptr;
@@ -27,11 +29,10 @@ struct DevBuf {
     if (e == hipSuccess) cap = want;
     return e;
   }
-  void release() {
-    if (p) (void)hipFree(p);
-    p = nullptr;
-    cap = 0;
-  }
+  DevBuf() = default;
+  DevBuf(const DevBuf&) = delete;
+  DevBuf& operator=(const DevBuf&) = delete;
+  ~DevBuf() { if (p) (void)hipFree(p); }
 };
 
 struct icikt_ctx {
@@ -72,18 +73,8 @@ struct icikt_ctx {
   // filled by a kernel at once, the host copies (h_pi / h_pj: only the host-built task lists read them) on demand
   int64_t combn_S = -1, combn_begin = 0, combn_end = 0;
   bool h_pairs_valid = false;
-  void* copy_pool = nullptr;      // worker threads of the staged transfers' host-side copies (icikt_capi.cpp: CopyPool)
-  void* pinned_tasks = nullptr;   // pinned staging of the task list the pipelined host path generates chunk by chunk
-  size_t pinned_tasks_bytes = 0;
   bool units_dirty = false;   // h_units has been rebuilt on the host and not uploaded yet
-  // result copies of 256 KB or more cross a pinned buffer of the library's (one per array of a call, kept from call
-  // to call) and are moved to the caller's array by finish_downloads()
-  struct Bounce { void* pinned; void* dst; size_t bytes; hipEvent_t ev; };   // ev: recorded behind the piece's D2H copy (may be null)
-  struct PinnedSlot { void* p = nullptr; size_t bytes = 0; };
-  std::vector<PinnedSlot> out_pinned;   // result downloads: one pinned buffer per array of a call, kept from call to call
-  std::vector<Bounce> bounced_out;
-  std::vector<hipEvent_t> ev_out;         // events of the result pieces in flight (a pool, reused from call to call)
-  size_t ev_out_used = 0;
+  icikt::host::Transfers xfer;   // the pinned buffers, threads and events that move caller memory (icikt_transfer.h)
 
   // host-path staging: a second stream for H2D copies that run ahead of K0 by column chunks
   hipStream_t copy_stream = nullptr;
@@ -94,11 +85,6 @@ struct icikt_ctx {
   std::vector<hipEvent_t> ev_chunk;        // pre-pass of chunk k done
   std::vector<int64_t> chunk_col_end;      // columns [.., chunk_col_end[k]) have arrived with chunk k (this call)
   int pipe_mode = -1;                      // -1: the library's choice; 0 / 1: off / on whenever possible (debug plan)
-  hipEvent_t ev_copy[4] = {};
-  void* pinned = nullptr;   // pinned staging area: the matrix in column chunks (two halves), pair / task lists in 8 MB pieces
-  size_t pinned_bytes = 0;
-  bool host_pinned = false; // for the duration of a host entry called with ICIKT_FLAG_HOST_PINNED: the caller has page-locked
-                            // the matrix and the result arrays, they are copied from / into directly (PinnedScope)
   DevBuf<double> d_X, d_out4, d_Xp;  // d_Xp: masked column pairs of icikt_pairs_complete_f64
   // full-matrix entry (icikt_matrix_f64): the exclusion rule the pre-pass applies while it reads the matrix and the
   // optional keep bytes it writes (both only for the duration of that call), the assembled matrices, the reduction
@@ -178,42 +164,11 @@ int upload_prepare_pairs(icikt_ctx* c, const double* X, int64_t n_feat, int64_t 
 int make_mask_spec(icikt_ctx* c, const double* global_na, int n_global_na, icikt::MaskSpec* ms);
 // Build the pair kernel's task list on the host now (prepare_alloc and a pair list must be in place).
 void prebuild_units(icikt_ctx* c);
-// Host <-> device copies of the caller's memory.  THE LIBRARY NEVER PAGE-LOCKS CALLER MEMORY (no hipHostRegister /
-// hipHostUnregister anywhere in it, since round 4) and never hands pageable memory of 256 KB or more to an asynchronous
-// copy: rounds 2 and 3 each saw one GPU memory-access fault at a host heap address inside a host entry, with
-// per-call registrations of heap ranges that Python frees and reuses; DESIGN.md section 6 lists what a reading of
-// that code found (registrations of neighbouring, non-page-aligned heap ranges set up and torn down independently
-// while copies from a neighbour were in flight) and why the mode was deleted rather than repaired.
-//   * the matrix: double-buffered column chunks through the library's pinned buffer (hipHostMalloc, kept from call to
-//     call), host-side copies on a few threads, each chunk's pre-pass and pair-kernel launches enqueued before the
-//     host stages the next chunk;
-//   * pair lists: a bounce buffer in 8 MB pieces (upload_sync); results: one pinned buffer per array (download /
-//     finish_downloads);
-//   * ICIKT_FLAG_HOST_PINNED: the caller states that the matrix and the result arrays of THIS call lie in memory it
-//     has page-locked itself (hipHostMalloc / hipHostRegister): they are copied from and into directly.  The library
-//     does not probe the caller's memory (hipPointerGetAttributes logs an error for every pageable pointer).
-// Copies below kLockMin take the runtime's staging path, which does not touch the caller's pages from the GPU.
-constexpr size_t kLockMin = (size_t)256 << 10;
-struct PinnedScope {
-  icikt_ctx* c;
-  PinnedScope(icikt_ctx* ctx, uint32_t flags) : c(ctx) { c->host_pinned = (flags & ICIKT_FLAG_HOST_PINNED) != 0; }
-  ~PinnedScope() { c->host_pinned = false; }
-  PinnedScope(const PinnedScope&) = delete;
-  PinnedScope& operator=(const PinnedScope&) = delete;
-};
-// grow c->pinned to at least `need` bytes (no copy may be in flight from or into it)
-int ensure_bounce(icikt_ctx* c, size_t need);
-void destroy_copy_pool(void* pool);
-// H2D on c->stream, complete (and the host range released) on return
-int upload_sync(icikt_ctx* c, void* dst, const void* src, size_t bytes);
-// after the stream that carries download() copies has been synchronised: deliver the bounced ones
-void finish_downloads(icikt_ctx* c, bool ok = true);
-// The end of a host entry: waits for the stream AND delivers the bounced results piece by piece as their copies
-// complete (a piece is moved to the caller's array while the next one still crosses PCIe).  ok: nothing failed so far;
-// returns the stream's status.  On an error the caller's arrays may hold part of the results: the call fails.
-hipError_t finish_stream(icikt_ctx* c, bool ok);
-// D2H of a result array into the caller's buffer on c->stream (not synchronised; finish_downloads afterwards)
-int download(icikt_ctx* c, void* dst, const void* src, size_t bytes);
+// The arguments the pair and matrix entries share, `who` prefixing the message: shape, null matrix, pair list (none: all
+// pairs, *n_pairs set), null output (out5: needed for any column, out4: for any pair), perspective and alternative.
+int check_pair_args(icikt_ctx* c, const char* who, const double* X, int64_t n_feat, int64_t n_samp, int64_t ld,
+                    const int32_t* pi, const int32_t* pj, int64_t* n_pairs, const void* out, bool out5,
+                    int perspective, int alternative);
 
 }  // namespace host
 }  // namespace icikt

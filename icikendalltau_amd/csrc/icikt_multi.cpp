@@ -81,13 +81,10 @@ struct icikt_multi {
   std::vector<double> rank_ms;                        // [rank][ICIKT_MULTI_PHASES + 1]: its phases, then its barrier waits
   int ranks_used = 0;                                 // of the last call: n, or 1 when it ran on the first device alone
   std::vector<int64_t> bounds;                        // of the last call: rank r ran pairs [bounds[r], bounds[r + 1]) of the list
-  void* root_compact = nullptr;                       // cost-weighted blocks, matrix entry: the gathered slots made contiguous
-  size_t root_compact_bytes = 0;
-  // rank 0's gather targets
-  void* root_out4 = nullptr;
-  void* root_counts = nullptr;
-  void* root_reasons = nullptr;
-  size_t root_out4_bytes = 0, root_counts_bytes = 0, root_reasons_bytes = 0;
+  // rank 0's gather targets (a slot per rank), and with cost-weighted blocks the slots made one contiguous list
+  DevBuf<double> root_out4, compact_out4;
+  DevBuf<int64_t> root_counts, compact_counts;
+  DevBuf<int32_t> root_reasons, compact_reasons;
 };
 
 extern "C" int icikt_cost_blocks(const uint32_t* col_cost, int64_t n_samp, const int32_t* pj, int64_t n_pairs, int n_blocks,
@@ -203,16 +200,6 @@ hipError_t peer_copy(void* dst, int dst_dev, const void* src, int src_dev, size_
   return hipMemcpyPeerAsync(dst, dst_dev, src, src_dev, bytes, s);
 }
 
-hipError_t grow(void** p, size_t* cap, size_t want) {
-  if (want <= *cap) return hipSuccess;
-  if (*p) (void)hipFree(*p);
-  *p = nullptr;
-  *cap = 0;
-  hipError_t e = hipMalloc(p, want);
-  if (e == hipSuccess) *cap = want;
-  return e;
-}
-
 #define RANKCHK_HIP(call)                                                                        \
   do {                                                                                           \
     hipError_t e__ = (call);                                                                     \
@@ -270,6 +257,11 @@ void rank_main(Call& a, int r) {
     t_prev = t;
   };
   size_t order_slice = 0, meta_slice = 0;
+  const bool with_reasons = a.reasons || a.matrix;   // (the matrix entry's assembly reads the reasons)
+  // Every rank stages its columns through its own pinned buffer (icikt_transfer.h: the library never page-locks the
+  // caller's memory); with ICIKT_FLAG_HOST_PINNED the caller has page-locked the matrix and the result arrays (portably,
+  // for several devices: hipHostMallocPortable / hipHostRegisterPortable) and every rank DMAs its columns straight out of it.
+  const icikt::host::PinnedScope scope(c, a.flags);
 
   // ---- phase A: this rank's pair block, its share of the columns: H2D + K0 ---------------------------------
   auto phase_a = [&]() {
@@ -293,10 +285,8 @@ void rank_main(Call& a, int r) {
     if (!a.balance) icikt::host::prebuild_units(c);   // the task list of this rank's pair block, while its columns are copied
     RANKCHK_HIP(c->d_out4.reserve((size_t)std::max<int64_t>(a.slot, 1) * 4));
     if (a.counts) RANKCHK_HIP(c->d_counts.reserve((size_t)std::max<int64_t>(a.slot, 1) * ICIKT_CNT_FIELDS));
-    if (a.reasons) RANKCHK_HIP(c->d_reasons.reserve((size_t)std::max<int64_t>(a.slot, 1)));
-    if (a.matrix && !a.reasons) RANKCHK_HIP(c->d_reasons.reserve((size_t)std::max<int64_t>(a.slot, 1)));
+    if (with_reasons) RANKCHK_HIP(c->d_reasons.reserve((size_t)std::max<int64_t>(a.slot, 1)));
     if (r == 0 && a.matrix) {
-      RANKCHK_HIP(grow(&m->root_reasons, &m->root_reasons_bytes, (size_t)G * a.slot * sizeof(int32_t)));
       RANKCHK_HIP(c->d_out5.reserve(5 * (size_t)S * (size_t)S));
       RANKCHK_HIP(c->d_red.reserve(8));
       if (a.pi) {   // the assembly needs the WHOLE pair list on the first device (combn order is computed)
@@ -306,13 +296,15 @@ void rank_main(Call& a, int r) {
         RANKCHK(icikt::host::upload_sync(c, c->d_pj_all.p, a.pj, (size_t)a.P * sizeof(int32_t)));
       }
     }
-    if (r == 0 && a.balance && a.matrix)
-      RANKCHK_HIP(grow(&m->root_compact, &m->root_compact_bytes, (size_t)a.P * 4 * sizeof(double) + (size_t)a.P * sizeof(int32_t) + 64));
     if (r == 0) {
-      RANKCHK_HIP(grow(&m->root_out4, &m->root_out4_bytes, (size_t)G * a.slot * 4 * sizeof(double)));
-      if (a.counts)
-        RANKCHK_HIP(grow(&m->root_counts, &m->root_counts_bytes, (size_t)G * a.slot * ICIKT_CNT_FIELDS * sizeof(int64_t)));
-      if (a.reasons) RANKCHK_HIP(grow(&m->root_reasons, &m->root_reasons_bytes, (size_t)G * a.slot * sizeof(int32_t)));
+      RANKCHK_HIP(m->root_out4.reserve((size_t)G * a.slot * 4));
+      if (a.counts) RANKCHK_HIP(m->root_counts.reserve((size_t)G * a.slot * ICIKT_CNT_FIELDS));
+      if (with_reasons) RANKCHK_HIP(m->root_reasons.reserve((size_t)G * a.slot));
+    }
+    if (r == 0 && a.balance) {
+      RANKCHK_HIP(m->compact_out4.reserve((size_t)a.P * 4));
+      if (a.counts) RANKCHK_HIP(m->compact_counts.reserve((size_t)a.P * ICIKT_CNT_FIELDS));
+      if (with_reasons) RANKCHK_HIP(m->compact_reasons.reserve((size_t)a.P));
     }
     order_slice = (size_t)a.cols_per * (size_t)c->pv.n_ord * sizeof(uint16_t);
     meta_slice = (size_t)a.cols_per * (size_t)c->pv.mstride * sizeof(unsigned long long);
@@ -375,102 +367,83 @@ void rank_main(Call& a, int r) {
     }
     if (a.timing) mark(ICIKT_MULTI_PHASE_EXCHANGE);   // (without the flag the exchange is only enqueued: counted with the pairs)
     RANKCHK(icikt_run_dev(c, a.perspective, a.alternative, a.continuity, a.flags & ~ICIKT_FLAG_TIMING, c->d_out4.p,
-                          a.counts ? c->d_counts.p : nullptr, (a.reasons || a.matrix) ? c->d_reasons.p : nullptr));
+                          a.counts ? c->d_counts.p : nullptr, with_reasons ? c->d_reasons.p : nullptr));
     if (!m->rccl) RANKCHK_HIP(hipStreamSynchronize(c->stream));  // rank 0 reads the results after the barrier
   };
   phase_b();
   mark(ICIKT_MULTI_PHASE_PAIRS);
   rendezvous();
-  // NB: a rank that failed inside phase B may have left its peers inside a collective that it never entered;
-  // everything that can fail for reasons of its own (allocation, argument checks) happens in phase A for that
-  // reason, and phase B failures are launch failures that hit every rank alike.
+  // NB: a rank that failed inside phase B may have left its peers inside a collective that it never entered.  The
+  // allocations happen in phase A for that reason, and the pair list is checked in full before the rank threads start;
+  // with cost-weighted blocks the set_pairs calls run in phase B, over a list that can no longer fail them.
   if (!all_ok(a)) {
     (void)hipStreamSynchronize(c->stream);
     return;
   }
 
-  // ---- phase C: gather to rank 0, one D2H -------------------------------------------------------------------
+  // ---- phase C: gather to rank 0, one D2H per array -----------------------------------------------------------
   auto phase_c = [&]() {
-    const size_t n4 = (size_t)a.slot * 4;
+    const size_t n4 = (size_t)a.slot * 4, nc = (size_t)a.slot * ICIKT_CNT_FIELDS;
     if (m->rccl) {
-      RANKCHK_NCCL(ncclGather(c->d_out4.p, m->root_out4, n4, ncclDouble, 0, m->comms[(size_t)r], c->stream));
-      if (a.counts)
-        RANKCHK_NCCL(ncclGather(c->d_counts.p, m->root_counts, (size_t)a.slot * ICIKT_CNT_FIELDS, ncclInt64, 0,
-                                m->comms[(size_t)r], c->stream));
-      if (a.reasons || a.matrix)
-        RANKCHK_NCCL(ncclGather(c->d_reasons.p, m->root_reasons, (size_t)a.slot, ncclInt32, 0, m->comms[(size_t)r], c->stream));
+      RANKCHK_NCCL(ncclGather(c->d_out4.p, m->root_out4.p, n4, ncclDouble, 0, m->comms[(size_t)r], c->stream));
+      if (a.counts) RANKCHK_NCCL(ncclGather(c->d_counts.p, m->root_counts.p, nc, ncclInt64, 0, m->comms[(size_t)r], c->stream));
+      if (with_reasons)
+        RANKCHK_NCCL(ncclGather(c->d_reasons.p, m->root_reasons.p, (size_t)a.slot, ncclInt32, 0, m->comms[(size_t)r], c->stream));
     } else if (r == 0) {
       for (int p = 0; p < G; ++p) {
-        RANKCHK_HIP(peer_copy(static_cast<double*>(m->root_out4) + (size_t)p * n4, m->devices[0], a.out4_dev[(size_t)p],
-                              m->devices[(size_t)p], n4 * sizeof(double), c->stream));
+        RANKCHK_HIP(peer_copy(m->root_out4.p + (size_t)p * n4, m->devices[0], a.out4_dev[(size_t)p], m->devices[(size_t)p],
+                              n4 * sizeof(double), c->stream));
         if (a.counts)
-          RANKCHK_HIP(peer_copy(static_cast<int64_t*>(m->root_counts) + (size_t)p * a.slot * ICIKT_CNT_FIELDS, m->devices[0],
-                                a.counts_dev[(size_t)p], m->devices[(size_t)p],
-                                (size_t)a.slot * ICIKT_CNT_FIELDS * sizeof(int64_t), c->stream));
-        if (a.reasons || a.matrix)
-          RANKCHK_HIP(peer_copy(static_cast<int32_t*>(m->root_reasons) + (size_t)p * a.slot, m->devices[0],
-                                a.reasons_dev[(size_t)p], m->devices[(size_t)p], (size_t)a.slot * sizeof(int32_t), c->stream));
+          RANKCHK_HIP(peer_copy(m->root_counts.p + (size_t)p * nc, m->devices[0], a.counts_dev[(size_t)p], m->devices[(size_t)p],
+                                nc * sizeof(int64_t), c->stream));
+        if (with_reasons)
+          RANKCHK_HIP(peer_copy(m->root_reasons.p + (size_t)p * a.slot, m->devices[0], a.reasons_dev[(size_t)p],
+                                m->devices[(size_t)p], (size_t)a.slot * sizeof(int32_t), c->stream));
       }
     }
-    if (a.matrix) {
-      // the keep bytes of this rank's columns; on the first rank the assembly over the gathered results (the blocks
-      // are consecutive and only the last one is short: the first P records ARE the pair list's results, in order)
-      if (a.keep && c1 > c0)
-        RANKCHK(icikt::host::download(c, a.keep + (size_t)c0 * (size_t)a.n_feat, c->d_keep.p + (size_t)c0 * (size_t)a.n_feat,
-                                      (size_t)(c1 - c0) * (size_t)a.n_feat));
-      if (r == 0) {
-        const double* all4 = static_cast<const double*>(m->root_out4);
-        const int32_t* allr = static_cast<const int32_t*>(m->root_reasons);
-        if (a.balance) {
-          // cost-weighted blocks have different lengths: the ranks' slots are made one contiguous list, in list order
-          double* c4 = static_cast<double*>(m->root_compact);
-          int32_t* cr = reinterpret_cast<int32_t*>(c4 + (size_t)a.P * 4);
-          for (int p = 0; p < G; ++p) {
-            const size_t len = (size_t)(a.bounds[(size_t)p + 1] - a.bounds[(size_t)p]);
-            if (len == 0) continue;
-            RANKCHK_HIP(hipMemcpyAsync(c4 + (size_t)a.bounds[(size_t)p] * 4, all4 + (size_t)p * n4, len * 4 * sizeof(double),
+    if (a.matrix && a.keep && c1 > c0)   // the keep bytes of this rank's columns
+      RANKCHK(icikt::host::download(c, a.keep + (size_t)c0 * (size_t)a.n_feat, c->d_keep.p + (size_t)c0 * (size_t)a.n_feat,
+                                    (size_t)(c1 - c0) * (size_t)a.n_feat));
+    if (r == 0) {
+      // equal blocks are consecutive and only the last one is short: the first P records of the gathered arrays ARE the
+      // pair list's results, in order.  Cost-weighted blocks have different lengths: the ranks' slots are made one
+      // contiguous list first.
+      const double* all4 = m->root_out4.p;
+      const int64_t* allc = m->root_counts.p;
+      const int32_t* allr = m->root_reasons.p;
+      if (a.balance) {
+        for (int p = 0; p < G; ++p) {
+          const size_t b0 = (size_t)a.bounds[(size_t)p], len = (size_t)(a.bounds[(size_t)p + 1] - a.bounds[(size_t)p]);
+          if (len == 0) continue;
+          RANKCHK_HIP(hipMemcpyAsync(m->compact_out4.p + b0 * 4, all4 + (size_t)p * n4, len * 4 * sizeof(double),
+                                     hipMemcpyDeviceToDevice, c->stream));
+          if (a.counts)
+            RANKCHK_HIP(hipMemcpyAsync(m->compact_counts.p + b0 * ICIKT_CNT_FIELDS, allc + (size_t)p * nc,
+                                       len * ICIKT_CNT_FIELDS * sizeof(int64_t), hipMemcpyDeviceToDevice, c->stream));
+          if (with_reasons)
+            RANKCHK_HIP(hipMemcpyAsync(m->compact_reasons.p + b0, allr + (size_t)p * (size_t)a.slot, len * sizeof(int32_t),
                                        hipMemcpyDeviceToDevice, c->stream));
-            RANKCHK_HIP(hipMemcpyAsync(cr + (size_t)a.bounds[(size_t)p], allr + (size_t)p * (size_t)a.slot, len * sizeof(int32_t),
-                                       hipMemcpyDeviceToDevice, c->stream));
-          }
-          all4 = c4; allr = cr;
         }
+        all4 = m->compact_out4.p; allc = m->compact_counts.p; allr = m->compact_reasons.p;
+      }
+      if (a.matrix) {
         RANKCHK_HIP(icikt::launch_out_stats(c->pv, all4, allr, a.P, nullptr, c->d_red.p, c->stream));
         RANKCHK_HIP(icikt::launch_assemble(c->pv, all4, a.pi ? c->d_pi_all.p : nullptr,
                                            a.pi ? c->d_pj_all.p : nullptr, a.P, nullptr, c->d_red.p, a.scale_max, a.diag_good,
                                            c->d_out5.p, c->stream));
         RANKCHK(icikt::host::download(c, a.out5, c->d_out5.p, 5 * (size_t)S * (size_t)S * sizeof(double)));
         RANKCHK(icikt::host::download(c, a.red, c->d_red.p, sizeof(a.red)));
-      }
-    } else if (r == 0 && !a.balance) {
-      // blocks are consecutive and only the last one is short: the first P records of the gathered array
-      RANKCHK(icikt::host::download(c, a.out4, m->root_out4, (size_t)a.P * 4 * sizeof(double)));
-      if (a.counts) RANKCHK(icikt::host::download(c, a.counts, m->root_counts, (size_t)a.P * ICIKT_CNT_FIELDS * sizeof(int64_t)));
-      if (a.reasons) RANKCHK(icikt::host::download(c, a.reasons, m->root_reasons, (size_t)a.P * sizeof(int32_t)));
-    } else if (r == 0) {
-      // cost-weighted blocks: every rank's slot holds a block of its own length -> one copy per rank and array
-      for (int p = 0; p < G; ++p) {
-        const size_t b0 = (size_t)a.bounds[(size_t)p], len = (size_t)(a.bounds[(size_t)p + 1] - a.bounds[(size_t)p]);
-        if (len == 0) continue;
-        RANKCHK(icikt::host::download(c, a.out4 + b0 * 4, static_cast<const double*>(m->root_out4) + (size_t)p * n4,
-                                      len * 4 * sizeof(double)));
-        if (a.counts)
-          RANKCHK(icikt::host::download(c, a.counts + b0 * ICIKT_CNT_FIELDS,
-                                        static_cast<const int64_t*>(m->root_counts) + (size_t)p * (size_t)a.slot * ICIKT_CNT_FIELDS,
-                                        len * ICIKT_CNT_FIELDS * sizeof(int64_t)));
-        if (a.reasons)
-          RANKCHK(icikt::host::download(c, a.reasons + b0, static_cast<const int32_t*>(m->root_reasons) + (size_t)p * (size_t)a.slot,
-                                        len * sizeof(int32_t)));
+      } else {
+        RANKCHK(icikt::host::download(c, a.out4, all4, (size_t)a.P * 4 * sizeof(double)));
+        if (a.counts) RANKCHK(icikt::host::download(c, a.counts, allc, (size_t)a.P * ICIKT_CNT_FIELDS * sizeof(int64_t)));
+        if (a.reasons) RANKCHK(icikt::host::download(c, a.reasons, allr, (size_t)a.P * sizeof(int32_t)));
       }
     }
-    const hipError_t es = icikt::host::finish_stream(c, true);   // (delivers the bounced results piece by piece as they arrive)
-    RANKCHK_HIP(es);
+    RANKCHK_HIP(icikt::host::finish_stream(c, true));   // (delivers the bounced results piece by piece as they arrive)
   };
   phase_c();
-  if (!c->bounced_out.empty()) {   // phase C left early: nothing may still write the caller's arrays
-    (void)hipStreamSynchronize(c->stream);
-    icikt::host::finish_downloads(c, false);
-  }
+  // phase C left early: the bounced results are dropped, and nothing may still write the caller's arrays
+  if (a.rc[(size_t)r] != ICIKT_SUCCESS) (void)icikt::host::finish_stream(c, false);
   mark(ICIKT_MULTI_PHASE_GATHER);
   rendezvous();  // "copy" exchange: nobody returns (and lets its buffers be reused) while rank 0 still reads them
 }
@@ -534,13 +507,9 @@ void icikt_multi_destroy(icikt_multi* m) {
       (void)hipSetDevice(m->devices[r]);
       (void)ncclCommDestroy(m->comms[r]);
     }
-  if (!m->devices.empty()) (void)hipSetDevice(m->devices[0]);
-  if (m->root_out4) (void)hipFree(m->root_out4);
-  if (m->root_counts) (void)hipFree(m->root_counts);
-  if (m->root_reasons) (void)hipFree(m->root_reasons);
-  if (m->root_compact) (void)hipFree(m->root_compact);
   for (icikt_ctx* c : m->ctx) icikt_ctx_destroy(c);
-  delete m;
+  if (!m->devices.empty()) (void)hipSetDevice(m->devices[0]);
+  delete m;   // (rank 0's gather buffers, on the first device)
 }
 
 const char* icikt_multi_last_error(const icikt_multi* m) { return m ? m->err.c_str() : "null handle"; }
@@ -633,17 +602,11 @@ int multi_impl(icikt_multi* m, const double* X, int64_t n_feat, int64_t n_samp, 
     m->phase_ms[ICIKT_MULTI_PHASE_PAIRS] = m->rank_ms[ICIKT_MULTI_PHASE_PAIRS] = now_ms() - t0;
     return ICIKT_SUCCESS;
   }
-  // argument checks (the ranks run unchecked): same texts as the single-device path
-  if (!X) return mfail(m, ICIKT_E_INVALID, "pairs_multi: null matrix");
-  if (n_pairs < 0 || (pi && !pj)) return mfail(m, ICIKT_E_INVALID, "pairs_multi: bad pair list");
-  if (pi)
-    for (int64_t p = 0; p < n_pairs; ++p)
-      if (pi[p] < 0 || pi[p] >= n_samp || pj[p] < 0 || pj[p] >= n_samp)
-        return mfail(m, ICIKT_E_INVALID, "pairs_multi: column index out of range");
-  if (mx ? !mx->out5 : !out4) return mfail(m, ICIKT_E_INVALID, "pairs_multi: null output");
-  if (perspective != ICIKT_PERSPECTIVE_LOCAL && perspective != ICIKT_PERSPECTIVE_GLOBAL)
-    return mfail(m, ICIKT_E_INVALID, "pairs_multi: perspective must be local (0) or global (1)");
-  if (alternative < 0 || alternative > ICIKT_ALT_OTHER) return mfail(m, ICIKT_E_INVALID, "pairs_multi: bad alternative code");
+  // argument checks (the ranks run unchecked): the single-device path's, under the prefix pairs_multi
+  const int rca = icikt::host::check_pair_args(m->ctx[0], "pairs_multi", X, n_feat, n_samp, ld, pi, pj, &n_pairs,
+                                               mx ? static_cast<const void*>(mx->out5) : out4, mx != nullptr, perspective,
+                                               alternative);
+  if (rca) return mfail(m, rca, icikt_last_error(m->ctx[0]));
 
   Call a{};
   a.m = m; a.X = X; a.n_feat = n_feat; a.n_samp = n_samp; a.ld = ld; a.pi = pi; a.pj = pj; a.P = n_pairs;
@@ -671,11 +634,6 @@ int multi_impl(icikt_multi* m, const double* X, int64_t n_feat, int64_t n_samp, 
   a.order_base.assign((size_t)G, nullptr); a.meta_base.assign((size_t)G, nullptr);
   a.out4_dev.assign((size_t)G, nullptr); a.counts_dev.assign((size_t)G, nullptr); a.reasons_dev.assign((size_t)G, nullptr);
 
-  // Every rank stages its columns through its own pinned buffer (icikt_host.h: the library never page-locks the caller's
-  // memory); with ICIKT_FLAG_HOST_PINNED the caller has page-locked the matrix and the result arrays (portably, for
-  // several devices: hipHostMallocPortable / hipHostRegisterPortable) and every rank DMAs its columns straight out of it.
-  for (icikt_ctx* c : m->ctx) c->host_pinned = (flags & ICIKT_FLAG_HOST_PINNED) != 0;
-
   std::vector<std::thread> th;
   bool started = true;
   try {
@@ -690,7 +648,6 @@ int multi_impl(icikt_multi* m, const double* X, int64_t n_feat, int64_t n_samp, 
   }
   if (started) rank_main(a, 0);  // the calling thread is rank 0
   for (auto& t : th) t.join();
-  for (icikt_ctx* c : m->ctx) c->host_pinned = false;
   m->ranks_used = G;
   m->bounds = a.bounds;
   for (int r = 0; r < G; ++r)

@@ -1,0 +1,109 @@
+// icikt_transfer.h -- how the library moves the caller's memory between host and device.  The one owner of that
+// policy: nothing outside icikt_transfer.cpp reads the pinned buffers, the result pieces or the caller-pinned state.
+// THE LIBRARY NEVER PAGE-LOCKS CALLER MEMORY (no hipHostRegister / hipHostUnregister anywhere in it, since round 4) and
+// never hands pageable memory of 256 KB or more to an asynchronous copy: rounds 2 and 3 each saw one GPU memory-access
+// fault at a host heap address inside a host entry, with per-call registrations of heap ranges that Python frees and
+// reuses; DESIGN.md section 6 lists what a reading of that code found (registrations of neighbouring, non-page-aligned
+// heap ranges set up and torn down independently while copies from a neighbour were in flight) and why the mode was
+// deleted rather than repaired.
+//   * the matrix: double-buffered column chunks through the library's pinned buffer (hipHostMalloc, kept from call to
+//     call), host-side copies on a few threads, each chunk's pre-pass and pair-kernel launches enqueued before the
+//     host stages the next chunk (MatrixUpload);
+//   * pair lists: a bounce buffer in 8 MB pieces (upload_sync); results: one pinned buffer per array (download /
+//     finish_stream);
+//   * ICIKT_FLAG_HOST_PINNED: the caller states that the matrix and the result arrays of THIS call lie in memory it
+//     has page-locked itself (hipHostMalloc / hipHostRegister): they are copied from and into directly.  The library
+//     does not probe the caller's memory (hipPointerGetAttributes logs an error for every pageable pointer).
+// Copies below kLockMin take the runtime's staging path, which does not touch the caller's pages from the GPU.
+#ifndef ICIKT_TRANSFER_H
+#define ICIKT_TRANSFER_H
+
+#include <hip/hip_runtime.h>
+
+#include <cstdint>
+#include <vector>
+
+#include "icikt.h"
+
+namespace icikt {
+namespace host {
+
+constexpr size_t kLockMin = (size_t)256 << 10;
+
+// a pinned host buffer of the library's (hipHostMalloc), grown on demand (no copy in flight in it then) and kept
+struct PinnedBuf {
+  void* p = nullptr;
+  size_t bytes = 0;
+  hipError_t reserve(size_t need);
+  PinnedBuf() = default;
+  PinnedBuf(PinnedBuf&& o) noexcept : p(o.p), bytes(o.bytes) { o.p = nullptr; o.bytes = 0; }
+  PinnedBuf(const PinnedBuf&) = delete;
+  PinnedBuf& operator=(const PinnedBuf&) = delete;
+  ~PinnedBuf();
+};
+
+struct CopyPool;
+
+// Everything a context uses to move caller memory (icikt_ctx::xfer)
+struct Transfers {
+  CopyPool* pool = nullptr;         // worker threads of the host-side copies (started on first use)
+  PinnedBuf stage;                  // the matrix in column chunks (two halves), pair / task lists in 8 MB pieces
+  hipEvent_t ev_copy[4] = {};       // [0]: the copy stream waits for the compute stream; [1..3]: behind chunk copies
+  PinnedBuf tasks;                  // the task list the pipelined all-pairs path writes chunk by chunk
+  // results of 256 KB or more: one pinned slot per array of a call (its position among the call's bounced downloads,
+  // kept from call to call), copied in pieces with an event behind each, moved to the caller's array by finish_stream
+  struct Piece { void* pinned; void* dst; size_t bytes; hipEvent_t ev; };   // ev may be null
+  std::vector<PinnedBuf> out_slots;
+  std::vector<Piece> pieces;
+  size_t n_downloads = 0;           // bounced downloads of the current call
+  std::vector<hipEvent_t> ev_out;   // events of the pieces in flight (a pool, reused from call to call)
+  size_t ev_out_used = 0;
+  bool host_pinned = false;         // the current call was made with ICIKT_FLAG_HOST_PINNED (PinnedScope)
+  ~Transfers();
+  hipError_t init();                // creates ev_copy
+};
+
+// For the duration of a host entry: the caller has page-locked the matrix and the result arrays when `flags` holds
+// ICIKT_FLAG_HOST_PINNED, and they are copied from / into directly.  The only way that state is set.
+struct PinnedScope {
+  icikt_ctx* c;
+  PinnedScope(icikt_ctx* ctx, uint32_t flags);
+  ~PinnedScope();
+  PinnedScope(const PinnedScope&) = delete;
+  PinnedScope& operator=(const PinnedScope&) = delete;
+};
+
+// One upload of the caller's matrix in column chunks (upload_and_prepare's loop), on c->copy_stream.  The route:
+//   staged (default)  through the library's pinned double buffer (a threaded host memcpy per chunk): the GPU never
+//                     touches the caller's pages, and the library never page-locks them
+//   in place          ICIKT_FLAG_HOST_PINNED on the call: the caller has page-locked the matrix itself; the copies are
+//                     DMA straight out of it
+//   small             matrices below kLockMin bytes take the runtime's own staging path
+struct MatrixUpload {
+  icikt_ctx* c;
+  size_t col_bytes, ld_bytes, chunk_bytes;   // a column, the caller's leading dimension, the largest chunk
+  bool staged = false, in_place = false;     // the route (in place: copies may still read the caller's matrix after the host went on)
+  // picks the route for a span of `span` bytes, grows the staging buffer, and makes c->copy_stream (and `also`, when
+  // not null) wait for the work already on c->stream: it may still read the device copy the chunks overwrite
+  hipError_t begin(size_t span, hipStream_t also);
+  // chunk k (0, 1, ... in order): nc columns from src to dst; *done is recorded behind the copy
+  hipError_t copy(int k, double* dst, const double* src, int64_t nc, hipEvent_t* done);
+};
+
+// H2D on c->stream, complete on return
+int upload_sync(icikt_ctx* c, void* dst, const void* src, size_t bytes);
+// D2H of a result array into the caller's buffer on c->stream (not synchronised: finish_stream delivers it)
+int download(icikt_ctx* c, void* dst, const void* src, size_t bytes);
+// Waits for c->stream AND delivers the bounced results piece by piece as their copies complete (a piece is moved to the
+// caller's array while the next one still crosses PCIe); ok = false (something failed already) drops them.  Returns the
+// stream's status.  On an error the caller's arrays may hold part of the results: the call fails.
+hipError_t finish_stream(icikt_ctx* c, bool ok);
+// The end of a host entry with status rc so far: finish_stream, then the other two streams (nothing may still touch the
+// caller's memory when the entry returns).  Returns rc, or ICIKT_E_HIP "who: ..." when the stream failed.
+int end_call(icikt_ctx* c, const char* who, int rc);
+// the pinned buffer of the pipelined all-pairs path's task list, n int32 words at least
+int task_staging(icikt_ctx* c, size_t n, int32_t** out);
+
+}  // namespace host
+}  // namespace icikt
+#endif
