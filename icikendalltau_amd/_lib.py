@@ -15,7 +15,7 @@ _PKG = os.path.dirname(os.path.abspath(__file__))
 _ROOT = os.path.dirname(_PKG)
 LIB_PATH = os.environ.get("ICIKT_LIB") or os.path.join(_PKG, "libicikt_hip.so")  # ICIKT_LIB: A/B of builds (tools)
 SOURCES = [os.path.join(_PKG, "csrc", f) for f in ("icikt_kernels.hip", "icikt_capi.cpp", "icikt_multi.cpp",
-                                                       "icikt_transfer.cpp")]
+                                                       "icikt_transfer.cpp", "icikt_cor.hip")]
 HEADERS = [os.path.join(_ROOT, "include", "icikt.h"), os.path.join(_PKG, "csrc", "icikt_device.h"),
            os.path.join(_PKG, "csrc", "icikt_host.h"), os.path.join(_PKG, "csrc", "icikt_transfer.h")]
 
@@ -38,6 +38,9 @@ MAX_FEATURES_WIDE = 262144    # the plain 32-bit path (exact integer arithmetic)
 PREP_ARRAYS = 5  # order, rec, hirow, meta (bitsets + stats per column), tgroups
 PREP_EXCHANGE = (0, 3)  # order and meta: the rest is rebuilt by expand_cols_dev()
 
+METHOD = {"pearson": 0, "spearman": 1}   # ICIKT_METHOD_*
+COR_OK, COR_SHORT, COR_NA, COR_TIES = range(4)   # ICIKT_COR_*: per-pair reasons of icikt_cor_pairs_f64
+
 REASON_OK, REASON_ALL_MISSING, REASON_SHORT, REASON_SINGLE_UNIQUE, REASON_TIES_EQ_TOTAL = range(5)
 REASON_WARNINGS = {
     REASON_SHORT: "Warning: The vectors only have a single value, NA returned!",  # src/kendallc.cpp:225
@@ -54,6 +57,7 @@ EXPORTS = (
     "icikt_pairs_multi_f64", "icikt_multi_phase_ms", "icikt_multi_debug_set_plan",
     "icikt_matrix_f64", "icikt_matrix_multi_f64", "icikt_multi_rank_phase_ms", "icikt_multi_ranks_used",
     "icikt_debug_step_stats", "icikt_multi_comm_ranks", "icikt_multi_block_bounds", "icikt_cost_blocks",
+    "icikt_cor_pairs_f64",
 )
 
 
@@ -137,6 +141,8 @@ def lib():
                                            c_vp, c_vp, c_vp]
     L.icikt_pair_f64.argtypes = [c_vp, c_vp, c_vp, c_i64, c_int, c_int, c_int, c_u32, c_vp, c_vp, c_vp]
     L.icikt_missingness_f64.argtypes = [c_vp, c_vp, c_i64, c_i64, c_i64, c_vp, c_vp, c_i64, c_vp]
+    L.icikt_cor_pairs_f64.argtypes = [c_vp, c_vp, c_i64, c_i64, c_i64, c_vp, c_vp, c_i64, c_int, c_int, c_int, c_int,
+                                      c_u32, c_vp, c_vp]
     L.icikt_selftest.argtypes = [c_vp]
     L.icikt_debug_set_plan.argtypes = [c_vp, ctypes.c_char_p]
     L.icikt_multi_create.argtypes = [ctypes.POINTER(c_int), c_int, c_int, ctypes.POINTER(c_vp)]
@@ -377,6 +383,23 @@ class Context:
                                                  P, alt, int(bool(continuity)), flags, _ptr(out), _ptr(cnt), _ptr(rsn)),
                   "icikt_pairs_complete_f64")
         return out, cnt, rsn
+
+    def cor_pairs(self, X, pi, pj, method="pearson", pairwise=False, alternative="two.sided", continuity=False,
+                  flags: int = 0):
+        """cor_fast's pairs (icikt_cor_pairs_f64): (out3 [P, 3]: rho, p-value, n_values; reasons [P], ICIKT_COR_*)."""
+        Xf = np.asfortranarray(X, dtype=np.float64)
+        if Xf.ndim != 2:
+            raise ValueError("X must be 2-D (features x samples)")
+        n_feat, n_samp = Xf.shape
+        pi_a = np.ascontiguousarray(pi, dtype=np.int32)
+        pj_a = np.ascontiguousarray(pj, dtype=np.int32)
+        P = pi_a.shape[0]
+        out = np.empty((P, 3), dtype=np.float64)
+        rsn = np.zeros(P, dtype=np.int32)
+        self._chk(lib().icikt_cor_pairs_f64(self._h, _ptr(Xf), n_feat, n_samp, max(n_feat, 0), _ptr(pi_a), _ptr(pj_a), P,
+                                            METHOD[method], int(bool(pairwise)), ALTERNATIVE[alternative],
+                                            int(bool(continuity)), flags, _ptr(out), _ptr(rsn)), "icikt_cor_pairs_f64")
+        return out, rsn
 
     def pair(self, x, y, perspective="local", alternative="two.sided", continuity=False, flags: int = 0):
         x = np.ascontiguousarray(x, dtype=np.float64)

@@ -58,6 +58,10 @@ class HipEngine:
         return self.ctx.matrix(data_matrix, global_na, pi, pj, perspective, alternative, continuity, self.flags,
                                scale_max, diag_good, want_keep=True)
 
+    def cor_pairs(self, X, pi, pj, method, pairwise, alternative, continuity):
+        """cor_fast's pairs on the device (icikt_cor_pairs_f64): (out3: rho, p-value, n_values; reasons)."""
+        return self.ctx.cor_pairs(X, pi, pj, method, pairwise, alternative, continuity)
+
     def pairs_complete(self, X, pi, pj):
         """kt_fast(use = "pairwise.complete.obs") on the device: (out4, reasons)."""
         out, _cnt, rsn = self.ctx.pairs_complete(X, pi, pj, "two.sided", False, self.flags)
@@ -113,6 +117,9 @@ class MultiHipEngine(HipEngine):
 
     def missingness(self, X, pi, pj):  # a bitset popcount: one device is plenty
         return self._one().missingness(X, pi, pj)
+
+    def cor_pairs(self, X, pi, pj, method, pairwise, alternative, continuity):  # cor_fast runs on one device
+        return self._one().cor_pairs(X, pi, pj, method, pairwise, alternative, continuity)
 
     def pairs_complete(self, X, pi, pj):  # kt_fast's per-pair masking path exists on one device only
         out, _cnt, rsn = self._one().pairs_complete(X, pi, pj, "two.sided", False, self.flags)
@@ -677,3 +684,270 @@ def kt_fast(x, y=None, use="everything", alternative="two.sided", continuity=Fal
     names_arr = np.asarray(names, dtype=object)
     cols = {"s1": names_arr[pi], "s2": names_arr[pj], "core": core.astype(np.float64), "tau": tau, "pvalue": pvalue}
     return {"tau": pd.DataFrame(cols) if pd is not None else cols, "run_time": t_diff}
+
+
+# --------------------------------------------------------------------------------------------------
+# cor_fast (R/other_correlations.R) -- DESIGN.md section 9
+# --------------------------------------------------------------------------------------------------
+_COR_TIES_WARNING = "Cannot compute exact p-value with ties"
+
+
+def _lgammacor(x):
+    r = 1.0 / x
+    r2 = r * r
+    return r * (1 / 12 + r2 * (-1 / 360 + r2 * (1 / 1260 + r2 * (-1 / 1680 + r2 * (1 / 1188 + r2 * (-691 / 360360))))))
+
+
+def _lbeta(a, b):
+    """log B(a, b) as R's lbeta computes it (no cancellation of lgamma differences at large arguments)."""
+    p, q = min(a, b), max(a, b)
+    if p >= 10:
+        corr = _lgammacor(p) + _lgammacor(q) - _lgammacor(p + q)
+        return -0.5 * math.log(q) + 0.918938533204672741780329736406 + corr + (p - 0.5) * math.log(p / (p + q)) + \
+            q * math.log1p(-p / (p + q))
+    if q >= 10:
+        corr = _lgammacor(q) - _lgammacor(p + q)
+        return math.lgamma(p) + corr + p - p * math.log(p + q) + (q - 0.5) * math.log1p(-p / (p + q))
+    return math.lgamma(p) + math.lgamma(q) - math.lgamma(p + q)
+
+
+def _incbeta_cf(a, b, x, y):
+    tiny, eps = 1e-300, 1e-16
+    front = math.exp(a * math.log(x) + b * math.log(y) - _lbeta(a, b)) / a
+    d = 1.0 - (a + b) * x / (a + 1.0)
+    d = 1.0 / (tiny if abs(d) < tiny else d)
+    c, f = 1.0, d
+    for m in range(1, 200000):
+        for num in (m * (b - m) * x / ((a + 2 * m - 1) * (a + 2 * m)),
+                    -(a + m) * (a + b + m) * x / ((a + 2 * m) * (a + 2 * m + 1))):
+            d = 1.0 + num * d
+            d = 1.0 / (tiny if abs(d) < tiny else d)
+            c = 1.0 + num / c
+            c = tiny if abs(c) < tiny else c
+            f *= d * c
+        if abs(d * c - 1.0) < eps:
+            break
+    return front * f
+
+
+def _incbeta(a, b, x, y):
+    """Regularized incomplete beta I_x(a, b); y = 1 - x, given separately."""
+    if x <= 0:
+        return 0.0
+    if y <= 0:
+        return 1.0
+    if x > (a + 1) / (a + b + 2):
+        return 1.0 - _incbeta_cf(b, a, y, x)
+    return _incbeta_cf(a, b, x, y)
+
+
+def _t_tail(t, df):
+    """P(T > |t|), Student's t with df degrees of freedom."""
+    if math.isinf(t):
+        return 0.0
+    t2 = t * t
+    return 0.5 * _incbeta(0.5 * df, 0.5, df / (df + t2), t2 / (df + t2))
+
+
+def _pt(t, df, lower):
+    if math.isnan(t) or not df > 0:
+        return math.nan
+    tail = _t_tail(t, df)
+    return tail if lower == (t < 0) else 1.0 - tail
+
+
+_PRHO_UPPER: dict = {}
+
+
+def _prho_upper(n):
+    """upper[k] = permutations of n rows whose S = sum (i - perm(i))^2 is >= 2 k (n <= 9)."""
+    if n not in _PRHO_UPPER:
+        import itertools
+        base = np.arange(n)
+        counts = np.zeros((n ** 3 - n) // 6 + 1, dtype=np.int64)
+        for perm in itertools.permutations(range(n)):
+            counts[int(((base - np.asarray(perm)) ** 2).sum()) // 2] += 1
+        _PRHO_UPPER[n] = np.cumsum(counts[::-1])[::-1]
+    return _PRHO_UPPER[n]
+
+
+def _prho(is_, n, lower):
+    """AS 89 (R's prho): P[S >= is] (lower = False) or P[S < is] (lower = True) for n untied rows."""
+    pv = 0.0 if lower else 1.0
+    if n <= 1 or is_ <= 0:
+        return pv
+    if is_ > n * (n * n - 1) / 3:
+        return 1.0 - pv
+    if n <= 9:
+        fact = math.factorial(n)
+        ifr = float(_prho_upper(n)[int(math.ceil(is_ / 2))])
+        return (fact - ifr if lower else ifr) / fact
+    b = 1.0 / n
+    x = (6.0 * (is_ - 1) * b / (n * n - 1) - 1) * math.sqrt(1 / b - 1)
+    y = x * x
+    u = x * b * (0.2274 + b * (0.2531 + 0.1745 * b) + y * (-0.0758 + b * (0.1033 + 0.3932 * b) - y * b * (
+        0.0879 + 0.0151 * b - y * (0.0072 - 0.0831 * b + y * b * (0.0131 - 4.6e-4 * y)))))
+    y = u / math.exp(y / 2)
+    up = 0.5 * math.erfc(x / math.sqrt(2))
+    pv = (1.0 - up) - y if lower else y + up
+    return min(1.0, max(0.0, pv))
+
+
+def _pspearman(q, n, lower, exact, continuity):
+    if n <= 1290 and exact:
+        return _prho(round(q) + 2 * lower, n, lower)
+    den = n * (n * n - 1) / 6
+    r = 1 - q / den
+    if continuity:
+        r -= math.copysign(1.0, r) / den if r != 0 else 0.0
+    with np.errstate(divide="ignore", invalid="ignore"):
+        t = float(np.float64(r) / np.sqrt(np.float64((1 - r * r) / (n - 2)))) if n > 2 else math.nan
+    return _pt(t, n - 2, not lower)
+
+
+def cor_test_pvalue(rho, n, method, alternative="two.sided", continuity=False, ties=False):
+    """stats::cor.test.default's p-value of an estimate rho over n rows (DESIGN.md section 9): the same formulas the
+    device epilogue (icikt_cor.hip, k_cor_epilogue) runs."""
+    if math.isnan(rho):
+        return math.nan
+    if method == "pearson":
+        df = n - 2
+        with np.errstate(divide="ignore", invalid="ignore"):
+            t = float(np.sqrt(np.float64(df)) * rho / np.sqrt(np.float64(1 - rho * rho)))
+        if alternative == "two.sided":
+            return 2.0 * _t_tail(t, df)
+        return _pt(t, df, alternative == "less")
+    exact = n < 1290 and not ties
+    q = (n ** 3 - n) * (1 - rho) / 6
+    if alternative == "two.sided":
+        p = _pspearman(q, n, not (q > (n ** 3 - n) / 6), exact, continuity)
+        return min(2 * p, 1.0)
+    return _pspearman(q, n, alternative == "greater", exact, continuity)
+
+
+def _rank2(v):
+    """2 * rank(v, ties.method = "average") (integers), and whether v has ties."""
+    order = np.argsort(v, kind="stable")
+    sv = v[order]
+    starts = np.r_[True, sv[1:] != sv[:-1]]
+    gid = np.cumsum(starts) - 1
+    first = np.flatnonzero(starts)
+    ends = np.r_[first[1:], len(v)]
+    r = np.empty(len(v), dtype=np.int64)
+    r[order] = first[gid] + ends[gid] + 1
+    return r, bool(len(first) < len(v))
+
+
+def _cor_pairs_numpy(X, pi, pj, method, pairwise, alternative, continuity):
+    """The front end's path for engines without cor_pairs (the CPU tests' checker engines): the arithmetic of the
+    device kernels, pair by pair, in numpy.  Returns (out3, reasons) like the HIP engine."""
+    P = len(pi)
+    out = np.full((P, 3), np.nan)
+    rsn = np.zeros(P, dtype=np.int32)
+    for p in range(P):
+        x, y = X[:, pi[p]], X[:, pj[p]]
+        joint = ~np.isnan(x) & ~np.isnan(y)
+        x, y = x[joint], y[joint]
+        n = len(x)
+        out[p, 2] = n
+        if n < (3 if (pairwise or method == "pearson") else 2):
+            rsn[p] = _lib.COR_SHORT
+            continue
+        ties = False
+        if method == "spearman":
+            (x, tx), (y, ty) = _rank2(x), _rank2(y)
+            ties = tx or ty
+            x, y = x - (n + 1), y - (n + 1)
+            sxx, syy, sxy = float((x * x).sum()), float((y * y).sum()), float((x * y).sum())
+        else:
+            if x.min() == x.max() or y.min() == y.max():
+                sxx = syy = sxy = 0.0
+            else:
+                with np.errstate(invalid="ignore"):
+                    xc, yc = x - x.mean(), y - y.mean()
+                    sxx, syy, sxy = float((xc * xc).sum()), float((yc * yc).sum()), float((xc * yc).sum())
+        if not (sxx > 0 and syy > 0) or math.isnan(sxy / math.sqrt(sxx * syy)):
+            rsn[p] = _lib.COR_NA
+            continue
+        rho = min(1.0, max(-1.0, sxy / math.sqrt(sxx * syy)))
+        if method == "spearman" and ties and n < 1290:
+            rsn[p] = _lib.COR_TIES
+        out[p, 0] = rho
+        out[p, 1] = cor_test_pvalue(rho, n, method, alternative, continuity, ties)
+    return out, rsn
+
+
+_COR_ALTERNATIVES = ("two.sided", "less", "greater")
+
+
+def cor_fast(x, y=None, use="everything", method="pearson", alternative="two.sided", continuity=False,
+             include_only=None, return_matrix=True, colnames=None, engine=None):
+    """stats::cor.test estimates and p-values for every pair of columns (R/other_correlations.R:27-141).
+
+    Same arguments, defaults, NA policies, return shapes and error texts as the reference: ``use`` as in ``kt_fast``
+    ("everything"/"all.obs": any NA -> every entry NA; "complete.obs": rows with an NA dropped first;
+    "pairwise.complete.obs": per pair, and a pair with fewer than 3 joint rows is NA), ``method`` "pearson" or
+    "spearman", self comparisons part of the result, ``include_only`` through ``setup_comparisons``.  Returns
+    ``{"rho", "pvalue", "run_time"}`` (S x S, 0 outside the listed pairs) or, with ``return_matrix=False``,
+    ``{"rho": data.frame(s1, s2, core, rho, pvalue, n_values), "run_time"}``.  Every pair runs on the MI355X
+    (icikt_cor_pairs_f64); an ``engine`` without ``cor_pairs`` (CPU tests) gets the same arithmetic in numpy.
+    Unlike the reference, ``n_values`` is each pair's own count (R/other_correlations.R:167 overwrites the whole
+    vector with one pair's count).
+    """
+    na_method = _match_use(use)
+    if na_method == "na.or.complete":
+        raise ValueError("'na.or.complete' is not a supported value for `use`. "
+                         "Please use one of all.obs complete.obs pairwise.complete everthing.")  # R/utils.R:86-90 (sic)
+    if method not in ("pearson", "spearman"):
+        raise ValueError("'arg' should be one of 'pearson', 'spearman'")
+    if alternative not in _COR_ALTERNATIVES:
+        raise ValueError("'arg' should be one of " + ", ".join(f"'{a}'" for a in _COR_ALTERNATIVES))
+    if y is None:
+        if not (pd is not None and isinstance(x, pd.DataFrame)) and np.ndim(x) < 2:
+            raise ValueError("`x` and `y` should both be provided as vectors, or `x` should be matrix-like.")
+        X, names = _as_matrix(x, colnames, "x")
+    else:
+        if np.ndim(x) > 1 or np.ndim(y) > 1:
+            raise ValueError("Both `x` and `y` must be vectors.")
+        X = np.column_stack([np.asarray(x, dtype=np.float64), np.asarray(y, dtype=np.float64)])
+        names = list(colnames) if colnames is not None else ["x", "y"]
+    pi, pj, core = setup_comparisons(names, include_only, diag_good=False, ncore=1)
+    P = len(pi)
+    out = np.full((P, 3), np.nan)
+    na_vals = np.isnan(X)
+    do_computation = True
+    if na_method in ("everything", "all.obs") and na_vals.any():
+        do_computation = False
+    if na_method == "complete.obs":
+        keep = ~na_vals.any(axis=1)
+        if keep.sum() == 0:
+            do_computation = False
+        else:
+            X = X[keep]
+    pairwise = na_method == "pairwise.complete.obs" and bool(np.isnan(X).any())
+    t_diff = 0.0
+    if do_computation:
+        if not pairwise and X.shape[0] < (3 if method == "pearson" else 2):
+            raise ValueError("not enough finite observations")  # stats::cor.test.default
+        eng = engine or _default_engine()
+        t1 = time.perf_counter()
+        if hasattr(eng, "cor_pairs"):
+            out, rsn = eng.cor_pairs(np.asfortranarray(X), pi, pj, method, pairwise, alternative, continuity)
+        else:
+            out, rsn = _cor_pairs_numpy(X, pi, pj, method, pairwise, alternative, continuity)
+        t_diff = time.perf_counter() - t1
+        if (rsn == _lib.COR_TIES).any():
+            warnings.warn(_COR_TIES_WARNING, RuntimeWarning, stacklevel=2)
+    rho, pvalue, n_values = out[:, 0], out[:, 1], out[:, 2]
+    if return_matrix:
+        S = len(names)
+        rm, pm = np.zeros((S, S)), np.zeros((S, S))
+        rm[pi, pj] = rho
+        rm[pj, pi] = rho
+        pm[pi, pj] = pvalue
+        pm[pj, pi] = pvalue
+        return {"rho": _named_matrix(rm, names), "pvalue": _named_matrix(pm, names), "run_time": t_diff}
+    names_arr = np.asarray(names, dtype=object)
+    cols = {"s1": names_arr[pi], "s2": names_arr[pj], "core": core.astype(np.float64), "rho": rho, "pvalue": pvalue,
+            "n_values": n_values}
+    return {"rho": pd.DataFrame(cols) if pd is not None else cols, "run_time": t_diff}

@@ -212,6 +212,40 @@ hipError_t launch_mask_pairs(const double* dX, int64_t ld, int n, const int32_t*
                              int64_t npairs, double* dXp, hipStream_t s);
 // pi / pj of pairs [begin, begin + count) of combn(S, 2) order, computed on the device
 hipError_t launch_fill_combn(int32_t* pi, int32_t* pj, int64_t S, int64_t begin, int64_t count, hipStream_t s);
+// ---- cor_fast (icikt_cor.hip) ----
+constexpr uint32_t COR_CONSTANT = 1u;   // per side of a pair (second side << 8): no variance among the rows used
+constexpr uint32_t COR_TIES = 2u;       // ... Spearman: tied ranks among them
+constexpr int COR_OK = 0, COR_SHORT = 1, COR_NA = 2, COR_TIES_WARN = 3;   // == ICIKT_COR_* of include/icikt.h
+// per pair: the rows used and the centred cross / square sums (Spearman: of doubled ranks, exact integers)
+struct CorAcc {
+  double m, sxy, sxx, syy;
+  uint32_t flags, pad;
+};
+struct CorPrep {
+  const double* X;   // the matrix on the device, NaN = NA
+  int64_t ld, n;     // leading dimension, rows
+  int S;             // columns
+  int method;        // 0 Pearson, 1 Spearman
+  double* Z;         // n x S: centred values (Pearson) / centred doubled ranks (Spearman); NA = NaN
+  int32_t* cnt;      // non-NA rows per column
+  double* colss;     // sum of squares of a column's Z
+  uint8_t* flags;    // COR_CONSTANT | COR_TIES per column
+  int32_t *ord, *gs, *ge;   // Spearman, n x S: sorted order of the non-NA rows, each position's tie group [gs, ge)
+  uint64_t* keys;    // Spearman: sort scratch, np2 per workgroup
+  int32_t* idx;
+  int np2;
+};
+hipError_t launch_cor_prep(const CorPrep& cp, int blocks, hipStream_t s);
+// all pairs of combn(S, 2) order (then the S self pairs when diag) of a matrix without NA
+hipError_t launch_cor_tile(const CorPrep& cp, int diag, CorAcc* acc, hipStream_t s);
+hipError_t launch_cor_dots(const CorPrep& cp, int pairwise, const int32_t* pi, const int32_t* pj, int64_t P, CorAcc* acc,
+                           hipStream_t s);
+// scratch: blocks x (2 n + 1) int32
+hipError_t launch_cor_spearman_pw(const CorPrep& cp, const int32_t* pi, const int32_t* pj, int64_t P, int blocks,
+                                  int32_t* scratch, CorAcc* acc, hipStream_t s);
+// prho_upper: the exact upper-tail permutation counts of Spearman's S for n = 2 .. 9 (cor_prho_table)
+hipError_t launch_cor_epilogue(const CorAcc* acc, int64_t P, int method, int pairwise, int alternative, int continuity,
+                               const uint32_t* prho_upper, double* out3, int32_t* reasons, hipStream_t s);
 hipError_t launch_selftest(uint32_t* d_out, hipStream_t s);
 hipError_t read_step_stats(unsigned long long* out24, int reset);
 

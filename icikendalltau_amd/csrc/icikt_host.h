@@ -100,6 +100,17 @@ struct icikt_ctx {
   DevBuf<int32_t> d_reasons;
   DevBuf<uint32_t> d_self;
 
+  // cor_fast (icikt_cor_pairs_f64)
+  struct CorBufs {
+    DevBuf<double> z, colss;
+    DevBuf<int32_t> cnt, order, scratch;   // order: ord | gs | ge, n x S each
+    DevBuf<uint8_t> flags;
+    DevBuf<unsigned long long> keys;
+    DevBuf<icikt::CorAcc> acc;
+    DevBuf<uint32_t> prho;                  // exact upper tails of Spearman's S, n = 2 .. 9 (uploaded once)
+    bool prho_ready = false;
+  } cor;
+
   // launch-plan overrides of the pair kernel (icikt_debug_set_plan; -1 = the library's choice)
   struct PlanOverride {
     int np = -1, pend = -1, wpb = -1, half = -1, grid_mult = -1, grid_cap = -1, hyb = -1;

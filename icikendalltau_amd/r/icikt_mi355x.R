@@ -139,3 +139,48 @@ ici_kendalltau_gpu = function(data_matrix, global_na = c(NA, Inf, 0), perspectiv
 #   split_cor = ici_split_all_gpu(split_comparisons, exclude_data, perspective, do_log_memory, alternative,
 #                                 continuity, n_gpu = n_gpu)
 # With n_gpu = 1 this is ici_split_gpu() on the single chunk.
+
+# cor_fast() (R/other_correlations.R:27-141) with every pair on the device: the reference's own argument checks
+# (check_na_method, check_x_y, setup_comparisons) and NA policies, then ONE .Call of icikt_rglue_cor.c (a DLL of its
+# own: dyn.load("icikt_rglue_cor.so")) instead of the per-pair stats::cor.test loop of cor_split.  Same return shapes;
+# n_values is each pair's own count (cor_split overwrites the whole vector on a pair with < 3 joint rows, :167).
+.icikt_cor_ties = "Cannot compute exact p-value with ties"
+
+cor_fast_gpu = function(x, y = NULL, use = "everything", method = "pearson", alternative = "two.sided",
+                        continuity = FALSE, include_only = NULL, return_matrix = TRUE, device = 0L) {
+  x_arg = rlang::caller_arg(x)
+  y_arg = rlang::caller_arg(y)
+  na_method = match.arg(use, c("all.obs", "complete.obs", "pairwise.complete.obs", "everything", "na.or.complete"))
+  check_na_method(na_method)
+  method = match.arg(method, c("pearson", "spearman"))
+  alternative = match.arg(alternative, c("two.sided", "less", "greater"))
+  x = check_x_y(x = x, y = y, x_arg = x_arg, y_arg = y_arg)
+  storage.mode(x) = "double"
+  cmp = do.call(rbind, setup_comparisons(colnames(x), include_only = include_only, diag_good = FALSE, ncore = 1L,
+                                         which = method, include_arg = NULL))
+  na_vals = is.na(x)
+  do_computation = !(na_method %in% c("everything", "all.obs") && any(na_vals))
+  if (na_method %in% "complete.obs") {
+    keep = rowSums(na_vals) == 0
+    if (sum(keep) == 0) do_computation = FALSE else x = x[keep, , drop = FALSE]
+  }
+  pairwise = na_method %in% "pairwise.complete.obs" && anyNA(x)
+  cmp$rho = NA_real_; cmp$pvalue = NA_real_; cmp$n_values = NA_real_
+  t_diff = 0
+  if (do_computation) {
+    if (!pairwise && nrow(x) < (if (method == "pearson") 3L else 2L)) stop("not enough finite observations")
+    t1 = Sys.time()
+    res = .Call("icikt_R_cor", x, match(cmp$s1, colnames(x)), match(cmp$s2, colnames(x)), method, pairwise,
+                alternative, continuity, as.integer(device), FALSE)
+    t_diff = as.numeric(difftime(Sys.time(), t1, units = "secs"))
+    if (any(res$reason == 3L)) warning(.icikt_cor_ties)
+    cmp$rho = res$rho; cmp$pvalue = res$pvalue; cmp$n_values = res$n_values
+  }
+  if (!return_matrix) return(list(rho = cmp, run_time = t_diff))
+  rho_matrix = matrix(0, nrow = ncol(x), ncol = ncol(x), dimnames = list(colnames(x), colnames(x)))
+  pvalue_matrix = rho_matrix
+  one_way = cbind(cmp$s1, cmp$s2); back_way = cbind(cmp$s2, cmp$s1)
+  rho_matrix[one_way] = cmp$rho; rho_matrix[back_way] = cmp$rho
+  pvalue_matrix[one_way] = cmp$pvalue; pvalue_matrix[back_way] = cmp$pvalue
+  list(rho = rho_matrix, pvalue = pvalue_matrix, run_time = t_diff)
+}

@@ -294,6 +294,22 @@ int icikt_pairs_complete_f64(icikt_ctx *ctx, const double *X, int64_t n_feat, in
                              const int32_t *pi, const int32_t *pj, int64_t n_pairs, int alternative,
                              int continuity, uint32_t flags, double *out4, int64_t *counts, int32_t *reasons);
 
+/* cor_fast (R/other_correlations.R): stats::cor.test estimates and p-values of Pearson or Spearman for every listed
+ * pair of columns (self pairs allowed).  NaN = NA.  pairwise = 0: no NA in the listed columns (the caller has applied
+ * use = "everything" / "complete.obs"); pairwise = 1: per pair, the rows missing in either column are dropped, and a
+ * pair with fewer than 3 such rows is NA (cor_split).  alternative: ICIKT_ALT_TWO_SIDED / LESS / GREATER; continuity:
+ * Spearman's t approximation only.  out3: P x 3 row-major (rho, p-value, n_values); reasons: ICIKT_COR_* per pair.
+ * flags: ICIKT_FLAG_TIMING (icikt_kernel_ms: pre-pass, products, epilogue), ICIKT_FLAG_HOST_PINNED. */
+#define ICIKT_METHOD_PEARSON 0
+#define ICIKT_METHOD_SPEARMAN 1
+#define ICIKT_COR_OK 0
+#define ICIKT_COR_SHORT 1      /* too few rows: fewer than 3 (pairwise, Pearson) or 2 (Spearman): NA */
+#define ICIKT_COR_NA 2         /* zero variance, or +-Inf in a Pearson pair: NA (cor's "standard deviation is zero") */
+#define ICIKT_COR_TIES 3       /* Spearman, n < 1290 with ties: "Cannot compute exact p-value with ties", t approximation */
+int icikt_cor_pairs_f64(icikt_ctx *ctx, const double *X, int64_t n_feat, int64_t n_samp, int64_t ld,
+                        const int32_t *pi, const int32_t *pj, int64_t n_pairs, int method, int pairwise,
+                        int alternative, int continuity, uint32_t flags, double *out3, int32_t *reasons);
+
 /* pairwise_completeness() arithmetic (R/kendalltau.R:611-629): missingness[p] = #rows missing in
  * either column, from a host matrix whose missing cells are NaN.  Self pairs allowed. */
 int icikt_missingness_f64(icikt_ctx *ctx, const double *X, int64_t n_feat, int64_t n_samp, int64_t ld,
