@@ -838,9 +838,29 @@ def _rank2(v):
     return r, bool(len(first) < len(v))
 
 
+def _pearson_sums(x, y):
+    """Sxx, Syy, Sxy of one pair's rows, centred and scaled as the device's pairwise kernel does it (DESIGN.md section
+    9): each side's deviations from its mean, times the power of two (exact) that brings the largest into [0.5, 1),
+    then Σd² - (Σd)²/m and Σde - Σd Σe/m, which take out what the rounding of the means leaves."""
+    m = len(x)
+    if not (np.isfinite(x).all() and np.isfinite(y).all()):
+        return math.nan, math.nan, math.nan
+    dev = []
+    for v in (x, y):
+        d = v - math.fsum(v) / m
+        s = float(np.abs(d).max())
+        dev.append(np.ldexp(d, -math.frexp(s)[1]) if s > 0 else d)
+    d, e = dev
+    sd, se = float(d.sum()), float(e.sum())
+    return (float((d * d).sum()) - sd * sd / m, float((e * e).sum()) - se * se / m,
+            float((d * e).sum()) - sd * se / m)
+
+
 def _cor_pairs_numpy(X, pi, pj, method, pairwise, alternative, continuity):
-    """The front end's path for engines without cor_pairs (the CPU tests' checker engines): the arithmetic of the
-    device kernels, pair by pair, in numpy.  Returns (out3, reasons) like the HIP engine."""
+    """The front end's path for engines without cor_pairs (the CPU tests' checker engines), pair by pair in numpy.
+    Spearman: the device's exact integer sums of doubled ranks.  Pearson: the device's corrected and scaled sums
+    (_pearson_sums), though not its summation order, so estimates agree with the device to rounding, not bit for bit.
+    Returns (out3, reasons) like the HIP engine."""
     P = len(pi)
     out = np.full((P, 3), np.nan)
     rsn = np.zeros(P, dtype=np.int32)
@@ -863,9 +883,7 @@ def _cor_pairs_numpy(X, pi, pj, method, pairwise, alternative, continuity):
             if x.min() == x.max() or y.min() == y.max():
                 sxx = syy = sxy = 0.0
             else:
-                with np.errstate(invalid="ignore"):
-                    xc, yc = x - x.mean(), y - y.mean()
-                    sxx, syy, sxy = float((xc * xc).sum()), float((yc * yc).sum()), float((xc * yc).sum())
+                sxx, syy, sxy = _pearson_sums(x, y)
         if not (sxx > 0 and syy > 0) or math.isnan(sxy / math.sqrt(sxx * syy)):
             rsn[p] = _lib.COR_NA
             continue

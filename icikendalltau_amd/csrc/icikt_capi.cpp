@@ -1512,9 +1512,11 @@ static std::vector<uint32_t> cor_prho_table() {
 extern "C" {
 
 // cor_fast: pre-pass (K_PREPARE timer), pair products (K_PAIRS), cor.test epilogue (K_EPILOGUE), all on c->stream.
-//   Pearson, no NA             Z^T Z of the mean-shifted columns: 64 x 64 tiles when the list is all of combn(S, 2)
-//                              (then the self pairs, or not), one wave per pair otherwise
-//   Pearson, pairwise          one wave per pair: the jointly present rows' sums, centred at the end
+//   Pearson, no NA             Z^T Z of the mean-shifted, power-of-two-scaled columns, less Σz_i Σz_j / n: 64 x 64
+//                              tiles when the list is all of combn(S, 2) (then the self pairs, or not), one wave per
+//                              pair otherwise
+//   Pearson, pairwise          one wave per pair, two passes over the raw columns: the jointly present rows' mean and
+//                              spread, then their centred, scaled and corrected sums (numerics)
 //   Spearman, no NA            as Pearson, on the centred doubled ranks (integers: the sums are exact)
 //   Spearman, pairwise         one workgroup per pair: the subset ranks from prefix counts, sums in int64
 int icikt_cor_pairs_f64(icikt_ctx* c, const double* X, int64_t n_feat, int64_t n_samp, int64_t ld,
@@ -1578,6 +1580,7 @@ int icikt_cor_pairs_f64(icikt_ctx* c, const double* X, int64_t n_feat, int64_t n
     const size_t nS = (size_t)std::max<int64_t>(n * n_samp, 1);
     HIPCHK(c, cb.z.reserve(nS));
     HIPCHK(c, cb.colss.reserve((size_t)std::max<int64_t>(n_samp, 1)));
+    HIPCHK(c, cb.colsum.reserve((size_t)std::max<int64_t>(n_samp, 1)));
     HIPCHK(c, cb.cnt.reserve((size_t)std::max<int64_t>(n_samp, 1)));
     HIPCHK(c, cb.flags.reserve((size_t)std::max<int64_t>(n_samp, 1)));
     HIPCHK(c, cb.acc.reserve((size_t)n_pairs));
@@ -1592,6 +1595,7 @@ int icikt_cor_pairs_f64(icikt_ctx* c, const double* X, int64_t n_feat, int64_t n
     cp.Z = cb.z.p;
     cp.cnt = cb.cnt.p;
     cp.colss = cb.colss.p;
+    cp.colsum = cb.colsum.p;
     cp.flags = cb.flags.p;
     cp.np2 = np2;
     if (spearman) {

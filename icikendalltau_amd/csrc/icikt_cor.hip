@@ -1,11 +1,12 @@
 // icikt_cor.hip -- cor_fast (R/other_correlations.R): Pearson / Spearman estimates and cor.test p-values for a pair list.
 //
-//   KC0  k_cor_prep          one workgroup per column: non-NA count, Pearson: column shifted by its own mean (NA = NaN),
-//                            Spearman: doubled average ranks (rank(ties.method = "average") * 2, integers) centred on
-//                            n + 1, the sorted order and each sorted position's tie-group bounds
+//   KC0  k_cor_prep          one workgroup per column: non-NA count, Pearson: column shifted by its own mean and scaled
+//                            by a power of two (NA = NaN), Σz, Σz², Spearman: doubled average ranks
+//                            (rank(ties.method = "average") * 2, integers) centred on n + 1, the sorted order and each
+//                            sorted position's tie-group bounds
 //   KC1  k_cor_tile          all pairs (+ self pairs) without NA: one 64 x 64 tile of Z^T Z per workgroup (f64 FMA)
-//        k_cor_dots          any pair list: one wave per pair; dense (Z^T Z) or pairwise Pearson (the jointly present
-//                            rows' n, sums, sums of squares, cross products, min / max)
+//        k_cor_dots          any pair list: one wave per pair; dense (Z^T Z) or pairwise Pearson (two passes over the
+//                            raw columns: the jointly present rows' n, mean, min / max, then their centred sums)
 //        k_cor_spearman_pw   pairwise Spearman with NA: one workgroup per pair, O(n), no per-pair sort: the subset ranks
 //                            of each side from prefix counts of the other side's presence along its sorted order
 //   KC2  k_cor_epilogue      one thread per pair: rho, stats::cor.test.default's p-value, n_values, reason
@@ -62,6 +63,33 @@ template <typename T>
 __device__ inline T wave_sum(T v) {
   for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
   return v;
+}
+
+// TwoSum (Knuth): hi + lo += v with the rounding error of hi + v kept exactly in lo
+__device__ inline void two_sum_acc(double& hi, double& lo, double v) {
+  const double s = hi + v, bp = s - hi;
+  lo += (hi - (s - bp)) + (v - bp);
+  hi = s;
+}
+
+// the wave's TwoSum total; (lo + l) + err is symmetric in the two lanes of a step, so every lane ends with the same
+// hi and lo
+__device__ inline void wave_two_sum(double& hi, double& lo) {
+  for (int o = 32; o > 0; o >>= 1) {
+    const double h = __shfl_xor(hi, o, 64), l = __shfl_xor(lo, o, 64);
+    const double s = hi + h, bp = s - hi;
+    lo = (lo + l) + ((hi - (s - bp)) + (h - bp));
+    hi = s;
+  }
+}
+
+// 2^-e for the spread s in [2^(e-1), 2^e): an exact rescaling of deviations up to s into [0.5, 1), so that their
+// squares neither overflow (s ~ 1e300) nor underflow (s ~ 1e-300); 1 when s is 0, Inf or NaN
+__device__ inline double cor_scale(double s) {
+  if (!(s > 0.0) || s - s != 0.0) return 1.0;
+  int e;
+  frexp(s, &e);
+  return ldexp(1.0, -(e < -1022 ? -1022 : e));
 }
 
 struct Add { template <typename T> __device__ T operator()(T a, T b) const { return a + b; } };
@@ -123,14 +151,14 @@ __global__ void __launch_bounds__(CT) k_cor_prep(CorPrep cp) {
     const double* x = cp.X + (int64_t)c * cp.ld;
     double* z = cp.Z + (int64_t)c * n;
     int cnt = 0, cntf = 0;
-    double sum = 0.0, mn = INFINITY, mx = -INFINITY;
+    double sum = 0.0, mn = INFINITY, mx = -INFINITY, mnf = INFINITY, mxf = -INFINITY;
     for (int64_t r = threadIdx.x; r < n; r += CT) {
       const double v = x[r];
       if (v == v) {
         ++cnt;
         mn = fmin(mn, v);
         mx = fmax(mx, v);
-        if (v - v == 0.0) { ++cntf; sum += v; }
+        if (v - v == 0.0) { ++cntf; sum += v; mnf = fmin(mnf, v); mxf = fmax(mxf, v); }
       }
     }
     cnt = block_reduce(cnt, shi, Add());
@@ -138,6 +166,8 @@ __global__ void __launch_bounds__(CT) k_cor_prep(CorPrep cp) {
     sum = block_reduce(sum, shd, Add());
     mn = block_reduce(mn, shd, Min());
     mx = block_reduce(mx, shd, Max());
+    mnf = block_reduce(mnf, shd, Min());
+    mxf = block_reduce(mxf, shd, Max());
     uint32_t fl = (cnt == 0 || mn == mx) ? COR_CONSTANT : 0u;
     if (cp.method == 0) {
       // Pearson: shift by the mean of the finite values, refined once (a constant column becomes exactly 0)
@@ -148,15 +178,24 @@ __global__ void __launch_bounds__(CT) k_cor_prep(CorPrep cp) {
       }
       corr = block_reduce(corr, shd, Add());
       const double mean = cntf ? m1 + corr / cntf : 0.0;
-      double ss = 0.0;
+      // Z = (x - mean) 2^-e, the largest finite deviation in [0.5, 1); Σz and Σz² of the same Z: the products kernels
+      // subtract Σz_i Σz_j / n, which takes out the rounding of the mean (n δ², large when |mean| >> sd)
+      const double sc = cntf ? cor_scale(fmax(mxf - mean, mean - mnf)) : 1.0;
+      double ss = 0.0, sz = 0.0;
       for (int64_t r = threadIdx.x; r < n; r += CT) {
         const double v = x[r];
-        const double d = (v == v) ? v - mean : (double)NAN;
+        const double d = (v == v) ? (v - mean) * sc : (double)NAN;
         z[r] = d;
-        if (v == v) ss += d * d;
+        if (v == v) { sz += d; ss += d * d; }
       }
       ss = block_reduce(ss, shd, Add());
-      if (threadIdx.x == 0) { cp.cnt[c] = cnt; cp.colss[c] = ss; cp.flags[c] = fl; }
+      sz = block_reduce(sz, shd, Add());
+      if (threadIdx.x == 0) {
+        cp.cnt[c] = cnt;
+        cp.colss[c] = cnt ? ss - sz * sz / cnt : 0.0;
+        cp.colsum[c] = sz;
+        cp.flags[c] = fl;
+      }
       continue;
     }
     // Spearman: sort, tie groups, doubled average ranks
@@ -216,7 +255,7 @@ __global__ void __launch_bounds__(CT) k_cor_prep(CorPrep cp) {
     ss = block_reduce(ss, shl, Add());
     tied = block_reduce(tied, shi, Max());
     if (tied) fl |= COR_TIES;
-    if (threadIdx.x == 0) { cp.cnt[c] = cnt; cp.colss[c] = (double)ss; cp.flags[c] = fl; }
+    if (threadIdx.x == 0) { cp.cnt[c] = cnt; cp.colss[c] = (double)ss; cp.colsum[c] = 0.0; cp.flags[c] = fl; }
     __syncthreads();
   }
 }
@@ -226,10 +265,11 @@ __device__ inline int64_t combn_index(int64_t i, int64_t j, int64_t S) {
   return i * S - i * (i + 1) / 2 + (j - i - 1);
 }
 
+// colss holds the corrected Σz² - (Σz)² / n, so a self pair is the very sum of its variances: rho = 1 exactly
 __device__ inline void dense_acc(CorAcc* a, double sxy, int i, int j, const int32_t* cnt, const double* colss,
-                                 const uint8_t* flags) {
+                                 const double* colsum, const uint8_t* flags) {
   a->m = (double)cnt[i];
-  a->sxy = (i == j) ? colss[i] : sxy;   // a self pair from the very sums of its variances: rho = 1 exactly
+  a->sxy = (i == j) ? colss[i] : sxy - colsum[i] * colsum[j] / a->m;
   a->sxx = colss[i];
   a->syy = colss[j];
   a->flags = (uint32_t)flags[i] | ((uint32_t)flags[j] << 8);
@@ -238,7 +278,8 @@ __device__ inline void dense_acc(CorAcc* a, double sxy, int i, int j, const int3
 // Z^T Z over the upper triangle of 64 x 64 tiles; thread (ty, tx) holds rows ty + 16 a, columns tx + 16 b of its tile
 __global__ void __launch_bounds__(CT) k_cor_tile(const double* __restrict__ Z, int64_t n, int S, int diag,
                                                  const int32_t* __restrict__ cnt, const double* __restrict__ colss,
-                                                 const uint8_t* __restrict__ flags, CorAcc* __restrict__ acc) {
+                                                 const double* __restrict__ colsum, const uint8_t* __restrict__ flags,
+                                                 CorAcc* __restrict__ acc) {
   constexpr int T = 64, KB = 16;
   __shared__ double A[KB][T + 1], B[KB][T + 1];
   // blockIdx.x -> (bi, bj), bi <= bj
@@ -279,53 +320,73 @@ __global__ void __launch_bounds__(CT) k_cor_tile(const double* __restrict__ Z, i
       if (i >= S || j >= S || i > j) continue;
       if (i == j && !diag) continue;
       const int64_t p = (i == j) ? ncombn + i : combn_index(i, j, S);
-      dense_acc(&acc[p], s[u][v], i, j, cnt, colss, flags);
+      dense_acc(&acc[p], s[u][v], i, j, cnt, colss, colsum, flags);
     }
 }
 
-// one wave per pair of any list.  PW: pairwise Pearson (NaN = NA): the jointly present rows' sums, centred at the end
+// one wave per pair of any list.  Dense: V = Z (stride n), Σ z_i z_j.  PW, pairwise Pearson: V = the raw matrix
+// (stride ld, NaN = NA), two passes over the jointly present rows.  Centring on each column's mean (Z) would not do:
+// a pair's rows can sit far from it (left-censoring), and the shift has already rounded away what tells them apart.
+//   1. count, TwoSum Σx and Σy (means good to an ulp), min / max of the raw values (exact zero-variance test)
+//   2. d = (x - mean_x) 2^-ex, e likewise, with 2^-ex from the pair's own spread: Sxy = Σde - Σd Σe / m, and so on
 template <bool PW>
-__global__ void __launch_bounds__(CT) k_cor_dots(const double* __restrict__ Z, int64_t n, const int32_t* __restrict__ pi,
-                                                 const int32_t* __restrict__ pj, int64_t P, const int32_t* __restrict__ cnt,
-                                                 const double* __restrict__ colss, const uint8_t* __restrict__ flags,
-                                                 CorAcc* __restrict__ acc) {
+__global__ void __launch_bounds__(CT) k_cor_dots(const double* __restrict__ V, int64_t n, int64_t ld,
+                                                 const int32_t* __restrict__ pi, const int32_t* __restrict__ pj,
+                                                 int64_t P, const int32_t* __restrict__ cnt,
+                                                 const double* __restrict__ colss, const double* __restrict__ colsum,
+                                                 const uint8_t* __restrict__ flags, CorAcc* __restrict__ acc) {
   const int lane = threadIdx.x & 63;
   const int64_t nw = (int64_t)gridDim.x * (CT / 64);
   for (int64_t p = (int64_t)blockIdx.x * (CT / 64) + (threadIdx.x >> 6); p < P; p += nw) {
     const int i = pi[p], j = pj[p];
-    const double* x = Z + (int64_t)i * n;
-    const double* y = Z + (int64_t)j * n;
+    const double* x = V + (int64_t)i * ld;
+    const double* y = V + (int64_t)j * ld;
     if (!PW) {
       double s = 0.0;
       for (int64_t r = lane; r < n; r += 64) s = fma(x[r], y[r], s);
       s = wave_sum(s);
-      if (lane == 0) dense_acc(&acc[p], s, i, j, cnt, colss, flags);
+      if (lane == 0) dense_acc(&acc[p], s, i, j, cnt, colss, colsum, flags);
       continue;
     }
-    double m = 0, sx = 0, sy = 0, sxx = 0, syy = 0, sxy = 0;
+    double m = 0, sx = 0, ex = 0, sy = 0, ey = 0;
     double mnx = INFINITY, mxx = -INFINITY, mny = INFINITY, mxy = -INFINITY;
     for (int64_t r = lane; r < n; r += 64) {
       const double a = x[r], b = y[r];
-      if (a == a && b == b) {   // (a row with +-Inf on one side and NA on the other stays out: no Inf * 0)
+      if (a == a && b == b) {   // (a row with +-Inf on one side and NA on the other stays out)
         m += 1.0;
-        sx += a; sy += b;
-        sxx = fma(a, a, sxx); syy = fma(b, b, syy); sxy = fma(a, b, sxy);
+        two_sum_acc(sx, ex, a);
+        two_sum_acc(sy, ey, b);
         mnx = fmin(mnx, a); mxx = fmax(mxx, a); mny = fmin(mny, b); mxy = fmax(mxy, b);
       }
     }
-    m = wave_sum(m); sx = wave_sum(sx); sy = wave_sum(sy);
-    sxx = wave_sum(sxx); syy = wave_sum(syy); sxy = wave_sum(sxy);
+    m = wave_sum(m);
+    wave_two_sum(sx, ex);
+    wave_two_sum(sy, ey);
     for (int o = 32; o > 0; o >>= 1) {
       mnx = fmin(mnx, __shfl_xor(mnx, o, 64)); mxx = fmax(mxx, __shfl_xor(mxx, o, 64));
       mny = fmin(mny, __shfl_xor(mny, o, 64)); mxy = fmax(mxy, __shfl_xor(mxy, o, 64));
     }
+    // (+-Inf in the subset makes the means NaN, then every sum: the epilogue's NA)
+    const double mx = m > 0 ? (sx + ex) / m : 0.0, my = m > 0 ? (sy + ey) / m : 0.0;
+    const double cx = cor_scale(fmax(mxx - mx, mx - mnx)), cy = cor_scale(fmax(mxy - my, my - mny));
+    double sd = 0, se = 0, sdd = 0, see = 0, sde = 0;
+    for (int64_t r = lane; r < n; r += 64) {
+      const double a = x[r], b = y[r];
+      if (a == a && b == b) {
+        const double d = (a - mx) * cx, e = (b - my) * cy;
+        sd += d; se += e;
+        sdd = fma(d, d, sdd); see = fma(e, e, see); sde = fma(d, e, sde);
+      }
+    }
+    sd = wave_sum(sd); se = wave_sum(se);
+    sdd = wave_sum(sdd); see = wave_sum(see); sde = wave_sum(sde);
     if (lane == 0) {
       CorAcc a;
       a.m = m;
       if (m > 0) {
-        a.sxy = sxy - sx * sy / m;
-        a.sxx = sxx - sx * sx / m;
-        a.syy = syy - sy * sy / m;
+        a.sxy = sde - sd * se / m;
+        a.sxx = sdd - sd * sd / m;
+        a.syy = see - se * se / m;
       } else {
         a.sxy = a.sxx = a.syy = 0.0;
       }
@@ -569,7 +630,7 @@ hipError_t launch_cor_tile(const CorPrep& cp, int diag, CorAcc* acc, hipStream_t
   (void)hipGetLastError();
   const int64_t nb = (cp.S + 63) / 64;
   hipLaunchKernelGGL(k_cor_tile, dim3((unsigned)(nb * (nb + 1) / 2)), dim3(CT), 0, s, cp.Z, cp.n, cp.S, diag, cp.cnt,
-                     cp.colss, cp.flags, acc);
+                     cp.colss, cp.colsum, cp.flags, acc);
   return hipGetLastError();
 }
 
@@ -579,11 +640,11 @@ hipError_t launch_cor_dots(const CorPrep& cp, int pairwise, const int32_t* pi, c
   (void)hipGetLastError();
   const int64_t blocks = std::min<int64_t>((P + 3) / 4, 65536);
   if (pairwise)
-    hipLaunchKernelGGL(k_cor_dots<true>, dim3((unsigned)blocks), dim3(CT), 0, s, cp.Z, cp.n, pi, pj, P, cp.cnt, cp.colss,
-                       cp.flags, acc);
+    hipLaunchKernelGGL(k_cor_dots<true>, dim3((unsigned)blocks), dim3(CT), 0, s, cp.X, cp.n, cp.ld, pi, pj, P, cp.cnt,
+                       cp.colss, cp.colsum, cp.flags, acc);
   else
-    hipLaunchKernelGGL(k_cor_dots<false>, dim3((unsigned)blocks), dim3(CT), 0, s, cp.Z, cp.n, pi, pj, P, cp.cnt, cp.colss,
-                       cp.flags, acc);
+    hipLaunchKernelGGL(k_cor_dots<false>, dim3((unsigned)blocks), dim3(CT), 0, s, cp.Z, cp.n, cp.n, pi, pj, P, cp.cnt,
+                       cp.colss, cp.colsum, cp.flags, acc);
   return hipGetLastError();
 }
 

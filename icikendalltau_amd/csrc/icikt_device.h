@@ -228,7 +228,8 @@ struct CorPrep {
   int method;        // 0 Pearson, 1 Spearman
   double* Z;         // n x S: centred values (Pearson) / centred doubled ranks (Spearman); NA = NaN
   int32_t* cnt;      // non-NA rows per column
-  double* colss;     // sum of squares of a column's Z
+  double* colss;     // Pearson: Σz² - (Σz)² / n of a column's Z; Spearman: Σz²
+  double* colsum;    // Σz (Spearman: 0)
   uint8_t* flags;    // COR_CONSTANT | COR_TIES per column
   int32_t *ord, *gs, *ge;   // Spearman, n x S: sorted order of the non-NA rows, each position's tie group [gs, ge)
   uint64_t* keys;    // Spearman: sort scratch, np2 per workgroup

@@ -102,7 +102,7 @@ struct icikt_ctx {
 
   // cor_fast (icikt_cor_pairs_f64)
   struct CorBufs {
-    DevBuf<double> z, colss;
+    DevBuf<double> z, colss, colsum;
     DevBuf<int32_t> cnt, order, scratch;   // order: ord | gs | ge, n x S each
     DevBuf<uint8_t> flags;
     DevBuf<unsigned long long> keys;

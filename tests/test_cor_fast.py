@@ -1,7 +1,9 @@
 """cor_fast (R/other_correlations.R) without a GPU: the front end through the numpy path (engines without cor_pairs)
-against scipy and mpmath, the reference's own README and testthat values, Spearman's exact p-values against
-permutation enumeration, the ABI constants, and the R glue of icikt_R_cor compiled with warnings as errors."""
+against scipy and mpmath, Pearson on ill-conditioned data against exact arithmetic, the reference's own README and
+testthat values, Spearman's exact p-values against permutation enumeration, the ABI constants, and the R glue of
+icikt_R_cor compiled with warnings as errors."""
 import ctypes
+from fractions import Fraction
 import math
 import os
 import re
@@ -15,7 +17,7 @@ from scipy import stats
 
 from icikendalltau_amd import _lib, api, cor_fast
 from oracle.rrng import RRandom
-from tests.cor_checker import check_pairs, exact_upper
+from tests.cor_checker import assert_matches_exact, check_pairs, exact_pearson, exact_upper, ill_dense, ill_pairwise
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -163,3 +165,61 @@ def test_abi_constants():
     for k, v in (("OK", _lib.COR_OK), ("SHORT", _lib.COR_SHORT), ("NA", _lib.COR_NA), ("TIES", _lib.COR_TIES)):
         assert int(defs["ICIKT_COR_" + k]) == v
     assert "icikt_cor_pairs_f64" in _lib.EXPORTS
+
+
+def _fraction_rho(x, y):
+    """rho of exact rationals by the two-pass definition, rounded once (an independent route to exact_pearson's)."""
+    fx, fy = [Fraction(float(v)) for v in x], [Fraction(float(v)) for v in y]
+    m = len(fx)
+    mx, my = sum(fx) / m, sum(fy) / m
+    sxy = sum((a - mx) * (b - my) for a, b in zip(fx, fy))
+    sxx = sum((a - mx) ** 2 for a in fx)
+    syy = sum((b - my) ** 2 for b in fy)
+    if sxx == 0 or syy == 0:
+        return math.nan
+    r2 = sxy * sxy / (sxx * syy)
+    with mpmath.workprec(400):
+        mag = mpmath.sqrt(mpmath.mpf(r2.numerator) / r2.denominator)
+        return float(mag if sxy >= 0 else -mag)
+
+
+def test_exact_pearson_against_fractions():
+    rng = np.random.default_rng(11)
+    one = np.nextafter(1.0, 2.0)
+    cases = [([1.0, 2.0, 3.0], [1.0, 2.0, 3.0]), ([1.0, 2.0, 3.0], [-3.0, -4.0, -5.0]),
+             ([1.0, one, 1.0, one], [0.5, 2.0, -1.0, 3.0]), ([1e300, -1e300, 5e299], [1e-300, 3e-300, -2e-300]),
+             ([1e12 + 0.5, 1e12 - 0.25, 1e12 + 1.0, 1e12], [-1e6 + 1e-6, -1e6, -1e6 - 3e-6, -1e6 + 2e-6]),
+             ([1e250, 0.0, 1.0, -2.0], [1.0, 2.0, 4.0, 8.0])]
+    for _ in range(40):
+        m = int(rng.integers(2, 9))
+        sc = 10.0 ** rng.integers(-300, 301, size=2)
+        off = rng.choice([0.0, 1e6, -1e12, 1e200], size=2)
+        cases.append((off[0] + sc[0] * rng.normal(size=m), off[1] + sc[1] * rng.normal(size=m)))
+    for x, y in cases:
+        x, y = np.asarray(x, float), np.asarray(y, float)
+        want = _fraction_rho(x, y)
+        got = exact_pearson(x, y)
+        assert (math.isnan(got) and math.isnan(want)) or got == want, (x, y, got, want)
+    assert exact_pearson([1.0, 2.0, 3.0], [2.0, 4.0, 6.0]) == 1.0
+    assert exact_pearson([1.0, 2.0, 3.0], [2.0, 0.0, -2.0]) == -1.0
+    assert math.isnan(exact_pearson([1.0, 1.0, 1.0], [1.0, 2.0, 3.0]))
+    assert math.isnan(exact_pearson([5e-324, 5e-324], [1.0, 2.0]))
+
+
+def _compare_exact(X, use):
+    """cor_fast through the numpy path against the exact reference (cor_checker.assert_matches_exact)."""
+    names = _names(X.shape[1])
+    got = cor_fast(X, use=use, colnames=names, return_matrix=False, engine=ENG)["rho"]
+    pi, pj, _ = api.setup_comparisons(names, None, diag_good=False)
+    want, _w = check_pairs(X, pi, pj, "pearson", use == "pairwise.complete.obs", exact=True)
+    assert_matches_exact(got["rho"], got["pvalue"], got["n_values"], want, label=use)
+
+
+@pytest.mark.parametrize("n", [3, 65, 2000, 65536])
+def test_pearson_ill_conditioned_dense(n):
+    _compare_exact(ill_dense(n, n), "everything")
+
+
+@pytest.mark.parametrize("n", [3, 65, 2000, 65536])
+def test_pearson_ill_conditioned_pairwise(n):
+    _compare_exact(ill_pairwise(n, n + 1), "pairwise.complete.obs")
