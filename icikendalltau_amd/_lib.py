@@ -15,9 +15,11 @@ _PKG = os.path.dirname(os.path.abspath(__file__))
 _ROOT = os.path.dirname(_PKG)
 LIB_PATH = os.environ.get("ICIKT_LIB") or os.path.join(_PKG, "libicikt_hip.so")  # ICIKT_LIB: A/B of builds (tools)
 SOURCES = [os.path.join(_PKG, "csrc", f) for f in ("icikt_kernels.hip", "icikt_capi.cpp", "icikt_multi.cpp",
-                                                       "icikt_transfer.cpp", "icikt_cor.hip")]
+                                                       "icikt_transfer.cpp", "icikt_cor.hip",
+                                                       "icikt_diag.hip")]
 HEADERS = [os.path.join(_ROOT, "include", "icikt.h"), os.path.join(_PKG, "csrc", "icikt_device.h"),
-           os.path.join(_PKG, "csrc", "icikt_host.h"), os.path.join(_PKG, "csrc", "icikt_transfer.h")]
+           os.path.join(_PKG, "csrc", "icikt_host.h"), os.path.join(_PKG, "csrc", "icikt_transfer.h"),
+           os.path.join(_PKG, "csrc", "icikt_colsort.h")]
 
 # include/icikt.h
 SUCCESS = 0
@@ -57,7 +59,7 @@ EXPORTS = (
     "icikt_pairs_multi_f64", "icikt_multi_phase_ms", "icikt_multi_debug_set_plan",
     "icikt_matrix_f64", "icikt_matrix_multi_f64", "icikt_multi_rank_phase_ms", "icikt_multi_ranks_used",
     "icikt_debug_step_stats", "icikt_multi_comm_ranks", "icikt_multi_block_bounds", "icikt_cost_blocks",
-    "icikt_cor_pairs_f64",
+    "icikt_cor_pairs_f64", "icikt_col_medians_f64", "icikt_censor_counts_f64", "icikt_rank_order_f64",
 )
 
 
@@ -143,6 +145,11 @@ def lib():
     L.icikt_missingness_f64.argtypes = [c_vp, c_vp, c_i64, c_i64, c_i64, c_vp, c_vp, c_i64, c_vp]
     L.icikt_cor_pairs_f64.argtypes = [c_vp, c_vp, c_i64, c_i64, c_i64, c_vp, c_vp, c_i64, c_int, c_int, c_int, c_int,
                                       c_u32, c_vp, c_vp]
+    L.icikt_col_medians_f64.argtypes = [c_vp, c_vp, c_i64, c_i64, c_i64, c_vp, c_int, c_int, c_u32, c_vp]
+    L.icikt_censor_counts_f64.argtypes = [c_vp, c_vp, c_i64, c_i64, c_i64, c_vp, c_int, c_vp, c_int, c_u32, c_vp, c_vp,
+                                          c_vp, c_vp]
+    L.icikt_rank_order_f64.argtypes = [c_vp, c_vp, c_i64, c_i64, c_i64, c_vp, c_int, c_vp, c_i64, c_u32, c_vp, c_vp,
+                                       c_vp, c_vp, c_vp, c_vp, c_vp]
     L.icikt_selftest.argtypes = [c_vp]
     L.icikt_debug_set_plan.argtypes = [c_vp, ctypes.c_char_p]
     L.icikt_multi_create.argtypes = [ctypes.POINTER(c_int), c_int, c_int, ctypes.POINTER(c_vp)]
@@ -400,6 +407,71 @@ class Context:
                                             METHOD[method], int(bool(pairwise)), ALTERNATIVE[alternative],
                                             int(bool(continuity)), flags, _ptr(out), _ptr(rsn)), "icikt_cor_pairs_f64")
         return out, rsn
+
+    # -- missing-value diagnostics (icikt_col_medians_f64 / icikt_censor_counts_f64 / icikt_rank_order_f64) --------
+    @staticmethod
+    def _diag_input(X, global_na):
+        Xf = np.asfortranarray(X, dtype=np.float64)
+        if Xf.ndim != 2:
+            raise ValueError("X must be 2-D (features x samples)")
+        gna = np.ascontiguousarray([] if global_na is None else np.atleast_1d(global_na), dtype=np.float64)
+        return Xf, gna
+
+    def col_medians(self, X, na_rm=False, global_na=None, flags: int = 0):
+        """stats::median of every column (NaN = NA; global_na: cells the rule excludes as well)."""
+        Xf, gna = self._diag_input(X, global_na)
+        n_feat, n_samp = Xf.shape
+        out = np.empty(n_samp, dtype=np.float64)
+        self._chk(lib().icikt_col_medians_f64(self._h, _ptr(Xf), n_feat, n_samp, max(n_feat, 1), _ptr(gna) if gna.size
+                                              else None, int(gna.size), int(bool(na_rm)), flags, _ptr(out)),
+                  "icikt_col_medians_f64")
+        return out
+
+    def censor_counts(self, X, global_na, cls, n_class: int, flags: int = 0, want_medians: bool = False):
+        """test_left_censorship's per-class counts: (trials [n_class], success [n_class], n_excluded, medians)."""
+        Xf, gna = self._diag_input(X, global_na)
+        n_feat, n_samp = Xf.shape
+        cls_a = np.ascontiguousarray(cls, dtype=np.int32)
+        if cls_a.shape != (n_samp,):
+            raise ValueError("cls must give one class per column")
+        trials = np.zeros(n_class, dtype=np.int64)
+        success = np.zeros(n_class, dtype=np.int64)
+        n_ex = np.zeros(1, dtype=np.int64)
+        med = np.empty(n_samp, dtype=np.float64) if want_medians else None
+        self._chk(lib().icikt_censor_counts_f64(self._h, _ptr(Xf), n_feat, n_samp, max(n_feat, 1),
+                                                _ptr(gna) if gna.size else None, int(gna.size), _ptr(cls_a),
+                                                int(n_class), flags, _ptr(trials), _ptr(success), _ptr(n_ex), _ptr(med)),
+                  "icikt_censor_counts_f64")
+        return trials, success, int(n_ex[0]), med
+
+    def rank_order(self, X, global_na, cols, flags: int = 0, want_data: bool = True, n_feat: int | None = None):
+        """rank_order_data for the columns `cols` of X: dict of n_kept, n_na, median_rank, row_order, col_order and
+        (want_data) original / ordered (n_kept x len(cols)).  n_feat: only the first n_feat rows of X count (X then
+        passes with its own row count as the leading dimension)."""
+        Xf, gna = self._diag_input(X, global_na)
+        ld, n_samp = Xf.shape
+        n_feat = ld if n_feat is None else int(n_feat)
+        ld = max(ld, 1)
+        cols_a = np.ascontiguousarray(cols, dtype=np.int32)
+        n_cols = cols_a.shape[0]
+        n_kept = np.zeros(1, dtype=np.int64)
+        n_na = np.empty(max(n_feat, 1), dtype=np.int32)
+        med = np.empty(max(n_feat, 1), dtype=np.float64)
+        rord = np.empty(max(n_feat, 1), dtype=np.int32)
+        cord = np.empty(max(n_cols, 1), dtype=np.int32)
+        orig = np.empty(max(n_feat * n_cols, 1), dtype=np.float64) if want_data else None
+        ordd = np.empty(max(n_feat * n_cols, 1), dtype=np.float64) if want_data else None
+        self._chk(lib().icikt_rank_order_f64(self._h, _ptr(Xf), n_feat, n_samp, ld, _ptr(gna) if gna.size else None,
+                                             int(gna.size), _ptr(cols_a), n_cols, flags, _ptr(n_kept), _ptr(n_na),
+                                             _ptr(med), _ptr(rord), _ptr(cord), _ptr(orig), _ptr(ordd)),
+                  "icikt_rank_order_f64")
+        k = int(n_kept[0])
+        out = {"n_kept": k, "n_na": n_na[:n_feat], "median_rank": med[:n_feat], "row_order": rord[:k],
+               "col_order": cord[:n_cols]}
+        if want_data:
+            out["original"] = orig[:k * n_cols].reshape((k, n_cols), order="F")
+            out["ordered"] = ordd[:k * n_cols].reshape((k, n_cols), order="F")
+        return out
 
     def pair(self, x, y, perspective="local", alternative="two.sided", continuity=False, flags: int = 0):
         x = np.ascontiguousarray(x, dtype=np.float64)

@@ -62,6 +62,23 @@ class HipEngine:
         """cor_fast's pairs on the device (icikt_cor_pairs_f64): (out3: rho, p-value, n_values; reasons)."""
         return self.ctx.cor_pairs(X, pi, pj, method, pairwise, alternative, continuity)
 
+    def col_medians(self, X, na_rm):
+        """calculate_matrix_medians on the device (icikt_col_medians_f64)."""
+        return self._diag_ctx().col_medians(X, na_rm)
+
+    def censor_counts(self, X, global_na, cls, n_class):
+        """test_left_censorship's per-class counts on the device (icikt_censor_counts_f64): (trials, success,
+        n_excluded)."""
+        trials, success, n_ex, _med = self._diag_ctx().censor_counts(X, global_na, cls, n_class)
+        return trials, success, n_ex
+
+    def rank_order(self, X, global_na, cols):
+        """rank_order_data of one class on the device (icikt_rank_order_f64)."""
+        return self._diag_ctx().rank_order(X, global_na, cols)
+
+    def _diag_ctx(self):
+        return self.ctx
+
     def pairs_complete(self, X, pi, pj):
         """kt_fast(use = "pairwise.complete.obs") on the device: (out4, reasons)."""
         out, _cnt, rsn = self.ctx.pairs_complete(X, pi, pj, "two.sided", False, self.flags)
@@ -117,6 +134,9 @@ class MultiHipEngine(HipEngine):
 
     def missingness(self, X, pi, pj):  # a bitset popcount: one device is plenty
         return self._one().missingness(X, pi, pj)
+
+    def _diag_ctx(self):  # the missing-value diagnostics run on one device
+        return self._one()
 
     def cor_pairs(self, X, pi, pj, method, pairwise, alternative, continuity):  # cor_fast runs on one device
         return self._one().cor_pairs(X, pi, pj, method, pairwise, alternative, continuity)
@@ -711,9 +731,11 @@ def _lbeta(a, b):
     return math.lgamma(p) + math.lgamma(q) - math.lgamma(p + q)
 
 
-def _incbeta_cf(a, b, x, y):
+def _incbeta_cf(a, b, x, y, front=None):
+    """The continued fraction of I_x(a, b) times its front factor x^a y^b / (a B(a, b)) (computed here unless given)."""
     tiny, eps = 1e-300, 1e-16
-    front = math.exp(a * math.log(x) + b * math.log(y) - _lbeta(a, b)) / a
+    if front is None:
+        front = math.exp(a * math.log(x) + b * math.log(y) - _lbeta(a, b)) / a
     d = 1.0 - (a + b) * x / (a + 1.0)
     d = 1.0 / (tiny if abs(d) < tiny else d)
     c, f = 1.0, d
@@ -969,3 +991,318 @@ def cor_fast(x, y=None, use="everything", method="pearson", alternative="two.sid
     cols = {"s1": names_arr[pi], "s2": names_arr[pj], "core": core.astype(np.float64), "rho": rho, "pvalue": pvalue,
             "n_values": n_values}
     return {"rho": pd.DataFrame(cols) if pd is not None else cols, "run_time": t_diff}
+
+
+# --------------------------------------------------------------------------------------------------
+# missing-value diagnostics (R/left_censorship.R, R/rank-ordering.R) -- DESIGN.md section 10
+# --------------------------------------------------------------------------------------------------
+_R_NA_BITS = 0x7FF00000000007A2     # R's NA_real_
+_R_NAN_BITS = 0x7FF8000000000000    # R_NaN
+_LN_SQRT_2PI = 0.918938533204672741780329736406
+
+
+def _bits(b):
+    return float(np.array([b], dtype=np.uint64).view(np.float64)[0])
+
+
+def _stirlerr(n):
+    """log(n!) - log(sqrt(2 pi n) (n / e)^n), n >= 0 (Loader's stirlerr)."""
+    if n == 0:
+        return 0.0
+    if n <= 15:
+        return math.lgamma(n + 1.0) - (n + 0.5) * math.log(n) + n - _LN_SQRT_2PI
+    nn = 1.0 / (n * n)
+    return (1 / 12 - (1 / 360 - (1 / 1260 - (1 / 1680 - nn / 1188) * nn) * nn) * nn) / n
+
+
+def _bd0(x, np_):
+    """x log(x / np) + np - x without cancellation (Loader)."""
+    if abs(x - np_) < 0.1 * (x + np_):
+        v = (x - np_) / (x + np_)
+        s = (x - np_) * v
+        ej = 2 * x * v
+        for j in range(1, 1000):
+            ej *= v * v
+            s1 = s + ej / (2 * j + 1)
+            if s1 == s:
+                return s1
+            s = s1
+        return s
+    return x * math.log(x / np_) + np_ - x
+
+
+def _dbinom(k, n, p):
+    """P(X = k), X ~ Bin(n, p), to a relative accuracy that does not degrade with n (Loader's dbinom_raw)."""
+    q = 1.0 - p
+    if k == 0:
+        return math.exp(n * math.log1p(-p)) if p < 0.5 else math.exp(n * math.log(q))
+    if k == n:
+        return math.exp(n * math.log(p))
+    lc = _stirlerr(n) - _stirlerr(k) - _stirlerr(n - k) - _bd0(k, n * p) - _bd0(n - k, n * q)
+    return math.exp(lc) * math.sqrt(n / (2 * math.pi * k * (n - k)))
+
+
+def pbinom_upper(x, n, p=0.5):
+    """P(X >= x), X ~ Bin(n, p): R's pbinom(x - 1, n, p, lower.tail = FALSE), through the incomplete beta
+    I_p(x, n - x + 1) with its front factor from _dbinom."""
+    x, n = int(x), int(n)
+    if x <= 0:
+        return 1.0
+    if x > n:
+        return 0.0
+    a, b, q = float(x), float(n - x + 1), 1.0 - p
+    if p > (a + 1) / (a + b + 2):
+        return 1.0 - _incbeta_cf(b, a, q, p, front=_dbinom(x - 1, n, p) * p)   # 1 - P(X <= x - 1)
+    return _incbeta_cf(a, b, p, q, front=_dbinom(x, n, p) * q)
+
+
+def qbeta_binom_lower(alpha, x, n):
+    """qbeta(alpha, x, n - x + 1) for 1 <= x <= n: the q with P(Bin(n, q) >= x) = alpha, by safeguarded Newton steps
+    (the derivative of the tail in q is n dbinom(x - 1, n - 1, q))."""
+    lo, hi = 0.0, 1.0
+    q = min(max(x / n - 1.6448536269514722 * math.sqrt(max(x * (n - x), 1) / n ** 3), 1e-300), 1.0 - 1e-16)
+    for _ in range(200):
+        g = pbinom_upper(x, n, q) - alpha
+        if g > 0:
+            hi = q
+        else:
+            lo = q
+        d = n * _dbinom(x - 1, n - 1, q) if n > 1 else 1.0
+        step = g / d if d > 0 else math.inf
+        qn = q - step
+        if not (lo < qn < hi):
+            qn = 0.5 * (lo + hi)
+        if abs(qn - q) <= 2e-16 * q or hi - lo <= 2e-16 * hi:
+            return qn
+        q = qn
+    return q
+
+
+def _binom_test_greater(x, n):
+    """stats::binom.test(x, n, p = 0.5, alternative = "greater")."""
+    if n < 1 or x > n:
+        raise ValueError("'n' must be a positive integer >= 'x'")
+    return {
+        "statistic": int(x), "statistic_name": "number of successes",
+        "parameter": int(n), "parameter_name": "number of trials",
+        "p_value": pbinom_upper(x, n, 0.5),
+        "conf_int": (0.0 if x == 0 else qbeta_binom_lower(0.05, x, n), 1.0), "conf_level": 0.95,
+        "estimate": x / n, "estimate_name": "probability of success",
+        "null_value": 0.5, "alternative": "greater", "method": "Exact binomial test",
+        "data_name": "total_success and total_trials",
+    }
+
+
+def _diag_matrix(data_matrix, colnames, arg):
+    """_as_matrix for the diagnostics, which need no column names: (X, names, row labels or None)."""
+    rows = None
+    if pd is not None and isinstance(data_matrix, pd.DataFrame):
+        rows = data_matrix.index
+    elif colnames is None:
+        colnames = list(range(np.shape(data_matrix)[1])) if np.ndim(data_matrix) == 2 else []
+    X, names = _as_matrix(data_matrix, colnames, arg)
+    return X, names, rows
+
+
+def _class_levels(sample_classes, S, default):
+    """split(., sample_classes) in factor() order: (levels, class index of every column).  Numbers sort numerically,
+    strings as sorted() does (R's locale collation can order mixed-case labels differently)."""
+    if sample_classes is None:
+        labels = [default] * S
+    else:
+        labels = list(np.asarray(sample_classes, dtype=object).ravel())
+        if len(labels) != S:
+            raise ValueError("`sample_classes` must give one class per column")
+    numeric = all(isinstance(v, (int, float, np.integer, np.floating)) and not isinstance(v, (bool, np.bool_))
+                  for v in labels)
+    if not numeric:
+        labels = [str(v) for v in labels]
+    levels = sorted(set(labels))
+    pos = {v: i for i, v in enumerate(levels)}
+    return levels, np.array([pos[v] for v in labels], dtype=np.int32)
+
+
+def _device_rule(X, global_na):
+    """The global_na rule as the device takes it: (X, global_na, host exclusion mask or None).  More than 32 distinct
+    finite values: the host masks X (NaN) and passes NA alone."""
+    vals = [] if global_na is None else [float(v) for v in np.atleast_1d(np.asarray(global_na, dtype=np.float64))]
+    if len({v for v in vals if math.isfinite(v)}) <= _lib.MASK_VALS:
+        return X, vals, None
+    excl = setup_missing_matrix(X, vals)
+    return _masked_fortran(X, excl), [math.nan], excl
+
+
+def _r_median_sorted(v):
+    """R's median of sorted values (no NA): NA when empty, a zero as +0, mean() of the middle two."""
+    m = v.shape[0]
+    if m == 0:
+        return _bits(_R_NA_BITS)
+    if m & 1:
+        return float(v[m // 2]) + 0.0
+    a, b = float(v[m // 2 - 1]), float(v[m // 2])
+    s = a + b
+    if math.isfinite(s):
+        return 0.5 * s + 0.0
+    if math.isfinite(a) and math.isfinite(b):
+        return 0.5 * a + 0.5 * b
+    return _bits(_R_NAN_BITS) if math.isnan(s) else s
+
+
+def _col_medians_numpy(X, na_rm, miss=None):
+    miss = np.isnan(X) if miss is None else miss
+    out = np.empty(X.shape[1])
+    for j in range(X.shape[1]):
+        if miss[:, j].any() and not na_rm:
+            out[j] = _bits(_R_NA_BITS)
+        else:
+            out[j] = _r_median_sorted(np.sort(X[~miss[:, j], j]))
+    return out
+
+
+def _censor_numpy(X, global_na, cls, n_class):
+    excl = setup_missing_matrix(X, global_na)
+    miss = excl | np.isnan(X)
+    med = _col_medians_numpy(X, True, miss)
+    trials = np.zeros(n_class, dtype=np.int64)
+    success = np.zeros(n_class, dtype=np.int64)
+    for k in range(n_class):
+        cols = np.flatnonzero(cls == k)
+        rows = miss[:, cols].any(axis=1)
+        sub, mm, mk = X[rows][:, cols], miss[rows][:, cols], med[cols]
+        valid = ~mm & ~np.isnan(mk)[None, :]
+        with np.errstate(invalid="ignore"):
+            trials[k] = int(valid.sum())
+            success[k] = int((valid & (sub < mk[None, :])).sum())
+    return trials, success, int(excl.sum())
+
+
+def _rank2_na_first(col, miss):
+    """2 * rank(col, na.last = FALSE) with the missing cells `miss` (integers)."""
+    out = np.zeros(col.shape[0], dtype=np.int64)
+    k = int(miss.sum())
+    out[miss] = 2 * np.arange(1, k + 1)
+    v = col[~miss] + 0.0   # -0 ties with 0
+    if v.size:
+        _u, inv, cnt = np.unique(v, return_inverse=True, return_counts=True)
+        start = np.concatenate(([0], np.cumsum(cnt)[:-1]))
+        out[~miss] = 2 * k + 2 * start[inv] + cnt[inv] + 1
+    return out
+
+
+def _rank_order_numpy(X, global_na, cols):
+    Xc = X[:, cols]
+    miss = setup_missing_matrix(Xc, global_na) | np.isnan(Xc)
+    n, m = Xc.shape
+    n_na = miss.sum(axis=1).astype(np.int32)
+    kept = n_na < m
+    rows = np.flatnonzero(kept)
+    sub, msub = Xc[rows], miss[rows]
+    med = np.full(n, _bits(_R_NA_BITS))
+    if rows.size:
+        r2 = np.column_stack([_rank2_na_first(sub[:, j], msub[:, j]) for j in range(m)])
+        med[rows] = np.median(r2 / 2.0, axis=1)
+    row_order = rows[np.argsort(-med[rows], kind="stable")].astype(np.int32)
+    col_order = np.argsort(-msub.sum(axis=0), kind="stable").astype(np.int32)
+    orig = np.array(sub, dtype=np.float64, order="F")
+    orig[msub] = _bits(_R_NA_BITS)
+    return {"n_kept": int(rows.size), "n_na": n_na, "median_rank": med, "row_order": row_order,
+            "col_order": col_order, "original": orig,
+            "ordered": np.asfortranarray(orig[np.searchsorted(rows, row_order)][:, col_order])}
+
+
+def calculate_matrix_medians(in_matrix, use="col", na_rm=False, engine=None):
+    """stats::median of every column (use = "row": of every row) of a numeric matrix (R/left_censorship.R:141-149).
+
+    ``na_rm`` is median's na.rm: without it a column holding NaN gives NA.  An empty column gives NA; the mean of
+    -Inf and Inf gives NaN.  Any ``use`` other than "row" means columns, as ``%in% "row"`` does.  Runs on the MI355X
+    (icikt_col_medians_f64); an ``engine`` without ``col_medians`` gets the same arithmetic in numpy.
+    """
+    X, _names, _rows = _diag_matrix(in_matrix, None, "in_matrix")
+    if use == "row":
+        X = X.T
+    X = np.asfortranarray(X)
+    eng = engine or _default_engine()
+    if hasattr(eng, "col_medians"):
+        return eng.col_medians(X, na_rm)
+    return _col_medians_numpy(X, na_rm)
+
+
+def test_left_censorship(data_matrix, global_na=(float("nan"), float("inf"), 0), sample_classes=None, engine=None):
+    """Binomial test of left censorship (R/left_censorship.R:35-128).
+
+    A cell is missing when it is NaN or ``global_na`` excludes it (setup_missing_matrix).  Per class of
+    ``sample_classes`` (default: one class "A"; classes in factor() order -- numbers numerically, strings as sorted()
+    orders them, which R's locale collation can differ from for mixed-case labels), over the rows with a missing cell:
+    ``trials`` counts the non-missing cells compared with their column's median (NA removed, over all rows of the
+    column), ``success`` those below it.  Returns ``{"values": data.frame(trials, success, class), "binomial_test":
+    binom.test(sum(success), sum(trials), p = 0.5, alternative = "greater")}``, or None (with a message) when the
+    ``global_na`` rule excludes nothing.  The counts run on the MI355X (icikt_censor_counts_f64); an ``engine`` without
+    ``censor_counts`` gets the same arithmetic in numpy.
+    """
+    X, _names, _rows = _diag_matrix(data_matrix, None, "data_matrix")
+    levels, cls = _class_levels(sample_classes, X.shape[1], "A")
+    Xd, gna, excl = _device_rule(np.asfortranarray(X), global_na)
+    eng = engine or _default_engine()
+    if hasattr(eng, "censor_counts"):
+        trials, success, n_ex = eng.censor_counts(Xd, gna, cls, len(levels))
+    else:
+        trials, success, n_ex = _censor_numpy(Xd, gna, cls, len(levels))
+    if excl is not None:
+        n_ex = int(excl.sum())
+    if n_ex == 0:
+        print("i `data_matrix` has no missing values, returning NULL")
+        return None
+    cols = {"trials": np.asarray(trials, dtype=np.int64), "success": np.asarray(success, dtype=np.int64),
+            "class": np.array([str(v) for v in levels], dtype=object)}
+    values = pd.DataFrame(cols) if pd is not None else cols
+    return {"values": values, "binomial_test": _binom_test_greater(int(np.sum(success)), int(np.sum(trials)))}
+
+
+test_left_censorship.__test__ = False   # a library function, not a pytest test
+
+
+def rank_order_data(data_matrix, global_na=(float("nan"), float("inf"), 0), sample_classes=None, colnames=None,
+                    engine=None):
+    """Rank-ordered view of the missing values (R/rank-ordering.R:15-73).
+
+    Per class of ``sample_classes`` (default: one class "rmf_abcd"): missing cells (NaN or excluded by ``global_na``)
+    become NA, rows missing in every column of the class are dropped, each column is ranked with
+    rank(x, na.last = FALSE), and the rows are ordered by their median rank (decreasing) and the columns by their
+    share of NA (decreasing); both orders are stable.  A class returns ``{"original", "ordered", "n_na_rank":
+    data.frame(n_na, median_rank[, split]), "row_order", "col_order"}`` -- the last two 0-based, an addition over the
+    reference -- or None when no row is left.  One class returns its element, several a dict in class order.  Columns
+    are split by position (the reference splits colnames(), which fails without column names).  Runs on the MI355X
+    (icikt_rank_order_f64, one call per class); an ``engine`` without ``rank_order`` gets the same arithmetic in numpy.
+    """
+    X, names, rows = _diag_matrix(data_matrix, colnames, "data_matrix")
+    levels, cls = _class_levels(sample_classes, X.shape[1], "rmf_abcd")
+    Xd, gna, _excl = _device_rule(np.asfortranarray(X), global_na)
+    eng = engine or _default_engine()
+    row_labels = np.asarray(rows) if rows is not None else np.arange(X.shape[0])
+    out = {}
+    for k, level in enumerate(levels):
+        cols = np.flatnonzero(cls == k).astype(np.int32)
+        if hasattr(eng, "rank_order"):
+            r = eng.rank_order(Xd, gna, cols)
+        else:
+            r = _rank_order_numpy(Xd, gna, cols)
+        if r["n_kept"] == 0:
+            out[level] = None
+            continue
+        kept = np.flatnonzero(r["n_na"] < len(cols))
+        cnames = [names[j] for j in cols]
+        n_na_rank = {"n_na": r["n_na"][kept], "median_rank": r["median_rank"][kept]}
+        if level != "rmf_abcd":
+            n_na_rank["split"] = np.array([str(level)] * kept.size, dtype=object)
+        if pd is not None:
+            original = pd.DataFrame(r["original"], index=row_labels[kept], columns=cnames)
+            ordered = pd.DataFrame(r["ordered"], index=row_labels[r["row_order"]],
+                                   columns=[cnames[j] for j in r["col_order"]])
+            n_na_rank = pd.DataFrame(n_na_rank, index=row_labels[kept])
+        else:
+            original, ordered = r["original"], r["ordered"]
+        out[level] = {"original": original, "ordered": ordered, "n_na_rank": n_na_rank,
+                      "row_order": np.asarray(r["row_order"]), "col_order": np.asarray(r["col_order"])}
+    if len(out) == 1:
+        return next(iter(out.values()))
+    return out

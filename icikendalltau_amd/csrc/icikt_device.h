@@ -247,6 +247,34 @@ hipError_t launch_cor_spearman_pw(const CorPrep& cp, const int32_t* pi, const in
 // prho_upper: the exact upper-tail permutation counts of Spearman's S for n = 2 .. 9 (cor_prho_table)
 hipError_t launch_cor_epilogue(const CorAcc* acc, int64_t P, int method, int pairwise, int alternative, int continuity,
                                const uint32_t* prho_upper, double* out3, int32_t* reasons, hipStream_t s);
+// ---- missing-value diagnostics (icikt_diag.hip) ----
+// per-column pass: the rule, counts, sort, median; rank mode (rank2 != nullptr) the doubled ranks
+struct DiagCol {
+  const double* X;   // the matrix on the device
+  int64_t ld, n;     // leading dimension, rows
+  int S;             // columns
+  MaskSpec ms;       // global_na rule (a NaN is missing whatever it holds)
+  int na_rm;         // 0: a column with a missing cell has median NA
+  double* median;    // [S] median of the non-missing values, NA_real_ / R_NaN as R's median gives
+  int32_t* nmiss;    // [S] missing cells (NaN or excluded)
+  int32_t* nexcl;    // [S] cells the rule excludes
+  const uint8_t* kept;   // rank mode: [n] row kept (not missing in every column)
+  int32_t* rank2;    // rank mode: n x S doubled rank(x, na.last = FALSE) over the kept rows (dropped rows: 0); else nullptr
+  uint64_t* keys;    // sort scratch, np2 per workgroup
+  int32_t *idx, *gs;
+  int np2;
+};
+hipError_t launch_diag_col(const DiagCol& dc, int blocks, hipStream_t s);
+// out3[3 k ..]: trials, successes, missing cells of class k (zeroed by the caller)
+hipError_t launch_diag_censor(const double* X, int64_t ld, int64_t n, const MaskSpec& ms, const int32_t* cols,
+                              const int32_t* off, int n_class, const double* median, unsigned long long* out3,
+                              hipStream_t s);
+hipError_t launch_diag_rowmiss(const double* X, int64_t n, int n_cols, const MaskSpec& ms, int32_t* n_na,
+                               uint8_t* kept, unsigned long long* n_kept, hipStream_t s);
+hipError_t launch_diag_median_rank(const int32_t* rank2, int64_t n, int n_cols, const uint8_t* kept, double* med,
+                                   hipStream_t s);
+hipError_t launch_diag_gather(const double* X, int64_t n, const MaskSpec& ms, const int32_t* rows, int64_t n_out,
+                              const int32_t* colsel, int n_cols, double* out, hipStream_t s);
 hipError_t launch_selftest(uint32_t* d_out, hipStream_t s);
 hipError_t read_step_stats(unsigned long long* out24, int reset);
 

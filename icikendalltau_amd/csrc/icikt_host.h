@@ -111,6 +111,14 @@ struct icikt_ctx {
     bool prho_ready = false;
   } cor;
 
+  // missing-value diagnostics (icikt_col_medians_f64, icikt_censor_counts_f64, icikt_rank_order_f64)
+  struct DiagBufs {
+    DevBuf<double> median, medrank, out;
+    DevBuf<int32_t> nmiss, nexcl, nna, rank2, idx, gs, lists;   // lists: the host-built row / column index lists
+    DevBuf<uint8_t> kept;
+    DevBuf<unsigned long long> keys, red;
+  } diag;
+
   // launch-plan overrides of the pair kernel (icikt_debug_set_plan; -1 = the library's choice)
   struct PlanOverride {
     int np = -1, pend = -1, wpb = -1, half = -1, grid_mult = -1, grid_cap = -1, hyb = -1;

@@ -184,3 +184,63 @@ cor_fast_gpu = function(x, y = NULL, use = "everything", method = "pearson", alt
   pvalue_matrix[one_way] = cmp$pvalue; pvalue_matrix[back_way] = cmp$pvalue
   list(rho = rho_matrix, pvalue = pvalue_matrix, run_time = t_diff)
 }
+
+# ---- missing-value diagnostics (R/left_censorship.R, R/rank-ordering.R) over icikt_rglue_diag.c (a DLL of its own:
+# dyn.load("icikt_rglue_diag.so")).  Same arguments, defaults and return shapes as the reference; the counts, medians
+# and ranks come from the device.  Columns are split by position (the reference splits colnames()).
+.icikt_device_rule = function(data_matrix, global_na) {
+  # more than 32 distinct finite global_na values: mask on the host and pass NA alone
+  finite = unique(global_na[is.finite(global_na)])
+  if (length(finite) <= 32) return(list(x = data_matrix, global_na = as.double(global_na), n_excluded = NULL))
+  missing_loc = setup_missing_matrix(data_matrix, global_na)
+  data_matrix[missing_loc] = NA
+  list(x = data_matrix, global_na = NA_real_, n_excluded = sum(missing_loc))
+}
+
+calculate_matrix_medians_gpu = function(in_matrix, use = "col", na.rm = FALSE, device = 0L) {
+  if (use %in% "row") in_matrix = t(in_matrix)
+  storage.mode(in_matrix) = "double"
+  .Call("icikt_R_col_medians", in_matrix, NULL, isTRUE(na.rm), as.integer(device))
+}
+
+test_left_censorship_gpu = function(data_matrix, global_na = c(NA, Inf, 0), sample_classes = NULL, device = 0L) {
+  if (inherits(data_matrix, "data.frame")) data_matrix = as.matrix(data_matrix)
+  storage.mode(data_matrix) = "double"
+  if (is.null(sample_classes)) sample_classes = rep("A", ncol(data_matrix))
+  cls = factor(sample_classes)
+  rule = .icikt_device_rule(data_matrix, global_na)
+  res = .Call("icikt_R_censor_counts", rule$x, rule$global_na, as.integer(cls), as.integer(device))
+  n_excluded = if (is.null(rule$n_excluded)) res$n_excluded else rule$n_excluded
+  if (n_excluded == 0) {
+    arg = rlang::caller_arg(data_matrix)
+    cli::cli_inform(message = c("i" = "{.arg {arg}} has no missing values, returning NULL"))
+    return(NULL)
+  }
+  split_counts = data.frame(trials = res$trials, success = res$success, class = levels(cls))
+  binom_res = stats::binom.test(sum(split_counts$success), sum(split_counts$trials), p = 0.5, alternative = "greater")
+  list(values = split_counts, binomial_test = binom_res)
+}
+
+rank_order_data_gpu = function(data_matrix, global_na = c(NA, Inf, 0), sample_classes = NULL, device = 0L) {
+  if (inherits(data_matrix, "data.frame")) data_matrix = as.matrix(data_matrix)
+  storage.mode(data_matrix) = "double"
+  if (is.null(sample_classes)) sample_classes = rep("rmf_abcd", ncol(data_matrix))
+  rule = .icikt_device_rule(data_matrix, global_na)
+  split_classes = split(seq_len(ncol(data_matrix)), sample_classes)
+  split_ranks = lapply(names(split_classes), function(split_id) {
+    cols = split_classes[[split_id]]
+    res = .Call("icikt_R_rank_order", rule$x, rule$global_na, as.integer(cols), as.integer(device))
+    if (length(res$row_order) == 0) return(NULL)
+    kept = sort(res$row_order)
+    original = res$original
+    dimnames(original) = list(rownames(data_matrix)[kept], colnames(data_matrix)[cols])
+    ordered = res$ordered
+    dimnames(ordered) = list(rownames(data_matrix)[res$row_order], colnames(data_matrix)[cols][res$col_order])
+    n_na_rank = data.frame(n_na = res$n_na, median_rank = res$median_rank)
+    if (!(split_id %in% "rmf_abcd")) n_na_rank$split = split_id
+    list(original = original, ordered = ordered, n_na_rank = n_na_rank)
+  })
+  names(split_ranks) = names(split_classes)
+  if (length(split_ranks) == 1) split_ranks = split_ranks[[1]]
+  split_ranks
+}

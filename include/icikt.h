@@ -310,6 +310,36 @@ int icikt_cor_pairs_f64(icikt_ctx *ctx, const double *X, int64_t n_feat, int64_t
                         const int32_t *pi, const int32_t *pj, int64_t n_pairs, int method, int pairwise,
                         int alternative, int continuity, uint32_t flags, double *out3, int32_t *reasons);
 
+/* Missing-value diagnostics (R/left_censorship.R, R/rank-ordering.R).  X as everywhere: column-major
+ * n_feat x n_samp, leading dimension ld.  A cell is missing when it is NaN or when setup_missing_matrix(global_na)
+ * (R/utils.R:1-23) excludes it: global_na as in icikt_matrix_f64 (NaN = NA, +-Inf = Inf, at most 32 distinct finite
+ * values, ICIKT_E_INVALID beyond: the front-ends mask such a matrix themselves and pass NaN).  n_feat up to
+ * ICIKT_MAX_FEATURES_WIDE.  flags: ICIKT_FLAG_TIMING (icikt_kernel_ms: ICIKT_K_PREPARE the matrix's H2D, ICIKT_K_PAIRS
+ * the column and row passes, ICIKT_K_EPILOGUE the gathers of rank_order), ICIKT_FLAG_HOST_PINNED.  NA results carry
+ * R's NA_real_ bit pattern, NaN results R_NaN's (0x7FF8000000000000); a zero median is +0. */
+/* medians[j]: stats::median of column j (calculate_matrix_medians(use = "col")); na_rm = 0: NA when the column has a
+ * missing cell; NA for a column without values. */
+int icikt_col_medians_f64(icikt_ctx *ctx, const double *X, int64_t n_feat, int64_t n_samp, int64_t ld,
+                          const double *global_na, int n_global_na, int na_rm, uint32_t flags, double *medians);
+/* test_left_censorship's counts for every class at once: cls[j] in [0, n_class) is column j's class.  Per class, over the
+ * rows with a missing cell among its columns: trials[k] = cells whose x < median(column, na.rm = TRUE) is not NA,
+ * success[k] = cells where it is TRUE.  n_excluded: the cells the global_na rule excludes (the reference's early
+ * return).  medians (optional, n_samp): the column medians the comparison used. */
+int icikt_censor_counts_f64(icikt_ctx *ctx, const double *X, int64_t n_feat, int64_t n_samp, int64_t ld,
+                            const double *global_na, int n_global_na, const int32_t *cls, int n_class, uint32_t flags,
+                            int64_t *trials, int64_t *success, int64_t *n_excluded, double *medians);
+/* rank_order_data for one class, the columns cols[0 .. n_cols) (only they cross PCIe).  Rows missing in every listed
+ * column are dropped; *n_kept rows stay.  Per row of X (n_feat): n_na = missing cells, median_rank = median of the row's
+ * rank(x, na.last = FALSE) over the kept rows (NA_real_ for a dropped row).  row_order[0 .. n_kept): row indices of X,
+ * order(median_rank, decreasing = TRUE) over the kept rows; col_order[n_cols]: positions in cols,
+ * order(colMeans(is.na), decreasing = TRUE); both stable.  original / ordered (optional, n_kept x n_cols column-major,
+ * room for n_feat x n_cols): the kept rows in row order / in row_order and col_order; missing cells NA_real_, the others
+ * bitwise copies. */
+int icikt_rank_order_f64(icikt_ctx *ctx, const double *X, int64_t n_feat, int64_t n_samp, int64_t ld,
+                         const double *global_na, int n_global_na, const int32_t *cols, int64_t n_cols, uint32_t flags,
+                         int64_t *n_kept, int32_t *n_na, double *median_rank, int32_t *row_order, int32_t *col_order,
+                         double *original, double *ordered);
+
 /* pairwise_completeness() arithmetic (R/kendalltau.R:611-629): missingness[p] = #rows missing in
  * either column, from a host matrix whose missing cells are NaN.  Self pairs allowed. */
 int icikt_missingness_f64(icikt_ctx *ctx, const double *X, int64_t n_feat, int64_t n_samp, int64_t ld,
