@@ -1,114 +1,25 @@
 """The missing-value diagnostics on the MI355X (icikt_col_medians_f64, icikt_censor_counts_f64, icikt_rank_order_f64)
-against an independent restatement in this file: numpy's sort for the medians, scipy's rankdata for the ranks, numpy's
-stable argsort for the orders.  Every comparison is exact: medians and copied cells bit for bit, counts, ranks and
-orders equal."""
+against an independent restatement (tests/diag_checker.py): numpy's sort for the medians, one sort per column block for
+the ranks (pinned to scipy's rankdata), numpy's stable argsort for the orders.  Every comparison is exact: medians and
+copied cells bit for bit, counts, ranks and orders equal."""
 import math
 import os
 
 import numpy as np
 import pytest
-import scipy.stats as st
 
 import icikendalltau_amd as ik
 from icikendalltau_amd import _lib
+from tests.diag_checker import DEFAULT_NA, NA_BITS, bits, ref_col_medians, ref_censor, ref_rank_order, rule
 
 pytestmark = pytest.mark.gpu
 
 GOLDEN = os.path.join(os.path.dirname(__file__), "golden")
-NA_BITS = np.uint64(0x7FF00000000007A2)
-NAN_BITS = np.uint64(0x7FF8000000000000)
-DEFAULT_NA = (math.nan, math.inf, 0.0)
 
 
 @pytest.fixture(scope="module")
 def ctx():
     return _lib.default_context()
-
-
-def bits(a):
-    return np.ascontiguousarray(a, dtype=np.float64).view(np.uint64)
-
-
-def rule(X, gna):
-    """setup_missing_matrix(X, gna) | is.na(X)"""
-    miss = np.isnan(X).copy()
-    ex = np.zeros(X.shape, dtype=bool)
-    for v in gna:
-        if math.isnan(v):
-            ex |= np.isnan(X)
-        elif math.isinf(v):
-            ex |= np.isinf(X)
-        else:
-            ex |= X == v
-    return miss | ex, ex
-
-
-def ref_median(v):
-    """R's median of the values v (no NA): NA bits when empty, +0 for a zero, NaN bits for mean(-Inf, Inf)."""
-    v = np.sort(v)
-    m = v.size
-    if m == 0:
-        return NA_BITS
-    if m % 2:
-        r = v[m // 2] + 0.0
-    else:
-        a, b = float(v[m // 2 - 1]), float(v[m // 2])
-        with np.errstate(over="ignore", invalid="ignore"):
-            s = np.float64(a) + np.float64(b)
-        r = 0.5 * s if np.isfinite(s) else (0.5 * a + 0.5 * b if np.isfinite(a) and np.isfinite(b) else s)
-        r = r + 0.0
-        if np.isnan(r):
-            return NAN_BITS
-    return np.array([r]).view(np.uint64)[0]
-
-
-def ref_col_medians(X, miss, na_rm):
-    out = np.empty(X.shape[1], dtype=np.uint64)
-    for j in range(X.shape[1]):
-        out[j] = NA_BITS if (miss[:, j].any() and not na_rm) else ref_median(X[~miss[:, j], j])
-    return out
-
-
-def ref_censor(X, gna, cls, n_class):
-    miss, ex = rule(X, gna)
-    med = ref_col_medians(X, miss, True).view(np.float64)
-    tr, su = np.zeros(n_class, np.int64), np.zeros(n_class, np.int64)
-    for k in range(n_class):
-        cols = np.flatnonzero(cls == k)
-        rows = miss[:, cols].any(axis=1)
-        for j in cols:
-            if np.isnan(med[j]):
-                continue
-            x = X[rows, j][~miss[rows, j]]
-            tr[k] += x.size
-            su[k] += int((x < med[j]).sum())
-    return tr, su, int(ex.sum()), med
-
-
-def ref_rank_order(X, gna, cols):
-    Xc = X[:, cols]
-    miss, _ = rule(Xc, gna)
-    n, m = Xc.shape
-    n_na = miss.sum(axis=1)
-    kept = np.flatnonzero(n_na < m)
-    med = np.full(n, np.nan)
-    ranks = np.zeros((kept.size, m))
-    for j in range(m):
-        mk = miss[kept, j]
-        k = int(mk.sum())
-        ranks[mk, j] = np.arange(1, k + 1)
-        if (~mk).any():
-            ranks[~mk, j] = k + st.rankdata(Xc[kept, j][~mk] + 0.0, method="average")
-    if kept.size:
-        med[kept] = np.median(ranks, axis=1)
-    row_order = kept[np.argsort(-med[kept], kind="stable")]
-    col_order = np.argsort(-miss[kept].sum(axis=0), kind="stable")
-    orig = Xc[kept].copy()
-    ob = orig.view(np.uint64)
-    ob[miss[kept]] = NA_BITS
-    pos = np.searchsorted(kept, row_order)
-    return dict(n_kept=kept.size, n_na=n_na, median_rank=med, row_order=row_order, col_order=col_order,
-                original=orig, ordered=orig[pos][:, col_order], ranks=ranks)
 
 
 def check_medians(ctx, X, na_rm):
