@@ -4,6 +4,7 @@
     python bench.py --gpus N --steps K --warmup W [--config c2|c3|c4|c5]
     python bench.py --gpus N --launcher inlib     one process, N GPUs behind ONE C call (icikt_pairs_multi_f64)
     python bench.py ... --dump-outputs DIR        also write the last timed step's results as DIR/*.npy (see dump_outputs)
+    python bench.py ... --full                    also everything measured and checked beside the headline figure (below)
 
 `python bench.py --gpus N` runs AS TYPED for N = 1, 2, 4, 8: with N > 1 and no WORLD_SIZE in the environment this
 process -- before it imports torch or touches a GPU -- starts `python -m torch.distributed.run --nnodes=1
@@ -27,10 +28,16 @@ One "step" = one full pass of the hot path over the matrix, input already reside
   contiguous block of the combn-ordered pair list (the reference's `core` chunks, R/kendalltau.R:250-255) -> K2
   epilogue -> (N > 1) RCCL gather of the P/N x 4 results to rank 0.
 value = pairs of the whole job / wall time (max over ranks); total work is fixed, so scaling = strong.
-Beside it, timed the same way (K steps, mean): `pcie_inclusive` -- the host-buffer entry icikt_pairs_f64, i.e. the metric
-as SURVEY.md section 8(d) words it (H2D of the matrix, kernels, D2H of the results) -- and `full_matrix_wall_ms` -- the
-icikt_matrix_f64 call that returns the five S x S matrices of ici_kendalltau().
-Exit status is non-zero when the results disagree with the oracle sample (a wrong line is not a bench line).
+
+A plain run does what that figure needs and no more: set-up, warm-up, the K timed steps, --dump-outputs, the JSON line
+(with the per-phase and per-kernel times the timed steps themselves recorded).  --full adds, after the timed region and
+without touching it, every leg that takes runs of its own: the oracle check of the results (`check`; the exit status is
+non-zero when they disagree: a wrong line is not a bench line) and the CPU baseline on the same sample, the counter passes
+behind `roofline` (child rocprofv3 runs), and, timed the same way (K steps, mean), `pcie_inclusive` -- the host-buffer
+entry icikt_pairs_f64, i.e. the metric as SURVEY.md section 8(d) words it (H2D of the matrix, kernels, D2H of the
+results) -- and `full_matrix_wall_ms` -- the icikt_matrix_f64 call that returns the five S x S matrices of
+ici_kendalltau() --, the Python front-end's end-to-end call, the c5 subset legs and the single-core CPU latencies.
+--cpu-sample, --no-extras, --pmc and --save-pmc shape those legs, so they only matter under --full.
 """
 from __future__ import annotations
 
@@ -509,9 +516,6 @@ def run_inlib(args, cfg):
         out, _c, _r = m.pairs(X, perspective="global", want_counts=False)
     elapsed = time.perf_counter() - t0
     dumped = dump_outputs(args.dump_outputs, {"global": out}) if args.dump_outputs else None
-    m.pairs(X, perspective="global", want_counts=False, flags=_lib.FLAG_TIMING)
-    phases = m.phase_ms()
-    ranks = m.rank_phase_ms()[:max(1, m.ranks_used)]
     line = {
         "metric": "column-pairs/s (+ full-matrix wall time) at 10k feat x 1k samp",
         "value": P_total * args.steps / elapsed, "unit": "column-pairs/s", "n_gpus": args.gpus, "steps": args.steps,
@@ -523,12 +527,15 @@ def run_inlib(args, cfg):
                    "pairs": P_total, "n_feat": n, "n_samp": S, "exchange": "rccl" if m.uses_rccl else "copy"},
         "rccl_ranks": m.comm_ranks,          # ncclCommCount of the handle's communicator (0: device copies, no communicator)
         "ranks_used": m.ranks_used,
-        "phase_ms_synced": phases,
-        "rank_phase_ms": spread(ranks, _lib.MULTI_PHASES + ("wait",)),
     }
     if dumped:
         line["dump_outputs"] = dumped
-    if args.cpu_sample > 0:
+    if args.full:
+        # the phase times take a call of their own (FLAG_TIMING synchronises between the phases)
+        m.pairs(X, perspective="global", want_counts=False, flags=_lib.FLAG_TIMING)
+        line["phase_ms_synced"] = m.phase_ms()
+        line["rank_phase_ms"] = spread(m.rank_phase_ms()[:max(1, m.ranks_used)], _lib.MULTI_PHASES + ("wait",))
+    if args.full and args.cpu_sample > 0:
         _b, sel, ref_out, ref_cnt = cpu_baseline(X, P_total, min(args.cpu_sample, 2000))
         line["check"] = check_against_oracle(out[sel], cnt[sel] if cnt is not None else None, ref_out, ref_cnt)
     m.close()
@@ -553,6 +560,10 @@ def main(argv=None):
     ap.add_argument("--n-samp", type=int, default=None)
     ap.add_argument("--n-na", type=int, default=None)
     ap.add_argument("--seed", type=int, default=None)
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also run every leg beside the headline figure: oracle check + CPU baseline, "
+                         "roofline counter passes, the PCIe-inclusive / full-matrix / end-to-end legs (the options below "
+                         "shape those legs and do nothing without --full)")
     ap.add_argument("--cpu-sample", type=int, default=None, help="pairs timed on the CPU baseline (0 = skip)")
     ap.add_argument("--no-extras", action="store_true", help="skip the PCIe-inclusive / end-to-end legs")
     ap.add_argument("--pmc", choices=("live", "record", "off"), default="live",
@@ -567,6 +578,8 @@ def main(argv=None):
         raise SystemExit("--gpus must be >= 1")
     if (args.steps is not None and args.steps < 1) or (args.warmup is not None and args.warmup < 0):
         raise SystemExit("--steps must be >= 1 and --warmup >= 0")
+    if args.save_pmc and not args.full:
+        raise SystemExit("--save-pmc needs --full: a plain run takes no counters")
     if args.dump_outputs:
         # the ranks of a self-launch run in ROOT: they get the directory as the caller meant it (the last one given wins)
         args.dump_outputs = os.path.abspath(args.dump_outputs)
@@ -731,11 +744,13 @@ def main(argv=None):
         #  step together process P_local pairs, so the step's K1 time is what the bytes are divided by)
         k1_ms, k1_n = k_ms["pairs"]
         k1_avg_s = (k1_ms / args.steps) / 1e3
-        # counters of the dominant kernel: measured with the run (child rocprofv3 passes, after the timed region), or the
-        # committed record IF it was taken on this source; otherwise null + a note, never a stale constant
+        # counters of the dominant kernel (--full): measured with the run (child rocprofv3 passes, after the timed region), or
+        # the committed record IF it was taken on this source; otherwise null + a note, never a stale constant
         pmc, pmc_source, pmc_note = None, "none", None
         std_workload = all(cfg[k] == CONFIGS[args.config][k] for k in ("n_feat", "n_samp", "n_na", "seed")) and world == 1
-        if args.pmc != "off" and std_workload:
+        if not args.full:
+            pmc_note = "counters are taken under --full only"
+        elif args.pmc != "off" and std_workload:
             if args.pmc == "live":
                 try:
                     pmc = collect_pmc(args.config)
@@ -780,7 +795,7 @@ def main(argv=None):
         }
         if dumped:
             line["dump_outputs"] = dumped
-        if world == 1 and args.cpu_sample > 0:
+        if args.full and world == 1 and args.cpu_sample > 0:
             base, sel, ref_out, ref_cnt = cpu_baseline(X, P_total, args.cpu_sample)
             line["cpu_baseline"] = base
             # the sampled pairs once more through the counts-carrying entry: integers bit-exact, doubles <= 1e-10;
@@ -802,7 +817,7 @@ def main(argv=None):
                 line["check"]["local_max_abs_diff"] = d
                 line["check"]["ok"] = line["check"]["ok"] and d <= ATOL
             ctx.set_pairs_combn(S, begin, end)
-        if distributed:
+        if args.full and distributed:
             # the assembled result: rank blocks concatenated in combn order (no NaN may be left in real pairs)
             full = sharding.assemble(gathered, P_total, n_each).cpu().numpy()
             chk = {"assembled_pairs": int(full.shape[0]), "nan_rows": int(np.isnan(full[:, 0]).sum())}
@@ -820,7 +835,7 @@ def main(argv=None):
                 line["check"].update(chk)
             else:
                 line["check"] = chk
-        if not distributed and not args.no_extras:
+        if args.full and not distributed and not args.no_extras:
             extras(line, args, cfg, X, ctx, dev)
         status = 0 if line.get("check", {}).get("ok", True) else 1
         print(json.dumps(line), flush=True)
@@ -834,7 +849,7 @@ def main(argv=None):
 
 
 def extras(line, args, cfg, X, ctx, dev):
-    """N = 1 only, after the resident timed region: the figures SURVEY.md section 8(d) asks for beside the metric, each
+    """--full, N = 1 only, after the resident timed region: the figures SURVEY.md section 8(d) asks for beside the metric, each
     over K steps (mean, not a best-of)."""
     import torch
     from icikendalltau_amd import _lib, api

@@ -318,6 +318,19 @@ def test_bench_self_launch_command_line():
     assert r.returncode != 0 and "invalid choice" in r.stderr
 
 
+def test_bench_full_option():
+    """bench.py --full: the option exists (off by default: a plain run is the headline figure alone), the self-launching
+    parent hands it on to its ranks, and an option that only means something with it says so instead of being ignored."""
+    import subprocess
+    import sys
+    import bench
+    r = subprocess.run([sys.executable, "bench.py", "--help"], cwd=bench.ROOT, capture_output=True, text=True)
+    assert r.returncode == 0 and "--full" in r.stdout
+    assert bench.child_command(["--gpus", "2", "--full"], 2, 29612)[11:] == ["--gpus", "2", "--full"]
+    r = subprocess.run([sys.executable, "bench.py", "--gpus", "1", "--save-pmc"], cwd=bench.ROOT, capture_output=True, text=True)
+    assert r.returncode != 0 and "--full" in r.stderr and r.stdout == ""
+
+
 def test_cost_weighted_block_cut_arithmetic():
     """icikt_cost_blocks (the cut behind ICIKT_FLAG_BALANCE_COST; host arithmetic of the C library, no device): against a
     brute-force walk over the pairs -- block k begins with the first pair whose preceding pairs cost >= total k / G --
