@@ -14,12 +14,13 @@ import numpy as np
 _PKG = os.path.dirname(os.path.abspath(__file__))
 _ROOT = os.path.dirname(_PKG)
 LIB_PATH = os.environ.get("ICIKT_LIB") or os.path.join(_PKG, "libicikt_hip.so")  # ICIKT_LIB: A/B of builds (tools)
-SOURCES = [os.path.join(_PKG, "csrc", f) for f in ("icikt_kernels.hip", "icikt_capi.cpp", "icikt_multi.cpp",
-                                                       "icikt_transfer.cpp", "icikt_cor.hip",
+SOURCES = [os.path.join(_PKG, "csrc", f) for f in ("icikt_kernels.hip", "icikt_prepass.hip", "icikt_epilogue.hip",
+                                                       "icikt_capi.cpp", "icikt_capi_cor.cpp", "icikt_capi_diag.cpp",
+                                                       "icikt_multi.cpp", "icikt_transfer.cpp", "icikt_cor.hip",
                                                        "icikt_diag.hip")]
 HEADERS = [os.path.join(_ROOT, "include", "icikt.h"), os.path.join(_PKG, "csrc", "icikt_device.h"),
-           os.path.join(_PKG, "csrc", "icikt_host.h"), os.path.join(_PKG, "csrc", "icikt_transfer.h"),
-           os.path.join(_PKG, "csrc", "icikt_colsort.h")]
+           os.path.join(_PKG, "csrc", "icikt_wave.h"), os.path.join(_PKG, "csrc", "icikt_host.h"),
+           os.path.join(_PKG, "csrc", "icikt_transfer.h"), os.path.join(_PKG, "csrc", "icikt_colsort.h")]
 
 # include/icikt.h
 SUCCESS = 0

@@ -1,7 +1,10 @@
-// icikt_capi.cpp -- host side of the C ABI declared in include/icikt.h.
+// icikt_capi.cpp -- host side of the C ABI declared in include/icikt.h: the pair engine.
 //
-// Owns the HIP device/stream/workspaces of a context and sequences the three kernels of
-// icikt_kernels.hip.  There is deliberately NO CPU implementation of the arithmetic here: when no
+// Owns the HIP device/stream/workspaces of a context and sequences the pre-pass (icikt_prepass.hip), the pair kernels
+// (icikt_kernels.hip) and the epilogue and assembly (icikt_epilogue.hip): the context, the launch plan of the pair kernel
+// (plan_k1, matrix_tied, the task lists, launch_pair_tasks), the prepare / run / pairs / matrix / complete / missingness
+// entries, the debug hooks and the self-test.  cor_fast's entry is in icikt_capi_cor.cpp, the missing-value diagnostics'
+// in icikt_capi_diag.cpp.  There is deliberately NO CPU implementation of the arithmetic here: when no
 // HIP device is usable every entry point fails with ICIKT_E_NO_DEVICE / ICIKT_E_HIP.
 #include <hip/hip_runtime.h>
 
@@ -25,25 +28,6 @@ using icikt::PrepView;
 static_assert(ICIKT_CNT_FIELDS == icikt::ICIKT_CNT_FIELDS_, "counts record layout");
 static_assert(ICIKT_PERSPECTIVE_LOCAL == icikt::ICIKT_PERSPECTIVE_LOCAL_, "perspective code");
 
-namespace icikt {
-namespace host {
-
-int fail(icikt_ctx* c, int code, const std::string& msg) {
-  if (c) c->err = msg;
-  return code;
-}
-
-int use_device(icikt_ctx* c) {
-  HIPCHK(c, hipSetDevice(c->device));
-  return ICIKT_SUCCESS;
-}
-
-}  // namespace host
-}  // namespace icikt
-
-using icikt::host::fail;
-using icikt::host::use_device;
-
 namespace {
 
 // fold the recorded event pairs of kernel k into the accumulated time (waits for them to complete)
@@ -56,6 +40,21 @@ int flush_timer(icikt_ctx* c, int k) {
     c->launches[k] += 1;
   }
   c->ev_used[k] = 0;
+  return ICIKT_SUCCESS;
+}
+
+}  // namespace
+
+namespace icikt {
+namespace host {
+
+int fail(icikt_ctx* c, int code, const std::string& msg) {
+  if (c) c->err = msg;
+  return code;
+}
+
+int use_device(icikt_ctx* c) {
+  HIPCHK(c, hipSetDevice(c->device));
   return ICIKT_SUCCESS;
 }
 
@@ -85,13 +84,23 @@ int timer_end(icikt_ctx* c, int k, uint32_t flags) {
   return ICIKT_SUCCESS;
 }
 
+}  // namespace host
+}  // namespace icikt
+
+using icikt::host::fail;
+using icikt::host::use_device;
+using icikt::host::timer_begin;
+using icikt::host::timer_end;
+
+namespace {
+
 // launch plan of the pair kernel for a given n
 struct K1Plan {
   int np;            // pairs per wave: 2 (one per half, consecutive pairs with the same pi) or 1
   int wpb;           // waves per workgroup
   size_t lds_bytes;
   int perpair_bytes;
-  int opts;          // bit 0: half-wave hot step (one pair per 32-lane half, 32-row sub-steps)
+  int opts;          // the pair kernel's option word (K1_OPT_* of icikt_device.h)
   int half_items;    // words per lane of a half-wave prefix rebuild (0: no half-wave step)
   int stride;        // 64-bit words between a pair's LDS / pend arrays (k1_lds_stride)
   int split;         // half-wave kernels: segments a task is cut in (1 | 2 | 4) when the task list leaves the chip half empty
@@ -112,7 +121,7 @@ K1Plan plan_k1(const PrepView& pv, int64_t n_pairs, int n_cu, const icikt_ctx::P
   // persistent grid: rounds 1-2): the plan keys pend / gridmult / gridcap of icikt_debug_set_plan are accepted and ignored.
   // 18 337 .. 30 656 rows: BOTH families fit.  Continuous columns run 25-50 % faster in the long-column kernel (n = 20 000:
   // 1.98e7 vs 1.55e7 pairs/s; 30 000: 1.33e7 vs 0.88e7: the half-wave prefix rebuild costs 11 .. 15 words per lane there,
-  // the long-column kernel takes singleton rows in the half layout over the two-level counts: bit 2 of `opts` below),
+  // the long-column kernel takes singleton rows in the half layout over the two-level counts: K1_OPT_HALF_LAYOUT below),
   // tied columns 1.4-2.1x faster in the half-wave kernels (their MIXED steps use the packed chains and the pre-pass's
   // masks; n = 30 000, ~15 000 / 3 000 / 600 distinct values: 1.48 / 1.95 / 1.74 ms vs 2.46 / 4.12 / 2.83): `tied` (the
   // prepared columns average more than eight tie groups: matrix_tied below) chooses.
@@ -144,27 +153,27 @@ K1Plan plan_k1(const PrepView& pv, int64_t n_pairs, int n_cu, const icikt_ctx::P
     if (8 * two > lds_cap) wpb = 1;
   }
   if (ov.wpb > 0) wpb = std::max(1, std::min(8, ov.wpb));
-  pl.opts = 1;
-  if (ov.half >= 0 && !both_fit) pl.opts = ov.half ? 1 : 0;
-  int tg_max = 128;  // bits 8..: whole-wave kernels: joint ties of a closing group from the gathered column's tie-group list
+  pl.opts = icikt::K1_OPT_HALF;
+  if (ov.half >= 0 && !both_fit) pl.opts = ov.half ? icikt::K1_OPT_HALF : 0;
+  int tg_max = 128;  // whole-wave kernels: joint ties of a closing group from the gathered column's tie-group list
                      // while it has at most this many groups (the kernels cap it at 128: two listed groups per lane), else row
                      // by row; half-wave kernels: the entries of a pair's counter table (count mode), sized below
   if (ov.has_tgmax) tg_max = std::max(-1, std::min(1 << 20, ov.tgmax));
   const bool row_only = tg_max < 0;
-  if (row_only) { pl.opts |= 2; tg_max = 0; }  // bit 1: row mode only
-  // bits 8..15: list mode (range counts per listed tie group at a group's close: a cost per CLOSE, right for few, long
+  if (row_only) { pl.opts |= icikt::K1_OPT_ROW_ONLY; tg_max = 0; }
+  // list mode (range counts per listed tie group at a group's close: a cost per CLOSE, right for few, long
   // groups -- and same-address atomics of count mode would serialise there) up to this many tie groups
   int tg_list = std::min(tg_max, 128);   // (raised to 256 below for the half-wave kernels of 11 .. 15 words per lane)
   // half-wave kernels: a half rebuilds a prefix with half_items words per lane, unpredicated, so the LDS arrays of such
   // a kernel are padded to 32 * half_items words; every other plan runs pairs on the whole wave
   pl.half_items = icikt::k1_half_items(pv.Wp);
-  if (np != 2 || !half_ok || !(pl.opts & 1)) {
-    pl.opts &= ~1;
+  if (np != 2 || !half_ok || !(pl.opts & icikt::K1_OPT_HALF)) {
+    pl.opts &= ~icikt::K1_OPT_HALF;
     pl.half_items = 0;
   }
-  // bit 2: two long-column pairs of a whole-wave kernel take the singleton region in the half layout (one pair per
+  // two long-column pairs of a whole-wave kernel take the singleton region in the half layout (one pair per
   // 32-lane half, 32-row sub-steps, the half-wave in-step chain)
-  if (np == 2 && pl.half_items == 0 && ov.hyb != 0) pl.opts |= 4;
+  if (np == 2 && pl.half_items == 0 && ov.hyb != 0) pl.opts |= icikt::K1_OPT_HALF_LAYOUT;
   // final layout: the kernel derives the same stride from (Wp, half_items)
   pl.stride = icikt::k1_lds_stride(pv.Wp, pl.half_items);
   if (pl.half_items > 0) {
@@ -251,15 +260,15 @@ K1Plan plan_k1(const PrepView& pv, int64_t n_pairs, int n_cu, const icikt_ctx::P
       while (cap > 0 && pair_bytes(cap) * np > lds_cap) cap /= 2;
     }
     pl.perpair_bytes = (int)pair_bytes(cap);
-    pl.opts |= cap << 18;   // bits 18..: entries of a pair's counter table (count mode); 0: none
+    pl.opts |= icikt::k1_opt_pack_cnt_cap(cap);   // entries of a pair's counter table (count mode); 0: none
   }
   // (eight listed groups per lane in the kernels that have the registers: list mode up to 256 tie groups there -- count
   //  mode has 64 counters beside their 4.9 KB of LDS state per pair, and row mode streams a long group three times)
   if (pl.half_items > 9 && !row_only) tg_list = std::min(ov.has_tgmax ? std::max(0, ov.tgmax) : 256, 256);
   if (ov.list >= 0) tg_list = std::min(tg_list, ov.list);
-  pl.opts |= tg_list << 8;          // bits 8..17
-  if (ov.solo == 0) pl.opts |= 8;   // bit 3: no SOLO steps
-  if (pl.half_items > 0) pl.opts |= tg_max << 18;   // bits 18..: entries of a pair's counter table (count mode)
+  pl.opts |= icikt::k1_opt_pack_tg_list(tg_list);
+  if (ov.solo == 0) pl.opts |= icikt::K1_OPT_NO_SOLO;
+  if (pl.half_items > 0) pl.opts |= icikt::k1_opt_pack_cnt_cap(tg_max);   // entries of a pair's counter table (count mode)
   const int fit = std::max(1, (int)(lds_cap / ((size_t)pl.perpair_bytes * np)));
   pl.np = np;
   pl.wpb = std::min(wpb, fit);
@@ -441,7 +450,7 @@ int launch_pair_tasks(icikt_ctx* c, const K1Plan& pl, int first, int count) {
   int split = 1, opts = pl.opts;
   if (pl.half_items > 0 && pl.np == 2 && pl.split > 1) {
     split = pl.split;
-    opts |= (split == 2 ? 1 : 2) << 4;
+    opts |= icikt::k1_opt_pack_segments(split);
     HIPCHK(c, icikt::launch_zero_raw(c->d_unit_start.p + 2 * (size_t)first, count, c->d_raw.p, c->stream));
   }
   const int want = (int)(((int64_t)count * split + pl.wpb - 1) / pl.wpb);
@@ -467,7 +476,7 @@ int launch_pair_tasks(icikt_ctx* c, const K1Plan& pl, int first, int count) {
   if (c->plan_ov.verbose)
     fprintf(stderr, "[icikt] K1 plan: np=%d half_items=%d wpb=%d lds=%zu B/block (%d B/pair, %d tie-group counters), %d blocks/CU x %d CUs, "
             "grid=%d%s, tasks=%d (from %d), %d segment(s) per task\n",
-            pl.np, pl.half_items, pl.wpb, pl.lds_bytes, pl.perpair_bytes, pl.opts >> 18, per_cu,
+            pl.np, pl.half_items, pl.wpb, pl.lds_bytes, pl.perpair_bytes, icikt::k1_opt_cnt_cap(pl.opts), per_cu,
             c->prop.multiProcessorCount, blocks, persistent ? " (persistent)" : "", count, first, split);
   HIPCHK(c, icikt::launch_k1(c->pv, c->d_unit_start.p + 2 * (size_t)first, count, c->d_pi.p, c->d_pj.p, c->d_raw.p, pl.np,
                              pl.half_items, pl.wpb, blocks, pl.lds_bytes, pl.perpair_bytes,
@@ -573,12 +582,20 @@ static const char* const kTooLong =
 static const char* const kNoWide =
     "n_feat exceeds ICIKT_MAX_FEATURES (65535 rows per column): this entry has no path for wide columns";
 
-static int check_shape(icikt_ctx* c, const char* who, int64_t n_feat, int64_t n_samp, int64_t ld, bool wide_ok = true) {
+namespace icikt {
+namespace host {
+
+int check_shape(icikt_ctx* c, const char* who, int64_t n_feat, int64_t n_samp, int64_t ld, bool wide_ok) {
   if (n_feat < 0 || n_samp < 0 || ld < n_feat) return fail(c, ICIKT_E_INVALID, std::string(who) + ": bad matrix shape");
   if (n_feat > ICIKT_MAX_FEATURES_WIDE) return fail(c, ICIKT_E_TOO_LONG, std::string(who) + ": " + kTooLong);
   if (n_feat > ICIKT_MAX_FEATURES && !wide_ok) return fail(c, ICIKT_E_TOO_LONG, std::string(who) + ": " + kNoWide);
   return ICIKT_SUCCESS;
 }
+
+}  // namespace host
+}  // namespace icikt
+
+using icikt::host::check_shape;
 
 static int check_col_range(icikt_ctx* c, int64_t n_samp, int64_t col_begin, int64_t col_end, int64_t alloc_cols,
                            int64_t n_feat = 0) {
@@ -1202,21 +1219,14 @@ int upload_prepare_pairs(icikt_ctx* c, const double* X, int64_t n_feat, int64_t 
   return ICIKT_SUCCESS;
 }
 
-}  // namespace host
-}  // namespace icikt
-
 // every index of a host pair list inside [0, n_samp)
-static int check_pair_list(icikt_ctx* c, const char* who, const int32_t* pi, const int32_t* pj, int64_t n_pairs,
-                           int64_t n_samp) {
+int check_pair_list(icikt_ctx* c, const char* who, const int32_t* pi, const int32_t* pj, int64_t n_pairs, int64_t n_samp) {
   if (n_pairs < 0 || (n_pairs > 0 && (!pi || !pj))) return fail(c, ICIKT_E_INVALID, std::string(who) + ": bad pair list");
   for (int64_t p = 0; p < n_pairs; ++p)
     if (pi[p] < 0 || pi[p] >= n_samp || pj[p] < 0 || pj[p] >= n_samp)
       return fail(c, ICIKT_E_INVALID, std::string(who) + ": column index out of range");
   return ICIKT_SUCCESS;
 }
-
-namespace icikt {
-namespace host {
 
 int check_pair_args(icikt_ctx* c, const char* who, const double* X, int64_t n_feat, int64_t n_samp, int64_t ld,
                     const int32_t* pi, const int32_t* pj, int64_t* n_pairs, const void* out, bool out5,
@@ -1241,6 +1251,7 @@ int check_pair_args(icikt_ctx* c, const char* who, const double* X, int64_t n_fe
 
 }  // namespace host
 }  // namespace icikt
+using icikt::host::check_pair_list;
 
 extern "C" {
 
@@ -1487,154 +1498,7 @@ int icikt_missingness_f64(icikt_ctx* c, const double* X, int64_t n_feat, int64_t
 
 }  // extern "C"
 
-// Spearman's exact null distribution for n = 2 .. 9 (prho, AS 89 as R enumerates it): for each n, upper[k] = the
-// permutations whose S = sum (i - perm(i))^2 is >= 2 k, k = 0 .. (n^3 - n) / 6 (S is always even)
-static std::vector<uint32_t> cor_prho_table() {
-  std::vector<uint32_t> out;
-  for (int n = 2; n <= 9; ++n) {
-    const int kmax = (n * n * n - n) / 6;
-    std::vector<uint32_t> cnt((size_t)kmax + 1, 0u);
-    int perm[9];
-    for (int i = 0; i < n; ++i) perm[i] = i;
-    do {
-      int sq = 0;
-      for (int i = 0; i < n; ++i) sq += (i - perm[i]) * (i - perm[i]);
-      cnt[(size_t)(sq / 2)] += 1;
-    } while (std::next_permutation(perm, perm + n));
-    std::vector<uint32_t> up((size_t)kmax + 1);
-    uint32_t acc = 0;
-    for (int k = kmax; k >= 0; --k) { acc += cnt[(size_t)k]; up[(size_t)k] = acc; }
-    out.insert(out.end(), up.begin(), up.end());
-  }
-  return out;
-}
-
 extern "C" {
-
-// cor_fast: pre-pass (K_PREPARE timer), pair products (K_PAIRS), cor.test epilogue (K_EPILOGUE), all on c->stream.
-//   Pearson, no NA             Z^T Z of the mean-shifted, power-of-two-scaled columns, less Σz_i Σz_j / n: 64 x 64
-//                              tiles when the list is all of combn(S, 2) (then the self pairs, or not), one wave per
-//                              pair otherwise
-//   Pearson, pairwise          one wave per pair, two passes over the raw columns: the jointly present rows' mean and
-//                              spread, then their centred, scaled and corrected sums (numerics)
-//   Spearman, no NA            as Pearson, on the centred doubled ranks (integers: the sums are exact)
-//   Spearman, pairwise         one workgroup per pair: the subset ranks from prefix counts, sums in int64
-int icikt_cor_pairs_f64(icikt_ctx* c, const double* X, int64_t n_feat, int64_t n_samp, int64_t ld,
-                        const int32_t* pi, const int32_t* pj, int64_t n_pairs, int method, int pairwise,
-                        int alternative, int continuity, uint32_t flags, double* out3, int32_t* reasons) {
-  if (!c) return ICIKT_E_INVALID;
-  int rc = check_shape(c, "cor", n_feat, n_samp, ld);
-  if (rc) return rc;
-  if (n_feat > 0 && n_samp > 0 && !X) return fail(c, ICIKT_E_INVALID, "cor: null matrix");
-  rc = check_pair_list(c, "cor", pi, pj, n_pairs, n_samp);
-  if (rc) return rc;
-  if (method != ICIKT_METHOD_PEARSON && method != ICIKT_METHOD_SPEARMAN)
-    return fail(c, ICIKT_E_INVALID, "cor: method must be pearson (0) or spearman (1)");
-  if (alternative < ICIKT_ALT_TWO_SIDED || alternative > ICIKT_ALT_GREATER)
-    return fail(c, ICIKT_E_INVALID, "cor: alternative must be two.sided (0), less (1) or greater (2)");
-  if (n_pairs == 0) return ICIKT_SUCCESS;
-  if (!out3 || !reasons) return fail(c, ICIKT_E_INVALID, "cor: null output");
-  rc = use_device(c);
-  if (rc) return rc;
-  rc = icikt_set_pairs(c, pi, pj, n_pairs);
-  if (rc) return rc;
-  // the list is all of combn(S, 2) (optionally followed by the S self pairs, as setup_comparisons(diag_good = FALSE)
-  // makes it): one tile kernel covers it
-  const int64_t ncombn = n_samp * (n_samp - 1) / 2;
-  int full = 0;   // 1: combn, 2: combn + self pairs
-  if (n_pairs == ncombn || n_pairs == ncombn + n_samp) {
-    full = n_pairs == ncombn ? 1 : 2;
-    int64_t p = 0;
-    for (int64_t i = 0; i < n_samp && full; ++i)
-      for (int64_t j = i + 1; j < n_samp; ++j, ++p)
-        if (pi[p] != i || pj[p] != j) { full = 0; break; }
-    for (int64_t i = 0; full == 2 && i < n_samp; ++i)
-      if (pi[ncombn + i] != i || pj[ncombn + i] != i) full = 0;
-  }
-  const icikt::host::PinnedScope scope(c, flags);
-  icikt_ctx::CorBufs& cb = c->cor;
-  auto body = [&]() -> int {
-    if (!cb.prho_ready) {
-      const std::vector<uint32_t> t = cor_prho_table();
-      HIPCHK(c, cb.prho.reserve(t.size()));
-      int r = icikt::host::upload_sync(c, cb.prho.p, t.data(), t.size() * sizeof(uint32_t));
-      if (r) return r;
-      cb.prho_ready = true;
-    }
-    if (n_feat > 0) {
-      int r = icikt::host::upload_and_prepare(c, X, n_feat, n_samp, ld, 0, n_samp, 0u, false, nullptr,
-                                              icikt::host::kPrepassNone);
-      if (r) return r;
-    }
-    const int64_t n = n_feat;
-    const bool spearman = method == ICIKT_METHOD_SPEARMAN;
-    // (dense Spearman sums of centred doubled ranks are integers below (n^3 - n) / 3 < 2^53 for every n the library
-    // takes: exact in f64; the pairwise kernel sums in int64)
-    const bool spearman_pw = spearman && pairwise;
-    int np2 = 1;
-    while (np2 < n) np2 <<= 1;
-    const int prep_blocks = (int)std::max<int64_t>(1, std::min<int64_t>({n_samp, 2048,
-        std::max<int64_t>(1, ((int64_t)1 << 29) / ((int64_t)np2 * 12))}));
-    const int pw_blocks = (int)std::max<int64_t>(1, std::min<int64_t>({n_pairs, 4096,
-        std::max<int64_t>(1, ((int64_t)1 << 29) / ((2 * n + 1) * 4))}));
-    const size_t nS = (size_t)std::max<int64_t>(n * n_samp, 1);
-    HIPCHK(c, cb.z.reserve(nS));
-    HIPCHK(c, cb.colss.reserve((size_t)std::max<int64_t>(n_samp, 1)));
-    HIPCHK(c, cb.colsum.reserve((size_t)std::max<int64_t>(n_samp, 1)));
-    HIPCHK(c, cb.cnt.reserve((size_t)std::max<int64_t>(n_samp, 1)));
-    HIPCHK(c, cb.flags.reserve((size_t)std::max<int64_t>(n_samp, 1)));
-    HIPCHK(c, cb.acc.reserve((size_t)n_pairs));
-    HIPCHK(c, c->d_out4.reserve((size_t)n_pairs * 3));
-    HIPCHK(c, c->d_reasons.reserve((size_t)n_pairs));
-    icikt::CorPrep cp{};
-    cp.X = c->d_X.p;
-    cp.ld = n;
-    cp.n = n;
-    cp.S = (int)n_samp;
-    cp.method = method;
-    cp.Z = cb.z.p;
-    cp.cnt = cb.cnt.p;
-    cp.colss = cb.colss.p;
-    cp.colsum = cb.colsum.p;
-    cp.flags = cb.flags.p;
-    cp.np2 = np2;
-    if (spearman) {
-      HIPCHK(c, cb.order.reserve(3 * nS));
-      HIPCHK(c, cb.keys.reserve((size_t)prep_blocks * np2));
-      HIPCHK(c, cb.scratch.reserve(std::max<size_t>((size_t)prep_blocks * np2,
-                                                    spearman_pw ? (size_t)pw_blocks * (size_t)(2 * n + 1) : 0)));
-      cp.ord = cb.order.p;
-      cp.gs = cb.order.p + nS;
-      cp.ge = cb.order.p + 2 * nS;
-      cp.keys = reinterpret_cast<uint64_t*>(cb.keys.p);
-      cp.idx = cb.scratch.p;
-    }
-    int r = timer_begin(c, ICIKT_K_PREPARE, flags);
-    if (r) return r;
-    HIPCHK(c, icikt::launch_cor_prep(cp, prep_blocks, c->stream));
-    r = timer_end(c, ICIKT_K_PREPARE, flags);
-    if (!r) r = timer_begin(c, ICIKT_K_PAIRS, flags);
-    if (r) return r;
-    if (spearman_pw) {
-      HIPCHK(c, icikt::launch_cor_spearman_pw(cp, c->d_pi.p, c->d_pj.p, n_pairs, pw_blocks, cb.scratch.p, cb.acc.p,
-                                              c->stream));
-    } else if (full && !pairwise) {
-      HIPCHK(c, icikt::launch_cor_tile(cp, full == 2, cb.acc.p, c->stream));
-    } else {
-      HIPCHK(c, icikt::launch_cor_dots(cp, pairwise, c->d_pi.p, c->d_pj.p, n_pairs, cb.acc.p, c->stream));
-    }
-    r = timer_end(c, ICIKT_K_PAIRS, flags);
-    if (!r) r = timer_begin(c, ICIKT_K_EPILOGUE, flags);
-    if (r) return r;
-    HIPCHK(c, icikt::launch_cor_epilogue(cb.acc.p, n_pairs, method, pairwise, alternative, continuity, cb.prho.p,
-                                         c->d_out4.p, c->d_reasons.p, c->stream));
-    r = timer_end(c, ICIKT_K_EPILOGUE, flags);
-    if (!r) r = icikt::host::download(c, out3, c->d_out4.p, (size_t)n_pairs * 3 * sizeof(double));
-    if (!r) r = icikt::host::download(c, reasons, c->d_reasons.p, (size_t)n_pairs * sizeof(int32_t));
-    return r;
-  };
-  return icikt::host::end_call(c, "cor", body());
-}
 
 // Development / test hook: "key=value,key=value" overrides of the pair kernel's launch plan and of the host
 // path's H2D mode; NULL or "" restores the library's choices.  Keys: np (pairs per wave: 1 | 2), pend (l | g),
@@ -1756,262 +1620,6 @@ int icikt_selftest(icikt_ctx* c) {
     }
   }
   return ICIKT_SUCCESS;
-}
-
-}  // extern "C"
-
-// ---- missing-value diagnostics (R/left_censorship.R, R/rank-ordering.R) ----
-// Timers: K_PREPARE the matrix's H2D, K_PAIRS the column and row passes, K_EPILOGUE the orders and the gathers.
-namespace {
-
-// the per-column pass over the device matrix dX (n x S, leading dimension n); rank mode when kept != nullptr
-int diag_col_pass(icikt_ctx* c, const double* dX, int64_t n, int64_t S, const icikt::MaskSpec& ms, int na_rm,
-                  const uint8_t* kept, int32_t* rank2) {
-  icikt_ctx::DiagBufs& db = c->diag;
-  int np2 = 1;
-  while (np2 < n) np2 <<= 1;
-  const int blocks = (int)std::max<int64_t>(1, std::min<int64_t>({S, 2048,
-      std::max<int64_t>(1, ((int64_t)1 << 29) / ((int64_t)np2 * 16))}));
-  const size_t scratch = (size_t)blocks * (size_t)np2;
-  const size_t nS = (size_t)std::max<int64_t>(S, 1);
-  HIPCHK(c, db.keys.reserve(scratch));
-  HIPCHK(c, db.idx.reserve(scratch));
-  HIPCHK(c, db.gs.reserve(scratch));
-  HIPCHK(c, db.median.reserve(nS));
-  HIPCHK(c, db.nmiss.reserve(nS));
-  HIPCHK(c, db.nexcl.reserve(nS));
-  icikt::DiagCol dc{};
-  dc.X = dX;
-  dc.ld = n;
-  dc.n = n;
-  dc.S = (int)S;
-  dc.ms = ms;
-  dc.na_rm = na_rm;
-  dc.median = db.median.p;
-  dc.nmiss = db.nmiss.p;
-  dc.nexcl = db.nexcl.p;
-  dc.kept = kept;
-  dc.rank2 = rank2;
-  dc.keys = reinterpret_cast<uint64_t*>(db.keys.p);
-  dc.idx = db.idx.p;
-  dc.gs = db.gs.p;
-  dc.np2 = np2;
-  HIPCHK(c, icikt::launch_diag_col(dc, blocks, c->stream));
-  return ICIKT_SUCCESS;
-}
-
-// shape, matrix, global_na of the three entries; sets *ms
-int diag_args(icikt_ctx* c, const char* who, const double* X, int64_t n_feat, int64_t n_samp, int64_t ld,
-              const double* global_na, int n_global_na, icikt::MaskSpec* ms) {
-  int rc = check_shape(c, who, n_feat, n_samp, ld);
-  if (rc) return rc;
-  if (n_feat > 0 && n_samp > 0 && !X) return fail(c, ICIKT_E_INVALID, std::string(who) + ": null matrix");
-  if (n_samp > INT32_MAX) return fail(c, ICIKT_E_INVALID, std::string(who) + ": too many columns");
-  rc = icikt::host::make_mask_spec(c, global_na, n_global_na, ms);
-  if (rc) c->err = std::string(who) + c->err.substr(c->err.find(':'));
-  return rc;
-}
-
-}  // namespace
-
-extern "C" {
-
-int icikt_col_medians_f64(icikt_ctx* c, const double* X, int64_t n_feat, int64_t n_samp, int64_t ld,
-                          const double* global_na, int n_global_na, int na_rm, uint32_t flags, double* medians) {
-  if (!c) return ICIKT_E_INVALID;
-  icikt::MaskSpec ms;
-  int rc = diag_args(c, "col_medians", X, n_feat, n_samp, ld, global_na, n_global_na, &ms);
-  if (rc) return rc;
-  if (n_samp == 0) return ICIKT_SUCCESS;
-  if (!medians) return fail(c, ICIKT_E_INVALID, "col_medians: null output");
-  rc = use_device(c);
-  if (rc) return rc;
-  const icikt::host::PinnedScope scope(c, flags);
-  auto body = [&]() -> int {
-    int r = icikt::host::upload_and_prepare(c, X, n_feat, n_samp, ld, 0, n_samp, flags, false, nullptr,
-                                            icikt::host::kPrepassNone);
-    if (!r) r = timer_begin(c, ICIKT_K_PAIRS, flags);
-    if (!r) r = diag_col_pass(c, c->d_X.p, n_feat, n_samp, ms, na_rm, nullptr, nullptr);
-    if (!r) r = timer_end(c, ICIKT_K_PAIRS, flags);
-    if (!r) r = icikt::host::download(c, medians, c->diag.median.p, (size_t)n_samp * sizeof(double));
-    return r;
-  };
-  return icikt::host::end_call(c, "col_medians", body());
-}
-
-int icikt_censor_counts_f64(icikt_ctx* c, const double* X, int64_t n_feat, int64_t n_samp, int64_t ld,
-                            const double* global_na, int n_global_na, const int32_t* cls, int n_class, uint32_t flags,
-                            int64_t* trials, int64_t* success, int64_t* n_excluded, double* medians) {
-  if (!c) return ICIKT_E_INVALID;
-  icikt::MaskSpec ms;
-  int rc = diag_args(c, "censor_counts", X, n_feat, n_samp, ld, global_na, n_global_na, &ms);
-  if (rc) return rc;
-  if (n_class < 1) return fail(c, ICIKT_E_INVALID, "censor_counts: n_class must be at least 1");
-  if (n_samp > 0 && !cls) return fail(c, ICIKT_E_INVALID, "censor_counts: null class list");
-  if (!trials || !success || !n_excluded) return fail(c, ICIKT_E_INVALID, "censor_counts: null output");
-  // the columns grouped by class, in column order within a class
-  std::vector<int32_t> off((size_t)n_class + 1, 0), cols((size_t)n_samp);
-  for (int64_t j = 0; j < n_samp; ++j) {
-    if (cls[j] < 0 || cls[j] >= n_class) return fail(c, ICIKT_E_INVALID, "censor_counts: class index out of range");
-    ++off[(size_t)cls[j] + 1];
-  }
-  for (int k = 0; k < n_class; ++k) off[(size_t)k + 1] += off[(size_t)k];
-  {
-    std::vector<int32_t> fill(off.begin(), off.end() - 1);
-    for (int64_t j = 0; j < n_samp; ++j) cols[(size_t)fill[(size_t)cls[j]]++] = (int32_t)j;
-  }
-  for (int k = 0; k < n_class; ++k) trials[k] = success[k] = 0;
-  *n_excluded = 0;
-  if (n_samp == 0) return ICIKT_SUCCESS;
-  rc = use_device(c);
-  if (rc) return rc;
-  const icikt::host::PinnedScope scope(c, flags);
-  icikt_ctx::DiagBufs& db = c->diag;
-  std::vector<unsigned long long> out3((size_t)n_class * 3);
-  std::vector<int32_t> nexcl((size_t)n_samp);
-  auto body = [&]() -> int {
-    int r = icikt::host::upload_and_prepare(c, X, n_feat, n_samp, ld, 0, n_samp, flags, false, nullptr,
-                                            icikt::host::kPrepassNone);
-    if (r) return r;
-    HIPCHK(c, db.lists.reserve(off.size() + cols.size()));
-    HIPCHK(c, db.red.reserve(out3.size()));
-    r = icikt::host::upload_sync(c, db.lists.p, off.data(), off.size() * sizeof(int32_t));
-    if (!r) r = icikt::host::upload_sync(c, db.lists.p + off.size(), cols.data(), cols.size() * sizeof(int32_t));
-    if (!r) r = timer_begin(c, ICIKT_K_PAIRS, flags);
-    if (r) return r;
-    HIPCHK(c, hipMemsetAsync(db.red.p, 0, out3.size() * sizeof(unsigned long long), c->stream));
-    r = diag_col_pass(c, c->d_X.p, n_feat, n_samp, ms, 1, nullptr, nullptr);
-    if (r) return r;
-    HIPCHK(c, icikt::launch_diag_censor(c->d_X.p, n_feat, n_feat, ms, db.lists.p + off.size(), db.lists.p, n_class,
-                                        db.median.p, db.red.p, c->stream));
-    r = timer_end(c, ICIKT_K_PAIRS, flags);
-    if (!r) r = icikt::host::download(c, out3.data(), db.red.p, out3.size() * sizeof(unsigned long long));
-    if (!r) r = icikt::host::download(c, nexcl.data(), db.nexcl.p, nexcl.size() * sizeof(int32_t));
-    if (!r && medians) r = icikt::host::download(c, medians, db.median.p, (size_t)n_samp * sizeof(double));
-    return r;
-  };
-  rc = icikt::host::end_call(c, "censor_counts", body());
-  if (rc) return rc;
-  for (int k = 0; k < n_class; ++k) {
-    trials[k] = (int64_t)out3[3 * (size_t)k];
-    success[k] = (int64_t)out3[3 * (size_t)k + 1];
-  }
-  int64_t ex = 0;
-  for (int32_t v : nexcl) ex += v;
-  *n_excluded = ex;
-  return ICIKT_SUCCESS;
-}
-
-int icikt_rank_order_f64(icikt_ctx* c, const double* X, int64_t n_feat, int64_t n_samp, int64_t ld,
-                         const double* global_na, int n_global_na, const int32_t* cols, int64_t n_cols, uint32_t flags,
-                         int64_t* n_kept, int32_t* n_na, double* median_rank, int32_t* row_order, int32_t* col_order,
-                         double* original, double* ordered) {
-  if (!c) return ICIKT_E_INVALID;
-  icikt::MaskSpec ms;
-  int rc = diag_args(c, "rank_order", X, n_feat, n_samp, ld, global_na, n_global_na, &ms);
-  if (rc) return rc;
-  if (n_cols < 1 || n_cols > n_samp || !cols) return fail(c, ICIKT_E_INVALID, "rank_order: bad column list");
-  for (int64_t j = 0; j < n_cols; ++j)
-    if (cols[j] < 0 || cols[j] >= n_samp) return fail(c, ICIKT_E_INVALID, "rank_order: column index out of range");
-  if (!n_kept || (n_feat > 0 && (!n_na || !median_rank || !row_order)) || !col_order)
-    return fail(c, ICIKT_E_INVALID, "rank_order: null output");
-  *n_kept = 0;
-  rc = use_device(c);
-  if (rc) return rc;
-  const int64_t n = n_feat;
-  // the class's columns as one block: in place when they are consecutive, else gathered on the host (one pass)
-  bool consecutive = true;
-  for (int64_t j = 1; j < n_cols && consecutive; ++j) consecutive = cols[j] == cols[0] + j;
-  std::vector<double> gathered;
-  const double* src = n > 0 ? X + (int64_t)cols[0] * ld : X;
-  int64_t src_ld = ld;
-  if (!consecutive && n > 0) {
-    gathered.resize((size_t)n * (size_t)n_cols);
-    for (int64_t j = 0; j < n_cols; ++j)
-      std::memcpy(gathered.data() + (size_t)j * (size_t)n, X + (int64_t)cols[j] * ld, (size_t)n * sizeof(double));
-    src = gathered.data();
-    src_ld = n;
-  }
-  const icikt::host::PinnedScope scope(c, gathered.empty() ? flags : (flags & ~ICIKT_FLAG_HOST_PINNED));
-  icikt_ctx::DiagBufs& db = c->diag;
-  std::vector<int32_t> nmiss((size_t)n_cols);
-  unsigned long long kept_count = 0;
-  // device passes, then the counts and medians back to the host
-  auto passes = [&]() -> int {
-    int r = icikt::host::upload_and_prepare(c, src, n, n_cols, src_ld, 0, n_cols, flags, false, nullptr,
-                                            icikt::host::kPrepassNone);
-    if (r) return r;
-    const size_t nn = (size_t)std::max<int64_t>(n, 1);
-    HIPCHK(c, db.kept.reserve(nn));
-    HIPCHK(c, db.nna.reserve(nn));
-    HIPCHK(c, db.medrank.reserve(nn));
-    HIPCHK(c, db.rank2.reserve(nn * (size_t)n_cols));
-    HIPCHK(c, db.red.reserve(1));
-    r = timer_begin(c, ICIKT_K_PAIRS, flags);
-    if (r) return r;
-    HIPCHK(c, hipMemsetAsync(db.red.p, 0, sizeof(unsigned long long), c->stream));
-    HIPCHK(c, icikt::launch_diag_rowmiss(c->d_X.p, n, (int)n_cols, ms, db.nna.p, db.kept.p, db.red.p, c->stream));
-    r = diag_col_pass(c, c->d_X.p, n, n_cols, ms, 1, db.kept.p, db.rank2.p);
-    if (r) return r;
-    HIPCHK(c, icikt::launch_diag_median_rank(db.rank2.p, n, (int)n_cols, db.kept.p, db.medrank.p, c->stream));
-    r = timer_end(c, ICIKT_K_PAIRS, flags);
-    if (!r) r = icikt::host::download(c, &kept_count, db.red.p, sizeof(unsigned long long));
-    if (!r) r = icikt::host::download(c, nmiss.data(), db.nmiss.p, nmiss.size() * sizeof(int32_t));
-    if (!r && n > 0) r = icikt::host::download(c, n_na, db.nna.p, (size_t)n * sizeof(int32_t));
-    if (!r && n > 0) r = icikt::host::download(c, median_rank, db.medrank.p, (size_t)n * sizeof(double));
-    if (r) return r;
-    const hipError_t e = icikt::host::finish_stream(c, true);
-    if (e != hipSuccess) return fail(c, ICIKT_E_HIP, std::string("rank_order: ") + hipGetErrorString(e));
-    return ICIKT_SUCCESS;
-  };
-  rc = passes();
-  if (rc) return icikt::host::end_call(c, "rank_order", rc);
-  const int64_t nk = (int64_t)kept_count;
-  // order(median_rank, decreasing = TRUE) over the kept rows, order(colMeans(is.na), decreasing = TRUE): both stable.
-  // (The dropped rows are missing in every column: they shift every column's count alike.)
-  std::vector<int32_t> kept_rows;
-  kept_rows.reserve((size_t)nk);
-  for (int64_t r = 0; r < n; ++r)
-    if (n_na[r] < n_cols) kept_rows.push_back((int32_t)r);
-  if ((int64_t)kept_rows.size() != nk) return icikt::host::end_call(c, "rank_order",
-      fail(c, ICIKT_E_HIP, "rank_order: kept-row count differs between device and host"));
-  std::vector<int32_t> rord(kept_rows);
-  std::stable_sort(rord.begin(), rord.end(), [&](int32_t a, int32_t b) { return median_rank[a] > median_rank[b]; });
-  std::vector<int32_t> cord((size_t)n_cols);
-  for (int64_t j = 0; j < n_cols; ++j) cord[(size_t)j] = (int32_t)j;
-  std::stable_sort(cord.begin(), cord.end(), [&](int32_t a, int32_t b) { return nmiss[(size_t)a] > nmiss[(size_t)b]; });
-  std::copy(rord.begin(), rord.end(), row_order);
-  std::copy(cord.begin(), cord.end(), col_order);
-  *n_kept = nk;
-  auto gathers = [&]() -> int {
-    if (nk == 0 || (!original && !ordered)) return ICIKT_SUCCESS;
-    std::vector<int32_t> lists;   // kept rows | row order | identity columns | column order
-    lists.reserve(2 * (size_t)nk + 2 * (size_t)n_cols);
-    lists.insert(lists.end(), kept_rows.begin(), kept_rows.end());
-    lists.insert(lists.end(), rord.begin(), rord.end());
-    for (int64_t j = 0; j < n_cols; ++j) lists.push_back((int32_t)j);
-    lists.insert(lists.end(), cord.begin(), cord.end());
-    HIPCHK(c, db.lists.reserve(lists.size()));
-    int r = icikt::host::upload_sync(c, db.lists.p, lists.data(), lists.size() * sizeof(int32_t));
-    if (r) return r;
-    const size_t cells = (size_t)nk * (size_t)n_cols;
-    HIPCHK(c, db.out.reserve(2 * cells));
-    r = timer_begin(c, ICIKT_K_EPILOGUE, flags);
-    if (r) return r;
-    const int32_t* d_kept = db.lists.p;
-    const int32_t* d_rord = d_kept + nk;
-    const int32_t* d_cid = d_rord + nk;
-    const int32_t* d_cord = d_cid + n_cols;
-    if (original)
-      HIPCHK(c, icikt::launch_diag_gather(c->d_X.p, n, ms, d_kept, nk, d_cid, (int)n_cols, db.out.p, c->stream));
-    if (ordered)
-      HIPCHK(c, icikt::launch_diag_gather(c->d_X.p, n, ms, d_rord, nk, d_cord, (int)n_cols, db.out.p + cells, c->stream));
-    r = timer_end(c, ICIKT_K_EPILOGUE, flags);
-    if (!r && original) r = icikt::host::download(c, original, db.out.p, cells * sizeof(double));
-    if (!r && ordered) r = icikt::host::download(c, ordered, db.out.p + cells, cells * sizeof(double));
-    return r;
-  };
-  return icikt::host::end_call(c, "rank_order", gathers());
 }
 
 }  // extern "C"

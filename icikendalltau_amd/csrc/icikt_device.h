@@ -1,5 +1,6 @@
-// icikt_device.h -- structures shared by the kernels (icikt_kernels.hip) and the C-ABI host side
-// (icikt_capi.cpp).  Internal; the public boundary is include/icikt.h.
+// icikt_device.h -- structures, layouts and launcher declarations shared by the device units (icikt_prepass.hip,
+// icikt_kernels.hip, icikt_epilogue.hip, icikt_cor.hip, icikt_diag.hip) and the C-ABI host side (icikt_capi*.cpp,
+// icikt_multi.cpp).  Internal; the public boundary is include/icikt.h.
 #ifndef ICIKT_DEVICE_H
 #define ICIKT_DEVICE_H
 
@@ -36,6 +37,10 @@ __host__ __device__ inline uint32_t tprog_rows(uint32_t e) { return e & 127u; }
 __host__ __device__ inline uint32_t tprog_kind(uint32_t e) { return (e >> 7) & 3u; }
 __host__ __device__ inline bool tprog_closes(uint32_t e) { return ((e >> 9) & 1u) != 0u; }
 __host__ __device__ inline uint32_t tprog_n0(uint32_t e) { return (e >> 10) & 63u; }
+// What the generator (k0_tie_program, icikt_prepass.hip) and the pair kernel that walks the program (k1_pairs) must agree on:
+constexpr int TPROG_KS = 32;   // == k1_ks(true): MIXED steps take groups of up to this many rows
+constexpr int TPROG_WIN = 16384, TPROG_LIST = 1024;   // positions of a generator window; steps listed per window
+constexpr int TPROG_MARKS = 4;   // segment marks written behind the program (prog_tail: positions, then their steps)
 
 // setup_missing_matrix (R/utils.R:1-23) on the device: which cells of the data matrix are excluded (become NA,
 // R/kendalltau.R:119-121) before the pre-pass.  The pre-pass applies it while it reads the matrix, so the masked copy
@@ -173,6 +178,24 @@ __host__ __device__ inline int k1_lds_stride(int Wp, int half_items) {
   if (half_items > 0) return 32 * half_items;
   return (Wp + 7) & ~7;
 }
+
+// The pair kernel's option word (`opts` of launch_k1 and k1_pairs; one int as a kernel argument): packed by the host's
+// launch plan (plan_k1, launch_pair_tasks in icikt_capi.cpp), read by the kernel, both through the names below
+// (a flag is tested as `opts & K1_OPT_...`, a field read through its accessor).
+constexpr int K1_OPT_HALF = 1;          // bit 0: half-wave hot step (one pair per 32-lane half, 32-row sub-steps)
+constexpr int K1_OPT_ROW_ONLY = 2;      // bit 1: row mode only (joint ties of a long group neither from a list nor from counters)
+constexpr int K1_OPT_HALF_LAYOUT = 4;   // bit 2: two long-column pairs of a whole-wave kernel take the singleton region in the
+                                        // half layout (one pair per 32-lane half, 32-row sub-steps, the half-wave in-step chain)
+constexpr int K1_OPT_NO_SOLO = 8;       // bit 3: no SOLO steps
+constexpr int K1_OPT_SEG_SHIFT = 4;     // bits 4..5: log2 of the segments a half-wave task is cut in (1, 2 or 4)
+constexpr int K1_OPT_LIST_SHIFT = 8, K1_OPT_LIST_MASK = 0x3FF;   // bits 8..17: list mode's reach, in tie groups of the gathered column
+constexpr int K1_OPT_CNT_SHIFT = 18;    // bits 18 and up: entries of a pair's counter table (count mode); 0: none
+__host__ __device__ constexpr int k1_opt_segments(int opts) { return 1 << ((opts >> K1_OPT_SEG_SHIFT) & 3); }
+__host__ __device__ constexpr int k1_opt_tg_list(int opts) { return (opts >> K1_OPT_LIST_SHIFT) & K1_OPT_LIST_MASK; }
+__host__ __device__ constexpr int k1_opt_cnt_cap(int opts) { return opts >> K1_OPT_CNT_SHIFT; }
+__host__ __device__ constexpr int k1_opt_pack_segments(int split) { return (split == 4 ? 2 : split == 2 ? 1 : 0) << K1_OPT_SEG_SHIFT; }
+__host__ __device__ constexpr int k1_opt_pack_tg_list(int tg_list) { return tg_list << K1_OPT_LIST_SHIFT; }
+__host__ __device__ constexpr int k1_opt_pack_cnt_cap(int entries) { return entries << K1_OPT_CNT_SHIFT; }
 
 // ms: cells to exclude while reading dX (nullptr: NaN = missing, nothing else); keep: optional [n_samp][n] bytes,
 // 1 = not excluded (the reference's `keep = t(!exclude_loc)`, R/kendalltau.R:417)

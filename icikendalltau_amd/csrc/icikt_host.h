@@ -1,4 +1,5 @@
-// icikt_host.h -- host-side internals shared by icikt_capi.cpp (one device) and icikt_multi.cpp (several
+// icikt_host.h -- host-side internals shared by the entry files of one device (icikt_capi.cpp: the pair engine,
+// icikt_capi_cor.cpp: cor_fast, icikt_capi_diag.cpp: the missing-value diagnostics) and icikt_multi.cpp (several
 // devices, RCCL).  Internal; the public boundary is include/icikt.h.
 #ifndef ICIKT_HOST_H
 #define ICIKT_HOST_H
@@ -149,6 +150,14 @@ namespace host {
 
 int fail(icikt_ctx* c, int code, const std::string& msg);
 int use_device(icikt_ctx* c);
+// entry checks and timers shared by the entry files (defined in icikt_capi.cpp)
+// matrix shape of an entry, `who` prefixing the message; wide_ok: the entry has a path for columns past ICIKT_MAX_FEATURES
+int check_shape(icikt_ctx* c, const char* who, int64_t n_feat, int64_t n_samp, int64_t ld, bool wide_ok = true);
+// every index of a host pair list inside [0, n_samp)
+int check_pair_list(icikt_ctx* c, const char* who, const int32_t* pi, const int32_t* pj, int64_t n_pairs, int64_t n_samp);
+// with ICIKT_FLAG_TIMING: an event pair of kernel id k (ICIKT_K_*) around what the caller puts on c->stream in between
+int timer_begin(icikt_ctx* c, int k, uint32_t flags);
+int timer_end(icikt_ctx* c, int k, uint32_t flags);
 
 #define HIPCHK(c, call)                                                                               \
   do {                                                                                                \

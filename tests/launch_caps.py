@@ -3,9 +3,9 @@ only), and vectorised cor_fast references for pair lists too long for tests/cor_
 
 Past its cap a workgroup (or wave, or y-block) handles several columns or pairs; the later rounds reuse the LDS,
 per-block scratch and scan carries of the round before.  Keep these formulas in step with:
-- diag_col_blocks:     icikt_capi.cpp, diag_col_pass()        (k_diag_col, 16 bytes of scratch per padded row)
-- cor_prep_blocks:     icikt_capi.cpp, icikt_cor_pairs_f64()  prep_blocks (k_cor_prep, 12 bytes per padded row)
-- spearman_pw_blocks:  icikt_capi.cpp, icikt_cor_pairs_f64()  pw_blocks (k_cor_spearman_pw, 2 n + 1 int32 per block)
+- diag_col_blocks:     icikt_capi_diag.cpp, diag_col_pass()        (k_diag_col, 16 bytes of scratch per padded row)
+- cor_prep_blocks:     icikt_capi_cor.cpp, icikt_cor_pairs_f64()  prep_blocks (k_cor_prep, 12 bytes per padded row)
+- spearman_pw_blocks:  icikt_capi_cor.cpp, icikt_cor_pairs_f64()  pw_blocks (k_cor_spearman_pw, 2 n + 1 int32 per block)
 - cor_dots_waves:      icikt_cor.hip, launch_cor_dots()       (k_cor_dots, 4 waves per block, at most 65 536 blocks)
 - gather_y_blocks:     icikt_diag.hip, launch_diag_gather()   (k_diag_gather, y-grid)"""
 import numpy as np

@@ -54,7 +54,7 @@ def test_random_with_na(hip_ctx, n, perspective):
 @pytest.mark.parametrize("n", [700, 5000, 12000, 40000])
 def test_values_that_differ_only_in_their_low_bits(hip_ctx, n):
     """The pre-pass sorts one-word elements first -- the top 48 bits of a value's sortable key | its row -- and repeats a
-    column with (full key, row) elements when the full keys show an inversion (icikt_kernels.hip: kv_gt, k0_prepare).
+    column with (full key, row) elements when the full keys show an inversion (icikt_prepass.hip: kv_gt, k0_prepare).
     Columns whose values share their top 48 key bits and differ below them (relative differences under 2^-36) must take
     that second pass: distinct low bits in random order, with ties among them, beside ordinary columns, negative values
     (keys complemented), +-0 and missing values; and the boundary case where only SOME neighbours collide."""

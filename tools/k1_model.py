@@ -1,4 +1,4 @@
-"""Numpy model of K0/K1 (development aid: same algorithm as icikt_kernels.hip, lane loops written out)."""
+"""Numpy model of K0/K1 (development aid: same algorithm as icikt_prepass.hip / icikt_kernels.hip, lane loops written out)."""
 import numpy as np
 
 def k0(col):

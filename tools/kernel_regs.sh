@@ -1,10 +1,14 @@
 #!/bin/bash
-# Per-kernel VGPR / SGPR / scratch / LDS of the built library (development aid): compiles the kernels to assembly and
-# prints the .amdhsa metadata of every k1_pairs instantiation (and K0).
+# Per-kernel VGPR / SGPR / scratch / LDS of the built library (development aid): compiles the pair-kernel unit and the
+# pre-pass unit to assembly and prints the .amdhsa metadata of every k1_pairs instantiation (and K0).
 ROOT="$(cd "$(dirname "$0")/.." && pwd)"
 OUT=${1:-/tmp/icikt_kernels.s}
-/opt/rocm/bin/hipcc -O3 --offload-arch=gfx950 -std=c++17 -S --cuda-device-only -I "$ROOT/include" -I "$ROOT/icikendalltau_amd/csrc" \
-  "$ROOT/icikendalltau_amd/csrc/icikt_kernels.hip" -o "$OUT" $EXTRA || exit 1
+: > "$OUT"
+for unit in icikt_kernels.hip icikt_prepass.hip; do
+  /opt/rocm/bin/hipcc -O3 --offload-arch=gfx950 -std=c++17 -S --cuda-device-only -I "$ROOT/include" -I "$ROOT/icikendalltau_amd/csrc" \
+    "$ROOT/icikendalltau_amd/csrc/$unit" -o "$OUT.unit" $EXTRA || exit 1
+  cat "$OUT.unit" >> "$OUT" && rm -f "$OUT.unit"
+done
 python3 - "$OUT" <<'PY'
 import re, sys
 txt = open(sys.argv[1]).read()
