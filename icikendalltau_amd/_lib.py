@@ -17,7 +17,7 @@ LIB_PATH = os.environ.get("ICIKT_LIB") or os.path.join(_PKG, "libicikt_hip.so") 
 SOURCES = [os.path.join(_PKG, "csrc", f) for f in ("icikt_kernels.hip", "icikt_prepass.hip", "icikt_epilogue.hip",
                                                        "icikt_capi.cpp", "icikt_capi_cor.cpp", "icikt_capi_diag.cpp",
                                                        "icikt_multi.cpp", "icikt_transfer.cpp", "icikt_cor.hip",
-                                                       "icikt_diag.hip")]
+                                                       "icikt_diag.hip", "icikt_ingest.hip")]
 HEADERS = [os.path.join(_ROOT, "include", "icikt.h"), os.path.join(_PKG, "csrc", "icikt_device.h"),
            os.path.join(_PKG, "csrc", "icikt_wave.h"), os.path.join(_PKG, "csrc", "icikt_host.h"),
            os.path.join(_PKG, "csrc", "icikt_transfer.h"), os.path.join(_PKG, "csrc", "icikt_colsort.h")]
@@ -61,7 +61,53 @@ EXPORTS = (
     "icikt_matrix_f64", "icikt_matrix_multi_f64", "icikt_multi_rank_phase_ms", "icikt_multi_ranks_used",
     "icikt_debug_step_stats", "icikt_multi_comm_ranks", "icikt_multi_block_bounds", "icikt_cost_blocks",
     "icikt_cor_pairs_f64", "icikt_col_medians_f64", "icikt_censor_counts_f64", "icikt_rank_order_f64",
+    "icikt_pairs_in", "icikt_matrix_in", "icikt_pairs_complete_in", "icikt_missingness_in", "icikt_cor_pairs_in",
+    "icikt_col_medians_in", "icikt_censor_counts_in", "icikt_rank_order_in", "icikt_convert_dev",
 )
+
+# icikt_input: the caller's matrix as a typed, strided view (ICIKT_DTYPE_*, ICIKT_ORDER_*)
+DTYPE_F64, DTYPE_F32, DTYPE_I32, DTYPE_I64 = range(4)
+ORDER_COL, ORDER_ROW = 0, 1
+DTYPES = {np.dtype(np.float64): DTYPE_F64, np.dtype(np.float32): DTYPE_F32, np.dtype(np.int32): DTYPE_I32,
+          np.dtype(np.int64): DTYPE_I64}
+
+
+class InputView(ctypes.Structure):
+    """icikt_input (include/icikt.h)."""
+    _fields_ = [("data", ctypes.c_void_p), ("dtype", ctypes.c_int), ("order", ctypes.c_int), ("ld", ctypes.c_int64)]
+
+
+def input_view(X):
+    """(array, dtype code, order, ld, copied): how the *_in entries read X where it lies.  No copy is made of a 2-D,
+    aligned, native-endian ndarray of float64, float32, int32 or int64 whose strides are (itemsize, k * itemsize) with
+    k >= n_feat (ORDER_COL, ld = k) or (k * itemsize, itemsize) with k >= n_samp (ORDER_ROW, ld = k): contiguous arrays
+    of either order and their slices X[:, a:b], X[a:b, :].  Everything else is copied to an F-ordered float64 array
+    (copied = True), as every matrix was before the view existed."""
+    if (isinstance(X, np.ndarray) and X.ndim == 2 and X.size > 0 and X.dtype in DTYPES and X.dtype.isnative
+            and X.flags.aligned):
+        n_feat, n_samp = X.shape
+        it = X.dtype.itemsize
+        s0, s1 = X.strides
+        code = DTYPES[X.dtype]
+        # (a dimension of extent 1 has a stride numpy never uses: such an array is read in the order the other
+        #  stride fits, column-major first)
+        if (s0 == it or n_feat == 1) and ((s1 > 0 and s1 % it == 0 and s1 // it >= n_feat) or n_samp == 1):
+            return X, code, ORDER_COL, (n_feat if n_samp == 1 else s1 // it), False
+        if (s1 == it or n_samp == 1) and ((s0 > 0 and s0 % it == 0 and s0 // it >= n_samp) or n_feat == 1):
+            return X, code, ORDER_ROW, (n_samp if n_feat == 1 else s0 // it), False
+    Xf = np.asfortranarray(X, dtype=np.float64)
+    if Xf.ndim != 2:
+        raise ValueError("X must be 2-D (features x samples)")
+    return Xf, DTYPE_F64, ORDER_COL, max(Xf.shape[0], 1), True
+
+
+def _view_arg(X, flags: int = 0):
+    """(array kept alive, icikt_input by reference, n_feat, n_samp, flags): FLAG_HOST_PINNED speaks of the caller's
+    memory, so it is cleared when the entry reads a copy of the library's own making."""
+    a, code, order, ld, copied = input_view(X)
+    v = InputView(a.ctypes.data, code, order, ld)
+    return a, v, a.shape[0], a.shape[1], (flags & ~FLAG_HOST_PINNED) if copied else flags
+
 
 
 class IciktError(RuntimeError):
@@ -172,6 +218,12 @@ def lib():
     L.icikt_multi_rank_phase_ms.argtypes = [c_vp, c_int, ctypes.POINTER(ctypes.c_double)]
     L.icikt_multi_ranks_used.argtypes = [c_vp]
     L.icikt_debug_step_stats.argtypes = [c_vp, c_vp, c_int]
+    # the *_in twins: (ctx, const icikt_input*, n_feat, n_samp, ...) where the _f64 entry has (ctx, X, n_feat, n_samp, ld, ...)
+    for nm in ("pairs", "matrix", "pairs_complete", "missingness", "cor_pairs", "col_medians", "censor_counts",
+               "rank_order"):
+        f64 = getattr(L, f"icikt_{nm}_f64").argtypes
+        getattr(L, f"icikt_{nm}_in").argtypes = [c_vp, ctypes.POINTER(InputView), c_i64, c_i64] + list(f64[5:])
+    L.icikt_convert_dev.argtypes = [c_vp, c_vp, c_int, c_int, c_i64, c_i64, c_i64, c_vp, c_i64]
     for name in EXPORTS:
         if getattr(L, name).restype is not None and name not in ("icikt_last_error", "icikt_num_pairs",
                                                                    "icikt_multi_last_error"):
@@ -202,11 +254,18 @@ def pinned_empty(shape, dtype=np.float64, order="C"):
 
 
 def _matrix_call(fn, handle, chk, X, global_na, pi, pj, perspective, alternative, continuity, flags, scale_max,
-                 diag_good, want_keep):
-    """icikt_matrix_f64 / icikt_matrix_multi_f64: (out5 [5, S, S], keep [S, n_feat] bool or None, reason_counts [5])."""
-    if not (isinstance(X, np.ndarray) and X.dtype == np.float64 and X.ndim == 2 and X.flags.f_contiguous):
-        X = np.asfortranarray(X, dtype=np.float64)
-    n_feat, n_samp = X.shape
+                 diag_good, want_keep, view=False):
+    """icikt_matrix_in (view) / icikt_matrix_f64 / icikt_matrix_multi_f64: (out5 [5, S, S], keep [S, n_feat] bool or
+    None, reason_counts [5])."""
+    if view:
+        X, v, n_feat, n_samp, flags = _view_arg(X, flags)
+        xargs = (ctypes.byref(v), n_feat, n_samp)
+    else:
+        if not (isinstance(X, np.ndarray) and X.dtype == np.float64 and X.ndim == 2 and X.flags.f_contiguous):
+            X = np.asfortranarray(X, dtype=np.float64)
+            flags &= ~FLAG_HOST_PINNED   # (a pageable copy of this function's)
+        n_feat, n_samp = X.shape
+        xargs = (_ptr(X), n_feat, n_samp, max(n_feat, 0))
     gna = np.ascontiguousarray([] if global_na is None else np.atleast_1d(global_na), dtype=np.float64)
     if pi is None:
         pi_a = pj_a = None
@@ -215,11 +274,12 @@ def _matrix_call(fn, handle, chk, X, global_na, pi, pj, perspective, alternative
         pi_a = np.ascontiguousarray(pi, dtype=np.int32)
         pj_a = np.ascontiguousarray(pj, dtype=np.int32)
         P = pi_a.shape[0]
-    out5 = np.empty((5, n_samp, n_samp), dtype=np.float64)
-    keep = np.empty((n_samp, n_feat), dtype=np.uint8) if want_keep else None
+    alloc = pinned_empty if (flags & FLAG_HOST_PINNED) else np.empty   # the result arrays are this function's: pinned when the call says so
+    out5 = alloc((5, n_samp, n_samp), dtype=np.float64)
+    keep = alloc((n_samp, n_feat), dtype=np.uint8) if want_keep else None
     rc5 = np.zeros(5, dtype=np.int64)
     alt = ALTERNATIVE.get(alternative, ALT_OTHER)
-    chk(fn(handle, _ptr(X), n_feat, n_samp, max(n_feat, 0), _ptr(gna) if gna.size else None, int(gna.size), _ptr(pi_a),
+    chk(fn(handle, *xargs, _ptr(gna) if gna.size else None, int(gna.size), _ptr(pi_a),
            _ptr(pj_a), P, PERSPECTIVE[perspective], alt, int(bool(continuity)), flags, int(bool(scale_max)),
            int(bool(diag_good)), _ptr(out5), _ptr(keep), _ptr(rc5)), fn.__name__)
     return out5, (keep.view(np.bool_) if keep is not None else None), rc5
@@ -236,6 +296,7 @@ class Context:
         if rc != SUCCESS:
             raise IciktError(f"icikt_ctx_create(device={device}) failed with code {rc}")
         self.device = int(device)
+        self.f64_entries = False   # tests / tools: the host methods call the _f64 entries on an F-ordered float64 copy
 
     def close(self):
         if getattr(self, "_h", None) is not None and self._h.value:
@@ -340,13 +401,34 @@ class Context:
         self._chk(lib().icikt_debug_set_plan(self._h, (spec or "").encode()), "icikt_debug_set_plan")
 
     # -- host-buffer path ------------------------------------------------------------------------
+    def _entry(self, name, X, flags=0, ld_floor=0):
+        """(entry function, its name, the arguments that describe X, n_feat, n_samp, flags, the array to keep alive):
+        icikt_<name>_in on input_view(X), read where it lies; with f64_entries icikt_<name>_f64 on an F-ordered
+        float64 copy."""
+        if self.f64_entries:
+            Xf = np.asfortranarray(X, dtype=np.float64)
+            if Xf.ndim != 2:
+                raise ValueError("X must be 2-D (features x samples)")
+            if Xf is not X:
+                flags &= ~FLAG_HOST_PINNED
+            n_feat, n_samp = Xf.shape
+            fn = f"icikt_{name}_f64"
+            return getattr(lib(), fn), fn, (_ptr(Xf), n_feat, n_samp, max(n_feat, ld_floor)), n_feat, n_samp, flags, Xf
+        a, v, n_feat, n_samp, flags = _view_arg(X, flags)
+        fn = f"icikt_{name}_in"
+        return getattr(lib(), fn), fn, (ctypes.byref(v), n_feat, n_samp), n_feat, n_samp, flags, (a, v)
+
+    def convert_dev(self, d_src: int, dtype: int, order: int, n_feat: int, n_samp: int, ld: int, d_dst: int,
+                    dst_ld: int):
+        """icikt_convert_dev: a device block of DTYPE_* cells in ORDER_* layout -> the column-major float64 device matrix
+        prepare_dev takes (asynchronous on the context's stream)."""
+        self._chk(lib().icikt_convert_dev(self._h, ctypes.c_void_p(d_src or 0), dtype, order, n_feat, n_samp, ld,
+                                          ctypes.c_void_p(d_dst or 0), dst_ld), "icikt_convert_dev")
+
     def pairs(self, X, pi=None, pj=None, perspective="global", alternative="two.sided", continuity=False,
               flags: int = 0, want_counts: bool = True):
         """ici_split() over a host matrix (n_feat x n_samp, NaN = missing); pairs 0-based or None = all."""
-        Xf = np.asfortranarray(X, dtype=np.float64)
-        if Xf.ndim != 2:
-            raise ValueError("X must be 2-D (features x samples)")
-        n_feat, n_samp = Xf.shape
+        fn, fname, xargs, n_feat, n_samp, flags, _keep = self._entry("pairs", X, flags)
         if pi is None:
             P = n_samp * (n_samp - 1) // 2
             pi_a = pj_a = None
@@ -362,9 +444,8 @@ class Context:
             cnt[...] = 0
         rsn[...] = 0
         alt = ALTERNATIVE.get(alternative, ALT_OTHER)
-        self._chk(lib().icikt_pairs_f64(self._h, _ptr(Xf), n_feat, n_samp, max(n_feat, 0), _ptr(pi_a), _ptr(pj_a), P,
-                                        PERSPECTIVE[perspective], alt, int(bool(continuity)), flags, _ptr(out),
-                                        _ptr(cnt), _ptr(rsn)), "icikt_pairs_f64")
+        self._chk(fn(self._h, *xargs, _ptr(pi_a), _ptr(pj_a), P, PERSPECTIVE[perspective], alt, int(bool(continuity)),
+                     flags, _ptr(out), _ptr(cnt), _ptr(rsn)), fname)
         return out, cnt, rsn
 
     def matrix(self, X, global_na=None, pi=None, pj=None, perspective="global", alternative="two.sided",
@@ -372,14 +453,14 @@ class Context:
         """ici_kendalltau() below its argument checks in ONE call (icikt_matrix_f64): the exclusion rule, the pair
         kernels and scale_and_reshape all run on the device.  X: raw data (features x samples, F-ordered float64 is
         taken as is); global_na: the values setup_missing_matrix excludes (NaN = NA, Inf, finite values)."""
-        return _matrix_call(lib().icikt_matrix_f64, self._h, self._chk, X, global_na, pi, pj, perspective, alternative,
-                            continuity, flags, scale_max, diag_good, want_keep)
+        fn = lib().icikt_matrix_f64 if self.f64_entries else lib().icikt_matrix_in
+        return _matrix_call(fn, self._h, self._chk, X, global_na, pi, pj, perspective, alternative,
+                            continuity, flags, scale_max, diag_good, want_keep, view=not self.f64_entries)
 
     def pairs_complete(self, X, pi, pj, alternative="two.sided", continuity=False, flags: int = 0,
                        want_counts: bool = False):
         """kt_fast(use = "pairwise.complete.obs"): per pair, rows with a missing value in either vector are dropped."""
-        Xf = np.asfortranarray(X, dtype=np.float64)
-        n_feat, n_samp = Xf.shape
+        fn, fname, xargs, n_feat, n_samp, flags, _keep = self._entry("pairs_complete", X, flags)
         pi_a = np.ascontiguousarray(pi, dtype=np.int32)
         pj_a = np.ascontiguousarray(pj, dtype=np.int32)
         P = pi_a.shape[0]
@@ -387,51 +468,39 @@ class Context:
         cnt = np.zeros((P, len(CNT_FIELDS)), dtype=np.int64) if want_counts else None
         rsn = np.zeros(P, dtype=np.int32)
         alt = ALTERNATIVE.get(alternative, ALT_OTHER)
-        self._chk(lib().icikt_pairs_complete_f64(self._h, _ptr(Xf), n_feat, n_samp, max(n_feat, 0), _ptr(pi_a), _ptr(pj_a),
-                                                 P, alt, int(bool(continuity)), flags, _ptr(out), _ptr(cnt), _ptr(rsn)),
-                  "icikt_pairs_complete_f64")
+        self._chk(fn(self._h, *xargs, _ptr(pi_a), _ptr(pj_a), P, alt, int(bool(continuity)), flags, _ptr(out), _ptr(cnt),
+                     _ptr(rsn)), fname)
         return out, cnt, rsn
 
     def cor_pairs(self, X, pi, pj, method="pearson", pairwise=False, alternative="two.sided", continuity=False,
                   flags: int = 0):
         """cor_fast's pairs (icikt_cor_pairs_f64): (out3 [P, 3]: rho, p-value, n_values; reasons [P], ICIKT_COR_*)."""
-        Xf = np.asfortranarray(X, dtype=np.float64)
-        if Xf.ndim != 2:
-            raise ValueError("X must be 2-D (features x samples)")
-        n_feat, n_samp = Xf.shape
+        fn, fname, xargs, n_feat, n_samp, flags, _keep = self._entry("cor_pairs", X, flags)
         pi_a = np.ascontiguousarray(pi, dtype=np.int32)
         pj_a = np.ascontiguousarray(pj, dtype=np.int32)
         P = pi_a.shape[0]
         out = np.empty((P, 3), dtype=np.float64)
         rsn = np.zeros(P, dtype=np.int32)
-        self._chk(lib().icikt_cor_pairs_f64(self._h, _ptr(Xf), n_feat, n_samp, max(n_feat, 0), _ptr(pi_a), _ptr(pj_a), P,
-                                            METHOD[method], int(bool(pairwise)), ALTERNATIVE[alternative],
-                                            int(bool(continuity)), flags, _ptr(out), _ptr(rsn)), "icikt_cor_pairs_f64")
+        self._chk(fn(self._h, *xargs, _ptr(pi_a), _ptr(pj_a), P, METHOD[method], int(bool(pairwise)),
+                     ALTERNATIVE[alternative], int(bool(continuity)), flags, _ptr(out), _ptr(rsn)), fname)
         return out, rsn
 
     # -- missing-value diagnostics (icikt_col_medians_f64 / icikt_censor_counts_f64 / icikt_rank_order_f64) --------
-    @staticmethod
-    def _diag_input(X, global_na):
-        Xf = np.asfortranarray(X, dtype=np.float64)
-        if Xf.ndim != 2:
-            raise ValueError("X must be 2-D (features x samples)")
+    def _diag_input(self, name, X, global_na, flags):
         gna = np.ascontiguousarray([] if global_na is None else np.atleast_1d(global_na), dtype=np.float64)
-        return Xf, gna
+        return self._entry(name, X, flags, ld_floor=1), gna
 
     def col_medians(self, X, na_rm=False, global_na=None, flags: int = 0):
         """stats::median of every column (NaN = NA; global_na: cells the rule excludes as well)."""
-        Xf, gna = self._diag_input(X, global_na)
-        n_feat, n_samp = Xf.shape
+        (fn, fname, xargs, n_feat, n_samp, flags, _keep), gna = self._diag_input("col_medians", X, global_na, flags)
         out = np.empty(n_samp, dtype=np.float64)
-        self._chk(lib().icikt_col_medians_f64(self._h, _ptr(Xf), n_feat, n_samp, max(n_feat, 1), _ptr(gna) if gna.size
-                                              else None, int(gna.size), int(bool(na_rm)), flags, _ptr(out)),
-                  "icikt_col_medians_f64")
+        self._chk(fn(self._h, *xargs, _ptr(gna) if gna.size else None, int(gna.size), int(bool(na_rm)), flags, _ptr(out)),
+                  fname)
         return out
 
     def censor_counts(self, X, global_na, cls, n_class: int, flags: int = 0, want_medians: bool = False):
         """test_left_censorship's per-class counts: (trials [n_class], success [n_class], n_excluded, medians)."""
-        Xf, gna = self._diag_input(X, global_na)
-        n_feat, n_samp = Xf.shape
+        (fn, fname, xargs, n_feat, n_samp, flags, _keep), gna = self._diag_input("censor_counts", X, global_na, flags)
         cls_a = np.ascontiguousarray(cls, dtype=np.int32)
         if cls_a.shape != (n_samp,):
             raise ValueError("cls must give one class per column")
@@ -439,20 +508,17 @@ class Context:
         success = np.zeros(n_class, dtype=np.int64)
         n_ex = np.zeros(1, dtype=np.int64)
         med = np.empty(n_samp, dtype=np.float64) if want_medians else None
-        self._chk(lib().icikt_censor_counts_f64(self._h, _ptr(Xf), n_feat, n_samp, max(n_feat, 1),
-                                                _ptr(gna) if gna.size else None, int(gna.size), _ptr(cls_a),
-                                                int(n_class), flags, _ptr(trials), _ptr(success), _ptr(n_ex), _ptr(med)),
-                  "icikt_censor_counts_f64")
+        self._chk(fn(self._h, *xargs, _ptr(gna) if gna.size else None, int(gna.size), _ptr(cls_a), int(n_class), flags,
+                     _ptr(trials), _ptr(success), _ptr(n_ex), _ptr(med)), fname)
         return trials, success, int(n_ex[0]), med
 
     def rank_order(self, X, global_na, cols, flags: int = 0, want_data: bool = True, n_feat: int | None = None):
         """rank_order_data for the columns `cols` of X: dict of n_kept, n_na, median_rank, row_order, col_order and
         (want_data) original / ordered (n_kept x len(cols)).  n_feat: only the first n_feat rows of X count (X then
         passes with its own row count as the leading dimension)."""
-        Xf, gna = self._diag_input(X, global_na)
-        ld, n_samp = Xf.shape
-        n_feat = ld if n_feat is None else int(n_feat)
-        ld = max(ld, 1)
+        (fn, fname, xargs, rows, n_samp, flags, _keep), gna = self._diag_input("rank_order", X, global_na, flags)
+        n_feat = rows if n_feat is None else int(n_feat)
+        xargs = (xargs[0], n_feat) + tuple(xargs[2:])   # (the view / ld keeps X's own row count as the leading dimension)
         cols_a = np.ascontiguousarray(cols, dtype=np.int32)
         n_cols = cols_a.shape[0]
         n_kept = np.zeros(1, dtype=np.int64)
@@ -462,10 +528,8 @@ class Context:
         cord = np.empty(max(n_cols, 1), dtype=np.int32)
         orig = np.empty(max(n_feat * n_cols, 1), dtype=np.float64) if want_data else None
         ordd = np.empty(max(n_feat * n_cols, 1), dtype=np.float64) if want_data else None
-        self._chk(lib().icikt_rank_order_f64(self._h, _ptr(Xf), n_feat, n_samp, ld, _ptr(gna) if gna.size else None,
-                                             int(gna.size), _ptr(cols_a), n_cols, flags, _ptr(n_kept), _ptr(n_na),
-                                             _ptr(med), _ptr(rord), _ptr(cord), _ptr(orig), _ptr(ordd)),
-                  "icikt_rank_order_f64")
+        self._chk(fn(self._h, *xargs, _ptr(gna) if gna.size else None, int(gna.size), _ptr(cols_a), n_cols, flags,
+                     _ptr(n_kept), _ptr(n_na), _ptr(med), _ptr(rord), _ptr(cord), _ptr(orig), _ptr(ordd)), fname)
         k = int(n_kept[0])
         out = {"n_kept": k, "n_na": n_na[:n_feat], "median_rank": med[:n_feat], "row_order": rord[:k],
                "col_order": cord[:n_cols]}
@@ -487,13 +551,11 @@ class Context:
         return out, dict(zip(CNT_FIELDS, cnt.tolist())), int(rsn[0])
 
     def missingness(self, X, pi, pj):
-        Xf = np.asfortranarray(X, dtype=np.float64)
-        n_feat, n_samp = Xf.shape
+        fn, fname, xargs, n_feat, n_samp, _flags, _keep = self._entry("missingness", X)
         pi_a = np.ascontiguousarray(pi, dtype=np.int32)
         pj_a = np.ascontiguousarray(pj, dtype=np.int32)
         out = np.zeros(pi_a.shape[0], dtype=np.int64)
-        self._chk(lib().icikt_missingness_f64(self._h, _ptr(Xf), n_feat, n_samp, max(n_feat, 0), _ptr(pi_a),
-                                              _ptr(pj_a), pi_a.shape[0], _ptr(out)), "icikt_missingness_f64")
+        self._chk(fn(self._h, *xargs, _ptr(pi_a), _ptr(pj_a), pi_a.shape[0], _ptr(out)), fname)
         return out
 
 

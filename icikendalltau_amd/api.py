@@ -271,8 +271,9 @@ def ici_kt_counts(x, y, perspective="local", device=None, exact_int64=False):
 # --------------------------------------------------------------------------------------------------
 # input checks (R/utils.R:1-66)
 # --------------------------------------------------------------------------------------------------
-def _as_matrix(data_matrix, colnames, arg):
-    """check_if_colnames_null / transform_to_matrix / check_if_numeric."""
+def _as_matrix(data_matrix, colnames, arg, keep_dtype=False):
+    """check_if_colnames_null / transform_to_matrix / check_if_numeric.  keep_dtype: a float32, int32 or int64 matrix
+    stays what it is (a HipEngine's context reads it where it lies, _for_engine); everything else is float64."""
     if pd is not None and isinstance(data_matrix, pd.DataFrame):
         print(f"i `{arg}` is a data.frame, converting to matrix ...")  # R/utils.R:53-57
         if colnames is None:
@@ -288,7 +289,18 @@ def _as_matrix(data_matrix, colnames, arg):
     colnames = [str(c) for c in colnames]
     if len(colnames) != arr.shape[1]:
         raise ValueError("length of colnames does not match the number of columns")
+    if keep_dtype and arr.dtype in _lib.DTYPES:
+        return arr, colnames
     return np.asarray(arr, dtype=np.float64), colnames
+
+
+def _for_engine(X, eng, fortran=True):
+    """The matrix as an engine takes it.  A HipEngine's context reads float64, float32, int32 and int64 matrices of
+    either memory order where they lie (_lib.input_view: no host copy); every other engine gets the float64 matrix it
+    always got."""
+    if isinstance(eng, HipEngine):
+        return X
+    return np.asfortranarray(X, dtype=np.float64) if fortran else np.asarray(X, dtype=np.float64)
 
 
 def setup_missing_matrix(data_matrix: np.ndarray, global_na) -> np.ndarray:
@@ -474,7 +486,7 @@ def ici_kendalltau(data_matrix, global_na=(float("nan"), float("inf"), 0), persp
     completeness, cor), "run_time"}``.  Column names are required, as in the reference (``colnames=``
     for a bare ndarray).
     """
-    data_matrix, names = _as_matrix(data_matrix, colnames, "data_matrix")
+    data_matrix, names = _as_matrix(data_matrix, colnames, "data_matrix", keep_dtype=True)
     n_sample = data_matrix.shape[1]
 
     _dist, _rank, world = _dist_info()
@@ -501,7 +513,7 @@ def ici_kendalltau(data_matrix, global_na=(float("nan"), float("inf"), 0), persp
         else:
             pi, pj, _core = setup_comparisons(names, include_only, diag_good, ncore=ncore)
         t1 = time.perf_counter()
-        out5, keep, rcounts = eng.matrix(data_matrix, global_na, pi, pj, perspective, alternative, continuity,
+        out5, keep, rcounts = eng.matrix(_for_engine(data_matrix, eng, fortran=False), global_na, pi, pj, perspective, alternative, continuity,
                                          scale_max, diag_good)
         t_diff = time.perf_counter() - t1
         for code in (_lib.REASON_SHORT, _lib.REASON_SINGLE_UNIQUE, _lib.REASON_TIES_EQ_TOTAL):
@@ -513,6 +525,7 @@ def ici_kendalltau(data_matrix, global_na=(float("nan"), float("inf"), 0), persp
         res["run_time"] = t_diff
         return res
 
+    data_matrix = np.asarray(data_matrix, dtype=np.float64)   # (the branches below edit the matrix on the host)
     exclude_loc = setup_missing_matrix(data_matrix, global_na)
     exclude_data = _masked_fortran(data_matrix, exclude_loc)
     pi, pj, core = setup_comparisons(names, include_only, diag_good, ncore=ncore)
@@ -642,7 +655,7 @@ def kt_fast(x, y=None, use="everything", alternative="two.sided", continuity=Fal
     if y is None:
         if not (pd is not None and isinstance(x, pd.DataFrame)) and np.ndim(x) < 2:
             raise ValueError("`x` and `y` should both be provided as vectors, or `x` should be matrix-like.")
-        X, names = _as_matrix(x, colnames, "x")
+        X, names = _as_matrix(x, colnames, "x", keep_dtype=True)
     else:
         if np.ndim(x) > 1 or np.ndim(y) > 1:
             raise ValueError("Both `x` and `y` must be vectors.")
@@ -664,16 +677,17 @@ def kt_fast(x, y=None, use="everything", alternative="two.sided", continuity=Fal
         if keep.sum() == 0:
             do_computation = False
         else:
-            X = X[keep]
+            X = np.asarray(X, dtype=np.float64)[keep]
     if do_computation:
         t1 = time.perf_counter()
         if na_method == "pairwise.complete.obs" and np.isnan(X).any() and hasattr(eng, "pairs_complete"):
-            # masking, per-pair sorts and counting on the device (icikt_pairs_complete_f64)
-            out, rsn = eng.pairs_complete(np.asfortranarray(X), pi, pj)
+            # masking, per-pair sorts and counting on the device (icikt_pairs_complete_in)
+            out, rsn = eng.pairs_complete(_for_engine(X, eng), pi, pj)
             for r in rsn[rsn > 1]:
                 _warn_reason(r)
             tau, pvalue = out[:, 0].copy(), out[:, 1].copy()
         elif na_method == "pairwise.complete.obs" and np.isnan(X).any():
+            X = np.asarray(X, dtype=np.float64)
             na = np.isnan(X)
             for b in range(0, P, max_pair_chunk):
                 sl = slice(b, min(P, b + max_pair_chunk))
@@ -688,7 +702,7 @@ def kt_fast(x, y=None, use="everything", alternative="two.sided", continuity=Fal
                     _warn_reason(r)
                 tau[sl], pvalue[sl] = out[:, 0], out[:, 1]
         else:
-            out, rsn = eng.pairs(np.asfortranarray(X), pi, pj, "local", "two.sided", False)
+            out, rsn = eng.pairs(_for_engine(X, eng), pi, pj, "local", "two.sided", False)
             for r in rsn[rsn > 1]:
                 _warn_reason(r)
             tau, pvalue = out[:, 0].copy(), out[:, 1].copy()
@@ -945,7 +959,7 @@ def cor_fast(x, y=None, use="everything", method="pearson", alternative="two.sid
     if y is None:
         if not (pd is not None and isinstance(x, pd.DataFrame)) and np.ndim(x) < 2:
             raise ValueError("`x` and `y` should both be provided as vectors, or `x` should be matrix-like.")
-        X, names = _as_matrix(x, colnames, "x")
+        X, names = _as_matrix(x, colnames, "x", keep_dtype=True)
     else:
         if np.ndim(x) > 1 or np.ndim(y) > 1:
             raise ValueError("Both `x` and `y` must be vectors.")
@@ -963,7 +977,7 @@ def cor_fast(x, y=None, use="everything", method="pearson", alternative="two.sid
         if keep.sum() == 0:
             do_computation = False
         else:
-            X = X[keep]
+            X = np.asarray(X, dtype=np.float64)[keep]
     pairwise = na_method == "pairwise.complete.obs" and bool(np.isnan(X).any())
     t_diff = 0.0
     if do_computation:
@@ -972,9 +986,9 @@ def cor_fast(x, y=None, use="everything", method="pearson", alternative="two.sid
         eng = engine or _default_engine()
         t1 = time.perf_counter()
         if hasattr(eng, "cor_pairs"):
-            out, rsn = eng.cor_pairs(np.asfortranarray(X), pi, pj, method, pairwise, alternative, continuity)
+            out, rsn = eng.cor_pairs(_for_engine(X, eng), pi, pj, method, pairwise, alternative, continuity)
         else:
-            out, rsn = _cor_pairs_numpy(X, pi, pj, method, pairwise, alternative, continuity)
+            out, rsn = _cor_pairs_numpy(np.asarray(X, dtype=np.float64), pi, pj, method, pairwise, alternative, continuity)
         t_diff = time.perf_counter() - t1
         if (rsn == _lib.COR_TIES).any():
             warnings.warn(_COR_TIES_WARNING, RuntimeWarning, stacklevel=2)
@@ -1100,7 +1114,7 @@ def _diag_matrix(data_matrix, colnames, arg):
         rows = data_matrix.index
     elif colnames is None:
         colnames = list(range(np.shape(data_matrix)[1])) if np.ndim(data_matrix) == 2 else []
-    X, names = _as_matrix(data_matrix, colnames, arg)
+    X, names = _as_matrix(data_matrix, colnames, arg, keep_dtype=True)
     return X, names, rows
 
 
@@ -1128,6 +1142,7 @@ def _device_rule(X, global_na):
     vals = [] if global_na is None else [float(v) for v in np.atleast_1d(np.asarray(global_na, dtype=np.float64))]
     if len({v for v in vals if math.isfinite(v)}) <= _lib.MASK_VALS:
         return X, vals, None
+    X = np.asarray(X, dtype=np.float64)
     excl = setup_missing_matrix(X, vals)
     return _masked_fortran(X, excl), [math.nan], excl
 
@@ -1220,11 +1235,10 @@ def calculate_matrix_medians(in_matrix, use="col", na_rm=False, engine=None):
     X, _names, _rows = _diag_matrix(in_matrix, None, "in_matrix")
     if use == "row":
         X = X.T
-    X = np.asfortranarray(X)
     eng = engine or _default_engine()
     if hasattr(eng, "col_medians"):
-        return eng.col_medians(X, na_rm)
-    return _col_medians_numpy(X, na_rm)
+        return eng.col_medians(_for_engine(X, eng), na_rm)
+    return _col_medians_numpy(np.asfortranarray(X, dtype=np.float64), na_rm)
 
 
 def test_left_censorship(data_matrix, global_na=(float("nan"), float("inf"), 0), sample_classes=None, engine=None):
@@ -1241,8 +1255,8 @@ def test_left_censorship(data_matrix, global_na=(float("nan"), float("inf"), 0),
     """
     X, _names, _rows = _diag_matrix(data_matrix, None, "data_matrix")
     levels, cls = _class_levels(sample_classes, X.shape[1], "A")
-    Xd, gna, excl = _device_rule(np.asfortranarray(X), global_na)
     eng = engine or _default_engine()
+    Xd, gna, excl = _device_rule(_for_engine(X, eng), global_na)
     if hasattr(eng, "censor_counts"):
         trials, success, n_ex = eng.censor_counts(Xd, gna, cls, len(levels))
     else:
@@ -1276,8 +1290,8 @@ def rank_order_data(data_matrix, global_na=(float("nan"), float("inf"), 0), samp
     """
     X, names, rows = _diag_matrix(data_matrix, colnames, "data_matrix")
     levels, cls = _class_levels(sample_classes, X.shape[1], "rmf_abcd")
-    Xd, gna, _excl = _device_rule(np.asfortranarray(X), global_na)
     eng = engine or _default_engine()
+    Xd, gna, _excl = _device_rule(_for_engine(X, eng), global_na)
     row_labels = np.asarray(rows) if rows is not None else np.arange(X.shape[0])
     out = {}
     for k, level in enumerate(levels):

@@ -586,9 +586,25 @@ namespace icikt {
 namespace host {
 
 int check_shape(icikt_ctx* c, const char* who, int64_t n_feat, int64_t n_samp, int64_t ld, bool wide_ok) {
-  if (n_feat < 0 || n_samp < 0 || ld < n_feat) return fail(c, ICIKT_E_INVALID, std::string(who) + ": bad matrix shape");
+  if (n_feat < 0 || n_samp < 0 || ld < n_feat) return fail(c, ICIKT_E_INVALID, std::string(who) + ": bad matrix shape (n_feat, n_samp or ld)");
   if (n_feat > ICIKT_MAX_FEATURES_WIDE) return fail(c, ICIKT_E_TOO_LONG, std::string(who) + ": " + kTooLong);
   if (n_feat > ICIKT_MAX_FEATURES && !wide_ok) return fail(c, ICIKT_E_TOO_LONG, std::string(who) + ": " + kNoWide);
+  return ICIKT_SUCCESS;
+}
+
+int check_view(icikt_ctx* c, const char* who, const icikt_input* X, int64_t n_feat, int64_t n_samp, bool wide_ok) {
+  const std::string w(who);
+  if (!X) return fail(c, ICIKT_E_INVALID, w + ": X is null (the icikt_input view of the matrix)");
+  if (X->dtype < ICIKT_DTYPE_F64 || X->dtype > ICIKT_DTYPE_I64)
+    return fail(c, ICIKT_E_INVALID, w + ": X->dtype must be one of ICIKT_DTYPE_F64, _F32, _I32, _I64");
+  if (X->order != ICIKT_ORDER_COL && X->order != ICIKT_ORDER_ROW)
+    return fail(c, ICIKT_E_INVALID, w + ": X->order must be ICIKT_ORDER_COL or ICIKT_ORDER_ROW");
+  const bool row = X->order == ICIKT_ORDER_ROW;
+  if (row && n_feat >= 0 && n_samp >= 0 && X->ld < n_samp)
+    return fail(c, ICIKT_E_INVALID, w + ": bad matrix shape (X->ld is below n_samp, the row of a row-major view)");
+  const int rc = check_shape(c, who, n_feat, n_samp, row ? n_feat : X->ld, wide_ok);
+  if (rc) return rc;
+  if (n_feat > 0 && n_samp > 0 && !X->data) return fail(c, ICIKT_E_INVALID, w + ": null matrix");
   return ICIKT_SUCCESS;
 }
 
@@ -596,6 +612,8 @@ int check_shape(icikt_ctx* c, const char* who, int64_t n_feat, int64_t n_samp, i
 }  // namespace icikt
 
 using icikt::host::check_shape;
+using icikt::host::check_view;
+using icikt::host::f64_view;
 
 static int check_col_range(icikt_ctx* c, int64_t n_samp, int64_t col_begin, int64_t col_end, int64_t alloc_cols,
                            int64_t n_feat = 0) {
@@ -777,7 +795,7 @@ int icikt_prepare_cols_f64(icikt_ctx* c, const double* X, int64_t n_feat, int64_
   rc = prepare_alloc(c, n_feat, n_samp, alloc_cols, col_end - col_begin);
   if (rc) return rc;
   const icikt::host::PinnedScope scope(c, flags);
-  rc = icikt::host::upload_and_prepare(c, X, n_feat, n_samp, ld, col_begin, col_end, flags);
+  rc = icikt::host::upload_and_prepare(c, f64_view(X, ld), n_feat, n_samp, col_begin, col_end, flags);
   if (rc) return rc;
   c->prepared = true;
   return ICIKT_SUCCESS;
@@ -972,7 +990,11 @@ namespace host {
 // while chunk i + 1 crosses PCIe.  How the caller's matrix is read: MatrixUpload (icikt_transfer.h).
 // prepass: kPrepassFull = K0; kPrepassMask = missing-row bitsets only (pairwise_completeness); kPrepassNone = the
 // columns are only copied (icikt_pairs_complete_f64 sorts masked copies, not the columns).
-int upload_and_prepare(icikt_ctx* c, const double* X, int64_t n_feat, int64_t n_samp, int64_t ld, int64_t col_begin,
+// X is the caller's view of the whole matrix; a view that is not column-major float64 is widened / transposed on the
+// device chunk by chunk (MatrixUpload::copy), so everything behind a chunk's event sees the same float64 columns.
+constexpr size_t kRowRunBytes = 512;               // a row-major chunk: runs of at least this many bytes ...
+constexpr size_t kRowHalfMax = (size_t)64 << 20;   // ... while a half of the staging blocks stays within this
+int upload_and_prepare(icikt_ctx* c, const icikt_input& X, int64_t n_feat, int64_t n_samp, int64_t col_begin,
                        int64_t col_end, uint32_t flags, bool pipelined, const std::function<int(size_t, int64_t)>* on_chunk,
                        int prepass) {
   // what runs over the columns of a chunk once they are on the device
@@ -996,16 +1018,24 @@ int upload_and_prepare(icikt_ctx* c, const double* X, int64_t n_feat, int64_t n_
     // pre-pass launches the last pair-kernel launch waits for (c4: ten chunks of 104 columns finished their pre-pass
     // 1.4 ms after the last copy, four chunks of 256 right behind it)
     if (pipelined) chunk = std::max<int64_t>(chunk, std::min<int64_t>(c->prop.multiProcessorCount, (n_samp / 4) & ~(int64_t)1));
+    // A row-major view gives the chunk as n_feat runs of `chunk` cells, and 8 MB of a tall matrix are few columns (four
+    // float64 columns at 262 144 rows: runs of 32 bytes).  The host's packing rate grows with the run up to about 512
+    // bytes (DESIGN.md section 11 has the figures), so a row-major chunk is at least that wide where a half of the
+    // staging blocks stays within 64 MB.
+    if (X.order == ICIKT_ORDER_ROW) {
+      const size_t es = dtype_bytes(X.dtype);
+      chunk = std::max<int64_t>(chunk, (int64_t)std::min(kRowRunBytes / es, std::max<size_t>(1, kRowHalfMax / ((size_t)n_feat * es))));
+    }
     if (prepass == kPrepassFull) chunk = std::min<int64_t>(chunk, std::max(1, c->sort_chunk));
-    const size_t span = ((size_t)(ncols - 1) * (size_t)ld + (size_t)n_feat) * sizeof(double);
-    MatrixUpload up{c, col_bytes, (size_t)ld * sizeof(double), (size_t)chunk * col_bytes};
+    const size_t span = view_span(view_from_col(X, col_begin), n_feat, ncols);
+    MatrixUpload up{c, X, n_feat, view_is_plain(X) ? chunk : std::min<int64_t>(chunk, ncols)};
     hipError_t e = up.begin(span, pipelined ? c->prep_stream : nullptr);
     int k = 0;
     const int64_t first_chunk = chunk;   // (a short first chunk was measured twice: no gain -- what the last pair-kernel launch waits for is the last chunk's pre-pass, which finds no free CU until the launch before it drains)
     for (int64_t c0 = col_begin, step = first_chunk; c0 < col_end && e == hipSuccess && rc == 0; c0 += step, step = chunk, ++k) {
       const int64_t nc = std::min<int64_t>(step, col_end - c0);
       hipEvent_t ev = nullptr;
-      e = up.copy(k, c->d_X.p + (size_t)c0 * (size_t)n_feat, X + c0 * ld, nc, &ev);
+      e = up.copy(k, c->d_X.p + (size_t)c0 * (size_t)n_feat, c0, nc, &ev);
       if (pipelined) {
         // the chunk's pre-pass on the pre-pass stream; an event of its own tells the pair kernel's stream when
         if (e == hipSuccess) e = hipStreamWaitEvent(c->prep_stream, ev, 0);
@@ -1063,8 +1093,11 @@ void prebuild_units(icikt_ctx* c) {
 // launch per chunk behind that chunk's pre-pass event.  The pairs among the columns that have arrived are counted
 // while the rest of the matrix still crosses PCIe: the available work grows with the square of the arrived columns,
 // so after the first millisecond of a c4-sized call the GPU never waits for the link again.
-int upload_prepare_pairs(icikt_ctx* c, const double* X, int64_t n_feat, int64_t n_samp, int64_t ld, uint32_t flags) {
+int upload_prepare_pairs(icikt_ctx* c, const icikt_input& X, int64_t n_feat, int64_t n_samp, uint32_t flags) {
   const size_t col_bytes = (size_t)n_feat * sizeof(double);
+  // (the size that decides for the pipeline is the float64 matrix's, whatever the view's element type and order: a view
+  //  runs the launches its float64 copy runs)
+  const int64_t ld = view_is_plain(X) ? X.ld : n_feat;
   const size_t span = (n_samp > 0 && n_feat > 0) ? ((size_t)(n_samp - 1) * (size_t)ld + (size_t)n_feat) * sizeof(double) : 0;
   const bool can = !c->pv.wide && n_feat > 0 && c->n_pairs > 0;
   const bool want = c->pipe_mode < 0 ? (span >= ((size_t)24 << 20)) : (c->pipe_mode == 1 && (size_t)n_samp * col_bytes > ((size_t)8 << 20));
@@ -1073,7 +1106,7 @@ int upload_prepare_pairs(icikt_ctx* c, const double* X, int64_t n_feat, int64_t 
   // size, and a launch per chunk puts those latencies one behind the other (50 000 x 96 tied columns: 15.5 -> 9.5 ms)
   const bool merge_launches = c->plan_ov.merge >= 0 ? c->plan_ov.merge != 0 : c->n_pairs < (int64_t)4 * 48 * c->prop.multiProcessorCount;
   if (!(can && want)) {
-    int rc = upload_and_prepare(c, X, n_feat, n_samp, ld, 0, n_samp, flags);
+    int rc = upload_and_prepare(c, X, n_feat, n_samp, 0, n_samp, flags);
     if (rc) return rc;
     c->prepared = true;
     prebuild_units(c);   // host work under the copies; icikt_run_dev uploads the list
@@ -1137,7 +1170,7 @@ int upload_prepare_pairs(icikt_ctx* c, const double* X, int64_t n_feat, int64_t 
       return launch_pair_tasks(c, pl, (int)first, (int)cnt);
     };
     rc = timer_begin(c, ICIKT_K_PAIRS, flags);
-    if (rc == 0) rc = upload_and_prepare(c, X, n_feat, n_samp, ld, 0, n_samp, flags & ~ICIKT_FLAG_TIMING, true, &on_chunk);
+    if (rc == 0) rc = upload_and_prepare(c, X, n_feat, n_samp, 0, n_samp, flags & ~ICIKT_FLAG_TIMING, true, &on_chunk);
     if (rc) { (void)hipStreamSynchronize(c->prep_stream); return rc; }
     c->prepared = true;
     nchunks = c->chunk_col_end.size();
@@ -1146,7 +1179,7 @@ int upload_prepare_pairs(icikt_ctx* c, const double* X, int64_t n_feat, int64_t 
     c->units_dirty = true;
     t_enq = t_built = t_up = ms_since();
   } else {
-  rc = upload_and_prepare(c, X, n_feat, n_samp, ld, 0, n_samp, flags & ~ICIKT_FLAG_TIMING, true, nullptr);
+  rc = upload_and_prepare(c, X, n_feat, n_samp, 0, n_samp, flags & ~ICIKT_FLAG_TIMING, true, nullptr);
   if (rc) return rc;
   c->prepared = true;
   t_enq = ms_since();
@@ -1228,13 +1261,12 @@ int check_pair_list(icikt_ctx* c, const char* who, const int32_t* pi, const int3
   return ICIKT_SUCCESS;
 }
 
-int check_pair_args(icikt_ctx* c, const char* who, const double* X, int64_t n_feat, int64_t n_samp, int64_t ld,
+int check_pair_args(icikt_ctx* c, const char* who, const icikt_input* X, int64_t n_feat, int64_t n_samp,
                     const int32_t* pi, const int32_t* pj, int64_t* n_pairs, const void* out, bool out5,
                     int perspective, int alternative) {
   const std::string w(who);
-  int rc = check_shape(c, who, n_feat, n_samp, ld);
+  int rc = check_view(c, who, X, n_feat, n_samp);
   if (rc) return rc;
-  if (n_feat > 0 && n_samp > 0 && !X) return fail(c, ICIKT_E_INVALID, w + ": null matrix");
   if (pi == nullptr) {
     if (pj != nullptr) return fail(c, ICIKT_E_INVALID, w + ": pi is null but pj is not");
     *n_pairs = n_samp * (n_samp - 1) / 2;
@@ -1258,9 +1290,17 @@ extern "C" {
 int icikt_pairs_f64(icikt_ctx* c, const double* X, int64_t n_feat, int64_t n_samp, int64_t ld,
                     const int32_t* pi, const int32_t* pj, int64_t n_pairs, int perspective, int alternative,
                     int continuity, uint32_t flags, double* out4, int64_t* counts, int32_t* reasons) {
+  const icikt_input v = f64_view(X, ld);
+  return icikt_pairs_in(c, &v, n_feat, n_samp, pi, pj, n_pairs, perspective, alternative, continuity, flags, out4, counts,
+                        reasons);
+}
+
+int icikt_pairs_in(icikt_ctx* c, const icikt_input* X, int64_t n_feat, int64_t n_samp, const int32_t* pi,
+                   const int32_t* pj, int64_t n_pairs, int perspective, int alternative, int continuity, uint32_t flags,
+                   double* out4, int64_t* counts, int32_t* reasons) {
   if (!c) return ICIKT_E_INVALID;
   // every argument is validated before the first asynchronous copy reads the caller's memory
-  int rc = icikt::host::check_pair_args(c, "pairs", X, n_feat, n_samp, ld, pi, pj, &n_pairs, out4, false, perspective,
+  int rc = icikt::host::check_pair_args(c, "pairs", X, n_feat, n_samp, pi, pj, &n_pairs, out4, false, perspective,
                                         alternative);
   if (rc) return rc;
   rc = use_device(c);
@@ -1273,7 +1313,7 @@ int icikt_pairs_f64(icikt_ctx* c, const double* X, int64_t n_feat, int64_t n_sam
   // crosses PCIe (it used to wait for the copies first and build the list afterwards, with the GPU idle: 1.2 ms of
   // 14.3 on c4).  Nothing may still read the caller's matrix when the call returns: end_call.
   const icikt::host::PinnedScope scope(c, flags);
-  rc = icikt::host::upload_prepare_pairs(c, X, n_feat, n_samp, ld, flags);
+  rc = icikt::host::upload_prepare_pairs(c, *X, n_feat, n_samp, flags);
   const int64_t P = c->n_pairs;
   if (rc || P == 0) return icikt::host::end_call(c, "pairs", rc);
   auto body = [&]() -> int {
@@ -1329,8 +1369,17 @@ int icikt_matrix_f64(icikt_ctx* c, const double* X, int64_t n_feat, int64_t n_sa
                      int n_global_na, const int32_t* pi, const int32_t* pj, int64_t n_pairs, int perspective,
                      int alternative, int continuity, uint32_t flags, int scale_max, int diag_good, double* out5,
                      uint8_t* keep, int64_t* reason_counts) {
+  const icikt_input v = f64_view(X, ld);
+  return icikt_matrix_in(c, &v, n_feat, n_samp, global_na, n_global_na, pi, pj, n_pairs, perspective, alternative,
+                         continuity, flags, scale_max, diag_good, out5, keep, reason_counts);
+}
+
+int icikt_matrix_in(icikt_ctx* c, const icikt_input* X, int64_t n_feat, int64_t n_samp, const double* global_na,
+                    int n_global_na, const int32_t* pi, const int32_t* pj, int64_t n_pairs, int perspective,
+                    int alternative, int continuity, uint32_t flags, int scale_max, int diag_good, double* out5,
+                    uint8_t* keep, int64_t* reason_counts) {
   if (!c) return ICIKT_E_INVALID;
-  int rc = icikt::host::check_pair_args(c, "matrix", X, n_feat, n_samp, ld, pi, pj, &n_pairs, out5, true, perspective,
+  int rc = icikt::host::check_pair_args(c, "matrix", X, n_feat, n_samp, pi, pj, &n_pairs, out5, true, perspective,
                                         alternative);
   if (rc) return rc;
   icikt::MaskSpec ms;
@@ -1354,7 +1403,7 @@ int icikt_matrix_f64(icikt_ctx* c, const double* X, int64_t n_feat, int64_t n_sa
   const icikt::host::PinnedScope scope(c, flags);
   c->k0_mask = &ms;
   c->k0_keep = keep_bytes ? c->d_keep.p : nullptr;
-  rc = icikt::host::upload_prepare_pairs(c, X, n_feat, n_samp, ld, flags);
+  rc = icikt::host::upload_prepare_pairs(c, *X, n_feat, n_samp, flags);
   c->k0_mask = nullptr;
   c->k0_keep = nullptr;
   if (rc) return icikt::host::end_call(c, "matrix", rc);
@@ -1387,10 +1436,17 @@ extern "C" {
 int icikt_pairs_complete_f64(icikt_ctx* c, const double* X, int64_t n_feat, int64_t n_samp, int64_t ld,
                              const int32_t* pi, const int32_t* pj, int64_t n_pairs, int alternative, int continuity,
                              uint32_t flags, double* out4, int64_t* counts, int32_t* reasons) {
+  const icikt_input v = f64_view(X, ld);
+  return icikt_pairs_complete_in(c, &v, n_feat, n_samp, pi, pj, n_pairs, alternative, continuity, flags, out4, counts,
+                                 reasons);
+}
+
+int icikt_pairs_complete_in(icikt_ctx* c, const icikt_input* X, int64_t n_feat, int64_t n_samp, const int32_t* pi,
+                            const int32_t* pj, int64_t n_pairs, int alternative, int continuity, uint32_t flags,
+                            double* out4, int64_t* counts, int32_t* reasons) {
   if (!c) return ICIKT_E_INVALID;
-  int rc = check_shape(c, "pairs_complete", n_feat, n_samp, ld, /*wide_ok=*/false);
+  int rc = check_view(c, "pairs_complete", X, n_feat, n_samp, /*wide_ok=*/false);
   if (rc) return rc;
-  if (n_feat > 0 && n_samp > 0 && !X) return fail(c, ICIKT_E_INVALID, "pairs_complete: null matrix");
   rc = check_pair_list(c, "pairs_complete", pi, pj, n_pairs, n_samp);
   if (rc) return rc;
   if (n_pairs == 0) return ICIKT_SUCCESS;
@@ -1410,7 +1466,7 @@ int icikt_pairs_complete_f64(icikt_ctx* c, const double* X, int64_t n_feat, int6
     HIPCHK(c, hipMemcpyAsync(all_pj.p, c->d_pj.p, (size_t)n_pairs * sizeof(int32_t), hipMemcpyDeviceToDevice, c->stream));
     int r = ICIKT_SUCCESS;
     if (n_feat > 0) {  // H2D of the matrix (staged like every other matrix upload); none of its own columns is sorted, only the masked pair columns are
-      r = icikt::host::upload_and_prepare(c, X, n_feat, n_samp, ld, 0, n_samp, 0u, false, nullptr, icikt::host::kPrepassNone);
+      r = icikt::host::upload_and_prepare(c, *X, n_feat, n_samp, 0, n_samp, 0u, false, nullptr, icikt::host::kPrepassNone);
       if (r) return r;
     }
     const int64_t chunk = std::max<int64_t>(1, std::min<int64_t>(n_pairs, ((int64_t)3 << 29) / std::max<int64_t>(16 * n_feat, 16)));
@@ -1467,13 +1523,18 @@ int icikt_pair_f64(icikt_ctx* c, const double* x, const double* y, int64_t n, in
 
 int icikt_missingness_f64(icikt_ctx* c, const double* X, int64_t n_feat, int64_t n_samp, int64_t ld,
                           const int32_t* pi, const int32_t* pj, int64_t n_pairs, int64_t* missingness) {
+  const icikt_input v = f64_view(X, ld);
+  return icikt_missingness_in(c, &v, n_feat, n_samp, pi, pj, n_pairs, missingness);
+}
+
+int icikt_missingness_in(icikt_ctx* c, const icikt_input* X, int64_t n_feat, int64_t n_samp, const int32_t* pi,
+                         const int32_t* pj, int64_t n_pairs, int64_t* missingness) {
   if (!c) return ICIKT_E_INVALID;
-  int rc = check_shape(c, "missingness", n_feat, n_samp, ld);
+  int rc = check_view(c, "missingness", X, n_feat, n_samp);
   if (rc) return rc;
   if (n_pairs < 0) return fail(c, ICIKT_E_INVALID, "missingness: bad shape");
   if (n_pairs == 0) return ICIKT_SUCCESS;
   if (!pi || !pj || !missingness) return fail(c, ICIKT_E_INVALID, "missingness: null argument");
-  if (n_feat > 0 && n_samp > 0 && !X) return fail(c, ICIKT_E_INVALID, "missingness: null matrix");
   rc = check_pair_list(c, "missingness", pi, pj, n_pairs, n_samp);
   if (rc) return rc;
   rc = use_device(c);
@@ -1485,7 +1546,7 @@ int icikt_missingness_f64(icikt_ctx* c, const double* X, int64_t n_feat, int64_t
   rc = icikt::host::mask_alloc(c, n_feat, n_samp);
   if (rc) return rc;
   if (n_feat > 0) {
-    rc = icikt::host::upload_and_prepare(c, X, n_feat, n_samp, ld, 0, n_samp, 0u, false, nullptr, icikt::host::kPrepassMask);
+    rc = icikt::host::upload_and_prepare(c, *X, n_feat, n_samp, 0, n_samp, 0u, false, nullptr, icikt::host::kPrepassMask);
     if (rc) return rc;
   }
   auto body = [&]() -> int {
@@ -1494,6 +1555,21 @@ int icikt_missingness_f64(icikt_ctx* c, const double* X, int64_t n_feat, int64_t
     return icikt::host::download(c, missingness, c->d_counts.p, (size_t)n_pairs * sizeof(int64_t));
   };
   return icikt::host::end_call(c, "missingness", body());
+}
+
+int icikt_convert_dev(icikt_ctx* c, const void* d_src, int dtype, int order, int64_t n_feat, int64_t n_samp, int64_t ld,
+                      double* d_dst, int64_t dst_ld) {
+  if (!c) return ICIKT_E_INVALID;
+  const icikt_input v{d_src, dtype, order, ld};
+  int rc = check_view(c, "convert", &v, n_feat, n_samp);
+  if (rc) return rc;
+  if (dst_ld < n_feat) return fail(c, ICIKT_E_INVALID, "convert: dst_ld is below n_feat");
+  if (n_feat == 0 || n_samp == 0) return ICIKT_SUCCESS;
+  if (!d_dst) return fail(c, ICIKT_E_INVALID, "convert: null d_dst");
+  rc = use_device(c);
+  if (rc) return rc;
+  HIPCHK(c, icikt::launch_ingest(d_src, dtype, order, ld, n_feat, n_samp, d_dst, dst_ld, c->stream));
+  return ICIKT_SUCCESS;
 }
 
 }  // extern "C"

@@ -53,10 +53,17 @@ extern "C" {
 int icikt_cor_pairs_f64(icikt_ctx* c, const double* X, int64_t n_feat, int64_t n_samp, int64_t ld,
                         const int32_t* pi, const int32_t* pj, int64_t n_pairs, int method, int pairwise,
                         int alternative, int continuity, uint32_t flags, double* out3, int32_t* reasons) {
+  const icikt_input v = icikt::host::f64_view(X, ld);
+  return icikt_cor_pairs_in(c, &v, n_feat, n_samp, pi, pj, n_pairs, method, pairwise, alternative, continuity, flags, out3,
+                            reasons);
+}
+
+int icikt_cor_pairs_in(icikt_ctx* c, const icikt_input* X, int64_t n_feat, int64_t n_samp, const int32_t* pi,
+                       const int32_t* pj, int64_t n_pairs, int method, int pairwise, int alternative, int continuity,
+                       uint32_t flags, double* out3, int32_t* reasons) {
   if (!c) return ICIKT_E_INVALID;
-  int rc = check_shape(c, "cor", n_feat, n_samp, ld);
+  int rc = icikt::host::check_view(c, "cor", X, n_feat, n_samp);
   if (rc) return rc;
-  if (n_feat > 0 && n_samp > 0 && !X) return fail(c, ICIKT_E_INVALID, "cor: null matrix");
   rc = check_pair_list(c, "cor", pi, pj, n_pairs, n_samp);
   if (rc) return rc;
   if (method != ICIKT_METHOD_PEARSON && method != ICIKT_METHOD_SPEARMAN)
@@ -93,7 +100,7 @@ int icikt_cor_pairs_f64(icikt_ctx* c, const double* X, int64_t n_feat, int64_t n
       cb.prho_ready = true;
     }
     if (n_feat > 0) {
-      int r = icikt::host::upload_and_prepare(c, X, n_feat, n_samp, ld, 0, n_samp, 0u, false, nullptr,
+      int r = icikt::host::upload_and_prepare(c, *X, n_feat, n_samp, 0, n_samp, 0u, false, nullptr,
                                               icikt::host::kPrepassNone);
       if (r) return r;
     }

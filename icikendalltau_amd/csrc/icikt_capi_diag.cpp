@@ -13,7 +13,7 @@
 #include "icikt_device.h"
 #include "icikt_host.h"
 
-using icikt::host::check_shape;
+using icikt::host::f64_view;
 using icikt::host::fail;
 using icikt::host::timer_begin;
 using icikt::host::timer_end;
@@ -60,11 +60,10 @@ int diag_col_pass(icikt_ctx* c, const double* dX, int64_t n, int64_t S, const ic
 }
 
 // shape, matrix, global_na of the three entries; sets *ms
-int diag_args(icikt_ctx* c, const char* who, const double* X, int64_t n_feat, int64_t n_samp, int64_t ld,
+int diag_args(icikt_ctx* c, const char* who, const icikt_input* X, int64_t n_feat, int64_t n_samp,
               const double* global_na, int n_global_na, icikt::MaskSpec* ms) {
-  int rc = check_shape(c, who, n_feat, n_samp, ld);
+  int rc = icikt::host::check_view(c, who, X, n_feat, n_samp);
   if (rc) return rc;
-  if (n_feat > 0 && n_samp > 0 && !X) return fail(c, ICIKT_E_INVALID, std::string(who) + ": null matrix");
   if (n_samp > INT32_MAX) return fail(c, ICIKT_E_INVALID, std::string(who) + ": too many columns");
   rc = icikt::host::make_mask_spec(c, global_na, n_global_na, ms);
   if (rc) c->err = std::string(who) + c->err.substr(c->err.find(':'));
@@ -77,9 +76,15 @@ extern "C" {
 
 int icikt_col_medians_f64(icikt_ctx* c, const double* X, int64_t n_feat, int64_t n_samp, int64_t ld,
                           const double* global_na, int n_global_na, int na_rm, uint32_t flags, double* medians) {
+  const icikt_input v = f64_view(X, ld);
+  return icikt_col_medians_in(c, &v, n_feat, n_samp, global_na, n_global_na, na_rm, flags, medians);
+}
+
+int icikt_col_medians_in(icikt_ctx* c, const icikt_input* X, int64_t n_feat, int64_t n_samp, const double* global_na,
+                         int n_global_na, int na_rm, uint32_t flags, double* medians) {
   if (!c) return ICIKT_E_INVALID;
   icikt::MaskSpec ms;
-  int rc = diag_args(c, "col_medians", X, n_feat, n_samp, ld, global_na, n_global_na, &ms);
+  int rc = diag_args(c, "col_medians", X, n_feat, n_samp, global_na, n_global_na, &ms);
   if (rc) return rc;
   if (n_samp == 0) return ICIKT_SUCCESS;
   if (!medians) return fail(c, ICIKT_E_INVALID, "col_medians: null output");
@@ -87,7 +92,7 @@ int icikt_col_medians_f64(icikt_ctx* c, const double* X, int64_t n_feat, int64_t
   if (rc) return rc;
   const icikt::host::PinnedScope scope(c, flags);
   auto body = [&]() -> int {
-    int r = icikt::host::upload_and_prepare(c, X, n_feat, n_samp, ld, 0, n_samp, flags, false, nullptr,
+    int r = icikt::host::upload_and_prepare(c, *X, n_feat, n_samp, 0, n_samp, flags, false, nullptr,
                                             icikt::host::kPrepassNone);
     if (!r) r = timer_begin(c, ICIKT_K_PAIRS, flags);
     if (!r) r = diag_col_pass(c, c->d_X.p, n_feat, n_samp, ms, na_rm, nullptr, nullptr);
@@ -101,9 +106,17 @@ int icikt_col_medians_f64(icikt_ctx* c, const double* X, int64_t n_feat, int64_t
 int icikt_censor_counts_f64(icikt_ctx* c, const double* X, int64_t n_feat, int64_t n_samp, int64_t ld,
                             const double* global_na, int n_global_na, const int32_t* cls, int n_class, uint32_t flags,
                             int64_t* trials, int64_t* success, int64_t* n_excluded, double* medians) {
+  const icikt_input v = f64_view(X, ld);
+  return icikt_censor_counts_in(c, &v, n_feat, n_samp, global_na, n_global_na, cls, n_class, flags, trials, success,
+                                n_excluded, medians);
+}
+
+int icikt_censor_counts_in(icikt_ctx* c, const icikt_input* X, int64_t n_feat, int64_t n_samp, const double* global_na,
+                           int n_global_na, const int32_t* cls, int n_class, uint32_t flags, int64_t* trials,
+                           int64_t* success, int64_t* n_excluded, double* medians) {
   if (!c) return ICIKT_E_INVALID;
   icikt::MaskSpec ms;
-  int rc = diag_args(c, "censor_counts", X, n_feat, n_samp, ld, global_na, n_global_na, &ms);
+  int rc = diag_args(c, "censor_counts", X, n_feat, n_samp, global_na, n_global_na, &ms);
   if (rc) return rc;
   if (n_class < 1) return fail(c, ICIKT_E_INVALID, "censor_counts: n_class must be at least 1");
   if (n_samp > 0 && !cls) return fail(c, ICIKT_E_INVALID, "censor_counts: null class list");
@@ -129,7 +142,7 @@ int icikt_censor_counts_f64(icikt_ctx* c, const double* X, int64_t n_feat, int64
   std::vector<unsigned long long> out3((size_t)n_class * 3);
   std::vector<int32_t> nexcl((size_t)n_samp);
   auto body = [&]() -> int {
-    int r = icikt::host::upload_and_prepare(c, X, n_feat, n_samp, ld, 0, n_samp, flags, false, nullptr,
+    int r = icikt::host::upload_and_prepare(c, *X, n_feat, n_samp, 0, n_samp, flags, false, nullptr,
                                             icikt::host::kPrepassNone);
     if (r) return r;
     HIPCHK(c, db.lists.reserve(off.size() + cols.size()));
@@ -165,9 +178,18 @@ int icikt_rank_order_f64(icikt_ctx* c, const double* X, int64_t n_feat, int64_t 
                          const double* global_na, int n_global_na, const int32_t* cols, int64_t n_cols, uint32_t flags,
                          int64_t* n_kept, int32_t* n_na, double* median_rank, int32_t* row_order, int32_t* col_order,
                          double* original, double* ordered) {
+  const icikt_input v = f64_view(X, ld);
+  return icikt_rank_order_in(c, &v, n_feat, n_samp, global_na, n_global_na, cols, n_cols, flags, n_kept, n_na, median_rank,
+                             row_order, col_order, original, ordered);
+}
+
+int icikt_rank_order_in(icikt_ctx* c, const icikt_input* X, int64_t n_feat, int64_t n_samp, const double* global_na,
+                        int n_global_na, const int32_t* cols, int64_t n_cols, uint32_t flags, int64_t* n_kept,
+                        int32_t* n_na, double* median_rank, int32_t* row_order, int32_t* col_order, double* original,
+                        double* ordered) {
   if (!c) return ICIKT_E_INVALID;
   icikt::MaskSpec ms;
-  int rc = diag_args(c, "rank_order", X, n_feat, n_samp, ld, global_na, n_global_na, &ms);
+  int rc = diag_args(c, "rank_order", X, n_feat, n_samp, global_na, n_global_na, &ms);
   if (rc) return rc;
   if (n_cols < 1 || n_cols > n_samp || !cols) return fail(c, ICIKT_E_INVALID, "rank_order: bad column list");
   for (int64_t j = 0; j < n_cols; ++j)
@@ -178,18 +200,28 @@ int icikt_rank_order_f64(icikt_ctx* c, const double* X, int64_t n_feat, int64_t 
   rc = use_device(c);
   if (rc) return rc;
   const int64_t n = n_feat;
-  // the class's columns as one block: in place when they are consecutive, else gathered on the host (one pass)
+  // the class's columns as one block: in place when they are consecutive (the view from column cols[0] on, in either
+  // order), else gathered on the host in the view's element type, column-major (one pass)
   bool consecutive = true;
   for (int64_t j = 1; j < n_cols && consecutive; ++j) consecutive = cols[j] == cols[0] + j;
-  std::vector<double> gathered;
-  const double* src = n > 0 ? X + (int64_t)cols[0] * ld : X;
-  int64_t src_ld = ld;
+  std::vector<char> gathered;
+  icikt_input src = n > 0 ? icikt::host::view_from_col(*X, cols[0]) : *X;
   if (!consecutive && n > 0) {
-    gathered.resize((size_t)n * (size_t)n_cols);
-    for (int64_t j = 0; j < n_cols; ++j)
-      std::memcpy(gathered.data() + (size_t)j * (size_t)n, X + (int64_t)cols[j] * ld, (size_t)n * sizeof(double));
-    src = gathered.data();
-    src_ld = n;
+    const size_t es = icikt::host::dtype_bytes(X->dtype);
+    gathered.resize((size_t)n * (size_t)n_cols * es);
+    const char* base = static_cast<const char*>(X->data);
+    for (int64_t j = 0; j < n_cols; ++j) {
+      char* dstc = gathered.data() + (size_t)j * (size_t)n * es;
+      if (X->order == ICIKT_ORDER_COL) {
+        std::memcpy(dstc, base + (size_t)cols[j] * (size_t)X->ld * es, (size_t)n * es);
+      } else {
+        const char* s0 = base + (size_t)cols[j] * es;
+        const size_t step = (size_t)X->ld * es;
+        if (es == 4) for (int64_t r = 0; r < n; ++r) std::memcpy(dstc + 4 * (size_t)r, s0 + (size_t)r * step, 4);
+        else for (int64_t r = 0; r < n; ++r) std::memcpy(dstc + 8 * (size_t)r, s0 + (size_t)r * step, 8);
+      }
+    }
+    src = icikt_input{gathered.data(), X->dtype, ICIKT_ORDER_COL, n};
   }
   const icikt::host::PinnedScope scope(c, gathered.empty() ? flags : (flags & ~ICIKT_FLAG_HOST_PINNED));
   icikt_ctx::DiagBufs& db = c->diag;
@@ -197,7 +229,7 @@ int icikt_rank_order_f64(icikt_ctx* c, const double* X, int64_t n_feat, int64_t 
   unsigned long long kept_count = 0;
   // device passes, then the counts and medians back to the host
   auto passes = [&]() -> int {
-    int r = icikt::host::upload_and_prepare(c, src, n, n_cols, src_ld, 0, n_cols, flags, false, nullptr,
+    int r = icikt::host::upload_and_prepare(c, src, n, n_cols, 0, n_cols, flags, false, nullptr,
                                             icikt::host::kPrepassNone);
     if (r) return r;
     const size_t nn = (size_t)std::max<int64_t>(n, 1);

@@ -298,6 +298,10 @@ hipError_t launch_diag_median_rank(const int32_t* rank2, int64_t n, int n_cols, 
                                    hipStream_t s);
 hipError_t launch_diag_gather(const double* X, int64_t n, const MaskSpec& ms, const int32_t* rows, int64_t n_out,
                               const int32_t* colsel, int n_cols, double* out, hipStream_t s);
+// icikt_ingest.hip: nc columns of the column-major float64 matrix dst (leading dimension dst_ld) from a device block of
+// ICIKT_DTYPE_* cells in ICIKT_ORDER_* layout with leading dimension src_ld (elements)
+hipError_t launch_ingest(const void* src, int dtype, int order, int64_t src_ld, int64_t n, int64_t nc, double* dst,
+                         int64_t dst_ld, hipStream_t s);
 hipError_t launch_selftest(uint32_t* d_out, hipStream_t s);
 hipError_t read_step_stats(unsigned long long* out24, int reset);
 

@@ -278,7 +278,7 @@ void rank_main(Call& a, int r) {
         c->k0_keep = c->d_keep.p;
       }
     }
-    const int rc_up = icikt::host::upload_and_prepare(c, a.X, a.n_feat, S, a.ld, c0, c1, a.flags & ~ICIKT_FLAG_TIMING);
+    const int rc_up = icikt::host::upload_and_prepare(c, icikt::host::f64_view(a.X, a.ld), a.n_feat, S, c0, c1, a.flags & ~ICIKT_FLAG_TIMING);
     c->k0_mask = nullptr;
     c->k0_keep = nullptr;
     RANKCHK(rc_up);
@@ -603,7 +603,8 @@ int multi_impl(icikt_multi* m, const double* X, int64_t n_feat, int64_t n_samp, 
     return ICIKT_SUCCESS;
   }
   // argument checks (the ranks run unchecked): the single-device path's, under the prefix pairs_multi
-  const int rca = icikt::host::check_pair_args(m->ctx[0], "pairs_multi", X, n_feat, n_samp, ld, pi, pj, &n_pairs,
+  const icikt_input xv = icikt::host::f64_view(X, ld);
+  const int rca = icikt::host::check_pair_args(m->ctx[0], "pairs_multi", &xv, n_feat, n_samp, pi, pj, &n_pairs,
                                                mx ? static_cast<const void*>(mx->out5) : out4, mx != nullptr, perspective,
                                                alternative);
   if (rca) return mfail(m, rca, icikt_last_error(m->ctx[0]));

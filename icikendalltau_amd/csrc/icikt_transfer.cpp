@@ -143,29 +143,49 @@ hipError_t Transfers::init() {
 PinnedScope::PinnedScope(icikt_ctx* ctx, uint32_t flags) : c(ctx) { c->xfer.host_pinned = (flags & ICIKT_FLAG_HOST_PINNED) != 0; }
 PinnedScope::~PinnedScope() { c->xfer.host_pinned = false; }
 
+// a half of the staging buffers for a view that is not column-major float64: the largest chunk in the view's element type
+static size_t ingest_half(const MatrixUpload& u) {
+  return (((size_t)u.chunk_cols * (size_t)u.n_feat * dtype_bytes(u.v.dtype)) + 255) & ~(size_t)255;
+}
+
 hipError_t MatrixUpload::begin(size_t span, hipStream_t also) {
   Transfers& t = c->xfer;
   in_place = span >= kLockMin && t.host_pinned;
   staged = span >= kLockMin && !t.host_pinned;
-  hipError_t e = staged ? t.stage.reserve(2 * chunk_bytes) : hipSuccess;
+  const bool plain = view_is_plain(v);
+  const size_t half = plain ? (size_t)chunk_cols * (size_t)n_feat * sizeof(double) : ingest_half(*this);
+  hipError_t e = staged ? t.stage.reserve(2 * half) : hipSuccess;
+  if (e == hipSuccess && !plain) e = c->d_ingest.reserve(2 * half);
   if (e == hipSuccess) e = hipEventRecord(t.ev_copy[0], c->stream);
   if (e == hipSuccess) e = hipStreamWaitEvent(c->copy_stream, t.ev_copy[0], 0);
   if (e == hipSuccess && also) e = hipStreamWaitEvent(also, t.ev_copy[0], 0);
   return e;
 }
 
-hipError_t MatrixUpload::copy(int k, double* dst, const double* src, int64_t nc, hipEvent_t* done) {
+hipError_t MatrixUpload::copy(int k, double* dst, int64_t c0, int64_t nc, hipEvent_t* done) {
   Transfers& t = c->xfer;
   hipError_t e = hipSuccess;
+  const bool plain = view_is_plain(v), row = v.order == ICIKT_ORDER_ROW;
+  const size_t es = dtype_bytes(v.dtype);
+  // the chunk in the caller's memory: `runs` runs of run_bytes, ld_bytes apart (COL: a run is a column; ROW: a run is
+  // the chunk's part of a row)
+  const char* src = static_cast<const char*>(view_from_col(v, c0).data);
+  const size_t ld_bytes = (size_t)v.ld * es;
+  const size_t run_bytes = (size_t)(row ? nc : n_feat) * es, runs = (size_t)(row ? n_feat : nc);
+  const size_t half = plain ? (size_t)chunk_cols * (size_t)n_feat * sizeof(double) : ingest_half(*this);
+  // where it lands, runs packed: the device matrix itself, or a half of the device staging block
+  void* land = plain ? static_cast<void*>(dst) : static_cast<void*>(c->d_ingest.p + (size_t)(k & 1) * half);
   if (staged) {
-    char* stage = static_cast<char*>(t.stage.p) + (size_t)(k & 1) * chunk_bytes;
+    char* stage = static_cast<char*>(t.stage.p) + (size_t)(k & 1) * half;
     if (k >= 2) e = hipEventSynchronize(t.ev_copy[1 + ((k - 2) % 3)]);  // the copy that last used this half
     if (e != hipSuccess) return e;
-    par_copy2d(t, stage, col_bytes, src, ld_bytes, col_bytes, (size_t)nc);
-    e = hipMemcpyAsync(dst, stage, (size_t)nc * col_bytes, hipMemcpyHostToDevice, c->copy_stream);
+    par_copy2d(t, stage, run_bytes, src, ld_bytes, run_bytes, runs);
+    e = hipMemcpyAsync(land, stage, runs * run_bytes, hipMemcpyHostToDevice, c->copy_stream);
   } else {
-    e = hipMemcpy2DAsync(dst, col_bytes, src, ld_bytes, col_bytes, (size_t)nc, hipMemcpyHostToDevice, c->copy_stream);
+    e = hipMemcpy2DAsync(land, run_bytes, src, ld_bytes, run_bytes, runs, hipMemcpyHostToDevice, c->copy_stream);
   }
+  if (e == hipSuccess && !plain)
+    e = icikt::launch_ingest(land, v.dtype, v.order, row ? nc : n_feat, n_feat, nc, dst, n_feat, c->copy_stream);
   *done = t.ev_copy[1 + (k % 3)];
   if (e == hipSuccess) e = hipEventRecord(*done, c->copy_stream);
   return e;

@@ -79,16 +79,39 @@ struct PinnedScope {
 //   in place          ICIKT_FLAG_HOST_PINNED on the call: the caller has page-locked the matrix itself; the copies are
 //                     DMA straight out of it
 //   small             matrices below kLockMin bytes take the runtime's own staging path
+// A column-major float64 chunk lands in the device matrix itself.  Any other view (icikt_input) travels in ITS element
+// type and order -- the same three routes, a strided copy of `rows` runs each -- into a device staging block of two
+// halves (icikt_ctx::d_ingest), and k_ingest (icikt_ingest.hip) widens / transposes it into the device matrix on the
+// copy stream, right behind its copy: stream order is what keeps a half from being overwritten before it has been read.
 struct MatrixUpload {
   icikt_ctx* c;
-  size_t col_bytes, ld_bytes, chunk_bytes;   // a column, the caller's leading dimension, the largest chunk
+  icikt_input v;                             // the caller's matrix (element type, order, leading dimension in elements)
+  int64_t n_feat, chunk_cols;                // rows of a column, columns of the largest chunk
   bool staged = false, in_place = false;     // the route (in place: copies may still read the caller's matrix after the host went on)
-  // picks the route for a span of `span` bytes, grows the staging buffer, and makes c->copy_stream (and `also`, when
+  // picks the route for a span of `span` bytes, grows the staging buffers, and makes c->copy_stream (and `also`, when
   // not null) wait for the work already on c->stream: it may still read the device copy the chunks overwrite
   hipError_t begin(size_t span, hipStream_t also);
-  // chunk k (0, 1, ... in order): nc columns from src to dst; *done is recorded behind the copy
-  hipError_t copy(int k, double* dst, const double* src, int64_t nc, hipEvent_t* done);
+  // chunk k (0, 1, ... in order): columns [c0, c0 + nc) of the view into dst, column-major float64 with leading
+  // dimension n_feat; *done is recorded behind the copy and, for a view that is not column-major float64, behind the
+  // conversion (k_ingest) that follows it on the copy stream
+  hipError_t copy(int k, double* dst, int64_t c0, int64_t nc, hipEvent_t* done);
 };
+
+inline size_t dtype_bytes(int dtype) { return dtype == ICIKT_DTYPE_F32 || dtype == ICIKT_DTYPE_I32 ? 4 : 8; }
+inline bool view_is_plain(const icikt_input& v) { return v.dtype == ICIKT_DTYPE_F64 && v.order == ICIKT_ORDER_COL; }
+inline icikt_input f64_view(const double* X, int64_t ld) { return icikt_input{X, ICIKT_DTYPE_F64, ICIKT_ORDER_COL, ld}; }
+// bytes from the first to the last cell of columns [0, ncols) of an n_feat-row view
+inline size_t view_span(const icikt_input& v, int64_t n_feat, int64_t ncols) {
+  if (n_feat <= 0 || ncols <= 0) return 0;
+  const size_t major = (size_t)(v.order == ICIKT_ORDER_ROW ? n_feat : ncols), minor = (size_t)(v.order == ICIKT_ORDER_ROW ? ncols : n_feat);
+  return ((major - 1) * (size_t)v.ld + minor) * dtype_bytes(v.dtype);
+}
+// the view of columns [c0, ...) of v
+inline icikt_input view_from_col(const icikt_input& v, int64_t c0) {
+  icikt_input o = v;
+  if (v.data) o.data = static_cast<const char*>(v.data) + (size_t)c0 * (v.order == ICIKT_ORDER_ROW ? (size_t)1 : (size_t)v.ld) * dtype_bytes(v.dtype);
+  return o;
+}
 
 // H2D on c->stream, complete on return
 int upload_sync(icikt_ctx* c, void* dst, const void* src, size_t bytes);

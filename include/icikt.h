@@ -14,6 +14,10 @@
  *   - X is column-major n_feat x n_samp with leading dimension ld (R matrix layout; columns are
  *     samples, R/kendalltau.R:6).  Missing = NaN of any payload (R's NA_real_ is a NaN;
  *     Rcpp is_na() is true for NA and NaN, src/kendallc.cpp:181).
+ *   - The *_in host entries take the same matrix as a typed, strided VIEW (icikt_input): float64, float32, int32 or
+ *     int64 cells, column- or row-major, read where it lies.  An entry given a view V returns what its _f64 twin
+ *     returns on the column-major float64 matrix M[r, c] = (double)V[r, c]; the widening and the transpose run on
+ *     the device (icikt_convert_dev's kernel), never as a host copy.
  *   - Pair indices are 0-based column indices; pair p is ici_kt(x = X[, pi[p]], y = X[, pj[p]]).
  *   - out4 is P x 4 row-major: tau, pvalue, tau_max, completeness (src/kendallc.cpp:171-172).
  *     Degenerate pairs get R's NA_real_ bit pattern (0x7FF00000000007A2) in all four and a reason.
@@ -114,6 +118,18 @@ extern "C" {
 #define ICIKT_K_COUNT 3
 
 typedef struct icikt_ctx icikt_ctx;
+
+/* The caller's matrix as the *_in host entries read it: n_feat x n_samp cells of `dtype` at `data`, ld in ELEMENTS.
+ * The cells are converted as C converts them, (double)v: float32 and int32 exactly, int64 to the nearest double (ties
+ * to even above 2^53, as numpy's astype), a float64 cell bit for bit (NaN payloads kept: NA_real_ stays NA_real_), a
+ * float32 NaN to some float64 NaN.  global_na is applied after the conversion, in float64. */
+#define ICIKT_DTYPE_F64 0
+#define ICIKT_DTYPE_F32 1
+#define ICIKT_DTYPE_I32 2
+#define ICIKT_DTYPE_I64 3
+#define ICIKT_ORDER_COL 0   /* element (r, c) at data[r + c*ld], ld >= n_feat (the _f64 entries' layout) */
+#define ICIKT_ORDER_ROW 1   /* element (r, c) at data[r*ld + c], ld >= n_samp                            */
+typedef struct { const void *data; int dtype; int order; int64_t ld; } icikt_input;
 
 int icikt_version(void);
 /* Number of visible HIP devices (0 and ICIKT_E_NO_DEVICE when none). */
@@ -344,6 +360,47 @@ int icikt_rank_order_f64(icikt_ctx *ctx, const double *X, int64_t n_feat, int64_
  * either column, from a host matrix whose missing cells are NaN.  Self pairs allowed. */
 int icikt_missingness_f64(icikt_ctx *ctx, const double *X, int64_t n_feat, int64_t n_samp, int64_t ld,
                           const int32_t *pi, const int32_t *pj, int64_t n_pairs, int64_t *missingness);
+
+/* ---- the host entries on a typed, strided view of the caller's matrix ------------------------------------------
+ *
+ * Each takes `const icikt_input *X, n_feat, n_samp` where its _f64 twin takes `const double *X, n_feat, n_samp, ld`;
+ * every other argument, every output and the error contract are the twin's, and the _f64 entries are these with
+ * {X, ICIKT_DTYPE_F64, ICIKT_ORDER_COL, ld}.  The matrix crosses PCIe in its own element type (float32 and int32:
+ * half the bytes) and is widened / transposed on the device into the column-major float64 matrix the kernels read.
+ * ICIKT_FLAG_HOST_PINNED keeps its meaning: the caller has page-locked `data`, which is then read in place.  A null
+ * view or null data, an unknown dtype or order, ld below n_feat (COL) or n_samp (ROW): ICIKT_E_INVALID, the message
+ * names the argument.  icikt_rank_order_in: consecutive columns are read in place in either order; other column lists
+ * are gathered on the host, in the view's element type, before they cross PCIe. */
+int icikt_pairs_in(icikt_ctx *ctx, const icikt_input *X, int64_t n_feat, int64_t n_samp, const int32_t *pi,
+                   const int32_t *pj, int64_t n_pairs, int perspective, int alternative, int continuity, uint32_t flags,
+                   double *out4, int64_t *counts, int32_t *reasons);
+int icikt_matrix_in(icikt_ctx *ctx, const icikt_input *X, int64_t n_feat, int64_t n_samp, const double *global_na,
+                    int n_global_na, const int32_t *pi, const int32_t *pj, int64_t n_pairs, int perspective,
+                    int alternative, int continuity, uint32_t flags, int scale_max, int diag_good, double *out5,
+                    uint8_t *keep, int64_t *reason_counts);
+int icikt_pairs_complete_in(icikt_ctx *ctx, const icikt_input *X, int64_t n_feat, int64_t n_samp, const int32_t *pi,
+                            const int32_t *pj, int64_t n_pairs, int alternative, int continuity, uint32_t flags,
+                            double *out4, int64_t *counts, int32_t *reasons);
+int icikt_missingness_in(icikt_ctx *ctx, const icikt_input *X, int64_t n_feat, int64_t n_samp, const int32_t *pi,
+                         const int32_t *pj, int64_t n_pairs, int64_t *missingness);
+int icikt_cor_pairs_in(icikt_ctx *ctx, const icikt_input *X, int64_t n_feat, int64_t n_samp, const int32_t *pi,
+                       const int32_t *pj, int64_t n_pairs, int method, int pairwise, int alternative, int continuity,
+                       uint32_t flags, double *out3, int32_t *reasons);
+int icikt_col_medians_in(icikt_ctx *ctx, const icikt_input *X, int64_t n_feat, int64_t n_samp, const double *global_na,
+                         int n_global_na, int na_rm, uint32_t flags, double *medians);
+int icikt_censor_counts_in(icikt_ctx *ctx, const icikt_input *X, int64_t n_feat, int64_t n_samp,
+                           const double *global_na, int n_global_na, const int32_t *cls, int n_class, uint32_t flags,
+                           int64_t *trials, int64_t *success, int64_t *n_excluded, double *medians);
+int icikt_rank_order_in(icikt_ctx *ctx, const icikt_input *X, int64_t n_feat, int64_t n_samp, const double *global_na,
+                        int n_global_na, const int32_t *cols, int64_t n_cols, uint32_t flags, int64_t *n_kept,
+                        int32_t *n_na, double *median_rank, int32_t *row_order, int32_t *col_order, double *original,
+                        double *ordered);
+/* The conversion alone, device to device, asynchronous on the context's stream: d_src is a DEVICE block of `dtype` cells
+ * in `order` with leading dimension ld (elements); d_dst receives the column-major float64 matrix with leading dimension
+ * dst_ld >= n_feat (rows [n_feat, dst_ld) of d_dst are left as they are) -- what icikt_prepare_dev takes.  The way in
+ * for a matrix that is on the device already (a torch tensor's data_ptr()).  The two blocks must not overlap. */
+int icikt_convert_dev(icikt_ctx *ctx, const void *d_src, int dtype, int order, int64_t n_feat, int64_t n_samp,
+                      int64_t ld, double *d_dst, int64_t dst_ld);
 
 /* Device self-test of the wavefront primitives the pair kernel relies on (DPP scan / shift). */
 int icikt_selftest(icikt_ctx *ctx);
