@@ -17,7 +17,7 @@ LIB_PATH = os.environ.get("ICIKT_LIB") or os.path.join(_PKG, "libicikt_hip.so") 
 SOURCES = [os.path.join(_PKG, "csrc", f) for f in ("icikt_kernels.hip", "icikt_prepass.hip", "icikt_epilogue.hip",
                                                        "icikt_capi.cpp", "icikt_capi_cor.cpp", "icikt_capi_diag.cpp",
                                                        "icikt_multi.cpp", "icikt_transfer.cpp", "icikt_cor.hip",
-                                                       "icikt_diag.hip", "icikt_ingest.hip")]
+                                                       "icikt_diag.hip", "icikt_ingest.hip", "icikt_sparse.hip")]
 HEADERS = [os.path.join(_ROOT, "include", "icikt.h"), os.path.join(_PKG, "csrc", "icikt_device.h"),
            os.path.join(_PKG, "csrc", "icikt_wave.h"), os.path.join(_PKG, "csrc", "icikt_host.h"),
            os.path.join(_PKG, "csrc", "icikt_transfer.h"), os.path.join(_PKG, "csrc", "icikt_colsort.h")]
@@ -63,6 +63,8 @@ EXPORTS = (
     "icikt_cor_pairs_f64", "icikt_col_medians_f64", "icikt_censor_counts_f64", "icikt_rank_order_f64",
     "icikt_pairs_in", "icikt_matrix_in", "icikt_pairs_complete_in", "icikt_missingness_in", "icikt_cor_pairs_in",
     "icikt_col_medians_in", "icikt_censor_counts_in", "icikt_rank_order_in", "icikt_convert_dev",
+    "icikt_pairs_csc", "icikt_matrix_csc", "icikt_missingness_csc", "icikt_col_medians_csc", "icikt_censor_counts_csc",
+    "icikt_rank_order_csc", "icikt_scatter_csc_dev",
 )
 
 # icikt_input: the caller's matrix as a typed, strided view (ICIKT_DTYPE_*, ICIKT_ORDER_*)
@@ -103,10 +105,125 @@ def input_view(X):
 
 def _view_arg(X, flags: int = 0):
     """(array kept alive, icikt_input by reference, n_feat, n_samp, flags): FLAG_HOST_PINNED speaks of the caller's
-    memory, so it is cleared when the entry reads a copy of the library's own making."""
+    memory, so it is cleared when the entry reads a copy of the library's own making.  A sparse matrix (is_sparse) gives
+    its CscView and an icikt_csc_input instead: the *_csc entries take it where the *_in entries take the dense view."""
+    if is_sparse(X):
+        s = csc_view(X)
+        return s, s.struct(), s.shape[0], s.shape[1], (flags & ~FLAG_HOST_PINNED) if s.copied else flags
     a, code, order, ld, copied = input_view(X)
     v = InputView(a.ctypes.data, code, order, ld)
     return a, v, a.shape[0], a.shape[1], (flags & ~FLAG_HOST_PINNED) if copied else flags
+
+
+# icikt_csc_input: the caller's matrix in compressed-sparse-column form (ICIKT_INDEX_*)
+INDEX_I32, INDEX_I64 = 0, 1
+INDEX_TYPES = {np.dtype(np.int32): INDEX_I32, np.dtype(np.int64): INDEX_I64}
+
+
+class CscInput(ctypes.Structure):
+    """icikt_csc_input (include/icikt.h)."""
+    _fields_ = [("values", ctypes.c_void_p), ("indices", ctypes.c_void_p), ("indptr", ctypes.c_void_p),
+                ("dtype", ctypes.c_int), ("index_type", ctypes.c_int), ("fill", ctypes.c_double)]
+
+
+class CscView:
+    """A features x samples matrix in CSC form as the *_csc entries read it (csc_view builds it): data / indices /
+    indptr as numpy arrays of supported types, shape, fill (a one-element float64 array: its 64 bits travel as they
+    are), and copied: whether any of the three arrays is a copy csc_view made (a cast, or tocsc)."""
+
+    def __init__(self, data, indices, indptr, shape, fill, copied):
+        self.data, self.indices, self.indptr = data, indices, indptr
+        self.shape = (int(shape[0]), int(shape[1]))
+        self.fill = np.array([fill], dtype=np.float64) if not isinstance(fill, np.ndarray) else fill
+        self.copied = bool(copied)
+        self.format = "csc"
+
+    def struct(self):
+        """The icikt_csc_input of this view (the view must outlive the call that gets it)."""
+        v = CscInput(self.data.ctypes.data if self.data.size else None,
+                     self.indices.ctypes.data if self.indices.size else None, self.indptr.ctypes.data,
+                     DTYPES[self.data.dtype], INDEX_TYPES[self.indices.dtype], 0.0)
+        ctypes.memmove(ctypes.addressof(v) + CscInput.fill.offset, self.fill.ctypes.data, 8)   # (the bits, whatever they are)
+        return v
+
+    def toarray(self):
+        """The dense column-major float64 matrix the view stands for (the definition in include/icikt.h; duplicates:
+        the last one wins here, the library refuses them)."""
+        n, S = self.shape
+        M = np.empty((n, S), dtype=np.float64, order="F")
+        M.view(np.uint64)[...] = self.fill.view(np.uint64)[0]
+        cols = np.repeat(np.arange(S), np.diff(self.indptr[:S + 1]))
+        lo, hi = int(self.indptr[0]), int(self.indptr[S])
+        M[self.indices[lo:hi], cols] = self.data[lo:hi]
+        return M
+
+
+def is_sparse(A) -> bool:
+    """A CscView, or anything that looks like a scipy.sparse matrix / array (scipy itself is never imported here): a
+    `format` string and a 2-D `shape`, and either the CSC arrays or a `tocsc` method."""
+    if isinstance(A, CscView):
+        return True
+    if isinstance(A, np.ndarray) or not isinstance(getattr(A, "format", None), str):
+        return False
+    if len(getattr(A, "shape", ())) != 2:
+        return False
+    return hasattr(A, "tocsc") or (A.format == "csc" and all(hasattr(A, k) for k in ("data", "indices", "indptr")))
+
+
+def csc_view(A, fill=0.0) -> CscView:
+    """How the *_csc entries read a sparse matrix A (features x samples): duck-typed on .format == "csc", .data,
+    .indices, .indptr and .shape, so scipy stays optional.  The three arrays stay where they lie (copied = False) when
+    data is float64, float32, int32 or int64 and indices / indptr share int32 or int64 -- which holds for
+    scipy.sparse.csc_matrix / csc_array and for the transpose of a CSR matrix (cells x genes -> features x samples).
+    Anything else is cast, O(nnz) on the host: float16 -> float32, other floats -> float64, bool and integers of up to
+    32 bits -> int32 (uint32 -> int64), uint64 -> float64; mixed or other index types -> int64.  Any other sparse format
+    (csr, coo, ...) goes through A.tocsc(), also O(nnz) on the host.  fill: the value of every cell without an entry
+    (0.0: scipy's toarray), carried bit for bit."""
+    if isinstance(A, CscView):
+        if isinstance(fill, (int, float)) and fill == 0.0 and not np.signbit(fill):
+            return A
+        return CscView(A.data, A.indices, A.indptr, A.shape, np.array([fill], dtype=np.float64), A.copied)
+    if not is_sparse(A):
+        raise TypeError("csc_view needs a sparse matrix (an object with .format, .shape and the CSC arrays or .tocsc())")
+    copied = False
+    if A.format != "csc":
+        A = A.tocsc()
+        copied = True
+    data, indices, indptr = np.asarray(A.data), np.asarray(A.indices), np.asarray(A.indptr)
+    n_feat, n_samp = (int(v) for v in A.shape)
+    if data.ndim != 1 or indices.ndim != 1 or indptr.ndim != 1 or indptr.shape[0] != n_samp + 1:
+        raise ValueError("a CSC matrix needs 1-D data / indices and n_samp + 1 column offsets in indptr")
+    if indices.shape[0] < data.shape[0]:
+        raise ValueError("a CSC matrix needs a row index for every stored value")
+
+    def plain(a):
+        return a.dtype.isnative and a.flags.c_contiguous and a.flags.aligned
+
+    if not (data.dtype in DTYPES and plain(data)):
+        k, size = data.dtype.kind, data.dtype.itemsize
+        if k == "f":
+            to = np.float32 if size <= 4 else np.float64
+        elif k == "b" or (k == "i" and size <= 4) or (k == "u" and size < 4):
+            to = np.int32
+        elif k in "iu" and (k == "i" or size == 4):
+            to = np.int64
+        elif k == "u":
+            to = np.float64
+        else:
+            raise TypeError("the values of a sparse matrix must be of a numeric type")
+        data = np.ascontiguousarray(data, dtype=to)
+        copied = True
+    if not (indices.dtype == indptr.dtype and indices.dtype in INDEX_TYPES and plain(indices) and plain(indptr)):
+        if indices.dtype.kind not in "iu" or indptr.dtype.kind not in "iu":
+            raise TypeError("indices and indptr of a sparse matrix must be integers")
+        narrow = indices.dtype.itemsize <= 4 and indptr.dtype.itemsize <= 4 and \
+            indices.dtype != np.uint32 and indptr.dtype != np.uint32
+        to = np.int32 if narrow else np.int64
+        indices = np.ascontiguousarray(indices, dtype=to)
+        indptr = np.ascontiguousarray(indptr, dtype=to)
+        copied = True
+    f = np.array([fill], dtype=np.float64) if not isinstance(fill, np.ndarray) else np.ascontiguousarray(fill, dtype=np.float64).reshape(1)
+    return CscView(data, indices, indptr, (n_feat, n_samp), f, copied)
 
 
 
@@ -224,6 +341,11 @@ def lib():
         f64 = getattr(L, f"icikt_{nm}_f64").argtypes
         getattr(L, f"icikt_{nm}_in").argtypes = [c_vp, ctypes.POINTER(InputView), c_i64, c_i64] + list(f64[5:])
     L.icikt_convert_dev.argtypes = [c_vp, c_vp, c_int, c_int, c_i64, c_i64, c_i64, c_vp, c_i64]
+    # the *_csc twins: (ctx, const icikt_csc_input*, n_feat, n_samp, ...)
+    for nm in ("pairs", "matrix", "missingness", "col_medians", "censor_counts", "rank_order"):
+        f64 = getattr(L, f"icikt_{nm}_f64").argtypes
+        getattr(L, f"icikt_{nm}_csc").argtypes = [c_vp, ctypes.POINTER(CscInput), c_i64, c_i64] + list(f64[5:])
+    L.icikt_scatter_csc_dev.argtypes = [c_vp, c_vp, c_vp, c_vp, c_int, c_int, ctypes.c_double, c_i64, c_i64, c_vp, c_i64]
     for name in EXPORTS:
         if getattr(L, name).restype is not None and name not in ("icikt_last_error", "icikt_num_pairs",
                                                                    "icikt_multi_last_error"):
@@ -261,6 +383,9 @@ def _matrix_call(fn, handle, chk, X, global_na, pi, pj, perspective, alternative
         X, v, n_feat, n_samp, flags = _view_arg(X, flags)
         xargs = (ctypes.byref(v), n_feat, n_samp)
     else:
+        if is_sparse(X):
+            X = csc_view(X).toarray()
+            flags &= ~FLAG_HOST_PINNED
         if not (isinstance(X, np.ndarray) and X.dtype == np.float64 and X.ndim == 2 and X.flags.f_contiguous):
             X = np.asfortranarray(X, dtype=np.float64)
             flags &= ~FLAG_HOST_PINNED   # (a pageable copy of this function's)
@@ -405,8 +530,9 @@ class Context:
         """(entry function, its name, the arguments that describe X, n_feat, n_samp, flags, the array to keep alive):
         icikt_<name>_in on input_view(X), read where it lies; with f64_entries icikt_<name>_f64 on an F-ordered
         float64 copy."""
+        sparse = is_sparse(X)
         if self.f64_entries:
-            Xf = np.asfortranarray(X, dtype=np.float64)
+            Xf = csc_view(X).toarray() if sparse else np.asfortranarray(X, dtype=np.float64)
             if Xf.ndim != 2:
                 raise ValueError("X must be 2-D (features x samples)")
             if Xf is not X:
@@ -415,8 +541,20 @@ class Context:
             fn = f"icikt_{name}_f64"
             return getattr(lib(), fn), fn, (_ptr(Xf), n_feat, n_samp, max(n_feat, ld_floor)), n_feat, n_samp, flags, Xf
         a, v, n_feat, n_samp, flags = _view_arg(X, flags)
-        fn = f"icikt_{name}_in"
+        fn = f"icikt_{name}_csc" if sparse else f"icikt_{name}_in"
+        if sparse and not hasattr(lib(), fn):
+            raise IciktError(f"{name}: no entry for a sparse matrix (densify it: zero is a value there, not a missing cell)")
         return getattr(lib(), fn), fn, (ctypes.byref(v), n_feat, n_samp), n_feat, n_samp, flags, (a, v)
+
+    def scatter_csc_dev(self, d_values: int, d_indices: int, d_indptr: int, dtype: int, index_type: int, fill,
+                        n_feat: int, n_samp: int, d_dst: int, dst_ld: int):
+        """icikt_scatter_csc_dev: DEVICE arrays of a CSC matrix (DTYPE_* values, INDEX_* indices and column offsets) ->
+        the column-major float64 device matrix prepare_dev takes, cells without an entry = fill.  Returns after the
+        context's stream has been synchronised; malformed input raises."""
+        self._chk(lib().icikt_scatter_csc_dev(self._h, ctypes.c_void_p(d_values or 0), ctypes.c_void_p(d_indices or 0),
+                                              ctypes.c_void_p(d_indptr or 0), dtype, index_type, ctypes.c_double(fill),
+                                              n_feat, n_samp, ctypes.c_void_p(d_dst or 0), dst_ld),
+                  "icikt_scatter_csc_dev")
 
     def convert_dev(self, d_src: int, dtype: int, order: int, n_feat: int, n_samp: int, ld: int, d_dst: int,
                     dst_ld: int):
@@ -453,7 +591,8 @@ class Context:
         """ici_kendalltau() below its argument checks in ONE call (icikt_matrix_f64): the exclusion rule, the pair
         kernels and scale_and_reshape all run on the device.  X: raw data (features x samples, F-ordered float64 is
         taken as is); global_na: the values setup_missing_matrix excludes (NaN = NA, Inf, finite values)."""
-        fn = lib().icikt_matrix_f64 if self.f64_entries else lib().icikt_matrix_in
+        fn = lib().icikt_matrix_f64 if self.f64_entries else \
+            (lib().icikt_matrix_csc if is_sparse(X) else lib().icikt_matrix_in)
         return _matrix_call(fn, self._h, self._chk, X, global_na, pi, pj, perspective, alternative,
                             continuity, flags, scale_max, diag_good, want_keep, view=not self.f64_entries)
 

@@ -271,9 +271,28 @@ def ici_kt_counts(x, y, perspective="local", device=None, exact_int64=False):
 # --------------------------------------------------------------------------------------------------
 # input checks (R/utils.R:1-66)
 # --------------------------------------------------------------------------------------------------
-def _as_matrix(data_matrix, colnames, arg, keep_dtype=False):
+def _densify(A):
+    """A sparse matrix as the dense one it stands for (toarray(): absent cells are 0), O(n_feat * n_samp) on the host."""
+    return A.toarray() if hasattr(A, "toarray") else _lib.csc_view(A).toarray()
+
+
+def _as_matrix(data_matrix, colnames, arg, keep_dtype=False, keep_sparse=False):
     """check_if_colnames_null / transform_to_matrix / check_if_numeric.  keep_dtype: a float32, int32 or int64 matrix
-    stays what it is (a HipEngine's context reads it where it lies, _for_engine); everything else is float64."""
+    stays what it is (a HipEngine's context reads it where it lies, _for_engine); everything else is float64.
+    keep_sparse: a sparse matrix (scipy.sparse, or anything _lib.is_sparse takes) stays what it is too -- a HipEngine's
+    context reads its CSC arrays where they lie (_lib.csc_view) -- after the same checks; without it it is densified."""
+    if _lib.is_sparse(data_matrix):
+        if colnames is None:
+            raise ValueError(f"Colnames of `{arg}` must be be specified.")
+        kind = np.asarray(getattr(data_matrix, "data", np.zeros(0))).dtype.kind
+        if kind not in "fiub":
+            raise TypeError(f"`{arg}` must be a numeric type.")
+        colnames = [str(c) for c in colnames]
+        if len(colnames) != data_matrix.shape[1]:
+            raise ValueError("length of colnames does not match the number of columns")
+        if keep_sparse:
+            return data_matrix, colnames
+        data_matrix = _densify(data_matrix)
     if pd is not None and isinstance(data_matrix, pd.DataFrame):
         print(f"i `{arg}` is a data.frame, converting to matrix ...")  # R/utils.R:53-57
         if colnames is None:
@@ -298,6 +317,12 @@ def _for_engine(X, eng, fortran=True):
     """The matrix as an engine takes it.  A HipEngine's context reads float64, float32, int32 and int64 matrices of
     either memory order where they lie (_lib.input_view: no host copy); every other engine gets the float64 matrix it
     always got."""
+    if _lib.is_sparse(X):
+        # (one context reads the CSC arrays where they lie; the multi-device entries and every other engine take the
+        #  dense matrix)
+        if isinstance(eng, HipEngine) and not isinstance(eng, MultiHipEngine):
+            return X
+        X = _densify(X)
     if isinstance(eng, HipEngine):
         return X
     return np.asfortranarray(X, dtype=np.float64) if fortran else np.asarray(X, dtype=np.float64)
@@ -485,8 +510,14 @@ def ici_kendalltau(data_matrix, global_na=(float("nan"), float("inf"), 0), persp
     or with ``return_matrix=False`` ``{"cor": data.frame(s1, s2, core, raw, pvalue, taumax,
     completeness, cor), "run_time"}``.  Column names are required, as in the reference (``colnames=``
     for a bare ndarray).
+
+    ``data_matrix`` may be a sparse matrix (scipy.sparse of any format, features x samples; column names from
+    ``colnames=``): with the default ``global_na`` its absent cells are the missing ones.  On one MI355X its CSC arrays
+    go to the device as they are (icikt_matrix_csc; other formats through ``tocsc()``, O(nnz)).  The branches that edit
+    the matrix on the host densify it with ``toarray()``: ``check_timing``, ``return_matrix=False``, more than 32
+    finite ``global_na`` values, several GPUs or ranks, and an ``engine`` that is not the HIP one.
     """
-    data_matrix, names = _as_matrix(data_matrix, colnames, "data_matrix", keep_dtype=True)
+    data_matrix, names = _as_matrix(data_matrix, colnames, "data_matrix", keep_dtype=True, keep_sparse=True)
     n_sample = data_matrix.shape[1]
 
     _dist, _rank, world = _dist_info()
@@ -525,6 +556,8 @@ def ici_kendalltau(data_matrix, global_na=(float("nan"), float("inf"), 0), persp
         res["run_time"] = t_diff
         return res
 
+    if _lib.is_sparse(data_matrix):
+        data_matrix = _densify(data_matrix)
     data_matrix = np.asarray(data_matrix, dtype=np.float64)   # (the branches below edit the matrix on the host)
     exclude_loc = setup_missing_matrix(data_matrix, global_na)
     exclude_data = _masked_fortran(data_matrix, exclude_loc)
@@ -602,14 +635,24 @@ def ici_kendalltau(data_matrix, global_na=(float("nan"), float("inf"), 0), persp
 # --------------------------------------------------------------------------------------------------
 def pairwise_completeness(data_matrix, global_na=(float("nan"), float("inf"), 0), include_only=None,
                           return_matrix=True, colnames=None, engine=None):
-    data_matrix, names = _as_matrix(data_matrix, colnames, "data_matrix")
-    exclude_loc = setup_missing_matrix(data_matrix, global_na)
+    """Pairwise completeness of the samples (R/kendalltau.R:563-629).  A sparse ``data_matrix`` stays sparse on a HIP
+    engine: the rule of ``global_na`` is applied to its stored values and to the value of its absent cells (0), O(nnz)
+    on the host, and the CSC arrays go to the device (icikt_missingness_csc); any other engine gets ``toarray()``."""
+    eng = engine or _default_engine()
+    data_matrix, names = _as_matrix(data_matrix, colnames, "data_matrix", keep_sparse=isinstance(eng, HipEngine))
     _dist, _rank, world = _dist_info()
     pi, pj, core = setup_comparisons(names, include_only, diag_good=False, ncore=world)
-    eng = engine or _default_engine()
-    masked = np.asfortranarray(np.where(exclude_loc, np.nan, 0.0))
+    n_feat = data_matrix.shape[0]
+    if _lib.is_sparse(data_matrix):
+        s = _lib.csc_view(data_matrix)
+        stored = np.where(setup_missing_matrix(np.asarray(s.data, dtype=np.float64), global_na), np.nan, 0.0)
+        absent = np.nan if bool(setup_missing_matrix(np.zeros(1), global_na)[0]) else 0.0
+        masked = _lib.CscView(stored, s.indices, s.indptr, s.shape, np.array([absent]), True)
+    else:
+        exclude_loc = setup_missing_matrix(data_matrix, global_na)
+        masked = np.asfortranarray(np.where(exclude_loc, np.nan, 0.0))
     missingness = eng.missingness(masked, pi, pj).astype(np.float64)
-    completeness = 1 - (missingness / exclude_loc.shape[0])
+    completeness = 1 - (missingness / n_feat)
     if return_matrix:
         m = np.zeros((len(names), len(names)))
         m[pi, pj] = completeness
@@ -648,6 +691,8 @@ def kt_fast(x, y=None, use="everything", alternative="two.sided", continuity=Fal
     both (src/kendallc.cpp:180-185) and nothing missing remains; the HIP engine masks, sorts and counts every
     pair on the device (icikt_pairs_complete_f64), other engines get the masked vectors from the host.
     """
+    if _lib.is_sparse(x):   # zero is a value here, not a missing cell: the dense matrix is what is meant
+        x = _densify(x)
     na_method = _match_use(use)
     if na_method == "na.or.complete":
         raise ValueError("'na.or.complete' is not a supported value for `use`. "
@@ -948,6 +993,8 @@ def cor_fast(x, y=None, use="everything", method="pearson", alternative="two.sid
     Unlike the reference, ``n_values`` is each pair's own count (R/other_correlations.R:167 overwrites the whole
     vector with one pair's count).
     """
+    if _lib.is_sparse(x):   # zero is a value here, not a missing cell: the dense matrix is what is meant
+        x = _densify(x)
     na_method = _match_use(use)
     if na_method == "na.or.complete":
         raise ValueError("'na.or.complete' is not a supported value for `use`. "
@@ -1112,9 +1159,11 @@ def _diag_matrix(data_matrix, colnames, arg):
     rows = None
     if pd is not None and isinstance(data_matrix, pd.DataFrame):
         rows = data_matrix.index
+    elif colnames is None and _lib.is_sparse(data_matrix):
+        colnames = list(range(data_matrix.shape[1]))
     elif colnames is None:
         colnames = list(range(np.shape(data_matrix)[1])) if np.ndim(data_matrix) == 2 else []
-    X, names = _as_matrix(data_matrix, colnames, arg, keep_dtype=True)
+    X, names = _as_matrix(data_matrix, colnames, arg, keep_dtype=True, keep_sparse=True)
     return X, names, rows
 
 
@@ -1142,6 +1191,8 @@ def _device_rule(X, global_na):
     vals = [] if global_na is None else [float(v) for v in np.atleast_1d(np.asarray(global_na, dtype=np.float64))]
     if len({v for v in vals if math.isfinite(v)}) <= _lib.MASK_VALS:
         return X, vals, None
+    if _lib.is_sparse(X):
+        X = _densify(X)
     X = np.asarray(X, dtype=np.float64)
     excl = setup_missing_matrix(X, vals)
     return _masked_fortran(X, excl), [math.nan], excl
@@ -1230,15 +1281,17 @@ def calculate_matrix_medians(in_matrix, use="col", na_rm=False, engine=None):
 
     ``na_rm`` is median's na.rm: without it a column holding NaN gives NA.  An empty column gives NA; the mean of
     -Inf and Inf gives NaN.  Any ``use`` other than "row" means columns, as ``%in% "row"`` does.  Runs on the MI355X
-    (icikt_col_medians_f64); an ``engine`` without ``col_medians`` gets the same arithmetic in numpy.
+    (icikt_col_medians_f64); an ``engine`` without ``col_medians`` gets the same arithmetic in numpy.  A sparse
+    ``in_matrix`` goes to the device as its CSC arrays (absent cells are zeros, and zeros are values here);
+    ``use="row"`` and any engine but the HIP one densify it with ``toarray()``.
     """
     X, _names, _rows = _diag_matrix(in_matrix, None, "in_matrix")
     if use == "row":
-        X = X.T
+        X = (_densify(X) if _lib.is_sparse(X) else X).T
     eng = engine or _default_engine()
     if hasattr(eng, "col_medians"):
         return eng.col_medians(_for_engine(X, eng), na_rm)
-    return _col_medians_numpy(np.asfortranarray(X, dtype=np.float64), na_rm)
+    return _col_medians_numpy(np.asfortranarray(_densify(X) if _lib.is_sparse(X) else X, dtype=np.float64), na_rm)
 
 
 def test_left_censorship(data_matrix, global_na=(float("nan"), float("inf"), 0), sample_classes=None, engine=None):
@@ -1251,7 +1304,8 @@ def test_left_censorship(data_matrix, global_na=(float("nan"), float("inf"), 0),
     column), ``success`` those below it.  Returns ``{"values": data.frame(trials, success, class), "binomial_test":
     binom.test(sum(success), sum(trials), p = 0.5, alternative = "greater")}``, or None (with a message) when the
     ``global_na`` rule excludes nothing.  The counts run on the MI355X (icikt_censor_counts_f64); an ``engine`` without
-    ``censor_counts`` gets the same arithmetic in numpy.
+    ``censor_counts`` gets the same arithmetic in numpy.  A sparse ``data_matrix`` goes to the device as its CSC arrays;
+    more than 32 finite ``global_na`` values and any engine but the HIP one densify it with ``toarray()``.
     """
     X, _names, _rows = _diag_matrix(data_matrix, None, "data_matrix")
     levels, cls = _class_levels(sample_classes, X.shape[1], "A")
@@ -1287,6 +1341,8 @@ def rank_order_data(data_matrix, global_na=(float("nan"), float("inf"), 0), samp
     reference -- or None when no row is left.  One class returns its element, several a dict in class order.  Columns
     are split by position (the reference splits colnames(), which fails without column names).  Runs on the MI355X
     (icikt_rank_order_f64, one call per class); an ``engine`` without ``rank_order`` gets the same arithmetic in numpy.
+    A sparse ``data_matrix`` goes to the device as its CSC arrays (column names from ``colnames=``); more than 32 finite
+    ``global_na`` values and any engine but the HIP one densify it with ``toarray()``.
     """
     X, names, rows = _diag_matrix(data_matrix, colnames, "data_matrix")
     levels, cls = _class_levels(sample_classes, X.shape[1], "rmf_abcd")

@@ -608,6 +608,29 @@ int check_view(icikt_ctx* c, const char* who, const icikt_input* X, int64_t n_fe
   return ICIKT_SUCCESS;
 }
 
+int check_src(icikt_ctx* c, const char* who, const MatrixSrc& X, int64_t n_feat, int64_t n_samp, bool wide_ok) {
+  if (!X.sparse) return check_view(c, who, X.null ? nullptr : &X.v, n_feat, n_samp, wide_ok);
+  const std::string w(who);
+  if (X.null) return fail(c, ICIKT_E_INVALID, w + ": X is null (the icikt_csc_input view of the matrix)");
+  const icikt_csc_input& s = X.s;
+  if (s.dtype < ICIKT_DTYPE_F64 || s.dtype > ICIKT_DTYPE_I64)
+    return fail(c, ICIKT_E_INVALID, w + ": X->dtype must be one of ICIKT_DTYPE_F64, _F32, _I32, _I64");
+  if (s.index_type != ICIKT_INDEX_I32 && s.index_type != ICIKT_INDEX_I64)
+    return fail(c, ICIKT_E_INVALID, w + ": X->index_type must be ICIKT_INDEX_I32 or ICIKT_INDEX_I64");
+  const int rc = check_shape(c, who, n_feat, n_samp, n_feat, wide_ok);
+  if (rc) return rc;
+  if (!s.indptr) return fail(c, ICIKT_E_INVALID, w + ": X->indptr is null (n_samp + 1 column offsets)");
+  if (csc_ptr(s, 0) < 0) return fail(c, ICIKT_E_INVALID, w + ": X->indptr[0] is negative");
+  for (int64_t j = 0; j < n_samp; ++j)
+    if (csc_ptr(s, j + 1) < csc_ptr(s, j))
+      return fail(c, ICIKT_E_INVALID, w + ": X->indptr decreases at column " + std::to_string((long long)j));
+  if (csc_ptr(s, n_samp) > csc_ptr(s, 0)) {
+    if (!s.values) return fail(c, ICIKT_E_INVALID, w + ": X->values is null (the matrix has entries)");
+    if (!s.indices) return fail(c, ICIKT_E_INVALID, w + ": X->indices is null (the matrix has entries)");
+  }
+  return ICIKT_SUCCESS;
+}
+
 }  // namespace host
 }  // namespace icikt
 
@@ -994,7 +1017,7 @@ namespace host {
 // device chunk by chunk (MatrixUpload::copy), so everything behind a chunk's event sees the same float64 columns.
 constexpr size_t kRowRunBytes = 512;               // a row-major chunk: runs of at least this many bytes ...
 constexpr size_t kRowHalfMax = (size_t)64 << 20;   // ... while a half of the staging blocks stays within this
-int upload_and_prepare(icikt_ctx* c, const icikt_input& X, int64_t n_feat, int64_t n_samp, int64_t col_begin,
+int upload_and_prepare(icikt_ctx* c, const MatrixSrc& X, int64_t n_feat, int64_t n_samp, int64_t col_begin,
                        int64_t col_end, uint32_t flags, bool pipelined, const std::function<int(size_t, int64_t)>* on_chunk,
                        int prepass) {
   // what runs over the columns of a chunk once they are on the device
@@ -1004,6 +1027,7 @@ int upload_and_prepare(icikt_ctx* c, const icikt_input& X, int64_t n_feat, int64
     return ICIKT_SUCCESS;
   };
   c->chunk_col_end.clear();
+  c->xfer.csc_pending = false;
   const size_t nel = (size_t)std::max<int64_t>(n_feat * n_samp, 1);
   HIPCHK(c, c->d_X.reserve(nel));
   int rc = timer_begin(c, ICIKT_K_PREPARE, flags);
@@ -1022,13 +1046,23 @@ int upload_and_prepare(icikt_ctx* c, const icikt_input& X, int64_t n_feat, int64
     // float64 columns at 262 144 rows: runs of 32 bytes).  The host's packing rate grows with the run up to about 512
     // bytes (DESIGN.md section 11 has the figures), so a row-major chunk is at least that wide where a half of the
     // staging blocks stays within 64 MB.
-    if (X.order == ICIKT_ORDER_ROW) {
-      const size_t es = dtype_bytes(X.dtype);
+    if (!X.sparse && X.v.order == ICIKT_ORDER_ROW) {
+      const size_t es = dtype_bytes(X.v.dtype);
       chunk = std::max<int64_t>(chunk, (int64_t)std::min(kRowRunBytes / es, std::max<size_t>(1, kRowHalfMax / ((size_t)n_feat * es))));
     }
     if (prepass == kPrepassFull) chunk = std::min<int64_t>(chunk, std::max(1, c->sort_chunk));
-    const size_t span = view_span(view_from_col(X, col_begin), n_feat, ncols);
-    MatrixUpload up{c, X, n_feat, view_is_plain(X) ? chunk : std::min<int64_t>(chunk, ncols)};
+    MatrixUpload up{c, X, n_feat, (!X.sparse && view_is_plain(X.v)) ? chunk : std::min<int64_t>(chunk, ncols)};
+    size_t span = 0;
+    if (X.sparse) {
+      // the bytes the route is chosen by are the entries' (values + indices of the columns); the halves of the staging
+      // blocks hold the chunk with the most entries
+      up.n_samp = n_samp;
+      for (int64_t c0 = col_begin; c0 < col_end; c0 += chunk)
+        up.csc_max_nnz = std::max(up.csc_max_nnz, csc_ptr(X.s, std::min(c0 + chunk, col_end)) - csc_ptr(X.s, c0));
+      span = (size_t)(csc_ptr(X.s, col_end) - csc_ptr(X.s, col_begin)) * (dtype_bytes(X.s.dtype) + index_bytes(X.s.index_type));
+    } else {
+      span = view_span(view_from_col(X.v, col_begin), n_feat, ncols);
+    }
     hipError_t e = up.begin(span, pipelined ? c->prep_stream : nullptr);
     int k = 0;
     const int64_t first_chunk = chunk;   // (a short first chunk was measured twice: no gain -- what the last pair-kernel launch waits for is the last chunk's pre-pass, which finds no free CU until the launch before it drains)
@@ -1061,14 +1095,24 @@ int upload_and_prepare(icikt_ctx* c, const icikt_input& X, int64_t n_feat, int64
         if (e == hipSuccess) rc = chunk_prepass(c0, c0 + nc, nullptr);
       }
     }
+    if (e == hipSuccess && rc == 0) e = up.finish();   // (a CSC view: the scatter kernel's error record comes back behind the last chunk)
     if (pipelined && (e != hipSuccess || rc)) (void)hipStreamSynchronize(c->prep_stream);
     // The staging buffer serves the later transfers of the call as their bounce buffer, so its last copy is waited for
     // here.  A matrix the caller has page-locked is read in place: the pipelined callers go on with host work (the task
     // list) and wait for the copy stream themselves before they return (end_call) -- no entry point returns while
     // a copy still reads the caller's memory.
-    if (!(pipelined && up.in_place) || e != hipSuccess || rc) (void)hipStreamSynchronize(c->copy_stream);
-    if (e != hipSuccess) return fail(c, ICIKT_E_HIP, std::string("H2D of the matrix: ") + hipGetErrorString(e));
-    if (rc) return rc;
+    const bool drained = !(pipelined && up.in_place) || e != hipSuccess || rc;
+    if (drained) {
+      const hipError_t es = hipStreamSynchronize(c->copy_stream);
+      if (e == hipSuccess) e = es;
+    }
+    if (e != hipSuccess) { c->xfer.csc_pending = false; return fail(c, ICIKT_E_HIP, std::string("H2D of the matrix: ") + hipGetErrorString(e)); }
+    if (rc) { c->xfer.csc_pending = false; return rc; }
+    // malformed CSC input fails the call as soon as the copy stream has drained (else: end_call)
+    if (drained) {
+      rc = csc_verdict(c);
+      if (rc) { if (pipelined) (void)hipStreamSynchronize(c->prep_stream); return rc; }
+    }
   } else if (ncols > 0 && prepass == kPrepassFull) {
     rc = prepare_launch(c, c->d_X.p, n_feat, col_begin, col_end);  // n_feat == 0: statistics of empty columns
     if (rc) return rc;
@@ -1093,11 +1137,11 @@ void prebuild_units(icikt_ctx* c) {
 // launch per chunk behind that chunk's pre-pass event.  The pairs among the columns that have arrived are counted
 // while the rest of the matrix still crosses PCIe: the available work grows with the square of the arrived columns,
 // so after the first millisecond of a c4-sized call the GPU never waits for the link again.
-int upload_prepare_pairs(icikt_ctx* c, const icikt_input& X, int64_t n_feat, int64_t n_samp, uint32_t flags) {
+int upload_prepare_pairs(icikt_ctx* c, const MatrixSrc& X, int64_t n_feat, int64_t n_samp, uint32_t flags) {
   const size_t col_bytes = (size_t)n_feat * sizeof(double);
   // (the size that decides for the pipeline is the float64 matrix's, whatever the view's element type and order: a view
   //  runs the launches its float64 copy runs)
-  const int64_t ld = view_is_plain(X) ? X.ld : n_feat;
+  const int64_t ld = (!X.sparse && view_is_plain(X.v)) ? X.v.ld : n_feat;
   const size_t span = (n_samp > 0 && n_feat > 0) ? ((size_t)(n_samp - 1) * (size_t)ld + (size_t)n_feat) * sizeof(double) : 0;
   const bool can = !c->pv.wide && n_feat > 0 && c->n_pairs > 0;
   const bool want = c->pipe_mode < 0 ? (span >= ((size_t)24 << 20)) : (c->pipe_mode == 1 && (size_t)n_samp * col_bytes > ((size_t)8 << 20));
@@ -1261,11 +1305,11 @@ int check_pair_list(icikt_ctx* c, const char* who, const int32_t* pi, const int3
   return ICIKT_SUCCESS;
 }
 
-int check_pair_args(icikt_ctx* c, const char* who, const icikt_input* X, int64_t n_feat, int64_t n_samp,
+int check_pair_args(icikt_ctx* c, const char* who, const MatrixSrc& X, int64_t n_feat, int64_t n_samp,
                     const int32_t* pi, const int32_t* pj, int64_t* n_pairs, const void* out, bool out5,
                     int perspective, int alternative) {
   const std::string w(who);
-  int rc = check_view(c, who, X, n_feat, n_samp);
+  int rc = check_src(c, who, X, n_feat, n_samp);
   if (rc) return rc;
   if (pi == nullptr) {
     if (pj != nullptr) return fail(c, ICIKT_E_INVALID, w + ": pi is null but pj is not");
@@ -1284,6 +1328,15 @@ int check_pair_args(icikt_ctx* c, const char* who, const icikt_input* X, int64_t
 }  // namespace host
 }  // namespace icikt
 using icikt::host::check_pair_list;
+using icikt::host::MatrixSrc;
+
+static int pairs_src(icikt_ctx* c, const MatrixSrc& X, int64_t n_feat, int64_t n_samp, const int32_t* pi,
+                     const int32_t* pj, int64_t n_pairs, int perspective, int alternative, int continuity, uint32_t flags,
+                     double* out4, int64_t* counts, int32_t* reasons);
+static int matrix_src(icikt_ctx* c, const MatrixSrc& X, int64_t n_feat, int64_t n_samp, const double* global_na,
+                      int n_global_na, const int32_t* pi, const int32_t* pj, int64_t n_pairs, int perspective,
+                      int alternative, int continuity, uint32_t flags, int scale_max, int diag_good, double* out5,
+                      uint8_t* keep, int64_t* reason_counts);
 
 extern "C" {
 
@@ -1298,6 +1351,23 @@ int icikt_pairs_f64(icikt_ctx* c, const double* X, int64_t n_feat, int64_t n_sam
 int icikt_pairs_in(icikt_ctx* c, const icikt_input* X, int64_t n_feat, int64_t n_samp, const int32_t* pi,
                    const int32_t* pj, int64_t n_pairs, int perspective, int alternative, int continuity, uint32_t flags,
                    double* out4, int64_t* counts, int32_t* reasons) {
+  return pairs_src(c, MatrixSrc::dense(X), n_feat, n_samp, pi, pj, n_pairs, perspective, alternative, continuity, flags, out4,
+                   counts, reasons);
+}
+
+int icikt_pairs_csc(icikt_ctx* c, const icikt_csc_input* X, int64_t n_feat, int64_t n_samp, const int32_t* pi,
+                    const int32_t* pj, int64_t n_pairs, int perspective, int alternative, int continuity, uint32_t flags,
+                    double* out4, int64_t* counts, int32_t* reasons) {
+  return pairs_src(c, MatrixSrc::csc(X), n_feat, n_samp, pi, pj, n_pairs, perspective, alternative, continuity, flags, out4,
+                   counts, reasons);
+}
+
+}  // extern "C"
+
+// the body of icikt_pairs_in / icikt_pairs_csc
+static int pairs_src(icikt_ctx* c, const MatrixSrc& X, int64_t n_feat, int64_t n_samp, const int32_t* pi,
+                     const int32_t* pj, int64_t n_pairs, int perspective, int alternative, int continuity, uint32_t flags,
+                     double* out4, int64_t* counts, int32_t* reasons) {
   if (!c) return ICIKT_E_INVALID;
   // every argument is validated before the first asynchronous copy reads the caller's memory
   int rc = icikt::host::check_pair_args(c, "pairs", X, n_feat, n_samp, pi, pj, &n_pairs, out4, false, perspective,
@@ -1313,7 +1383,7 @@ int icikt_pairs_in(icikt_ctx* c, const icikt_input* X, int64_t n_feat, int64_t n
   // crosses PCIe (it used to wait for the copies first and build the list afterwards, with the GPU idle: 1.2 ms of
   // 14.3 on c4).  Nothing may still read the caller's matrix when the call returns: end_call.
   const icikt::host::PinnedScope scope(c, flags);
-  rc = icikt::host::upload_prepare_pairs(c, *X, n_feat, n_samp, flags);
+  rc = icikt::host::upload_prepare_pairs(c, X, n_feat, n_samp, flags);
   const int64_t P = c->n_pairs;
   if (rc || P == 0) return icikt::host::end_call(c, "pairs", rc);
   auto body = [&]() -> int {
@@ -1332,8 +1402,6 @@ int icikt_pairs_in(icikt_ctx* c, const icikt_input* X, int64_t n_feat, int64_t n
   // success or not: nothing may still be reading or writing the caller's buffers when this returns
   return icikt::host::end_call(c, "pairs", body());
 }
-
-}  // extern "C"
 
 namespace icikt {
 namespace host {
@@ -1378,6 +1446,25 @@ int icikt_matrix_in(icikt_ctx* c, const icikt_input* X, int64_t n_feat, int64_t 
                     int n_global_na, const int32_t* pi, const int32_t* pj, int64_t n_pairs, int perspective,
                     int alternative, int continuity, uint32_t flags, int scale_max, int diag_good, double* out5,
                     uint8_t* keep, int64_t* reason_counts) {
+  return matrix_src(c, MatrixSrc::dense(X), n_feat, n_samp, global_na, n_global_na, pi, pj, n_pairs, perspective, alternative,
+                    continuity, flags, scale_max, diag_good, out5, keep, reason_counts);
+}
+
+int icikt_matrix_csc(icikt_ctx* c, const icikt_csc_input* X, int64_t n_feat, int64_t n_samp, const double* global_na,
+                     int n_global_na, const int32_t* pi, const int32_t* pj, int64_t n_pairs, int perspective,
+                     int alternative, int continuity, uint32_t flags, int scale_max, int diag_good, double* out5,
+                     uint8_t* keep, int64_t* reason_counts) {
+  return matrix_src(c, MatrixSrc::csc(X), n_feat, n_samp, global_na, n_global_na, pi, pj, n_pairs, perspective, alternative,
+                    continuity, flags, scale_max, diag_good, out5, keep, reason_counts);
+}
+
+}  // extern "C"
+
+// the body of icikt_matrix_in / icikt_matrix_csc
+static int matrix_src(icikt_ctx* c, const MatrixSrc& X, int64_t n_feat, int64_t n_samp, const double* global_na,
+                      int n_global_na, const int32_t* pi, const int32_t* pj, int64_t n_pairs, int perspective,
+                      int alternative, int continuity, uint32_t flags, int scale_max, int diag_good, double* out5,
+                      uint8_t* keep, int64_t* reason_counts) {
   if (!c) return ICIKT_E_INVALID;
   int rc = icikt::host::check_pair_args(c, "matrix", X, n_feat, n_samp, pi, pj, &n_pairs, out5, true, perspective,
                                         alternative);
@@ -1403,7 +1490,7 @@ int icikt_matrix_in(icikt_ctx* c, const icikt_input* X, int64_t n_feat, int64_t 
   const icikt::host::PinnedScope scope(c, flags);
   c->k0_mask = &ms;
   c->k0_keep = keep_bytes ? c->d_keep.p : nullptr;
-  rc = icikt::host::upload_prepare_pairs(c, *X, n_feat, n_samp, flags);
+  rc = icikt::host::upload_prepare_pairs(c, X, n_feat, n_samp, flags);
   c->k0_mask = nullptr;
   c->k0_keep = nullptr;
   if (rc) return icikt::host::end_call(c, "matrix", rc);
@@ -1425,8 +1512,6 @@ int icikt_matrix_in(icikt_ctx* c, const icikt_input* X, int64_t n_feat, int64_t 
   if (reason_counts) for (int k = 0; k < 5; ++k) reason_counts[k] = (int64_t)red[1 + k];
   return ICIKT_SUCCESS;
 }
-
-}  // extern "C"
 
 extern "C" {
 
@@ -1527,10 +1612,11 @@ int icikt_missingness_f64(icikt_ctx* c, const double* X, int64_t n_feat, int64_t
   return icikt_missingness_in(c, &v, n_feat, n_samp, pi, pj, n_pairs, missingness);
 }
 
-int icikt_missingness_in(icikt_ctx* c, const icikt_input* X, int64_t n_feat, int64_t n_samp, const int32_t* pi,
-                         const int32_t* pj, int64_t n_pairs, int64_t* missingness) {
+// the body of icikt_missingness_in / icikt_missingness_csc
+static int missingness_src(icikt_ctx* c, const MatrixSrc& X, int64_t n_feat, int64_t n_samp, const int32_t* pi,
+                           const int32_t* pj, int64_t n_pairs, int64_t* missingness) {
   if (!c) return ICIKT_E_INVALID;
-  int rc = check_view(c, "missingness", X, n_feat, n_samp);
+  int rc = icikt::host::check_src(c, "missingness", X, n_feat, n_samp);
   if (rc) return rc;
   if (n_pairs < 0) return fail(c, ICIKT_E_INVALID, "missingness: bad shape");
   if (n_pairs == 0) return ICIKT_SUCCESS;
@@ -1546,7 +1632,7 @@ int icikt_missingness_in(icikt_ctx* c, const icikt_input* X, int64_t n_feat, int
   rc = icikt::host::mask_alloc(c, n_feat, n_samp);
   if (rc) return rc;
   if (n_feat > 0) {
-    rc = icikt::host::upload_and_prepare(c, *X, n_feat, n_samp, 0, n_samp, 0u, false, nullptr, icikt::host::kPrepassMask);
+    rc = icikt::host::upload_and_prepare(c, X, n_feat, n_samp, 0, n_samp, 0u, false, nullptr, icikt::host::kPrepassMask);
     if (rc) return rc;
   }
   auto body = [&]() -> int {
@@ -1555,6 +1641,16 @@ int icikt_missingness_in(icikt_ctx* c, const icikt_input* X, int64_t n_feat, int
     return icikt::host::download(c, missingness, c->d_counts.p, (size_t)n_pairs * sizeof(int64_t));
   };
   return icikt::host::end_call(c, "missingness", body());
+}
+
+int icikt_missingness_in(icikt_ctx* c, const icikt_input* X, int64_t n_feat, int64_t n_samp, const int32_t* pi,
+                         const int32_t* pj, int64_t n_pairs, int64_t* missingness) {
+  return missingness_src(c, MatrixSrc::dense(X), n_feat, n_samp, pi, pj, n_pairs, missingness);
+}
+
+int icikt_missingness_csc(icikt_ctx* c, const icikt_csc_input* X, int64_t n_feat, int64_t n_samp, const int32_t* pi,
+                          const int32_t* pj, int64_t n_pairs, int64_t* missingness) {
+  return missingness_src(c, MatrixSrc::csc(X), n_feat, n_samp, pi, pj, n_pairs, missingness);
 }
 
 int icikt_convert_dev(icikt_ctx* c, const void* d_src, int dtype, int order, int64_t n_feat, int64_t n_samp, int64_t ld,
@@ -1569,6 +1665,47 @@ int icikt_convert_dev(icikt_ctx* c, const void* d_src, int dtype, int order, int
   rc = use_device(c);
   if (rc) return rc;
   HIPCHK(c, icikt::launch_ingest(d_src, dtype, order, ld, n_feat, n_samp, d_dst, dst_ld, c->stream));
+  return ICIKT_SUCCESS;
+}
+
+int icikt_scatter_csc_dev(icikt_ctx* c, const void* d_values, const void* d_indices, const void* d_indptr, int dtype,
+                          int index_type, double fill, int64_t n_feat, int64_t n_samp, double* d_dst, int64_t dst_ld) {
+  if (!c) return ICIKT_E_INVALID;
+  if (dtype < ICIKT_DTYPE_F64 || dtype > ICIKT_DTYPE_I64)
+    return fail(c, ICIKT_E_INVALID, "scatter_csc: dtype must be one of ICIKT_DTYPE_F64, _F32, _I32, _I64");
+  if (index_type != ICIKT_INDEX_I32 && index_type != ICIKT_INDEX_I64)
+    return fail(c, ICIKT_E_INVALID, "scatter_csc: index_type must be ICIKT_INDEX_I32 or ICIKT_INDEX_I64");
+  int rc = check_shape(c, "scatter_csc", n_feat, n_samp, n_feat);
+  if (rc) return rc;
+  if (dst_ld < n_feat) return fail(c, ICIKT_E_INVALID, "scatter_csc: dst_ld is below n_feat");
+  if (n_feat == 0 || n_samp == 0) return ICIKT_SUCCESS;
+  if (!d_dst) return fail(c, ICIKT_E_INVALID, "scatter_csc: null d_dst");
+  if (!d_indptr) return fail(c, ICIKT_E_INVALID, "scatter_csc: null d_indptr");
+  rc = use_device(c);
+  if (rc) return rc;
+  // the column offsets are read back and checked as the host entries check theirs: O(n_samp)
+  const size_t is = icikt::host::index_bytes(index_type);
+  std::vector<char> hp;
+  try {
+    hp.resize((size_t)(n_samp + 1) * is);
+  } catch (const std::bad_alloc&) {
+    return fail(c, ICIKT_E_NOMEM, "scatter_csc: host allocation failed");
+  }
+  HIPCHK(c, hipMemcpyAsync(hp.data(), d_indptr, hp.size(), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  const icikt_csc_input v{d_values, d_indices, hp.data(), dtype, index_type, fill};
+  // (values / indices are device pointers: check_src only asks whether they are null)
+  rc = icikt::host::check_src(c, "scatter_csc", MatrixSrc::csc(&v), n_feat, n_samp);
+  if (rc) return rc;
+  const int64_t nnz = icikt::host::csc_ptr(v, n_samp);
+  HIPCHK(c, c->d_csc_err.reserve(icikt::ICIKT_CSC_ERR_WORDS));
+  HIPCHK(c, hipMemsetAsync(c->d_csc_err.p, 0, icikt::ICIKT_CSC_ERR_WORDS * sizeof(unsigned long long), c->stream));
+  HIPCHK(c, icikt::launch_scatter_csc(d_values, dtype, d_indices, d_indptr, index_type, 0, 0, nnz, fill, n_feat, n_samp,
+                                      d_dst, dst_ld, c->d_csc_err.p, c->stream));
+  unsigned long long rec[icikt::ICIKT_CSC_ERR_WORDS] = {};
+  HIPCHK(c, hipMemcpyAsync(rec, c->d_csc_err.p, sizeof(rec), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  if (rec[0] != 0) return fail(c, ICIKT_E_INVALID, "scatter_csc: " + icikt::host::csc_message(rec));
   return ICIKT_SUCCESS;
 }
 

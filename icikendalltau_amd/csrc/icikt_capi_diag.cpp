@@ -15,6 +15,7 @@
 
 using icikt::host::f64_view;
 using icikt::host::fail;
+using icikt::host::MatrixSrc;
 using icikt::host::timer_begin;
 using icikt::host::timer_end;
 using icikt::host::use_device;
@@ -60,15 +61,25 @@ int diag_col_pass(icikt_ctx* c, const double* dX, int64_t n, int64_t S, const ic
 }
 
 // shape, matrix, global_na of the three entries; sets *ms
-int diag_args(icikt_ctx* c, const char* who, const icikt_input* X, int64_t n_feat, int64_t n_samp,
+int diag_args(icikt_ctx* c, const char* who, const MatrixSrc& X, int64_t n_feat, int64_t n_samp,
               const double* global_na, int n_global_na, icikt::MaskSpec* ms) {
-  int rc = icikt::host::check_view(c, who, X, n_feat, n_samp);
+  int rc = icikt::host::check_src(c, who, X, n_feat, n_samp);
   if (rc) return rc;
   if (n_samp > INT32_MAX) return fail(c, ICIKT_E_INVALID, std::string(who) + ": too many columns");
   rc = icikt::host::make_mask_spec(c, global_na, n_global_na, ms);
   if (rc) c->err = std::string(who) + c->err.substr(c->err.find(':'));
   return rc;
 }
+
+// the bodies the _in and _csc entries share
+int col_medians_src(icikt_ctx* c, const MatrixSrc& X, int64_t n_feat, int64_t n_samp, const double* global_na,
+                    int n_global_na, int na_rm, uint32_t flags, double* medians);
+int censor_counts_src(icikt_ctx* c, const MatrixSrc& X, int64_t n_feat, int64_t n_samp, const double* global_na,
+                      int n_global_na, const int32_t* cls, int n_class, uint32_t flags, int64_t* trials, int64_t* success,
+                      int64_t* n_excluded, double* medians);
+int rank_order_src(icikt_ctx* c, const MatrixSrc& X, int64_t n_feat, int64_t n_samp, const double* global_na,
+                   int n_global_na, const int32_t* cols, int64_t n_cols, uint32_t flags, int64_t* n_kept, int32_t* n_na,
+                   double* median_rank, int32_t* row_order, int32_t* col_order, double* original, double* ordered);
 
 }  // namespace
 
@@ -82,6 +93,20 @@ int icikt_col_medians_f64(icikt_ctx* c, const double* X, int64_t n_feat, int64_t
 
 int icikt_col_medians_in(icikt_ctx* c, const icikt_input* X, int64_t n_feat, int64_t n_samp, const double* global_na,
                          int n_global_na, int na_rm, uint32_t flags, double* medians) {
+  return col_medians_src(c, MatrixSrc::dense(X), n_feat, n_samp, global_na, n_global_na, na_rm, flags, medians);
+}
+
+int icikt_col_medians_csc(icikt_ctx* c, const icikt_csc_input* X, int64_t n_feat, int64_t n_samp,
+                          const double* global_na, int n_global_na, int na_rm, uint32_t flags, double* medians) {
+  return col_medians_src(c, MatrixSrc::csc(X), n_feat, n_samp, global_na, n_global_na, na_rm, flags, medians);
+}
+
+}  // extern "C"
+
+namespace {
+
+int col_medians_src(icikt_ctx* c, const MatrixSrc& X, int64_t n_feat, int64_t n_samp, const double* global_na,
+                    int n_global_na, int na_rm, uint32_t flags, double* medians) {
   if (!c) return ICIKT_E_INVALID;
   icikt::MaskSpec ms;
   int rc = diag_args(c, "col_medians", X, n_feat, n_samp, global_na, n_global_na, &ms);
@@ -92,7 +117,7 @@ int icikt_col_medians_in(icikt_ctx* c, const icikt_input* X, int64_t n_feat, int
   if (rc) return rc;
   const icikt::host::PinnedScope scope(c, flags);
   auto body = [&]() -> int {
-    int r = icikt::host::upload_and_prepare(c, *X, n_feat, n_samp, 0, n_samp, flags, false, nullptr,
+    int r = icikt::host::upload_and_prepare(c, X, n_feat, n_samp, 0, n_samp, flags, false, nullptr,
                                             icikt::host::kPrepassNone);
     if (!r) r = timer_begin(c, ICIKT_K_PAIRS, flags);
     if (!r) r = diag_col_pass(c, c->d_X.p, n_feat, n_samp, ms, na_rm, nullptr, nullptr);
@@ -102,6 +127,10 @@ int icikt_col_medians_in(icikt_ctx* c, const icikt_input* X, int64_t n_feat, int
   };
   return icikt::host::end_call(c, "col_medians", body());
 }
+
+}  // namespace
+
+extern "C" {
 
 int icikt_censor_counts_f64(icikt_ctx* c, const double* X, int64_t n_feat, int64_t n_samp, int64_t ld,
                             const double* global_na, int n_global_na, const int32_t* cls, int n_class, uint32_t flags,
@@ -114,6 +143,24 @@ int icikt_censor_counts_f64(icikt_ctx* c, const double* X, int64_t n_feat, int64
 int icikt_censor_counts_in(icikt_ctx* c, const icikt_input* X, int64_t n_feat, int64_t n_samp, const double* global_na,
                            int n_global_na, const int32_t* cls, int n_class, uint32_t flags, int64_t* trials,
                            int64_t* success, int64_t* n_excluded, double* medians) {
+  return censor_counts_src(c, MatrixSrc::dense(X), n_feat, n_samp, global_na, n_global_na, cls, n_class, flags, trials,
+                           success, n_excluded, medians);
+}
+
+int icikt_censor_counts_csc(icikt_ctx* c, const icikt_csc_input* X, int64_t n_feat, int64_t n_samp,
+                            const double* global_na, int n_global_na, const int32_t* cls, int n_class, uint32_t flags,
+                            int64_t* trials, int64_t* success, int64_t* n_excluded, double* medians) {
+  return censor_counts_src(c, MatrixSrc::csc(X), n_feat, n_samp, global_na, n_global_na, cls, n_class, flags, trials,
+                           success, n_excluded, medians);
+}
+
+}  // extern "C"
+
+namespace {
+
+int censor_counts_src(icikt_ctx* c, const MatrixSrc& X, int64_t n_feat, int64_t n_samp, const double* global_na,
+                      int n_global_na, const int32_t* cls, int n_class, uint32_t flags, int64_t* trials, int64_t* success,
+                      int64_t* n_excluded, double* medians) {
   if (!c) return ICIKT_E_INVALID;
   icikt::MaskSpec ms;
   int rc = diag_args(c, "censor_counts", X, n_feat, n_samp, global_na, n_global_na, &ms);
@@ -142,7 +189,7 @@ int icikt_censor_counts_in(icikt_ctx* c, const icikt_input* X, int64_t n_feat, i
   std::vector<unsigned long long> out3((size_t)n_class * 3);
   std::vector<int32_t> nexcl((size_t)n_samp);
   auto body = [&]() -> int {
-    int r = icikt::host::upload_and_prepare(c, *X, n_feat, n_samp, 0, n_samp, flags, false, nullptr,
+    int r = icikt::host::upload_and_prepare(c, X, n_feat, n_samp, 0, n_samp, flags, false, nullptr,
                                             icikt::host::kPrepassNone);
     if (r) return r;
     HIPCHK(c, db.lists.reserve(off.size() + cols.size()));
@@ -174,6 +221,10 @@ int icikt_censor_counts_in(icikt_ctx* c, const icikt_input* X, int64_t n_feat, i
   return ICIKT_SUCCESS;
 }
 
+}  // namespace
+
+extern "C" {
+
 int icikt_rank_order_f64(icikt_ctx* c, const double* X, int64_t n_feat, int64_t n_samp, int64_t ld,
                          const double* global_na, int n_global_na, const int32_t* cols, int64_t n_cols, uint32_t flags,
                          int64_t* n_kept, int32_t* n_na, double* median_rank, int32_t* row_order, int32_t* col_order,
@@ -187,6 +238,25 @@ int icikt_rank_order_in(icikt_ctx* c, const icikt_input* X, int64_t n_feat, int6
                         int n_global_na, const int32_t* cols, int64_t n_cols, uint32_t flags, int64_t* n_kept,
                         int32_t* n_na, double* median_rank, int32_t* row_order, int32_t* col_order, double* original,
                         double* ordered) {
+  return rank_order_src(c, MatrixSrc::dense(X), n_feat, n_samp, global_na, n_global_na, cols, n_cols, flags, n_kept, n_na,
+                        median_rank, row_order, col_order, original, ordered);
+}
+
+int icikt_rank_order_csc(icikt_ctx* c, const icikt_csc_input* X, int64_t n_feat, int64_t n_samp,
+                         const double* global_na, int n_global_na, const int32_t* cols, int64_t n_cols, uint32_t flags,
+                         int64_t* n_kept, int32_t* n_na, double* median_rank, int32_t* row_order, int32_t* col_order,
+                         double* original, double* ordered) {
+  return rank_order_src(c, MatrixSrc::csc(X), n_feat, n_samp, global_na, n_global_na, cols, n_cols, flags, n_kept, n_na,
+                        median_rank, row_order, col_order, original, ordered);
+}
+
+}  // extern "C"
+
+namespace {
+
+int rank_order_src(icikt_ctx* c, const MatrixSrc& X, int64_t n_feat, int64_t n_samp, const double* global_na,
+                   int n_global_na, const int32_t* cols, int64_t n_cols, uint32_t flags, int64_t* n_kept, int32_t* n_na,
+                   double* median_rank, int32_t* row_order, int32_t* col_order, double* original, double* ordered) {
   if (!c) return ICIKT_E_INVALID;
   icikt::MaskSpec ms;
   int rc = diag_args(c, "rank_order", X, n_feat, n_samp, global_na, n_global_na, &ms);
@@ -204,26 +274,65 @@ int icikt_rank_order_in(icikt_ctx* c, const icikt_input* X, int64_t n_feat, int6
   // order), else gathered on the host in the view's element type, column-major (one pass)
   bool consecutive = true;
   for (int64_t j = 1; j < n_cols && consecutive; ++j) consecutive = cols[j] == cols[0] + j;
-  std::vector<char> gathered;
-  icikt_input src = n > 0 ? icikt::host::view_from_col(*X, cols[0]) : *X;
+  std::vector<char> gathered, gathered_idx, gathered_ptr;
+  bool copied = false;   // the block is a copy of this function's: pageable, whatever the caller says about ITS memory
+  MatrixSrc src = X;
+  if (X.sparse) {
+    // consecutive columns: the same values / indices behind indptr + cols[0]; else slices of values / indices, column by
+    // column, and a rebuilt indptr -- O(entries of the listed columns)
+    const icikt_csc_input& s = X.s;
+    const size_t es = icikt::host::dtype_bytes(s.dtype), is = icikt::host::index_bytes(s.index_type);
+    if (consecutive) {
+      src.s.indptr = static_cast<const char*>(s.indptr) + (size_t)cols[0] * is;
+    } else {
+      size_t total = 0;
+      for (int64_t j = 0; j < n_cols; ++j) total += (size_t)(icikt::host::csc_ptr(s, cols[j] + 1) - icikt::host::csc_ptr(s, cols[j]));
+      gathered.resize(total * es);
+      gathered_idx.resize(total * is);
+      gathered_ptr.resize((size_t)(n_cols + 1) * is);
+      size_t at = 0;
+      auto put = [&](int64_t j, size_t v) {
+        if (is == 8) reinterpret_cast<int64_t*>(gathered_ptr.data())[j] = (int64_t)v;
+        else reinterpret_cast<int32_t*>(gathered_ptr.data())[j] = (int32_t)v;
+      };
+      for (int64_t j = 0; j < n_cols; ++j) {
+        const int64_t e0 = icikt::host::csc_ptr(s, cols[j]), cnt = icikt::host::csc_ptr(s, cols[j] + 1) - e0;
+        put(j, at);
+        if (cnt > 0) {
+          std::memcpy(gathered.data() + at * es, static_cast<const char*>(s.values) + (size_t)e0 * es, (size_t)cnt * es);
+          std::memcpy(gathered_idx.data() + at * is, static_cast<const char*>(s.indices) + (size_t)e0 * is, (size_t)cnt * is);
+        }
+        at += (size_t)cnt;
+      }
+      put(n_cols, at);
+      src.s.values = gathered.data();
+      src.s.indices = gathered_idx.data();
+      src.s.indptr = gathered_ptr.data();
+      copied = true;
+    }
+  } else {
+  src = MatrixSrc(n > 0 ? icikt::host::view_from_col(X.v, cols[0]) : X.v);
   if (!consecutive && n > 0) {
-    const size_t es = icikt::host::dtype_bytes(X->dtype);
+    const icikt_input* Xv = &X.v;
+    const size_t es = icikt::host::dtype_bytes(Xv->dtype);
     gathered.resize((size_t)n * (size_t)n_cols * es);
-    const char* base = static_cast<const char*>(X->data);
+    const char* base = static_cast<const char*>(Xv->data);
     for (int64_t j = 0; j < n_cols; ++j) {
       char* dstc = gathered.data() + (size_t)j * (size_t)n * es;
-      if (X->order == ICIKT_ORDER_COL) {
-        std::memcpy(dstc, base + (size_t)cols[j] * (size_t)X->ld * es, (size_t)n * es);
+      if (Xv->order == ICIKT_ORDER_COL) {
+        std::memcpy(dstc, base + (size_t)cols[j] * (size_t)Xv->ld * es, (size_t)n * es);
       } else {
         const char* s0 = base + (size_t)cols[j] * es;
-        const size_t step = (size_t)X->ld * es;
+        const size_t step = (size_t)Xv->ld * es;
         if (es == 4) for (int64_t r = 0; r < n; ++r) std::memcpy(dstc + 4 * (size_t)r, s0 + (size_t)r * step, 4);
         else for (int64_t r = 0; r < n; ++r) std::memcpy(dstc + 8 * (size_t)r, s0 + (size_t)r * step, 8);
       }
     }
-    src = icikt_input{gathered.data(), X->dtype, ICIKT_ORDER_COL, n};
+    src = MatrixSrc(icikt_input{gathered.data(), Xv->dtype, ICIKT_ORDER_COL, n});
+    copied = true;
   }
-  const icikt::host::PinnedScope scope(c, gathered.empty() ? flags : (flags & ~ICIKT_FLAG_HOST_PINNED));
+  }
+  const icikt::host::PinnedScope scope(c, copied ? (flags & ~ICIKT_FLAG_HOST_PINNED) : flags);
   icikt_ctx::DiagBufs& db = c->diag;
   std::vector<int32_t> nmiss((size_t)n_cols);
   unsigned long long kept_count = 0;
@@ -305,4 +414,4 @@ int icikt_rank_order_in(icikt_ctx* c, const icikt_input* X, int64_t n_feat, int6
   return icikt::host::end_call(c, "rank_order", gathers());
 }
 
-}  // extern "C"
+}  // namespace

@@ -302,6 +302,16 @@ hipError_t launch_diag_gather(const double* X, int64_t n, const MaskSpec& ms, co
 // ICIKT_DTYPE_* cells in ICIKT_ORDER_* layout with leading dimension src_ld (elements)
 hipError_t launch_ingest(const void* src, int dtype, int order, int64_t src_ld, int64_t n, int64_t nc, double* dst,
                          int64_t dst_ld, hipStream_t s);
+// icikt_sparse.hip: nc columns of the column-major float64 matrix dst from a device block of a CSC matrix's values
+// (ICIKT_DTYPE_*) and row indices (ICIKT_INDEX_*): entry e of the matrix lies at vals[e - base] / idx[e - base], the block
+// holds block_nnz entries, column j's entries are [indptr[col0 + j], indptr[col0 + j + 1]) (indptr on the device); cells
+// without an entry get `fill`.  An entry that is rejected is never stored through; the first rejection of a launch goes
+// to err[0 .. 4): kind (ICIKT_CSC_*; 0 = none, the host clears it), column, position of the entry, row index.
+enum : unsigned long long { ICIKT_CSC_BAD_ROW = 1, ICIKT_CSC_DUPLICATE = 2, ICIKT_CSC_BAD_INDPTR = 3 };
+constexpr int ICIKT_CSC_ERR_WORDS = 4;
+hipError_t launch_scatter_csc(const void* vals, int dtype, const void* idx, const void* indptr, int index_type,
+                              int64_t col0, int64_t base, int64_t block_nnz, double fill, int64_t n, int64_t nc,
+                              double* dst, int64_t dst_ld, unsigned long long* err, hipStream_t s);
 hipError_t launch_selftest(uint32_t* d_out, hipStream_t s);
 hipError_t read_step_stats(unsigned long long* out24, int reset);
 

@@ -88,6 +88,8 @@ struct icikt_ctx {
   int pipe_mode = -1;                      // -1: the library's choice; 0 / 1: off / on whenever possible (debug plan)
   DevBuf<double> d_X, d_out4, d_Xp;  // d_Xp: masked column pairs of icikt_pairs_complete_f64
   DevBuf<unsigned char> d_ingest;    // chunks of a view that is not column-major float64, as uploaded (two halves: MatrixUpload)
+  DevBuf<unsigned char> d_indptr;    // a CSC view's column offsets, uploaded once per call
+  DevBuf<unsigned long long> d_csc_err;   // k_scatter_csc's error record (ICIKT_CSC_ERR_WORDS words)
   // full-matrix entry (icikt_matrix_f64): the exclusion rule the pre-pass applies while it reads the matrix and the
   // optional keep bytes it writes (both only for the duration of that call), the assembled matrices, the reduction
   DevBuf<double> d_out5;
@@ -157,6 +159,10 @@ int check_shape(icikt_ctx* c, const char* who, int64_t n_feat, int64_t n_samp, i
 // the matrix of a host entry as a view: the view itself (null, dtype, order), check_shape with the view's leading
 // dimension (COL: ld >= n_feat; ROW: ld >= n_samp), and null data for a matrix with cells
 int check_view(icikt_ctx* c, const char* who, const icikt_input* X, int64_t n_feat, int64_t n_samp, bool wide_ok = true);
+// the matrix of a host entry as a dense view or a CSC view (MatrixSrc): check_view, or for a CSC view the view itself
+// (null, dtype, index_type), check_shape, indptr (null, indptr[0] < 0, decreasing: O(n_samp)) and null values / indices
+// for a matrix with entries
+int check_src(icikt_ctx* c, const char* who, const MatrixSrc& X, int64_t n_feat, int64_t n_samp, bool wide_ok = true);
 // every index of a host pair list inside [0, n_samp)
 int check_pair_list(icikt_ctx* c, const char* who, const int32_t* pi, const int32_t* pj, int64_t n_pairs, int64_t n_samp);
 // with ICIKT_FLAG_TIMING: an event pair of kernel id k (ICIKT_K_*) around what the caller puts on c->stream in between
@@ -184,21 +190,21 @@ int prepare_launch(icikt_ctx* c, const double* dX, int64_t ld, int64_t col_begin
 enum { kPrepassNone = 0, kPrepassFull = 1, kPrepassMask = 2 };
 // Allocate c->pv for the missing-row bitsets alone (meta; no order / rec / sort scratch).  Leaves the context unprepared.
 int mask_alloc(icikt_ctx* c, int64_t n_feat, int64_t n_samp);
-int upload_and_prepare(icikt_ctx* c, const icikt_input& X, int64_t n_feat, int64_t n_samp, int64_t col_begin,
+int upload_and_prepare(icikt_ctx* c, const MatrixSrc& X, int64_t n_feat, int64_t n_samp, int64_t col_begin,
                        int64_t col_end, uint32_t flags, bool pipelined = false,
                        const std::function<int(size_t, int64_t)>* on_chunk = nullptr,   // pipelined: called per chunk (index, columns arrived)
                        int prepass = kPrepassFull);
 // H2D + pre-pass + pair kernel of the host entries: pipelined by chunks when the matrix has several, else in sequence.
 // Leaves the pair kernel's counts in c->d_raw (raw_valid): the caller runs the epilogue (icikt_run_dev with
 // ICIKT_FLAG_REUSE_COUNTS).
-int upload_prepare_pairs(icikt_ctx* c, const icikt_input& X, int64_t n_feat, int64_t n_samp, uint32_t flags);
+int upload_prepare_pairs(icikt_ctx* c, const MatrixSrc& X, int64_t n_feat, int64_t n_samp, uint32_t flags);
 // global_na values (NaN = NA, +-Inf = Inf, anything else compared with ==) -> the pre-pass's exclusion rule
 int make_mask_spec(icikt_ctx* c, const double* global_na, int n_global_na, icikt::MaskSpec* ms);
 // Build the pair kernel's task list on the host now (prepare_alloc and a pair list must be in place).
 void prebuild_units(icikt_ctx* c);
 // The arguments the pair and matrix entries share, `who` prefixing the message: shape, null matrix, pair list (none: all
 // pairs, *n_pairs set), null output (out5: needed for any column, out4: for any pair), perspective and alternative.
-int check_pair_args(icikt_ctx* c, const char* who, const icikt_input* X, int64_t n_feat, int64_t n_samp,
+int check_pair_args(icikt_ctx* c, const char* who, const MatrixSrc& X, int64_t n_feat, int64_t n_samp,
                     const int32_t* pi, const int32_t* pj, int64_t* n_pairs, const void* out, bool out5,
                     int perspective, int alternative);
 

@@ -604,7 +604,7 @@ int multi_impl(icikt_multi* m, const double* X, int64_t n_feat, int64_t n_samp, 
   }
   // argument checks (the ranks run unchecked): the single-device path's, under the prefix pairs_multi
   const icikt_input xv = icikt::host::f64_view(X, ld);
-  const int rca = icikt::host::check_pair_args(m->ctx[0], "pairs_multi", &xv, n_feat, n_samp, pi, pj, &n_pairs,
+  const int rca = icikt::host::check_pair_args(m->ctx[0], "pairs_multi", icikt::host::MatrixSrc::dense(&xv), n_feat, n_samp, pi, pj, &n_pairs,
                                                mx ? static_cast<const void*>(mx->out5) : out4, mx != nullptr, perspective,
                                                alternative);
   if (rca) return mfail(m, rca, icikt_last_error(m->ctx[0]));

@@ -143,18 +143,34 @@ hipError_t Transfers::init() {
 PinnedScope::PinnedScope(icikt_ctx* ctx, uint32_t flags) : c(ctx) { c->xfer.host_pinned = (flags & ICIKT_FLAG_HOST_PINNED) != 0; }
 PinnedScope::~PinnedScope() { c->xfer.host_pinned = false; }
 
-// a half of the staging buffers for a view that is not column-major float64: the largest chunk in the view's element type
+// a half of the staging buffers for a view that is not column-major float64: the largest chunk in the view's element
+// type; for a CSC view the values and, behind them, the indices of the chunk with the most entries
 static size_t ingest_half(const MatrixUpload& u) {
-  return (((size_t)u.chunk_cols * (size_t)u.n_feat * dtype_bytes(u.v.dtype)) + 255) & ~(size_t)255;
+  if (u.x.sparse) return u.csc_val_cap + ((((size_t)u.csc_max_nnz * index_bytes(u.x.s.index_type)) + 255) & ~(size_t)255);
+  return (((size_t)u.chunk_cols * (size_t)u.n_feat * dtype_bytes(u.x.v.dtype)) + 255) & ~(size_t)255;
 }
 
 hipError_t MatrixUpload::begin(size_t span, hipStream_t also) {
   Transfers& t = c->xfer;
   in_place = span >= kLockMin && t.host_pinned;
   staged = span >= kLockMin && !t.host_pinned;
-  const bool plain = view_is_plain(v);
+  const bool plain = !x.sparse && view_is_plain(x.v);
+  hipError_t e = hipSuccess;
+  if (x.sparse) {
+    // indptr, once (the library's own bounce buffer when it is large: it is not one of the arrays the caller may have
+    // page-locked), and a clear error record; both on c->stream, which the copy stream is made to wait for below
+    csc_val_cap = (((size_t)csc_max_nnz * dtype_bytes(x.s.dtype)) + 255) & ~(size_t)255;
+    const size_t pbytes = (size_t)(n_samp + 1) * index_bytes(x.s.index_type);
+    e = c->d_indptr.reserve(pbytes);
+    if (e == hipSuccess) e = c->d_csc_err.reserve(icikt::ICIKT_CSC_ERR_WORDS);
+    if (e == hipSuccess) e = t.csc_rec.reserve(icikt::ICIKT_CSC_ERR_WORDS * sizeof(unsigned long long));
+    if (e != hipSuccess) return e;
+    if (upload_sync(c, c->d_indptr.p, x.s.indptr, pbytes) != ICIKT_SUCCESS) return hipErrorUnknown;
+    e = hipMemsetAsync(c->d_csc_err.p, 0, icikt::ICIKT_CSC_ERR_WORDS * sizeof(unsigned long long), c->stream);
+    if (e != hipSuccess) return e;
+  }
   const size_t half = plain ? (size_t)chunk_cols * (size_t)n_feat * sizeof(double) : ingest_half(*this);
-  hipError_t e = staged ? t.stage.reserve(2 * half) : hipSuccess;
+  e = staged ? t.stage.reserve(2 * half) : hipSuccess;
   if (e == hipSuccess && !plain) e = c->d_ingest.reserve(2 * half);
   if (e == hipSuccess) e = hipEventRecord(t.ev_copy[0], c->stream);
   if (e == hipSuccess) e = hipStreamWaitEvent(c->copy_stream, t.ev_copy[0], 0);
@@ -162,9 +178,46 @@ hipError_t MatrixUpload::begin(size_t span, hipStream_t also) {
   return e;
 }
 
+// chunk k of a CSC view: the two slices by the route of the upload, then the scatter
+static hipError_t copy_csc(MatrixUpload& u, int k, double* dst, int64_t c0, int64_t nc) {
+  icikt_ctx* c = u.c;
+  Transfers& t = c->xfer;
+  const icikt_csc_input& s = u.x.s;
+  const int64_t e0 = csc_ptr(s, c0), e1 = csc_ptr(s, c0 + nc), cnt = e1 - e0;
+  const size_t es = dtype_bytes(s.dtype), is = index_bytes(s.index_type), half = ingest_half(u);
+  unsigned char* land = c->d_ingest.p + (size_t)(k & 1) * half;
+  hipError_t e = hipSuccess;
+  if (u.staged && k >= 2) e = hipEventSynchronize(t.ev_copy[1 + ((k - 2) % 3)]);  // the copy that last used this half
+  if (e != hipSuccess) return e;
+  if (cnt > 0) {
+    const char* sv = static_cast<const char*>(s.values) + (size_t)e0 * es;
+    const char* si = static_cast<const char*>(s.indices) + (size_t)e0 * is;
+    if (u.staged) {
+      char* stage = static_cast<char*>(t.stage.p) + (size_t)(k & 1) * half;
+      par_memcpy(t, stage, sv, (size_t)cnt * es);
+      par_memcpy(t, stage + u.csc_val_cap, si, (size_t)cnt * is);
+      sv = stage;
+      si = stage + u.csc_val_cap;
+    }
+    e = hipMemcpyAsync(land, sv, (size_t)cnt * es, hipMemcpyHostToDevice, c->copy_stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(land + u.csc_val_cap, si, (size_t)cnt * is, hipMemcpyHostToDevice, c->copy_stream);
+  }
+  if (e == hipSuccess)
+    e = icikt::launch_scatter_csc(land, s.dtype, land + u.csc_val_cap, c->d_indptr.p, s.index_type, c0, e0, cnt, s.fill,
+                                  u.n_feat, nc, dst, u.n_feat, c->d_csc_err.p, c->copy_stream);
+  return e;
+}
+
 hipError_t MatrixUpload::copy(int k, double* dst, int64_t c0, int64_t nc, hipEvent_t* done) {
   Transfers& t = c->xfer;
   hipError_t e = hipSuccess;
+  if (x.sparse) {
+    e = copy_csc(*this, k, dst, c0, nc);
+    *done = t.ev_copy[1 + (k % 3)];
+    if (e == hipSuccess) e = hipEventRecord(*done, c->copy_stream);
+    return e;
+  }
+  const icikt_input& v = x.v;
   const bool plain = view_is_plain(v), row = v.order == ICIKT_ORDER_ROW;
   const size_t es = dtype_bytes(v.dtype);
   // the chunk in the caller's memory: `runs` runs of run_bytes, ld_bytes apart (COL: a run is a column; ROW: a run is
@@ -189,6 +242,35 @@ hipError_t MatrixUpload::copy(int k, double* dst, int64_t c0, int64_t nc, hipEve
   *done = t.ev_copy[1 + (k % 3)];
   if (e == hipSuccess) e = hipEventRecord(*done, c->copy_stream);
   return e;
+}
+
+hipError_t MatrixUpload::finish() {
+  Transfers& t = c->xfer;
+  if (!x.sparse) { t.csc_pending = false; return hipSuccess; }
+  t.csc_pending = true;
+  return hipMemcpyAsync(t.csc_rec.p, c->d_csc_err.p, icikt::ICIKT_CSC_ERR_WORDS * sizeof(unsigned long long),
+                        hipMemcpyDeviceToHost, c->copy_stream);
+}
+
+std::string csc_message(const unsigned long long* rec) {
+  const std::string at = " (column " + std::to_string((long long)rec[1]) + ", entry " + std::to_string((long long)rec[2]) + ")";
+  switch (rec[0]) {
+    case icikt::ICIKT_CSC_BAD_ROW:
+      return "X->indices: row index " + std::to_string((long long)rec[3]) + " outside [0, n_feat)" + at;
+    case icikt::ICIKT_CSC_DUPLICATE:
+      return "X->indices: duplicate entry (sum_duplicates) for row " + std::to_string((long long)rec[3]) + at;
+    default:
+      return "X->indptr: a column's offsets lie outside the arrays" + at;
+  }
+}
+
+int csc_verdict(icikt_ctx* c) {
+  Transfers& t = c->xfer;
+  if (!t.csc_pending) return ICIKT_SUCCESS;
+  t.csc_pending = false;
+  const unsigned long long* rec = static_cast<const unsigned long long*>(t.csc_rec.p);
+  if (!rec || rec[0] == 0) return ICIKT_SUCCESS;
+  return fail(c, ICIKT_E_INVALID, "sparse matrix: " + csc_message(rec));
 }
 
 int upload_sync(icikt_ctx* c, void* dst, const void* src, size_t bytes) {
@@ -263,7 +345,14 @@ hipError_t finish_stream(icikt_ctx* c, bool ok) {
 int end_call(icikt_ctx* c, const char* who, int rc) {
   const hipError_t es = finish_stream(c, rc == ICIKT_SUCCESS);
   (void)hipStreamSynchronize(c->prep_stream);   // (a pipelined upload from page-locked memory is not waited for before)
-  (void)hipStreamSynchronize(c->copy_stream);
+  const hipError_t ec = hipStreamSynchronize(c->copy_stream);
+  // a CSC upload whose error record is still unread (a pipelined upload from page-locked arrays): malformed input fails
+  // the call now that its streams have drained
+  if (c->xfer.csc_pending) {
+    if (ec != hipSuccess || rc) c->xfer.csc_pending = false;   // (a call that has failed already keeps its own message)
+    const int rv = csc_verdict(c);
+    if (rv) return rv;
+  }
   if (rc || es == hipSuccess) return rc;
   return fail(c, ICIKT_E_HIP, std::string(who) + ": " + hipGetErrorString(es));
 }

@@ -21,6 +21,7 @@
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
+#include <string>
 #include <vector>
 
 #include "icikt.h"
@@ -59,6 +60,8 @@ struct Transfers {
   std::vector<hipEvent_t> ev_out;   // events of the pieces in flight (a pool, reused from call to call)
   size_t ev_out_used = 0;
   bool host_pinned = false;         // the current call was made with ICIKT_FLAG_HOST_PINNED (PinnedScope)
+  PinnedBuf csc_rec;                // a CSC upload's error record as the copy stream delivered it (ICIKT_CSC_ERR_WORDS words)
+  bool csc_pending = false;         // ... and whether one is on its way / unread
   ~Transfers();
   hipError_t init();                // creates ev_copy
 };
@@ -83,10 +86,32 @@ struct PinnedScope {
 // type and order -- the same three routes, a strided copy of `rows` runs each -- into a device staging block of two
 // halves (icikt_ctx::d_ingest), and k_ingest (icikt_ingest.hip) widens / transposes it into the device matrix on the
 // copy stream, right behind its copy: stream order is what keeps a half from being overwritten before it has been read.
+// A CSC view (icikt_csc_input) keeps the chunks -- ranges of columns, sized by the float64 matrix
+// they become -- and the three routes; what travels for columns [c0, c0 + nc) is values[e0:e1] and indices[e0:e1],
+// e0 = indptr[c0], e1 = indptr[c0 + nc], into a half of the same device staging block (values first, indices behind
+// them at csc_val_cap), and k_scatter_csc (icikt_sparse.hip) writes the chunk's float64 columns behind the two copies.
+// indptr is uploaded once, by begin(); the halves are sized by the chunk with the most entries (csc_max_nnz).
+struct MatrixSrc {
+  bool sparse = false, null = false;         // null: the caller passed no view at all (the entry checks say so)
+  icikt_input v{};                           // dense: element type, order, leading dimension in elements
+  icikt_csc_input s{};                       // sparse
+  MatrixSrc() = default;
+  MatrixSrc(const icikt_input& d) : v(d) {}  // (a dense view converts: the callers that only know dense matrices)
+  static MatrixSrc dense(const icikt_input* p) { MatrixSrc m; if (p) m.v = *p; else m.null = true; return m; }
+  static MatrixSrc csc(const icikt_csc_input* p) { MatrixSrc m; m.sparse = true; if (p) m.s = *p; else m.null = true; return m; }
+};
+inline size_t index_bytes(int index_type) { return index_type == ICIKT_INDEX_I64 ? 8 : 4; }
+// indptr[i] of a CSC view
+inline int64_t csc_ptr(const icikt_csc_input& s, int64_t i) {
+  return s.index_type == ICIKT_INDEX_I64 ? static_cast<const int64_t*>(s.indptr)[i] : (int64_t)static_cast<const int32_t*>(s.indptr)[i];
+}
+
 struct MatrixUpload {
   icikt_ctx* c;
-  icikt_input v;                             // the caller's matrix (element type, order, leading dimension in elements)
+  MatrixSrc x;                               // the caller's matrix
   int64_t n_feat, chunk_cols;                // rows of a column, columns of the largest chunk
+  int64_t n_samp = 0, csc_max_nnz = 0;       // CSC: columns of the view (indptr holds n_samp + 1 offsets), entries of the fullest chunk
+  size_t csc_val_cap = 0;                    // CSC: bytes of a staging half that hold values (the indices follow)
   bool staged = false, in_place = false;     // the route (in place: copies may still read the caller's matrix after the host went on)
   // picks the route for a span of `span` bytes, grows the staging buffers, and makes c->copy_stream (and `also`, when
   // not null) wait for the work already on c->stream: it may still read the device copy the chunks overwrite
@@ -95,7 +120,15 @@ struct MatrixUpload {
   // dimension n_feat; *done is recorded behind the copy and, for a view that is not column-major float64, behind the
   // conversion (k_ingest) that follows it on the copy stream
   hipError_t copy(int k, double* dst, int64_t c0, int64_t nc, hipEvent_t* done);
+  // CSC: the error record's way back, on the copy stream behind the last chunk (csc_verdict reads it once that stream
+  // has been synchronised)
+  hipError_t finish();
 };
+// After c->copy_stream has been synchronised: ICIKT_SUCCESS, or ICIKT_E_INVALID with the message of the entry the scatter
+// kernel rejected during the upload the context made last (nothing to report when that upload was dense).
+int csc_verdict(icikt_ctx* c);
+// the message of an error record of k_scatter_csc (kind != 0)
+std::string csc_message(const unsigned long long* rec);
 
 inline size_t dtype_bytes(int dtype) { return dtype == ICIKT_DTYPE_F32 || dtype == ICIKT_DTYPE_I32 ? 4 : 8; }
 inline bool view_is_plain(const icikt_input& v) { return v.dtype == ICIKT_DTYPE_F64 && v.order == ICIKT_ORDER_COL; }

@@ -131,6 +131,33 @@ typedef struct icikt_ctx icikt_ctx;
 #define ICIKT_ORDER_ROW 1   /* element (r, c) at data[r*ld + c], ld >= n_samp                            */
 typedef struct { const void *data; int dtype; int order; int64_t ld; } icikt_input;
 
+/* The caller's matrix as the *_csc host entries read it: compressed-sparse-column, columns = samples as everywhere
+ * (scipy.sparse.csc_matrix's data / indices / indptr; R's dgCMatrix x / i / p; the transpose of a cells x genes CSR
+ * matrix).  An entry given a view V returns what its _f64 twin returns on the dense column-major float64 matrix M with
+ *   M[r, c] = (double)values[k]   if column c has an entry k (indptr[c] <= k < indptr[c + 1]) with indices[k] == r,
+ *   M[r, c] = fill                otherwise.
+ * The conversion is icikt_input's, (double)v; a float64 cell and `fill` travel as 64 bits (NA_real_ stays NA_real_, -0.0
+ * stays -0.0).  Explicitly stored zeros and NaNs are ordinary entries; the indices of a column may come in any order.
+ * global_na is applied afterwards, in float64, by the pre-pass, as for a dense matrix -- with the default global_na
+ * (NA, Inf, 0) and fill = 0 a CSC matrix is "the non-missing values, column by column".  M exists on the device only:
+ * what crosses PCIe is values, indices and indptr, and a kernel (icikt_scatter_csc_dev's) writes M there.
+ * Malformed input is an argument error (ICIKT_E_INVALID, the message names the argument, the context stays usable),
+ * never a device fault.  Checked on the host before the first copy: a null view, null arrays with entries, an unknown
+ * dtype or index_type, indptr[0] < 0, indptr decreasing.  Checked on the device, since the host never scans the
+ * entries: a row index outside [0, n_feat), and two entries of one column with the same row ("duplicate entry
+ * (sum_duplicates)": scipy would sum them, the library refuses).  The kernel stores nothing through an entry it
+ * rejects and records one of them (which one is unspecified); the call fails once its stream has drained, and the
+ * caller's result arrays may then hold partial results, as after any failed call. */
+#define ICIKT_INDEX_I32 0
+#define ICIKT_INDEX_I64 1
+typedef struct {
+  const void *values;   /* nnz cells of `dtype` (ICIKT_DTYPE_F64 / F32 / I32 / I64) */
+  const void *indices;  /* nnz row (feature) indices of `index_type`, each in [0, n_feat) */
+  const void *indptr;   /* n_samp + 1 offsets of `index_type`: column c's entries are [indptr[c], indptr[c+1]) */
+  int dtype, index_type;
+  double fill;          /* every cell without an entry holds this value, bit for bit (0.0 = scipy's toarray) */
+} icikt_csc_input;
+
 int icikt_version(void);
 /* Number of visible HIP devices (0 and ICIKT_E_NO_DEVICE when none). */
 int icikt_device_count(int *count);
@@ -401,6 +428,42 @@ int icikt_rank_order_in(icikt_ctx *ctx, const icikt_input *X, int64_t n_feat, in
  * for a matrix that is on the device already (a torch tensor's data_ptr()).  The two blocks must not overlap. */
 int icikt_convert_dev(icikt_ctx *ctx, const void *d_src, int dtype, int order, int64_t n_feat, int64_t n_samp,
                       int64_t ld, double *d_dst, int64_t dst_ld);
+
+/* ---- the host entries on a compressed-sparse-column view (icikt_csc_input above) ----------------------------------
+ *
+ * Each takes `const icikt_csc_input *X, n_feat, n_samp` where its _in twin takes `const icikt_input *X, n_feat, n_samp`;
+ * every other argument, every output and the error contract are the twin's, plus the argument errors of a malformed
+ * view.  The chunks, the pre-pass and the pair-kernel launches are the ones the dense float64 matrix would run; only
+ * values[e0:e1] and indices[e0:e1] of a chunk's columns cross PCIe (8 d n S + 4 (S + 1) bytes for float32 values and
+ * int32 indices at density d, where the dense float32 matrix moves 4 n S).  ICIKT_FLAG_HOST_PINNED keeps its meaning: the
+ * caller has page-locked `values`, `indices` and the result arrays; indptr is read by the host and copied once.
+ * icikt_rank_order_csc: consecutive columns are read in place; any other column list is gathered on the host as slices
+ * of values / indices plus a rebuilt indptr, O(entries of the listed columns). */
+int icikt_pairs_csc(icikt_ctx *ctx, const icikt_csc_input *X, int64_t n_feat, int64_t n_samp, const int32_t *pi,
+                    const int32_t *pj, int64_t n_pairs, int perspective, int alternative, int continuity, uint32_t flags,
+                    double *out4, int64_t *counts, int32_t *reasons);
+int icikt_matrix_csc(icikt_ctx *ctx, const icikt_csc_input *X, int64_t n_feat, int64_t n_samp, const double *global_na,
+                     int n_global_na, const int32_t *pi, const int32_t *pj, int64_t n_pairs, int perspective,
+                     int alternative, int continuity, uint32_t flags, int scale_max, int diag_good, double *out5,
+                     uint8_t *keep, int64_t *reason_counts);
+int icikt_missingness_csc(icikt_ctx *ctx, const icikt_csc_input *X, int64_t n_feat, int64_t n_samp, const int32_t *pi,
+                          const int32_t *pj, int64_t n_pairs, int64_t *missingness);
+int icikt_col_medians_csc(icikt_ctx *ctx, const icikt_csc_input *X, int64_t n_feat, int64_t n_samp,
+                          const double *global_na, int n_global_na, int na_rm, uint32_t flags, double *medians);
+int icikt_censor_counts_csc(icikt_ctx *ctx, const icikt_csc_input *X, int64_t n_feat, int64_t n_samp,
+                            const double *global_na, int n_global_na, const int32_t *cls, int n_class, uint32_t flags,
+                            int64_t *trials, int64_t *success, int64_t *n_excluded, double *medians);
+int icikt_rank_order_csc(icikt_ctx *ctx, const icikt_csc_input *X, int64_t n_feat, int64_t n_samp,
+                         const double *global_na, int n_global_na, const int32_t *cols, int64_t n_cols, uint32_t flags,
+                         int64_t *n_kept, int32_t *n_na, double *median_rank, int32_t *row_order, int32_t *col_order,
+                         double *original, double *ordered);
+/* The scatter alone, for arrays that are on the device already (the counterpart of icikt_convert_dev): d_values,
+ * d_indices and d_indptr are DEVICE arrays of a CSC matrix as in icikt_csc_input; d_dst receives the column-major
+ * float64 matrix with leading dimension dst_ld >= n_feat (rows [n_feat, dst_ld) of d_dst are left as they are).
+ * Unlike icikt_convert_dev it RETURNS AFTER THE CONTEXT'S STREAM HAS BEEN SYNCHRONISED, so that it can report malformed
+ * input: indptr is read back and checked as the host entries check it, the entries are checked by the kernel. */
+int icikt_scatter_csc_dev(icikt_ctx *ctx, const void *d_values, const void *d_indices, const void *d_indptr, int dtype,
+                          int index_type, double fill, int64_t n_feat, int64_t n_samp, double *d_dst, int64_t dst_ld);
 
 /* Device self-test of the wavefront primitives the pair kernel relies on (DPP scan / shift). */
 int icikt_selftest(icikt_ctx *ctx);
