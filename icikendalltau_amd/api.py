@@ -689,7 +689,8 @@ def kt_fast(x, y=None, use="everything", alternative="two.sided", continuity=Fal
     dropped.  The last one runs on the GPU as ici_kt(..., perspective = "local") of the two vectors with both
     entries of such rows set missing -- identical to dropping the rows, since "local" removes rows missing in
     both (src/kendallc.cpp:180-185) and nothing missing remains; the HIP engine masks, sorts and counts every
-    pair on the device (icikt_pairs_complete_f64), other engines get the masked vectors from the host.
+    pair on the device (icikt_pairs_complete_f64), other engines get the masked vectors from the host -- as does the
+    HIP engine for columns of more than 65 535 rows, which that entry does not take.
     """
     if _lib.is_sparse(x):   # zero is a value here, not a missing cell: the dense matrix is what is meant
         x = _densify(x)
@@ -725,8 +726,10 @@ def kt_fast(x, y=None, use="everything", alternative="two.sided", continuity=Fal
             X = np.asarray(X, dtype=np.float64)[keep]
     if do_computation:
         t1 = time.perf_counter()
-        if na_method == "pairwise.complete.obs" and np.isnan(X).any() and hasattr(eng, "pairs_complete"):
-            # masking, per-pair sorts and counting on the device (icikt_pairs_complete_in)
+        if na_method == "pairwise.complete.obs" and np.isnan(X).any() and hasattr(eng, "pairs_complete") and \
+                X.shape[0] <= _lib.MAX_FEATURES:
+            # masking, per-pair sorts and counting on the device (icikt_pairs_complete_in: no path for wide columns,
+            # which take the host-masked loop below through eng.pairs)
             out, rsn = eng.pairs_complete(_for_engine(X, eng), pi, pj)
             for r in rsn[rsn > 1]:
                 _warn_reason(r)

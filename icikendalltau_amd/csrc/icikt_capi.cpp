@@ -1582,7 +1582,15 @@ int icikt_pairs_complete_in(icikt_ctx* c, const icikt_input* X, int64_t n_feat, 
     }
     return ICIKT_SUCCESS;
   };
-  return icikt::host::end_call(c, "pairs_complete", body());
+  const int rb = body();
+  // the prepared matrix and the pair list are the last chunk's scratch columns and its (2k, 2k+1): nothing of the caller's.
+  // The device-resident calls start over (icikt_run_dev: ICIKT_E_STATE until icikt_prepare_dev and a pair list)
+  c->prepared = false;
+  c->raw_valid = false;
+  c->n_pairs = -1;
+  c->pairs_nsamp = -1;
+  c->wpb = 0;
+  return icikt::host::end_call(c, "pairs_complete", rb);
 }
 
 int icikt_pair_f64(icikt_ctx* c, const double* x, const double* y, int64_t n, int perspective, int alternative,

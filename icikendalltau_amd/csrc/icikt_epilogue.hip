@@ -241,15 +241,16 @@ k_missingness(PrepView pv, const int32_t* __restrict__ pi, const int32_t* __rest
 // ------------------------------------------------------------------------------------------------
 __global__ void __launch_bounds__(256)
 k_mask_pairs(const double* __restrict__ X, int64_t ld, int n, const int32_t* __restrict__ pi,
-             const int32_t* __restrict__ pj, int64_t first, double* __restrict__ Xp) {
-  const int64_t p = blockIdx.y;   // pair of the chunk
+             const int32_t* __restrict__ pj, int64_t first, int64_t npairs, double* __restrict__ Xp) {
   const int i = (int)(blockIdx.x * blockDim.x + threadIdx.x);
   if (i >= n) return;
-  const double a = X[(int64_t)pi[first + p] * ld + i], b = X[(int64_t)pj[first + p] * ld + i];
-  const bool drop = (a != a) || (b != b);
   const double na = __longlong_as_double(0x7FF8000000000000ll);
-  Xp[(2 * p) * (int64_t)n + i] = drop ? na : a;
-  Xp[(2 * p + 1) * (int64_t)n + i] = drop ? na : b;
+  for (int64_t p = blockIdx.y; p < npairs; p += gridDim.y) {   // pair of the chunk (the y-grid is capped: launch_mask_pairs)
+    const double a = X[(int64_t)pi[first + p] * ld + i], b = X[(int64_t)pj[first + p] * ld + i];
+    const bool drop = (a != a) || (b != b);
+    Xp[(2 * p) * (int64_t)n + i] = drop ? na : a;
+    Xp[(2 * p + 1) * (int64_t)n + i] = drop ? na : b;
+  }
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -430,8 +431,9 @@ hipError_t launch_mask_pairs(const double* dX, int64_t ld, int n, const int32_t*
                              int64_t npairs, double* dXp, hipStream_t s) {
   if (npairs <= 0 || n <= 0) return hipSuccess;
   (void)hipGetLastError();
-  hipLaunchKernelGGL(k_mask_pairs, dim3((unsigned)((n + 255) / 256), (unsigned)npairs), dim3(256), 0, s, dX, ld, n, pi,
-                     pj, first, dXp);
+  // a chunk holds up to (3 << 29) / (16 n) pairs, millions on short columns: past the y-grid's 65 535 blocks the kernel strides
+  hipLaunchKernelGGL(k_mask_pairs, dim3((unsigned)((n + 255) / 256), (unsigned)std::min<int64_t>(npairs, 65535)), dim3(256), 0, s,
+                     dX, ld, n, pi, pj, first, npairs, dXp);
   return hipGetLastError();
 }
 

@@ -332,7 +332,11 @@ int icikt_multi_debug_set_plan(icikt_multi *m, const char *spec);
 
 /* kt_fast(use = "pairwise.complete.obs") (R/kendalltau.R:310-354, 448-545): for every pair the rows with a missing
  * value in EITHER vector are dropped, then ici_kt(..., perspective = "local") of what remains.  The masking, the
- * per-pair sorts and the counting all run on the device (pairs in chunks); same outputs as icikt_pairs_f64. */
+ * per-pair sorts and the counting all run on the device (pairs in chunks); same outputs as icikt_pairs_f64.
+ * The call uses the context's prepared matrix and pair list for its own masked columns and leaves NEITHER behind,
+ * whether it succeeds or fails: afterwards icikt_run_dev, icikt_expand_cols_dev and icikt_prep_arrays answer
+ * ICIKT_E_STATE and icikt_num_pairs -1 until icikt_prepare_dev and icikt_set_pairs have been called again.  (A call
+ * refused at its argument checks touches nothing.) */
 int icikt_pairs_complete_f64(icikt_ctx *ctx, const double *X, int64_t n_feat, int64_t n_samp, int64_t ld,
                              const int32_t *pi, const int32_t *pj, int64_t n_pairs, int alternative,
                              int continuity, uint32_t flags, double *out4, int64_t *counts, int32_t *reasons);

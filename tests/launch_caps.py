@@ -7,7 +7,9 @@ per-block scratch and scan carries of the round before.  Keep these formulas in 
 - cor_prep_blocks:     icikt_capi_cor.cpp, icikt_cor_pairs_f64()  prep_blocks (k_cor_prep, 12 bytes per padded row)
 - spearman_pw_blocks:  icikt_capi_cor.cpp, icikt_cor_pairs_f64()  pw_blocks (k_cor_spearman_pw, 2 n + 1 int32 per block)
 - cor_dots_waves:      icikt_cor.hip, launch_cor_dots()       (k_cor_dots, 4 waves per block, at most 65 536 blocks)
-- gather_y_blocks:     icikt_diag.hip, launch_diag_gather()   (k_diag_gather, y-grid)"""
+- gather_y_blocks:     icikt_diag.hip, launch_diag_gather()   (k_diag_gather, y-grid)
+- complete_chunk:      icikt_capi.cpp, icikt_pairs_complete_in()  chunk (pairs per chunk: 1.5 GiB of masked columns)
+- mask_pairs_y_blocks: icikt_epilogue.hip, launch_mask_pairs()    (k_mask_pairs, y-grid: one y-block per pair of the chunk)"""
 import numpy as np
 from scipy import special, stats
 
@@ -39,6 +41,14 @@ def cor_dots_waves(P):
 
 def gather_y_blocks(n_cols):
     return min(n_cols, 65535)
+
+
+def complete_chunk(n):
+    return max(1, (3 << 29) // max(16 * n, 16))
+
+
+def mask_pairs_y_blocks(m):
+    return min(m, 65535)
 
 
 # ---- vectorised cor_fast references (pair batches) -------------------------------------------------------------------

@@ -11,12 +11,19 @@ from oracle import oracle as O
 class OracleEngine:
     name = "oracle"
 
+    def __init__(self, int32_compat=True):
+        """int32_compat: the reference's 32-bit tie sums, which wrap beyond 46 342 rows (what the library reproduces up to
+        65 535 rows without FLAG_EXACT_INT64); False: exact sums, as the library's wide-column path computes them."""
+        self.int32_compat = bool(int32_compat)
+
     def pairs(self, X, pi, pj, perspective, alternative, continuity):
-        out, _cnt, rsn = O.ici_pairs(X, pi, pj, perspective, alternative, continuity, want_counts=False)
+        out, _cnt, rsn = O.ici_pairs(X, pi, pj, perspective, alternative, continuity, int32_compat=self.int32_compat,
+                                     want_counts=False)
         return out, rsn
 
     def pairs_counts(self, X, pi, pj, perspective, alternative, continuity):
-        out, cnt, rsn = O.ici_pairs(X, pi, pj, perspective, alternative, continuity, want_counts=True)
+        out, cnt, rsn = O.ici_pairs(X, pi, pj, perspective, alternative, continuity, int32_compat=self.int32_compat,
+                                    want_counts=True)
         names = ("n", "missing", "dis", "ntie", "xtie", "ytie", "x0", "x1", "y0", "y1", "tot")
         return out, rsn, {k: cnt[:, i] for i, k in enumerate(names)}
 

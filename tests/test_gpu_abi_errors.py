@@ -118,6 +118,23 @@ def test_every_entry_refuses_bad_arguments(hip_ctx):
         assert L.icikt_run_dev(hf, 1, 0, 0, 0, dout.data_ptr(), None, None) == 0 and L.icikt_sync(hf) == 0
         ref, _c, _r = hip_ctx.pairs(X, pi, pj, "global", want_counts=False)
         assert np.array_equal(dout.cpu().numpy()[:3], ref, equal_nan=True)
+        # icikt_pairs_complete_f64 prepares its own masked columns with their own pair list and leaves neither behind:
+        # the device-resident calls start over instead of running on the last chunk's scratch pairs
+        oc = np.full((P, 4), 7.0)
+        assert L.icikt_pairs_complete_f64(hf, _p(X), n, S, n, _p(pi), _p(pj), P, 0, 0, 0, _p(oc), None, None) == 0
+        assert not np.any(oc == 7.0) and L.icikt_num_pairs(hf) == -1
+        dout.fill_(7.0)
+        for who, rc in (("run after pairs_complete", L.icikt_run_dev(hf, 1, 0, 0, 0, dout.data_ptr(), None, None)),
+                        ("expand after pairs_complete", L.icikt_expand_cols_dev(hf, 0, 2, 0)),
+                        ("prep_arrays after pairs_complete", L.icikt_prep_arrays(hf, ptrs, bpc))):
+            refused_f(rc, who)
+            assert rc == -5, (who, rc)                                         # ICIKT_E_STATE
+        assert L.icikt_sync(hf) == 0 and torch.all(dout == 7.0)
+        assert L.icikt_prepare_dev(hf, dX.data_ptr(), n, S, n, 0) == 0
+        refused_f(L.icikt_run_dev(hf, 1, 0, 0, 0, dout.data_ptr(), None, None), "run without pairs after pairs_complete")
+        assert L.icikt_set_pairs(hf, _p(pi), _p(pj), 3) == 0
+        assert L.icikt_run_dev(hf, 1, 0, 0, 0, dout.data_ptr(), None, None) == 0 and L.icikt_sync(hf) == 0
+        assert np.array_equal(dout.cpu().numpy()[:3], ref, equal_nan=True)
     finally:
         fresh.close()
     # ---- null handles ----------------------------------------------------------------------------------------------
