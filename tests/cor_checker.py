@@ -1,8 +1,10 @@
 """CPU checker of cor_fast (test infrastructure only): estimates from scipy's pearsonr / spearmanr, p-values from the
 regularized incomplete beta (scipy's betainc, mpmath's at 50 digits in the spot checks), Spearman's exact p-value by
-enumerating permutations.  Two pieces have no independent implementation here and no R to compare with: the AS 89
-Edgeworth series (10 <= n < 1290, no ties) and Spearman's continuity correction -- for those the checker takes the
-front end's own restatement (icikendalltau_amd.api), as DESIGN.md section 9 says.
+enumerating permutations.  Two pieces have no independent implementation in this module and no R to compare with:
+the AS 89 Edgeworth series (10 <= n < 1290, no ties) and Spearman's continuity correction -- for those the checker
+takes the front end's own restatement (icikendalltau_amd.api).  The series itself is pinned elsewhere, as DESIGN.md
+section 9 says: tests/spearman_exact.py holds ``api._prho`` and the device to the exact permutation distribution at
+n = 10 .. 16 within AS 89's own error, and to the t tail at n = 1289; the continuity correction stays unpinned.
 
 For ill-conditioned data (large offsets, extreme scales, a pair's rows far from its column's mean) scipy is no
 reference: ``exact_pearson`` is, Pearson's rho of the given doubles in exact integer arithmetic, rounded once."""
@@ -84,7 +86,7 @@ def spearman_pvalue(rho, n, alternative, continuity, ties):
                     return 0.0 if lower else 1.0
                 up, fact = exact_upper(n, is_)
                 return (fact - up) / fact if lower else up / fact
-            return api._prho(round(q) + 2 * lower, n, lower)          # Edgeworth: unpinned restatement
+            return api._prho(round(q) + 2 * lower, n, lower)          # Edgeworth: pinned in tests/spearman_exact.py
         r = 1 - q / den
         if continuity and r != 0:
             r -= math.copysign(1.0, r) / den                          # unpinned restatement

@@ -151,6 +151,51 @@ def main():
         "completeness": [0.9, 0.8, 1 - 1 / 9, 0.8],
     }
 
+    # -- the vignette's 3-column matrix: vignettes/ici-kendalltau.Rmd:146-156, docs/articles/ici-kendalltau.html
+    #    (the only published answer with max(taumax) < 1 through scale_max and a diagonal below 1)
+    r = RRandom(1234)
+    v1 = np.sort(r.rnorm(1000, 100, 10))
+    v2 = v1 + 10
+    v2[r.sample(1000, 100) - 1] = v1[:100]
+    v3 = v1.copy()
+    v3[np.concatenate([np.arange(10), r.sample(1000, 5) - 1])] = np.nan
+    np.savez_compressed(os.path.join(HERE, "vignette_s1_s3.npz"), s1=v1, s2=v2, s3=v3)
+    expected["vignette"] = {
+        "source": "vignettes/ici-kendalltau.Rmd:146-156; docs/articles/ici-kendalltau.html:385-387,417-422",
+        "r_code": "set.seed(1234); s1 = sort(rnorm(1000, 100, 10)); s2 = s1 + 10; s2[sample(1000, 100)] = s1[1:100]; "
+                  "s3 = s1; s3[c(1:10, sample(1000, 5))] = NA; ici_kendalltau(cbind(s1, s2, s3))",
+        "cor": {"s1-s2": 0.8049209, "s1-s3": 0.9907488, "s2-s3": 0.7956652},
+        "cor_diag": {"s1": 1.0, "s2": 1.0, "s3": 0.985},
+        "rows": [{"s1": "s1", "s2": "s2", "raw": 0.8049209, "taumax": 1.0, "completeness": 1.0, "cor": 0.8049209},
+                 {"s1": "s1", "s2": "s3", "raw": 0.9907488, "taumax": 0.9998949, "completeness": 0.985,
+                  "cor": 0.9907488},
+                 {"s1": "s2", "s2": "s3", "raw": 0.7956652, "taumax": 0.9998949, "completeness": 0.985,
+                  "cor": 0.7956652},
+                 {"s1": "s3", "s2": "s3", "raw": 0.985, "cor": 0.985}],
+        "abs_tol": 5e-8,
+    }
+
+    # -- README.md:203-213: kt_fast(x, y) of the x, y drawn after the README's s1 .. s4 (no fixture: the tests draw
+    #    them with oracle/rrng.py, as for the README's cor_fast answer)
+    expected["readme_kt_fast"] = {
+        "source": "README.md:203-213",
+        "r_code": "set.seed(1234); rnorm(1000, 100, 10); sample(100, 50); sample(100, 50); x = rnorm(1000); "
+                  "y = rnorm(1000); kt_fast(x, y)",
+        "tau": -0.003411411, "tau_abs_tol": 5e-10, "pvalue": 0.8716723, "pvalue_abs_tol": 5e-8,
+    }
+
+    # -- docs/reference/ici_kt.html:104-116: x = sort(rnorm(100)); y = x + 1; y2 = y; y2[1:10] = NA.  The answers
+    #    depend on the order of x alone, so any strictly increasing x gives them
+    expected["ici_kt_help"] = {
+        "source": "docs/reference/ici_kt.html:104-116",
+        "r_code": "x = sort(rnorm(100)); y = x + 1; y2 = y; y2[1:10] = NA; ici_kt(x, y); ici_kt(x, y2, 'global'); "
+                  "ici_kt(x, y2)",
+        "x_y": [1.0, 3.480281e-49, 1.0, 1.0],
+        "x_y2_global": [0.9954442, 2.228308e-48, 0.9954442, 0.9],
+        "x_y2_local": [0.9954442, 2.228308e-48, 0.9954442, 0.9],
+        "pvalue_rel_tol": 5e-7, "abs_tol": 5e-8,
+    }
+
     # -- yeast (BASELINE config c2 input; no golden outputs exist in the reference)
     if os.path.isdir(REF):
         Xy, rn, cn = yeast()

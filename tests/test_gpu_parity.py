@@ -315,6 +315,24 @@ def test_api_through_hip_engine(hip_ctx, golden_dir, expected):
         api.ici_kt(np.arange(10.0), np.ones(10))
 
 
+def test_published_answers_through_hip_engine(hip_ctx, golden_dir, expected):
+    """The vignette's 3-column matrix in both return forms (the matrix form assembles on the device,
+    icikt_matrix_f64), the README's kt_fast(x, y) and the ici_kt help page, on the MI355X."""
+    from icikendalltau_amd import api
+    from tests import published_answers as PA
+    M = PA.vignette_matrix(golden_dir)
+    names = ["s1", "s2", "s3"]
+    PA.check_vignette(api.ici_kendalltau(M, colnames=names),
+                      api.ici_kendalltau(M, colnames=names, return_matrix=False), expected["vignette"])
+    x, y = PA.readme_kt_fast_xy()
+    PA.check_readme_kt_fast(api.kt_fast(x, y), expected["readme_kt_fast"])
+    e = expected["ici_kt_help"]
+    for x, y, perspective, want in PA.ici_kt_help_cases(e):
+        out, _cnt, rsn = hip_ctx.pair(x, y, perspective)
+        assert rsn == 0
+        PA.check_ici_kt_help(out, want, e)
+
+
 def test_c5_shape_include_only_subset(hip_ctx):
     """Config c5's shape at a column count the oracle finishes in seconds: n = 50 000, 1 000 smallest values per
     column missing, include_only = the first four names (vector form: every pair with one of them),

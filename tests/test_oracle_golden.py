@@ -12,6 +12,8 @@ from scipy import stats
 
 from oracle import oracle as O
 from oracle.rrng import RRandom
+from tests.published_answers import (check_ici_kt_help, check_readme_kt_fast, check_vignette, ici_kt_help_cases,
+                                     readme_kt_fast_xy, vignette_matrix)
 
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
 
@@ -200,3 +202,27 @@ def test_local_derivation_identities():
         cb = int((np.isnan(x) & np.isnan(y)).sum())
         assert cl["dis"] == cg["dis"] and cl["n"] == cg["n"] - cb
         assert cl["ntie"] == cg["ntie"] - cb * (cb - 1) // 2
+
+
+def test_vignette_matrix(expected, golden_dir):
+    from icikendalltau_amd import api
+    from tests.oracle_engine import OracleEngine
+    M = vignette_matrix(golden_dir)
+    names = ["s1", "s2", "s3"]
+    check_vignette(api.ici_kendalltau(M, colnames=names, engine=OracleEngine()),
+                   api.ici_kendalltau(M, colnames=names, engine=OracleEngine(), return_matrix=False), expected["vignette"])
+
+
+def test_readme_kt_fast(expected):
+    from icikendalltau_amd import api
+    from tests.oracle_engine import OracleEngine
+    x, y = readme_kt_fast_xy()
+    check_readme_kt_fast(api.kt_fast(x, y, engine=OracleEngine()), expected["readme_kt_fast"])
+
+
+def test_ici_kt_help_page(expected):
+    e = expected["ici_kt_help"]
+    for x, y, perspective, want in ici_kt_help_cases(e):
+        out, _cnt, rsn = O.ici_kt(x, y, perspective)
+        assert rsn == 0
+        check_ici_kt_help(out, want, e)
