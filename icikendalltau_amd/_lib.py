@@ -16,7 +16,8 @@ _ROOT = os.path.dirname(_PKG)
 LIB_PATH = os.environ.get("ICIKT_LIB") or os.path.join(_PKG, "libicikt_hip.so")  # ICIKT_LIB: A/B of builds (tools)
 SOURCES = [os.path.join(_PKG, "csrc", f) for f in ("icikt_kernels.hip", "icikt_prepass.hip", "icikt_epilogue.hip",
                                                        "icikt_capi.cpp", "icikt_capi_cor.cpp", "icikt_capi_diag.cpp",
-                                                       "icikt_multi.cpp", "icikt_transfer.cpp", "icikt_cor.hip",
+                                                       "icikt_multi.cpp", "icikt_transfer.cpp", "icikt_cor.hip", "icikt_topk.hip",
+                                                       "icikt_capi_topk.cpp",
                                                        "icikt_diag.hip", "icikt_ingest.hip", "icikt_sparse.hip")]
 HEADERS = [os.path.join(_ROOT, "include", "icikt.h"), os.path.join(_PKG, "csrc", "icikt_device.h"),
            os.path.join(_PKG, "csrc", "icikt_wave.h"), os.path.join(_PKG, "csrc", "icikt_host.h"),
@@ -35,6 +36,8 @@ FLAG_BALANCE_COST = 16  # multi-device entries: pair blocks of equal cost (the s
 FLAG_HOST_PINNED = 8     # the caller has page-locked the matrix and the result arrays of the call (pinned_empty)
 CNT_FIELDS = ("n", "missing", "dis", "ntie", "xtie", "ytie", "x0", "x1", "y0", "y1", "tot")
 K_PREPARE, K_PAIRS, K_EPILOGUE = 0, 1, 2
+TOPK_MAX = 256                # ICIKT_TOPK_MAX: partners per sample of icikt_topk_*
+TOPK_MAX_SAMPLES = 65535      # ICIKT_TOPK_MAX_SAMPLES
 MASK_VALS = 32                # distinct finite global_na values of the device-side exclusion rule (icikt_device.h)
 MAX_FEATURES = 65535          # the tuned kernels
 MAX_FEATURES_WIDE = 262144    # the plain 32-bit path (exact integer arithmetic)
@@ -65,6 +68,7 @@ EXPORTS = (
     "icikt_col_medians_in", "icikt_censor_counts_in", "icikt_rank_order_in", "icikt_convert_dev",
     "icikt_pairs_csc", "icikt_matrix_csc", "icikt_missingness_csc", "icikt_col_medians_csc", "icikt_censor_counts_csc",
     "icikt_rank_order_csc", "icikt_scatter_csc_dev",
+    "icikt_topk_f64", "icikt_topk_in", "icikt_topk_csc",
 )
 
 # icikt_input: the caller's matrix as a typed, strided view (ICIKT_DTYPE_*, ICIKT_ORDER_*)
@@ -332,17 +336,19 @@ def lib():
     L.icikt_matrix_f64.argtypes = [c_vp, c_vp, c_i64, c_i64, c_i64, c_vp, c_int, c_vp, c_vp, c_i64, c_int, c_int, c_int,
                                    c_u32, c_int, c_int, c_vp, c_vp, c_vp]
     L.icikt_matrix_multi_f64.argtypes = L.icikt_matrix_f64.argtypes
+    L.icikt_topk_f64.argtypes = [c_vp, c_vp, c_i64, c_i64, c_i64, c_vp, c_int, c_int, c_int, c_int, c_int, c_u32, c_int,
+                                 c_vp, c_vp, c_vp, c_vp, c_vp]
     L.icikt_multi_rank_phase_ms.argtypes = [c_vp, c_int, ctypes.POINTER(ctypes.c_double)]
     L.icikt_multi_ranks_used.argtypes = [c_vp]
     L.icikt_debug_step_stats.argtypes = [c_vp, c_vp, c_int]
     # the *_in twins: (ctx, const icikt_input*, n_feat, n_samp, ...) where the _f64 entry has (ctx, X, n_feat, n_samp, ld, ...)
     for nm in ("pairs", "matrix", "pairs_complete", "missingness", "cor_pairs", "col_medians", "censor_counts",
-               "rank_order"):
+               "rank_order", "topk"):
         f64 = getattr(L, f"icikt_{nm}_f64").argtypes
         getattr(L, f"icikt_{nm}_in").argtypes = [c_vp, ctypes.POINTER(InputView), c_i64, c_i64] + list(f64[5:])
     L.icikt_convert_dev.argtypes = [c_vp, c_vp, c_int, c_int, c_i64, c_i64, c_i64, c_vp, c_i64]
     # the *_csc twins: (ctx, const icikt_csc_input*, n_feat, n_samp, ...)
-    for nm in ("pairs", "matrix", "missingness", "col_medians", "censor_counts", "rank_order"):
+    for nm in ("pairs", "matrix", "missingness", "col_medians", "censor_counts", "rank_order", "topk"):
         f64 = getattr(L, f"icikt_{nm}_f64").argtypes
         getattr(L, f"icikt_{nm}_csc").argtypes = [c_vp, ctypes.POINTER(CscInput), c_i64, c_i64] + list(f64[5:])
     L.icikt_scatter_csc_dev.argtypes = [c_vp, c_vp, c_vp, c_vp, c_int, c_int, ctypes.c_double, c_i64, c_i64, c_vp, c_i64]
@@ -595,6 +601,29 @@ class Context:
             (lib().icikt_matrix_csc if is_sparse(X) else lib().icikt_matrix_in)
         return _matrix_call(fn, self._h, self._chk, X, global_na, pi, pj, perspective, alternative,
                             continuity, flags, scale_max, diag_good, want_keep, view=not self.f64_entries)
+
+    def topk(self, X, k, global_na=None, perspective="global", alternative="two.sided", continuity=False,
+             flags: int = 0, scale_max=True):
+        """Every sample's k partners with the largest ICI-Kendall-tau, selected on the device (icikt_topk_f64): nothing
+        of size S x S exists on either side.  X and global_na as matrix() takes them.  Returns (idx [S, k] int32, -1
+        padded; vals5 [5, S, k]: cor, raw, pvalue, taumax, completeness, NA_real_ padded; n_valid [S]; max_taumax;
+        reason_counts [5]).  A column's partners are ordered by raw descending (by the doubles' bits: -0.0 below +0.0),
+        ties by the smaller index.  The argument checks are the library's: a bad k or perspective raises IciktError."""
+        fn, fname, xargs, n_feat, n_samp, flags, _keep = self._entry("topk", X, flags)
+        k = int(k)
+        gna = np.ascontiguousarray([] if global_na is None else np.atleast_1d(global_na), dtype=np.float64)
+        alloc = pinned_empty if (flags & FLAG_HOST_PINNED) else np.empty
+        idx = alloc((n_samp, max(k, 0)), dtype=np.int32)
+        vals = alloc((5, n_samp, max(k, 0)), dtype=np.float64)
+        n_valid = np.zeros(n_samp, dtype=np.int32)
+        mx = np.full(1, -np.inf)
+        rc5 = np.zeros(5, dtype=np.int64)
+        persp = PERSPECTIVE.get(perspective, perspective if isinstance(perspective, int) else -1)
+        alt = ALTERNATIVE.get(alternative, ALT_OTHER)
+        self._chk(fn(self._h, *xargs, _ptr(gna) if gna.size else None, int(gna.size), k, persp, alt,
+                     int(bool(continuity)), flags, int(bool(scale_max)), _ptr(idx), _ptr(vals), _ptr(n_valid), _ptr(mx),
+                     _ptr(rc5)), fname)
+        return idx, vals, n_valid, float(mx[0]), rc5
 
     def pairs_complete(self, X, pi, pj, alternative="two.sided", continuity=False, flags: int = 0,
                        want_counts: bool = False):

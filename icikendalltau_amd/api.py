@@ -58,6 +58,12 @@ class HipEngine:
         return self.ctx.matrix(data_matrix, global_na, pi, pj, perspective, alternative, continuity, self.flags,
                                scale_max, diag_good, want_keep=True)
 
+    def topk(self, data_matrix, k, global_na=None, perspective="global", alternative="two.sided", continuity=False,
+             flags=0, scale_max=True):
+        """Every sample's k best partners, selected on the device (icikt_topk_f64): Context.topk's contract."""
+        return self.ctx.topk(data_matrix, k, global_na, perspective, alternative, continuity, self.flags | flags,
+                             scale_max)
+
     def cor_pairs(self, X, pi, pj, method, pairwise, alternative, continuity):
         """cor_fast's pairs on the device (icikt_cor_pairs_f64): (out3: rho, p-value, n_values; reasons)."""
         return self.ctx.cor_pairs(X, pi, pj, method, pairwise, alternative, continuity)
@@ -140,6 +146,11 @@ class MultiHipEngine(HipEngine):
 
     def cor_pairs(self, X, pi, pj, method, pairwise, alternative, continuity):  # cor_fast runs on one device
         return self._one().cor_pairs(X, pi, pj, method, pairwise, alternative, continuity)
+
+    def topk(self, data_matrix, k, global_na=None, perspective="global", alternative="two.sided", continuity=False,
+             flags=0, scale_max=True):  # the top-k selection runs on one device
+        return self._one().topk(data_matrix, k, global_na, perspective, alternative, continuity, self.flags | flags,
+                                scale_max)
 
     def pairs_complete(self, X, pi, pj):  # kt_fast's per-pair masking path exists on one device only
         out, _cnt, rsn = self._one().pairs_complete(X, pi, pj, "two.sided", False, self.flags)
@@ -628,6 +639,102 @@ def ici_kendalltau(data_matrix, global_na=(float("nan"), float("inf"), 0), persp
     cols = {"s1": names_arr[s1], "s2": names_arr[s2], "core": core_col, "raw": raw, "pvalue": pvalue,
             "taumax": taumax, "completeness": completeness, "cor": cor}
     return {"cor": pd.DataFrame(cols) if pd is not None else cols, "run_time": t_diff}
+
+
+# --------------------------------------------------------------------------------------------------
+# ici_kendalltau_topk: every sample's k nearest partners (no counterpart in the reference)
+# --------------------------------------------------------------------------------------------------
+_TOPK_KEYS = ("cor", "raw", "pvalue", "taumax", "completeness")
+_NA_REAL_BITS = np.uint64(0x7FF00000000007A2)   # R's NA_real_: what the library pads with
+
+
+def _topk_numpy(mats5, k):
+    """The selection of icikt_topk_f64 from five full S x S matrices (cor, raw, pvalue, taumax, completeness), for
+    engines without a topk method (the CPU tests' checker engines).  Per column: partners j != c whose raw is not NA,
+    by raw descending in the order of the doubles' bits (-0.0 below +0.0), ties by the smaller index; padding -1 /
+    NA_real_.  Returns (idx [S, k], vals5 [5, S, k], n_valid [S])."""
+    mats5 = [np.ascontiguousarray(m, dtype=np.float64) for m in mats5]
+    raw = mats5[1]
+    S = raw.shape[0]
+    idx = np.full((S, k), -1, dtype=np.int32)
+    vals = np.empty((5, S, k), dtype=np.float64)
+    vals.view(np.uint64)[...] = _NA_REAL_BITS
+    n_valid = np.zeros(S, dtype=np.int32)
+    bits = raw.view(np.uint64)
+    sign = (bits >> np.uint64(63)).astype(bool)
+    key = np.where(sign, ~bits, bits | np.uint64(1 << 63))
+    partners = np.arange(S)
+    for c in range(S):
+        ok = ~np.isnan(raw[c])
+        ok[c] = False
+        cand = partners[ok]
+        order = np.lexsort((cand, ~key[c, cand]))[:k]     # ~key ascending = key descending, then the index
+        sel = cand[order]
+        m = len(sel)
+        n_valid[c] = m
+        idx[c, :m] = sel
+        for q in range(5):
+            vals[q, c, :m] = mats5[q][c, sel]
+    return idx, vals, n_valid
+
+
+def ici_kendalltau_topk(data_matrix, k, global_na=(float("nan"), float("inf"), 0), perspective="global", scale_max=True,
+                        alternative="two.sided", continuity=False, colnames=None, engine=None):
+    """For every sample (column) of a features x samples matrix its ``k`` partners with the largest ICI-Kendall-tau:
+    the rows of a kNN graph, without the S x S matrices ``ici_kendalltau`` returns.
+
+    The arguments are ``ici_kendalltau``'s (column names are required; a sparse matrix, float32 and integer matrices
+    are read where they lie).  On the HIP engine the selection runs on the device (icikt_topk_f64) and nothing of size
+    S x S exists on either side; ``k`` is an integer in 1 .. 256, and a matrix has at most 65 535 samples.
+
+    Partners are ordered by ``raw`` descending, ties by the smaller sample index; a pair whose ``raw`` is NA is no
+    one's partner (the reference's warning is raised once per such pair of reasons 2-4); ``cor`` is ``raw`` over the
+    largest ``taumax`` of all pairs when ``scale_max``.  Returns a dict: ``indices`` (S x k, -1 where a sample has fewer
+    than k partners), ``neighbors`` (their names, None padded), ``cor, raw, pvalue, taumax, completeness`` (S x k, NA
+    padded), ``n_valid`` (S), ``max_taumax`` and ``run_time``.  ``formats.topk_to_csr`` turns it into a sparse graph.
+    """
+    if isinstance(k, (bool, np.bool_)) or not isinstance(k, (int, np.integer)) or not 1 <= int(k) <= _lib.TOPK_MAX:
+        raise ValueError(f"`k` must be an integer in 1 .. {_lib.TOPK_MAX}")
+    k = int(k)
+    data_matrix, names = _as_matrix(data_matrix, colnames, "data_matrix", keep_dtype=True, keep_sparse=True)
+    n_sample = data_matrix.shape[1]
+    if n_sample < 2:
+        raise ValueError("No comparisons to do. Check the list of column names in "
+                         "`include_only` vs those in the samples.")  # R/kendalltau.R:240-247
+    eng = engine or _default_engine()
+    if hasattr(eng, "topk"):
+        n_finite = len({float(v) for v in np.atleast_1d(np.asarray([] if global_na is None else global_na,
+                                                                     dtype=np.float64)) if math.isfinite(v)})
+        X = data_matrix
+        if n_finite > _lib.MASK_VALS:   # more values than the device-side rule holds: masked here, NaN passed
+            if _lib.is_sparse(X):
+                X = _densify(X)
+            X = np.asarray(X, dtype=np.float64)
+            X = _masked_fortran(X, setup_missing_matrix(X, global_na))
+            global_na = (float("nan"),)
+        t1 = time.perf_counter()
+        idx, vals, n_valid, max_taumax, rcounts = eng.topk(_for_engine(X, eng, fortran=False), k, global_na, perspective,
+                                                           alternative, continuity, 0, scale_max)
+        t_diff = time.perf_counter() - t1
+        for code in (_lib.REASON_SHORT, _lib.REASON_SINGLE_UNIQUE, _lib.REASON_TIES_EQ_TOTAL):
+            for _ in range(int(rcounts[code])):   # one warning per offending pair, as ici_split raises them
+                _warn_reason(code)
+    else:
+        full = ici_kendalltau(data_matrix, global_na=global_na, perspective=perspective, scale_max=scale_max,
+                              diag_good=True, alternative=alternative, continuity=continuity, colnames=names, engine=eng)
+        t_diff = full["run_time"]
+        idx, vals, n_valid = _topk_numpy([np.asarray(full[key]) for key in _TOPK_KEYS], k)
+        iu = np.triu_indices(n_sample, k=1)
+        have = _na_rm(np.asarray(full["taumax"])[iu])
+        max_taumax = float(have.max()) if have.size else -math.inf
+    names_arr = np.asarray(list(names) + [None], dtype=object)
+    res = {"indices": idx, "neighbors": names_arr[idx]}    # (-1 picks the None behind the names)
+    for q, key in enumerate(_TOPK_KEYS):
+        res[key] = vals[q]
+    res["n_valid"] = n_valid
+    res["max_taumax"] = max_taumax
+    res["run_time"] = t_diff
+    return res
 
 
 # --------------------------------------------------------------------------------------------------

@@ -1728,7 +1728,8 @@ extern "C" {
 // cost the launch down to), split (1 | 2 | 4 segments per half-wave task), gridmult (persistent grid as a multiple of the resident waves, always), gridcap (persistent
 // grid: at most this many workgroups),
 // pipe (0 | 1: the host entries' chunk pipeline off / on whenever possible), k0 (0 | 1: the pre-pass always in its
-// 1 024-thread / 256-thread shape), verbose (0 | 1: print the plan to stderr).
+// 1 024-thread / 256-thread shape), tkblock (icikt_topk_*: pairs per block of whole combn rows; 1 = a row per block),
+// verbose (0 | 1: print the plan to stderr).
 // (The keys h2d and regfail of rounds 2-3 are gone with the mode they steered: the library no longer page-locks
 // caller memory, icikt_host.h.)
 int icikt_debug_set_plan(icikt_ctx* c, const char* spec) {
@@ -1763,6 +1764,7 @@ int icikt_debug_set_plan(icikt_ctx* c, const char* spec) {
     else if (key == "gridcap") ov.grid_cap = atoi(val.c_str());
     else if (key == "pipe") pipe = (val[0] == '1') ? 1 : 0;
     else if (key == "k0") k0 = (val[0] == '1') ? 1 : 0;
+    else if (key == "tkblock") ov.tkblock = atoll(val.c_str());
     else return fail(c, ICIKT_E_INVALID, "debug_set_plan: unknown key '" + key + "'");
   }
   c->plan_ov = ov;

@@ -212,6 +212,26 @@ hipError_t launch_out_stats(const PrepView& pv, const double* out4, const int32_
 hipError_t launch_assemble(const PrepView& pv, const double* out4, const int32_t* pi, const int32_t* pj, int64_t n_pairs,
                            const int64_t* n_good, const unsigned long long* red, int scale_max, int diag_good,
                            double* out5, hipStream_t s);
+// launch_out_stats without the zeroing of red: the statistics of one more block of pairs are added to what red holds
+// (icikt_topk_f64 runs the triangle in blocks; the caller zeroes red's 8 words before the first)
+hipError_t launch_out_stats_accum(const PrepView& pv, const double* out4, const int32_t* reasons, int64_t n_pairs,
+                                  unsigned long long* red, hipStream_t s);
+// ---- top-k partners per sample (icikt_topk.hip) ----
+// Every column's running list of its k best partners, twice (cur[c] says which copy is current; a merge writes the
+// other one and flips it): keys as dbl_sortable gives them, partner columns, and the four out4 doubles of each entry.
+struct TopkLists {
+  unsigned long long* key;   // [2][S][k]
+  int32_t* partner;          // [2][S][k]
+  double* vals;              // [2][S][k][4]: raw, pvalue, taumax, completeness
+  int32_t* count;            // [S] entries of the current list (zeroed before the first merge)
+  int32_t* cur;              // [S] 0 | 1 (zeroed likewise)
+  int k;                     // 1 .. ICIKT_TOPK_MAX
+};
+// out4: the records of the pairs of rows [row_a, row_b) of combn(S, 2), in combn order (row_b <= S - 1, S <= 65 535)
+hipError_t launch_topk_merge(const TopkLists& L, const double* out4, int S, int row_a, int row_b, hipStream_t s);
+// idx [S][k] (-1 padded), out5k [5][S][k] (NA_real_ padded), n_valid [S] (may be null); red: launch_out_stats' record
+hipError_t launch_topk_finish(const TopkLists& L, const unsigned long long* red, int S, int scale_max, int32_t* idx,
+                              double* out5k, int32_t* n_valid, hipStream_t s);
 // wide columns: one wave per pair, grid of `blocks` single-wave workgroups that fetch pairs from *task_ctr
 hipError_t launch_k1_wide(const PrepView& pv, const int32_t* pi, const int32_t* pj, PairRaw* raw, int64_t n_pairs,
                           int blocks, size_t lds_bytes, int* task_ctr, hipStream_t s);

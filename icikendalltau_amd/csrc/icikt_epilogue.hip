@@ -384,6 +384,15 @@ hipError_t launch_out_stats(const PrepView& pv, const double* out4, const int32_
   return hipGetLastError();
 }
 
+hipError_t launch_out_stats_accum(const PrepView& pv, const double* out4, const int32_t* reasons, int64_t n_pairs,
+                                  unsigned long long* red, hipStream_t s) {
+  if (n_pairs <= 0) return hipSuccess;
+  (void)hipGetLastError();
+  const int blocks = (int)std::max<int64_t>(1, std::min<int64_t>(2048, (n_pairs + 255) / 256));
+  hipLaunchKernelGGL(k_out_stats, dim3(blocks), dim3(256), 0, s, pv, out4, reasons, n_pairs, nullptr, red);
+  return hipGetLastError();
+}
+
 hipError_t launch_assemble(const PrepView& pv, const double* out4, const int32_t* pi, const int32_t* pj, int64_t n_pairs,
                            const int64_t* n_good, const unsigned long long* red, int scale_max, int diag_good,
                            double* out5, hipStream_t s) {

@@ -115,6 +115,13 @@ struct icikt_ctx {
     bool prho_ready = false;
   } cor;
 
+  // top-k partners per sample (icikt_topk_f64): the columns' lists (TopkLists), their state words and the results
+  struct TopkBufs {
+    DevBuf<unsigned long long> key;
+    DevBuf<int32_t> partner, state, idx, n_valid;
+    DevBuf<double> vals, out;
+  } topk;
+
   // missing-value diagnostics (icikt_col_medians_f64, icikt_censor_counts_f64, icikt_rank_order_f64)
   struct DiagBufs {
     DevBuf<double> median, medrank, out;
@@ -133,6 +140,7 @@ struct icikt_ctx {
     int split = -1;     // half-wave kernels: segments per task (1 | 2 | 4), whatever the launch's size
     int solo = -1;      // 0: SOLO steps of the tie program run as MIXED steps (with the in-step chains)
     int list = -1;      // list mode (range counts per listed tie group) up to this many tie groups: count mode takes over above
+    long long tkblock = -1;   // icikt_topk_*: pairs a block of whole combn rows may hold (default: the library's budget)
     bool verbose = false;
   } plan_ov;
 

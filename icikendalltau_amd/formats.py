@@ -6,6 +6,7 @@
   evaluates nothing from the file.
 * ``cor_matrix_2_long_df`` / ``long_df_2_cor_matrix``: the reference's converters between the square result
   matrices and the long data.frame storage form (R/reshaping.R:15-68).
+* ``topk_to_csr``: the result of ``ici_kendalltau_topk`` as a sparse samples x samples kNN graph (needs scipy).
 """
 from __future__ import annotations
 
@@ -237,3 +238,25 @@ def long_df_2_cor_matrix(long_df, is_square=True):
     if len(long_df) != m.shape[0] * m.shape[1] and is_square:
         m[c, r] = vals
     return pd.DataFrame(m, index=l1, columns=l2)
+
+
+# --------------------------------------------------------------------------------------------------
+# ici_kendalltau_topk -> a sparse kNN graph
+# --------------------------------------------------------------------------------------------------
+def topk_to_csr(result, value="cor"):
+    """The dict ``ici_kendalltau_topk`` returns as an S x S ``scipy.sparse.csr_matrix``: row s holds ``result[value]``
+    of sample s's partners at their column indices (in the list's order); padded slots are dropped, so the matrix has
+    ``sum(n_valid)`` stored entries.  scipy is optional for the package and needed here."""
+    try:
+        import scipy.sparse as sp
+    except ImportError as e:
+        raise ImportError("topk_to_csr needs scipy (optional for icikendalltau_amd, required for this converter)") from e
+    if value not in ("cor", "raw", "pvalue", "taumax", "completeness"):
+        raise ValueError("`value` must be one of cor, raw, pvalue, taumax, completeness")
+    idx = np.asarray(result["indices"])
+    vals = np.asarray(result[value], dtype=np.float64)
+    n_valid = np.asarray(result["n_valid"], dtype=np.int64)
+    S, k = idx.shape
+    real = np.arange(k)[None, :] < n_valid[:, None]
+    indptr = np.concatenate([[0], np.cumsum(n_valid)])
+    return sp.csr_matrix((vals[real], idx[real].astype(np.int32), indptr), shape=(S, S))

@@ -265,6 +265,35 @@ int icikt_matrix_f64(icikt_ctx *ctx, const double *X, int64_t n_feat, int64_t n_
                      int perspective, int alternative, int continuity, uint32_t flags, int scale_max, int diag_good,
                      double *out5, uint8_t *keep, int64_t *reason_counts);
 
+/* ---- top-k partners per sample, chosen on the device -----------------------------------------------------------
+ *
+ * For every column (sample) c of X its k partners j != c with the largest ICI-Kendall-tau, each with the five values
+ * icikt_matrix_f64 reports for that pair -- without anything of size n_samp^2 on the device or the host: the combn
+ * triangle runs through the pair engine in blocks of whole rows, and a selection kernel folds each block into the
+ * columns' lists (device memory: the prepared matrix, one block's buffers and 88 n_samp k bytes of lists).
+ *   candidates   all C(n_samp, 2) pairs, each seen from both of its columns; never the diagonal; a pair whose raw is
+ *                NA (reason codes 1..4) is no candidate for either column
+ *   order        raw descending in the total order of the doubles' bits (so -0.0 sorts below +0.0), ties by the smaller
+ *                partner index: a pure function of the set of (raw, partner), whatever the blocks
+ *   values       cor, raw, pvalue, taumax, completeness; cor = scale_max ? raw / max(taumax, na.rm = TRUE) : raw over
+ *                ALL computed pairs (-Inf when there is none), bit for bit the cell of icikt_matrix_f64's matrices;
+ *                the ranking is by raw whatever scale_max says
+ *   padding      a column with fewer than k valid partners: idx -1 and R's NA_real_ in all five values
+ * idx: [n_samp][k]; out5k: [5][n_samp][k]; n_valid (optional): [n_samp] real partners per column; max_taumax
+ * (optional): the scale's denominator; reason_counts (optional): [5] pairs per reason code, as icikt_matrix_f64.
+ * 1 <= k <= ICIKT_TOPK_MAX (k > n_samp - 1 means padding); n_samp <= ICIKT_TOPK_MAX_SAMPLES, so that pair indices
+ * stay 32-bit (ICIKT_E_INVALID beyond, the message names the limit); n_feat as icikt_run_dev takes it; global_na as
+ * icikt_matrix_f64.  Like icikt_pairs_complete_f64 the call leaves neither a prepared matrix nor a pair list behind:
+ * icikt_run_dev answers ICIKT_E_STATE and icikt_num_pairs -1 afterwards.  A call refused at its argument checks
+ * touches nothing.  With ICIKT_FLAG_TIMING the selection kernels are accounted under ICIKT_K_EPILOGUE.
+ * icikt_topk_in / icikt_topk_csc: the same on a typed view / a CSC view of the matrix (below). */
+#define ICIKT_TOPK_MAX 256
+#define ICIKT_TOPK_MAX_SAMPLES 65535
+int icikt_topk_f64(icikt_ctx *ctx, const double *X, int64_t n_feat, int64_t n_samp, int64_t ld, const double *global_na,
+                   int n_global_na, int k, int perspective, int alternative, int continuity, uint32_t flags,
+                   int scale_max, int32_t *idx, double *out5k, int32_t *n_valid, double *max_taumax,
+                   int64_t *reason_counts);
+
 /* ---- several GPUs behind one call (what the R glue binds when n_gpu > 1) ----------------------
  *
  * Replaces the reference's worker fan-out, computation$split_fun(split_comparisons, ici_split, ...)
@@ -405,6 +434,9 @@ int icikt_missingness_f64(icikt_ctx *ctx, const double *X, int64_t n_feat, int64
 int icikt_pairs_in(icikt_ctx *ctx, const icikt_input *X, int64_t n_feat, int64_t n_samp, const int32_t *pi,
                    const int32_t *pj, int64_t n_pairs, int perspective, int alternative, int continuity, uint32_t flags,
                    double *out4, int64_t *counts, int32_t *reasons);
+int icikt_topk_in(icikt_ctx *ctx, const icikt_input *X, int64_t n_feat, int64_t n_samp, const double *global_na,
+                  int n_global_na, int k, int perspective, int alternative, int continuity, uint32_t flags, int scale_max,
+                  int32_t *idx, double *out5k, int32_t *n_valid, double *max_taumax, int64_t *reason_counts);
 int icikt_matrix_in(icikt_ctx *ctx, const icikt_input *X, int64_t n_feat, int64_t n_samp, const double *global_na,
                     int n_global_na, const int32_t *pi, const int32_t *pj, int64_t n_pairs, int perspective,
                     int alternative, int continuity, uint32_t flags, int scale_max, int diag_good, double *out5,
@@ -450,6 +482,9 @@ int icikt_matrix_csc(icikt_ctx *ctx, const icikt_csc_input *X, int64_t n_feat, i
                      int n_global_na, const int32_t *pi, const int32_t *pj, int64_t n_pairs, int perspective,
                      int alternative, int continuity, uint32_t flags, int scale_max, int diag_good, double *out5,
                      uint8_t *keep, int64_t *reason_counts);
+int icikt_topk_csc(icikt_ctx *ctx, const icikt_csc_input *X, int64_t n_feat, int64_t n_samp, const double *global_na,
+                   int n_global_na, int k, int perspective, int alternative, int continuity, uint32_t flags, int scale_max,
+                   int32_t *idx, double *out5k, int32_t *n_valid, double *max_taumax, int64_t *reason_counts);
 int icikt_missingness_csc(icikt_ctx *ctx, const icikt_csc_input *X, int64_t n_feat, int64_t n_samp, const int32_t *pi,
                           const int32_t *pj, int64_t n_pairs, int64_t *missingness);
 int icikt_col_medians_csc(icikt_ctx *ctx, const icikt_csc_input *X, int64_t n_feat, int64_t n_samp,
@@ -481,7 +516,9 @@ int icikt_selftest(icikt_ctx *ctx);
  * pairs' counter tables may cost the launch occupancy), split (1 | 2 | 4: segments a half-wave task is cut in, whatever the
  * launch's size), merge (0 | 1: the pipelined host entries' pairs in a launch per chunk | in one launch behind the last chunk), gridmult / gridcap (persistent grid of the long-column kernel: a
  * multiple of the resident workgroups / at most this many), pipe (0 | 1: the host entries' chunk pipeline), k0 (0 | 1: the
- * pre-pass always in its 1 024-thread / 256-thread shape), verbose (0 | 1: print the chosen plan to stderr). */
+ * pre-pass always in its 1 024-thread / 256-thread shape), tkblock (icikt_topk_*: the pairs a block of whole combn rows
+ * may hold -- a block is always at least one row, so tkblock=1 runs a row per block), verbose (0 | 1: print the chosen
+ * plan to stderr). */
 int icikt_debug_set_plan(icikt_ctx *ctx, const char *spec);
 /* Development hook: per step kind of the pair kernel (hot loop, hot step in the main loop, MIXED, GROUP, general,
  * closed-form tail, set-up) the steps taken, their rows and the wave cycles spent, as out24 = [steps x 8 | rows x 8 |
