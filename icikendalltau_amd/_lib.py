@@ -17,7 +17,7 @@ LIB_PATH = os.environ.get("ICIKT_LIB") or os.path.join(_PKG, "libicikt_hip.so") 
 SOURCES = [os.path.join(_PKG, "csrc", f) for f in ("icikt_kernels.hip", "icikt_prepass.hip", "icikt_epilogue.hip",
                                                        "icikt_capi.cpp", "icikt_capi_cor.cpp", "icikt_capi_diag.cpp",
                                                        "icikt_multi.cpp", "icikt_transfer.cpp", "icikt_cor.hip", "icikt_topk.hip",
-                                                       "icikt_capi_topk.cpp",
+                                                       "icikt_capi_topk.cpp", "icikt_edges.hip", "icikt_capi_edges.cpp",
                                                        "icikt_diag.hip", "icikt_ingest.hip", "icikt_sparse.hip")]
 HEADERS = [os.path.join(_ROOT, "include", "icikt.h"), os.path.join(_PKG, "csrc", "icikt_device.h"),
            os.path.join(_PKG, "csrc", "icikt_wave.h"), os.path.join(_PKG, "csrc", "icikt_host.h"),
@@ -69,6 +69,7 @@ EXPORTS = (
     "icikt_pairs_csc", "icikt_matrix_csc", "icikt_missingness_csc", "icikt_col_medians_csc", "icikt_censor_counts_csc",
     "icikt_rank_order_csc", "icikt_scatter_csc_dev",
     "icikt_topk_f64", "icikt_topk_in", "icikt_topk_csc",
+    "icikt_edges_f64", "icikt_edges_in", "icikt_edges_csc",
 )
 
 # icikt_input: the caller's matrix as a typed, strided view (ICIKT_DTYPE_*, ICIKT_ORDER_*)
@@ -76,6 +77,19 @@ DTYPE_F64, DTYPE_F32, DTYPE_I32, DTYPE_I64 = range(4)
 ORDER_COL, ORDER_ROW = 0, 1
 DTYPES = {np.dtype(np.float64): DTYPE_F64, np.dtype(np.float32): DTYPE_F32, np.dtype(np.int32): DTYPE_I32,
           np.dtype(np.int64): DTYPE_I64}
+
+
+class EdgeRule(ctypes.Structure):
+    """icikt_edge_rule (include/icikt.h): a NaN bound is no bound."""
+    _fields_ = [("min_raw", ctypes.c_double), ("max_pvalue", ctypes.c_double), ("min_completeness", ctypes.c_double),
+                ("absolute", ctypes.c_int)]
+
+
+def edge_rule(min_raw=None, max_pvalue=None, min_completeness=None, absolute=False) -> EdgeRule:
+    """The icikt_edge_rule of the three bounds (None: no bound)."""
+    nan = float("nan")
+    return EdgeRule(nan if min_raw is None else float(min_raw), nan if max_pvalue is None else float(max_pvalue),
+                    nan if min_completeness is None else float(min_completeness), int(bool(absolute)))
 
 
 class InputView(ctypes.Structure):
@@ -338,17 +352,19 @@ def lib():
     L.icikt_matrix_multi_f64.argtypes = L.icikt_matrix_f64.argtypes
     L.icikt_topk_f64.argtypes = [c_vp, c_vp, c_i64, c_i64, c_i64, c_vp, c_int, c_int, c_int, c_int, c_int, c_u32, c_int,
                                  c_vp, c_vp, c_vp, c_vp, c_vp]
+    L.icikt_edges_f64.argtypes = [c_vp, c_vp, c_i64, c_i64, c_i64, c_vp, c_int, ctypes.POINTER(EdgeRule), c_int, c_int,
+                                  c_int, c_u32, c_int, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]
     L.icikt_multi_rank_phase_ms.argtypes = [c_vp, c_int, ctypes.POINTER(ctypes.c_double)]
     L.icikt_multi_ranks_used.argtypes = [c_vp]
     L.icikt_debug_step_stats.argtypes = [c_vp, c_vp, c_int]
     # the *_in twins: (ctx, const icikt_input*, n_feat, n_samp, ...) where the _f64 entry has (ctx, X, n_feat, n_samp, ld, ...)
     for nm in ("pairs", "matrix", "pairs_complete", "missingness", "cor_pairs", "col_medians", "censor_counts",
-               "rank_order", "topk"):
+               "rank_order", "topk", "edges"):
         f64 = getattr(L, f"icikt_{nm}_f64").argtypes
         getattr(L, f"icikt_{nm}_in").argtypes = [c_vp, ctypes.POINTER(InputView), c_i64, c_i64] + list(f64[5:])
     L.icikt_convert_dev.argtypes = [c_vp, c_vp, c_int, c_int, c_i64, c_i64, c_i64, c_vp, c_i64]
     # the *_csc twins: (ctx, const icikt_csc_input*, n_feat, n_samp, ...)
-    for nm in ("pairs", "matrix", "missingness", "col_medians", "censor_counts", "rank_order", "topk"):
+    for nm in ("pairs", "matrix", "missingness", "col_medians", "censor_counts", "rank_order", "topk", "edges"):
         f64 = getattr(L, f"icikt_{nm}_f64").argtypes
         getattr(L, f"icikt_{nm}_csc").argtypes = [c_vp, ctypes.POINTER(CscInput), c_i64, c_i64] + list(f64[5:])
     L.icikt_scatter_csc_dev.argtypes = [c_vp, c_vp, c_vp, c_vp, c_int, c_int, ctypes.c_double, c_i64, c_i64, c_vp, c_i64]
@@ -624,6 +640,40 @@ class Context:
                      int(bool(continuity)), flags, int(bool(scale_max)), _ptr(idx), _ptr(vals), _ptr(n_valid), _ptr(mx),
                      _ptr(rc5)), fname)
         return idx, vals, n_valid, float(mx[0]), rc5
+
+    def edges(self, X, min_raw=None, max_pvalue=None, min_completeness=None, absolute=False, max_edges=0,
+              global_na=None, perspective="global", alternative="two.sided", continuity=False, flags: int = 0,
+              scale_max=True, want_degree=True):
+        """Every pair i < j whose raw (fabs(raw) with absolute), p-value and completeness pass the bounds that are not
+        None, in combn order, compacted on the device (icikt_edges_f64): nothing of size S x S exists on either side.
+        The bounds apply to raw, not to cor.  X and global_na as matrix() takes them.  Returns (ei, ej [m] int32; vals5
+        [5, m]: cor, raw, pvalue, taumax, completeness; n_edges: ALL matching pairs; degree [S] int64 or None;
+        max_taumax; reason_counts [5]) with m = min(n_edges, max_edges): max_edges = 0 only counts, and n_edges >
+        max_edges says the list is truncated (call again with room).  The argument checks are the library's."""
+        fn, fname, xargs, n_feat, n_samp, flags, _keep = self._entry("edges", X, flags)
+        max_edges = int(max_edges)
+        rule = edge_rule(min_raw, max_pvalue, min_completeness, absolute)
+        gna = np.ascontiguousarray([] if global_na is None else np.atleast_1d(global_na), dtype=np.float64)
+        room = max(0, min(max_edges, n_samp * (n_samp - 1) // 2))   # (the library writes no slot past the triangle)
+        alloc = pinned_empty if (flags & FLAG_HOST_PINNED) else np.empty
+        ei = alloc(room, dtype=np.int32) if room else None
+        ej = alloc(room, dtype=np.int32) if room else None
+        vals = alloc((5, room), dtype=np.float64) if room else None
+        n_edges = np.zeros(1, dtype=np.int64)
+        degree = np.zeros(n_samp, dtype=np.int64) if want_degree else None
+        mx = np.full(1, -np.inf)
+        rc5 = np.zeros(5, dtype=np.int64)
+        persp = PERSPECTIVE.get(perspective, perspective if isinstance(perspective, int) else -1)
+        alt = ALTERNATIVE.get(alternative, ALT_OTHER)
+        self._chk(fn(self._h, *xargs, _ptr(gna) if gna.size else None, int(gna.size), ctypes.byref(rule), persp, alt,
+                     int(bool(continuity)), flags, int(bool(scale_max)), room if max_edges >= 0 else max_edges,
+                     _ptr(ei), _ptr(ej), _ptr(vals), _ptr(n_edges), _ptr(degree), _ptr(mx), _ptr(rc5)), fname)
+        m = min(int(n_edges[0]), room)
+        if room:
+            ei, ej, vals = ei[:m], ej[:m], vals[:, :m]
+        else:
+            ei, ej, vals = np.empty(0, np.int32), np.empty(0, np.int32), np.empty((5, 0), np.float64)
+        return ei, ej, vals, int(n_edges[0]), degree, float(mx[0]), rc5
 
     def pairs_complete(self, X, pi, pj, alternative="two.sided", continuity=False, flags: int = 0,
                        want_counts: bool = False):

@@ -64,6 +64,12 @@ class HipEngine:
         return self.ctx.topk(data_matrix, k, global_na, perspective, alternative, continuity, self.flags | flags,
                              scale_max)
 
+    def edges(self, data_matrix, min_raw=None, max_pvalue=None, min_completeness=None, absolute=False, max_edges=0,
+              global_na=None, perspective="global", alternative="two.sided", continuity=False, flags=0, scale_max=True):
+        """Every pair past the bounds, compacted on the device (icikt_edges_f64): Context.edges' contract."""
+        return self.ctx.edges(data_matrix, min_raw, max_pvalue, min_completeness, absolute, max_edges, global_na,
+                              perspective, alternative, continuity, self.flags | flags, scale_max)
+
     def cor_pairs(self, X, pi, pj, method, pairwise, alternative, continuity):
         """cor_fast's pairs on the device (icikt_cor_pairs_f64): (out3: rho, p-value, n_values; reasons)."""
         return self.ctx.cor_pairs(X, pi, pj, method, pairwise, alternative, continuity)
@@ -151,6 +157,12 @@ class MultiHipEngine(HipEngine):
              flags=0, scale_max=True):  # the top-k selection runs on one device
         return self._one().topk(data_matrix, k, global_na, perspective, alternative, continuity, self.flags | flags,
                                 scale_max)
+
+    def edges(self, data_matrix, min_raw=None, max_pvalue=None, min_completeness=None, absolute=False, max_edges=0,
+              global_na=None, perspective="global", alternative="two.sided", continuity=False, flags=0,
+              scale_max=True):  # the compaction runs on one device
+        return self._one().edges(data_matrix, min_raw, max_pvalue, min_completeness, absolute, max_edges, global_na,
+                                 perspective, alternative, continuity, self.flags | flags, scale_max)
 
     def pairs_complete(self, X, pi, pj):  # kt_fast's per-pair masking path exists on one device only
         out, _cnt, rsn = self._one().pairs_complete(X, pi, pj, "two.sided", False, self.flags)
@@ -732,6 +744,130 @@ def ici_kendalltau_topk(data_matrix, k, global_na=(float("nan"), float("inf"), 0
     for q, key in enumerate(_TOPK_KEYS):
         res[key] = vals[q]
     res["n_valid"] = n_valid
+    res["max_taumax"] = max_taumax
+    res["run_time"] = t_diff
+    return res
+
+
+# --------------------------------------------------------------------------------------------------
+# ici_kendalltau_edges: every pair past a threshold, the edge list of a correlation network (the reference's
+# return_matrix = FALSE data.frame and cor_matrix_2_long_df are its unfiltered form)
+# --------------------------------------------------------------------------------------------------
+EDGES_DEFAULT_CAPACITY = 2 ** 20   # max_edges=None: the first call has room for max(this, EDGES_CAPACITY_PER_SAMPLE x S)
+EDGES_CAPACITY_PER_SAMPLE = 32     # edges (and never more than the triangle holds)
+
+
+def _edge_bound(value, name):
+    if value is None:
+        return None
+    if isinstance(value, (bool, np.bool_)) or not isinstance(value, (int, float, np.integer, np.floating)):
+        raise ValueError(f"`{name}` must be a number or None")
+    if math.isnan(float(value)):
+        raise ValueError(f"`{name}` must not be NaN (None means no bound)")
+    return float(value)
+
+
+def _edges_numpy(mats5, min_raw, max_pvalue, min_completeness, absolute):
+    """The selection of icikt_edges_f64 from five full S x S matrices (cor, raw, pvalue, taumax, completeness), for
+    engines without an edges method (the CPU tests' checker engines): the upper triangle in combn order, raw not NA and
+    every bound that is not None, as plain comparisons of doubles.  Returns (ei, ej, vals5 [5, m], degree [S]): all of
+    the matching pairs."""
+    mats5 = [np.ascontiguousarray(m, dtype=np.float64) for m in mats5]
+    S = mats5[1].shape[0]
+    iu = np.triu_indices(S, k=1)             # row-major upper triangle: i ascending, then j ascending
+    raw, pvalue, comp = mats5[1][iu], mats5[2][iu], mats5[4][iu]
+    with np.errstate(invalid="ignore"):
+        ok = ~np.isnan(raw)
+        if min_raw is not None:
+            ok &= (np.abs(raw) if absolute else raw) >= min_raw
+        if max_pvalue is not None:
+            ok &= pvalue <= max_pvalue
+        if min_completeness is not None:
+            ok &= comp >= min_completeness
+    ei, ej = iu[0][ok].astype(np.int32), iu[1][ok].astype(np.int32)
+    vals = np.stack([m[iu][ok] for m in mats5]) if S > 1 else np.empty((5, 0))
+    degree = np.bincount(ei, minlength=S).astype(np.int64) + np.bincount(ej, minlength=S).astype(np.int64)
+    return ei, ej, vals, degree
+
+
+def ici_kendalltau_edges(data_matrix, min_raw=None, max_pvalue=None, min_completeness=None, absolute=False,
+                         max_edges=None, global_na=(float("nan"), float("inf"), 0), perspective="global",
+                         scale_max=True, alternative="two.sided", continuity=False, colnames=None, engine=None):
+    """Every pair of samples (columns) of a features x samples matrix whose ICI-Kendall-tau passes a cut-off: the edge
+    list of a correlation network, without the S x S matrices ``ici_kendalltau`` returns.
+
+    A pair i < j is an edge iff its ``raw`` is not NA and every bound that is not None holds: ``raw >= min_raw``
+    (``abs(raw) >= min_raw`` with ``absolute``), ``pvalue <= max_pvalue``, ``completeness >= min_completeness`` (a NaN
+    p-value fails a p-value bound).  The bounds apply to ``raw``, never to the scaled ``cor``: its denominator, the
+    largest ``taumax`` of all pairs, is known only once every pair has been computed.  Edges come in ``combn`` order (i
+    ascending, then j ascending).  The other arguments are ``ici_kendalltau``'s (column names are required; a sparse
+    matrix, float32 and integer matrices are read where they lie).  On the HIP engine the compaction runs on the device
+    (icikt_edges_f64), its cost and its memory follow the number of edges, not S x S; a matrix has at most 65 535 samples.
+
+    ``max_edges=None`` returns every edge: the first call has room for ``max(2**20, 32 S)`` of them, and when there are
+    more the call is repeated ONCE with room for all -- the whole computation twice, with the same result (it is a pure
+    function of the input); pass a ``max_edges`` that fits to avoid that.  An explicit ``max_edges`` truncates the list
+    in ``combn`` order; ``n_edges`` and ``degree`` still count every matching pair.
+
+    Returns a dict: ``s1``, ``s2`` (the samples' names), ``i``, ``j`` (their indices), ``cor, raw, pvalue, taumax,
+    completeness`` (one value per edge), ``n_edges``, ``degree`` (S: matching pairs per sample), ``max_taumax`` and
+    ``run_time``.  ``formats.edges_to_coo`` turns it into a sparse matrix.  The reference's warning is raised once per
+    pair whose ``raw`` is NA for reasons 2-4, as ``ici_kendalltau_topk`` raises it.
+    """
+    min_raw = _edge_bound(min_raw, "min_raw")
+    max_pvalue = _edge_bound(max_pvalue, "max_pvalue")
+    min_completeness = _edge_bound(min_completeness, "min_completeness")
+    if max_edges is not None and (isinstance(max_edges, (bool, np.bool_)) or not isinstance(max_edges, (int, np.integer))
+                                  or int(max_edges) < 0):
+        raise ValueError("`max_edges` must be a non-negative integer or None")
+    data_matrix, names = _as_matrix(data_matrix, colnames, "data_matrix", keep_dtype=True, keep_sparse=True)
+    n_sample = data_matrix.shape[1]
+    if n_sample < 2:
+        raise ValueError("No comparisons to do. Check the list of column names in "
+                         "`include_only` vs those in the samples.")  # R/kendalltau.R:240-247
+    total = n_sample * (n_sample - 1) // 2
+    eng = engine or _default_engine()
+    if hasattr(eng, "edges"):
+        n_finite = len({float(v) for v in np.atleast_1d(np.asarray([] if global_na is None else global_na,
+                                                                     dtype=np.float64)) if math.isfinite(v)})
+        X = data_matrix
+        if n_finite > _lib.MASK_VALS:   # more values than the device-side rule holds: masked here, NaN passed
+            if _lib.is_sparse(X):
+                X = _densify(X)
+            X = np.asarray(X, dtype=np.float64)
+            X = _masked_fortran(X, setup_missing_matrix(X, global_na))
+            global_na = (float("nan"),)
+        Xe = _for_engine(X, eng, fortran=False)
+        room = min(total, max(EDGES_DEFAULT_CAPACITY, EDGES_CAPACITY_PER_SAMPLE * n_sample)) if max_edges is None else int(max_edges)
+        t1 = time.perf_counter()
+        out = eng.edges(Xe, min_raw, max_pvalue, min_completeness, absolute, room, global_na, perspective, alternative,
+                        continuity, 0, scale_max)
+        if max_edges is None and out[3] > room:   # the second call is exact: the count does not depend on the room
+            out = eng.edges(Xe, min_raw, max_pvalue, min_completeness, absolute, out[3], global_na, perspective,
+                            alternative, continuity, 0, scale_max)
+        t_diff = time.perf_counter() - t1
+        ei, ej, vals, n_edges, degree, max_taumax, rcounts = out
+        for code in (_lib.REASON_SHORT, _lib.REASON_SINGLE_UNIQUE, _lib.REASON_TIES_EQ_TOTAL):
+            for _ in range(int(rcounts[code])):   # one warning per offending pair, as ici_split raises them
+                _warn_reason(code)
+    else:
+        full = ici_kendalltau(data_matrix, global_na=global_na, perspective=perspective, scale_max=scale_max,
+                              diag_good=True, alternative=alternative, continuity=continuity, colnames=names, engine=eng)
+        t_diff = full["run_time"]
+        ei, ej, vals, degree = _edges_numpy([np.asarray(full[key]) for key in _TOPK_KEYS], min_raw, max_pvalue,
+                                            min_completeness, absolute)
+        n_edges = int(ei.shape[0])
+        if max_edges is not None:
+            ei, ej, vals = ei[:int(max_edges)], ej[:int(max_edges)], vals[:, :int(max_edges)]
+        iu = np.triu_indices(n_sample, k=1)
+        have = _na_rm(np.asarray(full["taumax"])[iu])
+        max_taumax = float(have.max()) if have.size else -math.inf
+    names_arr = np.asarray(list(names), dtype=object)
+    res = {"s1": names_arr[ei], "s2": names_arr[ej], "i": ei, "j": ej}
+    for q, key in enumerate(_TOPK_KEYS):
+        res[key] = vals[q]
+    res["n_edges"] = int(n_edges)
+    res["degree"] = degree
     res["max_taumax"] = max_taumax
     res["run_time"] = t_diff
     return res

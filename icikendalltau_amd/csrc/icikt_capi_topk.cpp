@@ -20,32 +20,12 @@ using icikt::host::MatrixSrc;
 using icikt::host::timer_begin;
 using icikt::host::timer_end;
 
+using icikt::host::cut_rows;
+using icikt::host::row_offset;
+
 namespace {
 
-// Pairs of a block of whole rows when no tkblock key says otherwise.  2^24 pairs fill the chip (256 CUs x at most 32
-// waves x 2 pairs: 16 384 pairs in flight) a thousand times over, so a block's launch tail is lost in its body, and
-// the buffers of a block -- out4 32 B, the pair kernel's counts 24, pi / pj 8, the task list 8, reasons 4 per pair, a
-// ninth on top for the buffers' growth margin -- stay at 1.4 GB.  The whole triangle of up to 5 793 columns is ONE block.
-constexpr int64_t kTopkBlockPairs = (int64_t)1 << 24;
-
-// rows [a, b) of the combn triangle per block: the largest run from a within the budget, at least one row; a run of
-// several rows ends on an even row (the next block then starts on one: the pair kernel's tasks pair the rows 2a, 2a + 1)
-std::vector<std::pair<int, int>> cut_rows(int64_t S, int64_t budget) {
-  std::vector<std::pair<int, int>> blocks;
-  int64_t a = 0;
-  while (a < S - 1) {
-    int64_t b = a, pairs = 0;
-    while (b < S - 1 && (b == a || pairs + (S - 1 - b) <= budget)) { pairs += S - 1 - b; ++b; }
-    if (b < S - 1 && (b & 1) && b - a >= 2) --b;
-    blocks.emplace_back((int)a, (int)b);
-    a = b;
-  }
-  return blocks;
-}
-
-int64_t row_offset(int64_t S, int64_t i) { return i * (2 * S - i - 1) / 2; }
-
-// the body of the three entries
+// the body of the three entries (the block cut: cut_rows, icikt_host.h)
 int topk_src(icikt_ctx* c, const MatrixSrc& X, int64_t n_feat, int64_t n_samp, const double* global_na, int n_global_na,
              int k, int perspective, int alternative, int continuity, uint32_t flags, int scale_max, int32_t* idx,
              double* out5k, int32_t* n_valid, double* max_taumax, int64_t* reason_counts) {
@@ -72,7 +52,7 @@ int topk_src(icikt_ctx* c, const MatrixSrc& X, int64_t n_feat, int64_t n_samp, c
 
   const int64_t S = n_samp, total = S * (S - 1) / 2;
   const size_t SK = (size_t)S * (size_t)k;
-  const int64_t budget = c->plan_ov.tkblock > 0 ? c->plan_ov.tkblock : kTopkBlockPairs;
+  const int64_t budget = c->plan_ov.tkblock > 0 ? c->plan_ov.tkblock : icikt::host::kTriangleBlockPairs;
   const std::vector<std::pair<int, int>> blocks = cut_rows(S, budget);
   int64_t block_max = 1;
   for (const auto& b : blocks) block_max = std::max(block_max, row_offset(S, b.second) - row_offset(S, b.first));

@@ -1,6 +1,6 @@
 // icikt_device.h -- structures, layouts and launcher declarations shared by the device units (icikt_prepass.hip,
-// icikt_kernels.hip, icikt_epilogue.hip, icikt_cor.hip, icikt_diag.hip) and the C-ABI host side (icikt_capi*.cpp,
-// icikt_multi.cpp).  Internal; the public boundary is include/icikt.h.
+// icikt_kernels.hip, icikt_epilogue.hip, icikt_cor.hip, icikt_diag.hip, icikt_topk.hip, icikt_edges.hip) and the C-ABI
+// host side (icikt_capi*.cpp, icikt_multi.cpp).  Internal; the public boundary is include/icikt.h.
 #ifndef ICIKT_DEVICE_H
 #define ICIKT_DEVICE_H
 
@@ -232,6 +232,28 @@ hipError_t launch_topk_merge(const TopkLists& L, const double* out4, int S, int 
 // idx [S][k] (-1 padded), out5k [5][S][k] (NA_real_ padded), n_valid [S] (may be null); red: launch_out_stats' record
 hipError_t launch_topk_finish(const TopkLists& L, const unsigned long long* red, int S, int scale_max, int32_t* idx,
                               double* out5k, int32_t* n_valid, hipStream_t s);
+// ---- pairs past a threshold, compacted in combn order (icikt_edges.hip) ----
+struct EdgeRule {              // == icikt_edge_rule: a NaN bound is no bound
+  double min_raw, max_pvalue, min_completeness;
+  int absolute;
+};
+// the kept edges as planes of `cap` slots each: every store is a plain 4- or 8-byte one
+struct EdgeOut {
+  int32_t *ei, *ej;
+  double *cor, *raw, *pvalue, *taumax, *completeness;
+  long long cap;
+};
+// tiles of a block of n_pairs pairs: words of `counts` and `bases`, and a 16th of the words of `ballots`
+long long edge_tiles(long long n_pairs);
+constexpr int EDGE_TILE_WORDS = 16;
+// out4: the records of n_pairs consecutive pairs of combn(S, 2) from pair `first` on (S <= 65 535).  The block's matching
+// pairs are counted into *total (a device word the caller zeroes before a call's first block) and degree ([S], zeroed
+// likewise, may be null), and those whose rank among ALL matching pairs so far is below E.cap are stored at that rank.
+hipError_t launch_edge_block(const EdgeRule& R, const double* out4, long long n_pairs, long long first, int S,
+                             unsigned long long* ballots, uint32_t* counts, unsigned long long* bases,
+                             unsigned long long* total, unsigned long long* degree, const EdgeOut& E, hipStream_t s);
+// E.cor of the first n edges (n <= E.cap); red: launch_out_stats' record
+hipError_t launch_edge_finish(const EdgeOut& E, long long n, const unsigned long long* red, int scale_max, hipStream_t s);
 // wide columns: one wave per pair, grid of `blocks` single-wave workgroups that fetch pairs from *task_ctr
 hipError_t launch_k1_wide(const PrepView& pv, const int32_t* pi, const int32_t* pj, PairRaw* raw, int64_t n_pairs,
                           int blocks, size_t lds_bytes, int* task_ctr, hipStream_t s);

@@ -9,6 +9,7 @@
 #include <cstdint>
 #include <string>
 #include <functional>
+#include <utility>
 #include <vector>
 
 #include "icikt.h"
@@ -122,6 +123,15 @@ struct icikt_ctx {
     DevBuf<double> vals, out;
   } topk;
 
+  // pairs past a threshold (icikt_edges_f64): a block's ballot words, tile counts and tile bases, the running total
+  // (word 0 of `total`), the degrees and the planes of the kept edges
+  struct EdgeBufs {
+    DevBuf<unsigned long long> ballots, bases, total, degree;
+    DevBuf<uint32_t> counts;
+    DevBuf<int32_t> ei, ej;
+    DevBuf<double> vals;   // [5][cap]: cor, raw, pvalue, taumax, completeness
+  } edges;
+
   // missing-value diagnostics (icikt_col_medians_f64, icikt_censor_counts_f64, icikt_rank_order_f64)
   struct DiagBufs {
     DevBuf<double> median, medrank, out;
@@ -140,7 +150,7 @@ struct icikt_ctx {
     int split = -1;     // half-wave kernels: segments per task (1 | 2 | 4), whatever the launch's size
     int solo = -1;      // 0: SOLO steps of the tie program run as MIXED steps (with the in-step chains)
     int list = -1;      // list mode (range counts per listed tie group) up to this many tie groups: count mode takes over above
-    long long tkblock = -1;   // icikt_topk_*: pairs a block of whole combn rows may hold (default: the library's budget)
+    long long tkblock = -1;   // icikt_topk_* and icikt_edges_*: pairs a block of whole combn rows may hold (default: the library's budget)
     bool verbose = false;
   } plan_ov;
 
@@ -215,6 +225,29 @@ void prebuild_units(icikt_ctx* c);
 int check_pair_args(icikt_ctx* c, const char* who, const MatrixSrc& X, int64_t n_feat, int64_t n_samp,
                     const int32_t* pi, const int32_t* pj, int64_t* n_pairs, const void* out, bool out5,
                     int perspective, int alternative);
+
+// ---- the combn triangle in blocks of whole rows (icikt_topk_*, icikt_edges_*) ----
+// Pairs of a block of whole rows when no tkblock key says otherwise.  2^24 pairs fill the chip (256 CUs x at most 32
+// waves x 2 pairs: 16 384 pairs in flight) a thousand times over, so a block's launch tail is lost in its body, and
+// the buffers of a block -- out4 32 B, the pair kernel's counts 24, pi / pj 8, the task list 8, reasons 4 per pair, a
+// ninth on top for the buffers' growth margin -- stay at 1.4 GB.  The whole triangle of up to 5 793 columns is ONE block.
+constexpr int64_t kTriangleBlockPairs = (int64_t)1 << 24;
+// first pair of row i of combn(S, 2)
+inline int64_t row_offset(int64_t S, int64_t i) { return i * (2 * S - i - 1) / 2; }
+// rows [a, b) of the combn triangle per block: the largest run from a within the budget, at least one row; a run of
+// several rows ends on an even row (the next block then starts on one: the pair kernel's tasks pair the rows 2a, 2a + 1)
+inline std::vector<std::pair<int, int>> cut_rows(int64_t S, int64_t budget) {
+  std::vector<std::pair<int, int>> blocks;
+  int64_t a = 0;
+  while (a < S - 1) {
+    int64_t b = a, pairs = 0;
+    while (b < S - 1 && (b == a || pairs + (S - 1 - b) <= budget)) { pairs += S - 1 - b; ++b; }
+    if (b < S - 1 && (b & 1) && b - a >= 2) --b;
+    blocks.emplace_back((int)a, (int)b);
+    a = b;
+  }
+  return blocks;
+}
 
 }  // namespace host
 }  // namespace icikt

@@ -7,6 +7,7 @@
 * ``cor_matrix_2_long_df`` / ``long_df_2_cor_matrix``: the reference's converters between the square result
   matrices and the long data.frame storage form (R/reshaping.R:15-68).
 * ``topk_to_csr``: the result of ``ici_kendalltau_topk`` as a sparse samples x samples kNN graph (needs scipy).
+* ``edges_to_coo``: the result of ``ici_kendalltau_edges`` as a sparse samples x samples matrix (needs scipy).
 """
 from __future__ import annotations
 
@@ -260,3 +261,25 @@ def topk_to_csr(result, value="cor"):
     real = np.arange(k)[None, :] < n_valid[:, None]
     indptr = np.concatenate([[0], np.cumsum(n_valid)])
     return sp.csr_matrix((vals[real], idx[real].astype(np.int32), indptr), shape=(S, S))
+
+
+# --------------------------------------------------------------------------------------------------
+# ici_kendalltau_edges -> a sparse correlation network
+# --------------------------------------------------------------------------------------------------
+def edges_to_coo(result, value="cor", symmetric=True):
+    """The dict ``ici_kendalltau_edges`` returns as an S x S ``scipy.sparse.coo_matrix`` of ``result[value]``: every
+    edge at (i, j) and, with ``symmetric``, at (j, i) as well (the upper triangle alone otherwise); the diagonal is
+    empty.  S is the length of ``result["degree"]``.  scipy is optional for the package and needed here."""
+    try:
+        import scipy.sparse as sp
+    except ImportError as e:
+        raise ImportError("edges_to_coo needs scipy (optional for icikendalltau_amd, required for this converter)") from e
+    if value not in ("cor", "raw", "pvalue", "taumax", "completeness"):
+        raise ValueError("`value` must be one of cor, raw, pvalue, taumax, completeness")
+    S = len(result["degree"])
+    i = np.asarray(result["i"], dtype=np.int32)
+    j = np.asarray(result["j"], dtype=np.int32)
+    vals = np.asarray(result[value], dtype=np.float64)
+    if symmetric:
+        i, j, vals = np.concatenate([i, j]), np.concatenate([j, i]), np.concatenate([vals, vals])
+    return sp.coo_matrix((vals, (i, j)), shape=(S, S))

@@ -294,6 +294,43 @@ int icikt_topk_f64(icikt_ctx *ctx, const double *X, int64_t n_feat, int64_t n_sa
                    int scale_max, int32_t *idx, double *out5k, int32_t *n_valid, double *max_taumax,
                    int64_t *reason_counts);
 
+/* ---- every pair past a threshold, compacted on the device ------------------------------------------------------
+ *
+ * The edge list of a correlation network: every pair i < j of columns of X whose values pass `rule`, with the five
+ * values icikt_matrix_f64 reports for that pair -- without anything of size n_samp^2 on the device or the host.  The
+ * combn triangle runs through the pair engine in blocks of whole rows, as for icikt_topk_f64, and an ordered stream
+ * compaction appends each block's matching records to the kept ones (device memory: the prepared matrix, one block's
+ * buffers and 48 min(max_edges, C(n_samp, 2)) bytes of kept edges).
+ *   rule         a pair is an edge iff its raw is not NA (reason code 0) and every bound of the rule that is not NaN
+ *                holds, as a plain IEEE comparison of doubles: raw >= min_raw (fabs(raw) >= min_raw when absolute != 0),
+ *                pvalue <= max_pvalue, completeness >= min_completeness.  A NaN pvalue therefore fails a p-value bound
+ *                and passes when there is none.  The diagonal is never an edge.  The bounds apply to RAW, never to cor:
+ *                cor's denominator, max(taumax) over all pairs, is known only after the last block.
+ *   order        combn order: i ascending, then j ascending.  The order is strict, so the output is a pure function of
+ *                the input, whatever the block cut.
+ *   values       ei / ej: the pair's columns; out5e: [5][max_edges] planes cor, raw, pvalue, taumax, completeness;
+ *                cor = scale_max ? raw / max(taumax, na.rm = TRUE) : raw over ALL computed pairs, bit for bit the cell
+ *                of icikt_matrix_f64's matrices
+ *   capacity     *n_edges: the number of matching pairs, ALL of them; the first min(*n_edges, max_edges) are written,
+ *                the slots behind them are left untouched.  *n_edges > max_edges is no error: call again with room.
+ *                max_edges = 0 (ei, ej, out5e may then be null) only counts.
+ * degree (optional): [n_samp] matching pairs that contain the column, all of them whatever max_edges; max_taumax and
+ * reason_counts (optional): as icikt_topk_f64.  n_samp <= ICIKT_TOPK_MAX_SAMPLES (ICIKT_E_INVALID beyond, the message
+ * names the limit); n_feat, global_na, the state the call leaves behind (none: icikt_run_dev answers ICIKT_E_STATE and
+ * icikt_num_pairs -1) and the refusal of bad arguments before anything -- the context or an output -- is touched: as
+ * icikt_topk_f64.  With ICIKT_FLAG_TIMING the compaction kernels are accounted under ICIKT_K_EPILOGUE.
+ * icikt_edges_in / icikt_edges_csc: the same on a typed view / a CSC view of the matrix (below). */
+typedef struct icikt_edge_rule {
+  double min_raw;           /* NaN: no bound.  raw >= min_raw; with absolute != 0: fabs(raw) >= min_raw */
+  double max_pvalue;        /* NaN: no bound.  pvalue <= max_pvalue */
+  double min_completeness;  /* NaN: no bound.  completeness >= min_completeness */
+  int absolute;
+} icikt_edge_rule;
+int icikt_edges_f64(icikt_ctx *ctx, const double *X, int64_t n_feat, int64_t n_samp, int64_t ld, const double *global_na,
+                    int n_global_na, const icikt_edge_rule *rule, int perspective, int alternative, int continuity,
+                    uint32_t flags, int scale_max, int64_t max_edges, int32_t *ei, int32_t *ej, double *out5e,
+                    int64_t *n_edges, int64_t *degree, double *max_taumax, int64_t *reason_counts);
+
 /* ---- several GPUs behind one call (what the R glue binds when n_gpu > 1) ----------------------
  *
  * Replaces the reference's worker fan-out, computation$split_fun(split_comparisons, ici_split, ...)
@@ -437,6 +474,10 @@ int icikt_pairs_in(icikt_ctx *ctx, const icikt_input *X, int64_t n_feat, int64_t
 int icikt_topk_in(icikt_ctx *ctx, const icikt_input *X, int64_t n_feat, int64_t n_samp, const double *global_na,
                   int n_global_na, int k, int perspective, int alternative, int continuity, uint32_t flags, int scale_max,
                   int32_t *idx, double *out5k, int32_t *n_valid, double *max_taumax, int64_t *reason_counts);
+int icikt_edges_in(icikt_ctx *ctx, const icikt_input *X, int64_t n_feat, int64_t n_samp, const double *global_na,
+                   int n_global_na, const icikt_edge_rule *rule, int perspective, int alternative, int continuity,
+                   uint32_t flags, int scale_max, int64_t max_edges, int32_t *ei, int32_t *ej, double *out5e,
+                   int64_t *n_edges, int64_t *degree, double *max_taumax, int64_t *reason_counts);
 int icikt_matrix_in(icikt_ctx *ctx, const icikt_input *X, int64_t n_feat, int64_t n_samp, const double *global_na,
                     int n_global_na, const int32_t *pi, const int32_t *pj, int64_t n_pairs, int perspective,
                     int alternative, int continuity, uint32_t flags, int scale_max, int diag_good, double *out5,
@@ -485,6 +526,10 @@ int icikt_matrix_csc(icikt_ctx *ctx, const icikt_csc_input *X, int64_t n_feat, i
 int icikt_topk_csc(icikt_ctx *ctx, const icikt_csc_input *X, int64_t n_feat, int64_t n_samp, const double *global_na,
                    int n_global_na, int k, int perspective, int alternative, int continuity, uint32_t flags, int scale_max,
                    int32_t *idx, double *out5k, int32_t *n_valid, double *max_taumax, int64_t *reason_counts);
+int icikt_edges_csc(icikt_ctx *ctx, const icikt_csc_input *X, int64_t n_feat, int64_t n_samp, const double *global_na,
+                    int n_global_na, const icikt_edge_rule *rule, int perspective, int alternative, int continuity,
+                    uint32_t flags, int scale_max, int64_t max_edges, int32_t *ei, int32_t *ej, double *out5e,
+                    int64_t *n_edges, int64_t *degree, double *max_taumax, int64_t *reason_counts);
 int icikt_missingness_csc(icikt_ctx *ctx, const icikt_csc_input *X, int64_t n_feat, int64_t n_samp, const int32_t *pi,
                           const int32_t *pj, int64_t n_pairs, int64_t *missingness);
 int icikt_col_medians_csc(icikt_ctx *ctx, const icikt_csc_input *X, int64_t n_feat, int64_t n_samp,
@@ -516,7 +561,7 @@ int icikt_selftest(icikt_ctx *ctx);
  * pairs' counter tables may cost the launch occupancy), split (1 | 2 | 4: segments a half-wave task is cut in, whatever the
  * launch's size), merge (0 | 1: the pipelined host entries' pairs in a launch per chunk | in one launch behind the last chunk), gridmult / gridcap (persistent grid of the long-column kernel: a
  * multiple of the resident workgroups / at most this many), pipe (0 | 1: the host entries' chunk pipeline), k0 (0 | 1: the
- * pre-pass always in its 1 024-thread / 256-thread shape), tkblock (icikt_topk_*: the pairs a block of whole combn rows
+ * pre-pass always in its 1 024-thread / 256-thread shape), tkblock (icikt_topk_* and icikt_edges_*: the pairs a block of whole combn rows
  * may hold -- a block is always at least one row, so tkblock=1 runs a row per block), verbose (0 | 1: print the chosen
  * plan to stderr). */
 int icikt_debug_set_plan(icikt_ctx *ctx, const char *spec);
