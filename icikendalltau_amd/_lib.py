@@ -18,7 +18,8 @@ SOURCES = [os.path.join(_PKG, "csrc", f) for f in ("icikt_kernels.hip", "icikt_p
                                                        "icikt_capi.cpp", "icikt_capi_cor.cpp", "icikt_capi_diag.cpp",
                                                        "icikt_multi.cpp", "icikt_transfer.cpp", "icikt_cor.hip", "icikt_topk.hip",
                                                        "icikt_capi_topk.cpp", "icikt_edges.hip", "icikt_capi_edges.cpp",
-                                                       "icikt_diag.hip", "icikt_ingest.hip", "icikt_sparse.hip")]
+                                                       "icikt_diag.hip", "icikt_ingest.hip", "icikt_sparse.hip",
+                                                       "icikt_medians.hip", "icikt_capi_medians.cpp")]
 HEADERS = [os.path.join(_ROOT, "include", "icikt.h"), os.path.join(_PKG, "csrc", "icikt_device.h"),
            os.path.join(_PKG, "csrc", "icikt_wave.h"), os.path.join(_PKG, "csrc", "icikt_host.h"),
            os.path.join(_PKG, "csrc", "icikt_transfer.h"), os.path.join(_PKG, "csrc", "icikt_colsort.h")]
@@ -70,6 +71,7 @@ EXPORTS = (
     "icikt_rank_order_csc", "icikt_scatter_csc_dev",
     "icikt_topk_f64", "icikt_topk_in", "icikt_topk_csc",
     "icikt_edges_f64", "icikt_edges_in", "icikt_edges_csc",
+    "icikt_class_medians_f64", "icikt_class_medians_in", "icikt_class_medians_csc",
 )
 
 # icikt_input: the caller's matrix as a typed, strided view (ICIKT_DTYPE_*, ICIKT_ORDER_*)
@@ -354,17 +356,20 @@ def lib():
                                  c_vp, c_vp, c_vp, c_vp, c_vp]
     L.icikt_edges_f64.argtypes = [c_vp, c_vp, c_i64, c_i64, c_i64, c_vp, c_int, ctypes.POINTER(EdgeRule), c_int, c_int,
                                   c_int, c_u32, c_int, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]
+    L.icikt_class_medians_f64.argtypes = [c_vp, c_vp, c_i64, c_i64, c_i64, c_vp, c_int, c_vp, c_int, c_int, c_int, c_int,
+                                          c_u32, c_int, c_vp, c_vp, c_vp, c_vp]
     L.icikt_multi_rank_phase_ms.argtypes = [c_vp, c_int, ctypes.POINTER(ctypes.c_double)]
     L.icikt_multi_ranks_used.argtypes = [c_vp]
     L.icikt_debug_step_stats.argtypes = [c_vp, c_vp, c_int]
     # the *_in twins: (ctx, const icikt_input*, n_feat, n_samp, ...) where the _f64 entry has (ctx, X, n_feat, n_samp, ld, ...)
     for nm in ("pairs", "matrix", "pairs_complete", "missingness", "cor_pairs", "col_medians", "censor_counts",
-               "rank_order", "topk", "edges"):
+               "rank_order", "topk", "edges", "class_medians"):
         f64 = getattr(L, f"icikt_{nm}_f64").argtypes
         getattr(L, f"icikt_{nm}_in").argtypes = [c_vp, ctypes.POINTER(InputView), c_i64, c_i64] + list(f64[5:])
     L.icikt_convert_dev.argtypes = [c_vp, c_vp, c_int, c_int, c_i64, c_i64, c_i64, c_vp, c_i64]
     # the *_csc twins: (ctx, const icikt_csc_input*, n_feat, n_samp, ...)
-    for nm in ("pairs", "matrix", "missingness", "col_medians", "censor_counts", "rank_order", "topk", "edges"):
+    for nm in ("pairs", "matrix", "missingness", "col_medians", "censor_counts", "rank_order", "topk", "edges",
+               "class_medians"):
         f64 = getattr(L, f"icikt_{nm}_f64").argtypes
         getattr(L, f"icikt_{nm}_csc").argtypes = [c_vp, ctypes.POINTER(CscInput), c_i64, c_i64] + list(f64[5:])
     L.icikt_scatter_csc_dev.argtypes = [c_vp, c_vp, c_vp, c_vp, c_int, c_int, ctypes.c_double, c_i64, c_i64, c_vp, c_i64]
@@ -640,6 +645,33 @@ class Context:
                      int(bool(continuity)), flags, int(bool(scale_max)), _ptr(idx), _ptr(vals), _ptr(n_valid), _ptr(mx),
                      _ptr(rc5)), fname)
         return idx, vals, n_valid, float(mx[0]), rc5
+
+    def class_medians(self, X, cls=None, n_class=1, global_na=None, perspective="global", alternative="two.sided",
+                      continuity=False, flags: int = 0, scale_max=True):
+        """Every sample's median ICI-Kendall-tau over the other samples of its class, reduced on the device
+        (icikt_class_medians_f64): only the within-class pairs are computed, and nothing of size S x S exists on either
+        side.  cls: a class index in 0 .. n_class - 1 per column (None: one class); X and global_na as matrix() takes
+        them.  Returns (med2 [2, S]: cor, raw -- NA_real_ for a sample without a valid partner; n_valid [S];
+        max_taumax: the largest taumax of the COMPUTED pairs, cor's denominator; reason_counts [5] over those pairs).
+        The argument checks are the library's: a class index out of range or a bad perspective raises IciktError."""
+        fn, fname, xargs, n_feat, n_samp, flags, _keep = self._entry("class_medians", X, flags)
+        if cls is None:
+            cls_a = None
+        else:
+            cls_a = np.ascontiguousarray(cls, dtype=np.int32)
+            if cls_a.shape != (n_samp,):
+                raise ValueError("cls must give one class per column")
+        gna = np.ascontiguousarray([] if global_na is None else np.atleast_1d(global_na), dtype=np.float64)
+        med2 = np.empty((2, n_samp), dtype=np.float64)
+        n_valid = np.zeros(n_samp, dtype=np.int32)
+        mx = np.full(1, -np.inf)
+        rc5 = np.zeros(5, dtype=np.int64)
+        persp = PERSPECTIVE.get(perspective, perspective if isinstance(perspective, int) else -1)
+        alt = ALTERNATIVE.get(alternative, ALT_OTHER)
+        self._chk(fn(self._h, *xargs, _ptr(gna) if gna.size else None, int(gna.size), _ptr(cls_a), int(n_class), persp,
+                     alt, int(bool(continuity)), flags, int(bool(scale_max)), _ptr(med2), _ptr(n_valid), _ptr(mx),
+                     _ptr(rc5)), fname)
+        return med2, n_valid, float(mx[0]), rc5
 
     def edges(self, X, min_raw=None, max_pvalue=None, min_completeness=None, absolute=False, max_edges=0,
               global_na=None, perspective="global", alternative="two.sided", continuity=False, flags: int = 0,

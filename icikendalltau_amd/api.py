@@ -70,6 +70,13 @@ class HipEngine:
         return self.ctx.edges(data_matrix, min_raw, max_pvalue, min_completeness, absolute, max_edges, global_na,
                               perspective, alternative, continuity, self.flags | flags, scale_max)
 
+    def class_medians(self, data_matrix, cls=None, n_class=1, global_na=None, perspective="global",
+                      alternative="two.sided", continuity=False, flags=0, scale_max=True):
+        """Every sample's median over its class, reduced on the device (icikt_class_medians_f64): Context.class_medians'
+        contract."""
+        return self.ctx.class_medians(data_matrix, cls, n_class, global_na, perspective, alternative, continuity,
+                                      self.flags | flags, scale_max)
+
     def cor_pairs(self, X, pi, pj, method, pairwise, alternative, continuity):
         """cor_fast's pairs on the device (icikt_cor_pairs_f64): (out3: rho, p-value, n_values; reasons)."""
         return self.ctx.cor_pairs(X, pi, pj, method, pairwise, alternative, continuity)
@@ -163,6 +170,11 @@ class MultiHipEngine(HipEngine):
               scale_max=True):  # the compaction runs on one device
         return self._one().edges(data_matrix, min_raw, max_pvalue, min_completeness, absolute, max_edges, global_na,
                                  perspective, alternative, continuity, self.flags | flags, scale_max)
+
+    def class_medians(self, data_matrix, cls=None, n_class=1, global_na=None, perspective="global",
+                      alternative="two.sided", continuity=False, flags=0, scale_max=True):  # the reduction runs on one device
+        return self._one().class_medians(data_matrix, cls, n_class, global_na, perspective, alternative, continuity,
+                                         self.flags | flags, scale_max)
 
     def pairs_complete(self, X, pi, pj):  # kt_fast's per-pair masking path exists on one device only
         out, _cnt, rsn = self._one().pairs_complete(X, pi, pj, "two.sided", False, self.flags)
@@ -747,6 +759,124 @@ def ici_kendalltau_topk(data_matrix, k, global_na=(float("nan"), float("inf"), 0
     res["max_taumax"] = max_taumax
     res["run_time"] = t_diff
     return res
+
+
+# --------------------------------------------------------------------------------------------------
+# ici_kendalltau_medians: every sample's median ICI-Kendall-tau over the other samples of its class (the outlier
+# screen the matrix is computed for; the reference leaves the reduction to the user)
+# --------------------------------------------------------------------------------------------------
+def _r_median_pair(a, b):
+    """R's mean() of the two middle values, a zero as +0 (the even branch of _r_median_sorted)."""
+    s = a + b
+    if math.isfinite(s):
+        return 0.5 * s + 0.0
+    if math.isfinite(a) and math.isfinite(b):
+        return 0.5 * a + 0.5 * b + 0.0
+    return float(np.array([0x7FF8000000000000], dtype=np.uint64).view(np.float64)[0]) if math.isnan(s) else s
+
+
+def _class_medians_numpy(cor, raw, cls):
+    """The reduction of icikt_class_medians_f64 from full S x S cor and raw matrices, for engines without a
+    class_medians method (the CPU tests' checker engines).  The partners of sample s are the other samples of its class
+    whose raw with s is not NA; n_valid[s] counts them.  med_raw[s] is R's median(raw, na.rm = TRUE) over them: with the
+    values sorted ascending (a zero counts as +0), the middle one, or the mean of the two middle ones; med_cor[s] is
+    the same rule on the cor cells of the partners that supplied those middle raw values.  Without partners both are
+    NA_real_.  Returns (med2 [2, S]: cor, raw; n_valid [S])."""
+    cor = np.ascontiguousarray(cor, dtype=np.float64)
+    raw = np.ascontiguousarray(raw, dtype=np.float64)
+    cls = np.asarray(cls)
+    S = raw.shape[0]
+    med2 = np.empty((2, S), dtype=np.float64)
+    med2.view(np.uint64)[...] = _NA_REAL_BITS
+    n_valid = np.zeros(S, dtype=np.int32)
+    for s in range(S):
+        ok = (cls == cls[s]) & ~np.isnan(raw[s])
+        ok[s] = False
+        partners = np.nonzero(ok)[0]
+        v = len(partners)
+        n_valid[s] = v
+        if v == 0:
+            continue
+        order = np.argsort(raw[s, partners] + 0.0, kind="stable")
+        mid = partners[order[[(v - 1) // 2, v // 2]]]       # (twice the same partner when v is odd)
+        for q, mat in ((1, raw), (0, cor)):
+            a, b = float(mat[s, mid[0]]) + 0.0, float(mat[s, mid[1]]) + 0.0
+            med2[q, s] = a if v & 1 else _r_median_pair(a, b)
+    return med2, n_valid
+
+
+def ici_kendalltau_medians(data_matrix, sample_classes=None, global_na=(float("nan"), float("inf"), 0),
+                           perspective="global", scale_max=True, alternative="two.sided", continuity=False,
+                           colnames=None, engine=None):
+    """For every sample (column) of a features x samples matrix the median ICI-Kendall-tau to the other samples of its
+    class: the outlier screen of a quality-control run, without the S x S matrices ``ici_kendalltau`` returns and
+    without computing a pair that crosses classes.
+
+    ``sample_classes`` gives one label per column (None: one class); the other arguments are ``ici_kendalltau``'s
+    (column names are required; a sparse matrix, float32 and integer matrices are read where they lie).  On the HIP
+    engine the reduction runs on the device (icikt_class_medians_f64); a matrix has at most 65 535 samples.
+
+    The partners of a sample are the other samples of its class whose pair with it has a ``raw`` that is not NA (the
+    reference's warning is raised once per pair of reasons 2-4).  ``med_raw`` is R's ``median(raw, na.rm = TRUE)`` over
+    them, and ``med_cor`` the same over ``cor``.  With ``scale_max`` ``cor`` is ``raw`` over the largest ``taumax`` of
+    the COMPUTED, that is within-class, pairs -- what ``ici_kendalltau(include_only = <those pairs>)`` scales by, not
+    the maximum over all S (S - 1) / 2 pairs; ``med_raw`` does not depend on it.  A sample without a partner (a
+    singleton class among them) gets NA.  Returns a dict: ``sample_id`` and ``sample_class`` (names and labels in
+    column order), ``med_cor``, ``med_raw``, ``n_valid`` (S each), ``max_taumax`` (-inf when no pair was computed) and
+    ``run_time``.
+    """
+    data_matrix, names = _as_matrix(data_matrix, colnames, "data_matrix", keep_dtype=True, keep_sparse=True)
+    n_sample = data_matrix.shape[1]
+    levels, cls = _class_levels(sample_classes, n_sample, "all")
+    if n_sample < 2:
+        raise ValueError("No comparisons to do. Check the list of column names in "
+                         "`include_only` vs those in the samples.")  # R/kendalltau.R:240-247
+    eng = engine or _default_engine()
+    if hasattr(eng, "class_medians"):
+        n_finite = len({float(v) for v in np.atleast_1d(np.asarray([] if global_na is None else global_na,
+                                                                     dtype=np.float64)) if math.isfinite(v)})
+        X = data_matrix
+        if n_finite > _lib.MASK_VALS:   # more values than the device-side rule holds: masked here, NaN passed
+            if _lib.is_sparse(X):
+                X = _densify(X)
+            X = np.asarray(X, dtype=np.float64)
+            X = _masked_fortran(X, setup_missing_matrix(X, global_na))
+            global_na = (float("nan"),)
+        t1 = time.perf_counter()
+        med2, n_valid, max_taumax, rcounts = eng.class_medians(_for_engine(X, eng, fortran=False), cls, len(levels),
+                                                               global_na, perspective, alternative, continuity, 0,
+                                                               scale_max)
+        t_diff = time.perf_counter() - t1
+        for code in (_lib.REASON_SHORT, _lib.REASON_SINGLE_UNIQUE, _lib.REASON_TIES_EQ_TOTAL):
+            for _ in range(int(rcounts[code])):   # one warning per offending pair, as ici_split raises them
+                _warn_reason(code)
+    else:
+        # the within-class pairs, class by class, combn order inside a class
+        first, second = [], []
+        for k in range(len(levels)):
+            members = np.nonzero(cls == k)[0]
+            a, b = np.triu_indices(len(members), k=1)
+            first.extend(names[i] for i in members[a])
+            second.extend(names[i] for i in members[b])
+        if first:
+            full = ici_kendalltau(data_matrix, global_na=global_na, perspective=perspective, scale_max=scale_max,
+                                  diag_good=True, include_only=[first, second], alternative=alternative,
+                                  continuity=continuity, colnames=names, engine=eng)
+            t_diff = full["run_time"]
+            cor, raw, taumax = (np.asarray(full[key], dtype=np.float64) for key in ("cor", "raw", "taumax"))
+            med2, n_valid = _class_medians_numpy(cor, raw, cls)
+            same = (cls[:, None] == cls[None, :]) & np.triu(np.ones((n_sample, n_sample), dtype=bool), k=1)
+            have = _na_rm(taumax[same])
+            max_taumax = float(have.max()) if have.size else -math.inf
+        else:   # singletons alone: nothing to compute
+            t_diff = 0.0
+            med2 = np.empty((2, n_sample), dtype=np.float64)
+            med2.view(np.uint64)[...] = _NA_REAL_BITS
+            n_valid = np.zeros(n_sample, dtype=np.int32)
+            max_taumax = -math.inf
+    labels = [levels[k] for k in cls]
+    return {"sample_id": list(names), "sample_class": labels, "med_cor": med2[0], "med_raw": med2[1],
+            "n_valid": n_valid, "max_taumax": max_taumax, "run_time": t_diff}
 
 
 # --------------------------------------------------------------------------------------------------

@@ -1729,6 +1729,7 @@ extern "C" {
 // grid: at most this many workgroups),
 // pipe (0 | 1: the host entries' chunk pipeline off / on whenever possible), k0 (0 | 1: the pre-pass always in its
 // 1 024-thread / 256-thread shape), tkblock (icikt_topk_* / icikt_edges_*: pairs per block of whole combn rows; 1 = a row per block),
+// medlds (icikt_class_medians_*: partners up to which the select kernel stages a sample's keys in LDS, 0 .. 4096),
 // verbose (0 | 1: print the plan to stderr).
 // (The keys h2d and regfail of rounds 2-3 are gone with the mode they steered: the library no longer page-locks
 // caller memory, icikt_host.h.)
@@ -1765,6 +1766,11 @@ int icikt_debug_set_plan(icikt_ctx* c, const char* spec) {
     else if (key == "pipe") pipe = (val[0] == '1') ? 1 : 0;
     else if (key == "k0") k0 = (val[0] == '1') ? 1 : 0;
     else if (key == "tkblock") ov.tkblock = atoll(val.c_str());
+    else if (key == "medlds") {
+      ov.medlds = atoi(val.c_str());
+      if (ov.medlds < 0 || ov.medlds > icikt::MEDIAN_STAGE_MAX)
+        return fail(c, ICIKT_E_INVALID, "debug_set_plan: medlds must be in 0 .. 4096 keys");
+    }
     else return fail(c, ICIKT_E_INVALID, "debug_set_plan: unknown key '" + key + "'");
   }
   c->plan_ov = ov;

@@ -1,5 +1,5 @@
 // icikt_device.h -- structures, layouts and launcher declarations shared by the device units (icikt_prepass.hip,
-// icikt_kernels.hip, icikt_epilogue.hip, icikt_cor.hip, icikt_diag.hip, icikt_topk.hip, icikt_edges.hip) and the C-ABI
+// icikt_kernels.hip, icikt_epilogue.hip, icikt_cor.hip, icikt_diag.hip, icikt_topk.hip, icikt_edges.hip, icikt_medians.hip) and the C-ABI
 // host side (icikt_capi*.cpp, icikt_multi.cpp).  Internal; the public boundary is include/icikt.h.
 #ifndef ICIKT_DEVICE_H
 #define ICIKT_DEVICE_H
@@ -254,6 +254,22 @@ hipError_t launch_edge_block(const EdgeRule& R, const double* out4, long long n_
                              unsigned long long* total, unsigned long long* degree, const EdgeOut& E, hipStream_t s);
 // E.cor of the first n edges (n <= E.cap); red: launch_out_stats' record
 hipError_t launch_edge_finish(const EdgeOut& E, long long n, const unsigned long long* red, int scale_max, hipStream_t s);
+// ---- per-sample medians within classes (icikt_medians.hip) ----
+// Where a sample's partners lie in the kept plane: its class has size[s] members (ascending sample index), the sample
+// is member pos[s], and the class's combn triangle starts at pair base[s] of the call's pair order.
+struct MedianClasses {
+  const int32_t* pos;    // [S]
+  const int32_t* size;   // [S]
+  const long long* base; // [S]
+};
+constexpr int MEDIAN_STAGE_MAX = 4096;   // keys of k_median_select's LDS staging buffer (32 KB: four workgroups per CU)
+// kept[e] = the sortable key (colsort::cor_key) of pair e's raw, NA_KEY for a pair with a reason code; e < n_pairs
+hipError_t launch_median_keep(const double* out4, const int32_t* reasons, long long n_pairs, unsigned long long* kept,
+                              hipStream_t s);
+// med2 [2][S] (cor, raw; NA_real_ without partners), n_valid [S]; red: launch_out_stats' record; stage: partners up to
+// which a sample's keys are gathered into LDS once (0 .. MEDIAN_STAGE_MAX), above it every pass re-reads the plane
+hipError_t launch_median_select(const MedianClasses& mc, const unsigned long long* kept, const unsigned long long* red,
+                                int S, int scale_max, int stage, double* med2, int32_t* n_valid, hipStream_t s);
 // wide columns: one wave per pair, grid of `blocks` single-wave workgroups that fetch pairs from *task_ctr
 hipError_t launch_k1_wide(const PrepView& pv, const int32_t* pi, const int32_t* pj, PairRaw* raw, int64_t n_pairs,
                           int blocks, size_t lds_bytes, int* task_ctr, hipStream_t s);

@@ -132,6 +132,15 @@ struct icikt_ctx {
     DevBuf<double> vals;   // [5][cap]: cor, raw, pvalue, taumax, completeness
   } edges;
 
+  // per-sample medians within classes (icikt_class_medians_f64): the kept plane (a key per computed pair), the
+  // samples' places in their classes (MedianClasses) and the results
+  struct MedianBufs {
+    DevBuf<unsigned long long> kept;
+    DevBuf<int32_t> pos, size, n_valid;
+    DevBuf<long long> base;
+    DevBuf<double> med2;
+  } med;
+
   // missing-value diagnostics (icikt_col_medians_f64, icikt_censor_counts_f64, icikt_rank_order_f64)
   struct DiagBufs {
     DevBuf<double> median, medrank, out;
@@ -151,6 +160,7 @@ struct icikt_ctx {
     int solo = -1;      // 0: SOLO steps of the tie program run as MIXED steps (with the in-step chains)
     int list = -1;      // list mode (range counts per listed tie group) up to this many tie groups: count mode takes over above
     long long tkblock = -1;   // icikt_topk_* and icikt_edges_*: pairs a block of whole combn rows may hold (default: the library's budget)
+    int medlds = -1;          // icikt_class_medians_*: partners up to which the select kernel gathers a sample's keys into LDS (default: MEDIAN_STAGE_MAX)
     bool verbose = false;
   } plan_ov;
 

@@ -331,6 +331,44 @@ int icikt_edges_f64(icikt_ctx *ctx, const double *X, int64_t n_feat, int64_t n_s
                     uint32_t flags, int scale_max, int64_t max_edges, int32_t *ei, int32_t *ej, double *out5e,
                     int64_t *n_edges, int64_t *degree, double *max_taumax, int64_t *reason_counts);
 
+/* ---- per-sample median ICI-Kendall-tau within classes, reduced on the device --------------------------------------
+ *
+ * The quality-control figure the matrix is made for: for every column (sample) s of X the median of raw (and of cor)
+ * over the other samples of its class -- without anything of size n_samp^2 on the device or the host, and without
+ * computing a pair that crosses classes.  The within-class pairs run through the pair engine in blocks; a kernel
+ * keeps each pair's raw as a sortable 64-bit key, and after the last block a selection kernel finds every sample's
+ * median by a radix select over its partners' keys.
+ *   classes      cls[s] in 0 .. n_class - 1 per sample; cls == NULL: one class (n_class is then ignored).  A class may
+ *                be empty.  A class index outside the range is ICIKT_E_INVALID, found before anything is touched.
+ *   pairs        only pairs i < j with cls[i] == cls[j], listed class by class in class-index order, inside a class in
+ *                combn order over its members by ascending sample index (one class: the combn triangle)
+ *   partners     of sample s: the other members of its class whose pair with s has reason code 0 (raw is not NA);
+ *                n_valid[s] is their count
+ *   med_raw      R's median(raw, na.rm = TRUE) over the partners: the middle value, or the mean of the two middle
+ *                values, a zero returned as +0; NA_real_ (bits 0x7FF00000000007A2) when n_valid[s] == 0, which covers
+ *                singleton classes
+ *   med_cor      the same rule on a / m (and b / m) for the one or two middle raw values a (and b), m = scale_max ?
+ *                max(taumax, na.rm = TRUE) over the COMPUTED pairs : 1 -- the operands are bit for bit the cor cells of
+ *                icikt_matrix_f64 called with that pair list.  m is the WITHIN-CLASS maximum, not the maximum over all
+ *                C(n_samp, 2) pairs; med_raw does not depend on it.  Without scale_max med_cor equals med_raw.
+ * med2: [2][n_samp], cor then raw; n_valid (optional): [n_samp]; max_taumax (optional): m, -Inf when no pair was computed;
+ * reason_counts (optional): [5] computed pairs per reason code.  n_samp <= ICIKT_TOPK_MAX_SAMPLES (ICIKT_E_INVALID
+ * beyond, the message names the limit); n_feat, global_na, the state the call leaves behind (none: icikt_run_dev
+ * answers ICIKT_E_STATE and icikt_num_pairs -1) and the refusal of bad arguments before anything -- the context or an
+ * output -- is touched: as icikt_topk_f64.
+ * One class runs in blocks of whole combn rows (the tkblock budget, as icikt_topk_f64); several classes as an explicit
+ * pair list in slices of the same budget, each slice's pi / pj generated on the host when its turn comes (host memory
+ * O(block)).  Device memory: the prepared matrix, one block's buffers, 8 bytes per computed pair for the kept keys
+ * (sum over the classes of m (m - 1) / 2 pairs; one class of 65 535 samples: 17 GB) and 36 n_samp bytes of index
+ * arrays (position in class, class size, first pair of the class as int64: 16) and results (20); a failed allocation
+ * is ICIKT_E_HIP.
+ * With ICIKT_FLAG_TIMING the keep and select kernels are accounted under ICIKT_K_EPILOGUE.
+ * icikt_class_medians_in / icikt_class_medians_csc: the same on a typed view / a CSC view of the matrix (below). */
+int icikt_class_medians_f64(icikt_ctx *ctx, const double *X, int64_t n_feat, int64_t n_samp, int64_t ld,
+                            const double *global_na, int n_global_na, const int32_t *cls, int n_class, int perspective,
+                            int alternative, int continuity, uint32_t flags, int scale_max, double *med2,
+                            int32_t *n_valid, double *max_taumax, int64_t *reason_counts);
+
 /* ---- several GPUs behind one call (what the R glue binds when n_gpu > 1) ----------------------
  *
  * Replaces the reference's worker fan-out, computation$split_fun(split_comparisons, ici_split, ...)
@@ -478,6 +516,10 @@ int icikt_edges_in(icikt_ctx *ctx, const icikt_input *X, int64_t n_feat, int64_t
                    int n_global_na, const icikt_edge_rule *rule, int perspective, int alternative, int continuity,
                    uint32_t flags, int scale_max, int64_t max_edges, int32_t *ei, int32_t *ej, double *out5e,
                    int64_t *n_edges, int64_t *degree, double *max_taumax, int64_t *reason_counts);
+int icikt_class_medians_in(icikt_ctx *ctx, const icikt_input *X, int64_t n_feat, int64_t n_samp, const double *global_na,
+                           int n_global_na, const int32_t *cls, int n_class, int perspective, int alternative,
+                           int continuity, uint32_t flags, int scale_max, double *med2, int32_t *n_valid,
+                           double *max_taumax, int64_t *reason_counts);
 int icikt_matrix_in(icikt_ctx *ctx, const icikt_input *X, int64_t n_feat, int64_t n_samp, const double *global_na,
                     int n_global_na, const int32_t *pi, const int32_t *pj, int64_t n_pairs, int perspective,
                     int alternative, int continuity, uint32_t flags, int scale_max, int diag_good, double *out5,
@@ -530,6 +572,10 @@ int icikt_edges_csc(icikt_ctx *ctx, const icikt_csc_input *X, int64_t n_feat, in
                     int n_global_na, const icikt_edge_rule *rule, int perspective, int alternative, int continuity,
                     uint32_t flags, int scale_max, int64_t max_edges, int32_t *ei, int32_t *ej, double *out5e,
                     int64_t *n_edges, int64_t *degree, double *max_taumax, int64_t *reason_counts);
+int icikt_class_medians_csc(icikt_ctx *ctx, const icikt_csc_input *X, int64_t n_feat, int64_t n_samp,
+                            const double *global_na, int n_global_na, const int32_t *cls, int n_class, int perspective,
+                            int alternative, int continuity, uint32_t flags, int scale_max, double *med2,
+                            int32_t *n_valid, double *max_taumax, int64_t *reason_counts);
 int icikt_missingness_csc(icikt_ctx *ctx, const icikt_csc_input *X, int64_t n_feat, int64_t n_samp, const int32_t *pi,
                           const int32_t *pj, int64_t n_pairs, int64_t *missingness);
 int icikt_col_medians_csc(icikt_ctx *ctx, const icikt_csc_input *X, int64_t n_feat, int64_t n_samp,
@@ -562,7 +608,10 @@ int icikt_selftest(icikt_ctx *ctx);
  * launch's size), merge (0 | 1: the pipelined host entries' pairs in a launch per chunk | in one launch behind the last chunk), gridmult / gridcap (persistent grid of the long-column kernel: a
  * multiple of the resident workgroups / at most this many), pipe (0 | 1: the host entries' chunk pipeline), k0 (0 | 1: the
  * pre-pass always in its 1 024-thread / 256-thread shape), tkblock (icikt_topk_* and icikt_edges_*: the pairs a block of whole combn rows
- * may hold -- a block is always at least one row, so tkblock=1 runs a row per block), verbose (0 | 1: print the chosen
+ * may hold -- a block is always at least one row, so tkblock=1 runs a row per block; icikt_class_medians_*: the same
+ * budget for the rows of one class and for the slices of several classes' pair list), medlds (icikt_class_medians_*:
+ * the partners up to which the select kernel gathers a sample's keys into LDS once, 0 .. 4096; a sample with more
+ * re-reads the kept plane in every pass), verbose (0 | 1: print the chosen
  * plan to stderr). */
 int icikt_debug_set_plan(icikt_ctx *ctx, const char *spec);
 /* Development hook: per step kind of the pair kernel (hot loop, hot step in the main loop, MIXED, GROUP, general,
