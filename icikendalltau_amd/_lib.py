@@ -19,10 +19,11 @@ SOURCES = [os.path.join(_PKG, "csrc", f) for f in ("icikt_kernels.hip", "icikt_p
                                                        "icikt_multi.cpp", "icikt_transfer.cpp", "icikt_cor.hip", "icikt_topk.hip",
                                                        "icikt_capi_topk.cpp", "icikt_edges.hip", "icikt_capi_edges.cpp",
                                                        "icikt_diag.hip", "icikt_ingest.hip", "icikt_sparse.hip",
-                                                       "icikt_medians.hip", "icikt_capi_medians.cpp")]
+                                                       "icikt_medians.hip", "icikt_capi_medians.cpp", "icikt_capi_select.cpp")]
 HEADERS = [os.path.join(_ROOT, "include", "icikt.h"), os.path.join(_PKG, "csrc", "icikt_device.h"),
            os.path.join(_PKG, "csrc", "icikt_wave.h"), os.path.join(_PKG, "csrc", "icikt_host.h"),
-           os.path.join(_PKG, "csrc", "icikt_transfer.h"), os.path.join(_PKG, "csrc", "icikt_colsort.h")]
+           os.path.join(_PKG, "csrc", "icikt_transfer.h"), os.path.join(_PKG, "csrc", "icikt_colsort.h"),
+           os.path.join(_PKG, "csrc", "icikt_blocks.h")]
 
 # include/icikt.h
 SUCCESS = 0
@@ -437,6 +438,16 @@ def _matrix_call(fn, handle, chk, X, global_na, pi, pj, perspective, alternative
     return out5, (keep.view(np.bool_) if keep is not None else None), rc5
 
 
+def _select_args(global_na, perspective, alternative):
+    """What the selection entries (topk, edges, class_medians) share: the arguments (global_na, n_global_na) -- valid
+    while the first element, the array behind them, is alive --, (perspective, alternative) as codes, the max_taumax
+    cell and reason_counts [5]."""
+    gna = np.ascontiguousarray([] if global_na is None else np.atleast_1d(global_na), dtype=np.float64)
+    persp = PERSPECTIVE.get(perspective, perspective if isinstance(perspective, int) else -1)
+    return ((gna, _ptr(gna) if gna.size else None, int(gna.size)), (persp, ALTERNATIVE.get(alternative, ALT_OTHER)),
+            np.full(1, -np.inf), np.zeros(5, dtype=np.int64))
+
+
 class Context:
     """One HIP device + stream + workspaces (icikt_ctx)."""
 
@@ -632,18 +643,13 @@ class Context:
         ties by the smaller index.  The argument checks are the library's: a bad k or perspective raises IciktError."""
         fn, fname, xargs, n_feat, n_samp, flags, _keep = self._entry("topk", X, flags)
         k = int(k)
-        gna = np.ascontiguousarray([] if global_na is None else np.atleast_1d(global_na), dtype=np.float64)
+        gna, codes, mx, rc5 = _select_args(global_na, perspective, alternative)
         alloc = pinned_empty if (flags & FLAG_HOST_PINNED) else np.empty
         idx = alloc((n_samp, max(k, 0)), dtype=np.int32)
         vals = alloc((5, n_samp, max(k, 0)), dtype=np.float64)
         n_valid = np.zeros(n_samp, dtype=np.int32)
-        mx = np.full(1, -np.inf)
-        rc5 = np.zeros(5, dtype=np.int64)
-        persp = PERSPECTIVE.get(perspective, perspective if isinstance(perspective, int) else -1)
-        alt = ALTERNATIVE.get(alternative, ALT_OTHER)
-        self._chk(fn(self._h, *xargs, _ptr(gna) if gna.size else None, int(gna.size), k, persp, alt,
-                     int(bool(continuity)), flags, int(bool(scale_max)), _ptr(idx), _ptr(vals), _ptr(n_valid), _ptr(mx),
-                     _ptr(rc5)), fname)
+        self._chk(fn(self._h, *xargs, *gna[1:], k, *codes, int(bool(continuity)), flags, int(bool(scale_max)), _ptr(idx),
+                     _ptr(vals), _ptr(n_valid), _ptr(mx), _ptr(rc5)), fname)
         return idx, vals, n_valid, float(mx[0]), rc5
 
     def class_medians(self, X, cls=None, n_class=1, global_na=None, perspective="global", alternative="two.sided",
@@ -661,16 +667,11 @@ class Context:
             cls_a = np.ascontiguousarray(cls, dtype=np.int32)
             if cls_a.shape != (n_samp,):
                 raise ValueError("cls must give one class per column")
-        gna = np.ascontiguousarray([] if global_na is None else np.atleast_1d(global_na), dtype=np.float64)
+        gna, codes, mx, rc5 = _select_args(global_na, perspective, alternative)
         med2 = np.empty((2, n_samp), dtype=np.float64)
         n_valid = np.zeros(n_samp, dtype=np.int32)
-        mx = np.full(1, -np.inf)
-        rc5 = np.zeros(5, dtype=np.int64)
-        persp = PERSPECTIVE.get(perspective, perspective if isinstance(perspective, int) else -1)
-        alt = ALTERNATIVE.get(alternative, ALT_OTHER)
-        self._chk(fn(self._h, *xargs, _ptr(gna) if gna.size else None, int(gna.size), _ptr(cls_a), int(n_class), persp,
-                     alt, int(bool(continuity)), flags, int(bool(scale_max)), _ptr(med2), _ptr(n_valid), _ptr(mx),
-                     _ptr(rc5)), fname)
+        self._chk(fn(self._h, *xargs, *gna[1:], _ptr(cls_a), int(n_class), *codes, int(bool(continuity)), flags,
+                     int(bool(scale_max)), _ptr(med2), _ptr(n_valid), _ptr(mx), _ptr(rc5)), fname)
         return med2, n_valid, float(mx[0]), rc5
 
     def edges(self, X, min_raw=None, max_pvalue=None, min_completeness=None, absolute=False, max_edges=0,
@@ -685,7 +686,7 @@ class Context:
         fn, fname, xargs, n_feat, n_samp, flags, _keep = self._entry("edges", X, flags)
         max_edges = int(max_edges)
         rule = edge_rule(min_raw, max_pvalue, min_completeness, absolute)
-        gna = np.ascontiguousarray([] if global_na is None else np.atleast_1d(global_na), dtype=np.float64)
+        gna, codes, mx, rc5 = _select_args(global_na, perspective, alternative)
         room = max(0, min(max_edges, n_samp * (n_samp - 1) // 2))   # (the library writes no slot past the triangle)
         alloc = pinned_empty if (flags & FLAG_HOST_PINNED) else np.empty
         ei = alloc(room, dtype=np.int32) if room else None
@@ -693,13 +694,9 @@ class Context:
         vals = alloc((5, room), dtype=np.float64) if room else None
         n_edges = np.zeros(1, dtype=np.int64)
         degree = np.zeros(n_samp, dtype=np.int64) if want_degree else None
-        mx = np.full(1, -np.inf)
-        rc5 = np.zeros(5, dtype=np.int64)
-        persp = PERSPECTIVE.get(perspective, perspective if isinstance(perspective, int) else -1)
-        alt = ALTERNATIVE.get(alternative, ALT_OTHER)
-        self._chk(fn(self._h, *xargs, _ptr(gna) if gna.size else None, int(gna.size), ctypes.byref(rule), persp, alt,
-                     int(bool(continuity)), flags, int(bool(scale_max)), room if max_edges >= 0 else max_edges,
-                     _ptr(ei), _ptr(ej), _ptr(vals), _ptr(n_edges), _ptr(degree), _ptr(mx), _ptr(rc5)), fname)
+        self._chk(fn(self._h, *xargs, *gna[1:], ctypes.byref(rule), *codes, int(bool(continuity)), flags,
+                     int(bool(scale_max)), room if max_edges >= 0 else max_edges, _ptr(ei), _ptr(ej), _ptr(vals),
+                     _ptr(n_edges), _ptr(degree), _ptr(mx), _ptr(rc5)), fname)
         m = min(int(n_edges[0]), room)
         if room:
             ei, ej, vals = ei[:m], ej[:m], vals[:, :m]

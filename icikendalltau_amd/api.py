@@ -524,6 +524,36 @@ def _run_sharded(engine, X, pi, pj, core, perspective, alternative, continuity):
 # --------------------------------------------------------------------------------------------------
 # ici_kendalltau (R/kendalltau.R:96-179) + scale_and_reshape (:357-421)
 # --------------------------------------------------------------------------------------------------
+def _host_masks(global_na) -> bool:
+    """More distinct finite values than the device-side exclusion rule holds (MASK_VALS; the reference loops over any
+    number, R/utils.R:16-20): the host has to mask the matrix."""
+    vals = np.atleast_1d(np.asarray([] if global_na is None else global_na, dtype=np.float64))
+    return len({float(v) for v in vals if math.isfinite(v)}) > _lib.MASK_VALS
+
+
+def _mask_on_host(X, global_na):
+    """(X, global_na) as a device entry takes them: unchanged, or -- _host_masks -- X masked here and NaN passed."""
+    if not _host_masks(global_na):
+        return X, global_na
+    if _lib.is_sparse(X):
+        X = _densify(X)
+    X = np.asarray(X, dtype=np.float64)
+    return _masked_fortran(X, setup_missing_matrix(X, global_na)), (float("nan"),)
+
+
+def _warn_pairs(rcounts):
+    """One warning per offending pair, as ici_split raises them."""
+    for code in (_lib.REASON_SHORT, _lib.REASON_SINGLE_UNIQUE, _lib.REASON_TIES_EQ_TOTAL):
+        for _ in range(int(rcounts[code])):
+            _warn_reason(code)
+
+
+def _max_taumax(taumax, where):
+    """The largest taumax over the pairs `where` selects of a full result (-inf without one that is not NA)."""
+    have = _na_rm(np.asarray(taumax)[where])
+    return float(have.max()) if have.size else -math.inf
+
+
 def _named_matrix(values: np.ndarray, names):
     if pd is not None:
         return pd.DataFrame(values, index=list(names), columns=list(names))
@@ -562,11 +592,8 @@ def ici_kendalltau(data_matrix, global_na=(float("nan"), float("inf"), 0), persp
         ncore = len(engine.ctx.devices)
     eng = engine or _default_engine()
 
-    # the device-side exclusion rule holds up to MASK_VALS distinct finite values; the reference loops over any number
-    # (R/utils.R:16-20): a longer list takes the host-masking route below
-    n_finite = len({float(v) for v in np.atleast_1d(np.asarray([] if global_na is None else global_na, dtype=np.float64))
-                    if math.isfinite(v)})
-    if return_matrix and not check_timing and world == 1 and hasattr(eng, "matrix") and n_finite <= _lib.MASK_VALS:
+    host_masks = _host_masks(global_na)   # a list longer than the device-side rule takes the host-masking route below
+    if return_matrix and not check_timing and world == 1 and hasattr(eng, "matrix") and not host_masks:
         # One library call does everything below the argument checks on the device (icikt_matrix_f64): the exclusion
         # rule of setup_missing_matrix inside the pre-pass (no masked copy of the matrix on the host), the pair
         # kernels, scale_and_reshape, one copy of the five matrices back.  All pairs of the upper triangle need no
@@ -582,9 +609,7 @@ def ici_kendalltau(data_matrix, global_na=(float("nan"), float("inf"), 0), persp
         out5, keep, rcounts = eng.matrix(_for_engine(data_matrix, eng, fortran=False), global_na, pi, pj, perspective, alternative, continuity,
                                          scale_max, diag_good)
         t_diff = time.perf_counter() - t1
-        for code in (_lib.REASON_SHORT, _lib.REASON_SINGLE_UNIQUE, _lib.REASON_TIES_EQ_TOTAL):
-            for _ in range(int(rcounts[code])):   # one warning per offending pair, as ici_split raises them
-                _warn_reason(code)
+        _warn_pairs(rcounts)
         res = {key: _named_matrix(out5[k], names)
                for k, key in enumerate(("cor", "raw", "pvalue", "taumax", "completeness"))}
         res["keep"] = keep
@@ -727,30 +752,18 @@ def ici_kendalltau_topk(data_matrix, k, global_na=(float("nan"), float("inf"), 0
                          "`include_only` vs those in the samples.")  # R/kendalltau.R:240-247
     eng = engine or _default_engine()
     if hasattr(eng, "topk"):
-        n_finite = len({float(v) for v in np.atleast_1d(np.asarray([] if global_na is None else global_na,
-                                                                     dtype=np.float64)) if math.isfinite(v)})
-        X = data_matrix
-        if n_finite > _lib.MASK_VALS:   # more values than the device-side rule holds: masked here, NaN passed
-            if _lib.is_sparse(X):
-                X = _densify(X)
-            X = np.asarray(X, dtype=np.float64)
-            X = _masked_fortran(X, setup_missing_matrix(X, global_na))
-            global_na = (float("nan"),)
+        X, global_na = _mask_on_host(data_matrix, global_na)
         t1 = time.perf_counter()
         idx, vals, n_valid, max_taumax, rcounts = eng.topk(_for_engine(X, eng, fortran=False), k, global_na, perspective,
                                                            alternative, continuity, 0, scale_max)
         t_diff = time.perf_counter() - t1
-        for code in (_lib.REASON_SHORT, _lib.REASON_SINGLE_UNIQUE, _lib.REASON_TIES_EQ_TOTAL):
-            for _ in range(int(rcounts[code])):   # one warning per offending pair, as ici_split raises them
-                _warn_reason(code)
+        _warn_pairs(rcounts)
     else:
         full = ici_kendalltau(data_matrix, global_na=global_na, perspective=perspective, scale_max=scale_max,
                               diag_good=True, alternative=alternative, continuity=continuity, colnames=names, engine=eng)
         t_diff = full["run_time"]
         idx, vals, n_valid = _topk_numpy([np.asarray(full[key]) for key in _TOPK_KEYS], k)
-        iu = np.triu_indices(n_sample, k=1)
-        have = _na_rm(np.asarray(full["taumax"])[iu])
-        max_taumax = float(have.max()) if have.size else -math.inf
+        max_taumax = _max_taumax(full["taumax"], np.triu_indices(n_sample, k=1))
     names_arr = np.asarray(list(names) + [None], dtype=object)
     res = {"indices": idx, "neighbors": names_arr[idx]}    # (-1 picks the None behind the names)
     for q, key in enumerate(_TOPK_KEYS):
@@ -833,23 +846,13 @@ def ici_kendalltau_medians(data_matrix, sample_classes=None, global_na=(float("n
                          "`include_only` vs those in the samples.")  # R/kendalltau.R:240-247
     eng = engine or _default_engine()
     if hasattr(eng, "class_medians"):
-        n_finite = len({float(v) for v in np.atleast_1d(np.asarray([] if global_na is None else global_na,
-                                                                     dtype=np.float64)) if math.isfinite(v)})
-        X = data_matrix
-        if n_finite > _lib.MASK_VALS:   # more values than the device-side rule holds: masked here, NaN passed
-            if _lib.is_sparse(X):
-                X = _densify(X)
-            X = np.asarray(X, dtype=np.float64)
-            X = _masked_fortran(X, setup_missing_matrix(X, global_na))
-            global_na = (float("nan"),)
+        X, global_na = _mask_on_host(data_matrix, global_na)
         t1 = time.perf_counter()
         med2, n_valid, max_taumax, rcounts = eng.class_medians(_for_engine(X, eng, fortran=False), cls, len(levels),
                                                                global_na, perspective, alternative, continuity, 0,
                                                                scale_max)
         t_diff = time.perf_counter() - t1
-        for code in (_lib.REASON_SHORT, _lib.REASON_SINGLE_UNIQUE, _lib.REASON_TIES_EQ_TOTAL):
-            for _ in range(int(rcounts[code])):   # one warning per offending pair, as ici_split raises them
-                _warn_reason(code)
+        _warn_pairs(rcounts)
     else:
         # the within-class pairs, class by class, combn order inside a class
         first, second = [], []
@@ -866,8 +869,7 @@ def ici_kendalltau_medians(data_matrix, sample_classes=None, global_na=(float("n
             cor, raw, taumax = (np.asarray(full[key], dtype=np.float64) for key in ("cor", "raw", "taumax"))
             med2, n_valid = _class_medians_numpy(cor, raw, cls)
             same = (cls[:, None] == cls[None, :]) & np.triu(np.ones((n_sample, n_sample), dtype=bool), k=1)
-            have = _na_rm(taumax[same])
-            max_taumax = float(have.max()) if have.size else -math.inf
+            max_taumax = _max_taumax(taumax, same)
         else:   # singletons alone: nothing to compute
             t_diff = 0.0
             med2 = np.empty((2, n_sample), dtype=np.float64)
@@ -958,15 +960,7 @@ def ici_kendalltau_edges(data_matrix, min_raw=None, max_pvalue=None, min_complet
     total = n_sample * (n_sample - 1) // 2
     eng = engine or _default_engine()
     if hasattr(eng, "edges"):
-        n_finite = len({float(v) for v in np.atleast_1d(np.asarray([] if global_na is None else global_na,
-                                                                     dtype=np.float64)) if math.isfinite(v)})
-        X = data_matrix
-        if n_finite > _lib.MASK_VALS:   # more values than the device-side rule holds: masked here, NaN passed
-            if _lib.is_sparse(X):
-                X = _densify(X)
-            X = np.asarray(X, dtype=np.float64)
-            X = _masked_fortran(X, setup_missing_matrix(X, global_na))
-            global_na = (float("nan"),)
+        X, global_na = _mask_on_host(data_matrix, global_na)
         Xe = _for_engine(X, eng, fortran=False)
         room = min(total, max(EDGES_DEFAULT_CAPACITY, EDGES_CAPACITY_PER_SAMPLE * n_sample)) if max_edges is None else int(max_edges)
         t1 = time.perf_counter()
@@ -977,9 +971,7 @@ def ici_kendalltau_edges(data_matrix, min_raw=None, max_pvalue=None, min_complet
                             alternative, continuity, 0, scale_max)
         t_diff = time.perf_counter() - t1
         ei, ej, vals, n_edges, degree, max_taumax, rcounts = out
-        for code in (_lib.REASON_SHORT, _lib.REASON_SINGLE_UNIQUE, _lib.REASON_TIES_EQ_TOTAL):
-            for _ in range(int(rcounts[code])):   # one warning per offending pair, as ici_split raises them
-                _warn_reason(code)
+        _warn_pairs(rcounts)
     else:
         full = ici_kendalltau(data_matrix, global_na=global_na, perspective=perspective, scale_max=scale_max,
                               diag_good=True, alternative=alternative, continuity=continuity, colnames=names, engine=eng)
@@ -989,9 +981,7 @@ def ici_kendalltau_edges(data_matrix, min_raw=None, max_pvalue=None, min_complet
         n_edges = int(ei.shape[0])
         if max_edges is not None:
             ei, ej, vals = ei[:int(max_edges)], ej[:int(max_edges)], vals[:, :int(max_edges)]
-        iu = np.triu_indices(n_sample, k=1)
-        have = _na_rm(np.asarray(full["taumax"])[iu])
-        max_taumax = float(have.max()) if have.size else -math.inf
+        max_taumax = _max_taumax(full["taumax"], np.triu_indices(n_sample, k=1))
     names_arr = np.asarray(list(names), dtype=object)
     res = {"s1": names_arr[ei], "s2": names_arr[ej], "i": ei, "j": ej}
     for q, key in enumerate(_TOPK_KEYS):
@@ -1565,7 +1555,7 @@ def _device_rule(X, global_na):
     """The global_na rule as the device takes it: (X, global_na, host exclusion mask or None).  More than 32 distinct
     finite values: the host masks X (NaN) and passes NA alone."""
     vals = [] if global_na is None else [float(v) for v in np.atleast_1d(np.asarray(global_na, dtype=np.float64))]
-    if len({v for v in vals if math.isfinite(v)}) <= _lib.MASK_VALS:
+    if not _host_masks(vals):
         return X, vals, None
     if _lib.is_sparse(X):
         X = _densify(X)

@@ -1728,7 +1728,8 @@ extern "C" {
 // cost the launch down to), split (1 | 2 | 4 segments per half-wave task), gridmult (persistent grid as a multiple of the resident waves, always), gridcap (persistent
 // grid: at most this many workgroups),
 // pipe (0 | 1: the host entries' chunk pipeline off / on whenever possible), k0 (0 | 1: the pre-pass always in its
-// 1 024-thread / 256-thread shape), tkblock (icikt_topk_* / icikt_edges_*: pairs per block of whole combn rows; 1 = a row per block),
+// 1 024-thread / 256-thread shape), tkblock (icikt_topk_* / icikt_edges_* / icikt_class_medians_*: pairs per block of
+// whole combn rows, 1 = a row per block, or per slice of several classes' pair list),
 // medlds (icikt_class_medians_*: partners up to which the select kernel stages a sample's keys in LDS, 0 .. 4096),
 // verbose (0 | 1: print the plan to stderr).
 // (The keys h2d and regfail of rounds 2-3 are gone with the mode they steered: the library no longer page-locks

@@ -1,0 +1,139 @@
+// icikt_capi_select.cpp -- the host side the selection entries share (icikt_topk_*, icikt_edges_*,
+// icikt_class_medians_*; declared in icikt_host.h): their common checks, and the run of a call's blocks through the
+// pair engine.  Nothing of size S^2 is allocated: each block's records are folded by the entry's kernel before the
+// next block overwrites them.
+#include <hip/hip_runtime.h>
+
+#include <cmath>
+#include <cstring>
+#include <new>
+#include <string>
+
+#include "icikt.h"
+#include "icikt_device.h"
+#include "icikt_host.h"
+
+namespace icikt {
+namespace host {
+
+int select_check_shape(const SelectCall& s, const char* cap_why) {
+  if (!s.c) return ICIKT_E_INVALID;
+  const int rc = check_src(s.c, s.who, s.X, s.n_feat, s.n_samp);
+  if (rc) return rc;
+  if (s.n_samp > ICIKT_TOPK_MAX_SAMPLES)
+    return fail(s.c, ICIKT_E_INVALID, std::string(s.who) + ": n_samp exceeds ICIKT_TOPK_MAX_SAMPLES (65535 samples: " + cap_why + ")");
+  return ICIKT_SUCCESS;
+}
+
+int select_check_args(SelectCall& s) {
+  const SelectArgs& A = s.A;
+  if (A.perspective != ICIKT_PERSPECTIVE_LOCAL && A.perspective != ICIKT_PERSPECTIVE_GLOBAL)
+    return fail(s.c, ICIKT_E_INVALID, std::string(s.who) + ": perspective must be local (0) or global (1)");
+  if (A.alternative < 0 || A.alternative > ICIKT_ALT_OTHER)
+    return fail(s.c, ICIKT_E_INVALID, std::string(s.who) + ": bad alternative code");
+  const int rc = make_mask_spec(s.c, A.global_na, A.n_global_na, &s.ms);
+  if (rc) return rc;
+  if (A.reason_counts) for (int r = 0; r < 5; ++r) A.reason_counts[r] = 0;
+  if (A.max_taumax) *A.max_taumax = -HUGE_VAL;   // max(numeric(0), na.rm = TRUE)
+  return ICIKT_SUCCESS;
+}
+
+int select_budget(const SelectCall& s, int64_t* budget) {
+  *budget = s.c->plan_ov.tkblock > 0 ? s.c->plan_ov.tkblock : kTriangleBlockPairs;
+  return use_device(s.c);
+}
+
+int select_run(SelectCall& s, PairBlocks& blocks, const SelectSteps& steps) {
+  icikt_ctx* const c = s.c;
+  const SelectArgs& A = s.A;
+  const uint32_t flags = A.flags;
+  HIPCHK(c, c->d_red.reserve(8));
+  // from here on the context holds this call's scratch state and nothing of the caller's: whatever happens, the
+  // device-resident calls start over afterwards (icikt_run_dev: ICIKT_E_STATE, icikt_num_pairs: -1)
+  auto leave = [&](int r) {
+    r = end_call(c, s.who, r);
+    c->prepared = false;
+    c->raw_valid = false;
+    c->n_pairs = -1;
+    c->pairs_nsamp = -1;
+    c->wpb = 0;
+    c->combn_S = -1;
+    return r;
+  };
+  const PinnedScope scope(c, flags);
+  const uint32_t run_flags = flags & ~(uint32_t)ICIKT_FLAG_REUSE_COUNTS;
+  unsigned long long red[8] = {};
+  auto body = [&]() -> int {
+    int r = steps.start();
+    if (r) return r;
+    HIPCHK(c, hipMemsetAsync(c->d_red.p, 0, 8 * sizeof(unsigned long long), c->stream));
+    if (blocks.n_blocks > 0) {
+      HIPCHK(c, c->d_out4.reserve((size_t)blocks.block_max * 4));
+      HIPCHK(c, c->d_reasons.reserve((size_t)blocks.block_max));
+      PairBlock b;
+      bool more = false;
+      auto advance = [&]() -> int {
+        try { more = blocks.next(&b); } catch (const std::bad_alloc&) {
+          return fail(c, ICIKT_E_NOMEM, std::string(s.who) + ": host allocation failed");
+        }
+        return ICIKT_SUCCESS;
+      };
+      auto set_pairs = [&]() {
+        return b.pi ? icikt_set_pairs(c, b.pi, b.pj, b.count) : icikt_set_pairs_combn(c, blocks.S, b.begin, b.begin + b.count);
+      };
+      // a call that is one block takes the matrix entries' way in: copies, pre-pass and pair kernel pipelined by
+      // column chunks (upload_prepare_pairs); several blocks: the matrix first, then block after block
+      const bool one = blocks.n_blocks == 1;
+      r = advance();
+      if (!r && one) r = set_pairs();
+      if (r) return r;
+      r = prepare_alloc(c, s.n_feat, s.n_samp, s.n_samp, s.n_samp);
+      if (r) return r;
+      c->k0_mask = &s.ms;
+      c->k0_keep = nullptr;
+      r = one ? upload_prepare_pairs(c, s.X, s.n_feat, s.n_samp, flags)
+              : upload_and_prepare(c, s.X, s.n_feat, s.n_samp, 0, s.n_samp, flags);
+      c->k0_mask = nullptr;
+      if (r) return r;
+      c->prepared = true;
+      int64_t done = 0;
+      while (more) {
+        if (!one) {
+          r = set_pairs();
+          if (r) return r;
+        }
+        if (b.count <= 0 || b.begin != done || done + b.count > blocks.total)
+          return fail(c, ICIKT_E_STATE, std::string(s.who) + ": the block cut lost its place");
+        r = icikt_run_dev(c, A.perspective, A.alternative, A.continuity,
+                          run_flags | ((one && c->raw_valid) ? ICIKT_FLAG_REUSE_COUNTS : 0u), c->d_out4.p, nullptr,
+                          c->d_reasons.p);
+        if (r) return r;
+        r = timer_begin(c, ICIKT_K_EPILOGUE, flags);
+        if (r) return r;
+        HIPCHK(c, launch_out_stats_accum(c->pv, c->d_out4.p, c->d_reasons.p, b.count, c->d_red.p, c->stream));
+        r = steps.fold(b);
+        if (r) return r;
+        r = timer_end(c, ICIKT_K_EPILOGUE, flags);
+        if (r) return r;
+        done += b.count;
+        r = advance();
+        if (r) return r;
+      }
+      if (done != blocks.total) return fail(c, ICIKT_E_STATE, std::string(s.who) + ": the blocks do not add up to the pair list");
+    }
+    return steps.finish(red);
+  };
+  const int rc = leave(body());
+  c->k0_mask = nullptr;
+  if (rc) return rc;
+  // d_red: word 0 the largest taumax as an order-preserving key (0: no pair had one), words 1 .. 5 the reason counts
+  if (A.reason_counts) for (int r = 0; r < 5; ++r) A.reason_counts[r] = (int64_t)red[1 + r];
+  if (A.max_taumax && red[0]) {
+    const unsigned long long u = (red[0] >> 63) ? (red[0] & 0x7FFFFFFFFFFFFFFFull) : ~red[0];
+    std::memcpy(A.max_taumax, &u, sizeof(double));
+  }
+  return ICIKT_SUCCESS;
+}
+
+}  // namespace host
+}  // namespace icikt

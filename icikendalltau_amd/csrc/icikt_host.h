@@ -13,6 +13,7 @@
 #include <vector>
 
 #include "icikt.h"
+#include "icikt_blocks.h"
 #include "icikt_device.h"
 #include "icikt_transfer.h"
 
@@ -159,7 +160,7 @@ struct icikt_ctx {
     int split = -1;     // half-wave kernels: segments per task (1 | 2 | 4), whatever the launch's size
     int solo = -1;      // 0: SOLO steps of the tie program run as MIXED steps (with the in-step chains)
     int list = -1;      // list mode (range counts per listed tie group) up to this many tie groups: count mode takes over above
-    long long tkblock = -1;   // icikt_topk_* and icikt_edges_*: pairs a block of whole combn rows may hold (default: the library's budget)
+    long long tkblock = -1;   // icikt_topk_*, icikt_edges_*, icikt_class_medians_*: pairs a block (whole combn rows, or a slice of the class list) may hold (default: the library's budget)
     int medlds = -1;          // icikt_class_medians_*: partners up to which the select kernel gathers a sample's keys into LDS (default: MEDIAN_STAGE_MAX)
     bool verbose = false;
   } plan_ov;
@@ -236,28 +237,45 @@ int check_pair_args(icikt_ctx* c, const char* who, const MatrixSrc& X, int64_t n
                     const int32_t* pi, const int32_t* pj, int64_t* n_pairs, const void* out, bool out5,
                     int perspective, int alternative);
 
-// ---- the combn triangle in blocks of whole rows (icikt_topk_*, icikt_edges_*) ----
-// Pairs of a block of whole rows when no tkblock key says otherwise.  2^24 pairs fill the chip (256 CUs x at most 32
-// waves x 2 pairs: 16 384 pairs in flight) a thousand times over, so a block's launch tail is lost in its body, and
-// the buffers of a block -- out4 32 B, the pair kernel's counts 24, pi / pj 8, the task list 8, reasons 4 per pair, a
-// ninth on top for the buffers' growth margin -- stay at 1.4 GB.  The whole triangle of up to 5 793 columns is ONE block.
-constexpr int64_t kTriangleBlockPairs = (int64_t)1 << 24;
-// first pair of row i of combn(S, 2)
-inline int64_t row_offset(int64_t S, int64_t i) { return i * (2 * S - i - 1) / 2; }
-// rows [a, b) of the combn triangle per block: the largest run from a within the budget, at least one row; a run of
-// several rows ends on an even row (the next block then starts on one: the pair kernel's tasks pair the rows 2a, 2a + 1)
-inline std::vector<std::pair<int, int>> cut_rows(int64_t S, int64_t budget) {
-  std::vector<std::pair<int, int>> blocks;
-  int64_t a = 0;
-  while (a < S - 1) {
-    int64_t b = a, pairs = 0;
-    while (b < S - 1 && (b == a || pairs + (S - 1 - b) <= budget)) { pairs += S - 1 - b; ++b; }
-    if (b < S - 1 && (b & 1) && b - a >= 2) --b;
-    blocks.emplace_back((int)a, (int)b);
-    a = b;
-  }
-  return blocks;
-}
+// ---- the selection entries (icikt_topk_*, icikt_edges_*, icikt_class_medians_*): one driver, icikt_capi_select.cpp ----
+// (the blocks a call runs in: icikt_blocks.h; DESIGN.md "adding a selection entry")
+// the arguments the three entries share
+struct SelectArgs {
+  const double* global_na;
+  int n_global_na;
+  int perspective, alternative, continuity;
+  uint32_t flags;
+  double* max_taumax;
+  int64_t* reason_counts;
+};
+// one call of an entry: `who` prefixes its messages; ms is the exclusion rule select_check_args makes of global_na
+struct SelectCall {
+  icikt_ctx* c;
+  const char* who;
+  const MatrixSrc& X;
+  int64_t n_feat, n_samp;
+  SelectArgs A;
+  icikt::MaskSpec ms;
+};
+// what an entry adds to the driver's call sequence, all on c->stream
+struct SelectSteps {
+  std::function<int()> start;                         // its own device state, before the first block
+  std::function<int(const PairBlock&)> fold;          // its kernel over the block that is in c->d_out4 / c->d_reasons (the
+                                                      // driver has run launch_out_stats_accum inside the same timer pair)
+  std::function<int(unsigned long long* red)> finish; // its last kernel and its downloads, c->d_red into red[8] among them
+};
+// The checks of an entry, in this order, before any output or anything of the context is touched:
+//   select_check_shape   the context, the matrix (check_src), ICIKT_TOPK_MAX_SAMPLES (`cap_why`: the entry's reason for it)
+//   (the entry's own)    k, rule, max_edges, cls, null outputs
+//   select_check_args    perspective, alternative, global_na; then resets max_taumax and reason_counts
+// select_budget (n_samp > 0) makes the context's device current and gives the pairs a block may hold (tkblock, else
+// kTriangleBlockPairs).  select_run runs the blocks -- a call of one block pipelined by column chunks
+// (upload_prepare_pairs), several blocks behind one upload -- then steps.finish, leaves the context without prepared
+// state or pair list, and decodes red into max_taumax and reason_counts.
+int select_check_shape(const SelectCall& s, const char* cap_why);
+int select_check_args(SelectCall& s);
+int select_budget(const SelectCall& s, int64_t* budget);
+int select_run(SelectCall& s, PairBlocks& blocks, const SelectSteps& steps);
 
 }  // namespace host
 }  // namespace icikt
