@@ -19,7 +19,8 @@ SOURCES = [os.path.join(_PKG, "csrc", f) for f in ("icikt_kernels.hip", "icikt_p
                                                        "icikt_multi.cpp", "icikt_transfer.cpp", "icikt_cor.hip", "icikt_topk.hip",
                                                        "icikt_capi_topk.cpp", "icikt_edges.hip", "icikt_capi_edges.cpp",
                                                        "icikt_diag.hip", "icikt_ingest.hip", "icikt_sparse.hip",
-                                                       "icikt_medians.hip", "icikt_capi_medians.cpp", "icikt_capi_select.cpp")]
+                                                       "icikt_medians.hip", "icikt_capi_medians.cpp", "icikt_capi_select.cpp",
+                                                       "icikt_quantiles.hip", "icikt_capi_quantiles.cpp")]
 HEADERS = [os.path.join(_ROOT, "include", "icikt.h"), os.path.join(_PKG, "csrc", "icikt_device.h"),
            os.path.join(_PKG, "csrc", "icikt_wave.h"), os.path.join(_PKG, "csrc", "icikt_host.h"),
            os.path.join(_PKG, "csrc", "icikt_transfer.h"), os.path.join(_PKG, "csrc", "icikt_colsort.h"),
@@ -40,6 +41,8 @@ CNT_FIELDS = ("n", "missing", "dis", "ntie", "xtie", "ytie", "x0", "x1", "y0", "
 K_PREPARE, K_PAIRS, K_EPILOGUE = 0, 1, 2
 TOPK_MAX = 256                # ICIKT_TOPK_MAX: partners per sample of icikt_topk_*
 TOPK_MAX_SAMPLES = 65535      # ICIKT_TOPK_MAX_SAMPLES
+QUANTILE_MAX_PROBS = 32       # ICIKT_QUANTILE_MAX_PROBS: probabilities per call of icikt_quantiles_*
+HIST_MAX_BINS = 1024          # ICIKT_HIST_MAX_BINS
 MASK_VALS = 32                # distinct finite global_na values of the device-side exclusion rule (icikt_device.h)
 MAX_FEATURES = 65535          # the tuned kernels
 MAX_FEATURES_WIDE = 262144    # the plain 32-bit path (exact integer arithmetic)
@@ -73,6 +76,7 @@ EXPORTS = (
     "icikt_topk_f64", "icikt_topk_in", "icikt_topk_csc",
     "icikt_edges_f64", "icikt_edges_in", "icikt_edges_csc",
     "icikt_class_medians_f64", "icikt_class_medians_in", "icikt_class_medians_csc",
+    "icikt_quantiles_f64", "icikt_quantiles_in", "icikt_quantiles_csc",
 )
 
 # icikt_input: the caller's matrix as a typed, strided view (ICIKT_DTYPE_*, ICIKT_ORDER_*)
@@ -359,18 +363,21 @@ def lib():
                                   c_int, c_u32, c_int, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]
     L.icikt_class_medians_f64.argtypes = [c_vp, c_vp, c_i64, c_i64, c_i64, c_vp, c_int, c_vp, c_int, c_int, c_int, c_int,
                                           c_u32, c_int, c_vp, c_vp, c_vp, c_vp]
+    L.icikt_quantiles_f64.argtypes = [c_vp, c_vp, c_i64, c_i64, c_i64, c_vp, c_int, c_vp, c_int, c_int, c_int, c_int,
+                                      c_u32, c_int, c_vp, c_int, c_vp, c_int, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp,
+                                      c_vp]
     L.icikt_multi_rank_phase_ms.argtypes = [c_vp, c_int, ctypes.POINTER(ctypes.c_double)]
     L.icikt_multi_ranks_used.argtypes = [c_vp]
     L.icikt_debug_step_stats.argtypes = [c_vp, c_vp, c_int]
     # the *_in twins: (ctx, const icikt_input*, n_feat, n_samp, ...) where the _f64 entry has (ctx, X, n_feat, n_samp, ld, ...)
     for nm in ("pairs", "matrix", "pairs_complete", "missingness", "cor_pairs", "col_medians", "censor_counts",
-               "rank_order", "topk", "edges", "class_medians"):
+               "rank_order", "topk", "edges", "class_medians", "quantiles"):
         f64 = getattr(L, f"icikt_{nm}_f64").argtypes
         getattr(L, f"icikt_{nm}_in").argtypes = [c_vp, ctypes.POINTER(InputView), c_i64, c_i64] + list(f64[5:])
     L.icikt_convert_dev.argtypes = [c_vp, c_vp, c_int, c_int, c_i64, c_i64, c_i64, c_vp, c_i64]
     # the *_csc twins: (ctx, const icikt_csc_input*, n_feat, n_samp, ...)
     for nm in ("pairs", "matrix", "missingness", "col_medians", "censor_counts", "rank_order", "topk", "edges",
-               "class_medians"):
+               "class_medians", "quantiles"):
         f64 = getattr(L, f"icikt_{nm}_f64").argtypes
         getattr(L, f"icikt_{nm}_csc").argtypes = [c_vp, ctypes.POINTER(CscInput), c_i64, c_i64] + list(f64[5:])
     L.icikt_scatter_csc_dev.argtypes = [c_vp, c_vp, c_vp, c_vp, c_int, c_int, ctypes.c_double, c_i64, c_i64, c_vp, c_i64]
@@ -439,7 +446,7 @@ def _matrix_call(fn, handle, chk, X, global_na, pi, pj, perspective, alternative
 
 
 def _select_args(global_na, perspective, alternative):
-    """What the selection entries (topk, edges, class_medians) share: the arguments (global_na, n_global_na) -- valid
+    """What the selection entries (topk, edges, class_medians, quantiles) share: the arguments (global_na, n_global_na) -- valid
     while the first element, the array behind them, is alive --, (perspective, alternative) as codes, the max_taumax
     cell and reason_counts [5]."""
     gna = np.ascontiguousarray([] if global_na is None else np.atleast_1d(global_na), dtype=np.float64)
@@ -673,6 +680,42 @@ class Context:
         self._chk(fn(self._h, *xargs, *gna[1:], _ptr(cls_a), int(n_class), *codes, int(bool(continuity)), flags,
                      int(bool(scale_max)), _ptr(med2), _ptr(n_valid), _ptr(mx), _ptr(rc5)), fname)
         return med2, n_valid, float(mx[0]), rc5
+
+    def quantiles(self, X, probs=(), breaks=None, cls=None, n_class=1, global_na=None, perspective="global",
+                  alternative="two.sided", continuity=False, flags: int = 0, scale_max=True):
+        """Exact quantiles (R's type 7) and a histogram of raw over ALL pairs, reduced on the device
+        (icikt_quantiles_f64): nothing of size S x S exists on the host or as five planes on the device.  probs: up to
+        32 values in [0, 1]; breaks: strictly increasing bin edges (numpy.histogram's bins), None for no histogram;
+        cls: a class index in 0 .. n_class - 1 per column, which splits the result into the groups all / within-class
+        / between-class pairs (None: the one group of all pairs).  Returns (q2 [2, n_group, n_probs]: cor, raw --
+        NA_real_ for a group without a valid pair; order2 [n_group, n_probs, 2]: the two order statistics each
+        quantile interpolates; n_valid, n_na [n_group] int64; hist [n_group, n_bins] int64; outside [n_group, 2]:
+        values below the first and above the last break; max_taumax; reason_counts [5]).  The argument checks are the
+        library's: a bad prob, break, class index or perspective raises IciktError."""
+        fn, fname, xargs, n_feat, n_samp, flags, _keep = self._entry("quantiles", X, flags)
+        if cls is None:
+            cls_a = None
+        else:
+            cls_a = np.ascontiguousarray(cls, dtype=np.int32)
+            if cls_a.shape != (n_samp,):
+                raise ValueError("cls must give one class per column")
+        probs_a = np.ascontiguousarray(np.atleast_1d(np.asarray(probs, dtype=np.float64)).ravel())
+        breaks_a = np.empty(0) if breaks is None else np.ascontiguousarray(np.atleast_1d(breaks), dtype=np.float64).ravel()
+        n_probs, n_breaks = int(probs_a.size), int(breaks_a.size)
+        n_group = 1 if cls_a is None else 3
+        gna, codes, mx, rc5 = _select_args(global_na, perspective, alternative)
+        q2 = np.empty((2, n_group, n_probs), dtype=np.float64)
+        order2 = np.empty((n_group, n_probs, 2), dtype=np.float64)
+        n_valid = np.zeros(n_group, dtype=np.int64)
+        n_na = np.zeros(n_group, dtype=np.int64)
+        hist = np.zeros((n_group, max(n_breaks - 1, 0)), dtype=np.int64)
+        outside = np.zeros((n_group, 2), dtype=np.int64)
+        self._chk(fn(self._h, *xargs, *gna[1:], _ptr(cls_a), int(n_class), *codes, int(bool(continuity)), flags,
+                     int(bool(scale_max)), _ptr(probs_a) if n_probs else None, n_probs,
+                     _ptr(breaks_a) if n_breaks else None, n_breaks, _ptr(q2) if n_probs else None,
+                     _ptr(order2) if n_probs else None, _ptr(n_valid), _ptr(n_na),
+                     _ptr(hist) if n_breaks > 1 else None, _ptr(outside), _ptr(mx), _ptr(rc5)), fname)
+        return q2, order2, n_valid, n_na, hist, outside, float(mx[0]), rc5
 
     def edges(self, X, min_raw=None, max_pvalue=None, min_completeness=None, absolute=False, max_edges=0,
               global_na=None, perspective="global", alternative="two.sided", continuity=False, flags: int = 0,

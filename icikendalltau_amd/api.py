@@ -77,6 +77,13 @@ class HipEngine:
         return self.ctx.class_medians(data_matrix, cls, n_class, global_na, perspective, alternative, continuity,
                                       self.flags | flags, scale_max)
 
+    def quantiles(self, data_matrix, probs=(), breaks=None, cls=None, n_class=1, global_na=None, perspective="global",
+                  alternative="two.sided", continuity=False, flags=0, scale_max=True):
+        """Exact quantiles and a histogram of raw over all pairs, reduced on the device (icikt_quantiles_f64):
+        Context.quantiles' arguments and result."""
+        return self.ctx.quantiles(data_matrix, probs, breaks, cls, n_class, global_na, perspective, alternative,
+                                  continuity, self.flags | flags, scale_max)
+
     def cor_pairs(self, X, pi, pj, method, pairwise, alternative, continuity):
         """cor_fast's pairs on the device (icikt_cor_pairs_f64): (out3: rho, p-value, n_values; reasons)."""
         return self.ctx.cor_pairs(X, pi, pj, method, pairwise, alternative, continuity)
@@ -175,6 +182,11 @@ class MultiHipEngine(HipEngine):
                       alternative="two.sided", continuity=False, flags=0, scale_max=True):  # the reduction runs on one device
         return self._one().class_medians(data_matrix, cls, n_class, global_na, perspective, alternative, continuity,
                                          self.flags | flags, scale_max)
+
+    def quantiles(self, data_matrix, probs=(), breaks=None, cls=None, n_class=1, global_na=None, perspective="global",
+                  alternative="two.sided", continuity=False, flags=0, scale_max=True):   # the select runs on one device
+        return self._one().quantiles(data_matrix, probs, breaks, cls, n_class, global_na, perspective, alternative,
+                                     continuity, self.flags | flags, scale_max)
 
     def pairs_complete(self, X, pi, pj):  # kt_fast's per-pair masking path exists on one device only
         out, _cnt, rsn = self._one().pairs_complete(X, pi, pj, "two.sided", False, self.flags)
@@ -879,6 +891,142 @@ def ici_kendalltau_medians(data_matrix, sample_classes=None, global_na=(float("n
     labels = [levels[k] for k in cls]
     return {"sample_id": list(names), "sample_class": labels, "med_cor": med2[0], "med_raw": med2[1],
             "n_valid": n_valid, "max_taumax": max_taumax, "run_time": t_diff}
+
+
+# --------------------------------------------------------------------------------------------------
+# ici_kendalltau_quantiles: exact quantiles and a histogram of raw over all pairs (the cut-off ici_kendalltau_edges is
+# called with, the distribution a quality-control report draws; the reference leaves both to the user)
+# --------------------------------------------------------------------------------------------------
+def _type7(a, b, index, lo):
+    """R's quantile(type = 7) between the order statistics a = x[lo] and b = x[hi]: every product and sum rounded on its
+    own, a zero as +0."""
+    if index == lo or a == b:
+        return a + 0.0
+    h = index - lo
+    wa = (1.0 - h) * a
+    wb = h * b
+    return (wa + wb) + 0.0
+
+
+def _quantiles_numpy(cor, raw, cls, probs, breaks):
+    """The reduction of icikt_quantiles_f64 from full S x S cor and raw matrices, for engines without a quantiles
+    method (the CPU tests' checker engines).  Groups: every pair i < j; with cls also the pairs with cls[i] == cls[j]
+    and those with cls[i] != cls[j].  A pair whose raw is NA is no value (n_na).  With the v valid raw values of a group
+    ascending x[1..v] (a zero counts as +0) and index = 1 + (v - 1) p, order2 holds x[floor(index)] and x[ceil(index)],
+    quantile_raw is R's type 7 between them and quantile_cor the same rule on the cor cells of those two pairs; NA_real_
+    when v = 0.  hist is numpy.histogram(valid raw, bins=breaks), outside the values below the first and above the last
+    break.  Returns (q2 [2, G, n_probs]: cor, raw; order2 [G, n_probs, 2]; n_valid, n_na [G]; hist [G, n_bins];
+    outside [G, 2])."""
+    cor = np.ascontiguousarray(cor, dtype=np.float64)
+    raw = np.ascontiguousarray(raw, dtype=np.float64)
+    probs = np.atleast_1d(np.asarray(probs, dtype=np.float64)).ravel()
+    S = raw.shape[0]
+    iu, ju = np.triu_indices(S, k=1)
+    with np.errstate(invalid="ignore"):      # (NA_real_ is a signalling NaN)
+        r, c = raw[iu, ju] + 0.0, cor[iu, ju] + 0.0
+    if cls is None:
+        members = [np.ones(r.shape[0], dtype=bool)]
+    else:
+        cls = np.asarray(cls)
+        same = cls[iu] == cls[ju]
+        members = [np.ones(r.shape[0], dtype=bool), same, ~same]
+    G, n_probs = len(members), probs.shape[0]
+    n_bins = 0 if breaks is None else len(breaks) - 1
+    q2 = np.empty((2, G, n_probs), dtype=np.float64)
+    order2 = np.empty((G, n_probs, 2), dtype=np.float64)
+    q2.view(np.uint64)[...] = _NA_REAL_BITS
+    order2.view(np.uint64)[...] = _NA_REAL_BITS
+    n_valid, n_na = np.zeros(G, dtype=np.int64), np.zeros(G, dtype=np.int64)
+    hist, outside = np.zeros((G, n_bins), dtype=np.int64), np.zeros((G, 2), dtype=np.int64)
+    for g, member in enumerate(members):
+        ok = member & ~np.isnan(r)
+        x, xc = r[ok], c[ok]
+        v = x.shape[0]
+        n_valid[g], n_na[g] = v, int(member.sum()) - v
+        if n_bins:
+            hist[g] = np.histogram(x, bins=np.asarray(breaks, dtype=np.float64))[0]
+            outside[g] = int(np.sum(x < breaks[0])), int(np.sum(x > breaks[-1]))
+        if v == 0:
+            continue
+        order = np.argsort(x, kind="stable")
+        for k, p in enumerate(probs):
+            index = 1.0 + float(v - 1) * float(p)
+            lo, hi = math.floor(index), math.ceil(index)
+            a, b = order[lo - 1], order[hi - 1]
+            order2[g, k] = x[a], x[b]
+            q2[1, g, k] = _type7(float(x[a]), float(x[b]), index, float(lo))
+            q2[0, g, k] = _type7(float(xc[a]), float(xc[b]), index, float(lo))
+    return q2, order2, n_valid, n_na, hist, outside
+
+
+def ici_kendalltau_quantiles(data_matrix, probs=(0, 0.25, 0.5, 0.75, 1), breaks=200, sample_classes=None,
+                             global_na=(float("nan"), float("inf"), 0), perspective="global", scale_max=True,
+                             alternative="two.sided", continuity=False, colnames=None, engine=None):
+    """Exact quantiles and a histogram of the ICI-Kendall-tau of ALL S (S - 1) / 2 pairs of samples (columns) of a
+    features x samples matrix, without the S x S matrices ``ici_kendalltau`` returns: the 99th percentile
+    ``ici_kendalltau_edges`` is called with, and the distribution a quality-control report draws.
+
+    ``probs``: up to 32 probabilities in [0, 1], any order, repeats allowed.  ``breaks``: an int for that many equal bins
+    over [-1, 1] (``np.linspace(-1.0, 1.0, breaks + 1)``), an array of strictly increasing bin edges, used as given,
+    or None for no histogram; at most 1 024 bins.  ``sample_classes`` gives one label per column and splits the result
+    into the groups ``["all", "within", "between"]`` (pairs of one class, pairs across classes); without it the one
+    group is ``["all"]``.  The other arguments are ``ici_kendalltau``'s (column names are required; a sparse matrix,
+    float32 and integer matrices are read where they lie).  On the HIP engine the reduction runs on the device
+    (icikt_quantiles_f64); a matrix has at most 65 535 samples.
+
+    A pair whose ``raw`` is NA is no value (the reference's warning is raised once per pair of reasons 2-4) and counts
+    in ``n_na``.  ``quantile_raw`` is R's ``quantile(raw, probs, type = 7, na.rm = TRUE)`` -- numpy's "linear" method --
+    over a group's values, exactly: the two order statistics are selected, not estimated.  ``quantile_cor`` is the same
+    over ``cor``; with ``scale_max`` ``cor`` is ``raw`` over the largest ``taumax`` of all pairs.  A group without a
+    value gets NA.  ``counts`` is ``numpy.histogram(raw, bins=breaks)`` per group (the last bin is closed on the right),
+    ``n_below`` and ``n_above`` count the values outside the breaks.  Returns a dict: ``probs``, ``group``,
+    ``quantile_cor``, ``quantile_raw`` (n_group x n_probs), ``n_valid``, ``n_na`` (n_group), ``breaks`` (None without
+    a histogram), ``counts`` (n_group x n_bins), ``n_below``, ``n_above``, ``max_taumax`` and ``run_time``.
+    """
+    data_matrix, names = _as_matrix(data_matrix, colnames, "data_matrix", keep_dtype=True, keep_sparse=True)
+    n_sample = data_matrix.shape[1]
+    if sample_classes is None:
+        levels, cls, groups = ["all"], None, ["all"]
+    else:
+        levels, cls = _class_levels(sample_classes, n_sample, "all")
+        groups = ["all", "within", "between"]
+    if n_sample < 2:
+        raise ValueError("No comparisons to do. Check the list of column names in "
+                         "`include_only` vs those in the samples.")  # R/kendalltau.R:240-247
+    probs_a = np.atleast_1d(np.asarray(probs, dtype=np.float64)).ravel()
+    if probs_a.shape[0] > _lib.QUANTILE_MAX_PROBS or not np.all((probs_a >= 0) & (probs_a <= 1)):
+        raise ValueError(f"`probs` must be at most {_lib.QUANTILE_MAX_PROBS} values in [0, 1]")
+    if breaks is None:
+        breaks_a = None
+    else:
+        if isinstance(breaks, (int, np.integer)) and not isinstance(breaks, (bool, np.bool_)):
+            if not 1 <= int(breaks) <= _lib.HIST_MAX_BINS:
+                raise ValueError(f"`breaks` as a number of bins must be in 1 .. {_lib.HIST_MAX_BINS}")
+            breaks_a = np.linspace(-1.0, 1.0, int(breaks) + 1)
+        else:
+            breaks_a = np.ascontiguousarray(np.atleast_1d(breaks), dtype=np.float64).ravel()
+        if not 2 <= breaks_a.shape[0] <= _lib.HIST_MAX_BINS + 1 or not np.all(np.isfinite(breaks_a)) \
+                or not np.all(np.diff(breaks_a) > 0):
+            raise ValueError(f"`breaks` must be 2 .. {_lib.HIST_MAX_BINS + 1} finite, strictly increasing bin edges")
+    eng = engine or _default_engine()
+    if hasattr(eng, "quantiles"):
+        X, global_na = _mask_on_host(data_matrix, global_na)
+        t1 = time.perf_counter()
+        q2, _order2, n_valid, n_na, hist, outside, max_taumax, rcounts = eng.quantiles(
+            _for_engine(X, eng, fortran=False), probs_a, breaks_a, cls, len(levels), global_na, perspective, alternative,
+            continuity, 0, scale_max)
+        t_diff = time.perf_counter() - t1
+        _warn_pairs(rcounts)
+    else:
+        full = ici_kendalltau(data_matrix, global_na=global_na, perspective=perspective, scale_max=scale_max,
+                              diag_good=True, alternative=alternative, continuity=continuity, colnames=names, engine=eng)
+        t_diff = full["run_time"]
+        cor, raw, taumax = (np.asarray(full[key], dtype=np.float64) for key in ("cor", "raw", "taumax"))
+        q2, _order2, n_valid, n_na, hist, outside = _quantiles_numpy(cor, raw, cls, probs_a, breaks_a)
+        max_taumax = _max_taumax(taumax, np.triu(np.ones((n_sample, n_sample), dtype=bool), k=1))
+    return {"probs": probs_a, "group": groups, "quantile_cor": q2[0], "quantile_raw": q2[1], "n_valid": n_valid,
+            "n_na": n_na, "breaks": breaks_a, "counts": hist, "n_below": outside[:, 0].copy(),
+            "n_above": outside[:, 1].copy(), "max_taumax": max_taumax, "run_time": t_diff}
 
 
 # --------------------------------------------------------------------------------------------------

@@ -1731,6 +1731,7 @@ extern "C" {
 // 1 024-thread / 256-thread shape), tkblock (icikt_topk_* / icikt_edges_* / icikt_class_medians_*: pairs per block of
 // whole combn rows, 1 = a row per block, or per slice of several classes' pair list),
 // medlds (icikt_class_medians_*: partners up to which the select kernel stages a sample's keys in LDS, 0 .. 4096),
+// qbatch (icikt_quantiles_*: targets per batch of the select, 1 .. 32),
 // verbose (0 | 1: print the plan to stderr).
 // (The keys h2d and regfail of rounds 2-3 are gone with the mode they steered: the library no longer page-locks
 // caller memory, icikt_host.h.)
@@ -1771,6 +1772,11 @@ int icikt_debug_set_plan(icikt_ctx* c, const char* spec) {
       ov.medlds = atoi(val.c_str());
       if (ov.medlds < 0 || ov.medlds > icikt::MEDIAN_STAGE_MAX)
         return fail(c, ICIKT_E_INVALID, "debug_set_plan: medlds must be in 0 .. 4096 keys");
+    }
+    else if (key == "qbatch") {
+      ov.qbatch = atoi(val.c_str());
+      if (ov.qbatch < 1 || ov.qbatch > icikt::QUANT_BATCH_MAX)
+        return fail(c, ICIKT_E_INVALID, "debug_set_plan: qbatch must be in 1 .. 32 targets");
     }
     else return fail(c, ICIKT_E_INVALID, "debug_set_plan: unknown key '" + key + "'");
   }

@@ -1,5 +1,5 @@
 // icikt_capi_select.cpp -- the host side the selection entries share (icikt_topk_*, icikt_edges_*,
-// icikt_class_medians_*; declared in icikt_host.h): their common checks, and the run of a call's blocks through the
+// icikt_class_medians_*, icikt_quantiles_*; declared in icikt_host.h): their common checks, and the run of a call's blocks through the
 // pair engine.  Nothing of size S^2 is allocated: each block's records are folded by the entry's kernel before the
 // next block overwrites them.
 #include <hip/hip_runtime.h>

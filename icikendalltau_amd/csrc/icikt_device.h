@@ -1,5 +1,5 @@
 // icikt_device.h -- structures, layouts and launcher declarations shared by the device units (icikt_prepass.hip,
-// icikt_kernels.hip, icikt_epilogue.hip, icikt_cor.hip, icikt_diag.hip, icikt_topk.hip, icikt_edges.hip, icikt_medians.hip) and the C-ABI
+// icikt_kernels.hip, icikt_epilogue.hip, icikt_cor.hip, icikt_diag.hip, icikt_topk.hip, icikt_edges.hip, icikt_medians.hip, icikt_quantiles.hip) and the C-ABI
 // host side (icikt_capi*.cpp, icikt_multi.cpp).  Internal; the public boundary is include/icikt.h.
 #ifndef ICIKT_DEVICE_H
 #define ICIKT_DEVICE_H
@@ -270,6 +270,32 @@ hipError_t launch_median_keep(const double* out4, const int32_t* reasons, long l
 // which a sample's keys are gathered into LDS once (0 .. MEDIAN_STAGE_MAX), above it every pass re-reads the plane
 hipError_t launch_median_select(const MedianClasses& mc, const unsigned long long* kept, const unsigned long long* red,
                                 int S, int scale_max, int stage, double* med2, int32_t* n_valid, hipStream_t s);
+// ---- quantiles and histogram of all pairs (icikt_quantiles.hip) ----
+constexpr int QUANT_MAX_BINS = 1024;    // == ICIKT_HIST_MAX_BINS: k_quant_fold stages 1 025 breaks and 2 x 1 026 counters in LDS
+constexpr int QUANT_HEAD = 4;           // words of a counted group before its bins: n_valid, n_na, below, above
+constexpr int QUANT_BATCH_MAX = 32;     // targets of one select batch: k_quant_count holds 32 x 256 counters (32 KB) in LDS
+// the select's targets: the key of rank `rank` (0-based, among the valid keys ascending) of group `group` (0 every
+// pair, 1 cls[i] == cls[j], 2 the others); prefix starts at 0 and is the key after the eighth pass
+struct QuantTargets {
+  unsigned long long* prefix;
+  long long* rank;
+  int32_t* group;
+};
+// out4 / reasons: the records of n_pairs consecutive pairs of combn(S, 2) from pair `first` on (S <= 65 535).  totals:
+// per counted group c (0 every pair; 1 cls[i] == cls[j], only with cls) QUANT_HEAD + max(n_breaks - 1, 0) words from
+// c times that on, added to (the caller zeroes them before a call's first block): n_valid, n_na, raw below breaks[0],
+// raw above the last break, then the bins as numpy.histogram counts them.  breaks: n_breaks (0, or 2 ..
+// QUANT_MAX_BINS + 1) device doubles, strictly increasing.  kept (may be null): the whole plane, one sortable key
+// (colsort::cor_key, NA_KEY for a pair with a reason code) per pair of the triangle, written at first + e.
+hipError_t launch_quant_fold(const double* out4, const int32_t* reasons, long long n_pairs, long long first, int S,
+                             const int32_t* cls, const double* breaks, int n_breaks, unsigned long long* kept,
+                             unsigned long long* totals, hipStream_t s);
+// one digit (shift = 56, 48 .. 0, in this order) of the radix select over the kept plane of all n_pairs pairs for
+// targets [t0, t0 + nt), nt <= QUANT_BATCH_MAX: count adds to hist [nt][256] (zeroed before the first pass), pick
+// extends the targets' prefixes, reduces their ranks and zeroes hist again
+hipError_t launch_quant_count(const unsigned long long* kept, long long n_pairs, int S, const int32_t* cls,
+                              const QuantTargets& T, int t0, int nt, int shift, unsigned long long* hist, hipStream_t s);
+hipError_t launch_quant_pick(const QuantTargets& T, int t0, int nt, int shift, unsigned long long* hist, hipStream_t s);
 // wide columns: one wave per pair, grid of `blocks` single-wave workgroups that fetch pairs from *task_ctr
 hipError_t launch_k1_wide(const PrepView& pv, const int32_t* pi, const int32_t* pj, PairRaw* raw, int64_t n_pairs,
                           int blocks, size_t lds_bytes, int* task_ctr, hipStream_t s);

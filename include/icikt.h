@@ -369,6 +369,53 @@ int icikt_class_medians_f64(icikt_ctx *ctx, const double *X, int64_t n_feat, int
                             int alternative, int continuity, uint32_t flags, int scale_max, double *med2,
                             int32_t *n_valid, double *max_taumax, int64_t *reason_counts);
 
+/* ---- exact quantiles and a histogram of raw over all pairs, reduced on the device ---------------------------------
+ *
+ * The distribution of the pair values: from a features x samples matrix the exact quantiles (R's quantile(type = 7))
+ * and a histogram of raw over all C(n_samp, 2) pairs -- the cut-off icikt_edges_f64 is called with, the picture a
+ * quality-control report draws -- without anything of size n_samp^2 on the host or as five planes on the device.  The
+ * whole combn triangle runs through the pair engine in blocks of whole rows (the tkblock budget, as icikt_topk_f64).
+ *   groups       n_group = 1 when cls == NULL (n_class is then ignored), else 3: group 0 every pair, group 1 the pairs
+ *                with cls[i] == cls[j], group 2 the pairs with cls[i] != cls[j].  cls[s] in 0 .. n_class - 1, checked
+ *                as icikt_class_medians_f64 checks it.
+ *   values       a pair with a non-zero reason code has an NA raw: it is no value and counts in n_na[g]; n_valid[g]
+ *                counts the others.  Values are ordered by the sortable key of icikt_class_medians_f64: -0 and +0 are
+ *                one value, and a zero comes back as +0.
+ *   probs        n_probs (0 .. ICIKT_QUANTILE_MAX_PROBS) doubles in [0, 1], in any order, repeats allowed; NaN or a
+ *                value outside is ICIKT_E_INVALID, the message names the index.  n_probs = 0: no quantiles, and nothing
+ *                is kept per pair.
+ *   breaks       n_breaks = 0 (no histogram), or 2 .. ICIKT_HIST_MAX_BINS + 1 finite, strictly increasing doubles
+ *                (else ICIKT_E_INVALID, the message names the index).  The device only compares raw with these values.
+ *   order2       [n_group][n_probs][2]: with the v = n_valid[g] values ascending x[1..v], index = 1 + (v - 1) p in
+ *                double arithmetic, the order statistics x[floor(index)] and x[ceil(index)]; NA_real_ (bits
+ *                0x7FF00000000007A2) twice when v = 0
+ *   q2           [2][n_group][n_probs], cor then raw.  raw: a = x[lo], b = x[hi], h = index - lo: a when index == lo or
+ *                a == b, else (1 - h) a + h b, every operation rounded on its own (no fused multiply-add), a zero as
+ *                +0.  cor: the same rule on a / m and b / m, m = scale_max ? max(taumax, na.rm = TRUE) over all
+ *                computed pairs : 1 -- the operands icikt_matrix_f64's cor cells are made of.  NA_real_ when v = 0.
+ *   hist         [n_group][n_breaks - 1], numpy.histogram(valid raw, bins = breaks): bin k counts breaks[k] <= raw <
+ *                breaks[k + 1], the last bin also raw == breaks[n_breaks - 1]
+ *   outside      [n_group][2]: valid raw < breaks[0], valid raw > breaks[n_breaks - 1] (0 without breaks)
+ * q2 and order2 are required when n_probs > 0, hist when n_breaks > 0; n_valid, n_na ([n_group] each), outside,
+ * max_taumax and reason_counts (as icikt_topk_f64) are optional.  n_samp <= ICIKT_TOPK_MAX_SAMPLES (ICIKT_E_INVALID
+ * beyond, the message names the limit); n_feat, global_na, the state the call leaves behind (none: icikt_run_dev
+ * answers ICIKT_E_STATE and icikt_num_pairs -1) and the refusal of bad arguments before anything -- the context or an
+ * output -- is touched: as icikt_topk_f64.  The result is a pure function of the input: integer counts alone, whatever
+ * the block cut.
+ * Device memory: the prepared matrix, one block's buffers, and with n_probs > 0 8 bytes per pair of the triangle for
+ * the kept keys (n_samp = 65 535: 17 GB; group membership is recomputed from a pair's index, not kept); besides that
+ * 4 n_samp bytes of class index, 8 n_breaks + 16 (n_breaks + 3) bytes of breaks and totals and 69 KB for the select's
+ * targets and digit histograms.  A failed allocation is ICIKT_E_HIP.
+ * With ICIKT_FLAG_TIMING the fold and select kernels are accounted under ICIKT_K_EPILOGUE.
+ * icikt_quantiles_in / icikt_quantiles_csc: the same on a typed view / a CSC view of the matrix (below). */
+#define ICIKT_QUANTILE_MAX_PROBS 32
+#define ICIKT_HIST_MAX_BINS 1024
+int icikt_quantiles_f64(icikt_ctx *ctx, const double *X, int64_t n_feat, int64_t n_samp, int64_t ld,
+                        const double *global_na, int n_global_na, const int32_t *cls, int n_class, int perspective,
+                        int alternative, int continuity, uint32_t flags, int scale_max, const double *probs, int n_probs,
+                        const double *breaks, int n_breaks, double *q2, double *order2, int64_t *n_valid, int64_t *n_na,
+                        int64_t *hist, int64_t *outside, double *max_taumax, int64_t *reason_counts);
+
 /* ---- several GPUs behind one call (what the R glue binds when n_gpu > 1) ----------------------
  *
  * Replaces the reference's worker fan-out, computation$split_fun(split_comparisons, ici_split, ...)
@@ -520,6 +567,11 @@ int icikt_class_medians_in(icikt_ctx *ctx, const icikt_input *X, int64_t n_feat,
                            int n_global_na, const int32_t *cls, int n_class, int perspective, int alternative,
                            int continuity, uint32_t flags, int scale_max, double *med2, int32_t *n_valid,
                            double *max_taumax, int64_t *reason_counts);
+int icikt_quantiles_in(icikt_ctx *ctx, const icikt_input *X, int64_t n_feat, int64_t n_samp, const double *global_na,
+                       int n_global_na, const int32_t *cls, int n_class, int perspective, int alternative,
+                       int continuity, uint32_t flags, int scale_max, const double *probs, int n_probs,
+                       const double *breaks, int n_breaks, double *q2, double *order2, int64_t *n_valid, int64_t *n_na,
+                       int64_t *hist, int64_t *outside, double *max_taumax, int64_t *reason_counts);
 int icikt_matrix_in(icikt_ctx *ctx, const icikt_input *X, int64_t n_feat, int64_t n_samp, const double *global_na,
                     int n_global_na, const int32_t *pi, const int32_t *pj, int64_t n_pairs, int perspective,
                     int alternative, int continuity, uint32_t flags, int scale_max, int diag_good, double *out5,
@@ -576,6 +628,11 @@ int icikt_class_medians_csc(icikt_ctx *ctx, const icikt_csc_input *X, int64_t n_
                             const double *global_na, int n_global_na, const int32_t *cls, int n_class, int perspective,
                             int alternative, int continuity, uint32_t flags, int scale_max, double *med2,
                             int32_t *n_valid, double *max_taumax, int64_t *reason_counts);
+int icikt_quantiles_csc(icikt_ctx *ctx, const icikt_csc_input *X, int64_t n_feat, int64_t n_samp, const double *global_na,
+                        int n_global_na, const int32_t *cls, int n_class, int perspective, int alternative,
+                        int continuity, uint32_t flags, int scale_max, const double *probs, int n_probs,
+                        const double *breaks, int n_breaks, double *q2, double *order2, int64_t *n_valid, int64_t *n_na,
+                        int64_t *hist, int64_t *outside, double *max_taumax, int64_t *reason_counts);
 int icikt_missingness_csc(icikt_ctx *ctx, const icikt_csc_input *X, int64_t n_feat, int64_t n_samp, const int32_t *pi,
                           const int32_t *pj, int64_t n_pairs, int64_t *missingness);
 int icikt_col_medians_csc(icikt_ctx *ctx, const icikt_csc_input *X, int64_t n_feat, int64_t n_samp,
@@ -611,7 +668,8 @@ int icikt_selftest(icikt_ctx *ctx);
  * may hold -- a block is always at least one row, so tkblock=1 runs a row per block; icikt_class_medians_*: the same
  * budget for the rows of one class and for the slices of several classes' pair list), medlds (icikt_class_medians_*:
  * the partners up to which the select kernel gathers a sample's keys into LDS once, 0 .. 4096; a sample with more
- * re-reads the kept plane in every pass), verbose (0 | 1: print the chosen
+ * re-reads the kept plane in every pass), qbatch (icikt_quantiles_*: the targets -- distinct (group, rank) -- the
+ * select runs per batch of eight passes, 1 .. 32), verbose (0 | 1: print the chosen
  * plan to stderr). */
 int icikt_debug_set_plan(icikt_ctx *ctx, const char *spec);
 /* Development hook: per step kind of the pair kernel (hot loop, hot step in the main loop, MIXED, GROUP, general,
