@@ -20,11 +20,12 @@ SOURCES = [os.path.join(_PKG, "csrc", f) for f in ("icikt_kernels.hip", "icikt_p
                                                        "icikt_capi_topk.cpp", "icikt_edges.hip", "icikt_capi_edges.cpp",
                                                        "icikt_diag.hip", "icikt_ingest.hip", "icikt_sparse.hip",
                                                        "icikt_medians.hip", "icikt_capi_medians.cpp", "icikt_capi_select.cpp",
-                                                       "icikt_quantiles.hip", "icikt_capi_quantiles.cpp")]
+                                                       "icikt_quantiles.hip", "icikt_capi_quantiles.cpp",
+                                                       "icikt_classmat.hip", "icikt_capi_classmat.cpp")]
 HEADERS = [os.path.join(_ROOT, "include", "icikt.h"), os.path.join(_PKG, "csrc", "icikt_device.h"),
            os.path.join(_PKG, "csrc", "icikt_wave.h"), os.path.join(_PKG, "csrc", "icikt_host.h"),
            os.path.join(_PKG, "csrc", "icikt_transfer.h"), os.path.join(_PKG, "csrc", "icikt_colsort.h"),
-           os.path.join(_PKG, "csrc", "icikt_blocks.h")]
+           os.path.join(_PKG, "csrc", "icikt_blocks.h"), os.path.join(_PKG, "csrc", "icikt_select.h")]
 
 # include/icikt.h
 SUCCESS = 0
@@ -77,6 +78,7 @@ EXPORTS = (
     "icikt_edges_f64", "icikt_edges_in", "icikt_edges_csc",
     "icikt_class_medians_f64", "icikt_class_medians_in", "icikt_class_medians_csc",
     "icikt_quantiles_f64", "icikt_quantiles_in", "icikt_quantiles_csc",
+    "icikt_class_matrix_f64", "icikt_class_matrix_in", "icikt_class_matrix_csc",
 )
 
 # icikt_input: the caller's matrix as a typed, strided view (ICIKT_DTYPE_*, ICIKT_ORDER_*)
@@ -363,6 +365,7 @@ def lib():
                                   c_int, c_u32, c_int, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]
     L.icikt_class_medians_f64.argtypes = [c_vp, c_vp, c_i64, c_i64, c_i64, c_vp, c_int, c_vp, c_int, c_int, c_int, c_int,
                                           c_u32, c_int, c_vp, c_vp, c_vp, c_vp]
+    L.icikt_class_matrix_f64.argtypes = L.icikt_class_medians_f64.argtypes
     L.icikt_quantiles_f64.argtypes = [c_vp, c_vp, c_i64, c_i64, c_i64, c_vp, c_int, c_vp, c_int, c_int, c_int, c_int,
                                       c_u32, c_int, c_vp, c_int, c_vp, c_int, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp,
                                       c_vp]
@@ -371,13 +374,13 @@ def lib():
     L.icikt_debug_step_stats.argtypes = [c_vp, c_vp, c_int]
     # the *_in twins: (ctx, const icikt_input*, n_feat, n_samp, ...) where the _f64 entry has (ctx, X, n_feat, n_samp, ld, ...)
     for nm in ("pairs", "matrix", "pairs_complete", "missingness", "cor_pairs", "col_medians", "censor_counts",
-               "rank_order", "topk", "edges", "class_medians", "quantiles"):
+               "rank_order", "topk", "edges", "class_medians", "quantiles", "class_matrix"):
         f64 = getattr(L, f"icikt_{nm}_f64").argtypes
         getattr(L, f"icikt_{nm}_in").argtypes = [c_vp, ctypes.POINTER(InputView), c_i64, c_i64] + list(f64[5:])
     L.icikt_convert_dev.argtypes = [c_vp, c_vp, c_int, c_int, c_i64, c_i64, c_i64, c_vp, c_i64]
     # the *_csc twins: (ctx, const icikt_csc_input*, n_feat, n_samp, ...)
     for nm in ("pairs", "matrix", "missingness", "col_medians", "censor_counts", "rank_order", "topk", "edges",
-               "class_medians", "quantiles"):
+               "class_medians", "quantiles", "class_matrix"):
         f64 = getattr(L, f"icikt_{nm}_f64").argtypes
         getattr(L, f"icikt_{nm}_csc").argtypes = [c_vp, ctypes.POINTER(CscInput), c_i64, c_i64] + list(f64[5:])
     L.icikt_scatter_csc_dev.argtypes = [c_vp, c_vp, c_vp, c_vp, c_int, c_int, ctypes.c_double, c_i64, c_i64, c_vp, c_i64]
@@ -680,6 +683,32 @@ class Context:
         self._chk(fn(self._h, *xargs, *gna[1:], _ptr(cls_a), int(n_class), *codes, int(bool(continuity)), flags,
                      int(bool(scale_max)), _ptr(med2), _ptr(n_valid), _ptr(mx), _ptr(rc5)), fname)
         return med2, n_valid, float(mx[0]), rc5
+
+    def class_matrix(self, X, cls=None, n_class=1, global_na=None, perspective="global", alternative="two.sided",
+                     continuity=False, flags: int = 0, scale_max=True):
+        """Every sample's median ICI-Kendall-tau to every class, reduced on the device (icikt_class_matrix_f64): all
+        pairs are computed, and nothing of size S x S exists on the host or as five planes on the device.  cls: a class
+        index in 0 .. n_class - 1 per column (None: one class, a table of one column); X and global_na as matrix()
+        takes them.  Returns (med2 [2, S, n_class]: cor, raw -- NA_real_ for a cell without a valid partner; n_valid
+        [S, n_class]; max_taumax: the largest taumax of ALL pairs, cor's denominator; reason_counts [5] over all
+        pairs).  The arrays are views of the library's layout, the sample index fastest.  The argument checks are the
+        library's: a class index out of range, more than 65 535 classes or a bad perspective raises IciktError."""
+        fn, fname, xargs, n_feat, n_samp, flags, _keep = self._entry("class_matrix", X, flags)
+        if cls is None:
+            cls_a = None
+            n_class = 1
+        else:
+            cls_a = np.ascontiguousarray(cls, dtype=np.int32)
+            if cls_a.shape != (n_samp,):
+                raise ValueError("cls must give one class per column")
+        n_class = int(n_class)
+        room = n_class if 1 <= n_class <= 65535 else 1    # (the library refuses the others before it writes)
+        gna, codes, mx, rc5 = _select_args(global_na, perspective, alternative)
+        med2 = np.empty((2, room, n_samp), dtype=np.float64)
+        n_valid = np.zeros((room, n_samp), dtype=np.int32)
+        self._chk(fn(self._h, *xargs, *gna[1:], _ptr(cls_a), n_class, *codes, int(bool(continuity)), flags,
+                     int(bool(scale_max)), _ptr(med2), _ptr(n_valid), _ptr(mx), _ptr(rc5)), fname)
+        return med2.transpose(0, 2, 1), n_valid.T, float(mx[0]), rc5
 
     def quantiles(self, X, probs=(), breaks=None, cls=None, n_class=1, global_na=None, perspective="global",
                   alternative="two.sided", continuity=False, flags: int = 0, scale_max=True):

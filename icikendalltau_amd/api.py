@@ -77,6 +77,13 @@ class HipEngine:
         return self.ctx.class_medians(data_matrix, cls, n_class, global_na, perspective, alternative, continuity,
                                       self.flags | flags, scale_max)
 
+    def class_matrix(self, data_matrix, cls=None, n_class=1, global_na=None, perspective="global",
+                     alternative="two.sided", continuity=False, flags=0, scale_max=True):
+        """Every sample's median to every class, reduced on the device (icikt_class_matrix_f64): Context.class_matrix's
+        contract."""
+        return self.ctx.class_matrix(data_matrix, cls, n_class, global_na, perspective, alternative, continuity,
+                                     self.flags | flags, scale_max)
+
     def quantiles(self, data_matrix, probs=(), breaks=None, cls=None, n_class=1, global_na=None, perspective="global",
                   alternative="two.sided", continuity=False, flags=0, scale_max=True):
         """Exact quantiles and a histogram of raw over all pairs, reduced on the device (icikt_quantiles_f64):
@@ -182,6 +189,11 @@ class MultiHipEngine(HipEngine):
                       alternative="two.sided", continuity=False, flags=0, scale_max=True):  # the reduction runs on one device
         return self._one().class_medians(data_matrix, cls, n_class, global_na, perspective, alternative, continuity,
                                          self.flags | flags, scale_max)
+
+    def class_matrix(self, data_matrix, cls=None, n_class=1, global_na=None, perspective="global",
+                     alternative="two.sided", continuity=False, flags=0, scale_max=True):  # the reduction runs on one device
+        return self._one().class_matrix(data_matrix, cls, n_class, global_na, perspective, alternative, continuity,
+                                        self.flags | flags, scale_max)
 
     def quantiles(self, data_matrix, probs=(), breaks=None, cls=None, n_class=1, global_na=None, perspective="global",
                   alternative="two.sided", continuity=False, flags=0, scale_max=True):   # the select runs on one device
@@ -891,6 +903,103 @@ def ici_kendalltau_medians(data_matrix, sample_classes=None, global_na=(float("n
     labels = [levels[k] for k in cls]
     return {"sample_id": list(names), "sample_class": labels, "med_cor": med2[0], "med_raw": med2[1],
             "n_valid": n_valid, "max_taumax": max_taumax, "run_time": t_diff}
+
+
+# --------------------------------------------------------------------------------------------------
+# ici_kendalltau_class_matrix: every sample's median ICI-Kendall-tau to every class (the table a mislabelled or
+# swapped sample shows up in, and from which an unlabelled one is assigned; the reference leaves it to the user)
+# --------------------------------------------------------------------------------------------------
+def _class_matrix_numpy(cor, raw, cls, n_class):
+    """The reduction of icikt_class_matrix_f64 from full S x S cor and raw matrices, for engines without a class_matrix
+    method (the CPU tests' checker engines).  The partners of cell (s, c) are the samples t != s with cls[t] == c whose
+    raw with s is not NA; n_valid[s, c] counts them.  med_raw[s, c] is R's median(raw, na.rm = TRUE) over them
+    (_class_medians_numpy's rule), med_cor[s, c] the same rule on the cor cells of the partners that supplied the middle
+    raw values.  Without partners both are NA_real_.  Returns (med2 [2, S, n_class]: cor, raw; n_valid [S, n_class])."""
+    cor = np.ascontiguousarray(cor, dtype=np.float64)
+    raw = np.ascontiguousarray(raw, dtype=np.float64)
+    cls = np.asarray(cls)
+    S = raw.shape[0]
+    med2 = np.empty((2, S, n_class), dtype=np.float64)
+    med2.view(np.uint64)[...] = _NA_REAL_BITS
+    n_valid = np.zeros((S, n_class), dtype=np.int32)
+    members = [cls == c for c in range(n_class)]
+    for s in range(S):
+        valid = ~np.isnan(raw[s])
+        valid[s] = False
+        for c in range(n_class):
+            partners = np.nonzero(members[c] & valid)[0]
+            v = len(partners)
+            n_valid[s, c] = v
+            if v == 0:
+                continue
+            order = np.argsort(raw[s, partners] + 0.0, kind="stable")
+            mid = partners[order[[(v - 1) // 2, v // 2]]]       # (twice the same partner when v is odd)
+            for q, mat in ((1, raw), (0, cor)):
+                a, b = float(mat[s, mid[0]]) + 0.0, float(mat[s, mid[1]]) + 0.0
+                med2[q, s, c] = a if v & 1 else _r_median_pair(a, b)
+    return med2, n_valid
+
+
+def _nearest_class(med_raw, n_valid, levels):
+    """Per sample the label of the class with the largest med_raw among the cells with a partner; ties go to the class
+    that is earlier in `levels`; None when no cell has one."""
+    med_raw = np.asarray(med_raw, dtype=np.float64)
+    has = np.asarray(n_valid) > 0
+    score = np.where(has, med_raw, -np.inf)
+    best = np.argmax(score, axis=1) if score.shape[1] else np.zeros(score.shape[0], dtype=np.intp)   # (the first maximum)
+    return [levels[int(k)] if row.any() else None for k, row in zip(best, has)]
+
+
+def ici_kendalltau_class_matrix(data_matrix, sample_classes, global_na=(float("nan"), float("inf"), 0),
+                                perspective="global", scale_max=True, alternative="two.sided", continuity=False,
+                                colnames=None, engine=None):
+    """For every sample (column) of a features x samples matrix the median ICI-Kendall-tau to the members of EVERY
+    class: the S x C table in which a mislabelled or swapped sample correlates better with another class than with the
+    one it is labelled as, and from which a new sample is assigned to its nearest class -- without the S x S matrices
+    ``ici_kendalltau`` returns.
+
+    ``sample_classes`` gives one label per column (required); the other arguments are ``ici_kendalltau``'s (column names
+    are required; a sparse matrix, float32 and integer matrices are read where they lie).  On the HIP engine the
+    reduction runs on the device (icikt_class_matrix_f64); a matrix has at most 65 535 samples and 65 535 classes.
+
+    The partners of cell (s, c) are the samples of class c other than s whose pair with s has a ``raw`` that is not NA
+    (the reference's warning is raised once per pair of reasons 2-4, over all pairs).  ``med_raw`` is R's
+    ``median(raw, na.rm = TRUE)`` over them and ``med_cor`` the same over ``cor``; with ``scale_max`` ``cor`` is ``raw``
+    over the largest ``taumax`` of ALL S (S - 1) / 2 pairs, as in ``ici_kendalltau``.  A cell without a partner (the own
+    cell of a singleton among them) is NA.  The own-class column is ``ici_kendalltau_medians``' ``med_raw``.  Returns a
+    dict: ``sample_id`` and ``sample_class`` (names and labels in column order), ``classes`` (the levels, in the column
+    order of the tables), ``med_cor``, ``med_raw``, ``n_valid`` (S x C each), ``nearest_class`` (per sample the label
+    of the class with the largest ``med_raw`` among the cells with a partner, ties to the earlier class, None without
+    one), ``max_taumax`` and ``run_time``.
+    """
+    data_matrix, names = _as_matrix(data_matrix, colnames, "data_matrix", keep_dtype=True, keep_sparse=True)
+    n_sample = data_matrix.shape[1]
+    if sample_classes is None:
+        raise ValueError("`sample_classes` must give one class per column")
+    levels, cls = _class_levels(sample_classes, n_sample, "all")
+    if n_sample < 2:
+        raise ValueError("No comparisons to do. Check the list of column names in "
+                         "`include_only` vs those in the samples.")  # R/kendalltau.R:240-247
+    eng = engine or _default_engine()
+    if hasattr(eng, "class_matrix"):
+        X, global_na = _mask_on_host(data_matrix, global_na)
+        t1 = time.perf_counter()
+        med2, n_valid, max_taumax, rcounts = eng.class_matrix(_for_engine(X, eng, fortran=False), cls, len(levels),
+                                                              global_na, perspective, alternative, continuity, 0,
+                                                              scale_max)
+        t_diff = time.perf_counter() - t1
+        _warn_pairs(rcounts)
+    else:
+        full = ici_kendalltau(data_matrix, global_na=global_na, perspective=perspective, scale_max=scale_max,
+                              diag_good=True, alternative=alternative, continuity=continuity, colnames=names, engine=eng)
+        t_diff = full["run_time"]
+        cor, raw = (np.asarray(full[key], dtype=np.float64) for key in ("cor", "raw"))
+        med2, n_valid = _class_matrix_numpy(cor, raw, cls, len(levels))
+        max_taumax = _max_taumax(full["taumax"], np.triu_indices(n_sample, k=1))
+    labels = [levels[k] for k in cls]
+    return {"sample_id": list(names), "sample_class": labels, "classes": list(levels), "med_cor": med2[0],
+            "med_raw": med2[1], "n_valid": n_valid, "nearest_class": _nearest_class(med2[1], n_valid, levels),
+            "max_taumax": max_taumax, "run_time": t_diff}
 
 
 # --------------------------------------------------------------------------------------------------

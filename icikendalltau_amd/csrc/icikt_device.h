@@ -1,5 +1,5 @@
 // icikt_device.h -- structures, layouts and launcher declarations shared by the device units (icikt_prepass.hip,
-// icikt_kernels.hip, icikt_epilogue.hip, icikt_cor.hip, icikt_diag.hip, icikt_topk.hip, icikt_edges.hip, icikt_medians.hip, icikt_quantiles.hip) and the C-ABI
+// icikt_kernels.hip, icikt_epilogue.hip, icikt_cor.hip, icikt_diag.hip, icikt_topk.hip, icikt_edges.hip, icikt_medians.hip, icikt_quantiles.hip, icikt_classmat.hip) and the C-ABI
 // host side (icikt_capi*.cpp, icikt_multi.cpp).  Internal; the public boundary is include/icikt.h.
 #ifndef ICIKT_DEVICE_H
 #define ICIKT_DEVICE_H
@@ -270,6 +270,14 @@ hipError_t launch_median_keep(const double* out4, const int32_t* reasons, long l
 // which a sample's keys are gathered into LDS once (0 .. MEDIAN_STAGE_MAX), above it every pass re-reads the plane
 hipError_t launch_median_select(const MedianClasses& mc, const unsigned long long* kept, const unsigned long long* red,
                                 int S, int scale_max, int stage, double* med2, int32_t* n_valid, hipStream_t s);
+// ---- per-sample medians to every class (icikt_classmat.hip) ----
+constexpr int CLASS_MATRIX_MAX_CLASSES = 65535;   // k_class_select's grid is (S, n_class): the second dimension's limit
+// kept: the whole combn(S, 2) plane launch_median_keep writes; member [S]: the sample indices sorted stably by class;
+// first [n_class + 1]: class c is member[first[c] .. first[c + 1]).  med2 [2][n_class][S] (cor, raw; NA_real_ for a
+// cell without partners), n_valid [n_class][S]; red and stage as launch_median_select takes them
+hipError_t launch_class_select(const int32_t* member, const int32_t* first, const unsigned long long* kept,
+                               const unsigned long long* red, int S, int n_class, int scale_max, int stage, double* med2,
+                               int32_t* n_valid, hipStream_t s);
 // ---- quantiles and histogram of all pairs (icikt_quantiles.hip) ----
 constexpr int QUANT_MAX_BINS = 1024;    // == ICIKT_HIST_MAX_BINS: k_quant_fold stages 1 025 breaks and 2 x 1 026 counters in LDS
 constexpr int QUANT_HEAD = 4;           // words of a counted group before its bins: n_valid, n_na, below, above

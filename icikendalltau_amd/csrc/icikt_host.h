@@ -142,6 +142,14 @@ struct icikt_ctx {
     DevBuf<double> med2;
   } med;
 
+  // per-sample medians to every class (icikt_class_matrix_f64): the kept plane (a key per pair of the triangle), the
+  // samples sorted by class with each class's range, and the results per (class, sample) cell
+  struct ClassMatBufs {
+    DevBuf<unsigned long long> kept;
+    DevBuf<int32_t> member, first, n_valid;
+    DevBuf<double> med2;
+  } cmat;
+
   // quantiles and histogram of all pairs (icikt_quantiles_f64): the kept plane (a key per pair of the triangle, only
   // when quantiles are asked for), the class index, the breaks, the counted groups' totals, and the select's targets
   // (QuantTargets) with their digit histograms
@@ -171,7 +179,7 @@ struct icikt_ctx {
     int solo = -1;      // 0: SOLO steps of the tie program run as MIXED steps (with the in-step chains)
     int list = -1;      // list mode (range counts per listed tie group) up to this many tie groups: count mode takes over above
     long long tkblock = -1;   // icikt_topk_*, icikt_edges_*, icikt_class_medians_*, icikt_quantiles_*: pairs a block (whole combn rows, or a slice of the class list) may hold (default: the library's budget)
-    int medlds = -1;          // icikt_class_medians_*: partners up to which the select kernel gathers a sample's keys into LDS (default: MEDIAN_STAGE_MAX)
+    int medlds = -1;          // icikt_class_medians_*, icikt_class_matrix_*: partners up to which the select kernel gathers a sample's keys into LDS (default: MEDIAN_STAGE_MAX)
     int qbatch = -1;          // icikt_quantiles_*: targets the select runs per batch (default: QUANT_BATCH_MAX)
     bool verbose = false;
   } plan_ov;
@@ -248,7 +256,7 @@ int check_pair_args(icikt_ctx* c, const char* who, const MatrixSrc& X, int64_t n
                     const int32_t* pi, const int32_t* pj, int64_t* n_pairs, const void* out, bool out5,
                     int perspective, int alternative);
 
-// ---- the selection entries (icikt_topk_*, icikt_edges_*, icikt_class_medians_*, icikt_quantiles_*): one driver, icikt_capi_select.cpp ----
+// ---- the selection entries (icikt_topk_*, icikt_edges_*, icikt_class_medians_*, icikt_quantiles_*, icikt_class_matrix_*): one driver, icikt_capi_select.cpp ----
 // (the blocks a call runs in: icikt_blocks.h; DESIGN.md "adding a selection entry")
 // the arguments the entries share
 struct SelectArgs {

@@ -416,6 +416,45 @@ int icikt_quantiles_f64(icikt_ctx *ctx, const double *X, int64_t n_feat, int64_t
                         const double *breaks, int n_breaks, double *q2, double *order2, int64_t *n_valid, int64_t *n_na,
                         int64_t *hist, int64_t *outside, double *max_taumax, int64_t *reason_counts);
 
+/* ---- per-sample median ICI-Kendall-tau to every class, reduced on the device --------------------------------------
+ *
+ * The other half of icikt_class_medians_f64: for every column (sample) s of X and every class c the median of raw (and
+ * of cor) over the members of c -- the table in which a mislabelled or swapped sample correlates better with another
+ * class than with its own, and from which an unlabelled sample is assigned to its nearest class -- without anything of
+ * size n_samp^2 on the host or as five planes on the device.  The whole combn triangle runs through the pair engine in
+ * blocks of whole rows (the tkblock budget, as icikt_topk_f64); a kernel keeps each pair's raw as a sortable 64-bit
+ * key, and after the last block a selection kernel finds every cell's median by a radix select over the keys of the
+ * sample's pairs with the class's members.
+ *   classes      cls[s] in 0 .. n_class - 1 per sample; cls == NULL: one class (n_class is then ignored and the table
+ *                has one column).  A class may be empty.  n_class <= 65 535, the second dimension of the select
+ *                kernel's grid; beyond it, and for a class index outside the range, ICIKT_E_INVALID before anything is
+ *                touched.
+ *   partners     of cell (s, c): the members t != s of class c whose pair with s has reason code 0 (raw is not NA);
+ *                n_valid[s, c] is their count
+ *   med_raw      R's median(raw, na.rm = TRUE) over the partners, by icikt_class_medians_f64's rule: the middle value, or
+ *                the mean of the two middle values, a zero returned as +0; NA_real_ (bits 0x7FF00000000007A2) when
+ *                n_valid[s, c] == 0: an empty class, the sample's own singleton class, NA pairs alone
+ *   med_cor      the same rule on a / m (and b / m) for the one or two middle raw values a (and b), m = scale_max ?
+ *                max(taumax, na.rm = TRUE) over ALL C(n_samp, 2) pairs : 1 -- the operands are bit for bit the cor cells
+ *                of icikt_matrix_f64 over all pairs.  Without scale_max med_cor equals med_raw.
+ * The own-class column c = cls[s] carries the med_raw and n_valid of icikt_class_medians_f64 bit for bit; with one class
+ * med_cor agrees as well, both entries then scaling by the same m.
+ * med2: [2][n_class][n_samp], cor then raw, the sample index fastest (column-major n_samp x n_class planes); n_valid
+ * (optional): [n_class][n_samp] in the same layout; max_taumax (optional): m, -Inf when no pair had one; reason_counts
+ * (optional): [5] pairs of the triangle per reason code.  n_samp <= ICIKT_TOPK_MAX_SAMPLES (ICIKT_E_INVALID beyond, the
+ * message names the limit); n_feat, global_na, the state the call leaves behind (none: icikt_run_dev answers
+ * ICIKT_E_STATE and icikt_num_pairs -1) and the refusal of bad arguments before anything -- the context or an output --
+ * is touched: as icikt_topk_f64.
+ * Device memory: the prepared matrix, one block's buffers, 8 bytes per pair of the triangle for the kept keys (n_samp =
+ * 65 535: 17 GB), 4 (n_samp + n_class + 1) bytes of member list and class ranges and 20 n_samp n_class bytes of
+ * results; a failed allocation is ICIKT_E_HIP.
+ * With ICIKT_FLAG_TIMING the keep and select kernels are accounted under ICIKT_K_EPILOGUE.
+ * icikt_class_matrix_in / icikt_class_matrix_csc: the same on a typed view / a CSC view of the matrix (below). */
+int icikt_class_matrix_f64(icikt_ctx *ctx, const double *X, int64_t n_feat, int64_t n_samp, int64_t ld,
+                           const double *global_na, int n_global_na, const int32_t *cls, int n_class, int perspective,
+                           int alternative, int continuity, uint32_t flags, int scale_max, double *med2,
+                           int32_t *n_valid, double *max_taumax, int64_t *reason_counts);
+
 /* ---- several GPUs behind one call (what the R glue binds when n_gpu > 1) ----------------------
  *
  * Replaces the reference's worker fan-out, computation$split_fun(split_comparisons, ici_split, ...)
@@ -572,6 +611,10 @@ int icikt_quantiles_in(icikt_ctx *ctx, const icikt_input *X, int64_t n_feat, int
                        int continuity, uint32_t flags, int scale_max, const double *probs, int n_probs,
                        const double *breaks, int n_breaks, double *q2, double *order2, int64_t *n_valid, int64_t *n_na,
                        int64_t *hist, int64_t *outside, double *max_taumax, int64_t *reason_counts);
+int icikt_class_matrix_in(icikt_ctx *ctx, const icikt_input *X, int64_t n_feat, int64_t n_samp, const double *global_na,
+                          int n_global_na, const int32_t *cls, int n_class, int perspective, int alternative,
+                          int continuity, uint32_t flags, int scale_max, double *med2, int32_t *n_valid,
+                          double *max_taumax, int64_t *reason_counts);
 int icikt_matrix_in(icikt_ctx *ctx, const icikt_input *X, int64_t n_feat, int64_t n_samp, const double *global_na,
                     int n_global_na, const int32_t *pi, const int32_t *pj, int64_t n_pairs, int perspective,
                     int alternative, int continuity, uint32_t flags, int scale_max, int diag_good, double *out5,
@@ -633,6 +676,10 @@ int icikt_quantiles_csc(icikt_ctx *ctx, const icikt_csc_input *X, int64_t n_feat
                         int continuity, uint32_t flags, int scale_max, const double *probs, int n_probs,
                         const double *breaks, int n_breaks, double *q2, double *order2, int64_t *n_valid, int64_t *n_na,
                         int64_t *hist, int64_t *outside, double *max_taumax, int64_t *reason_counts);
+int icikt_class_matrix_csc(icikt_ctx *ctx, const icikt_csc_input *X, int64_t n_feat, int64_t n_samp,
+                           const double *global_na, int n_global_na, const int32_t *cls, int n_class, int perspective,
+                           int alternative, int continuity, uint32_t flags, int scale_max, double *med2,
+                           int32_t *n_valid, double *max_taumax, int64_t *reason_counts);
 int icikt_missingness_csc(icikt_ctx *ctx, const icikt_csc_input *X, int64_t n_feat, int64_t n_samp, const int32_t *pi,
                           const int32_t *pj, int64_t n_pairs, int64_t *missingness);
 int icikt_col_medians_csc(icikt_ctx *ctx, const icikt_csc_input *X, int64_t n_feat, int64_t n_samp,
