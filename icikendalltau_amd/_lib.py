@@ -21,7 +21,8 @@ SOURCES = [os.path.join(_PKG, "csrc", f) for f in ("icikt_kernels.hip", "icikt_p
                                                        "icikt_diag.hip", "icikt_ingest.hip", "icikt_sparse.hip",
                                                        "icikt_medians.hip", "icikt_capi_medians.cpp", "icikt_capi_select.cpp",
                                                        "icikt_quantiles.hip", "icikt_capi_quantiles.cpp",
-                                                       "icikt_classmat.hip", "icikt_capi_classmat.cpp")]
+                                                       "icikt_classmat.hip", "icikt_capi_classmat.cpp",
+                                                       "icikt_padjust.hip", "icikt_capi_padjust.cpp")]
 HEADERS = [os.path.join(_ROOT, "include", "icikt.h"), os.path.join(_PKG, "csrc", "icikt_device.h"),
            os.path.join(_PKG, "csrc", "icikt_wave.h"), os.path.join(_PKG, "csrc", "icikt_host.h"),
            os.path.join(_PKG, "csrc", "icikt_transfer.h"), os.path.join(_PKG, "csrc", "icikt_colsort.h"),
@@ -44,6 +45,8 @@ TOPK_MAX = 256                # ICIKT_TOPK_MAX: partners per sample of icikt_top
 TOPK_MAX_SAMPLES = 65535      # ICIKT_TOPK_MAX_SAMPLES
 QUANTILE_MAX_PROBS = 32       # ICIKT_QUANTILE_MAX_PROBS: probabilities per call of icikt_quantiles_*
 HIST_MAX_BINS = 1024          # ICIKT_HIST_MAX_BINS
+ADJUST = {"bonferroni": 0, "holm": 1, "hochberg": 2, "BH": 3}   # ICIKT_ADJUST_*: R's p.adjust methods of icikt_padjust_*
+ADJUST_MAX_ALPHA = 16         # ICIKT_ADJUST_MAX_ALPHA: alphas per call of icikt_padjust_*
 MASK_VALS = 32                # distinct finite global_na values of the device-side exclusion rule (icikt_device.h)
 MAX_FEATURES = 65535          # the tuned kernels
 MAX_FEATURES_WIDE = 262144    # the plain 32-bit path (exact integer arithmetic)
@@ -79,6 +82,7 @@ EXPORTS = (
     "icikt_class_medians_f64", "icikt_class_medians_in", "icikt_class_medians_csc",
     "icikt_quantiles_f64", "icikt_quantiles_in", "icikt_quantiles_csc",
     "icikt_class_matrix_f64", "icikt_class_matrix_in", "icikt_class_matrix_csc",
+    "icikt_padjust_f64", "icikt_padjust_in", "icikt_padjust_csc",
 )
 
 # icikt_input: the caller's matrix as a typed, strided view (ICIKT_DTYPE_*, ICIKT_ORDER_*)
@@ -369,18 +373,20 @@ def lib():
     L.icikt_quantiles_f64.argtypes = [c_vp, c_vp, c_i64, c_i64, c_i64, c_vp, c_int, c_vp, c_int, c_int, c_int, c_int,
                                       c_u32, c_int, c_vp, c_int, c_vp, c_int, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp,
                                       c_vp]
+    L.icikt_padjust_f64.argtypes = [c_vp, c_vp, c_i64, c_i64, c_i64, c_vp, c_int, c_int, c_int, c_int, c_u32, c_int, c_vp,
+                                    c_int, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]
     L.icikt_multi_rank_phase_ms.argtypes = [c_vp, c_int, ctypes.POINTER(ctypes.c_double)]
     L.icikt_multi_ranks_used.argtypes = [c_vp]
     L.icikt_debug_step_stats.argtypes = [c_vp, c_vp, c_int]
     # the *_in twins: (ctx, const icikt_input*, n_feat, n_samp, ...) where the _f64 entry has (ctx, X, n_feat, n_samp, ld, ...)
     for nm in ("pairs", "matrix", "pairs_complete", "missingness", "cor_pairs", "col_medians", "censor_counts",
-               "rank_order", "topk", "edges", "class_medians", "quantiles", "class_matrix"):
+               "rank_order", "topk", "edges", "class_medians", "quantiles", "class_matrix", "padjust"):
         f64 = getattr(L, f"icikt_{nm}_f64").argtypes
         getattr(L, f"icikt_{nm}_in").argtypes = [c_vp, ctypes.POINTER(InputView), c_i64, c_i64] + list(f64[5:])
     L.icikt_convert_dev.argtypes = [c_vp, c_vp, c_int, c_int, c_i64, c_i64, c_i64, c_vp, c_i64]
     # the *_csc twins: (ctx, const icikt_csc_input*, n_feat, n_samp, ...)
     for nm in ("pairs", "matrix", "missingness", "col_medians", "censor_counts", "rank_order", "topk", "edges",
-               "class_medians", "quantiles", "class_matrix"):
+               "class_medians", "quantiles", "class_matrix", "padjust"):
         f64 = getattr(L, f"icikt_{nm}_f64").argtypes
         getattr(L, f"icikt_{nm}_csc").argtypes = [c_vp, ctypes.POINTER(CscInput), c_i64, c_i64] + list(f64[5:])
     L.icikt_scatter_csc_dev.argtypes = [c_vp, c_vp, c_vp, c_vp, c_int, c_int, ctypes.c_double, c_i64, c_i64, c_vp, c_i64]
@@ -449,7 +455,7 @@ def _matrix_call(fn, handle, chk, X, global_na, pi, pj, perspective, alternative
 
 
 def _select_args(global_na, perspective, alternative):
-    """What the selection entries (topk, edges, class_medians, quantiles) share: the arguments (global_na, n_global_na) -- valid
+    """What the selection entries (topk, edges, class_medians, quantiles, class_matrix, padjust) share: the arguments (global_na, n_global_na) -- valid
     while the first element, the array behind them, is alive --, (perspective, alternative) as codes, the max_taumax
     cell and reason_counts [5]."""
     gna = np.ascontiguousarray([] if global_na is None else np.atleast_1d(global_na), dtype=np.float64)
@@ -745,6 +751,37 @@ class Context:
                      _ptr(order2) if n_probs else None, _ptr(n_valid), _ptr(n_na),
                      _ptr(hist) if n_breaks > 1 else None, _ptr(outside), _ptr(mx), _ptr(rc5)), fname)
         return q2, order2, n_valid, n_na, hist, outside, float(mx[0]), rc5
+
+    def padjust(self, X, method, alpha, max_table=0, global_na=None, perspective="global", alternative="two.sided",
+                continuity=False, flags: int = 0):
+        """R's p.adjust over the p-values of ALL pairs, sorted, scanned and cut on the device (icikt_padjust_f64):
+        nothing of size S x S exists on the host or as five planes on the device.  method: "bonferroni", "holm",
+        "hochberg" or "BH" (or the ICIKT_ADJUST_* code); alpha: up to 16 levels in [0, 1]; X and global_na as matrix()
+        takes them.  The tests are the pairs with reason code 0 and a p-value that is not NaN.  Returns (n_tests [2]
+        int64: tests, other pairs; n_rejected [n_alpha] int64: tests whose adjusted p is <= alpha; p_cutoff [n_alpha]:
+        the largest rejected raw p -- edges(max_pvalue=p_cutoff) selects exactly the rejected pairs --, NA_real_ when
+        none; table [2, t]: the distinct p-values among the rejected tests of the largest alpha, ascending, and their
+        adjusted values, t = min(n_table, max_table); n_table: ALL distinct values, so n_table > max_table says the
+        table is truncated (call again with room); max_taumax; reason_counts [5]).  The argument checks are the
+        library's: a bad method, alpha or perspective raises IciktError."""
+        fn, fname, xargs, n_feat, n_samp, flags, _keep = self._entry("padjust", X, flags)
+        code = ADJUST.get(method, method if isinstance(method, (int, np.integer)) else -1)
+        alpha_a = np.ascontiguousarray(np.atleast_1d(np.asarray(alpha, dtype=np.float64)).ravel())
+        n_alpha = int(alpha_a.size)
+        max_table = int(max_table)
+        room = max(0, min(max_table, n_samp * (n_samp - 1) // 2))   # (no more distinct p-values than pairs)
+        gna, codes, mx, rc5 = _select_args(global_na, perspective, alternative)
+        n_tests = np.zeros(2, dtype=np.int64)
+        n_rej = np.zeros(max(n_alpha, 1), dtype=np.int64)
+        cutoff = np.empty(max(n_alpha, 1), dtype=np.float64)
+        table = np.empty((2, room), dtype=np.float64) if room else None
+        n_table = np.zeros(1, dtype=np.int64)
+        self._chk(fn(self._h, *xargs, *gna[1:], *codes, int(bool(continuity)), flags, int(code),
+                     _ptr(alpha_a) if n_alpha else None, n_alpha, room if max_table >= 0 else max_table, _ptr(n_tests),
+                     _ptr(n_rej), _ptr(cutoff), _ptr(table), _ptr(n_table), _ptr(mx), _ptr(rc5)), fname)
+        t = min(int(n_table[0]), room)
+        table = table[:, :t] if room else np.empty((2, 0), dtype=np.float64)
+        return n_tests, n_rej[:n_alpha], cutoff[:n_alpha], table, int(n_table[0]), float(mx[0]), rc5
 
     def edges(self, X, min_raw=None, max_pvalue=None, min_completeness=None, absolute=False, max_edges=0,
               global_na=None, perspective="global", alternative="two.sided", continuity=False, flags: int = 0,

@@ -91,6 +91,13 @@ class HipEngine:
         return self.ctx.quantiles(data_matrix, probs, breaks, cls, n_class, global_na, perspective, alternative,
                                   continuity, self.flags | flags, scale_max)
 
+    def padjust(self, data_matrix, method, alpha, max_table=0, global_na=None, perspective="global",
+                alternative="two.sided", continuity=False, flags=0):
+        """R's p.adjust over the p-values of all pairs, on the device (icikt_padjust_f64): Context.padjust's arguments
+        and result."""
+        return self.ctx.padjust(data_matrix, method, alpha, max_table, global_na, perspective, alternative, continuity,
+                                self.flags | flags)
+
     def cor_pairs(self, X, pi, pj, method, pairwise, alternative, continuity):
         """cor_fast's pairs on the device (icikt_cor_pairs_f64): (out3: rho, p-value, n_values; reasons)."""
         return self.ctx.cor_pairs(X, pi, pj, method, pairwise, alternative, continuity)
@@ -199,6 +206,11 @@ class MultiHipEngine(HipEngine):
                   alternative="two.sided", continuity=False, flags=0, scale_max=True):   # the select runs on one device
         return self._one().quantiles(data_matrix, probs, breaks, cls, n_class, global_na, perspective, alternative,
                                      continuity, self.flags | flags, scale_max)
+
+    def padjust(self, data_matrix, method, alpha, max_table=0, global_na=None, perspective="global",
+                alternative="two.sided", continuity=False, flags=0):   # the sort runs on one device
+        return self._one().padjust(data_matrix, method, alpha, max_table, global_na, perspective, alternative,
+                                   continuity, self.flags | flags)
 
     def pairs_complete(self, X, pi, pj):  # kt_fast's per-pair masking path exists on one device only
         out, _cnt, rsn = self._one().pairs_complete(X, pi, pj, "two.sided", False, self.flags)
@@ -1247,6 +1259,188 @@ def ici_kendalltau_edges(data_matrix, min_raw=None, max_pvalue=None, min_complet
     res["degree"] = degree
     res["max_taumax"] = max_taumax
     res["run_time"] = t_diff
+    return res
+
+
+# --------------------------------------------------------------------------------------------------
+# ici_kendalltau_padjust / ici_kendalltau_significant: R's p.adjust over the p-values of all pairs, and the edges that
+# stay significant after it (the reference leaves both to the user: p.adjust(out$pvalue[upper.tri(..)], "BH"))
+# --------------------------------------------------------------------------------------------------
+PADJUST_METHODS = ("bonferroni", "holm", "hochberg", "BH")   # p.adjust's spelling; "fdr" is its other name for "BH"
+PADJUST_DEFAULT_TABLE = 2 ** 20    # max_table=None: distinct p-values the first call has room for
+
+
+def _padjust_method(method):
+    if method in PADJUST_METHODS:
+        return method
+    if method == "fdr":
+        return "BH"
+    if method in ("BY", "hommel"):
+        raise ValueError(f"`method` {method!r} is not provided (its constants or recursions are not a scan); "
+                         f"use one of {', '.join(PADJUST_METHODS)}")
+    raise ValueError(f"`method` must be one of {', '.join(PADJUST_METHODS)} (or 'fdr' for BH), spelled as p.adjust "
+                     f"spells them, not {method!r}")
+
+
+def _padjust_alpha(alpha):
+    a = np.atleast_1d(np.asarray(alpha, dtype=np.float64)).ravel()
+    if not 1 <= a.shape[0] <= _lib.ADJUST_MAX_ALPHA or not np.all((a >= 0) & (a <= 1)):
+        raise ValueError(f"`alpha` must be 1 .. {_lib.ADJUST_MAX_ALPHA} values in [0, 1]")
+    return a
+
+
+def _padjust_numpy(pvalue_matrix, method, alpha):
+    """The reduction of icikt_padjust_f64 from a full S x S p-value matrix, for engines without a padjust method (the
+    CPU tests' checker engines).  The tests are the pairs i < j whose p-value is not NaN; sorted ascending, their
+    adjusted values are R's p.adjust, one IEEE operation at a time (bonferroni m p, holm cummax((m + 1 - j) p),
+    hochberg and BH cummin from the right of (m + 1 - j) p and (m / j) p, each clamped at 1).  Returns (n_tests [2]:
+    tests, other pairs; n_rejected [n_alpha]; p_cutoff [n_alpha], NA_real_ where nothing is rejected; table_p,
+    table_adjusted: ALL the distinct p-values among the rejected tests of the largest alpha, and their adjusted
+    values)."""
+    pv = np.ascontiguousarray(pvalue_matrix, dtype=np.float64)
+    alpha = np.atleast_1d(np.asarray(alpha, dtype=np.float64)).ravel()
+    S = pv.shape[0]
+    tri = pv[np.triu_indices(S, k=1)]
+    p = np.sort(tri[~np.isnan(tri)] + 0.0)
+    m = p.shape[0]
+    j = np.arange(1, m + 1, dtype=np.float64)
+    if method == "bonferroni":
+        adj = float(m) * p
+    elif method == "holm":
+        adj = np.maximum.accumulate((float(m + 1) - j) * p)
+    elif method == "hochberg":
+        adj = np.minimum.accumulate(((float(m + 1) - j) * p)[::-1])[::-1]
+    else:
+        adj = np.minimum.accumulate(((float(m) / j) * p)[::-1])[::-1]
+    adj = np.minimum(1.0, adj)
+    n_rejected = np.array([int(np.count_nonzero(adj <= a)) for a in alpha], dtype=np.int64)
+    p_cutoff = np.empty(alpha.shape[0], dtype=np.float64)
+    p_cutoff.view(np.uint64)[...] = _NA_REAL_BITS
+    for a, n in enumerate(n_rejected):
+        if n > 0:
+            p_cutoff[a] = p[n - 1]
+    most = int(n_rejected.max()) if n_rejected.size else 0
+    head = np.ones(most, dtype=bool)
+    if most > 1:
+        head[1:] = p[1:most] != p[:most - 1]
+    return (np.array([m, tri.shape[0] - m], dtype=np.int64), n_rejected, p_cutoff, p[:most][head].copy(),
+            adj[:most][head].copy())
+
+
+def ici_kendalltau_padjust(data_matrix, method="BH", alpha=0.05, max_table=None,
+                           global_na=(float("nan"), float("inf"), 0), perspective="global", alternative="two.sided",
+                           continuity=False, colnames=None, engine=None):
+    """Multiple-testing adjustment of the p-values of ALL S (S - 1) / 2 pairs of samples (columns) of a features x
+    samples matrix, without the S x S matrices ``ici_kendalltau`` returns: how many pairs stay significant at each
+    ``alpha`` after R's ``p.adjust(p, method)``, and the raw p-value to cut at.
+
+    ``method``: ``"bonferroni"``, ``"holm"``, ``"hochberg"`` or ``"BH"`` (``"fdr"`` is BH), spelled as ``p.adjust``
+    spells them; ``"BY"`` and ``"hommel"`` are not provided.  ``alpha``: one level or up to 16, each in [0, 1].  The
+    tests are the pairs whose p-value is not NA (a pair whose ``raw`` is NA is none: the reference's warning is raised
+    once per pair of reasons 2-4); ``n_tests`` is their count m, ``n_na`` the count of the others.  The adjusted
+    values are ``p.adjust``'s to the bit (for BH also ``scipy.stats.false_discovery_control``'s).  The other arguments
+    are ``ici_kendalltau``'s (column names are required; a sparse matrix, float32 and integer matrices are read where
+    they lie).  On the HIP engine the p-values are sorted, scanned and cut on the device (icikt_padjust_f64); a matrix
+    has at most 65 535 samples.
+
+    ``n_rejected[a]`` is the number of tests whose adjusted p-value is ``<= alpha[a]`` and ``p_cutoff[a]`` the largest
+    raw p-value among them (NA when there is none): ``adjusted <= alpha[a]`` exactly when ``pvalue <= p_cutoff[a]``, so
+    ``ici_kendalltau_edges(max_pvalue=p_cutoff[a])`` returns exactly the rejected pairs (``ici_kendalltau_significant``
+    does that).  ``table_p`` holds the distinct p-values among the rejected tests of the largest alpha, ascending, and
+    ``table_adjusted`` their adjusted values.  ``max_table=None`` returns the whole table: the first call has room for
+    ``2**20`` entries, and when there are more the call is repeated ONCE with room for all -- the whole computation
+    twice, with the same result; pass a ``max_table`` that fits to avoid that.  An explicit ``max_table`` truncates
+    the table; ``n_table`` still counts every distinct value.
+
+    Returns a dict: ``method``, ``alpha``, ``n_tests``, ``n_na``, ``n_rejected``, ``p_cutoff`` (one value per alpha),
+    ``table_p``, ``table_adjusted``, ``n_table``, ``max_taumax`` and ``run_time``.
+    """
+    method = _padjust_method(method)
+    alpha_a = _padjust_alpha(alpha)
+    if max_table is not None and (isinstance(max_table, (bool, np.bool_)) or not isinstance(max_table, (int, np.integer))
+                                  or int(max_table) < 0):
+        raise ValueError("`max_table` must be a non-negative integer or None")
+    data_matrix, names = _as_matrix(data_matrix, colnames, "data_matrix", keep_dtype=True, keep_sparse=True)
+    n_sample = data_matrix.shape[1]
+    if n_sample < 2:
+        raise ValueError("No comparisons to do. Check the list of column names in "
+                         "`include_only` vs those in the samples.")  # R/kendalltau.R:240-247
+    total = n_sample * (n_sample - 1) // 2
+    eng = engine or _default_engine()
+    if hasattr(eng, "padjust"):
+        X, global_na = _mask_on_host(data_matrix, global_na)
+        Xe = _for_engine(X, eng, fortran=False)
+        room = min(total, PADJUST_DEFAULT_TABLE) if max_table is None else int(max_table)
+        t1 = time.perf_counter()
+        out = eng.padjust(Xe, method, alpha_a, room, global_na, perspective, alternative, continuity, 0)
+        if max_table is None and out[4] > room:   # the second call is exact: the count does not depend on the room
+            out = eng.padjust(Xe, method, alpha_a, out[4], global_na, perspective, alternative, continuity, 0)
+        t_diff = time.perf_counter() - t1
+        n_tests, n_rejected, p_cutoff, table, n_table, max_taumax, rcounts = out
+        table_p, table_adj = table[0], table[1]
+        _warn_pairs(rcounts)
+    else:
+        full = ici_kendalltau(data_matrix, global_na=global_na, perspective=perspective, scale_max=True, diag_good=True,
+                              alternative=alternative, continuity=continuity, colnames=names, engine=eng)
+        t_diff = full["run_time"]
+        n_tests, n_rejected, p_cutoff, table_p, table_adj = _padjust_numpy(np.asarray(full["pvalue"]), method, alpha_a)
+        n_table = int(table_p.shape[0])
+        if max_table is not None:
+            table_p, table_adj = table_p[:int(max_table)], table_adj[:int(max_table)]
+        max_taumax = _max_taumax(full["taumax"], np.triu_indices(n_sample, k=1))
+    return {"method": method, "alpha": alpha_a, "n_tests": int(n_tests[0]), "n_na": int(n_tests[1]),
+            "n_rejected": n_rejected, "p_cutoff": p_cutoff, "table_p": table_p, "table_adjusted": table_adj,
+            "n_table": int(n_table), "max_taumax": max_taumax, "run_time": t_diff}
+
+
+def ici_kendalltau_significant(data_matrix, alpha=0.05, method="BH", min_raw=None, min_completeness=None, absolute=False,
+                               max_edges=None, global_na=(float("nan"), float("inf"), 0), perspective="global",
+                               scale_max=True, alternative="two.sided", continuity=False, colnames=None, engine=None):
+    """The pairs of samples whose ICI-Kendall-tau stays significant at ``alpha`` after ``p.adjust(p, method)`` over all
+    S (S - 1) / 2 pairs: the edge list of ``ici_kendalltau_edges`` with an ``adjusted`` column.
+
+    It COMPUTES ALL PAIRS TWICE: ``ici_kendalltau_padjust`` finds the raw p-value to cut at (``p_cutoff``), then
+    ``ici_kendalltau_edges`` is called with ``max_pvalue = p_cutoff`` and the caller's ``min_raw``, ``min_completeness``,
+    ``absolute`` and ``max_edges``; each edge's adjusted p-value is looked up in the first call's table by the bits of
+    its p-value (every edge's p-value is in that table by construction; an error is raised if one is not).  When
+    nothing is rejected the empty edge list is returned without the second call.  The adjustment is over ALL pairs with
+    a p-value, whatever the other bounds keep.
+
+    Returns ``ici_kendalltau_edges``' dict plus ``adjusted`` (one value per edge), ``alpha``, ``method``, ``n_tests``,
+    ``n_rejected`` and ``p_cutoff``; ``run_time`` is the sum of the two calls.
+    """
+    if isinstance(alpha, (bool, np.bool_)) or not isinstance(alpha, (int, float, np.integer, np.floating)) \
+            or not 0 <= float(alpha) <= 1:
+        raise ValueError("`alpha` must be one number in [0, 1]")
+    data_matrix, names = _as_matrix(data_matrix, colnames, "data_matrix", keep_dtype=True, keep_sparse=True)
+    adj = ici_kendalltau_padjust(data_matrix, method=method, alpha=float(alpha), max_table=None, global_na=global_na,
+                                 perspective=perspective, alternative=alternative, continuity=continuity,
+                                 colnames=names, engine=engine)
+    n_rejected, p_cutoff = int(adj["n_rejected"][0]), float(adj["p_cutoff"][0])
+    if n_rejected == 0:
+        none_i = np.empty(0, dtype=np.int32)
+        res = {"s1": np.empty(0, dtype=object), "s2": np.empty(0, dtype=object), "i": none_i, "j": none_i.copy()}
+        for key in _TOPK_KEYS:
+            res[key] = np.empty(0, dtype=np.float64)
+        res.update(n_edges=0, degree=np.zeros(data_matrix.shape[1], dtype=np.int64), max_taumax=adj["max_taumax"],
+                   run_time=adj["run_time"], adjusted=np.empty(0, dtype=np.float64))
+    else:
+        with warnings.catch_warnings():   # (the first call has raised the pairs' warnings)
+            warnings.simplefilter("ignore")
+            res = ici_kendalltau_edges(data_matrix, min_raw=min_raw, max_pvalue=p_cutoff,
+                                       min_completeness=min_completeness, absolute=absolute, max_edges=max_edges,
+                                       global_na=global_na, perspective=perspective, scale_max=scale_max,
+                                       alternative=alternative, continuity=continuity, colnames=names, engine=engine)
+        # p-values are >= 0 and a zero is +0 on both sides: the order of the bits is the order of the values
+        table_bits = np.ascontiguousarray(adj["table_p"], dtype=np.float64).view(np.uint64)
+        edge_bits = (np.ascontiguousarray(res["pvalue"], dtype=np.float64) + 0.0).view(np.uint64)
+        at = np.searchsorted(table_bits, edge_bits)
+        if np.any(at >= table_bits.shape[0]) or np.any(table_bits[np.minimum(at, table_bits.shape[0] - 1)] != edge_bits):
+            raise RuntimeError("ici_kendalltau_significant: an edge's p-value is not among the adjusted p-values")
+        res["adjusted"] = np.asarray(adj["table_adjusted"], dtype=np.float64)[at]
+        res["run_time"] = res["run_time"] + adj["run_time"]
+    res.update(alpha=float(alpha), method=adj["method"], n_tests=adj["n_tests"], n_rejected=n_rejected,
+               p_cutoff=p_cutoff)
     return res
 
 

@@ -1732,6 +1732,7 @@ extern "C" {
 // whole combn rows, 1 = a row per block, or per slice of several classes' pair list),
 // medlds (icikt_class_medians_*: partners up to which the select kernel stages a sample's keys in LDS, 0 .. 4096),
 // qbatch (icikt_quantiles_*: targets per batch of the select, 1 .. 32),
+// padjtile (icikt_padjust_*: keys of a wave's tile of the sort, 1 .. 2^30),
 // verbose (0 | 1: print the plan to stderr).
 // (The keys h2d and regfail of rounds 2-3 are gone with the mode they steered: the library no longer page-locks
 // caller memory, icikt_host.h.)
@@ -1777,6 +1778,11 @@ int icikt_debug_set_plan(icikt_ctx* c, const char* spec) {
       ov.qbatch = atoi(val.c_str());
       if (ov.qbatch < 1 || ov.qbatch > icikt::QUANT_BATCH_MAX)
         return fail(c, ICIKT_E_INVALID, "debug_set_plan: qbatch must be in 1 .. 32 targets");
+    }
+    else if (key == "padjtile") {
+      ov.padjtile = atoll(val.c_str());
+      if (ov.padjtile < 1 || ov.padjtile > (1ll << 30))
+        return fail(c, ICIKT_E_INVALID, "debug_set_plan: padjtile must be in 1 .. 2^30 keys");
     }
     else return fail(c, ICIKT_E_INVALID, "debug_set_plan: unknown key '" + key + "'");
   }

@@ -49,6 +49,21 @@ __device__ inline T block_reduce(T v, T* sh, Op op) {
 }
 
 
+// ctr[idx] += 1 for every lane of the wave with idx >= 0, runs of equal idx in neighbouring lanes as ONE atomic of the
+// run's length: the top digits of the keys and the bins of tied data are the same for most of a wave, and LDS atomics
+// on one address serialise.  Every lane of the wave must call it.
+__device__ __forceinline__ void run_add(unsigned int* ctr, int idx) {
+  const int lane = (int)(threadIdx.x & 63u);
+  const int prev = __shfl_up(idx, 1, 64);
+  const bool head = lane == 0 || idx != prev;
+  const unsigned long long heads = __ballot(head);
+  if (head && idx >= 0) {
+    const unsigned long long after = lane == 63 ? 0ull : heads >> (lane + 1);
+    const int len = after ? __ffsll((long long)after) : 64 - lane;   // lanes up to the next run's head
+    atomicAdd(&ctr[idx], (unsigned int)len);
+  }
+}
+
 struct Add { template <typename T> __device__ T operator()(T a, T b) const { return a + b; } };
 struct Max { template <typename T> __device__ T operator()(T a, T b) const { return a > b ? a : b; } };
 struct Min { template <typename T> __device__ T operator()(T a, T b) const { return a < b ? a : b; } };

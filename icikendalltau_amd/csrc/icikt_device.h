@@ -1,5 +1,5 @@
 // icikt_device.h -- structures, layouts and launcher declarations shared by the device units (icikt_prepass.hip,
-// icikt_kernels.hip, icikt_epilogue.hip, icikt_cor.hip, icikt_diag.hip, icikt_topk.hip, icikt_edges.hip, icikt_medians.hip, icikt_quantiles.hip, icikt_classmat.hip) and the C-ABI
+// icikt_kernels.hip, icikt_epilogue.hip, icikt_cor.hip, icikt_diag.hip, icikt_topk.hip, icikt_edges.hip, icikt_medians.hip, icikt_quantiles.hip, icikt_classmat.hip, icikt_padjust.hip) and the C-ABI
 // host side (icikt_capi*.cpp, icikt_multi.cpp).  Internal; the public boundary is include/icikt.h.
 #ifndef ICIKT_DEVICE_H
 #define ICIKT_DEVICE_H
@@ -304,6 +304,40 @@ hipError_t launch_quant_fold(const double* out4, const int32_t* reasons, long lo
 hipError_t launch_quant_count(const unsigned long long* kept, long long n_pairs, int S, const int32_t* cls,
                               const QuantTargets& T, int t0, int nt, int shift, unsigned long long* hist, hipStream_t s);
 hipError_t launch_quant_pick(const QuantTargets& T, int t0, int nt, int shift, unsigned long long* hist, hipStream_t s);
+// ---- multiple-testing adjustment of all pairs (icikt_padjust.hip) ----
+constexpr int PADJ_BONFERRONI = 0, PADJ_HOLM = 1, PADJ_HOCHBERG = 2, PADJ_BH = 3;   // == ICIKT_ADJUST_*
+constexpr int PADJ_MAX_ALPHA = 16;              // == ICIKT_ADJUST_MAX_ALPHA
+constexpr long long PADJ_MAX_TILES = 65536;     // tiles of a sort pass: 256 counters of 8 bytes each per tile (128 MB)
+constexpr int PADJ_SCAN_CHUNK = 1024;           // items a workgroup of a chip-wide scan reduces and scans at a time
+constexpr int PADJ_CUT_WORDS = 2 * PADJ_MAX_ALPHA + 1;   // launch_padj_cut's record
+// the keys a wave's tile of the sort holds for a plane of n keys: `want` (the padjtile plan key; 0: the library's 1 024)
+// raised until the plane has at most PADJ_MAX_TILES tiles
+long long padj_tile(long long n, long long want);
+// words of the aggregates a scan of this call needs at most (over the 256 counters of every tile, or over the n keys)
+long long padj_scan_chunks(long long n, long long tile);
+// out4 / reasons: the records of n_pairs consecutive pairs of combn(S, 2) from pair `first` on.  kept[first + e] = the
+// pair's p-value as a sortable key (colsort::cor_key), NA_KEY for a pair with a reason code or a NaN p; *total += the
+// valid keys; dhist [8][256] += the keys (NA_KEY included) per digit and digit value.  The caller zeroes total and dhist
+// before a call's first block.
+hipError_t launch_padj_fold(const double* out4, const int32_t* reasons, long long n_pairs, long long first, int S,
+                            unsigned long long* kept, unsigned long long* total, unsigned long long* dhist,
+                            hipStream_t s);
+// one digit (shift = 0, 8 .. 56, in this order) of the stable radix sort of the n keys of src into dst; counts: 256 words
+// per tile, agg: padj_scan_chunks words
+hipError_t launch_padj_sort_pass(const unsigned long long* src, unsigned long long* dst, long long n, long long tile,
+                                 int shift, unsigned long long* counts, unsigned long long* agg, hipStream_t s);
+// adj[i], i < m: the adjusted value (PADJ_* method) of the i-th of the m sorted keys; agg: padj_scan_chunks words
+hipError_t launch_padj_adjust(const unsigned long long* keys, long long m, int method, double* adj, double* agg,
+                              hipStream_t s);
+// cut [PADJ_CUT_WORDS]: per alpha (device doubles) the adjusted values <= alpha, from word PADJ_MAX_ALPHA on per alpha
+// the bits of the largest p among them (NA_real_: none), in the last word the largest of the counts
+hipError_t launch_padj_cut(const double* adj, const unsigned long long* keys, long long m, const double* alpha,
+                           int n_alpha, unsigned long long* cut, hipStream_t s);
+// the distinct keys among the first min(*extent, m) sorted positions, ascending: table [2][cap] gets the first cap of
+// them as p-values and their adjusted values, *n_table their full count; agg: padj_scan_chunks words
+hipError_t launch_padj_table(const unsigned long long* keys, const double* adj, long long m,
+                             const unsigned long long* extent, long long cap, double* table, unsigned long long* agg,
+                             unsigned long long* n_table, hipStream_t s);
 // wide columns: one wave per pair, grid of `blocks` single-wave workgroups that fetch pairs from *task_ctr
 hipError_t launch_k1_wide(const PrepView& pv, const int32_t* pi, const int32_t* pj, PairRaw* raw, int64_t n_pairs,
                           int blocks, size_t lds_bytes, int* task_ctr, hipStream_t s);

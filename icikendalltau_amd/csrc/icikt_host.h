@@ -160,6 +160,15 @@ struct icikt_ctx {
     DevBuf<double> breaks;
   } quant;
 
+  // multiple-testing adjustment of all pairs (icikt_padjust_f64): the kept plane (a key per pair of the triangle) and
+  // the sort's spare plane, which takes the adjusted values afterwards; the sort's (digit, tile) counters and the scans'
+  // chunk aggregates; the valid count, the fold's digit table, the alphas, the cut-offs' record, the table's count and
+  // the table itself
+  struct PadjBufs {
+    DevBuf<unsigned long long> kept, spare, counts, agg, total, dhist, cut, n_table;
+    DevBuf<double> alpha, table;
+  } padj;
+
   // missing-value diagnostics (icikt_col_medians_f64, icikt_censor_counts_f64, icikt_rank_order_f64)
   struct DiagBufs {
     DevBuf<double> median, medrank, out;
@@ -181,6 +190,7 @@ struct icikt_ctx {
     long long tkblock = -1;   // icikt_topk_*, icikt_edges_*, icikt_class_medians_*, icikt_quantiles_*: pairs a block (whole combn rows, or a slice of the class list) may hold (default: the library's budget)
     int medlds = -1;          // icikt_class_medians_*, icikt_class_matrix_*: partners up to which the select kernel gathers a sample's keys into LDS (default: MEDIAN_STAGE_MAX)
     int qbatch = -1;          // icikt_quantiles_*: targets the select runs per batch (default: QUANT_BATCH_MAX)
+    long long padjtile = -1;  // icikt_padjust_*: keys of a wave's tile of the sort (default: padj_tile's choice)
     bool verbose = false;
   } plan_ov;
 

@@ -46,21 +46,6 @@ __device__ __forceinline__ void q_pair_columns(int S, long long e, int* pi, int*
   *pj = i + 1 + (int)(e - q_rowoff(S, i));
 }
 
-// ctr[idx] += 1 for every lane of the wave with idx >= 0, runs of equal idx in neighbouring lanes as ONE atomic of the
-// run's length: the top digits of the keys and the bins of tied data are the same for most of a wave, and LDS atomics
-// on one address serialise.  Every lane of the wave must call it.
-__device__ __forceinline__ void q_run_add(unsigned int* ctr, int idx) {
-  const int lane = (int)(threadIdx.x & 63u);
-  const int prev = __shfl_up(idx, 1, 64);
-  const bool head = lane == 0 || idx != prev;
-  const unsigned long long heads = __ballot(head);
-  if (head && idx >= 0) {
-    const unsigned long long after = lane == 63 ? 0ull : heads >> (lane + 1);
-    const int len = after ? __ffsll((long long)after) : 64 - lane;   // lanes up to the next run's head
-    atomicAdd(&ctr[idx], (unsigned int)len);
-  }
-}
-
 // ---- fold: histogram, counts and kept keys of one block ----------------------------------------------------------
 
 // slot of a valid raw among nb breaks: 0 below breaks[0], 1 + k in bin k, nb above breaks[nb - 1]; the last bin is
@@ -115,8 +100,8 @@ k_quant_fold(const double* __restrict__ out4, const int32_t* __restrict__ reason
     }
     if (nb > 0) {
       const int slot = (in && valid) ? q_slot(s_brk, nb, v) : -1;
-      q_run_add(s_cnt, slot);
-      if (cls) q_run_add(s_cnt + nslot, within ? slot : -1);
+      run_add(s_cnt, slot);
+      if (cls) run_add(s_cnt + nslot, within ? slot : -1);
     }
   }
   if ((tid & 63) == 0) {   // the ballots gave every lane the wave's counts
@@ -239,9 +224,9 @@ k_quant_count(const unsigned long long* __restrict__ kept, long long n_pairs, in
           if (sb >= 0) b = sb * 256 + digit;
         }
       }
-      q_run_add(s_hist, a);
+      run_add(s_hist, a);
       if (cls) {
-        q_run_add(s_hist, b);
+        run_add(s_hist, b);
         off += 256;
         while (i < S - 2 && off >= S - 1 - i) {   // (behind the last row nothing is read: e >= end)
           off -= S - 1 - i;

@@ -455,6 +455,62 @@ int icikt_class_matrix_f64(icikt_ctx *ctx, const double *X, int64_t n_feat, int6
                            int alternative, int continuity, uint32_t flags, int scale_max, double *med2,
                            int32_t *n_valid, double *max_taumax, int64_t *reason_counts);
 
+/* ---- multiple-testing adjustment of the p-values of all pairs, on the device ----------------------------------------
+ *
+ * The step that follows every all-pairs call: R's p.adjust(p, method) over the p-values of all C(n_samp, 2) pairs, and
+ * from it the number of pairs rejected at each alpha and the raw p-value to cut at -- without anything of size n_samp^2
+ * on the host or as five planes on the device.  The whole combn triangle runs through the pair engine in blocks of
+ * whole rows (the tkblock budget, as icikt_topk_f64); a kernel keeps each pair's p-value as a sortable 64-bit key, and
+ * after the last block the device sorts the keys (a radix sort across the chip), scans them and compacts the table.
+ *   tests        the pairs i < j whose reason code is 0 and whose p-value is not NaN; m = n_tests[0] is their count,
+ *                n_tests[1] the count of the other pairs.  (Two-row input gives reason-free pairs with a NaN p: no
+ *                tests, as p.adjust drops an NA.)
+ *   method       ICIKT_ADJUST_BONFERRONI, _HOLM, _HOCHBERG or _BH.  With the m p-values ascending p(1) <= .. <= p(m), i
+ *                the 1-based position, the adjusted values in that order are R's p.adjust, one IEEE double operation at
+ *                a time:
+ *                  bonferroni  min(1, m p(i))
+ *                  holm        min(1, max over j <= i of (m + 1 - j) p(j))
+ *                  hochberg    min(1, min over j >= i of (m + 1 - j) p(j))
+ *                  BH          min(1, min over j >= i of (m / j) p(j)), the quotient rounded first, then the product
+ *                m, j and m + 1 - j are exact as doubles (m < 2^31); there is one division and one multiplication and no
+ *                addition of doubles, so nothing contracts into a fused multiply-add; maxima and minima are exact.  The
+ *                result is defined to the bit.  For all four methods the sequence is non-decreasing and constant on a
+ *                run of equal p-values: the adjusted value is a function of the value of p alone.
+ *   alpha        n_alpha (1 .. ICIKT_ADJUST_MAX_ALPHA) doubles in [0, 1]; NaN or a value outside is ICIKT_E_INVALID, the
+ *                message names the index
+ *   n_rejected   [n_alpha] the tests whose adjusted value is <= alpha[a]
+ *   p_cutoff     [n_alpha] p(n) with n = n_rejected[a], NA_real_ (bits 0x7FF00000000007A2) when n = 0.  Every method
+ *                rejects a lower set of the order, so adjusted <= alpha[a] iff pvalue <= p_cutoff[a] for every test:
+ *                icikt_edges_f64 with rule.max_pvalue = p_cutoff[a] selects exactly the rejected pairs.
+ *   table        [2][max_table]: the distinct p-values among the first max over a of n_rejected[a] sorted positions,
+ *                ascending, in plane 0 (a zero as +0), their adjusted values in plane 1.  *n_table: the number of
+ *                distinct values, ALL of them; the first min(*n_table, max_table) are written, the slots behind them are
+ *                left untouched.  *n_table > max_table is no error: call again with room.  max_table = 0 (table may then
+ *                be null) only counts.
+ * Without a test (m = 0; n_samp of 0 or 1 included) every n_rejected is 0, every p_cutoff NA_real_ and *n_table 0.
+ * n_tests, n_rejected, p_cutoff and n_table are required, table with max_table > 0; max_taumax and reason_counts (as
+ * icikt_topk_f64, over all pairs) are optional.  A bad method, n_alpha, alpha, a negative max_table, a null output:
+ * ICIKT_E_INVALID.  n_samp <= ICIKT_TOPK_MAX_SAMPLES (ICIKT_E_INVALID beyond, the message names the limit); n_feat,
+ * global_na, the state the call leaves behind (none: icikt_run_dev answers ICIKT_E_STATE and icikt_num_pairs -1) and the
+ * refusal of bad arguments before anything -- the context or an output -- is touched: as icikt_topk_f64.  The result is
+ * a pure function of the input: a sorted multiset of keys and scans of exact operations, whatever the block cut, the
+ * sort's tile or the grid.
+ * Device memory: the prepared matrix, one block's buffers, 16 bytes per pair of the triangle for the kept keys and the
+ * sort's second plane (n_samp = 65 535: 34 GB), 2 KB per tile of the sort (at most 65 536 tiles), 8 bytes per 1 024
+ * pairs for the scans and 16 min(max_table, pairs) bytes of table.  A failed allocation is ICIKT_E_HIP.
+ * With ICIKT_FLAG_TIMING the fold, sort, scan and table kernels are accounted under ICIKT_K_EPILOGUE.
+ * icikt_padjust_in / icikt_padjust_csc: the same on a typed view / a CSC view of the matrix (below). */
+#define ICIKT_ADJUST_BONFERRONI 0
+#define ICIKT_ADJUST_HOLM 1
+#define ICIKT_ADJUST_HOCHBERG 2
+#define ICIKT_ADJUST_BH 3
+#define ICIKT_ADJUST_MAX_ALPHA 16
+int icikt_padjust_f64(icikt_ctx *ctx, const double *X, int64_t n_feat, int64_t n_samp, int64_t ld,
+                      const double *global_na, int n_global_na, int perspective, int alternative, int continuity,
+                      uint32_t flags, int method, const double *alpha, int n_alpha, int64_t max_table, int64_t *n_tests,
+                      int64_t *n_rejected, double *p_cutoff, double *table, int64_t *n_table, double *max_taumax,
+                      int64_t *reason_counts);
+
 /* ---- several GPUs behind one call (what the R glue binds when n_gpu > 1) ----------------------
  *
  * Replaces the reference's worker fan-out, computation$split_fun(split_comparisons, ici_split, ...)
@@ -615,6 +671,10 @@ int icikt_class_matrix_in(icikt_ctx *ctx, const icikt_input *X, int64_t n_feat, 
                           int n_global_na, const int32_t *cls, int n_class, int perspective, int alternative,
                           int continuity, uint32_t flags, int scale_max, double *med2, int32_t *n_valid,
                           double *max_taumax, int64_t *reason_counts);
+int icikt_padjust_in(icikt_ctx *ctx, const icikt_input *X, int64_t n_feat, int64_t n_samp, const double *global_na,
+                     int n_global_na, int perspective, int alternative, int continuity, uint32_t flags, int method,
+                     const double *alpha, int n_alpha, int64_t max_table, int64_t *n_tests, int64_t *n_rejected,
+                     double *p_cutoff, double *table, int64_t *n_table, double *max_taumax, int64_t *reason_counts);
 int icikt_matrix_in(icikt_ctx *ctx, const icikt_input *X, int64_t n_feat, int64_t n_samp, const double *global_na,
                     int n_global_na, const int32_t *pi, const int32_t *pj, int64_t n_pairs, int perspective,
                     int alternative, int continuity, uint32_t flags, int scale_max, int diag_good, double *out5,
@@ -680,6 +740,10 @@ int icikt_class_matrix_csc(icikt_ctx *ctx, const icikt_csc_input *X, int64_t n_f
                            const double *global_na, int n_global_na, const int32_t *cls, int n_class, int perspective,
                            int alternative, int continuity, uint32_t flags, int scale_max, double *med2,
                            int32_t *n_valid, double *max_taumax, int64_t *reason_counts);
+int icikt_padjust_csc(icikt_ctx *ctx, const icikt_csc_input *X, int64_t n_feat, int64_t n_samp, const double *global_na,
+                      int n_global_na, int perspective, int alternative, int continuity, uint32_t flags, int method,
+                      const double *alpha, int n_alpha, int64_t max_table, int64_t *n_tests, int64_t *n_rejected,
+                      double *p_cutoff, double *table, int64_t *n_table, double *max_taumax, int64_t *reason_counts);
 int icikt_missingness_csc(icikt_ctx *ctx, const icikt_csc_input *X, int64_t n_feat, int64_t n_samp, const int32_t *pi,
                           const int32_t *pj, int64_t n_pairs, int64_t *missingness);
 int icikt_col_medians_csc(icikt_ctx *ctx, const icikt_csc_input *X, int64_t n_feat, int64_t n_samp,
@@ -716,7 +780,8 @@ int icikt_selftest(icikt_ctx *ctx);
  * budget for the rows of one class and for the slices of several classes' pair list), medlds (icikt_class_medians_*:
  * the partners up to which the select kernel gathers a sample's keys into LDS once, 0 .. 4096; a sample with more
  * re-reads the kept plane in every pass), qbatch (icikt_quantiles_*: the targets -- distinct (group, rank) -- the
- * select runs per batch of eight passes, 1 .. 32), verbose (0 | 1: print the chosen
+ * select runs per batch of eight passes, 1 .. 32), padjtile (icikt_padjust_*: the keys of a tile of the sort, the run one
+ * wave counts and scatters in order, 1 .. 2^30; raised when the plane would have more than 65 536 tiles), verbose (0 | 1: print the chosen
  * plan to stderr). */
 int icikt_debug_set_plan(icikt_ctx *ctx, const char *spec);
 /* Development hook: per step kind of the pair kernel (hot loop, hot step in the main loop, MIXED, GROUP, general,
