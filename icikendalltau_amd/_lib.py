@@ -22,7 +22,8 @@ SOURCES = [os.path.join(_PKG, "csrc", f) for f in ("icikt_kernels.hip", "icikt_p
                                                        "icikt_medians.hip", "icikt_capi_medians.cpp", "icikt_capi_select.cpp",
                                                        "icikt_quantiles.hip", "icikt_capi_quantiles.cpp",
                                                        "icikt_classmat.hip", "icikt_capi_classmat.cpp",
-                                                       "icikt_padjust.hip", "icikt_capi_padjust.cpp")]
+                                                       "icikt_padjust.hip", "icikt_capi_padjust.cpp",
+                                                       "icikt_mst.hip", "icikt_capi_mst.cpp")]
 HEADERS = [os.path.join(_ROOT, "include", "icikt.h"), os.path.join(_PKG, "csrc", "icikt_device.h"),
            os.path.join(_PKG, "csrc", "icikt_wave.h"), os.path.join(_PKG, "csrc", "icikt_host.h"),
            os.path.join(_PKG, "csrc", "icikt_transfer.h"), os.path.join(_PKG, "csrc", "icikt_colsort.h"),
@@ -83,6 +84,7 @@ EXPORTS = (
     "icikt_quantiles_f64", "icikt_quantiles_in", "icikt_quantiles_csc",
     "icikt_class_matrix_f64", "icikt_class_matrix_in", "icikt_class_matrix_csc",
     "icikt_padjust_f64", "icikt_padjust_in", "icikt_padjust_csc",
+    "icikt_mst_f64", "icikt_mst_in", "icikt_mst_csc",
 )
 
 # icikt_input: the caller's matrix as a typed, strided view (ICIKT_DTYPE_*, ICIKT_ORDER_*)
@@ -375,18 +377,20 @@ def lib():
                                       c_vp]
     L.icikt_padjust_f64.argtypes = [c_vp, c_vp, c_i64, c_i64, c_i64, c_vp, c_int, c_int, c_int, c_int, c_u32, c_int, c_vp,
                                     c_int, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]
+    L.icikt_mst_f64.argtypes = [c_vp, c_vp, c_i64, c_i64, c_i64, c_vp, c_int, c_int, c_int, c_int, c_u32, c_int,
+                                ctypes.c_double, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]
     L.icikt_multi_rank_phase_ms.argtypes = [c_vp, c_int, ctypes.POINTER(ctypes.c_double)]
     L.icikt_multi_ranks_used.argtypes = [c_vp]
     L.icikt_debug_step_stats.argtypes = [c_vp, c_vp, c_int]
     # the *_in twins: (ctx, const icikt_input*, n_feat, n_samp, ...) where the _f64 entry has (ctx, X, n_feat, n_samp, ld, ...)
     for nm in ("pairs", "matrix", "pairs_complete", "missingness", "cor_pairs", "col_medians", "censor_counts",
-               "rank_order", "topk", "edges", "class_medians", "quantiles", "class_matrix", "padjust"):
+               "rank_order", "topk", "edges", "class_medians", "quantiles", "class_matrix", "padjust", "mst"):
         f64 = getattr(L, f"icikt_{nm}_f64").argtypes
         getattr(L, f"icikt_{nm}_in").argtypes = [c_vp, ctypes.POINTER(InputView), c_i64, c_i64] + list(f64[5:])
     L.icikt_convert_dev.argtypes = [c_vp, c_vp, c_int, c_int, c_i64, c_i64, c_i64, c_vp, c_i64]
     # the *_csc twins: (ctx, const icikt_csc_input*, n_feat, n_samp, ...)
     for nm in ("pairs", "matrix", "missingness", "col_medians", "censor_counts", "rank_order", "topk", "edges",
-               "class_medians", "quantiles", "class_matrix", "padjust"):
+               "class_medians", "quantiles", "class_matrix", "padjust", "mst"):
         f64 = getattr(L, f"icikt_{nm}_f64").argtypes
         getattr(L, f"icikt_{nm}_csc").argtypes = [c_vp, ctypes.POINTER(CscInput), c_i64, c_i64] + list(f64[5:])
     L.icikt_scatter_csc_dev.argtypes = [c_vp, c_vp, c_vp, c_vp, c_int, c_int, ctypes.c_double, c_i64, c_i64, c_vp, c_i64]
@@ -782,6 +786,34 @@ class Context:
         t = min(int(n_table[0]), room)
         table = table[:, :t] if room else np.empty((2, 0), dtype=np.float64)
         return n_tests, n_rej[:n_alpha], cutoff[:n_alpha], table, int(n_table[0]), float(mx[0]), rc5
+
+    def mst(self, X, min_raw=None, global_na=None, perspective="global", alternative="two.sided", continuity=False,
+            flags: int = 0, scale_max=True):
+        """The maximum spanning forest of the samples under raw -- their single-linkage clustering -- found on the
+        device (icikt_mst_f64): all pairs are computed, and nothing of size S x S exists on the host or as five planes
+        on the device.  A pair is a candidate edge iff its raw is not NA and, with min_raw, raw >= min_raw; the strict
+        edge order is the larger raw first (-0 equal to +0), equal raw by the smaller combn index, so the forest is
+        unique.  X and global_na as matrix() takes them.  Returns (ti, tj [n_tree] int32: the edges i < j in the strict
+        order, which is the single-linkage merge order; vals5 [5, n_tree]: cor, raw, pvalue, taumax, completeness;
+        component [S] int32: the components of the candidate graph, numbered in order of their smallest sample;
+        n_components; n_rounds: the Boruvka rounds run; max_taumax; reason_counts [5]) with n_tree + n_components == S.
+        The argument checks are the library's: a bad perspective raises IciktError."""
+        fn, fname, xargs, n_feat, n_samp, flags, _keep = self._entry("mst", X, flags)
+        gna, codes, mx, rc5 = _select_args(global_na, perspective, alternative)
+        room = max(n_samp - 1, 0) if n_samp <= TOPK_MAX_SAMPLES else 0   # (the library refuses more samples before it writes)
+        ti = np.empty(max(room, 1), dtype=np.int32)
+        tj = np.empty(max(room, 1), dtype=np.int32)
+        vals = np.empty((5, max(room, 1)), dtype=np.float64)
+        component = np.zeros(max(n_samp, 1), dtype=np.int32)
+        n_tree = np.zeros(1, dtype=np.int64)
+        n_comp = np.zeros(1, dtype=np.int64)
+        n_rounds = np.zeros(1, dtype=np.int32)
+        self._chk(fn(self._h, *xargs, *gna[1:], *codes, int(bool(continuity)), flags, int(bool(scale_max)),
+                     float("nan") if min_raw is None else float(min_raw), _ptr(ti), _ptr(tj), _ptr(vals), _ptr(n_tree),
+                     _ptr(component), _ptr(n_comp), _ptr(n_rounds), _ptr(mx), _ptr(rc5)), fname)
+        m = int(n_tree[0])
+        # (the library's planes are room apart: one row of vals each when room >= 1)
+        return (ti[:m], tj[:m], vals[:, :m], component[:n_samp], int(n_comp[0]), int(n_rounds[0]), float(mx[0]), rc5)
 
     def edges(self, X, min_raw=None, max_pvalue=None, min_completeness=None, absolute=False, max_edges=0,
               global_na=None, perspective="global", alternative="two.sided", continuity=False, flags: int = 0,

@@ -98,6 +98,12 @@ class HipEngine:
         return self.ctx.padjust(data_matrix, method, alpha, max_table, global_na, perspective, alternative, continuity,
                                 self.flags | flags)
 
+    def mst(self, data_matrix, min_raw=None, global_na=None, perspective="global", alternative="two.sided",
+            continuity=False, flags=0, scale_max=True):
+        """The maximum spanning forest under raw, found on the device (icikt_mst_f64): Context.mst's contract."""
+        return self.ctx.mst(data_matrix, min_raw, global_na, perspective, alternative, continuity, self.flags | flags,
+                            scale_max)
+
     def cor_pairs(self, X, pi, pj, method, pairwise, alternative, continuity):
         """cor_fast's pairs on the device (icikt_cor_pairs_f64): (out3: rho, p-value, n_values; reasons)."""
         return self.ctx.cor_pairs(X, pi, pj, method, pairwise, alternative, continuity)
@@ -211,6 +217,11 @@ class MultiHipEngine(HipEngine):
                 alternative="two.sided", continuity=False, flags=0):   # the sort runs on one device
         return self._one().padjust(data_matrix, method, alpha, max_table, global_na, perspective, alternative,
                                    continuity, self.flags | flags)
+
+    def mst(self, data_matrix, min_raw=None, global_na=None, perspective="global", alternative="two.sided",
+            continuity=False, flags=0, scale_max=True):   # the rounds run on one device
+        return self._one().mst(data_matrix, min_raw, global_na, perspective, alternative, continuity,
+                               self.flags | flags, scale_max)
 
     def pairs_complete(self, X, pi, pj):  # kt_fast's per-pair masking path exists on one device only
         out, _cnt, rsn = self._one().pairs_complete(X, pi, pj, "two.sided", False, self.flags)
@@ -1257,6 +1268,128 @@ def ici_kendalltau_edges(data_matrix, min_raw=None, max_pvalue=None, min_complet
         res[key] = vals[q]
     res["n_edges"] = int(n_edges)
     res["degree"] = degree
+    res["max_taumax"] = max_taumax
+    res["run_time"] = t_diff
+    return res
+
+
+# --------------------------------------------------------------------------------------------------
+# ici_kendalltau_mst: the maximum spanning forest of the samples under raw -- their single-linkage clustering, and the
+# connected components of the thresholded network at every cut-off (the reference's workflow ends in a heatmap ordered
+# by a dendrogram; it leaves the clustering to hclust on the full matrix)
+# --------------------------------------------------------------------------------------------------
+def _mst_components(parent):
+    """Component labels from a union-find parent array: 0, 1, ... in order of each component's smallest sample."""
+    S = len(parent)
+    label = np.full(S, -1, dtype=np.int32)
+    component = np.empty(S, dtype=np.int32)
+    n = 0
+    for s in range(S):
+        r = s
+        while parent[r] != r:
+            r = parent[r]
+        if label[r] < 0:
+            label[r] = n
+            n += 1
+        component[s] = label[r]
+    return component, n
+
+
+def _mst_numpy(mats5, min_raw):
+    """The forest of icikt_mst_f64 from five full S x S matrices (cor, raw, pvalue, taumax, completeness), for engines
+    without an mst method (the CPU tests' checker engines): Kruskal over the candidate edges of the upper triangle --
+    raw not NA, and raw >= min_raw when that is not None -- in the strict edge order, np.lexsort by raw descending (-0
+    equal to +0) and then by the combn index, merged by union-find.  Returns (ti, tj, vals5 [5, n_tree], component [S],
+    n_components)."""
+    mats5 = [np.ascontiguousarray(m, dtype=np.float64) for m in mats5]
+    S = mats5[1].shape[0]
+    iu = np.triu_indices(S, k=1)             # row-major upper triangle: the combn order
+    raw = mats5[1][iu]
+    with np.errstate(invalid="ignore"):
+        ok = ~np.isnan(raw)
+        if min_raw is not None:
+            ok &= raw >= min_raw
+    cand = np.flatnonzero(ok)                # combn indices, ascending
+    order = cand[np.lexsort((cand, -(raw[cand] + 0.0)))]   # (+ 0.0: -0 sorts as +0)
+    parent = list(range(S))
+
+    def find(a):
+        while parent[a] != a:
+            parent[a] = parent[parent[a]]
+            a = parent[a]
+        return a
+
+    picked = []
+    ii, jj = iu[0], iu[1]
+    for e in order.tolist():
+        if len(picked) == S - 1:
+            break
+        a, b = find(int(ii[e])), find(int(jj[e]))
+        if a != b:
+            parent[max(a, b)] = min(a, b)
+            picked.append(e)
+    picked = np.asarray(picked, dtype=np.int64)
+    ti, tj = ii[picked].astype(np.int32), jj[picked].astype(np.int32)
+    vals = np.stack([m[iu][picked] for m in mats5]) if S > 1 else np.empty((5, 0))
+    component, n_comp = _mst_components(parent)
+    return ti, tj, vals, component, n_comp
+
+
+def ici_kendalltau_mst(data_matrix, min_raw=None, global_na=(float("nan"), float("inf"), 0), perspective="global",
+                       scale_max=True, alternative="two.sided", continuity=False, colnames=None, engine=None):
+    """The maximum spanning forest of the samples (columns) of a features x samples matrix under their ICI-Kendall-tau:
+    the single-linkage clustering of the samples, and the connected components of the correlation network at every
+    cut-off, without the S x S matrices ``ici_kendalltau`` returns.
+
+    A pair i < j is a *candidate edge* iff its ``raw`` is not NA, and ``raw >= min_raw`` when ``min_raw`` is given (a
+    plain comparison of doubles, as in ``ici_kendalltau_edges``).  The *strict edge order* is: larger ``raw`` first, -0
+    equal to +0; equal ``raw`` by the smaller ``combn`` index (i ascending, then j ascending).  The order is total, so
+    the maximum spanning forest under it is unique -- a pure function of the input.  Its edges are returned in that
+    order, which is Kruskal's order and the single-linkage merge order.  A sample all of whose pairs are NA or below
+    ``min_raw`` (a constant or all-missing column) is a component of its own.  Only single linkage is offered:
+    complete and average linkage need S - 1 dependent updates of an S x S table and are deliberately left out.
+
+    The other arguments are ``ici_kendalltau``'s (column names are required; a sparse matrix, float32 and integer
+    matrices are read where they lie).  On the HIP engine the forest is found on the device (icikt_mst_f64); a matrix
+    has at most 65 535 samples.
+
+    Returns a dict: ``s1``, ``s2`` (the samples' names), ``i``, ``j`` (their indices, i < j), ``cor, raw, pvalue,
+    taumax, completeness`` (one value per tree edge; ``cor = raw / max_taumax`` over all pairs with ``scale_max``),
+    ``n_tree``, ``component`` (S: the components of the candidate graph, numbered 0, 1, ... in order of their smallest
+    sample, as ``scipy.sparse.csgraph.connected_components`` numbers them), ``n_components`` (``n_tree + n_components
+    == S``), ``sample_id``, ``max_taumax`` and ``run_time``.  ``formats.mst_to_linkage`` turns it into a
+    ``scipy.cluster.hierarchy`` linkage matrix, ``formats.mst_cut`` into the components at any cut-off.  The
+    reference's warning is raised once per pair whose ``raw`` is NA for reasons 2-4, as ``ici_kendalltau_edges`` raises
+    it.
+    """
+    min_raw = _edge_bound(min_raw, "min_raw")
+    data_matrix, names = _as_matrix(data_matrix, colnames, "data_matrix", keep_dtype=True, keep_sparse=True)
+    n_sample = data_matrix.shape[1]
+    if n_sample < 2:
+        raise ValueError("No comparisons to do. Check the list of column names in "
+                         "`include_only` vs those in the samples.")  # R/kendalltau.R:240-247
+    eng = engine or _default_engine()
+    if hasattr(eng, "mst"):
+        X, global_na = _mask_on_host(data_matrix, global_na)
+        t1 = time.perf_counter()
+        ti, tj, vals, component, n_comp, _n_rounds, max_taumax, rcounts = eng.mst(
+            _for_engine(X, eng, fortran=False), min_raw, global_na, perspective, alternative, continuity, 0, scale_max)
+        t_diff = time.perf_counter() - t1
+        _warn_pairs(rcounts)
+    else:
+        full = ici_kendalltau(data_matrix, global_na=global_na, perspective=perspective, scale_max=scale_max,
+                              diag_good=True, alternative=alternative, continuity=continuity, colnames=names, engine=eng)
+        t_diff = full["run_time"]
+        ti, tj, vals, component, n_comp = _mst_numpy([np.asarray(full[key]) for key in _TOPK_KEYS], min_raw)
+        max_taumax = _max_taumax(full["taumax"], np.triu_indices(n_sample, k=1))
+    names_arr = np.asarray(list(names), dtype=object)
+    res = {"s1": names_arr[ti], "s2": names_arr[tj], "i": ti, "j": tj}
+    for q, key in enumerate(_TOPK_KEYS):
+        res[key] = vals[q]
+    res["n_tree"] = int(ti.shape[0])
+    res["component"] = component
+    res["n_components"] = int(n_comp)
+    res["sample_id"] = names_arr
     res["max_taumax"] = max_taumax
     res["run_time"] = t_diff
     return res

@@ -1,5 +1,5 @@
 // icikt_device.h -- structures, layouts and launcher declarations shared by the device units (icikt_prepass.hip,
-// icikt_kernels.hip, icikt_epilogue.hip, icikt_cor.hip, icikt_diag.hip, icikt_topk.hip, icikt_edges.hip, icikt_medians.hip, icikt_quantiles.hip, icikt_classmat.hip, icikt_padjust.hip) and the C-ABI
+// icikt_kernels.hip, icikt_epilogue.hip, icikt_cor.hip, icikt_diag.hip, icikt_topk.hip, icikt_edges.hip, icikt_medians.hip, icikt_quantiles.hip, icikt_classmat.hip, icikt_padjust.hip, icikt_mst.hip) and the C-ABI
 // host side (icikt_capi*.cpp, icikt_multi.cpp).  Internal; the public boundary is include/icikt.h.
 #ifndef ICIKT_DEVICE_H
 #define ICIKT_DEVICE_H
@@ -278,6 +278,19 @@ constexpr int CLASS_MATRIX_MAX_CLASSES = 65535;   // k_class_select's grid is (S
 hipError_t launch_class_select(const int32_t* member, const int32_t* first, const unsigned long long* kept,
                                const unsigned long long* red, int S, int n_class, int scale_max, int stage, double* med2,
                                int32_t* n_valid, hipStream_t s);
+// ---- maximum spanning forest / single linkage (icikt_mst.hip) ----
+constexpr int MST_MAX_ROUNDS = 17;   // components with a candidate at least halve per round (S < 2^16), and one round finds nothing
+// a sample's best edge out of its component: the key of its raw (0: none) and the partner (-1: none)
+struct MstBest {
+  unsigned long long key;
+  int32_t t, pad;
+};
+// kept: the whole combn(S, 2) plane launch_median_keep writes; comp [S]: a component label per sample; live [S]: 0 for
+// the samples of a component that found no candidate in an earlier round; min_key: colsort::cor_key of min_raw, 0 for
+// no bound.  best[s]: the best candidate edge (s, t) with comp[t] != comp[s] -- the largest key that is not NA_KEY and
+// not below min_key, equal keys by the smaller t
+hipError_t launch_mst_best(const unsigned long long* kept, const int32_t* comp, const int32_t* live,
+                           unsigned long long min_key, int S, MstBest* best, hipStream_t s);
 // ---- quantiles and histogram of all pairs (icikt_quantiles.hip) ----
 constexpr int QUANT_MAX_BINS = 1024;    // == ICIKT_HIST_MAX_BINS: k_quant_fold stages 1 025 breaks and 2 x 1 026 counters in LDS
 constexpr int QUANT_HEAD = 4;           // words of a counted group before its bins: n_valid, n_na, below, above

@@ -169,6 +169,14 @@ struct icikt_ctx {
     DevBuf<double> alpha, table;
   } padj;
 
+  // maximum spanning forest (icikt_mst_f64): the kept plane (a key per pair of the triangle), the samples' component
+  // labels and live flags, and every sample's best edge of a round
+  struct MstBufs {
+    DevBuf<unsigned long long> kept;
+    DevBuf<int32_t> comp, live;
+    DevBuf<icikt::MstBest> best;
+  } mst;
+
   // missing-value diagnostics (icikt_col_medians_f64, icikt_censor_counts_f64, icikt_rank_order_f64)
   struct DiagBufs {
     DevBuf<double> median, medrank, out;
@@ -266,7 +274,7 @@ int check_pair_args(icikt_ctx* c, const char* who, const MatrixSrc& X, int64_t n
                     const int32_t* pi, const int32_t* pj, int64_t* n_pairs, const void* out, bool out5,
                     int perspective, int alternative);
 
-// ---- the selection entries (icikt_topk_*, icikt_edges_*, icikt_class_medians_*, icikt_quantiles_*, icikt_class_matrix_*): one driver, icikt_capi_select.cpp ----
+// ---- the selection entries (icikt_topk_*, icikt_edges_*, icikt_class_medians_*, icikt_quantiles_*, icikt_class_matrix_*, icikt_padjust_*, icikt_mst_*): one driver, icikt_capi_select.cpp ----
 // (the blocks a call runs in: icikt_blocks.h; DESIGN.md "adding a selection entry")
 // the arguments the entries share
 struct SelectArgs {

@@ -8,6 +8,8 @@
   matrices and the long data.frame storage form (R/reshaping.R:15-68).
 * ``topk_to_csr``: the result of ``ici_kendalltau_topk`` as a sparse samples x samples kNN graph (needs scipy).
 * ``edges_to_coo``: the result of ``ici_kendalltau_edges`` as a sparse samples x samples matrix (needs scipy).
+* ``mst_to_linkage`` / ``mst_cut``: the result of ``ici_kendalltau_mst`` as a ``scipy.cluster.hierarchy`` linkage matrix
+  (single linkage), and as the network's component labels at any cut-off (neither needs scipy).
 """
 from __future__ import annotations
 
@@ -283,3 +285,75 @@ def edges_to_coo(result, value="cor", symmetric=True):
     if symmetric:
         i, j, vals = np.concatenate([i, j]), np.concatenate([j, i]), np.concatenate([vals, vals])
     return sp.coo_matrix((vals, (i, j)), shape=(S, S))
+
+
+# --------------------------------------------------------------------------------------------------
+# ici_kendalltau_mst -> a dendrogram, and the network's components at any cut-off
+# --------------------------------------------------------------------------------------------------
+def _mst_find(parent, a):
+    while parent[a] != a:
+        parent[a] = parent[parent[a]]
+        a = parent[a]
+    return a
+
+
+def mst_to_linkage(result, by="raw"):
+    """The dict ``ici_kendalltau_mst`` returns as a ``scipy.cluster.hierarchy`` linkage matrix of single linkage under
+    the distance ``1 - result[by]`` (``by``: "raw" or "cor"): (S - 1) x 4 float64, row k = (the two clusters merged at
+    step k, the smaller id first; the height ``1 - value`` of the tree's k-th edge; the new cluster's size), the samples
+    being clusters 0 .. S - 1 and step k making cluster S + k -- scipy's convention, so ``dendrogram``, ``fcluster`` and
+    ``leaves_list`` take it as it is.  The tree's edges come in the single-linkage merge order, so this is one pass of
+    union-find, O(S alpha(S)); scipy itself is not needed.  A forest that is not ONE tree has no dendrogram:
+    ``ValueError`` naming ``n_components`` (cut with ``mst_cut``, or cluster each component on its own)."""
+    if by not in ("raw", "cor"):
+        raise ValueError("`by` must be raw or cor")
+    S = len(result["component"])
+    n_comp = int(result["n_components"])
+    i = np.asarray(result["i"], dtype=np.int64)
+    j = np.asarray(result["j"], dtype=np.int64)
+    if n_comp != 1 or i.shape[0] != S - 1:
+        raise ValueError(f"the forest is not one tree (n_components = {n_comp}): a linkage matrix needs every sample "
+                         "connected; lower `min_raw`, or cut with mst_cut")
+    height = 1.0 - np.asarray(result[by], dtype=np.float64)
+    parent = list(range(S))
+    cluster = list(range(S))     # per union-find root: the id of the cluster it stands for
+    size = [1] * S
+    Z = np.empty((S - 1, 4), dtype=np.float64)
+    for k in range(S - 1):
+        a, b = _mst_find(parent, int(i[k])), _mst_find(parent, int(j[k]))
+        if a == b:
+            raise ValueError(f"edge {k} of the result closes a cycle: not a forest of ici_kendalltau_mst")
+        ca, cb = cluster[a], cluster[b]
+        parent[b] = a
+        size[a] += size[b]
+        cluster[a] = S + k
+        Z[k] = (min(ca, cb), max(ca, cb), height[k], size[a])
+    return Z
+
+
+def mst_cut(result, min_raw):
+    """The connected components of the network "every pair with ``raw >= min_raw``" from the tree alone: the tree's edges
+    below ``min_raw`` are dropped and the rest merged by union-find (a maximum spanning forest connects, at every
+    cut-off, exactly what the full graph connects).  ``result``: the dict of ``ici_kendalltau_mst`` called with no
+    ``min_raw``, or with one not above this one.  Returns the labels (S, int32), numbered 0, 1, ... in order of each
+    component's smallest sample: ``ici_kendalltau_mst(..., min_raw=min_raw)["component"]`` without computing a pair."""
+    S = len(result["component"])
+    i = np.asarray(result["i"], dtype=np.int64)
+    j = np.asarray(result["j"], dtype=np.int64)
+    with np.errstate(invalid="ignore"):
+        keep = np.asarray(result["raw"], dtype=np.float64) >= float(min_raw)
+    parent = list(range(S))
+    for a, b in zip(i[keep].tolist(), j[keep].tolist()):
+        a, b = _mst_find(parent, a), _mst_find(parent, b)
+        if a != b:
+            parent[max(a, b)] = min(a, b)
+    label = np.full(S, -1, dtype=np.int32)
+    component = np.empty(S, dtype=np.int32)
+    n = 0
+    for s in range(S):
+        r = _mst_find(parent, s)
+        if label[r] < 0:
+            label[r] = n
+            n += 1
+        component[s] = label[r]
+    return component

@@ -511,6 +511,48 @@ int icikt_padjust_f64(icikt_ctx *ctx, const double *X, int64_t n_feat, int64_t n
                       int64_t *n_rejected, double *p_cutoff, double *table, int64_t *n_table, double *max_taumax,
                       int64_t *reason_counts);
 
+/* ---- maximum spanning forest of the samples: single-linkage clustering, on the device -------------------------------
+ *
+ * Clustering the samples by their correlation, and the question of a correlation network "at which cut-off does it
+ * fall apart, and into which clusters": single-linkage clustering is the maximum spanning tree of the complete graph
+ * weighted by raw, and one tree gives the dendrogram and the connected components of the thresholded network at EVERY
+ * cut-off -- without anything of size n_samp^2 on the host or as five planes on the device.  The whole combn triangle
+ * runs through the pair engine in blocks of whole rows (the tkblock budget, as icikt_topk_f64); a kernel keeps each
+ * pair's raw as a sortable 64-bit key, and after the last block Boruvka rounds run over the kept keys: a kernel finds
+ * every sample's best edge out of its component, the host (O(n_samp) per round) picks each component's best, merges
+ * and uploads the new components.  Only comparisons enter, no addition of doubles: the result is defined to the bit.
+ * (Complete and average linkage need n_samp - 1 dependent updates of an n_samp x n_samp table; they are not offered.)
+ *   candidate    a pair i < j is a candidate edge iff its raw is not NA (reason code 0) and, when min_raw is not NaN,
+ *                raw >= min_raw -- a plain IEEE comparison, as icikt_edge_rule's
+ *   order        the STRICT EDGE ORDER: the larger raw first, -0 equal to +0; equal raw by the smaller combn index (i
+ *                ascending, then j ascending).  The order is total, so the maximum spanning forest under it is unique:
+ *                a pure function of the input, whatever the block cut, the round structure or the launch geometry.
+ *   ti, tj       [n_samp - 1] the forest's edges i < j IN THE STRICT ORDER: Kruskal's order, which is the single-linkage
+ *                merge order.  *n_tree of them are written, the slots behind them are left untouched.
+ *   out5t        [5][n_samp - 1] planes (n_samp - 1 apart): cor, raw, pvalue, taumax, completeness of each edge, bit for
+ *                bit the cells of icikt_matrix_f64; cor = scale_max ? raw / max(taumax, na.rm = TRUE) over ALL
+ *                C(n_samp, 2) pairs : raw
+ *   component    [n_samp] the sample's connected component in the candidate graph, the components numbered 0, 1, .. in
+ *                order of their smallest sample.  A sample all of whose pairs are NA or below min_raw -- a constant or
+ *                all-missing column -- is a component of its own.  *n_tree + *n_components == n_samp always.
+ *   n_rounds     the rounds run (a diagnostic): at most 17, since the components that still have a candidate at least
+ *                halve per round.  A round that merges nothing while candidates exist, or counts that do not add up, is
+ *                ICIKT_E_STATE with a message -- never a loop.
+ * ti, tj and out5t are required for n_samp > 1, component for n_samp > 0, n_tree, n_components and n_rounds always;
+ * max_taumax and reason_counts (as icikt_topk_f64, over all pairs) are optional.  n_samp <= ICIKT_TOPK_MAX_SAMPLES
+ * (ICIKT_E_INVALID beyond, the message names the limit); n_feat, global_na, the state the call leaves behind (none:
+ * icikt_run_dev answers ICIKT_E_STATE and icikt_num_pairs -1) and the refusal of bad arguments before anything -- the
+ * context or an output -- is touched: as icikt_topk_f64.
+ * Device memory: the prepared matrix, one block's buffers, 8 bytes per pair of the triangle for the kept keys (n_samp =
+ * 65 535: 17 GB) and 24 n_samp bytes of component labels, live flags and candidates; a failed allocation is ICIKT_E_HIP.
+ * With ICIKT_FLAG_TIMING the keep kernel, the rounds and the pair run over the tree's edges are accounted under
+ * ICIKT_K_EPILOGUE.
+ * icikt_mst_in / icikt_mst_csc: the same on a typed view / a CSC view of the matrix (below). */
+int icikt_mst_f64(icikt_ctx *ctx, const double *X, int64_t n_feat, int64_t n_samp, int64_t ld, const double *global_na,
+                  int n_global_na, int perspective, int alternative, int continuity, uint32_t flags, int scale_max,
+                  double min_raw, int32_t *ti, int32_t *tj, double *out5t, int64_t *n_tree, int32_t *component,
+                  int64_t *n_components, int32_t *n_rounds, double *max_taumax, int64_t *reason_counts);
+
 /* ---- several GPUs behind one call (what the R glue binds when n_gpu > 1) ----------------------
  *
  * Replaces the reference's worker fan-out, computation$split_fun(split_comparisons, ici_split, ...)
@@ -675,6 +717,10 @@ int icikt_padjust_in(icikt_ctx *ctx, const icikt_input *X, int64_t n_feat, int64
                      int n_global_na, int perspective, int alternative, int continuity, uint32_t flags, int method,
                      const double *alpha, int n_alpha, int64_t max_table, int64_t *n_tests, int64_t *n_rejected,
                      double *p_cutoff, double *table, int64_t *n_table, double *max_taumax, int64_t *reason_counts);
+int icikt_mst_in(icikt_ctx *ctx, const icikt_input *X, int64_t n_feat, int64_t n_samp, const double *global_na,
+                 int n_global_na, int perspective, int alternative, int continuity, uint32_t flags, int scale_max,
+                 double min_raw, int32_t *ti, int32_t *tj, double *out5t, int64_t *n_tree, int32_t *component,
+                 int64_t *n_components, int32_t *n_rounds, double *max_taumax, int64_t *reason_counts);
 int icikt_matrix_in(icikt_ctx *ctx, const icikt_input *X, int64_t n_feat, int64_t n_samp, const double *global_na,
                     int n_global_na, const int32_t *pi, const int32_t *pj, int64_t n_pairs, int perspective,
                     int alternative, int continuity, uint32_t flags, int scale_max, int diag_good, double *out5,
@@ -744,6 +790,10 @@ int icikt_padjust_csc(icikt_ctx *ctx, const icikt_csc_input *X, int64_t n_feat, 
                       int n_global_na, int perspective, int alternative, int continuity, uint32_t flags, int method,
                       const double *alpha, int n_alpha, int64_t max_table, int64_t *n_tests, int64_t *n_rejected,
                       double *p_cutoff, double *table, int64_t *n_table, double *max_taumax, int64_t *reason_counts);
+int icikt_mst_csc(icikt_ctx *ctx, const icikt_csc_input *X, int64_t n_feat, int64_t n_samp, const double *global_na,
+                  int n_global_na, int perspective, int alternative, int continuity, uint32_t flags, int scale_max,
+                  double min_raw, int32_t *ti, int32_t *tj, double *out5t, int64_t *n_tree, int32_t *component,
+                  int64_t *n_components, int32_t *n_rounds, double *max_taumax, int64_t *reason_counts);
 int icikt_missingness_csc(icikt_ctx *ctx, const icikt_csc_input *X, int64_t n_feat, int64_t n_samp, const int32_t *pi,
                           const int32_t *pj, int64_t n_pairs, int64_t *missingness);
 int icikt_col_medians_csc(icikt_ctx *ctx, const icikt_csc_input *X, int64_t n_feat, int64_t n_samp,
