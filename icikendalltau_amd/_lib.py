@@ -23,7 +23,8 @@ SOURCES = [os.path.join(_PKG, "csrc", f) for f in ("icikt_kernels.hip", "icikt_p
                                                        "icikt_quantiles.hip", "icikt_capi_quantiles.cpp",
                                                        "icikt_classmat.hip", "icikt_capi_classmat.cpp",
                                                        "icikt_padjust.hip", "icikt_capi_padjust.cpp",
-                                                       "icikt_mst.hip", "icikt_capi_mst.cpp")]
+                                                       "icikt_mst.hip", "icikt_capi_mst.cpp",
+                                                       "icikt_anosim.hip", "icikt_capi_anosim.cpp")]
 HEADERS = [os.path.join(_ROOT, "include", "icikt.h"), os.path.join(_PKG, "csrc", "icikt_device.h"),
            os.path.join(_PKG, "csrc", "icikt_wave.h"), os.path.join(_PKG, "csrc", "icikt_host.h"),
            os.path.join(_PKG, "csrc", "icikt_transfer.h"), os.path.join(_PKG, "csrc", "icikt_colsort.h"),
@@ -48,6 +49,7 @@ QUANTILE_MAX_PROBS = 32       # ICIKT_QUANTILE_MAX_PROBS: probabilities per call
 HIST_MAX_BINS = 1024          # ICIKT_HIST_MAX_BINS
 ADJUST = {"bonferroni": 0, "holm": 1, "hochberg": 2, "BH": 3}   # ICIKT_ADJUST_*: R's p.adjust methods of icikt_padjust_*
 ADJUST_MAX_ALPHA = 16         # ICIKT_ADJUST_MAX_ALPHA: alphas per call of icikt_padjust_*
+ANOSIM_MAX_PERM = 1000000     # ICIKT_ANOSIM_MAX_PERM: labellings per call of icikt_anosim_* beside the observed one
 MASK_VALS = 32                # distinct finite global_na values of the device-side exclusion rule (icikt_device.h)
 MAX_FEATURES = 65535          # the tuned kernels
 MAX_FEATURES_WIDE = 262144    # the plain 32-bit path (exact integer arithmetic)
@@ -85,6 +87,7 @@ EXPORTS = (
     "icikt_class_matrix_f64", "icikt_class_matrix_in", "icikt_class_matrix_csc",
     "icikt_padjust_f64", "icikt_padjust_in", "icikt_padjust_csc",
     "icikt_mst_f64", "icikt_mst_in", "icikt_mst_csc",
+    "icikt_anosim_f64", "icikt_anosim_in", "icikt_anosim_csc",
 )
 
 # icikt_input: the caller's matrix as a typed, strided view (ICIKT_DTYPE_*, ICIKT_ORDER_*)
@@ -379,18 +382,20 @@ def lib():
                                     c_int, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]
     L.icikt_mst_f64.argtypes = [c_vp, c_vp, c_i64, c_i64, c_i64, c_vp, c_int, c_int, c_int, c_int, c_u32, c_int,
                                 ctypes.c_double, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]
+    L.icikt_anosim_f64.argtypes = [c_vp, c_vp, c_i64, c_i64, c_i64, c_vp, c_int, c_int, c_int, c_int, c_u32, c_vp, c_int,
+                                   c_vp, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]
     L.icikt_multi_rank_phase_ms.argtypes = [c_vp, c_int, ctypes.POINTER(ctypes.c_double)]
     L.icikt_multi_ranks_used.argtypes = [c_vp]
     L.icikt_debug_step_stats.argtypes = [c_vp, c_vp, c_int]
     # the *_in twins: (ctx, const icikt_input*, n_feat, n_samp, ...) where the _f64 entry has (ctx, X, n_feat, n_samp, ld, ...)
     for nm in ("pairs", "matrix", "pairs_complete", "missingness", "cor_pairs", "col_medians", "censor_counts",
-               "rank_order", "topk", "edges", "class_medians", "quantiles", "class_matrix", "padjust", "mst"):
+               "rank_order", "topk", "edges", "class_medians", "quantiles", "class_matrix", "padjust", "mst", "anosim"):
         f64 = getattr(L, f"icikt_{nm}_f64").argtypes
         getattr(L, f"icikt_{nm}_in").argtypes = [c_vp, ctypes.POINTER(InputView), c_i64, c_i64] + list(f64[5:])
     L.icikt_convert_dev.argtypes = [c_vp, c_vp, c_int, c_int, c_i64, c_i64, c_i64, c_vp, c_i64]
     # the *_csc twins: (ctx, const icikt_csc_input*, n_feat, n_samp, ...)
     for nm in ("pairs", "matrix", "missingness", "col_medians", "censor_counts", "rank_order", "topk", "edges",
-               "class_medians", "quantiles", "class_matrix", "padjust", "mst"):
+               "class_medians", "quantiles", "class_matrix", "padjust", "mst", "anosim"):
         f64 = getattr(L, f"icikt_{nm}_f64").argtypes
         getattr(L, f"icikt_{nm}_csc").argtypes = [c_vp, ctypes.POINTER(CscInput), c_i64, c_i64] + list(f64[5:])
     L.icikt_scatter_csc_dev.argtypes = [c_vp, c_vp, c_vp, c_vp, c_int, c_int, ctypes.c_double, c_i64, c_i64, c_vp, c_i64]
@@ -814,6 +819,49 @@ class Context:
         m = int(n_tree[0])
         # (the library's planes are room apart: one row of vals each when room >= 1)
         return (ti[:m], tj[:m], vals[:, :m], component[:n_samp], int(n_comp[0]), int(n_rounds[0]), float(mx[0]), rc5)
+
+    def anosim(self, X, cls=None, n_class=1, perm_cls=None, global_na=None, perspective="global",
+               alternative="two.sided", continuity=False, flags: int = 0):
+        """ANOSIM of the classes under the dissimilarity 1 - raw with its permutation sums, on the device
+        (icikt_anosim_f64): all pairs are computed, ranked and summed there, and nothing of size S x S exists on the
+        host or as five planes on the device.  cls: a class index in 0 .. n_class - 1 per column (None: one class);
+        perm_cls: [n_perm, S] class indices, the labellings to compare with (None: none); X and global_na as matrix()
+        takes them.  Returns (n_pairs [2] int64: values M, NA pairs; w2, nw [1 + n_perm] int64: the doubled rank sum and
+        the count of the within-class values, index 0 the observed labelling; n_ge: the permutations whose R is defined
+        and >= the observed R, compared exactly; n_undefined: the permutations without an R; class_w2, class_nw
+        [n_class] int64: the observed sums per class; max_taumax; reason_counts [5]).  api.anosim_statistic turns a
+        (M, w2, nw) into the statistic.  The argument checks are the library's: a label out of range, more than 65 535 classes or a
+        bad perspective raises IciktError."""
+        fn, fname, xargs, n_feat, n_samp, flags, _keep = self._entry("anosim", X, flags)
+        if cls is None:
+            cls_a = None
+            n_class = 1
+        else:
+            cls_a = np.ascontiguousarray(cls, dtype=np.int32)
+            if cls_a.shape != (n_samp,):
+                raise ValueError("cls must give one class per column")
+        n_class = int(n_class)
+        if perm_cls is None:
+            perm_a, n_perm = None, 0
+        else:
+            perm_a = np.ascontiguousarray(perm_cls, dtype=np.int32)
+            if perm_a.ndim != 2 or perm_a.shape[1] != n_samp:
+                raise ValueError("perm_cls must be [n_perm, S]: one class per column in every row")
+            n_perm = int(perm_a.shape[0])
+        room = n_class if 1 <= n_class <= 65535 else 1    # (the library refuses the others before it writes)
+        n_lab = 1 + (n_perm if n_perm <= ANOSIM_MAX_PERM else 0)
+        gna, codes, mx, rc5 = _select_args(global_na, perspective, alternative)
+        n_pairs = np.zeros(2, dtype=np.int64)
+        w2 = np.zeros(n_lab, dtype=np.int64)
+        nw = np.zeros(n_lab, dtype=np.int64)
+        n_ge = np.zeros(1, dtype=np.int64)
+        n_undef = np.zeros(1, dtype=np.int64)
+        class_w2 = np.zeros(room, dtype=np.int64)
+        class_nw = np.zeros(room, dtype=np.int64)
+        self._chk(fn(self._h, *xargs, *gna[1:], *codes, int(bool(continuity)), flags, _ptr(cls_a), n_class,
+                     _ptr(perm_a) if n_perm else None, n_perm, _ptr(n_pairs), _ptr(w2), _ptr(nw), _ptr(n_ge),
+                     _ptr(n_undef), _ptr(class_w2), _ptr(class_nw), _ptr(mx), _ptr(rc5)), fname)
+        return n_pairs, w2, nw, int(n_ge[0]), int(n_undef[0]), class_w2, class_nw, float(mx[0]), rc5
 
     def edges(self, X, min_raw=None, max_pvalue=None, min_completeness=None, absolute=False, max_edges=0,
               global_na=None, perspective="global", alternative="two.sided", continuity=False, flags: int = 0,

@@ -13,6 +13,7 @@ from __future__ import annotations
 
 import math
 import time
+from fractions import Fraction
 import warnings
 from typing import Sequence
 
@@ -103,6 +104,13 @@ class HipEngine:
         """The maximum spanning forest under raw, found on the device (icikt_mst_f64): Context.mst's contract."""
         return self.ctx.mst(data_matrix, min_raw, global_na, perspective, alternative, continuity, self.flags | flags,
                             scale_max)
+
+    def anosim(self, data_matrix, cls=None, n_class=1, perm_cls=None, global_na=None, perspective="global",
+               alternative="two.sided", continuity=False, flags=0):
+        """ANOSIM's rank sums of the observed labelling and of every permutation, on the device (icikt_anosim_f64):
+        Context.anosim's arguments and result."""
+        return self.ctx.anosim(data_matrix, cls, n_class, perm_cls, global_na, perspective, alternative, continuity,
+                               self.flags | flags)
 
     def cor_pairs(self, X, pi, pj, method, pairwise, alternative, continuity):
         """cor_fast's pairs on the device (icikt_cor_pairs_f64): (out3: rho, p-value, n_values; reasons)."""
@@ -222,6 +230,11 @@ class MultiHipEngine(HipEngine):
             continuity=False, flags=0, scale_max=True):   # the rounds run on one device
         return self._one().mst(data_matrix, min_raw, global_na, perspective, alternative, continuity,
                                self.flags | flags, scale_max)
+
+    def anosim(self, data_matrix, cls=None, n_class=1, perm_cls=None, global_na=None, perspective="global",
+               alternative="two.sided", continuity=False, flags=0):   # the sort and the rank plane live on one device
+        return self._one().anosim(data_matrix, cls, n_class, perm_cls, global_na, perspective, alternative, continuity,
+                                  self.flags | flags)
 
     def pairs_complete(self, X, pi, pj):  # kt_fast's per-pair masking path exists on one device only
         out, _cnt, rsn = self._one().pairs_complete(X, pi, pj, "two.sided", False, self.flags)
@@ -1574,6 +1587,168 @@ def ici_kendalltau_significant(data_matrix, alpha=0.05, method="BH", min_raw=Non
         res["run_time"] = res["run_time"] + adj["run_time"]
     res.update(alpha=float(alpha), method=adj["method"], n_tests=adj["n_tests"], n_rejected=n_rejected,
                p_cutoff=p_cutoff)
+    return res
+
+
+# --------------------------------------------------------------------------------------------------
+# ici_kendalltau_anosim: do the classes separate under ICI-Kt?  Analysis of similarities (Clarke 1993; vegan::anosim)
+# on the dissimilarity 1 - raw with its permutation test (the reference leaves it to vegan on the S x S matrix)
+# --------------------------------------------------------------------------------------------------
+def _na_real():
+    return float(np.array([_NA_REAL_BITS], dtype=np.uint64).view(np.float64)[0])
+
+
+def anosim_statistic(M, w2, nw):
+    """ANOSIM's R of one labelling as an exact ``Fraction``, from the integers of icikt_anosim_f64: M values, w2 the
+    doubled rank sum and nw the count of the within-class values.  R = (T2 nw - w2 M) / (nw nB M) with T2 = M (M + 1)
+    and nB = M - nw, which is ((M + 1) nw - w2) / (nw nB).  None when nw = 0 or nB = 0: R is undefined."""
+    M, w2, nw = int(M), int(w2), int(nw)
+    if nw <= 0 or nw >= M:
+        return None
+    return Fraction((M + 1) * nw - w2, nw * (M - nw))
+
+
+def anosim_permutations(codes, permutations=999, seed=None, strata=None):
+    """The labellings ``ici_kendalltau_anosim`` compares with, [n_perm, S] int32, from the class codes of the columns.
+    THE CONTRACT: ``rng = numpy.random.default_rng(seed)`` is made once; permutation t = 0, 1, .. is
+    ``rng.permutation(codes)``, drawn in this sequence.  With ``strata`` (a label per column) permutation t starts as
+    a copy of ``codes``, and for every stratum, the strata in order of first appearance, the codes at the stratum's
+    columns (ascending) are replaced by ``rng.permutation`` of them, on the same stream.  An integer array
+    ``permutations`` of shape [n_perm, S] is returned as given (as int32); ``seed`` and ``strata`` are then unused."""
+    codes = np.ascontiguousarray(codes, dtype=np.int32).ravel()
+    S = codes.shape[0]
+    if not isinstance(permutations, (int, np.integer)) or isinstance(permutations, (bool, np.bool_)):
+        perms = np.asarray(permutations)
+        if perms.ndim != 2 or perms.shape[1] != S or not np.issubdtype(perms.dtype, np.integer):
+            raise ValueError("`permutations` must be a count or an integer array [n_perm, S] of class codes")
+        return np.ascontiguousarray(perms, dtype=np.int32)
+    n_perm = int(permutations)
+    if n_perm < 0 or n_perm > _lib.ANOSIM_MAX_PERM:
+        raise ValueError(f"`permutations` must be in 0 .. {_lib.ANOSIM_MAX_PERM}")
+    groups = None
+    if strata is not None:
+        labels = list(np.asarray(strata, dtype=object).ravel())
+        if len(labels) != S:
+            raise ValueError("`strata` must give one stratum per column")
+        where = {}
+        for s, v in enumerate(labels):   # (a dict keeps the order of first appearance)
+            where.setdefault(v, []).append(s)
+        groups = [np.asarray(ix, dtype=np.intp) for ix in where.values()]
+    rng = np.random.default_rng(seed)
+    out = np.empty((n_perm, S), dtype=np.int32)
+    for t in range(n_perm):
+        if groups is None:
+            out[t] = rng.permutation(codes)
+        else:
+            out[t] = codes
+            for ix in groups:
+                out[t, ix] = rng.permutation(codes[ix])
+    return out
+
+
+def _anosim_numpy(raw, cls, n_class, perms):
+    """The sums of icikt_anosim_f64 from a full S x S raw matrix, for engines without an anosim method (the CPU tests'
+    checker engines): (n_pairs [2], w2, nw [1 + n_perm], n_ge, n_undefined, class_w2, class_nw [n_class])."""
+    raw = np.asarray(raw, dtype=np.float64)
+    S = raw.shape[0]
+    iu, ju = np.triu_indices(S, k=1)
+    v = raw[iu, ju]
+    ok = ~np.isnan(v)
+    iu, ju, v = iu[ok], ju[ok], v[ok] + 0.0
+    M = int(v.shape[0])
+    asc = np.sort(v)
+    r2 = (2 * M - np.searchsorted(asc, v, "left") - np.searchsorted(asc, v, "right") + 1).astype(np.int64)
+    labs = np.vstack([np.asarray(cls, dtype=np.int64)[None, :], np.asarray(perms, dtype=np.int64).reshape(-1, S)])
+    w2 = np.zeros(labs.shape[0], dtype=np.int64)
+    nw = np.zeros(labs.shape[0], dtype=np.int64)
+    for q, lab in enumerate(labs):
+        same = lab[iu] == lab[ju]
+        w2[q], nw[q] = r2[same].sum(), same.sum()
+    obs = anosim_statistic(M, w2[0], nw[0])
+    stats = [anosim_statistic(M, a, b) for a, b in zip(w2[1:], nw[1:])]
+    n_ge = sum(1 for f in stats if f is not None and obs is not None and f >= obs)
+    n_undef = sum(1 for f in stats if f is None)
+    same = labs[0][iu] == labs[0][ju]
+    class_w2 = np.zeros(n_class, dtype=np.int64)
+    np.add.at(class_w2, labs[0][iu][same], r2[same])
+    class_nw = np.bincount(labs[0][iu][same], minlength=n_class).astype(np.int64)
+    return np.array([M, S * (S - 1) // 2 - M], dtype=np.int64), w2, nw, n_ge, n_undef, class_w2, class_nw
+
+
+def ici_kendalltau_anosim(data_matrix, sample_classes, permutations=999, seed=None, strata=None, return_perms=True,
+                          global_na=(float("nan"), float("inf"), 0), perspective="global", alternative="two.sided",
+                          continuity=False, colnames=None, engine=None):
+    """Do the classes of the samples (columns) of a features x samples matrix separate under ICI-Kendall-tau, and how
+    sure is that: analysis of similarities (Clarke 1993; ``vegan::anosim``) on the dissimilarity ``1 - raw`` with its
+    permutation test -- without the S x S matrices ``ici_kendalltau`` returns.
+
+    ``sample_classes`` gives one label per column (required; the levels are ``ici_kendalltau_class_matrix``'s, in the
+    same order).  A pair is a value when its ``raw`` is not NA (the reference's warning is raised once per pair of
+    reasons 2-4); the M values are ranked by ascending ``1 - raw``, that is descending ``raw``, ties by their average
+    (-0 equals +0).  The statistic is R = (mean rank between classes - mean rank within classes) / (M / 2); it is 1 when
+    every within-class pair correlates better than every between-class pair, about 0 when the labels say nothing.  R is
+    undefined (NA) without a within-class or without a between-class value.
+
+    THE PERMUTATIONS are fixed by (input, ``seed``): ``rng = numpy.random.default_rng(seed)`` is made once and
+    permutation t is ``rng.permutation(codes)`` of the columns' class codes, drawn in sequence; with ``strata`` (a label
+    per column) the codes are permuted within each stratum, the strata in order of first appearance, on the same stream
+    (``anosim_permutations`` is that rule).  ``permutations`` is their number (999, at most 1 000 000) or an integer
+    array [n_perm, S] of class codes used as given.  ``pvalue`` is ``(1 + n_ge) / (1 + n_perm)`` with ``n_ge`` the
+    permutations whose R is defined and ``>=`` the observed R -- compared exactly, as fractions of integers, so no
+    margin like vegan's ``sqrt(.Machine$double.eps)`` is subtracted; ``n_undefined`` permutations have no R and do not
+    count.  ``statistic``, ``pvalue`` and every other double come from the integers by one correctly rounded
+    conversion.  On the HIP engine ranks and sums are computed on the device (icikt_anosim_f64); a matrix has at most
+    65 535 samples.  The other arguments are ``ici_kendalltau``'s (column names are required; a sparse matrix, float32
+    and integer matrices are read where they lie).
+
+    Returns a dict: ``statistic``, ``pvalue`` (NA when the observed R is undefined), ``n_permutations``, ``n_ge``,
+    ``n_undefined``, ``n_valid`` (M), ``n_na``, ``perm_statistic`` ([n_perm], NA where undefined; only with
+    ``return_perms``), ``class_levels``, ``class_mean_rank`` (per class the mean rank of its within-class values, NA
+    without one), ``within_mean_rank``, ``between_mean_rank``, ``sums`` (the integers: ``w2``, ``nw`` [1 + n_perm],
+    index 0 the observed labelling, ``class_w2``, ``class_nw``), ``sample_id``, ``max_taumax`` and ``run_time``.
+    """
+    data_matrix, names = _as_matrix(data_matrix, colnames, "data_matrix", keep_dtype=True, keep_sparse=True)
+    n_sample = data_matrix.shape[1]
+    if sample_classes is None:
+        raise ValueError("`sample_classes` must give one class per column")
+    levels, cls = _class_levels(sample_classes, n_sample, "all")
+    if n_sample < 2:
+        raise ValueError("No comparisons to do. Check the list of column names in "
+                         "`include_only` vs those in the samples.")  # R/kendalltau.R:240-247
+    perms = anosim_permutations(cls, permutations, seed, strata)
+    eng = engine or _default_engine()
+    if hasattr(eng, "anosim"):
+        X, global_na = _mask_on_host(data_matrix, global_na)
+        t1 = time.perf_counter()
+        n_pairs, w2, nw, n_ge, n_undef, class_w2, class_nw, max_taumax, rcounts = eng.anosim(
+            _for_engine(X, eng, fortran=False), cls, len(levels), perms, global_na, perspective, alternative, continuity, 0)
+        t_diff = time.perf_counter() - t1
+        _warn_pairs(rcounts)
+    else:
+        full = ici_kendalltau(data_matrix, global_na=global_na, perspective=perspective, scale_max=True, diag_good=True,
+                              alternative=alternative, continuity=continuity, colnames=names, engine=eng)
+        t_diff = full["run_time"]
+        n_pairs, w2, nw, n_ge, n_undef, class_w2, class_nw = _anosim_numpy(np.asarray(full["raw"]), cls, len(levels), perms)
+        max_taumax = _max_taumax(full["taumax"], np.triu_indices(n_sample, k=1))
+    M, n_perm = int(n_pairs[0]), int(perms.shape[0])
+    na = _na_real()
+    as_float = lambda f: na if f is None else float(f)   # noqa: E731  (Fraction -> float rounds correctly, once)
+    obs = anosim_statistic(M, w2[0], nw[0])
+    W2, nW = int(w2[0]), int(nw[0])
+    res = {"statistic": as_float(obs),
+           "pvalue": na if obs is None else float(Fraction(1 + int(n_ge), 1 + n_perm)),
+           "n_permutations": n_perm, "n_ge": int(n_ge), "n_undefined": int(n_undef), "n_valid": M,
+           "n_na": int(n_pairs[1])}
+    if return_perms:
+        res["perm_statistic"] = np.array([as_float(anosim_statistic(M, a, b)) for a, b in zip(w2[1:], nw[1:])],
+                                         dtype=np.float64)
+    res.update(class_levels=list(levels),
+               class_mean_rank=np.array([as_float(Fraction(int(a), 2 * int(b)) if b else None)
+                                         for a, b in zip(class_w2, class_nw)], dtype=np.float64),
+               within_mean_rank=as_float(Fraction(W2, 2 * nW) if nW else None),
+               between_mean_rank=as_float(Fraction(M * (M + 1) - W2, 2 * (M - nW)) if M > nW else None),
+               sums={"w2": w2, "nw": nw, "class_w2": class_w2, "class_nw": class_nw},
+               sample_id=list(names), max_taumax=max_taumax, run_time=t_diff)
     return res
 
 

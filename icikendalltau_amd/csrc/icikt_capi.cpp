@@ -1732,7 +1732,9 @@ extern "C" {
 // whole combn rows, 1 = a row per block, or per slice of several classes' pair list),
 // medlds (icikt_class_medians_*: partners up to which the select kernel stages a sample's keys in LDS, 0 .. 4096),
 // qbatch (icikt_quantiles_*: targets per batch of the select, 1 .. 32),
-// padjtile (icikt_padjust_*: keys of a wave's tile of the sort, 1 .. 2^30),
+// padjtile (icikt_padjust_*, icikt_anosim_*: keys of a wave's tile of the sort, 1 .. 2^30),
+// anoperms (icikt_anosim_*: labellings per upload, 1 .. 2^20), anostrip (icikt_anosim_*: columns of a workgroup of the
+// permutation kernel, 1 .. 4096),
 // verbose (0 | 1: print the plan to stderr).
 // (The keys h2d and regfail of rounds 2-3 are gone with the mode they steered: the library no longer page-locks
 // caller memory, icikt_host.h.)
@@ -1783,6 +1785,16 @@ int icikt_debug_set_plan(icikt_ctx* c, const char* spec) {
       ov.padjtile = atoll(val.c_str());
       if (ov.padjtile < 1 || ov.padjtile > (1ll << 30))
         return fail(c, ICIKT_E_INVALID, "debug_set_plan: padjtile must be in 1 .. 2^30 keys");
+    }
+    else if (key == "anoperms") {
+      ov.anoperms = atoll(val.c_str());
+      if (ov.anoperms < 1 || ov.anoperms > icikt::ANO_PERMS_MAX)
+        return fail(c, ICIKT_E_INVALID, "debug_set_plan: anoperms must be in 1 .. 2^20 labellings");
+    }
+    else if (key == "anostrip") {
+      ov.anostrip = atoi(val.c_str());
+      if (ov.anostrip < icikt::ANO_STRIP_MIN || ov.anostrip > icikt::ANO_STRIP_MAX)
+        return fail(c, ICIKT_E_INVALID, "debug_set_plan: anostrip must be in 1 .. 4096 columns");
     }
     else return fail(c, ICIKT_E_INVALID, "debug_set_plan: unknown key '" + key + "'");
   }

@@ -1,5 +1,5 @@
 // icikt_device.h -- structures, layouts and launcher declarations shared by the device units (icikt_prepass.hip,
-// icikt_kernels.hip, icikt_epilogue.hip, icikt_cor.hip, icikt_diag.hip, icikt_topk.hip, icikt_edges.hip, icikt_medians.hip, icikt_quantiles.hip, icikt_classmat.hip, icikt_padjust.hip, icikt_mst.hip) and the C-ABI
+// icikt_kernels.hip, icikt_epilogue.hip, icikt_cor.hip, icikt_diag.hip, icikt_topk.hip, icikt_edges.hip, icikt_medians.hip, icikt_quantiles.hip, icikt_classmat.hip, icikt_padjust.hip, icikt_mst.hip, icikt_anosim.hip) and the C-ABI
 // host side (icikt_capi*.cpp, icikt_multi.cpp).  Internal; the public boundary is include/icikt.h.
 #ifndef ICIKT_DEVICE_H
 #define ICIKT_DEVICE_H
@@ -291,6 +291,30 @@ struct MstBest {
 // not below min_key, equal keys by the smaller t
 hipError_t launch_mst_best(const unsigned long long* kept, const int32_t* comp, const int32_t* live,
                            unsigned long long min_key, int S, MstBest* best, hipStream_t s);
+// ---- ANOSIM: class separation under 1 - raw with its permutation test (icikt_anosim.hip) ----
+constexpr int ANO_PB = 16;                // labellings a workgroup of the permutation kernel takes side by side
+constexpr int ANO_ROW_RUN = 256;          // rows of a workgroup's run
+constexpr int ANO_STRIP_MIN = 1, ANO_STRIP_MAX = 4096, ANO_STRIP_DEFAULT = 256;   // columns of a workgroup's strip (anostrip)
+constexpr long long ANO_PERMS_MAX = 1 << 20;        // labellings per upload (anoperms)
+constexpr long long ANO_BATCH_BYTES = 64ll << 20;   // ... and the bytes of labels an upload holds when no key says otherwise
+// kept: the whole combn plane launch_median_keep writes (n keys).  *total += the keys that are not NA_KEY; dhist [8][256]
+// += the keys (NA_KEY included) per digit and digit value.  The caller zeroes total and dhist.
+hipError_t launch_anosim_count(const unsigned long long* kept, long long n, unsigned long long* total,
+                               unsigned long long* dhist, hipStream_t s);
+// sorted: the plane's keys ascending (launch_padj_sort_pass), the m values first.  r2[e] = 2 m - lo - hi + 1 with lo the
+// keys below kept[e] and hi the keys at or below it: the doubled average rank in descending order; 0 for NA_KEY
+hipError_t launch_anosim_rank(const unsigned long long* kept, const unsigned long long* sorted, long long n, long long m,
+                              unsigned long long* r2, hipStream_t s);
+// cls [S] in 0 .. n_class - 1; class_w2 / class_nw [n_class] (zeroed by the caller) += r2 / 1 per value whose two
+// samples are both of the class
+hipError_t launch_anosim_classes(const unsigned long long* r2, const int32_t* cls, int S, unsigned long long* class_w2,
+                                 unsigned long long* class_nw, hipStream_t s);
+// labT [n_groups][S][ANO_PB] halfwords: labelling g * ANO_PB + p gives sample s the class labT[(g * S + s) * ANO_PB + p].
+// w2 / nw [n_groups][ANO_PB] (zeroed by the caller) += r2 / 1 per value whose two samples share a class under the
+// labelling; nw only with count_nw (without an NA pair in the plane it follows from the class sizes).  strip: the
+// columns of a workgroup, ANO_STRIP_MIN .. ANO_STRIP_MAX
+hipError_t launch_anosim_perm(const unsigned long long* r2, const uint16_t* labT, int S, int n_groups, int strip,
+                              int count_nw, unsigned long long* w2, unsigned long long* nw, hipStream_t s);
 // ---- quantiles and histogram of all pairs (icikt_quantiles.hip) ----
 constexpr int QUANT_MAX_BINS = 1024;    // == ICIKT_HIST_MAX_BINS: k_quant_fold stages 1 025 breaks and 2 x 1 026 counters in LDS
 constexpr int QUANT_HEAD = 4;           // words of a counted group before its bins: n_valid, n_na, below, above

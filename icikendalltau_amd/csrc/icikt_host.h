@@ -177,6 +177,15 @@ struct icikt_ctx {
     DevBuf<icikt::MstBest> best;
   } mst;
 
+  // ANOSIM (icikt_anosim_f64): the kept plane (a key per pair of the triangle), the two planes of the sort -- the one
+  // the sort leaves free takes the doubled ranks --, the sort's counters and the scans' aggregates, the valid count and
+  // the digit table, the observed labelling and its per-class sums, a batch of labellings and their sums
+  struct AnosimBufs {
+    DevBuf<unsigned long long> kept, sort_a, sort_b, counts, agg, total, dhist, class_sums, w2, nw;
+    DevBuf<int32_t> cls;
+    DevBuf<uint16_t> labels;
+  } ano;
+
   // missing-value diagnostics (icikt_col_medians_f64, icikt_censor_counts_f64, icikt_rank_order_f64)
   struct DiagBufs {
     DevBuf<double> median, medrank, out;
@@ -198,7 +207,9 @@ struct icikt_ctx {
     long long tkblock = -1;   // icikt_topk_*, icikt_edges_*, icikt_class_medians_*, icikt_quantiles_*: pairs a block (whole combn rows, or a slice of the class list) may hold (default: the library's budget)
     int medlds = -1;          // icikt_class_medians_*, icikt_class_matrix_*: partners up to which the select kernel gathers a sample's keys into LDS (default: MEDIAN_STAGE_MAX)
     int qbatch = -1;          // icikt_quantiles_*: targets the select runs per batch (default: QUANT_BATCH_MAX)
-    long long padjtile = -1;  // icikt_padjust_*: keys of a wave's tile of the sort (default: padj_tile's choice)
+    long long padjtile = -1;  // icikt_padjust_*, icikt_anosim_*: keys of a wave's tile of the sort (default: padj_tile's choice)
+    long long anoperms = -1;  // icikt_anosim_*: labellings per upload (default: ANO_BATCH_BYTES of labels)
+    int anostrip = -1;        // icikt_anosim_*: columns of a workgroup of the permutation kernel (default: ANO_STRIP_DEFAULT)
     bool verbose = false;
   } plan_ov;
 
@@ -274,7 +285,7 @@ int check_pair_args(icikt_ctx* c, const char* who, const MatrixSrc& X, int64_t n
                     const int32_t* pi, const int32_t* pj, int64_t* n_pairs, const void* out, bool out5,
                     int perspective, int alternative);
 
-// ---- the selection entries (icikt_topk_*, icikt_edges_*, icikt_class_medians_*, icikt_quantiles_*, icikt_class_matrix_*, icikt_padjust_*, icikt_mst_*): one driver, icikt_capi_select.cpp ----
+// ---- the selection entries (icikt_topk_*, icikt_edges_*, icikt_class_medians_*, icikt_quantiles_*, icikt_class_matrix_*, icikt_padjust_*, icikt_mst_*, icikt_anosim_*): one driver, icikt_capi_select.cpp ----
 // (the blocks a call runs in: icikt_blocks.h; DESIGN.md "adding a selection entry")
 // the arguments the entries share
 struct SelectArgs {

@@ -553,6 +553,61 @@ int icikt_mst_f64(icikt_ctx *ctx, const double *X, int64_t n_feat, int64_t n_sam
                   double min_raw, int32_t *ti, int32_t *tj, double *out5t, int64_t *n_tree, int32_t *component,
                   int64_t *n_components, int32_t *n_rounds, double *max_taumax, int64_t *reason_counts);
 
+/* ---- ANOSIM: do the classes separate under ICI-Kt, with a permutation test, on the device --------------------------
+ *
+ * The question a quality-control run asks once the samples carry class labels: analysis of similarities (Clarke 1993;
+ * vegan::anosim) on the dissimilarity 1 - raw, without anything of size n_samp^2 on the host or as five planes on the
+ * device.  The whole combn triangle runs through the pair engine in blocks of whole rows (the tkblock budget, as
+ * icikt_topk_f64); a kernel keeps each pair's raw as a sortable 64-bit key; after the last block the device sorts a
+ * copy of the keys, ranks every pair, and sums the ranks of the within-class pairs of every labelling.
+ *   value        a pair i < j is a value iff its raw is not NA (reason code 0); M = n_pairs[0] is their count,
+ *                n_pairs[1] the count of the other pairs
+ *   order        values compare as their raw does, -0 equal to +0; equal doubles are ties
+ *   rank         a value's average rank among the M values in ascending dissimilarity 1 - raw, that is in DESCENDING
+ *                raw: R's rank(1 - raw, ties = "average") without the rounding of 1 - raw.  The library works with the
+ *                DOUBLED rank r2 = 2 M - lo - hi + 1 (lo: the values below the pair's raw, hi: those at or below it),
+ *                an integer in 2 .. 2 M
+ *   sums         for a labelling L (a class index per sample) W2(L) is the sum of r2 over the values whose two samples
+ *                share a class, nW(L) their count; T2 = M (M + 1) is the sum over all values, nB = M - nW.  Then
+ *                  R(L) = (T2 nW - W2 M) / (nW nB M)
+ *                exactly: vegan's -diff(tapply(rank, within, mean)) / (length(rank) / 2); without an NA pair M / 2 is
+ *                n_samp (n_samp - 1) / 4 as there.  R is UNDEFINED when nW = 0 or nB = 0: one class, singleton classes
+ *                only, M = 0, or -- with NA pairs -- a labelling that leaves no within-class value.
+ *   cls          [n_samp] the observed labelling, each in 0 .. n_class - 1 (NULL: one class, n_class ignored);
+ *                1 <= n_class <= ICIKT_ANOSIM_MAX_CLASSES
+ *   perm_cls     [n_perm][n_samp] row-major, the labellings to compare with (the caller's permutations of cls; any
+ *                labels in 0 .. n_class - 1 are taken as given), 0 <= n_perm <= ICIKT_ANOSIM_MAX_PERM.  They are read
+ *                once, where they lie, and cross to the device in batches of bounded size; every label is checked on
+ *                the way: one out of range is ICIKT_E_INVALID, the message names the permutation and the sample.
+ *   w2, nw       [1 + n_perm] W2 and nW; index 0 is the observed labelling, index 1 + t permutation t
+ *   n_ge         the permutations whose R is defined and >= the observed R, compared EXACTLY by cross-multiplication in
+ *                128-bit integers (vegan subtracts sqrt(.Machine$double.eps) because it compares rounded doubles; exact
+ *                arithmetic needs no margin).  The p-value is (1 + n_ge) / (1 + n_perm).  0 when the observed R is
+ *                undefined.
+ *   n_undefined  the permutations without an R; they are not counted as >=
+ *   class_w2, class_nw   [n_class] the observed labelling's sums restricted to the values inside class c: class c's
+ *                mean within rank is class_w2[c] / (2 class_nw[c])
+ * Every sum is below 2^63 (T2 < 2^63 at 65 535 samples).  n_samp of 0 or 1 gives M = 0 and zero sums; it is no error.
+ * All outputs but max_taumax and reason_counts (as icikt_topk_f64, over all pairs) are required.  A bad n_class, a label
+ * of cls out of range, a negative or too large n_perm, n_perm > 0 with a null perm_cls, a null output: ICIKT_E_INVALID
+ * before anything -- the context or an output -- is touched; a label of perm_cls out of range: ICIKT_E_INVALID with
+ * the outputs untouched.  n_samp <= ICIKT_TOPK_MAX_SAMPLES; n_feat, global_na and the state the call leaves behind
+ * (none): as icikt_topk_f64.  The result is a pure function of the input and the labellings: integer sums, counts and
+ * comparisons, whatever the block cut, the sort's tile, the batch, the strip or the grid.
+ * Device memory: the prepared matrix, one block's buffers, 24 bytes per pair of the triangle for the kept keys, their
+ * sorted copy and the sort's second plane, which takes the ranks (n_samp = 65 535: 51 GB), 2 KB per tile of the sort,
+ * and a batch of labels at two bytes each (64 MB unless the anoperms plan key says otherwise).  A failed allocation is
+ * ICIKT_E_HIP.  With ICIKT_FLAG_TIMING the keep, count, sort, rank and permutation kernels are accounted under
+ * ICIKT_K_EPILOGUE.
+ * icikt_anosim_in / icikt_anosim_csc: the same on a typed view / a CSC view of the matrix (below). */
+#define ICIKT_ANOSIM_MAX_PERM 1000000
+#define ICIKT_ANOSIM_MAX_CLASSES 65535
+int icikt_anosim_f64(icikt_ctx *ctx, const double *X, int64_t n_feat, int64_t n_samp, int64_t ld,
+                     const double *global_na, int n_global_na, int perspective, int alternative, int continuity,
+                     uint32_t flags, const int32_t *cls, int n_class, const int32_t *perm_cls, int64_t n_perm,
+                     int64_t *n_pairs, int64_t *w2, int64_t *nw, int64_t *n_ge, int64_t *n_undefined,
+                     int64_t *class_w2, int64_t *class_nw, double *max_taumax, int64_t *reason_counts);
+
 /* ---- several GPUs behind one call (what the R glue binds when n_gpu > 1) ----------------------
  *
  * Replaces the reference's worker fan-out, computation$split_fun(split_comparisons, ici_split, ...)
@@ -721,6 +776,11 @@ int icikt_mst_in(icikt_ctx *ctx, const icikt_input *X, int64_t n_feat, int64_t n
                  int n_global_na, int perspective, int alternative, int continuity, uint32_t flags, int scale_max,
                  double min_raw, int32_t *ti, int32_t *tj, double *out5t, int64_t *n_tree, int32_t *component,
                  int64_t *n_components, int32_t *n_rounds, double *max_taumax, int64_t *reason_counts);
+int icikt_anosim_in(icikt_ctx *ctx, const icikt_input *X, int64_t n_feat, int64_t n_samp, const double *global_na,
+                    int n_global_na, int perspective, int alternative, int continuity, uint32_t flags,
+                    const int32_t *cls, int n_class, const int32_t *perm_cls, int64_t n_perm, int64_t *n_pairs,
+                    int64_t *w2, int64_t *nw, int64_t *n_ge, int64_t *n_undefined, int64_t *class_w2,
+                    int64_t *class_nw, double *max_taumax, int64_t *reason_counts);
 int icikt_matrix_in(icikt_ctx *ctx, const icikt_input *X, int64_t n_feat, int64_t n_samp, const double *global_na,
                     int n_global_na, const int32_t *pi, const int32_t *pj, int64_t n_pairs, int perspective,
                     int alternative, int continuity, uint32_t flags, int scale_max, int diag_good, double *out5,
@@ -794,6 +854,11 @@ int icikt_mst_csc(icikt_ctx *ctx, const icikt_csc_input *X, int64_t n_feat, int6
                   int n_global_na, int perspective, int alternative, int continuity, uint32_t flags, int scale_max,
                   double min_raw, int32_t *ti, int32_t *tj, double *out5t, int64_t *n_tree, int32_t *component,
                   int64_t *n_components, int32_t *n_rounds, double *max_taumax, int64_t *reason_counts);
+int icikt_anosim_csc(icikt_ctx *ctx, const icikt_csc_input *X, int64_t n_feat, int64_t n_samp, const double *global_na,
+                     int n_global_na, int perspective, int alternative, int continuity, uint32_t flags,
+                     const int32_t *cls, int n_class, const int32_t *perm_cls, int64_t n_perm, int64_t *n_pairs,
+                     int64_t *w2, int64_t *nw, int64_t *n_ge, int64_t *n_undefined, int64_t *class_w2,
+                     int64_t *class_nw, double *max_taumax, int64_t *reason_counts);
 int icikt_missingness_csc(icikt_ctx *ctx, const icikt_csc_input *X, int64_t n_feat, int64_t n_samp, const int32_t *pi,
                           const int32_t *pj, int64_t n_pairs, int64_t *missingness);
 int icikt_col_medians_csc(icikt_ctx *ctx, const icikt_csc_input *X, int64_t n_feat, int64_t n_samp,
@@ -831,7 +896,9 @@ int icikt_selftest(icikt_ctx *ctx);
  * the partners up to which the select kernel gathers a sample's keys into LDS once, 0 .. 4096; a sample with more
  * re-reads the kept plane in every pass), qbatch (icikt_quantiles_*: the targets -- distinct (group, rank) -- the
  * select runs per batch of eight passes, 1 .. 32), padjtile (icikt_padjust_*: the keys of a tile of the sort, the run one
- * wave counts and scatters in order, 1 .. 2^30; raised when the plane would have more than 65 536 tiles), verbose (0 | 1: print the chosen
+ * wave counts and scatters in order, 1 .. 2^30; raised when the plane would have more than 65 536 tiles; icikt_anosim_* sorts with
+ * the same tile), anoperms (icikt_anosim_*: the labellings per upload, 1 .. 2^20; the permutation kernel takes them 16 at a
+ * time), anostrip (icikt_anosim_*: the columns of the triangle a workgroup of the permutation kernel owns, 1 .. 4096), verbose (0 | 1: print the chosen
  * plan to stderr). */
 int icikt_debug_set_plan(icikt_ctx *ctx, const char *spec);
 /* Development hook: per step kind of the pair kernel (hot loop, hot step in the main loop, MIXED, GROUP, general,
