@@ -37,6 +37,11 @@ constexpr int K0_THREADS_SMALL = 256;
 #define ICIKT_K0_WAVES_SMALL 5    // the small shape is compiled for five waves per SIMD (<= 96 registers): a wave of it fits a SIMD on which ONE pair-kernel wave (80 of 512 registers, six resident) has retired
 #endif
 constexpr int K0_UB = 8;       // iterations of a column pass whose loads a thread issues together
+#ifdef ICIKT_K0_NO_NETWORK   // diagnostic build: keys built, stored and read back, no compare-exchange runs -- what the
+constexpr bool K0_NETWORK = false;   // pre-pass takes without its sort (tools/k0_time.py --no-network); its results are WRONG
+#else
+constexpr bool K0_NETWORK = true;
+#endif
 constexpr int K0_TILE = 4096;  // elements of the LDS-resident sort tile (48 KB) = threads x elements per thread of the standard shapes
 
 __device__ __forceinline__ unsigned long long sortable_key(double v) {
@@ -474,7 +479,10 @@ __device__ __forceinline__ void k0_prepare_body(const PrepView& pv, const double
         nexcl += excl ? 1 : 0;
         if (keep_c && i < n) keep_c[i] = excl ? 0 : 1;
         const unsigned long long b = __ballot(isna);
-        if (lane == 0 && (i >> 6) < W) mask[i >> 6] = b;
+        if (lane == 0 && (i >> 6) < W) {
+          mask[i >> 6] = b;
+          if (!WIDE) sh_bits_lds[i >> 6] = b;   // (the one-word sort compacts the column by it)
+        }
         if (i < n && !isna) tmin = (v < tmin) ? v : tmin;
         nna += isna ? 1 : 0;
       }
@@ -502,8 +510,101 @@ __device__ __forceinline__ void k0_prepare_body(const PrepView& pv, const double
   const double fill = tmin - 0.1;  // kendallc.cpp:214-215, double arithmetic
 
   // ---- phases 1b + 2: sortable keys, sort.  FAST: one word per element (top 48 key bits | row), see kv_gt ------
+  // The one-word sort orders only the column's PRESENT values, where that makes the network smaller.  A missing or excluded
+  // row's key is `fill`, below every present value: the fill group is exactly those rows, in row order, so a row's place
+  // in it is the number of set bits of the phase-1 bitset below it.  cna = rows kept out of the sort; 0 -- the column is
+  // sorted whole, as the three-word sort always is -- when fill is not below the minimum (it rounds to it for
+  // |min| > 2^49, and every row may be missing) or when the present values alone would take the same slots (c2-like
+  // columns: the prefix counts and the second list would only cost).  sh_bigpre[w] = missing rows in the words before w
+  // (phase 3 rewrites it).
+  // What enters the network for x values (F = x / TILE full tiles, r = x mod TILE left over):
+  //   np2   elements the tile sorts and merge levels run over, the first nreal of them real;
+  //   m     a SUB-TILE behind them: the r left-over values, padded to a power of two (>= one wave's 64 E elements), sorted by
+  //         the waves that hold them at offset sub_lo of the tile slot at np2.  F = 0: the whole sort, ascending.  F a power of
+  //         two: the np2 = F TILE values in front are sorted without any padding and the sub-tile, descending at the END of
+  //         its slot, is where a full sort of the upper half would have left its real elements; the last merge level then
+  //         exchanges only the m pairs that reach it, merges the lower half as usual and the sub-tile with the distances
+  //         below m (the stages above m would move it to the front of the upper half unchanged: it is stored there).
+  //         The sorted values end up contiguous at keys[0 .. x).
+  //   Other F (3, 5, 6, 7, ...): np2 = the power of two above x, tiles of padding skipped.
+  //   Short columns (npow2 < TILE): the all-LDS sort at the size it has always had.
+  // Returns the slots the network runs over.
+  auto sort_plan = [&](int x, int& np2, int& nreal, int& m, int& sub_lo) -> int {
+    np2 = npow2; nreal = x; m = 0; sub_lo = 0;
+    if (npow2 < TILE) return np2;
+    const int F = x / TILE, r = x - F * TILE;
+    const int rp2 = (r <= 64 * E) ? 64 * E : (1 << (32 - __builtin_clz((uint32_t)(r - 1))));
+    if (rp2 == TILE) np2 = 1 << (32 - __builtin_clz((uint32_t)(x - 1)));   // (more than half a tile left over: a tile like the others)
+    else if (F == 0) { np2 = 0; nreal = 0; m = rp2; }
+    else if ((F & (F - 1)) == 0 && r > 0) { np2 = nreal = F * TILE; m = rp2; sub_lo = K0_NETWORK ? TILE - m : 0; }
+    else np2 = 1 << (32 - __builtin_clz((uint32_t)(x - 1)));   // (x >= TILE here)
+    return np2 + m;
+  };
+  int cna = 0;
+  if constexpr (!WIDE) {
+    int a0, a1, a2, a3;
+    if (nna > 0 && fill < tmin && sort_plan(n - nna, a0, a1, a2, a3) < sort_plan(n, a0, a1, a2, a3)) {   // (uniform over the workgroup)
+      cna = nna;
+      int pbase = 0;
+      for (int wb = 0; wb < W; wb += NT) {
+        const int wi = wb + tid;
+        const int cnt = (wi < W) ? (int)__popcll(sh_bits_lds[wi]) : 0;
+        const int incl = (int)wave_incl_scan((uint32_t)cnt);
+        if (lane == 63) sh_i[tid >> 6] = incl;
+        __syncthreads();
+        int wbase = pbase, btot = 0;
+        for (int w = 0; w < NW; ++w) {
+          const int t = sh_i[w];
+          if (w < (tid >> 6)) wbase += t;
+          btot += t;
+        }
+        if (wi < W) sh_bigpre[wi] = (uint16_t)(wbase + incl - cnt);
+        pbase += btot;
+        __syncthreads();
+      }
+    }
+  }
+
   auto sort_pass = [&](auto fast_tag) {
   constexpr bool FAST = decltype(fast_tag)::value;
+  int np2 = npow2, nreal = n, m = 0, sub_lo = 0;
+  if constexpr (FAST) {
+    const int p = n - cna, r = p % TILE;
+    sort_plan(p, np2, nreal, m, sub_lo);
+    const int slot_end = ((m > 0) ? np2 + sub_lo + r : p);            // one past the last real element
+    const int pad_end = (m > 0) ? np2 + sub_lo + m : np2;
+    for (int base0 = 0; base0 < pv.n_pad; base0 += NT * K0_UB) {
+      double vv[K0_UB];
+#pragma unroll
+      for (int u = 0; u < K0_UB; ++u) {
+        const int i = base0 + u * NT + tid;
+        vv[u] = (i < n) ? col[i] : 0.0;
+      }
+#pragma unroll
+      for (int u = 0; u < K0_UB; ++u) {
+        const int i = base0 + u * NT + tid;
+        if (i < n) {
+          double v = vv[u];
+          int q = 0;          // missing rows in front of row i
+          bool gone = false;  // row i is one of them
+          if (cna) {
+            const unsigned long long w = sh_bits_lds[i >> 6];
+            q = (int)sh_bigpre[i >> 6] + (int)__popcll(w & ((1ull << (i & 63)) - 1ull));
+            gone = ((w >> (i & 63)) & 1ull) != 0ull;
+          } else if (v != v || mask_excluded(ms, v)) {
+            v = fill;
+          }
+          if (gone) {
+            idx[q] = (uint32_t)i;   // its place in the ascending order
+          } else {
+            const int d = i - q;    // dense index among the present values
+            keys[(d < np2 || m == 0) ? d : d + sub_lo] = (sortable_key(v) & ~0xFFFFull) | (unsigned long long)i;   // (n <= 65 535: the row fits the low 16 bits)
+          }
+        }
+      }
+    }
+    for (int i = slot_end + tid; i < pad_end; i += NT) keys[i] = ~0ull;
+  } else {
   for (int base0 = 0; base0 < npow2; base0 += NT * K0_UB) {
     double vv[K0_UB];
 #pragma unroll
@@ -529,6 +630,7 @@ __device__ __forceinline__ void k0_prepare_body(const PrepView& pv, const double
       }
     }
   }
+  }
   __syncthreads();
 
   // ---- phase 2: bitonic sort of (key, row): the row index breaks ties, which makes the result the
@@ -536,16 +638,16 @@ __device__ __forceinline__ void k0_prepare_body(const PrepView& pv, const double
   //      distances below the tile size run on an LDS-resident tile; only the long distances of the
   //      last merges touch global memory. -------------------------------------------------------------
   {
-    const int T = (npow2 < TILE) ? npow2 : TILE;
-    const int ntiles = npow2 / T;
-    if (T == TILE) {
+    const int T = (np2 < TILE && m == 0) ? np2 : TILE;
+    const int ntiles = np2 / T;
+    if (K0_NETWORK && T == TILE) {
       // full tiles: register / shuffle stages (k0_reg_stages) around the LDS stages with distance >= 256
       // (a wave holds 64 E consecutive elements: distances up to 32 E in registers, 64 E and more on the LDS tile)
       unsigned long long ek[E];
       uint32_t ei[E];
       for (int tile = 0; tile < ntiles; ++tile) {
         const int tb = tile * T;
-        if (tb >= n) continue;  // a tile of padding only (equal keys) is sorted in either direction already
+        if (tb >= nreal) continue;  // a tile of padding only (equal keys) is sorted in either direction already
         const int gi = tb + E * tid;
 #pragma unroll
         for (int r = 0; r < E; ++r) { ek[r] = keys[gi + r]; ei[r] = FAST ? 0u : idx[gi + r]; }
@@ -563,23 +665,85 @@ __device__ __forceinline__ void k0_prepare_body(const PrepView& pv, const double
 #pragma unroll
         for (int r = 0; r < E; ++r) { keys[gi + r] = ek[r]; if (!FAST) idx[gi + r] = ei[r]; }
       }
+      // the sub-tile (a body of its own: with run-time sizes in the loop above the full tiles' LDS passes lose their
+      // compile-time trip counts): cnt elements at offset lo of the slot at np2, held by the waves `mine` (every thread stays
+      // for the barriers); its last step sorts in the direction of bit kf of its index -- ascending in front of nothing (bit
+      // T of slot 0), descending behind np2 values (bit np2 of the slot at np2)
+      if constexpr (FAST) {
+        if (m > 0) {
+          const int tb = np2, lo = sub_lo, cnt = m, kf = (np2 > 0) ? np2 : T;
+          const bool mine = E * tid >= lo && E * tid < lo + cnt;   // (whole waves: lo and cnt are multiples of 64 E)
+          const int gi = tb + E * tid;
+          if (mine) {
+#pragma unroll
+            for (int r = 0; r < E; ++r) { ek[r] = keys[gi + r]; ei[r] = 0u; }
+            for (int k = 2; k <= 64 * E; k <<= 1) k0_reg_stages<FAST, E>(ek, ei, (k == cnt) ? kf : k, k >> 1, gi, tid);
+          }
+          for (int k = 128 * E; k <= cnt; k <<= 1) {
+            const int kd = (k == cnt) ? kf : k;
+            if (mine) {
+#pragma unroll
+              for (int r = 0; r < E; ++r) sh_tk[E * tid + r] = ek[r];
+            }
+            __syncthreads();
+            k0_mem_stages<FAST, NT>(sh_tk + lo, sh_ti + lo, cnt, tb + lo, kd, k >> 1, 64 * E, tid);
+            if (mine) {
+#pragma unroll
+              for (int r = 0; r < E; ++r) ek[r] = sh_tk[E * tid + r];
+            }
+            __syncthreads();
+            if (mine) k0_reg_stages<FAST, E>(ek, ei, kd, 32 * E, gi, tid);
+          }
+          if (mine) {
+#pragma unroll
+            for (int r = 0; r < E; ++r) keys[gi + r] = ek[r];
+          }
+        }
+      }
       __syncthreads();
       // merges across tiles: distances >= T in global memory, 2048..256 on the LDS tile, the rest in registers
-      for (int k = 2 * T; k <= npow2; k <<= 1) {
-        k0_mem_stages<FAST, NT>(keys, idx, npow2, 0, k, k >> 1, T, tid);   // (global scratch: __syncthreads orders a workgroup's global accesses)
-        for (int tile = 0; tile < ntiles; ++tile) {
-          const int tb = tile * T;
-          const int gi = tb + E * tid;
+      // With a sub-tile behind np2 values, one more level (k = 2 np2) merges the two: the upper half is padding but for the
+      // sub-tile at its end, so of the level's first stage only the m pairs that reach the sub-tile can exchange; the lower
+      // half then takes the level's other stages as usual, and the sub-tile those below m, as one more "tile" (ascending:
+      // direction bit k of an index below T), stored at the front of the upper half.
+      const int ktop = (m > 0 && np2 > 0) ? 2 * np2 : np2;
+      for (int k = 2 * T; k <= ktop; k <<= 1) {
+        const bool top = k > np2;
+        if constexpr (FAST) {
+          if (top) {
+            for (int x = tid; x < m; x += NT) {
+              const int i = np2 - m + x, l = np2 + sub_lo + x;
+              const unsigned long long ka = keys[i], kb = keys[l];
+              if (ka > kb) { keys[i] = kb; keys[l] = ka; }
+            }
+            __syncthreads();
+          }
+        }
+        k0_mem_stages<FAST, NT>(keys, idx, np2, 0, k, top ? (np2 >> 1) : (k >> 1), T, tid);   // (global scratch: __syncthreads orders a workgroup's global accesses)
+        for (int tile = 0; tile < ntiles + (top ? 1 : 0); ++tile) {
+          const bool sub = tile == ntiles;
+          const int tb = sub ? 0 : tile * T;                     // what the direction bit is taken from
+          const int lo = sub ? sub_lo : 0, cnt = sub ? m : T;
+          const bool mine = E * tid >= lo && E * tid < lo + cnt;
+          const int src = tile * T + E * tid, gi = tb + E * tid;
+          if (mine) {
 #pragma unroll
-          for (int r = 0; r < E; ++r) { sh_tk[E * tid + r] = keys[gi + r]; if (!FAST) sh_ti[E * tid + r] = idx[gi + r]; }
+            for (int r = 0; r < E; ++r) { sh_tk[E * tid + r] = keys[src + r]; if (!FAST) sh_ti[E * tid + r] = idx[src + r]; }
+          }
           __syncthreads();
-          k0_mem_stages<FAST, NT>(sh_tk, sh_ti, T, tb, k, T >> 1, 64 * E, tid);   // (the direction is constant inside a tile: k > T)
+          // (the direction is constant inside a tile: k > T)
+          if (sub) k0_mem_stages<FAST, NT>(sh_tk + lo, sh_ti + lo, cnt, tb, k, cnt >> 1, 64 * E, tid);
+          else k0_mem_stages<FAST, NT>(sh_tk, sh_ti, TILE, tb, k, TILE >> 1, 64 * E, tid);
+          if (mine) {
 #pragma unroll
-          for (int r = 0; r < E; ++r) { ek[r] = sh_tk[E * tid + r]; ei[r] = FAST ? 0u : sh_ti[E * tid + r]; }
+            for (int r = 0; r < E; ++r) { ek[r] = sh_tk[E * tid + r]; ei[r] = FAST ? 0u : sh_ti[E * tid + r]; }
+          }
           __syncthreads();
-          k0_reg_stages<FAST, E>(ek, ei, k, 32 * E, gi, tid);
+          if (mine) {
+            k0_reg_stages<FAST, E>(ek, ei, k, 32 * E, gi, tid);
 #pragma unroll
-          for (int r = 0; r < E; ++r) { keys[gi + r] = ek[r]; if (!FAST) idx[gi + r] = ei[r]; }
+            for (int r = 0; r < E; ++r) { keys[src - lo + r] = ek[r]; if (!FAST) idx[src - lo + r] = ei[r]; }
+          }
         }
         __syncthreads();
       }
@@ -587,7 +751,7 @@ __device__ __forceinline__ void k0_prepare_body(const PrepView& pv, const double
       // short columns (npow2 < 4096): one partial tile, every stage on LDS
       for (int i = tid; i < T; i += NT) { sh_tk[i] = keys[i]; if (!FAST) sh_ti[i] = idx[i]; }
       __syncthreads();
-      for (int k = 2; k <= T; k <<= 1) {
+      for (int k = 2; K0_NETWORK && k <= T; k <<= 1) {
         for (int j = k >> 1; j > 0; j >>= 1) {
           for (int t = tid; t < (T >> 1); t += NT) {
             const int i = ((t & ~(j - 1)) << 1) | (t & (j - 1));
@@ -627,8 +791,14 @@ __device__ __forceinline__ void k0_prepare_body(const PrepView& pv, const double
 #pragma unroll
       for (int u = 0; u < K0_UB; ++u) {
         const int k = base0 + u * NT + tid;
-        rowv[u] = (k < n) ? ((uint32_t)keys[k] & 0xFFFFu) : 0u;
-        rowp[u] = (lane == 0 && k > 0 && k < n) ? ((uint32_t)keys[k - 1] & 0xFFFFu) : 0u;   // a wave's first lane: its predecessor too
+        // (the ascending order: the cna rows kept out of the sort, listed in idx by the key pass, then the sorted words)
+        // (one load either way: the low half of a sorted word or a listed row, both below 65 536)
+        const auto row_at = [&](int q) -> uint32_t {
+          const uint32_t* w = (q < cna) ? idx + q : reinterpret_cast<const uint32_t*>(keys + (q - cna));
+          return *w & 0xFFFFu;
+        };
+        rowv[u] = (k < n) ? row_at(k) : 0u;
+        rowp[u] = (lane == 0 && k > 0 && k < n) ? row_at(k - 1) : 0u;   // a wave's first lane: its predecessor too
       }
 #pragma unroll
       for (int u = 0; u < K0_UB; ++u) {
@@ -645,7 +815,7 @@ __device__ __forceinline__ void k0_prepare_body(const PrepView& pv, const double
             double v = vv[u];
             if (v != v || mask_excluded(ms, v)) v = fill;
             fk = sortable_key(v);
-            idx[k] = rowv[u];
+            if (k >= cna) idx[k] = rowv[u];
           }
           unsigned long long prev = __shfl_up(fk, 1, 64);
           if (lane == 0 && k > 0 && k < n) {
@@ -660,7 +830,7 @@ __device__ __forceinline__ void k0_prepare_body(const PrepView& pv, const double
         }
       }
     }
-    if (__syncthreads_or(inv)) sort_pass(std::false_type{});
+    if (__syncthreads_or(inv) && K0_NETWORK) sort_pass(std::false_type{});
     else starts_done = true;
   }
 
