@@ -24,6 +24,7 @@ SOURCES = [os.path.join(_PKG, "csrc", f) for f in ("icikt_kernels.hip", "icikt_p
                                                        "icikt_classmat.hip", "icikt_capi_classmat.cpp",
                                                        "icikt_padjust.hip", "icikt_capi_padjust.cpp",
                                                        "icikt_mst.hip", "icikt_capi_mst.cpp",
+                                                       "icikt_hclust.hip", "icikt_capi_hclust.cpp",
                                                        "icikt_anosim.hip", "icikt_capi_anosim.cpp")]
 HEADERS = [os.path.join(_ROOT, "include", "icikt.h"), os.path.join(_PKG, "csrc", "icikt_device.h"),
            os.path.join(_PKG, "csrc", "icikt_wave.h"), os.path.join(_PKG, "csrc", "icikt_host.h"),
@@ -49,6 +50,7 @@ QUANTILE_MAX_PROBS = 32       # ICIKT_QUANTILE_MAX_PROBS: probabilities per call
 HIST_MAX_BINS = 1024          # ICIKT_HIST_MAX_BINS
 ADJUST = {"bonferroni": 0, "holm": 1, "hochberg": 2, "BH": 3}   # ICIKT_ADJUST_*: R's p.adjust methods of icikt_padjust_*
 ADJUST_MAX_ALPHA = 16         # ICIKT_ADJUST_MAX_ALPHA: alphas per call of icikt_padjust_*
+HCLUST = {"complete": 0, "average": 1, "single": 2}   # ICIKT_HCLUST_*: linkage methods of icikt_hclust_*
 ANOSIM_MAX_PERM = 1000000     # ICIKT_ANOSIM_MAX_PERM: labellings per call of icikt_anosim_* beside the observed one
 MASK_VALS = 32                # distinct finite global_na values of the device-side exclusion rule (icikt_device.h)
 MAX_FEATURES = 65535          # the tuned kernels
@@ -87,6 +89,7 @@ EXPORTS = (
     "icikt_class_matrix_f64", "icikt_class_matrix_in", "icikt_class_matrix_csc",
     "icikt_padjust_f64", "icikt_padjust_in", "icikt_padjust_csc",
     "icikt_mst_f64", "icikt_mst_in", "icikt_mst_csc",
+    "icikt_hclust_f64", "icikt_hclust_in", "icikt_hclust_csc",
     "icikt_anosim_f64", "icikt_anosim_in", "icikt_anosim_csc",
 )
 
@@ -382,6 +385,8 @@ def lib():
                                     c_int, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]
     L.icikt_mst_f64.argtypes = [c_vp, c_vp, c_i64, c_i64, c_i64, c_vp, c_int, c_int, c_int, c_int, c_u32, c_int,
                                 ctypes.c_double, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]
+    L.icikt_hclust_f64.argtypes = [c_vp, c_vp, c_i64, c_i64, c_i64, c_vp, c_int, c_int, c_int, c_int, c_u32, c_int, c_int,
+                                   ctypes.c_double, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]
     L.icikt_anosim_f64.argtypes = [c_vp, c_vp, c_i64, c_i64, c_i64, c_vp, c_int, c_int, c_int, c_int, c_u32, c_vp, c_int,
                                    c_vp, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]
     L.icikt_multi_rank_phase_ms.argtypes = [c_vp, c_int, ctypes.POINTER(ctypes.c_double)]
@@ -389,13 +394,13 @@ def lib():
     L.icikt_debug_step_stats.argtypes = [c_vp, c_vp, c_int]
     # the *_in twins: (ctx, const icikt_input*, n_feat, n_samp, ...) where the _f64 entry has (ctx, X, n_feat, n_samp, ld, ...)
     for nm in ("pairs", "matrix", "pairs_complete", "missingness", "cor_pairs", "col_medians", "censor_counts",
-               "rank_order", "topk", "edges", "class_medians", "quantiles", "class_matrix", "padjust", "mst", "anosim"):
+               "rank_order", "topk", "edges", "class_medians", "quantiles", "class_matrix", "padjust", "mst", "hclust", "anosim"):
         f64 = getattr(L, f"icikt_{nm}_f64").argtypes
         getattr(L, f"icikt_{nm}_in").argtypes = [c_vp, ctypes.POINTER(InputView), c_i64, c_i64] + list(f64[5:])
     L.icikt_convert_dev.argtypes = [c_vp, c_vp, c_int, c_int, c_i64, c_i64, c_i64, c_vp, c_i64]
     # the *_csc twins: (ctx, const icikt_csc_input*, n_feat, n_samp, ...)
     for nm in ("pairs", "matrix", "missingness", "col_medians", "censor_counts", "rank_order", "topk", "edges",
-               "class_medians", "quantiles", "class_matrix", "padjust", "mst", "anosim"):
+               "class_medians", "quantiles", "class_matrix", "padjust", "mst", "hclust", "anosim"):
         f64 = getattr(L, f"icikt_{nm}_f64").argtypes
         getattr(L, f"icikt_{nm}_csc").argtypes = [c_vp, ctypes.POINTER(CscInput), c_i64, c_i64] + list(f64[5:])
     L.icikt_scatter_csc_dev.argtypes = [c_vp, c_vp, c_vp, c_vp, c_int, c_int, ctypes.c_double, c_i64, c_i64, c_vp, c_i64]
@@ -819,6 +824,38 @@ class Context:
         m = int(n_tree[0])
         # (the library's planes are room apart: one row of vals each when room >= 1)
         return (ti[:m], tj[:m], vals[:, :m], component[:n_samp], int(n_comp[0]), int(n_rounds[0]), float(mx[0]), rc5)
+
+    def hclust(self, X, method="complete", min_raw=None, global_na=None, perspective="global", alternative="two.sided",
+               continuity=False, flags: int = 0, scale_max=True):
+        """Agglomerative clustering of the samples under raw with "complete", "average" or "single" linkage, run on the
+        device (icikt_hclust_f64): all pairs are computed, and nothing of size S x S exists on the host or as five
+        planes on the device.  A cluster lives in the slot of its smallest sample; each step merges the best live pair
+        of clusters a < b into a, in the strict order larger similarity first (-0 equal to +0), then smaller a, then
+        smaller b; the merged cluster's similarity to another is NA if either old one is, else the smaller (complete),
+        the larger (single) or the size-weighted mean (average: two products, two sums, one division, each rounded
+        once) of the two.  Merging ends at the first step whose best similarity is NA or below min_raw.  method may
+        also be the library's code; X and global_na as matrix() takes them.  Returns (ma, mb, msize [n_merges] int32:
+        the slots a < b and the new cluster's samples, in merge order; mraw, mcor [n_merges]; component [S] int32: the
+        clusters that are left, numbered in order of their smallest sample; n_components; max_taumax; reason_counts
+        [5]) with n_merges + n_components == S.  The argument checks are the library's: an unknown method or a bad
+        perspective raises IciktError."""
+        fn, fname, xargs, n_feat, n_samp, flags, _keep = self._entry("hclust", X, flags)
+        gna, codes, mx, rc5 = _select_args(global_na, perspective, alternative)
+        code = HCLUST.get(method, -1) if isinstance(method, str) else int(method)
+        room = max(n_samp - 1, 0) if n_samp <= TOPK_MAX_SAMPLES else 0   # (the library refuses more samples before it writes)
+        ma = np.empty(max(room, 1), dtype=np.int32)
+        mb = np.empty(max(room, 1), dtype=np.int32)
+        msize = np.empty(max(room, 1), dtype=np.int32)
+        mraw = np.empty(max(room, 1), dtype=np.float64)
+        mcor = np.empty(max(room, 1), dtype=np.float64)
+        component = np.zeros(max(n_samp, 1), dtype=np.int32)
+        n_merges = np.zeros(1, dtype=np.int64)
+        n_comp = np.zeros(1, dtype=np.int64)
+        self._chk(fn(self._h, *xargs, *gna[1:], *codes, int(bool(continuity)), flags, int(bool(scale_max)), code,
+                     float("nan") if min_raw is None else float(min_raw), _ptr(ma), _ptr(mb), _ptr(msize), _ptr(mraw),
+                     _ptr(mcor), _ptr(n_merges), _ptr(component), _ptr(n_comp), _ptr(mx), _ptr(rc5)), fname)
+        m = int(n_merges[0])
+        return (ma[:m], mb[:m], msize[:m], mraw[:m], mcor[:m], component[:n_samp], int(n_comp[0]), float(mx[0]), rc5)
 
     def anosim(self, X, cls=None, n_class=1, perm_cls=None, global_na=None, perspective="global",
                alternative="two.sided", continuity=False, flags: int = 0):

@@ -105,6 +105,13 @@ class HipEngine:
         return self.ctx.mst(data_matrix, min_raw, global_na, perspective, alternative, continuity, self.flags | flags,
                             scale_max)
 
+    def hclust(self, data_matrix, method="complete", min_raw=None, global_na=None, perspective="global",
+               alternative="two.sided", continuity=False, flags=0, scale_max=True):
+        """Complete, average or single linkage under raw, run on the device (icikt_hclust_f64): Context.hclust's
+        contract."""
+        return self.ctx.hclust(data_matrix, method, min_raw, global_na, perspective, alternative, continuity,
+                               self.flags | flags, scale_max)
+
     def anosim(self, data_matrix, cls=None, n_class=1, perm_cls=None, global_na=None, perspective="global",
                alternative="two.sided", continuity=False, flags=0):
         """ANOSIM's rank sums of the observed labelling and of every permutation, on the device (icikt_anosim_f64):
@@ -230,6 +237,11 @@ class MultiHipEngine(HipEngine):
             continuity=False, flags=0, scale_max=True):   # the rounds run on one device
         return self._one().mst(data_matrix, min_raw, global_na, perspective, alternative, continuity,
                                self.flags | flags, scale_max)
+
+    def hclust(self, data_matrix, method="complete", min_raw=None, global_na=None, perspective="global",
+               alternative="two.sided", continuity=False, flags=0, scale_max=True):   # the steps run on one device
+        return self._one().hclust(data_matrix, method, min_raw, global_na, perspective, alternative, continuity,
+                                  self.flags | flags, scale_max)
 
     def anosim(self, data_matrix, cls=None, n_class=1, perm_cls=None, global_na=None, perspective="global",
                alternative="two.sided", continuity=False, flags=0):   # the sort and the rank plane live on one device
@@ -1359,8 +1371,8 @@ def ici_kendalltau_mst(data_matrix, min_raw=None, global_na=(float("nan"), float
     equal to +0; equal ``raw`` by the smaller ``combn`` index (i ascending, then j ascending).  The order is total, so
     the maximum spanning forest under it is unique -- a pure function of the input.  Its edges are returned in that
     order, which is Kruskal's order and the single-linkage merge order.  A sample all of whose pairs are NA or below
-    ``min_raw`` (a constant or all-missing column) is a component of its own.  Only single linkage is offered:
-    complete and average linkage need S - 1 dependent updates of an S x S table and are deliberately left out.
+    ``min_raw`` (a constant or all-missing column) is a component of its own.  This is single linkage; complete and
+    average linkage, which need S - 1 dependent updates of an S x S table, are ``ici_kendalltau_hclust``.
 
     The other arguments are ``ici_kendalltau``'s (column names are required; a sparse matrix, float32 and integer
     matrices are read where they lie).  On the HIP engine the forest is found on the device (icikt_mst_f64); a matrix
@@ -1406,6 +1418,122 @@ def ici_kendalltau_mst(data_matrix, min_raw=None, global_na=(float("nan"), float
     res["max_taumax"] = max_taumax
     res["run_time"] = t_diff
     return res
+
+
+# --------------------------------------------------------------------------------------------------
+# ici_kendalltau_hclust: complete, average and single linkage of the samples under raw -- the dendrogram and heatmap
+# ordering by the methods R's hclust and scipy default to (the reference leaves them to hclust on the full matrix)
+# --------------------------------------------------------------------------------------------------
+HCLUST_METHODS = ("complete", "average", "single")
+
+
+def _hclust_numpy(mats5, method, min_raw):
+    """The merges of icikt_hclust_f64 from five full S x S matrices (only raw is read), for engines without an hclust
+    method (the CPU tests' checker engines): S - 1 steps over a copy of raw, each an argmax over the upper triangle of
+    the live slots -- row-major, so equal similarities go to the smaller a, then the smaller b -- and an update of row
+    and column a.  A NaN anywhere between two clusters makes them unmergeable; -0 counts as +0; average is
+    (n_a w_a + n_b w_b) / (n_a + n_b) in plain float64 operations.  Returns (ma, mb, msize, mraw, component [S],
+    n_components)."""
+    if method not in HCLUST_METHODS:
+        raise ValueError("`method` must be complete, average or single")
+    with np.errstate(invalid="ignore"):
+        W = np.array(mats5[1], dtype=np.float64) + 0.0      # (+ 0.0: -0 becomes +0)
+    S = W.shape[0]
+    np.fill_diagonal(W, np.nan)
+    W[np.tril_indices(S)] = np.nan                           # the upper triangle carries the table: W[a, b], a < b
+    W = np.fmax(W, W.T)                                      # ... mirrored, so that a row is a slot's similarities
+    alive = np.ones(S, dtype=bool)
+    size = np.ones(S, dtype=np.int64)
+    parent = np.arange(S)
+    ma, mb, msize, mraw = [], [], [], []
+    for _step in range(S - 1):
+        U = np.where(np.triu(alive[:, None] & alive[None, :], k=1), W, np.nan)
+        if np.all(np.isnan(U)):
+            break
+        flat = int(np.nanargmax(U))                          # the first of equal maxima in row-major order
+        a, b = divmod(flat, S)
+        best = U[a, b]
+        if min_raw is not None and not best >= min_raw:
+            break
+        wa, wb = W[a].copy(), W[b].copy()
+        if method == "complete":
+            new = np.minimum(wa, wb)                         # (np.minimum propagates NaN)
+        elif method == "single":
+            new = np.maximum(wa, wb)
+        else:
+            na, nb = float(size[a]), float(size[b])
+            new = (na * wa + nb * wb) / (na + nb) + 0.0
+        new[a] = np.nan
+        W[a, :] = new
+        W[:, a] = new
+        alive[b] = False
+        size[a] += size[b]
+        parent[b] = a
+        ma.append(a)
+        mb.append(b)
+        msize.append(int(size[a]))
+        mraw.append(best)
+    component, n_comp = _mst_components(parent)
+    return (np.asarray(ma, dtype=np.int32), np.asarray(mb, dtype=np.int32), np.asarray(msize, dtype=np.int32),
+            np.asarray(mraw, dtype=np.float64), component, n_comp)
+
+
+def ici_kendalltau_hclust(data_matrix, method="complete", min_raw=None, global_na=(float("nan"), float("inf"), 0),
+                          perspective="global", scale_max=True, alternative="two.sided", continuity=False, colnames=None,
+                          engine=None):
+    """Agglomerative clustering of the samples (columns) of a features x samples matrix under their ICI-Kendall-tau with
+    ``"complete"`` (R's ``hclust`` default), ``"average"`` (scipy's and seaborn's) or ``"single"`` linkage, without the
+    S x S matrices ``ici_kendalltau`` returns.
+
+    The rule.  The similarity of two samples is the pair's ``raw`` (-0 equal to +0); a pair whose ``raw`` is NA has
+    none.  A cluster lives in the slot of its smallest sample, and slot i starts as sample i.  Each step merges the
+    best live pair of clusters a < b into a, in a strict order: the larger similarity first, then the smaller a, then
+    the smaller b -- a total order, so the result is a pure function of the input.  The merged cluster's similarity to
+    a cluster k is NA if either old similarity is NA (two clusters merge only if every sample pair across them has a
+    ``raw``), else the smaller of the two (complete), the larger (single), or ``(n_a w_a + n_b w_b) / (n_a + n_b)`` in
+    plain doubles (average).  Merging ends at the first step whose best similarity is NA or below ``min_raw``; what is
+    left is a forest, its components numbered by their smallest sample.
+
+    The other arguments are ``ici_kendalltau``'s (column names are required; a sparse matrix, float32 and integer
+    matrices are read where they lie).  On the HIP engine the steps run on the device (icikt_hclust_f64), which keeps
+    12 bytes per cell of an S x S table; a matrix has at most 65 535 samples.
+
+    Returns a dict: ``merge_a``, ``merge_b`` (the slots a < b of each merge, in merge order), ``size`` (the samples of
+    the new cluster), ``raw`` (the similarity of the merge), ``cor`` (``raw / max_taumax`` over all pairs with
+    ``scale_max``), ``n_merges``, ``component`` (S), ``n_components`` (``n_merges + n_components == S``), ``method``,
+    ``sample_id``, ``max_taumax`` and ``run_time``.  ``formats.hclust_to_linkage`` turns it into a
+    ``scipy.cluster.hierarchy`` linkage matrix, ``formats.hclust_cut`` into the clusters at any similarity.  The
+    reference's warning is raised once per pair whose ``raw`` is NA for reasons 2-4, as ``ici_kendalltau_edges`` raises
+    it.
+    """
+    if method not in HCLUST_METHODS:
+        raise ValueError("`method` must be complete, average or single")
+    min_raw = _edge_bound(min_raw, "min_raw")
+    data_matrix, names = _as_matrix(data_matrix, colnames, "data_matrix", keep_dtype=True, keep_sparse=True)
+    n_sample = data_matrix.shape[1]
+    if n_sample < 2:
+        raise ValueError("No comparisons to do. Check the list of column names in "
+                         "`include_only` vs those in the samples.")  # R/kendalltau.R:240-247
+    eng = engine or _default_engine()
+    if hasattr(eng, "hclust"):
+        X, global_na = _mask_on_host(data_matrix, global_na)
+        t1 = time.perf_counter()
+        ma, mb, msize, mraw, mcor, component, n_comp, max_taumax, rcounts = eng.hclust(
+            _for_engine(X, eng, fortran=False), method, min_raw, global_na, perspective, alternative, continuity, 0,
+            scale_max)
+        t_diff = time.perf_counter() - t1
+        _warn_pairs(rcounts)
+    else:
+        full = ici_kendalltau(data_matrix, global_na=global_na, perspective=perspective, scale_max=scale_max,
+                              diag_good=True, alternative=alternative, continuity=continuity, colnames=names, engine=eng)
+        t_diff = full["run_time"]
+        ma, mb, msize, mraw, component, n_comp = _hclust_numpy([np.asarray(full[key]) for key in _TOPK_KEYS], method,
+                                                               min_raw)
+        max_taumax = _max_taumax(full["taumax"], np.triu_indices(n_sample, k=1))
+        mcor = mraw / max_taumax if scale_max else mraw.copy()
+    return {"merge_a": ma, "merge_b": mb, "size": msize, "raw": mraw, "cor": mcor, "n_merges": int(ma.shape[0]),
+            "component": component, "n_components": int(n_comp), "method": method,
+            "sample_id": np.asarray(list(names), dtype=object), "max_taumax": max_taumax, "run_time": t_diff}
 
 
 # --------------------------------------------------------------------------------------------------

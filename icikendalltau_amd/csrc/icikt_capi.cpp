@@ -1734,7 +1734,7 @@ extern "C" {
 // qbatch (icikt_quantiles_*: targets per batch of the select, 1 .. 32),
 // padjtile (icikt_padjust_*, icikt_anosim_*: keys of a wave's tile of the sort, 1 .. 2^30),
 // anoperms (icikt_anosim_*: labellings per upload, 1 .. 2^20), anostrip (icikt_anosim_*: columns of a workgroup of the
-// permutation kernel, 1 .. 4096),
+// permutation kernel, 1 .. 4096), hcgrid (icikt_hclust_*: workgroups of the rescan kernel, 1 .. 256),
 // verbose (0 | 1: print the plan to stderr).
 // (The keys h2d and regfail of rounds 2-3 are gone with the mode they steered: the library no longer page-locks
 // caller memory, icikt_host.h.)
@@ -1795,6 +1795,11 @@ int icikt_debug_set_plan(icikt_ctx* c, const char* spec) {
       ov.anostrip = atoi(val.c_str());
       if (ov.anostrip < icikt::ANO_STRIP_MIN || ov.anostrip > icikt::ANO_STRIP_MAX)
         return fail(c, ICIKT_E_INVALID, "debug_set_plan: anostrip must be in 1 .. 4096 columns");
+    }
+    else if (key == "hcgrid") {
+      ov.hcgrid = atoi(val.c_str());
+      if (ov.hcgrid < 1 || ov.hcgrid > icikt::HCLUST_GRID_MAX)
+        return fail(c, ICIKT_E_INVALID, "debug_set_plan: hcgrid must be in 1 .. 256 workgroups");
     }
     else return fail(c, ICIKT_E_INVALID, "debug_set_plan: unknown key '" + key + "'");
   }

@@ -1,5 +1,5 @@
 // icikt_device.h -- structures, layouts and launcher declarations shared by the device units (icikt_prepass.hip,
-// icikt_kernels.hip, icikt_epilogue.hip, icikt_cor.hip, icikt_diag.hip, icikt_topk.hip, icikt_edges.hip, icikt_medians.hip, icikt_quantiles.hip, icikt_classmat.hip, icikt_padjust.hip, icikt_mst.hip, icikt_anosim.hip) and the C-ABI
+// icikt_kernels.hip, icikt_epilogue.hip, icikt_cor.hip, icikt_diag.hip, icikt_topk.hip, icikt_edges.hip, icikt_medians.hip, icikt_quantiles.hip, icikt_classmat.hip, icikt_padjust.hip, icikt_mst.hip, icikt_hclust.hip, icikt_anosim.hip) and the C-ABI
 // host side (icikt_capi*.cpp, icikt_multi.cpp).  Internal; the public boundary is include/icikt.h.
 #ifndef ICIKT_DEVICE_H
 #define ICIKT_DEVICE_H
@@ -291,6 +291,35 @@ struct MstBest {
 // not below min_key, equal keys by the smaller t
 hipError_t launch_mst_best(const unsigned long long* kept, const int32_t* comp, const int32_t* live,
                            unsigned long long min_key, int S, MstBest* best, hipStream_t s);
+// ---- complete, average and single linkage (icikt_hclust.hip) ----
+constexpr int HCLUST_COMPLETE = 0, HCLUST_AVERAGE = 1, HCLUST_SINGLE = 2;   // == ICIKT_HCLUST_*
+constexpr int HCLUST_GRID_MAX = 256;   // workgroups of the rescan kernel (hcgrid)
+// the call's device state, HC_WORDS int32 words zeroed before the first scan: the call has ended; the merges recorded;
+// the entries of the rescan list; the step's slots a < b and their sizes before the merge
+constexpr int HC_DONE = 0, HC_MERGES = 1, HC_COUNT = 2, HC_A = 3, HC_B = 4, HC_NA = 5, HC_NB = 6, HC_WORDS = 8;
+// merge record t: slot b merged into slot a < b at the similarity `key` (colsort::cor_key), the new cluster's samples
+struct HcMerge {
+  int32_t a, b;
+  unsigned long long key;
+  int32_t size, pad;
+};
+static_assert(sizeof(HcMerge) == 24, "a merge record is 24 bytes");
+// kept: the whole combn(S, 2) plane launch_median_keep writes.  W [S][S]: the symmetric table of keys, NA_KEY on the
+// diagonal; alive [S] = 1, size [S] = 1
+hipError_t launch_hc_expand(const unsigned long long* kept, int S, unsigned long long* W, int32_t* alive, int32_t* size,
+                            hipStream_t s);
+// nn / nnkey of the rows list[0 .. state[HC_COUNT]) (all != 0: of every row, list unread): the row's best live partner --
+// the largest key that is not NA_KEY, equal keys by the smaller partner -- or -1 and key 0.  grid: 1 .. HCLUST_GRID_MAX
+hipError_t launch_hc_rescan(const unsigned long long* W, const int32_t* alive, const int32_t* list, const int32_t* state,
+                            int S, int all, int grid, int32_t* nn, unsigned long long* nnkey, hipStream_t s);
+// the step's merge: the best (nnkey[i], min(i, nn[i]), max(i, nn[i])) over live i, recorded as rec[state[HC_MERGES]];
+// state[HC_DONE] = 1 when no key is left or the best is below min_key (colsort::cor_key of min_raw, 0: no bound)
+hipError_t launch_hc_pick(const int32_t* nn, const unsigned long long* nnkey, int32_t* alive, int32_t* size,
+                          int32_t* state, HcMerge* rec, unsigned long long min_key, int S, hipStream_t s);
+// row and column a of W after the merge pick published (method: HCLUST_*), the neighbours that follow from it, and the
+// rows whose neighbour was a or b -- and a -- on the list
+hipError_t launch_hc_merge(unsigned long long* W, int32_t* nn, unsigned long long* nnkey, const int32_t* alive,
+                           int32_t* list, int32_t* state, int method, int S, hipStream_t s);
 // ---- ANOSIM: class separation under 1 - raw with its permutation test (icikt_anosim.hip) ----
 constexpr int ANO_PB = 16;                // labellings a workgroup of the permutation kernel takes side by side
 constexpr int ANO_ROW_RUN = 256;          // rows of a workgroup's run

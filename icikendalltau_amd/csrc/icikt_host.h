@@ -177,6 +177,15 @@ struct icikt_ctx {
     DevBuf<icikt::MstBest> best;
   } mst;
 
+  // complete, average and single linkage (icikt_hclust_f64): the kept plane (a key per pair of the triangle), the
+  // symmetric S x S table of keys, every slot's cached neighbour with its key, the live flags and cluster sizes, the
+  // rescan list, the call's state words (icikt_device.h: HC_*) and the merge records
+  struct HclustBufs {
+    DevBuf<unsigned long long> kept, table, nnkey;
+    DevBuf<int32_t> nn, alive, size, list, state;
+    DevBuf<icikt::HcMerge> rec;
+  } hc;
+
   // ANOSIM (icikt_anosim_f64): the kept plane (a key per pair of the triangle), the two planes of the sort -- the one
   // the sort leaves free takes the doubled ranks --, the sort's counters and the scans' aggregates, the valid count and
   // the digit table, the observed labelling and its per-class sums, a batch of labellings and their sums
@@ -210,6 +219,7 @@ struct icikt_ctx {
     long long padjtile = -1;  // icikt_padjust_*, icikt_anosim_*: keys of a wave's tile of the sort (default: padj_tile's choice)
     long long anoperms = -1;  // icikt_anosim_*: labellings per upload (default: ANO_BATCH_BYTES of labels)
     int anostrip = -1;        // icikt_anosim_*: columns of a workgroup of the permutation kernel (default: ANO_STRIP_DEFAULT)
+    int hcgrid = -1;          // icikt_hclust_*: workgroups of the rescan kernel (default: min(S, HCLUST_GRID_MAX))
     bool verbose = false;
   } plan_ov;
 
@@ -285,7 +295,7 @@ int check_pair_args(icikt_ctx* c, const char* who, const MatrixSrc& X, int64_t n
                     const int32_t* pi, const int32_t* pj, int64_t* n_pairs, const void* out, bool out5,
                     int perspective, int alternative);
 
-// ---- the selection entries (icikt_topk_*, icikt_edges_*, icikt_class_medians_*, icikt_quantiles_*, icikt_class_matrix_*, icikt_padjust_*, icikt_mst_*, icikt_anosim_*): one driver, icikt_capi_select.cpp ----
+// ---- the selection entries (icikt_topk_*, icikt_edges_*, icikt_class_medians_*, icikt_quantiles_*, icikt_class_matrix_*, icikt_padjust_*, icikt_mst_*, icikt_anosim_*, icikt_hclust_*): one driver, icikt_capi_select.cpp ----
 // (the blocks a call runs in: icikt_blocks.h; DESIGN.md "adding a selection entry")
 // the arguments the entries share
 struct SelectArgs {

@@ -10,6 +10,8 @@
 * ``edges_to_coo``: the result of ``ici_kendalltau_edges`` as a sparse samples x samples matrix (needs scipy).
 * ``mst_to_linkage`` / ``mst_cut``: the result of ``ici_kendalltau_mst`` as a ``scipy.cluster.hierarchy`` linkage matrix
   (single linkage), and as the network's component labels at any cut-off (neither needs scipy).
+* ``hclust_to_linkage`` / ``hclust_cut``: the result of ``ici_kendalltau_hclust`` (complete, average or single linkage)
+  as a ``scipy.cluster.hierarchy`` linkage matrix, and as the clusters at any similarity (neither needs scipy).
 """
 from __future__ import annotations
 
@@ -356,4 +358,71 @@ def mst_cut(result, min_raw):
             label[r] = n
             n += 1
         component[s] = label[r]
+    return component
+
+
+# --------------------------------------------------------------------------------------------------
+# ici_kendalltau_hclust -> a dendrogram, and the clusters at any similarity
+# --------------------------------------------------------------------------------------------------
+def hclust_to_linkage(result, by="raw"):
+    """The dict ``ici_kendalltau_hclust`` returns as a ``scipy.cluster.hierarchy`` linkage matrix under the distance
+    ``1 - result[by]`` (``by``: "raw" or "cor"): (S - 1) x 4 float64, row k = (the two clusters merged at step k, the
+    smaller id first; the height ``1 - value`` of the merge; the new cluster's size), the samples being clusters
+    0 .. S - 1 and step k making cluster S + k -- scipy's numbering, so ``dendrogram``, ``fcluster`` and
+    ``leaves_list`` take it as it is.  One pass over the merges, O(S); scipy itself is not needed.  Complete and single
+    linkage only take minima and maxima, so their heights never decrease.  Average linkage on similarities is
+    monotone in exact arithmetic; each of its updates rounds, so a height can in principle come out below the one
+    before it by an ulp or so.  Nothing is clamped: the heights are the similarities the merges were made at.
+    A forest that is not ONE tree has no dendrogram: ``ValueError`` naming ``n_components`` (cut with ``hclust_cut``,
+    or cluster each component on its own)."""
+    if by not in ("raw", "cor"):
+        raise ValueError("`by` must be raw or cor")
+    S = len(result["component"])
+    n_comp = int(result["n_components"])
+    a = np.asarray(result["merge_a"], dtype=np.int64)
+    b = np.asarray(result["merge_b"], dtype=np.int64)
+    if n_comp != 1 or a.shape[0] != S - 1:
+        raise ValueError(f"the result is a forest, not one tree (n_components = {n_comp}): a linkage matrix needs every "
+                         "sample merged; lower `min_raw`, or cut with hclust_cut")
+    height = 1.0 - np.asarray(result[by], dtype=np.float64)
+    size = np.asarray(result["size"], dtype=np.int64)
+    cluster = list(range(S))     # per slot: the id of the cluster that lives in it
+    alive = [True] * S
+    Z = np.empty((S - 1, 4), dtype=np.float64)
+    for k in range(S - 1):
+        sa, sb = int(a[k]), int(b[k])
+        if not (0 <= sa < sb < S and alive[sa] and alive[sb]):
+            raise ValueError(f"merge {k} of the result names a slot that is no cluster: not a result of ici_kendalltau_hclust")
+        ca, cb = cluster[sa], cluster[sb]
+        alive[sb] = False
+        cluster[sa] = S + k
+        Z[k] = (min(ca, cb), max(ca, cb), height[k], size[k])
+    return Z
+
+
+def hclust_cut(result, min_raw):
+    """The clusters at the similarity ``min_raw`` from the merges alone: the merges are replayed up to the first one whose
+    ``raw`` is below ``min_raw`` (NA compares as below), which is where ``ici_kendalltau_hclust(..., min_raw=min_raw)``
+    ends.  ``result``: the dict of ``ici_kendalltau_hclust`` called with no ``min_raw``, or with one not above this one.
+    Returns the labels (S, int32), numbered 0, 1, ... in order of each cluster's smallest sample: that call's
+    ``component`` without computing a pair."""
+    S = len(result["component"])
+    a = np.asarray(result["merge_a"], dtype=np.int64)
+    b = np.asarray(result["merge_b"], dtype=np.int64)
+    with np.errstate(invalid="ignore"):
+        keep = np.asarray(result["raw"], dtype=np.float64) >= float(min_raw)
+    n = int(np.argmin(keep)) if not np.all(keep) else int(keep.shape[0])
+    slot = np.arange(S)          # the slot a sample's cluster lives in: a slot merges into a smaller one, so one ascending pass resolves them
+    for sa, sb in zip(a[:n].tolist(), b[:n].tolist()):
+        slot[sb] = sa
+    label = np.full(S, -1, dtype=np.int32)
+    component = np.empty(S, dtype=np.int32)
+    k = 0
+    for s in range(S):
+        if slot[s] == s:
+            label[s] = k
+            k += 1
+        else:
+            slot[s] = slot[slot[s]]
+        component[s] = label[slot[s]]
     return component

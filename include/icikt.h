@@ -521,7 +521,7 @@ int icikt_padjust_f64(icikt_ctx *ctx, const double *X, int64_t n_feat, int64_t n
  * pair's raw as a sortable 64-bit key, and after the last block Boruvka rounds run over the kept keys: a kernel finds
  * every sample's best edge out of its component, the host (O(n_samp) per round) picks each component's best, merges
  * and uploads the new components.  Only comparisons enter, no addition of doubles: the result is defined to the bit.
- * (Complete and average linkage need n_samp - 1 dependent updates of an n_samp x n_samp table; they are not offered.)
+ * (Complete and average linkage need n_samp - 1 dependent updates of an n_samp x n_samp table: icikt_hclust_f64, below.)
  *   candidate    a pair i < j is a candidate edge iff its raw is not NA (reason code 0) and, when min_raw is not NaN,
  *                raw >= min_raw -- a plain IEEE comparison, as icikt_edge_rule's
  *   order        the STRICT EDGE ORDER: the larger raw first, -0 equal to +0; equal raw by the smaller combn index (i
@@ -552,6 +552,54 @@ int icikt_mst_f64(icikt_ctx *ctx, const double *X, int64_t n_feat, int64_t n_sam
                   int n_global_na, int perspective, int alternative, int continuity, uint32_t flags, int scale_max,
                   double min_raw, int32_t *ti, int32_t *tj, double *out5t, int64_t *n_tree, int32_t *component,
                   int64_t *n_components, int32_t *n_rounds, double *max_taumax, int64_t *reason_counts);
+
+/* ---- complete, average and single linkage of the samples, on the device ---------------------------------------------
+ *
+ * The sample dendrogram and heatmap ordering by the methods R's hclust ("complete") and scipy ("average") default to,
+ * without anything of size n_samp^2 on the host or as five planes on the device.  The whole combn triangle runs through
+ * the pair engine in blocks of whole rows (the tkblock budget, as icikt_topk_f64); a kernel keeps each pair's raw as a
+ * sortable 64-bit key; after the last block a kernel expands the keys into a symmetric n_samp x n_samp table, and
+ * n_samp - 1 steps of three short launches each (pick the best pair, update the merged row and column, rescan the rows
+ * whose cached neighbour went away) are queued without a host wait.  Only the merge records come back.
+ *   similarity   of two samples: the pair's raw, -0 equal to +0; a pair with a reason code or an NA raw has none (NA)
+ *   clusters     a cluster lives in the slot of its smallest sample; slots a < b merge into a
+ *   NA           the merged cluster's similarity to a cluster k is NA if either old one is: two clusters are mergeable
+ *                exactly when every sample pair across them has a raw
+ *   method       ICIKT_HCLUST_COMPLETE: the smaller of the two old similarities; ICIKT_HCLUST_SINGLE: the larger;
+ *                ICIKT_HCLUST_AVERAGE: (n_a w_a + n_b w_b) / (n_a + n_b) in IEEE doubles, each of the two products, the
+ *                two sums and the division rounded once, no fused operation
+ *   order        each step merges the best live pair in the STRICT ORDER: the larger similarity first, then the smaller
+ *                a, then the smaller b.  The order is total: the result is a pure function of the input, whatever the
+ *                block cut or the launch geometry.
+ *   end          at the first step whose best similarity is NA or, when min_raw is not NaN, below min_raw (a plain IEEE
+ *                comparison).  What is left is a forest.
+ *   ma, mb       [n_samp - 1] the slots a < b of each merge, in merge order; *n_merges of them are written, the slots
+ *                behind them are left untouched (as in msize, mraw, mcor)
+ *   msize        [n_samp - 1] the samples of the new cluster
+ *   mraw, mcor   [n_samp - 1] the similarity of the merge (-0 as +0) and mcor = scale_max ? mraw / max(taumax, na.rm =
+ *                TRUE) over ALL C(n_samp, 2) pairs : mraw
+ *   component    [n_samp] the sample's cluster when merging ended, the clusters numbered 0, 1, .. in order of their
+ *                smallest sample.  *n_merges + *n_components == n_samp always.
+ * ma, mb, msize, mraw and mcor are required for n_samp > 1, component for n_samp > 0, n_merges and n_components always;
+ * max_taumax and reason_counts (as icikt_topk_f64, over all pairs) are optional.  Any other method is ICIKT_E_INVALID
+ * (the message names `method`); n_samp <= ICIKT_TOPK_MAX_SAMPLES; n_feat, global_na, the state the call leaves behind
+ * and the refusal of bad arguments before anything -- the context or an output -- is touched: as icikt_topk_f64.
+ * Records that do not add up (n_merges + n_components != n_samp, a >= b, a slot that is no cluster any more, a merge
+ * without a similarity or below min_raw, complete or single merges whose similarities increase) are ICIKT_E_STATE with a
+ * message -- never a loop.
+ * Device memory: the prepared matrix, one block's buffers, 8 bytes per pair of the triangle for the kept keys and 8
+ * n_samp^2 bytes for the table (12 n_samp^2 together; n_samp = 65 535: 52 GB) and 40 n_samp bytes of neighbours, flags,
+ * sizes, list and records; a failed allocation is ICIKT_E_HIP.  With ICIKT_FLAG_TIMING the keep kernel, the table, the
+ * first scan and the steps are accounted under ICIKT_K_EPILOGUE.
+ * icikt_hclust_in / icikt_hclust_csc: the same on a typed view / a CSC view of the matrix (below). */
+#define ICIKT_HCLUST_COMPLETE 0
+#define ICIKT_HCLUST_AVERAGE 1
+#define ICIKT_HCLUST_SINGLE 2
+int icikt_hclust_f64(icikt_ctx *ctx, const double *X, int64_t n_feat, int64_t n_samp, int64_t ld,
+                     const double *global_na, int n_global_na, int perspective, int alternative, int continuity,
+                     uint32_t flags, int scale_max, int method, double min_raw, int32_t *ma, int32_t *mb,
+                     int32_t *msize, double *mraw, double *mcor, int64_t *n_merges, int32_t *component,
+                     int64_t *n_components, double *max_taumax, int64_t *reason_counts);
 
 /* ---- ANOSIM: do the classes separate under ICI-Kt, with a permutation test, on the device --------------------------
  *
@@ -776,6 +824,11 @@ int icikt_mst_in(icikt_ctx *ctx, const icikt_input *X, int64_t n_feat, int64_t n
                  int n_global_na, int perspective, int alternative, int continuity, uint32_t flags, int scale_max,
                  double min_raw, int32_t *ti, int32_t *tj, double *out5t, int64_t *n_tree, int32_t *component,
                  int64_t *n_components, int32_t *n_rounds, double *max_taumax, int64_t *reason_counts);
+int icikt_hclust_in(icikt_ctx *ctx, const icikt_input *X, int64_t n_feat, int64_t n_samp, const double *global_na,
+                    int n_global_na, int perspective, int alternative, int continuity, uint32_t flags, int scale_max,
+                    int method, double min_raw, int32_t *ma, int32_t *mb, int32_t *msize, double *mraw, double *mcor,
+                    int64_t *n_merges, int32_t *component, int64_t *n_components, double *max_taumax,
+                    int64_t *reason_counts);
 int icikt_anosim_in(icikt_ctx *ctx, const icikt_input *X, int64_t n_feat, int64_t n_samp, const double *global_na,
                     int n_global_na, int perspective, int alternative, int continuity, uint32_t flags,
                     const int32_t *cls, int n_class, const int32_t *perm_cls, int64_t n_perm, int64_t *n_pairs,
@@ -854,6 +907,11 @@ int icikt_mst_csc(icikt_ctx *ctx, const icikt_csc_input *X, int64_t n_feat, int6
                   int n_global_na, int perspective, int alternative, int continuity, uint32_t flags, int scale_max,
                   double min_raw, int32_t *ti, int32_t *tj, double *out5t, int64_t *n_tree, int32_t *component,
                   int64_t *n_components, int32_t *n_rounds, double *max_taumax, int64_t *reason_counts);
+int icikt_hclust_csc(icikt_ctx *ctx, const icikt_csc_input *X, int64_t n_feat, int64_t n_samp, const double *global_na,
+                     int n_global_na, int perspective, int alternative, int continuity, uint32_t flags, int scale_max,
+                     int method, double min_raw, int32_t *ma, int32_t *mb, int32_t *msize, double *mraw, double *mcor,
+                     int64_t *n_merges, int32_t *component, int64_t *n_components, double *max_taumax,
+                     int64_t *reason_counts);
 int icikt_anosim_csc(icikt_ctx *ctx, const icikt_csc_input *X, int64_t n_feat, int64_t n_samp, const double *global_na,
                      int n_global_na, int perspective, int alternative, int continuity, uint32_t flags,
                      const int32_t *cls, int n_class, const int32_t *perm_cls, int64_t n_perm, int64_t *n_pairs,
@@ -898,7 +956,8 @@ int icikt_selftest(icikt_ctx *ctx);
  * select runs per batch of eight passes, 1 .. 32), padjtile (icikt_padjust_*: the keys of a tile of the sort, the run one
  * wave counts and scatters in order, 1 .. 2^30; raised when the plane would have more than 65 536 tiles; icikt_anosim_* sorts with
  * the same tile), anoperms (icikt_anosim_*: the labellings per upload, 1 .. 2^20; the permutation kernel takes them 16 at a
- * time), anostrip (icikt_anosim_*: the columns of the triangle a workgroup of the permutation kernel owns, 1 .. 4096), verbose (0 | 1: print the chosen
+ * time), anostrip (icikt_anosim_*: the columns of the triangle a workgroup of the permutation kernel owns, 1 .. 4096), hcgrid (icikt_hclust_*: the workgroups of the
+ * kernel that rescans the listed rows of a step, 1 .. 256; default min(n_samp, 256)), verbose (0 | 1: print the chosen
  * plan to stderr). */
 int icikt_debug_set_plan(icikt_ctx *ctx, const char *spec);
 /* Development hook: per step kind of the pair kernel (hot loop, hot step in the main loop, MIXED, GROUP, general,
