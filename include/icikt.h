@@ -173,6 +173,29 @@ int icikt_sync(icikt_ctx *ctx);
 
 /* ---- device-resident path (what bench.py and the multi-GPU driver call) -------------------- */
 
+/* Stream contract.  The context's stream is its own (non-blocking) one, or the caller's after icikt_ctx_set_stream.
+ * A device-resident call is work on that stream at the place of the call: it reads its device arguments and the
+ * context's state no earlier, has written its device results no later, and never touches them from another stream.
+ * Work the caller enqueues on the same stream before or behind the call needs no other ordering (tests/
+ * test_gpu_caller_stream.py holds every call below to that).  Which calls return before the stream has reached them:
+ *   return at once     icikt_prepare_dev, icikt_prepare_cols_dev, icikt_expand_cols_dev, icikt_convert_dev,
+ *                      icikt_set_pairs_combn, and icikt_run_dev for a pair list it has run before -- whatever the
+ *                      flags, with the one exception below
+ *   synchronise        icikt_run_dev, the first run behind each pre-pass, for columns of 14 273 to 65 535 rows: the
+ *                      column statistics that size the pair kernel are read back once per prepared matrix (not with
+ *                      ICIKT_FLAG_REUSE_COUNTS on valid counts, not for shorter or wide columns);
+ *                      icikt_run_dev, the first run after icikt_set_pairs / icikt_set_pairs_combn (columns up to
+ *                      65 535 rows): the task list is built on the host and uploaded;
+ *                      icikt_set_pairs (the upload of the list); icikt_scatter_csc_dev (it reports malformed input);
+ *                      icikt_kernel_ms, icikt_reset_timers, and a timed call that finds 256 timed launches of its
+ *                      kernel unread; icikt_sync
+ *   may synchronise    any call that has to grow a workspace: the first of its shape on the context (hipMalloc).
+ * icikt_ctx_set_stream and icikt_ctx_use_own_stream wait for the stream the context leaves, so what was enqueued there
+ * is complete before the first call on the new stream; icikt_ctx_destroy waits for the stream the context is on before
+ * it frees anything, and never destroys a caller's stream.  The host entries (icikt_*_f64 / _in / _csc) take host
+ * arrays: their transfers and kernels start behind what the context's stream already holds, and they return when their
+ * results are in the caller's arrays. */
+
 /* Per-column pre-pass over a DEVICE matrix: NA bitsets, fill value min-0.1 (src/kendallc.cpp:214-219),
  * stable argsort + dense tie groups (sortedIndex/compare_self, :5-31), tie sums (count_rank_tie).
  * Asynchronous on the context's stream.  dX must stay valid until the stream reaches this point. */

@@ -591,6 +591,7 @@ def test_expand_cols_rebuilds_rec_hirow_tgroups(hip_ctx):
         # tgroups beyond a column's ntg entries and the pad rows of rec / hirow are unspecified: compare what K1 reads
         for t in derived.values():
             t.fill_(0xEE)
+        torch.cuda.synchronize()                   # (the fill runs on torch's stream, the rebuild on the context's)
         hip_ctx.expand_cols_dev(0, S)
         hip_ctx.sync()
         meta = view(3, S).cpu().numpy().view(np.uint32).reshape(S, -1)   # per column: 3 bitsets, then 16 words of stats

@@ -182,6 +182,7 @@ def test_exchanged_state_is_unchanged(hip_ctx):
     want = {i: t.clone() for i, t in derived.items()}
     for t in derived.values():
         t.fill_(0xEE)
+    torch.cuda.synchronize()                       # (the fill runs on torch's stream, the rebuild on the context's)
     hip_ctx.expand_cols_dev(0, S)
     hip_ctx.sync()
     ntg = view(3, S).cpu().numpy().view(np.uint32).reshape(S, -1)[:, -16 + 7]
