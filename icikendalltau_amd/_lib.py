@@ -29,7 +29,8 @@ SOURCES = [os.path.join(_PKG, "csrc", f) for f in ("icikt_kernels.hip", "icikt_p
 HEADERS = [os.path.join(_ROOT, "include", "icikt.h"), os.path.join(_PKG, "csrc", "icikt_device.h"),
            os.path.join(_PKG, "csrc", "icikt_wave.h"), os.path.join(_PKG, "csrc", "icikt_host.h"),
            os.path.join(_PKG, "csrc", "icikt_transfer.h"), os.path.join(_PKG, "csrc", "icikt_colsort.h"),
-           os.path.join(_PKG, "csrc", "icikt_blocks.h"), os.path.join(_PKG, "csrc", "icikt_select.h")]
+           os.path.join(_PKG, "csrc", "icikt_blocks.h"), os.path.join(_PKG, "csrc", "icikt_select.h"),
+           os.path.join(_PKG, "csrc", "icikt_keys.h")]
 
 # include/icikt.h
 SUCCESS = 0
@@ -469,13 +470,24 @@ def _matrix_call(fn, handle, chk, X, global_na, pi, pj, perspective, alternative
 
 
 def _select_args(global_na, perspective, alternative):
-    """What the selection entries (topk, edges, class_medians, quantiles, class_matrix, padjust) share: the arguments (global_na, n_global_na) -- valid
-    while the first element, the array behind them, is alive --, (perspective, alternative) as codes, the max_taumax
-    cell and reason_counts [5]."""
+    """What the nine selection entries (topk, edges, class_medians, class_matrix, quantiles, padjust, mst, anosim,
+    hclust) share: the arguments (global_na, n_global_na) -- valid while the first element, the array behind them, is
+    alive --, (perspective, alternative) as codes, the max_taumax cell and reason_counts [5]."""
     gna = np.ascontiguousarray([] if global_na is None else np.atleast_1d(global_na), dtype=np.float64)
     persp = PERSPECTIVE.get(perspective, perspective if isinstance(perspective, int) else -1)
     return ((gna, _ptr(gna) if gna.size else None, int(gna.size)), (persp, ALTERNATIVE.get(alternative, ALT_OTHER)),
             np.full(1, -np.inf), np.zeros(5, dtype=np.int64))
+
+
+def _class_arg(cls, n_samp):
+    """cls of class_medians, class_matrix, quantiles and anosim as the library takes it: None (one class), or a
+    contiguous int32 class index per column."""
+    if cls is None:
+        return None
+    cls_a = np.ascontiguousarray(cls, dtype=np.int32)
+    if cls_a.shape != (n_samp,):
+        raise ValueError("cls must give one class per column")
+    return cls_a
 
 
 class Context:
@@ -691,12 +703,7 @@ class Context:
         max_taumax: the largest taumax of the COMPUTED pairs, cor's denominator; reason_counts [5] over those pairs).
         The argument checks are the library's: a class index out of range or a bad perspective raises IciktError."""
         fn, fname, xargs, n_feat, n_samp, flags, _keep = self._entry("class_medians", X, flags)
-        if cls is None:
-            cls_a = None
-        else:
-            cls_a = np.ascontiguousarray(cls, dtype=np.int32)
-            if cls_a.shape != (n_samp,):
-                raise ValueError("cls must give one class per column")
+        cls_a = _class_arg(cls, n_samp)
         gna, codes, mx, rc5 = _select_args(global_na, perspective, alternative)
         med2 = np.empty((2, n_samp), dtype=np.float64)
         n_valid = np.zeros(n_samp, dtype=np.int32)
@@ -714,13 +721,9 @@ class Context:
         pairs).  The arrays are views of the library's layout, the sample index fastest.  The argument checks are the
         library's: a class index out of range, more than 65 535 classes or a bad perspective raises IciktError."""
         fn, fname, xargs, n_feat, n_samp, flags, _keep = self._entry("class_matrix", X, flags)
-        if cls is None:
-            cls_a = None
+        cls_a = _class_arg(cls, n_samp)
+        if cls_a is None:
             n_class = 1
-        else:
-            cls_a = np.ascontiguousarray(cls, dtype=np.int32)
-            if cls_a.shape != (n_samp,):
-                raise ValueError("cls must give one class per column")
         n_class = int(n_class)
         room = n_class if 1 <= n_class <= 65535 else 1    # (the library refuses the others before it writes)
         gna, codes, mx, rc5 = _select_args(global_na, perspective, alternative)
@@ -742,12 +745,7 @@ class Context:
         values below the first and above the last break; max_taumax; reason_counts [5]).  The argument checks are the
         library's: a bad prob, break, class index or perspective raises IciktError."""
         fn, fname, xargs, n_feat, n_samp, flags, _keep = self._entry("quantiles", X, flags)
-        if cls is None:
-            cls_a = None
-        else:
-            cls_a = np.ascontiguousarray(cls, dtype=np.int32)
-            if cls_a.shape != (n_samp,):
-                raise ValueError("cls must give one class per column")
+        cls_a = _class_arg(cls, n_samp)
         probs_a = np.ascontiguousarray(np.atleast_1d(np.asarray(probs, dtype=np.float64)).ravel())
         breaks_a = np.empty(0) if breaks is None else np.ascontiguousarray(np.atleast_1d(breaks), dtype=np.float64).ravel()
         n_probs, n_breaks = int(probs_a.size), int(breaks_a.size)
@@ -870,13 +868,9 @@ class Context:
         (M, w2, nw) into the statistic.  The argument checks are the library's: a label out of range, more than 65 535 classes or a
         bad perspective raises IciktError."""
         fn, fname, xargs, n_feat, n_samp, flags, _keep = self._entry("anosim", X, flags)
-        if cls is None:
-            cls_a = None
+        cls_a = _class_arg(cls, n_samp)
+        if cls_a is None:
             n_class = 1
-        else:
-            cls_a = np.ascontiguousarray(cls, dtype=np.int32)
-            if cls_a.shape != (n_samp,):
-                raise ValueError("cls must give one class per column")
         n_class = int(n_class)
         if perm_cls is None:
             perm_a, n_perm = None, 0

@@ -62,62 +62,62 @@ class HipEngine:
     def topk(self, data_matrix, k, global_na=None, perspective="global", alternative="two.sided", continuity=False,
              flags=0, scale_max=True):
         """Every sample's k best partners, selected on the device (icikt_topk_f64): Context.topk's contract."""
-        return self.ctx.topk(data_matrix, k, global_na, perspective, alternative, continuity, self.flags | flags,
-                             scale_max)
+        return self._select_ctx().topk(data_matrix, k, global_na, perspective, alternative, continuity,
+                                       self.flags | flags, scale_max)
 
     def edges(self, data_matrix, min_raw=None, max_pvalue=None, min_completeness=None, absolute=False, max_edges=0,
               global_na=None, perspective="global", alternative="two.sided", continuity=False, flags=0, scale_max=True):
         """Every pair past the bounds, compacted on the device (icikt_edges_f64): Context.edges' contract."""
-        return self.ctx.edges(data_matrix, min_raw, max_pvalue, min_completeness, absolute, max_edges, global_na,
-                              perspective, alternative, continuity, self.flags | flags, scale_max)
+        return self._select_ctx().edges(data_matrix, min_raw, max_pvalue, min_completeness, absolute, max_edges,
+                                        global_na, perspective, alternative, continuity, self.flags | flags, scale_max)
 
     def class_medians(self, data_matrix, cls=None, n_class=1, global_na=None, perspective="global",
                       alternative="two.sided", continuity=False, flags=0, scale_max=True):
         """Every sample's median over its class, reduced on the device (icikt_class_medians_f64): Context.class_medians'
         contract."""
-        return self.ctx.class_medians(data_matrix, cls, n_class, global_na, perspective, alternative, continuity,
-                                      self.flags | flags, scale_max)
+        return self._select_ctx().class_medians(data_matrix, cls, n_class, global_na, perspective, alternative,
+                                                continuity, self.flags | flags, scale_max)
 
     def class_matrix(self, data_matrix, cls=None, n_class=1, global_na=None, perspective="global",
                      alternative="two.sided", continuity=False, flags=0, scale_max=True):
         """Every sample's median to every class, reduced on the device (icikt_class_matrix_f64): Context.class_matrix's
         contract."""
-        return self.ctx.class_matrix(data_matrix, cls, n_class, global_na, perspective, alternative, continuity,
-                                     self.flags | flags, scale_max)
+        return self._select_ctx().class_matrix(data_matrix, cls, n_class, global_na, perspective, alternative,
+                                               continuity, self.flags | flags, scale_max)
 
     def quantiles(self, data_matrix, probs=(), breaks=None, cls=None, n_class=1, global_na=None, perspective="global",
                   alternative="two.sided", continuity=False, flags=0, scale_max=True):
         """Exact quantiles and a histogram of raw over all pairs, reduced on the device (icikt_quantiles_f64):
         Context.quantiles' arguments and result."""
-        return self.ctx.quantiles(data_matrix, probs, breaks, cls, n_class, global_na, perspective, alternative,
-                                  continuity, self.flags | flags, scale_max)
+        return self._select_ctx().quantiles(data_matrix, probs, breaks, cls, n_class, global_na, perspective,
+                                            alternative, continuity, self.flags | flags, scale_max)
 
     def padjust(self, data_matrix, method, alpha, max_table=0, global_na=None, perspective="global",
                 alternative="two.sided", continuity=False, flags=0):
         """R's p.adjust over the p-values of all pairs, on the device (icikt_padjust_f64): Context.padjust's arguments
         and result."""
-        return self.ctx.padjust(data_matrix, method, alpha, max_table, global_na, perspective, alternative, continuity,
-                                self.flags | flags)
+        return self._select_ctx().padjust(data_matrix, method, alpha, max_table, global_na, perspective, alternative,
+                                          continuity, self.flags | flags)
 
     def mst(self, data_matrix, min_raw=None, global_na=None, perspective="global", alternative="two.sided",
             continuity=False, flags=0, scale_max=True):
         """The maximum spanning forest under raw, found on the device (icikt_mst_f64): Context.mst's contract."""
-        return self.ctx.mst(data_matrix, min_raw, global_na, perspective, alternative, continuity, self.flags | flags,
-                            scale_max)
+        return self._select_ctx().mst(data_matrix, min_raw, global_na, perspective, alternative, continuity,
+                                      self.flags | flags, scale_max)
 
     def hclust(self, data_matrix, method="complete", min_raw=None, global_na=None, perspective="global",
                alternative="two.sided", continuity=False, flags=0, scale_max=True):
         """Complete, average or single linkage under raw, run on the device (icikt_hclust_f64): Context.hclust's
         contract."""
-        return self.ctx.hclust(data_matrix, method, min_raw, global_na, perspective, alternative, continuity,
-                               self.flags | flags, scale_max)
+        return self._select_ctx().hclust(data_matrix, method, min_raw, global_na, perspective, alternative, continuity,
+                                         self.flags | flags, scale_max)
 
     def anosim(self, data_matrix, cls=None, n_class=1, perm_cls=None, global_na=None, perspective="global",
                alternative="two.sided", continuity=False, flags=0):
         """ANOSIM's rank sums of the observed labelling and of every permutation, on the device (icikt_anosim_f64):
         Context.anosim's arguments and result."""
-        return self.ctx.anosim(data_matrix, cls, n_class, perm_cls, global_na, perspective, alternative, continuity,
-                               self.flags | flags)
+        return self._select_ctx().anosim(data_matrix, cls, n_class, perm_cls, global_na, perspective, alternative,
+                                         continuity, self.flags | flags)
 
     def cor_pairs(self, X, pi, pj, method, pairwise, alternative, continuity):
         """cor_fast's pairs on the device (icikt_cor_pairs_f64): (out3: rho, p-value, n_values; reasons)."""
@@ -138,6 +138,10 @@ class HipEngine:
         return self._diag_ctx().rank_order(X, global_na, cols)
 
     def _diag_ctx(self):
+        return self.ctx
+
+    def _select_ctx(self):
+        """The context the nine selection entries (topk ... anosim above) run on."""
         return self.ctx
 
     def pairs_complete(self, X, pi, pj):
@@ -199,54 +203,11 @@ class MultiHipEngine(HipEngine):
     def _diag_ctx(self):  # the missing-value diagnostics run on one device
         return self._one()
 
+    def _select_ctx(self):  # so do the selection entries: their folds, selects, sorts and rounds
+        return self._one()
+
     def cor_pairs(self, X, pi, pj, method, pairwise, alternative, continuity):  # cor_fast runs on one device
         return self._one().cor_pairs(X, pi, pj, method, pairwise, alternative, continuity)
-
-    def topk(self, data_matrix, k, global_na=None, perspective="global", alternative="two.sided", continuity=False,
-             flags=0, scale_max=True):  # the top-k selection runs on one device
-        return self._one().topk(data_matrix, k, global_na, perspective, alternative, continuity, self.flags | flags,
-                                scale_max)
-
-    def edges(self, data_matrix, min_raw=None, max_pvalue=None, min_completeness=None, absolute=False, max_edges=0,
-              global_na=None, perspective="global", alternative="two.sided", continuity=False, flags=0,
-              scale_max=True):  # the compaction runs on one device
-        return self._one().edges(data_matrix, min_raw, max_pvalue, min_completeness, absolute, max_edges, global_na,
-                                 perspective, alternative, continuity, self.flags | flags, scale_max)
-
-    def class_medians(self, data_matrix, cls=None, n_class=1, global_na=None, perspective="global",
-                      alternative="two.sided", continuity=False, flags=0, scale_max=True):  # the reduction runs on one device
-        return self._one().class_medians(data_matrix, cls, n_class, global_na, perspective, alternative, continuity,
-                                         self.flags | flags, scale_max)
-
-    def class_matrix(self, data_matrix, cls=None, n_class=1, global_na=None, perspective="global",
-                     alternative="two.sided", continuity=False, flags=0, scale_max=True):  # the reduction runs on one device
-        return self._one().class_matrix(data_matrix, cls, n_class, global_na, perspective, alternative, continuity,
-                                        self.flags | flags, scale_max)
-
-    def quantiles(self, data_matrix, probs=(), breaks=None, cls=None, n_class=1, global_na=None, perspective="global",
-                  alternative="two.sided", continuity=False, flags=0, scale_max=True):   # the select runs on one device
-        return self._one().quantiles(data_matrix, probs, breaks, cls, n_class, global_na, perspective, alternative,
-                                     continuity, self.flags | flags, scale_max)
-
-    def padjust(self, data_matrix, method, alpha, max_table=0, global_na=None, perspective="global",
-                alternative="two.sided", continuity=False, flags=0):   # the sort runs on one device
-        return self._one().padjust(data_matrix, method, alpha, max_table, global_na, perspective, alternative,
-                                   continuity, self.flags | flags)
-
-    def mst(self, data_matrix, min_raw=None, global_na=None, perspective="global", alternative="two.sided",
-            continuity=False, flags=0, scale_max=True):   # the rounds run on one device
-        return self._one().mst(data_matrix, min_raw, global_na, perspective, alternative, continuity,
-                               self.flags | flags, scale_max)
-
-    def hclust(self, data_matrix, method="complete", min_raw=None, global_na=None, perspective="global",
-               alternative="two.sided", continuity=False, flags=0, scale_max=True):   # the steps run on one device
-        return self._one().hclust(data_matrix, method, min_raw, global_na, perspective, alternative, continuity,
-                                  self.flags | flags, scale_max)
-
-    def anosim(self, data_matrix, cls=None, n_class=1, perm_cls=None, global_na=None, perspective="global",
-               alternative="two.sided", continuity=False, flags=0):   # the sort and the rank plane live on one device
-        return self._one().anosim(data_matrix, cls, n_class, perm_cls, global_na, perspective, alternative, continuity,
-                                  self.flags | flags)
 
     def pairs_complete(self, X, pi, pj):  # kt_fast's per-pair masking path exists on one device only
         out, _cnt, rsn = self._one().pairs_complete(X, pi, pj, "two.sided", False, self.flags)

@@ -1,6 +1,8 @@
-// icikt_blocks.h -- which pairs a selection entry (icikt_topk_*, icikt_edges_*, icikt_class_medians_*, icikt_quantiles_*) computes, and in
-// which blocks: whole rows of the combn triangle, or slices of the within-class pair list.  Plain C++, no device
-// header: tests/test_blocks_host.py compiles it alone.  Host memory is O(S) for the classes and O(block) for a slice.
+// icikt_blocks.h -- which pairs a selection entry (icikt_topk_*, icikt_edges_*, icikt_class_medians_*,
+// icikt_class_matrix_*, icikt_quantiles_*, icikt_padjust_*, icikt_mst_*, icikt_anosim_*, icikt_hclust_*) computes, and
+// in which blocks: whole rows of the combn triangle (all nine), or slices of the within-class pair list
+// (icikt_class_medians_* with several classes).  Plain C++, no device header: tests/test_blocks_host.py compiles it
+// alone.  Host memory is O(S) for the classes and O(block) for a slice.
 #ifndef ICIKT_BLOCKS_H
 #define ICIKT_BLOCKS_H
 

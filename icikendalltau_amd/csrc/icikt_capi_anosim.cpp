@@ -15,10 +15,12 @@
 // 128-bit integer with room to spare.  The comparison is exact; no margin is subtracted.
 //
 // Device memory: the prepared matrix, one block's buffers (icikt_blocks.h: kTriangleBlockPairs), and
-//   24 S (S - 1) / 2                               the kept keys in pair order, their sorted copy, and the sort's
-//                                                  spare plane, which takes the doubled ranks (S = 65 535: 51 GB)
-//   + 2 048 ceil(P / tile)                         the sort's (digit, tile) counters
-//   + 8 (max(P, 256 tiles) / 1 024 + 1)            a scan's chunk aggregates
+//   24 S (S - 1) / 2                               the kept keys in pair order, their sorted copy, and the plane the
+//                                                  sort ping-pongs it with, which takes the doubled ranks (S = 65 535:
+//                                                  51 GB): `kept`, `plane_a` and `plane_b` of the workspace
+//                                                  (icikt_ctx::sel, shared with the other entries)
+//   + 2 048 ceil(P / tile)                         the sort's (digit, tile) counters (the workspace's `counts`)
+//   + 8 (max(P, 256 tiles) / 1 024 + 1)            a scan's chunk aggregates (its `agg`)
 //   + 2 S ceil(batch / 16) 16 + 16 batch           a batch of labellings as halfwords, and its sums (by default at most
 //                                                  64 MB of labels per batch)
 //   + 4 S + 16 n_class + 16 KB                     the observed labelling, its per-class sums, the digit table
@@ -125,7 +127,6 @@ int anosim_src(icikt_ctx* c, const MatrixSrc& X, int64_t n_feat, int64_t n_samp,
 
   PairBlocks blocks = PairBlocks::rows(S, budget);
   const long long tile = icikt::padj_tile(P, c->plan_ov.padjtile > 0 ? c->plan_ov.padjtile : 0);
-  const long long n_tiles = (P + tile - 1) / tile;
   const int strip = c->plan_ov.anostrip > 0 ? c->plan_ov.anostrip : icikt::ANO_STRIP_DEFAULT;
   // labellings per upload: the plan key, else what ANO_BATCH_BYTES of halfwords hold, in whole groups of PB
   int64_t batch = c->plan_ov.anoperms > 0
@@ -136,13 +137,12 @@ int anosim_src(icikt_ctx* c, const MatrixSrc& X, int64_t n_feat, int64_t n_samp,
   const size_t lab_words = (size_t)groups_max * (size_t)S * PB;
 
   auto& ab = c->ano;
-  HIPCHK(c, ab.kept.reserve((size_t)std::max<int64_t>(P, 1)));
-  HIPCHK(c, ab.sort_a.reserve((size_t)std::max<int64_t>(P, 1)));
-  HIPCHK(c, ab.sort_b.reserve((size_t)std::max<int64_t>(P, 1)));
-  HIPCHK(c, ab.counts.reserve((size_t)std::max<long long>(256 * n_tiles, 1)));
-  HIPCHK(c, ab.agg.reserve((size_t)icikt::padj_scan_chunks(P, tile)));
-  HIPCHK(c, ab.total.reserve(1));
-  HIPCHK(c, ab.dhist.reserve(8 * 256));
+  auto& ws = c->sel;   // kept, plane_a, plane_b: the keys, their sorted copy, the ranks; the sort's scratch is select_sort's
+  HIPCHK(c, ws.kept.reserve((size_t)std::max<int64_t>(P, 1)));
+  HIPCHK(c, ws.plane_a.reserve((size_t)std::max<int64_t>(P, 1)));
+  HIPCHK(c, ws.plane_b.reserve((size_t)std::max<int64_t>(P, 1)));
+  HIPCHK(c, ws.total.reserve(1));
+  HIPCHK(c, ws.dhist.reserve(8 * 256));
   HIPCHK(c, ab.class_sums.reserve(2 * (size_t)C));
   HIPCHK(c, ab.cls.reserve((size_t)S));
   HIPCHK(c, ab.labels.reserve(lab_words));
@@ -168,27 +168,24 @@ int anosim_src(icikt_ctx* c, const MatrixSrc& X, int64_t n_feat, int64_t n_samp,
 
   icikt::host::SelectSteps steps;
   steps.start = [&]() -> int {
-    HIPCHK(c, hipMemsetAsync(ab.total.p, 0, sizeof(unsigned long long), c->stream));
-    HIPCHK(c, hipMemsetAsync(ab.dhist.p, 0, 8 * 256 * sizeof(unsigned long long), c->stream));
+    HIPCHK(c, hipMemsetAsync(ws.total.p, 0, sizeof(unsigned long long), c->stream));
+    HIPCHK(c, hipMemsetAsync(ws.dhist.p, 0, 8 * 256 * sizeof(unsigned long long), c->stream));
     HIPCHK(c, hipMemsetAsync(ab.class_sums.p, 0, 2 * (size_t)C * sizeof(unsigned long long), c->stream));
     return icikt::host::upload_sync(c, ab.cls.p, obs_cls.data(), (size_t)S * sizeof(int32_t));
   };
   // a block's raw values as sortable keys, before the next block overwrites them
-  steps.fold = [&](const icikt::host::PairBlock& b) -> int {
-    HIPCHK(c, icikt::launch_median_keep(c->d_out4.p, c->d_reasons.p, b.count, ab.kept.p + b.begin, c->stream));
-    return ICIKT_SUCCESS;
-  };
+  steps.fold = [&](const icikt::host::PairBlock& b) -> int { return icikt::host::select_keep_raw(c, b); };
   steps.finish = [&](unsigned long long* red) -> int {
     // M says whether anything is left to do, the digit table which digits to sort by: the one wait before the labellings
     unsigned long long h_total = 0ull, h_dhist[8 * 256];
     int r = icikt::host::timer_begin(c, ICIKT_K_EPILOGUE, flags);
     if (r) return r;
-    HIPCHK(c, icikt::launch_anosim_count(ab.kept.p, P, ab.total.p, ab.dhist.p, c->stream));
+    HIPCHK(c, icikt::launch_anosim_count(ws.kept.p, P, ws.total.p, ws.dhist.p, c->stream));
     r = icikt::host::timer_end(c, ICIKT_K_EPILOGUE, flags);
     if (r) return r;
     HIPCHK(c, hipMemcpyAsync(red, c->d_red.p, 8 * sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipMemcpyAsync(&h_total, ab.total.p, sizeof h_total, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipMemcpyAsync(h_dhist, ab.dhist.p, sizeof h_dhist, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(&h_total, ws.total.p, sizeof h_total, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(h_dhist, ws.dhist.p, sizeof h_dhist, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     if (h_total > (unsigned long long)P) return fail(c, ICIKT_E_STATE, "anosim: more values than pairs");
     M = (int64_t)h_total;
@@ -198,17 +195,11 @@ int anosim_src(icikt_ctx* c, const MatrixSrc& X, int64_t n_feat, int64_t n_samp,
     if (device) {
       r = icikt::host::timer_begin(c, ICIKT_K_EPILOGUE, flags);
       if (r) return r;
-      HIPCHK(c, hipMemcpyAsync(ab.sort_a.p, ab.kept.p, (size_t)P * sizeof(unsigned long long), hipMemcpyDeviceToDevice, c->stream));
-      unsigned long long *src = ab.sort_a.p, *dst = ab.sort_b.p;
-      for (int d = 0; d < 8; ++d) {
-        bool same = false;   // one digit value holds all P keys: the pass would move nothing
-        for (int v = 0; v < 256; ++v) same = same || h_dhist[d * 256 + v] == (unsigned long long)P;
-        if (same) continue;
-        HIPCHK(c, icikt::launch_padj_sort_pass(src, dst, P, tile, 8 * d, ab.counts.p, ab.agg.p, c->stream));
-        std::swap(src, dst);
-      }
-      ranks = dst;                      // the doubled ranks take the plane the sort has left free
-      HIPCHK(c, icikt::launch_anosim_rank(ab.kept.p, src, P, M, ranks, c->stream));
+      HIPCHK(c, hipMemcpyAsync(ws.plane_a.p, ws.kept.p, (size_t)P * sizeof(unsigned long long), hipMemcpyDeviceToDevice, c->stream));
+      unsigned long long* src = nullptr;   // kept stays in pair order for the rank pass: its copy is what is sorted
+      r = icikt::host::select_sort(c, P, tile, h_dhist, ws.plane_a.p, ws.plane_b.p, &src, &ranks);
+      if (r) return r;                  // (the doubled ranks take the plane the sort has left free)
+      HIPCHK(c, icikt::launch_anosim_rank(ws.kept.p, src, P, M, ranks, c->stream));
       HIPCHK(c, icikt::launch_anosim_classes(ranks, ab.cls.p, (int)S, ab.class_sums.p, ab.class_sums.p + C, c->stream));
       r = icikt::host::timer_end(c, ICIKT_K_EPILOGUE, flags);
       if (r) return r;

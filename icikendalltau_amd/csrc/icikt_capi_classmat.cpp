@@ -4,8 +4,9 @@
 // the next block overwrites them, and the select kernel reads the kept plane once the last block is through.
 //
 // Device memory: the prepared matrix, one block's buffers (icikt_blocks.h: kTriangleBlockPairs), 8 S (S - 1) / 2 bytes
-// of kept keys (65 535 samples: 17 GB), 4 (S + n_class + 1) bytes of member list and class ranges and 20 S n_class
-// bytes of results, each with the buffers' growth margin of a ninth.  Host memory: O(S + n_class), never O(S^2).
+// of kept keys in the workspace's `kept` plane (icikt_ctx::sel, shared with the other entries; 65 535 samples: 17 GB),
+// 4 (S + n_class + 1) bytes of member list and class ranges and 20 S n_class bytes of results, each with the buffers'
+// growth margin of a ninth.  Host memory: O(S + n_class), never O(S^2).
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -71,7 +72,7 @@ int classmat_src(icikt_ctx* c, const MatrixSrc& X, int64_t n_feat, int64_t n_sam
   PairBlocks blocks = PairBlocks::rows(S, budget);
   const int stage = c->plan_ov.medlds >= 0 ? c->plan_ov.medlds : icikt::MEDIAN_STAGE_MAX;
   auto& cm = c->cmat;
-  HIPCHK(c, cm.kept.reserve((size_t)std::max<int64_t>(blocks.total, 1)));
+  HIPCHK(c, c->sel.kept.reserve((size_t)std::max<int64_t>(blocks.total, 1)));
   HIPCHK(c, cm.member.reserve((size_t)S));
   HIPCHK(c, cm.first.reserve((size_t)C + 1));
   HIPCHK(c, cm.med2.reserve(2 * SC));
@@ -85,20 +86,17 @@ int classmat_src(icikt_ctx* c, const MatrixSrc& X, int64_t n_feat, int64_t n_sam
     return r;
   };
   // a block's raw values as sortable keys, before the next block overwrites them
-  steps.fold = [&](const icikt::host::PairBlock& b) -> int {
-    HIPCHK(c, icikt::launch_median_keep(c->d_out4.p, c->d_reasons.p, b.count, cm.kept.p + b.begin, c->stream));
-    return ICIKT_SUCCESS;
-  };
+  steps.fold = [&](const icikt::host::PairBlock& b) -> int { return icikt::host::select_keep_raw(c, b); };
   steps.finish = [&](unsigned long long* red) -> int {
     int r = icikt::host::timer_begin(c, ICIKT_K_EPILOGUE, flags);
     if (r) return r;
-    HIPCHK(c, icikt::launch_class_select(cm.member.p, cm.first.p, cm.kept.p, c->d_red.p, (int)S, C, A.scale_max ? 1 : 0,
+    HIPCHK(c, icikt::launch_class_select(cm.member.p, cm.first.p, c->sel.kept.p, c->d_red.p, (int)S, C, A.scale_max ? 1 : 0,
                                          stage, cm.med2.p, cm.n_valid.p, c->stream));
     r = icikt::host::timer_end(c, ICIKT_K_EPILOGUE, flags);
     if (r) return r;
     r = icikt::host::download(c, A.med2, cm.med2.p, 2 * SC * sizeof(double));
     if (!r && A.n_valid) r = icikt::host::download(c, A.n_valid, cm.n_valid.p, SC * sizeof(int32_t));
-    if (!r) r = icikt::host::download(c, red, c->d_red.p, 8 * sizeof(unsigned long long));
+    if (!r) r = icikt::host::select_download_red(c, red);
     return r;
   };
   return icikt::host::select_run(call, blocks, steps);

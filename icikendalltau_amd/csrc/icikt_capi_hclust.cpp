@@ -8,14 +8,13 @@
 // the state words come back, behind one wait; the host derives the components from the records and checks them in O(S).
 //
 // Device memory: the prepared matrix, one block's buffers (icikt_blocks.h: kTriangleBlockPairs), 8 S (S - 1) / 2 bytes
-// of kept keys, 8 S^2 bytes of table -- 12 S^2 together (65 535 samples: 52 GB) -- and 40 S bytes of neighbours (4 + 8),
+// of kept keys in the workspace's `kept` plane (icikt_ctx::sel, shared with the other entries), 8 S^2 bytes of table -- 12 S^2 together (65 535 samples: 52 GB) -- and 40 S bytes of neighbours (4 + 8),
 // live flags, sizes and list (4 each) and merge records (24, less one), each with the buffers' growth margin of a ninth.
 // Host memory: O(S), never O(S^2).
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
 #include <cmath>
-#include <cstring>
 #include <new>
 #include <string>
 #include <vector>
@@ -40,22 +39,6 @@ struct HclustArgs {
   int32_t* component;
   int64_t* n_components;
 };
-
-// colsort::cor_key on the host: order-preserving, -0 == +0; v is not NaN
-unsigned long long host_key(double v) {
-  if (v == 0.0) v = 0.0;
-  unsigned long long b;
-  std::memcpy(&b, &v, sizeof b);
-  return (b >> 63) ? ~b : (b | (1ull << 63));
-}
-
-// ... and back: the double of a key that is neither 0 nor NA_KEY
-double key_value(unsigned long long k) {
-  const unsigned long long u = (k >> 63) ? (k & 0x7FFFFFFFFFFFFFFFull) : ~k;
-  double v;
-  std::memcpy(&v, &u, sizeof v);
-  return v;
-}
 
 // the body of the three entries: the shared checks, the blocks and the call sequence are select_run's (icikt_host.h)
 int hclust_src(icikt_ctx* c, const MatrixSrc& X, int64_t n_feat, int64_t n_samp, const HclustArgs& A) {
@@ -83,11 +66,11 @@ int hclust_src(icikt_ctx* c, const MatrixSrc& X, int64_t n_feat, int64_t n_samp,
 
   const int64_t S = n_samp;
   const uint32_t flags = A.shared.flags;
-  const unsigned long long min_key = A.min_raw == A.min_raw ? host_key(A.min_raw) : 0ull;   // NaN: no bound
+  const unsigned long long min_key = A.min_raw == A.min_raw ? icikt::host::cor_key(A.min_raw) : 0ull;   // NaN: no bound
   const int grid = c->plan_ov.hcgrid > 0 ? c->plan_ov.hcgrid : (int)std::min<int64_t>(S, icikt::HCLUST_GRID_MAX);
   PairBlocks blocks = PairBlocks::rows(S, budget);
   auto& hb = c->hc;
-  HIPCHK(c, hb.kept.reserve((size_t)std::max<int64_t>(blocks.total, 1)));
+  HIPCHK(c, c->sel.kept.reserve((size_t)std::max<int64_t>(blocks.total, 1)));
   HIPCHK(c, hb.table.reserve((size_t)S * (size_t)S));
   HIPCHK(c, hb.nnkey.reserve((size_t)S));
   HIPCHK(c, hb.nn.reserve((size_t)S));
@@ -105,10 +88,7 @@ int hclust_src(icikt_ctx* c, const MatrixSrc& X, int64_t n_feat, int64_t n_samp,
   icikt::host::SelectSteps steps;
   steps.start = [&]() -> int { return ICIKT_SUCCESS; };
   // a block's raw values as sortable keys, before the next block overwrites them
-  steps.fold = [&](const icikt::host::PairBlock& b) -> int {
-    HIPCHK(c, icikt::launch_median_keep(c->d_out4.p, c->d_reasons.p, b.count, hb.kept.p + b.begin, c->stream));
-    return ICIKT_SUCCESS;
-  };
+  steps.fold = [&](const icikt::host::PairBlock& b) -> int { return icikt::host::select_keep_raw(c, b); };
   steps.finish = [&](unsigned long long* red) -> int {
     int32_t state[icikt::HC_WORDS] = {};
     try {
@@ -125,7 +105,7 @@ int hclust_src(icikt_ctx* c, const MatrixSrc& X, int64_t n_feat, int64_t n_samp,
       int r = icikt::host::timer_begin(c, ICIKT_K_EPILOGUE, flags);
       if (r) return r;
       HIPCHK(c, hipMemsetAsync(hb.state.p, 0, icikt::HC_WORDS * sizeof(int32_t), c->stream));
-      HIPCHK(c, icikt::launch_hc_expand(hb.kept.p, (int)S, hb.table.p, hb.alive.p, hb.size.p, c->stream));
+      HIPCHK(c, icikt::launch_hc_expand(c->sel.kept.p, (int)S, hb.table.p, hb.alive.p, hb.size.p, c->stream));
       HIPCHK(c, icikt::launch_hc_rescan(hb.table.p, hb.alive.p, hb.list.p, hb.state.p, (int)S, 1, grid, hb.nn.p,
                                         hb.nnkey.p, c->stream));
       for (int64_t t = 0; t < S - 1; ++t) {
@@ -160,7 +140,7 @@ int hclust_src(icikt_ctx* c, const MatrixSrc& X, int64_t n_feat, int64_t n_samp,
       if (m.a < 0 || m.b >= S || m.a >= m.b)
         return fail(c, ICIKT_E_STATE, at + " names the slots " + std::to_string(m.a) + ", " + std::to_string(m.b));
       if (!live[(size_t)m.a] || !live[(size_t)m.b]) return fail(c, ICIKT_E_STATE, at + " names a slot that is no cluster any more");
-      if (m.key == 0ull || m.key == ~0ull) return fail(c, ICIKT_E_STATE, at + " has no similarity");
+      if (m.key == 0ull || m.key == icikt::host::NA_KEY) return fail(c, ICIKT_E_STATE, at + " has no similarity");
       if (m.key < min_key) return fail(c, ICIKT_E_STATE, at + " lies below min_raw");
       if (m.size != size[(size_t)m.a] + size[(size_t)m.b]) return fail(c, ICIKT_E_STATE, at + " has another size than its two clusters");
       if (monotone && t > 0 && m.key > rec[(size_t)(t - 1)].key)
@@ -185,14 +165,10 @@ int hclust_src(icikt_ctx* c, const MatrixSrc& X, int64_t n_feat, int64_t n_samp,
   if (rc) return rc;
 
   // the outputs, once nothing can fail any more; the slots behind n_merges stay untouched
-  double max_cor = -HUGE_VAL;   // max(numeric(0), na.rm = TRUE) is -Inf in R
-  if (red0) {
-    const unsigned long long u = (red0 >> 63) ? (red0 & 0x7FFFFFFFFFFFFFFFull) : ~red0;
-    std::memcpy(&max_cor, &u, sizeof(double));
-  }
+  const double max_cor = icikt::host::max_taumax_of(red0);
   for (int64_t t = 0; t < n_merges; ++t) {
     const icikt::HcMerge& m = rec[(size_t)t];
-    const double raw = key_value(m.key);
+    const double raw = icikt::host::cor_key_value(m.key);
     A.ma[t] = m.a;
     A.mb[t] = m.b;
     A.msize[t] = m.size;

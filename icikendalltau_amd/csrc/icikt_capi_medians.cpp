@@ -4,7 +4,8 @@
 // next block overwrites them, and the select kernel reads the kept plane once the last block is through.
 //
 // Device memory: the prepared matrix, one block's buffers (icikt_blocks.h: kTriangleBlockPairs), 8 P bytes of kept keys
-// for the P = sum over the classes of m (m - 1) / 2 computed pairs (one class of 65 535 samples: 17 GB) and 36 S bytes:
+// in the workspace's `kept` plane (icikt_ctx::sel, shared with the other entries) for the P = sum over the classes of
+// m (m - 1) / 2 computed pairs (one class of 65 535 samples: 17 GB) and 36 S bytes:
 // the index arrays (position in class, class size, the class's first pair as int64: 16) and the results (20), each
 // with the buffers' growth margin of a ninth.  Host memory: O(S) for the classes and O(block) for a slice's pi / pj, never O(P).
 #include <hip/hip_runtime.h>
@@ -58,7 +59,7 @@ int medians_src(icikt_ctx* c, const MatrixSrc& X, int64_t n_feat, int64_t n_samp
   PairBlocks blocks = ci.runs.run.size() == 1 ? PairBlocks::rows(S, budget) : PairBlocks::slices(&ci.runs, ci.total, budget);
   const int stage = c->plan_ov.medlds >= 0 ? c->plan_ov.medlds : icikt::MEDIAN_STAGE_MAX;
   auto& md = c->med;
-  HIPCHK(c, md.kept.reserve((size_t)std::max<int64_t>(ci.total, 1)));
+  HIPCHK(c, c->sel.kept.reserve((size_t)std::max<int64_t>(ci.total, 1)));
   HIPCHK(c, md.pos.reserve((size_t)S));
   HIPCHK(c, md.size.reserve((size_t)S));
   HIPCHK(c, md.base.reserve((size_t)S));
@@ -75,20 +76,17 @@ int medians_src(icikt_ctx* c, const MatrixSrc& X, int64_t n_feat, int64_t n_samp
     return r;
   };
   // a block's raw values as sortable keys, before the next block overwrites them
-  steps.fold = [&](const icikt::host::PairBlock& b) -> int {
-    HIPCHK(c, icikt::launch_median_keep(c->d_out4.p, c->d_reasons.p, b.count, md.kept.p + b.begin, c->stream));
-    return ICIKT_SUCCESS;
-  };
+  steps.fold = [&](const icikt::host::PairBlock& b) -> int { return icikt::host::select_keep_raw(c, b); };
   steps.finish = [&](unsigned long long* red) -> int {
     int r = icikt::host::timer_begin(c, ICIKT_K_EPILOGUE, flags);
     if (r) return r;
-    HIPCHK(c, icikt::launch_median_select(mc, md.kept.p, c->d_red.p, (int)S, A.scale_max ? 1 : 0, stage, md.med2.p,
+    HIPCHK(c, icikt::launch_median_select(mc, c->sel.kept.p, c->d_red.p, (int)S, A.scale_max ? 1 : 0, stage, md.med2.p,
                                           md.n_valid.p, c->stream));
     r = icikt::host::timer_end(c, ICIKT_K_EPILOGUE, flags);
     if (r) return r;
     r = icikt::host::download(c, A.med2, md.med2.p, 2 * (size_t)S * sizeof(double));
     if (!r && A.n_valid) r = icikt::host::download(c, A.n_valid, md.n_valid.p, (size_t)S * sizeof(int32_t));
-    if (!r) r = icikt::host::download(c, red, c->d_red.p, 8 * sizeof(unsigned long long));
+    if (!r) r = icikt::host::select_download_red(c, red);
     return r;
   };
   return icikt::host::select_run(call, blocks, steps);

@@ -12,13 +12,13 @@
 // single-linkage merge order.
 //
 // Device memory: the prepared matrix, one block's buffers (icikt_blocks.h: kTriangleBlockPairs), 8 S (S - 1) / 2 bytes
-// of kept keys (65 535 samples: 17 GB) and 24 S bytes of component labels, live flags and candidates, each with the
+// of kept keys in the workspace's `kept` plane (icikt_ctx::sel, shared with the other entries; 65 535 samples: 17 GB)
+// and 24 S bytes of component labels, live flags and candidates, each with the
 // buffers' growth margin of a ninth.  Host memory: O(S), never O(S^2).
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
 #include <cmath>
-#include <cstring>
 #include <new>
 #include <numeric>
 #include <string>
@@ -45,14 +45,6 @@ struct MstArgs {
   int64_t* n_components;
   int32_t* n_rounds;
 };
-
-// colsort::cor_key on the host: order-preserving, -0 == +0; v is not NaN
-unsigned long long host_key(double v) {
-  if (v == 0.0) v = 0.0;
-  unsigned long long b;
-  std::memcpy(&b, &v, sizeof b);
-  return (b >> 63) ? ~b : (b | (1ull << 63));
-}
 
 // an edge of the forest: the key of its raw, its combn index and its ends i < j
 struct TreeEdge {
@@ -105,10 +97,10 @@ int mst_src(icikt_ctx* c, const MatrixSrc& X, int64_t n_feat, int64_t n_samp, co
 
   const int64_t S = n_samp;
   const uint32_t flags = A.shared.flags;
-  const unsigned long long min_key = A.min_raw == A.min_raw ? host_key(A.min_raw) : 0ull;   // NaN: no bound
+  const unsigned long long min_key = A.min_raw == A.min_raw ? icikt::host::cor_key(A.min_raw) : 0ull;   // NaN: no bound
   PairBlocks blocks = PairBlocks::rows(S, budget);
   auto& mb = c->mst;
-  HIPCHK(c, mb.kept.reserve((size_t)std::max<int64_t>(blocks.total, 1)));
+  HIPCHK(c, c->sel.kept.reserve((size_t)std::max<int64_t>(blocks.total, 1)));
   HIPCHK(c, mb.comp.reserve((size_t)S));
   HIPCHK(c, mb.live.reserve((size_t)S));
   HIPCHK(c, mb.best.reserve((size_t)S));
@@ -124,10 +116,7 @@ int mst_src(icikt_ctx* c, const MatrixSrc& X, int64_t n_feat, int64_t n_samp, co
   icikt::host::SelectSteps steps;
   steps.start = [&]() -> int { return ICIKT_SUCCESS; };
   // a block's raw values as sortable keys, before the next block overwrites them
-  steps.fold = [&](const icikt::host::PairBlock& b) -> int {
-    HIPCHK(c, icikt::launch_median_keep(c->d_out4.p, c->d_reasons.p, b.count, mb.kept.p + b.begin, c->stream));
-    return ICIKT_SUCCESS;
-  };
+  steps.fold = [&](const icikt::host::PairBlock& b) -> int { return icikt::host::select_keep_raw(c, b); };
   steps.finish = [&](unsigned long long* red) -> int {
     std::vector<icikt::MstBest> best;
     std::vector<unsigned long long> ckey;
@@ -154,7 +143,7 @@ int mst_src(icikt_ctx* c, const MatrixSrc& X, int64_t n_feat, int64_t n_samp, co
       if (!r) r = icikt::host::upload_sync(c, mb.live.p, live.data(), (size_t)S * sizeof(int32_t));
       if (!r) r = icikt::host::timer_begin(c, ICIKT_K_EPILOGUE, flags);
       if (r) return r;
-      HIPCHK(c, icikt::launch_mst_best(mb.kept.p, mb.comp.p, mb.live.p, min_key, (int)S, mb.best.p, c->stream));
+      HIPCHK(c, icikt::launch_mst_best(c->sel.kept.p, mb.comp.p, mb.live.p, min_key, (int)S, mb.best.p, c->stream));
       r = icikt::host::timer_end(c, ICIKT_K_EPILOGUE, flags);
       if (r) return r;
       HIPCHK(c, hipMemcpyAsync(best.data(), mb.best.p, (size_t)S * sizeof(icikt::MstBest), hipMemcpyDeviceToHost, c->stream));
@@ -166,7 +155,7 @@ int mst_src(icikt_ctx* c, const MatrixSrc& X, int64_t n_feat, int64_t n_samp, co
       for (int64_t s = 0; s < S; ++s) {
         const icikt::MstBest& b = best[(size_t)s];
         if (!live[(size_t)s] || !b.key) continue;
-        if (b.t < 0 || b.t >= S || b.t == s || comp[(size_t)b.t] == comp[(size_t)s] || b.key == ~0ull)
+        if (b.t < 0 || b.t >= S || b.t == s || comp[(size_t)b.t] == comp[(size_t)s] || b.key == icikt::host::NA_KEY)
           return fail(c, ICIKT_E_STATE, "mst: sample " + std::to_string(s) + " came back with a candidate that is no edge out of its component");
         const int32_t i = (int32_t)std::min<int64_t>(s, b.t), j = (int32_t)std::max<int64_t>(s, b.t);
         const TreeEdge e{b.key, icikt::host::row_offset(S, i) + (j - i - 1), i, j};
@@ -243,7 +232,7 @@ int mst_src(icikt_ctx* c, const MatrixSrc& X, int64_t n_feat, int64_t n_samp, co
     HIPCHK(c, hipStreamSynchronize(c->stream));
     for (int64_t e = 0; e < n_tree; ++e) {
       const double raw = out4[4 * (size_t)e];
-      if (reasons[(size_t)e] != 0 || raw != raw || host_key(raw) != tree[(size_t)e].key)
+      if (reasons[(size_t)e] != 0 || icikt::host::cor_key(raw) != tree[(size_t)e].key)
         return fail(c, ICIKT_E_STATE, "mst: the pair (" + std::to_string(pi[(size_t)e]) + ", " + std::to_string(pj[(size_t)e]) +
                                           ") of the tree has another raw as a pair list than in the triangle");
     }
@@ -254,11 +243,7 @@ int mst_src(icikt_ctx* c, const MatrixSrc& X, int64_t n_feat, int64_t n_samp, co
 
   // the outputs, once nothing can fail any more; the slots behind n_tree stay untouched
   const int64_t n_tree = (int64_t)tree.size();
-  double max_cor = -HUGE_VAL;   // max(numeric(0), na.rm = TRUE) is -Inf in R
-  if (red0) {
-    const unsigned long long u = (red0 >> 63) ? (red0 & 0x7FFFFFFFFFFFFFFFull) : ~red0;
-    std::memcpy(&max_cor, &u, sizeof(double));
-  }
+  const double max_cor = icikt::host::max_taumax_of(red0);
   const size_t plane = (size_t)(S - 1);
   for (int64_t e = 0; e < n_tree; ++e) {
     const double raw = out4[4 * (size_t)e];

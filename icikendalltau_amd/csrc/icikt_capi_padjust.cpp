@@ -6,13 +6,14 @@
 // of the alphas and compacts the table of distinct p-values -- the table's extent stays on the device.
 //
 // Device memory: the prepared matrix, one block's buffers (icikt_blocks.h: kTriangleBlockPairs), and
-//   16 S (S - 1) / 2                               the kept keys and the sort's spare plane, which takes the adjusted
-//                                                  values (S = 65 535: 34 GB)
+//   16 S (S - 1) / 2                               the kept keys and the plane the sort ping-pongs them with, which
+//                                                  takes the adjusted values (S = 65 535: 34 GB): `kept` and `plane_a`
+//                                                  of the workspace (icikt_ctx::sel, shared with the other entries)
 //   + 2 048 ceil(P / tile)                         the sort's (digit, tile) counters: 2 MB per 1 024 tiles, at most
-//                                                  65 536 tiles
-//   + 8 (max(P, 256 tiles) / 1 024 + 1)            a scan's chunk aggregates
+//                                                  65 536 tiles (the workspace's `counts`)
+//   + 8 (max(P, 256 tiles) / 1 024 + 1)            a scan's chunk aggregates (its `agg`)
 //   + 16 min(max_table, P)                         the table
-//   + 16 KB                                        the digit table, the alphas, the cut-offs' record
+//   + 16 KB                                        the digit table (the workspace's `dhist`), the alphas, the cut-offs' record
 // each with the buffers' growth margin of a ninth.  Host memory: O(1), never O(pairs).
 #include <hip/hip_runtime.h>
 
@@ -40,8 +41,6 @@ struct PadjArgs {
   double *p_cutoff, *table;
   int64_t* n_table;
 };
-
-const unsigned long long kNaReal = 0x7FF00000000007A2ull;   // R's NA_real_
 
 static_assert(ICIKT_ADJUST_BONFERRONI == icikt::PADJ_BONFERRONI && ICIKT_ADJUST_HOLM == icikt::PADJ_HOLM &&
                   ICIKT_ADJUST_HOCHBERG == icikt::PADJ_HOCHBERG && ICIKT_ADJUST_BH == icikt::PADJ_BH &&
@@ -83,7 +82,7 @@ int padjust_src(icikt_ctx* c, const MatrixSrc& X, int64_t n_feat, int64_t n_samp
     A.n_tests[1] = P - m;
     for (int a = 0; a < A.n_alpha; ++a) {
       A.n_rejected[a] = m > 0 ? (int64_t)h_cut[a] : 0;
-      const unsigned long long bits = m > 0 ? h_cut[icikt::PADJ_MAX_ALPHA + a] : kNaReal;
+      const unsigned long long bits = m > 0 ? h_cut[icikt::PADJ_MAX_ALPHA + a] : icikt::host::R_NA_BITS;
       std::memcpy(&A.p_cutoff[a], &bits, sizeof(double));
     }
     *A.n_table = n_table;
@@ -98,15 +97,13 @@ int padjust_src(icikt_ctx* c, const MatrixSrc& X, int64_t n_feat, int64_t n_samp
 
   PairBlocks blocks = PairBlocks::rows(S, budget);
   const long long tile = icikt::padj_tile(P, c->plan_ov.padjtile > 0 ? c->plan_ov.padjtile : 0);
-  const long long n_tiles = (P + tile - 1) / tile;
   const int64_t cap = std::min<int64_t>(A.max_table, P);   // (there are no more distinct p-values than pairs)
   auto& pb = c->padj;
-  HIPCHK(c, pb.kept.reserve((size_t)std::max<int64_t>(P, 1)));
-  HIPCHK(c, pb.spare.reserve((size_t)std::max<int64_t>(P, 1)));
-  HIPCHK(c, pb.counts.reserve((size_t)std::max<long long>(256 * n_tiles, 1)));
-  HIPCHK(c, pb.agg.reserve((size_t)icikt::padj_scan_chunks(P, tile)));
-  HIPCHK(c, pb.total.reserve(1));
-  HIPCHK(c, pb.dhist.reserve(8 * 256));
+  auto& ws = c->sel;   // kept and plane_a: the keys and the sort; the sort's counters and aggregates are select_sort's
+  HIPCHK(c, ws.kept.reserve((size_t)std::max<int64_t>(P, 1)));
+  HIPCHK(c, ws.plane_a.reserve((size_t)std::max<int64_t>(P, 1)));
+  HIPCHK(c, ws.total.reserve(1));
+  HIPCHK(c, ws.dhist.reserve(8 * 256));
   HIPCHK(c, pb.cut.reserve(icikt::PADJ_CUT_WORDS));
   HIPCHK(c, pb.n_table.reserve(1));
   HIPCHK(c, pb.alpha.reserve(icikt::PADJ_MAX_ALPHA));
@@ -117,40 +114,35 @@ int padjust_src(icikt_ctx* c, const MatrixSrc& X, int64_t n_feat, int64_t n_samp
   steps.start = [&]() -> int {
     const int r = icikt::host::upload_sync(c, pb.alpha.p, A.alpha, (size_t)A.n_alpha * sizeof(double));
     if (r) return r;
-    HIPCHK(c, hipMemsetAsync(pb.total.p, 0, sizeof(unsigned long long), c->stream));
-    HIPCHK(c, hipMemsetAsync(pb.dhist.p, 0, 8 * 256 * sizeof(unsigned long long), c->stream));
+    HIPCHK(c, hipMemsetAsync(ws.total.p, 0, sizeof(unsigned long long), c->stream));
+    HIPCHK(c, hipMemsetAsync(ws.dhist.p, 0, 8 * 256 * sizeof(unsigned long long), c->stream));
     return ICIKT_SUCCESS;
   };
   // a block's p-values as sortable keys, before the next block overwrites them
   steps.fold = [&](const icikt::host::PairBlock& b) -> int {
-    HIPCHK(c, icikt::launch_padj_fold(c->d_out4.p, c->d_reasons.p, b.count, b.begin, (int)S, pb.kept.p, pb.total.p,
-                                      pb.dhist.p, c->stream));
+    HIPCHK(c, icikt::launch_padj_fold(c->d_out4.p, c->d_reasons.p, b.count, b.begin, (int)S, ws.kept.p, ws.total.p,
+                                      ws.dhist.p, c->stream));
     return ICIKT_SUCCESS;
   };
   steps.finish = [&](unsigned long long* red) -> int {
     // m sizes the scans, the digit table says which digits to sort by: the one wait inside the call
     unsigned long long h_total = 0ull, h_dhist[8 * 256];
     HIPCHK(c, hipMemcpyAsync(red, c->d_red.p, 8 * sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipMemcpyAsync(&h_total, pb.total.p, sizeof h_total, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipMemcpyAsync(h_dhist, pb.dhist.p, sizeof h_dhist, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(&h_total, ws.total.p, sizeof h_total, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(h_dhist, ws.dhist.p, sizeof h_dhist, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     if (P == 0 || h_total == 0ull) return ICIKT_SUCCESS;
     if (h_total > (unsigned long long)P) return fail(c, ICIKT_E_STATE, "padjust: more tests than pairs");
     m = (int64_t)h_total;
     int r = icikt::host::timer_begin(c, ICIKT_K_EPILOGUE, flags);
     if (r) return r;
-    unsigned long long *src = pb.kept.p, *dst = pb.spare.p;
-    for (int d = 0; d < 8; ++d) {
-      bool same = false;   // one digit value holds all P keys: the pass would move nothing
-      for (int v = 0; v < 256; ++v) same = same || h_dhist[d * 256 + v] == (unsigned long long)P;
-      if (same) continue;
-      HIPCHK(c, icikt::launch_padj_sort_pass(src, dst, P, tile, 8 * d, pb.counts.p, pb.agg.p, c->stream));
-      std::swap(src, dst);
-    }
-    double* const adj = reinterpret_cast<double*>(dst);   // the adjusted values take the spare plane
-    HIPCHK(c, icikt::launch_padj_adjust(src, m, A.method, adj, reinterpret_cast<double*>(pb.agg.p), c->stream));
+    unsigned long long *src = nullptr, *dst = nullptr;
+    r = icikt::host::select_sort(c, P, tile, h_dhist, ws.kept.p, ws.plane_a.p, &src, &dst);
+    if (r) return r;
+    double* const adj = reinterpret_cast<double*>(dst);   // the adjusted values take the plane the sort has left free
+    HIPCHK(c, icikt::launch_padj_adjust(src, m, A.method, adj, reinterpret_cast<double*>(ws.agg.p), c->stream));
     HIPCHK(c, icikt::launch_padj_cut(adj, src, m, pb.alpha.p, A.n_alpha, pb.cut.p, c->stream));
-    HIPCHK(c, icikt::launch_padj_table(src, adj, m, pb.cut.p + 2 * icikt::PADJ_MAX_ALPHA, cap, pb.table.p, pb.agg.p,
+    HIPCHK(c, icikt::launch_padj_table(src, adj, m, pb.cut.p + 2 * icikt::PADJ_MAX_ALPHA, cap, pb.table.p, ws.agg.p,
                                        pb.n_table.p, c->stream));
     r = icikt::host::timer_end(c, ICIKT_K_EPILOGUE, flags);
     if (r) return r;

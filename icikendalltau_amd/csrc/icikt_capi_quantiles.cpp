@@ -7,8 +7,9 @@
 // statistics and the scale m only: the interpolation runs here, in plain C++ with no fused multiply-add.
 //
 // Device memory: the prepared matrix, one block's buffers (icikt_blocks.h: kTriangleBlockPairs), and
-//   (n_probs > 0 ? 8 S (S - 1) / 2 : 0)            the kept keys (S = 65 535: 17 GB); group membership is recomputed
-//                                                  from a pair's index, so there is no ninth byte per pair
+//   (n_probs > 0 ? 8 S (S - 1) / 2 : 0)            the kept keys, in the workspace's `kept` plane (icikt_ctx::sel,
+//                                                  shared with the other entries; S = 65 535: 17 GB); group membership
+//                                                  is recomputed from a pair's index: no ninth byte per pair
 //   + 4 S                                          the class index (with cls)
 //   + 8 n_breaks + 16 (4 + n_breaks - 1)           the breaks, the totals of the two counted groups
 //   + 20 * 192 + 8 * 32 * 256                      the select's targets and one batch's digit histograms
@@ -17,7 +18,6 @@
 
 #include <algorithm>
 #include <cmath>
-#include <cstring>
 #include <new>
 #include <string>
 #include <vector>
@@ -53,16 +53,6 @@ struct QuantFound {
   std::vector<double> index, lo;              // [n_group][n_probs]: 1 + (v - 1) p and its floor
 };
 
-const unsigned long long kNaReal = 0x7FF00000000007A2ull;   // R's NA_real_
-
-double from_bits(unsigned long long b) {
-  double v;
-  std::memcpy(&v, &b, sizeof v);
-  return v;
-}
-double key_value(unsigned long long k) {   // inverse of colsort::cor_key (which has made +0 of a zero)
-  return from_bits((k >> 63) ? (k & ~(1ull << 63)) : ~k);
-}
 double plus_zero(double v) { return v == 0.0 ? 0.0 : v; }
 
 // R's quantile(type = 7) between the order statistics a = x[lo] and b = x[hi], index = 1 + (v - 1) p.  Every product
@@ -123,10 +113,10 @@ void write_outputs(const QuantArgs& A, int n_group, const QuantFound& f, double 
     for (int k = 0; k < n_bins; ++k) A.hist[(size_t)g * n_bins + k] = f.hist[(size_t)g * n_bins + k];
     for (int p = 0; p < np; ++p) {
       const size_t cell = (size_t)g * np + p;
-      double a = from_bits(kNaReal), b = a, qr = a, qc = a;
+      double a = icikt::host::from_bits(icikt::host::R_NA_BITS), b = a, qr = a, qc = a;
       if (f.target[cell * 2] >= 0) {
-        a = key_value(f.key[(size_t)f.target[cell * 2]]);
-        b = key_value(f.key[(size_t)f.target[cell * 2 + 1]]);
+        a = icikt::host::cor_key_value(f.key[(size_t)f.target[cell * 2]]);
+        b = icikt::host::cor_key_value(f.key[(size_t)f.target[cell * 2 + 1]]);
         qr = type7_value(a, b, f.index[cell], f.lo[cell]);
         // the division is k_assemble's, on k_assemble's operands; max(numeric(0), na.rm = TRUE) is -Inf in R
         qc = A.scale_max ? type7_value(plus_zero(a / m), plus_zero(b / m), f.index[cell], f.lo[cell]) : qr;
@@ -203,7 +193,7 @@ int quantiles_src(icikt_ctx* c, const MatrixSrc& X, int64_t n_feat, int64_t n_sa
   const int batch = c->plan_ov.qbatch > 0 ? c->plan_ov.qbatch : icikt::QUANT_BATCH_MAX;
   const size_t max_targets = 2 * 3 * (size_t)ICIKT_QUANTILE_MAX_PROBS;
   auto& qb = c->quant;
-  if (A.n_probs > 0) HIPCHK(c, qb.kept.reserve((size_t)std::max<int64_t>(P, 1)));
+  if (A.n_probs > 0) HIPCHK(c, c->sel.kept.reserve((size_t)std::max<int64_t>(P, 1)));
   HIPCHK(c, qb.totals.reserve((size_t)n_counted * stride));
   HIPCHK(c, qb.prefix.reserve(max_targets));
   HIPCHK(c, qb.rank.reserve(max_targets));
@@ -212,7 +202,7 @@ int quantiles_src(icikt_ctx* c, const MatrixSrc& X, int64_t n_feat, int64_t n_sa
   if (A.cls) HIPCHK(c, qb.cls.reserve((size_t)S));
   if (A.n_breaks > 0) HIPCHK(c, qb.breaks.reserve((size_t)A.n_breaks));
   const int32_t* const d_cls = A.cls ? qb.cls.p : nullptr;
-  unsigned long long* const d_kept = A.n_probs > 0 ? qb.kept.p : nullptr;
+  unsigned long long* const d_kept = A.n_probs > 0 ? c->sel.kept.p : nullptr;
   const uint32_t flags = A.shared.flags;
   double m = 1.0;
 
@@ -249,13 +239,7 @@ int quantiles_src(icikt_ctx* c, const MatrixSrc& X, int64_t n_feat, int64_t n_sa
       found.above[g] = word(g, 3);
       for (int k = 0; k < n_bins; ++k) found.hist[(size_t)g * n_bins + k] = word(g, icikt::QUANT_HEAD + k);
     }
-    if (A.scale_max) {
-      m = -HUGE_VAL;
-      if (red[0]) {
-        const unsigned long long u = (red[0] >> 63) ? (red[0] & 0x7FFFFFFFFFFFFFFFull) : ~red[0];
-        std::memcpy(&m, &u, sizeof(double));
-      }
-    }
+    if (A.scale_max) m = icikt::host::max_taumax_of(red[0]);
     try { plan_targets(A, n_group, &found, &t_rank, &t_group); } catch (const std::bad_alloc&) {
       return fail(c, ICIKT_E_NOMEM, "quantiles: host allocation failed");
     }
@@ -273,7 +257,7 @@ int quantiles_src(icikt_ctx* c, const MatrixSrc& X, int64_t n_feat, int64_t n_sa
     for (int t0 = 0; t0 < n_t; t0 += batch) {
       const int nt = std::min(batch, n_t - t0);
       for (int shift = 56; shift >= 0; shift -= 8) {
-        HIPCHK(c, icikt::launch_quant_count(qb.kept.p, P, (int)S, d_cls, T, t0, nt, shift, qb.hist.p, c->stream));
+        HIPCHK(c, icikt::launch_quant_count(d_kept, P, (int)S, d_cls, T, t0, nt, shift, qb.hist.p, c->stream));
         HIPCHK(c, icikt::launch_quant_pick(T, t0, nt, shift, qb.hist.p, c->stream));
       }
     }

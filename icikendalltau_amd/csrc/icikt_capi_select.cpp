@@ -1,11 +1,13 @@
-// icikt_capi_select.cpp -- the host side the selection entries share (icikt_topk_*, icikt_edges_*,
-// icikt_class_medians_*, icikt_quantiles_*; declared in icikt_host.h): their common checks, and the run of a call's blocks through the
-// pair engine.  Nothing of size S^2 is allocated: each block's records are folded by the entry's kernel before the
-// next block overwrites them.
+// icikt_capi_select.cpp -- the host side the nine selection entries share (icikt_topk_*, icikt_edges_*,
+// icikt_class_medians_*, icikt_class_matrix_*, icikt_quantiles_*, icikt_padjust_*, icikt_mst_*, icikt_anosim_*,
+// icikt_hclust_*; declared in icikt_host.h): their common checks, the run of a call's blocks through the pair engine,
+// and the steps several of them take over the one set of key planes (icikt_ctx::sel) -- the fold that keeps a block's
+// raw as keys, the radix sort, the download of d_red.  The driver allocates nothing of size S^2: each block's records
+// are folded by the entry's kernel before the next block overwrites them.
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <cmath>
-#include <cstring>
 #include <new>
 #include <string>
 
@@ -128,10 +130,33 @@ int select_run(SelectCall& s, PairBlocks& blocks, const SelectSteps& steps) {
   if (rc) return rc;
   // d_red: word 0 the largest taumax as an order-preserving key (0: no pair had one), words 1 .. 5 the reason counts
   if (A.reason_counts) for (int r = 0; r < 5; ++r) A.reason_counts[r] = (int64_t)red[1 + r];
-  if (A.max_taumax && red[0]) {
-    const unsigned long long u = (red[0] >> 63) ? (red[0] & 0x7FFFFFFFFFFFFFFFull) : ~red[0];
-    std::memcpy(A.max_taumax, &u, sizeof(double));
+  if (A.max_taumax) *A.max_taumax = max_taumax_of(red[0]);
+  return ICIKT_SUCCESS;
+}
+
+int select_keep_raw(icikt_ctx* c, const PairBlock& b) {
+  HIPCHK(c, launch_median_keep(c->d_out4.p, c->d_reasons.p, b.count, c->sel.kept.p + b.begin, c->stream));
+  return ICIKT_SUCCESS;
+}
+
+int select_download_red(icikt_ctx* c, unsigned long long* red) {
+  return download(c, red, c->d_red.p, 8 * sizeof(unsigned long long));
+}
+
+int select_sort(icikt_ctx* c, int64_t P, long long tile, const unsigned long long* h_dhist, unsigned long long* a,
+                unsigned long long* b, unsigned long long** sorted, unsigned long long** spare) {
+  const long long n_tiles = (P + tile - 1) / tile;
+  HIPCHK(c, c->sel.counts.reserve((size_t)std::max<long long>(256 * n_tiles, 1)));
+  HIPCHK(c, c->sel.agg.reserve((size_t)padj_scan_chunks(P, tile)));
+  for (int d = 0; d < 8; ++d) {
+    bool same = false;   // one digit value holds all P keys: the pass would move nothing
+    for (int v = 0; v < 256; ++v) same = same || h_dhist[d * 256 + v] == (unsigned long long)P;
+    if (same) continue;
+    HIPCHK(c, launch_padj_sort_pass(a, b, P, tile, 8 * d, c->sel.counts.p, c->sel.agg.p, c->stream));
+    std::swap(a, b);
   }
+  *sorted = a;
+  *spare = b;
   return ICIKT_SUCCESS;
 }
 

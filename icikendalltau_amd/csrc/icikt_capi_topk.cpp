@@ -68,7 +68,7 @@ int topk_src(icikt_ctx* c, const MatrixSrc& X, int64_t n_feat, int64_t n_samp, c
     r = icikt::host::download(c, A.idx, tk.idx.p, SK * sizeof(int32_t));
     if (!r) r = icikt::host::download(c, A.out5k, tk.out.p, 5 * SK * sizeof(double));
     if (!r && A.n_valid) r = icikt::host::download(c, A.n_valid, tk.n_valid.p, (size_t)S * sizeof(int32_t));
-    if (!r) r = icikt::host::download(c, red, c->d_red.p, 8 * sizeof(unsigned long long));
+    if (!r) r = icikt::host::select_download_red(c, red);
     return r;
   };
   return icikt::host::select_run(call, blocks, steps);

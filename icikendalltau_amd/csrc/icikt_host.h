@@ -15,6 +15,7 @@
 #include "icikt.h"
 #include "icikt_blocks.h"
 #include "icikt_device.h"
+#include "icikt_keys.h"
 #include "icikt_transfer.h"
 
 // a device buffer, grown on demand and kept; freed with its owner (on the device current at that time)
@@ -133,64 +134,67 @@ struct icikt_ctx {
     DevBuf<double> vals;   // [5][cap]: cor, raw, pvalue, taumax, completeness
   } edges;
 
-  // per-sample medians within classes (icikt_class_medians_f64): the kept plane (a key per computed pair), the
-  // samples' places in their classes (MedianClasses) and the results
+  // the key planes and the sort's scratch of the selection entries, one set for all of them (DESIGN.md section 16 says
+  // who leaves what there): `kept` is the call's plane, one sortable key per pair of the call; plane_a and plane_b are
+  // what a sort ping-pongs between and what takes a rank or adjust pass afterwards (select_sort); counts are the
+  // sort's (digit, tile) counters, agg a scan's chunk aggregates, total and dhist the valid count and the digit table
+  // of the fold that feeds the sort
+  struct SelectWork {
+    DevBuf<unsigned long long> kept, plane_a, plane_b, counts, agg, total, dhist;
+  } sel;
+
+  // per-sample medians within classes (icikt_class_medians_f64): the samples' places in their classes (MedianClasses)
+  // and the results; the computed pairs' keys are in sel.kept
   struct MedianBufs {
-    DevBuf<unsigned long long> kept;
     DevBuf<int32_t> pos, size, n_valid;
     DevBuf<long long> base;
     DevBuf<double> med2;
   } med;
 
-  // per-sample medians to every class (icikt_class_matrix_f64): the kept plane (a key per pair of the triangle), the
-  // samples sorted by class with each class's range, and the results per (class, sample) cell
+  // per-sample medians to every class (icikt_class_matrix_f64): the samples sorted by class with each class's range,
+  // and the results per (class, sample) cell; the triangle's keys are in sel.kept
   struct ClassMatBufs {
-    DevBuf<unsigned long long> kept;
     DevBuf<int32_t> member, first, n_valid;
     DevBuf<double> med2;
   } cmat;
 
-  // quantiles and histogram of all pairs (icikt_quantiles_f64): the kept plane (a key per pair of the triangle, only
-  // when quantiles are asked for), the class index, the breaks, the counted groups' totals, and the select's targets
-  // (QuantTargets) with their digit histograms
+  // quantiles and histogram of all pairs (icikt_quantiles_f64): the class index, the breaks, the counted groups' totals,
+  // and the select's targets (QuantTargets) with their digit histograms; the triangle's keys are in sel.kept, only when
+  // quantiles are asked for
   struct QuantBufs {
-    DevBuf<unsigned long long> kept, totals, prefix, hist;
+    DevBuf<unsigned long long> totals, prefix, hist;
     DevBuf<long long> rank;
     DevBuf<int32_t> group, cls;
     DevBuf<double> breaks;
   } quant;
 
-  // multiple-testing adjustment of all pairs (icikt_padjust_f64): the kept plane (a key per pair of the triangle) and
-  // the sort's spare plane, which takes the adjusted values afterwards; the sort's (digit, tile) counters and the scans'
-  // chunk aggregates; the valid count, the fold's digit table, the alphas, the cut-offs' record, the table's count and
-  // the table itself
+  // multiple-testing adjustment of all pairs (icikt_padjust_f64): the alphas, the cut-offs' record, the table's count
+  // and the table itself; the keys, the sort and the adjusted values are in sel (kept, plane_a)
   struct PadjBufs {
-    DevBuf<unsigned long long> kept, spare, counts, agg, total, dhist, cut, n_table;
+    DevBuf<unsigned long long> cut, n_table;
     DevBuf<double> alpha, table;
   } padj;
 
-  // maximum spanning forest (icikt_mst_f64): the kept plane (a key per pair of the triangle), the samples' component
-  // labels and live flags, and every sample's best edge of a round
+  // maximum spanning forest (icikt_mst_f64): the samples' component labels and live flags, and every sample's best
+  // edge of a round; the triangle's keys are in sel.kept
   struct MstBufs {
-    DevBuf<unsigned long long> kept;
     DevBuf<int32_t> comp, live;
     DevBuf<icikt::MstBest> best;
   } mst;
 
-  // complete, average and single linkage (icikt_hclust_f64): the kept plane (a key per pair of the triangle), the
-  // symmetric S x S table of keys, every slot's cached neighbour with its key, the live flags and cluster sizes, the
-  // rescan list, the call's state words (icikt_device.h: HC_*) and the merge records
+  // complete, average and single linkage (icikt_hclust_f64): the symmetric S x S table of keys, every slot's cached
+  // neighbour with its key, the live flags and cluster sizes, the rescan list, the call's state words (icikt_device.h:
+  // HC_*) and the merge records; the triangle's keys are in sel.kept
   struct HclustBufs {
-    DevBuf<unsigned long long> kept, table, nnkey;
+    DevBuf<unsigned long long> table, nnkey;
     DevBuf<int32_t> nn, alive, size, list, state;
     DevBuf<icikt::HcMerge> rec;
   } hc;
 
-  // ANOSIM (icikt_anosim_f64): the kept plane (a key per pair of the triangle), the two planes of the sort -- the one
-  // the sort leaves free takes the doubled ranks --, the sort's counters and the scans' aggregates, the valid count and
-  // the digit table, the observed labelling and its per-class sums, a batch of labellings and their sums
+  // ANOSIM (icikt_anosim_f64): the observed labelling and its per-class sums, a batch of labellings and their sums; the
+  // keys, their sorted copy and the doubled ranks are in sel (kept, plane_a, plane_b)
   struct AnosimBufs {
-    DevBuf<unsigned long long> kept, sort_a, sort_b, counts, agg, total, dhist, class_sums, w2, nw;
+    DevBuf<unsigned long long> class_sums, w2, nw;
     DevBuf<int32_t> cls;
     DevBuf<uint16_t> labels;
   } ano;
@@ -321,6 +325,7 @@ struct SelectSteps {
   std::function<int(const PairBlock&)> fold;          // its kernel over the block that is in c->d_out4 / c->d_reasons (the
                                                       // driver has run launch_out_stats_accum inside the same timer pair)
   std::function<int(unsigned long long* red)> finish; // its last kernel and its downloads, c->d_red into red[8] among them
+                                                      // (select_download_red, or a copy of its own beside what it waits for)
 };
 // The checks of an entry, in this order, before any output or anything of the context is touched:
 //   select_check_shape   the context, the matrix (check_src), ICIKT_TOPK_MAX_SAMPLES (`cap_why`: the entry's reason for it)
@@ -334,6 +339,18 @@ int select_check_shape(const SelectCall& s, const char* cap_why);
 int select_check_args(SelectCall& s);
 int select_budget(const SelectCall& s, int64_t* budget);
 int select_run(SelectCall& s, PairBlocks& blocks, const SelectSteps& steps);
+// Steps several entries share, on c->stream; the key planes and the sort's scratch are c->sel's (SelectWork).
+// the fold that keeps a block's raw as keys: launch_median_keep into sel.kept at the block's place
+int select_keep_raw(icikt_ctx* c, const PairBlock& b);
+// the eight words of c->d_red into red, delivered with the call's results (download): a finish's last step
+int select_download_red(icikt_ctx* c, unsigned long long* red);
+// The stable radix sort of the P keys in `a`, ascending, `a` and `b` ping-ponging, tile keys per wave (padj_tile).
+// h_dhist [8][256] is the downloaded digit table of those keys: a digit is skipped iff one of its values holds all P
+// keys (the pass would move nothing).  Reserves sel.counts and sel.agg for this P and tile -- agg stays good for the
+// scans of the same P behind the sort.  *sorted is the plane that holds the keys in order, *spare the other one.  No
+// timer pair: the caller's is around the sort and its own kernels.
+int select_sort(icikt_ctx* c, int64_t P, long long tile, const unsigned long long* h_dhist, unsigned long long* a,
+                unsigned long long* b, unsigned long long** sorted, unsigned long long** spare);
 
 }  // namespace host
 }  // namespace icikt
