@@ -759,8 +759,12 @@ int prepare_launch(icikt_ctx* c, const double* dX, int64_t ld, int64_t col_begin
     const int64_t chunk = std::max(1, c->sort_chunk);
     for (int64_t c0 = col_begin; c0 < col_end; c0 += chunk) {
       const int nc = (int)std::min<int64_t>(chunk, col_end - c0);
-      const int small_shape = (c->k0_shape == 1 || (c->k0_shape < 0 && c->k0_small)) ? 1 : 0;
-      HIPCHK(c, icikt::launch_k0(pv, dX, ld, (int)c0, nc, c->k0_mask, c->k0_keep, small_shape, stream));
+      const int shape = (c->k0_shape < 0 && c->k0_small) ? (int)K0_SHAPE_SMALL
+                                                         : k0_launch_shape(c->k0_shape, pv.n, nc, c->prop.multiProcessorCount);
+      if (c->plan_ov.verbose)
+        fprintf(stderr, "[icikt] K0 plan: shape=%d (0 large, 1 small, 2 two per CU), %d rows x %d columns, %d CUs\n", shape, pv.n, nc,
+                c->prop.multiProcessorCount);
+      HIPCHK(c, icikt::launch_k0(pv, dX, ld, (int)c0, nc, c->k0_mask, c->k0_keep, shape, stream));
     }
   }
   return ICIKT_SUCCESS;
@@ -1769,7 +1773,7 @@ int icikt_debug_set_plan(icikt_ctx* c, const char* spec) {
     else if (key == "gridmult") ov.grid_mult = atoi(val.c_str());
     else if (key == "gridcap") ov.grid_cap = atoi(val.c_str());
     else if (key == "pipe") pipe = (val[0] == '1') ? 1 : 0;
-    else if (key == "k0") k0 = (val[0] == '1') ? 1 : 0;
+    else if (key == "k0") k0 = (val[0] == '1') ? 1 : (val[0] == '2') ? 2 : 0;
     else if (key == "tkblock") ov.tkblock = atoll(val.c_str());
     else if (key == "medlds") {
       ov.medlds = atoi(val.c_str());

@@ -15,6 +15,7 @@
 #include "icikt.h"
 #include "icikt_blocks.h"
 #include "icikt_device.h"
+#include "icikt_k0plan.h"
 #include "icikt_keys.h"
 #include "icikt_transfer.h"
 
@@ -100,7 +101,7 @@ struct icikt_ctx {
   DevBuf<unsigned long long> d_red;
   DevBuf<int32_t> d_pi_all, d_pj_all;     // icikt_matrix_multi_f64, explicit pair list: the whole list on the first device
   bool k0_small = false;    // (no caller sets it: the 256-thread shape of the pre-pass is reached through the plan key only)
-  int k0_shape = -1;        // debug plan key "k0": -1 the library's choice (the large shape), 0 the large shape, 1 the small one
+  int k0_shape = -1;        // debug plan key "k0": -1 the library's choice (icikt_k0plan.h), 0 the large shape, 1 the small one, 2 the 512-thread one
   const icikt::MaskSpec* k0_mask = nullptr;
   uint8_t* k0_keep = nullptr;
   DevBuf<int64_t> d_counts;

@@ -1,6 +1,6 @@
 // icikt_prepass.hip -- K0, the per-column pre-pass of the ICI-Kendall-tau engine (gfx950, wave64).
 //
-//   k0_prepare_{large,large8,wide,small}   one workgroup per column: NA bitset, fill = min - 0.1, stable sort (bitonic:
+//   k0_prepare_{large,large8,wide,small,pair}   one workgroup per column: NA bitset, fill = min - 0.1, stable sort (bitonic:
 //                    register, lane and LDS stages), tie groups, tie sums, and the column's TIE PROGRAM -- the steps a
 //                    half-wave pair kernel takes through it (entry layout and sizes: TPROG_* of icikt_device.h).
 //                    Replaces the two std::stable_sort calls per PAIR (kendallc.cpp:247,254) by one sort per COLUMN.
@@ -22,14 +22,23 @@ namespace icikt {
 // ------------------------------------------------------------------------------------------------
 // K0: per-column pre-pass
 // ------------------------------------------------------------------------------------------------
-// Two shapes of the pre-pass kernel, the same code: 1 024 threads x 4 elements each (16 waves: the fastest way through
-// ONE column, and what the library runs everywhere), and 256 threads x 16 elements (4 waves, one per SIMD, 96 VGPRs: a
+// Three shapes of the pre-pass kernel, the same code: 1 024 threads x 4 (or 8) elements each (16 waves: the fastest way
+// through ONE column, and what the library runs on single-round launches), 256 threads x 16 elements (4 waves, one per SIMD, 96 VGPRs: a
 // workgroup that fits a CU as soon as ONE workgroup of a running pair kernel retires, where the 1 024-thread shape needs
 // all four SIMDs' registers, i.e. an EMPTY CU).  The small shape was built in round 4 to let the later chunks of the
 // pipelined host path sort beside the pair kernel; measured, that overlap makes the call longer (both kernels are bound
 // by vector issue; icikt_capi.cpp, upload_and_prepare), so it is kept as an option of the debug plan (k0=1) and a test.
-constexpr int K0_THREADS = 1024;   // the large shape (and what the shared scratch arrays are sized for)
+// A third shape, 512 threads x 8 elements (8 waves, 128 VGPRs, no spills): TWO workgroups -- two columns -- fit a CU (16
+// waves, the register file, 2 x 74.5 KB of its 160 KB of LDS), so one column's dependent passes (each waits on a global
+// round trip) run under the other's.  That pays when the launch has more columns than the device has CUs; a launch of
+// one round is fastest with the 1 024-thread workgroup.  The host picks (icikt_k0plan.h: k0_pick_shape; plan key k0=2).
+// Static LDS per workgroup as the compiler lays it out (bitsets for the longest column, 65 535 rows; per-wave scratch by
+// the shape's waves; a sort area of 1.5 tiles): large 76 576 B, large8 125 728 B, small 76 192 B, pair 76 320 B, wide 66 080 B.
+constexpr int K0_THREADS = 1024;   // the large shape
 constexpr int K0_THREADS_SMALL = 256;
+constexpr int K0_THREADS_PAIR = 512;
+constexpr int K0_WORDS = 1024;     // words of a bitset over the rows of the longest column the tuned shapes take (65 535)
+constexpr int K0_LDS_PAIR_MAX = 80 * 1024;   // what a workgroup of the pair shape may use: half a CU's LDS
 #ifndef ICIKT_K0_MIN_WAVES
 #define ICIKT_K0_MIN_WAVES 4   // waves per SIMD the pre-pass is compiled for: 4 = one 1 024-thread workgroup per CU (<= 128 VGPRs)
 #endif
@@ -403,17 +412,22 @@ __device__ inline void k0_tie_program(const unsigned long long* gf, uint16_t* E,
 template <bool WIDE, int NT, int E>
 __device__ __forceinline__ void k0_prepare_body(const PrepView& pv, const double* __restrict__ X, int64_t ld, int col_begin,
                                                 const MaskSpec& ms, uint8_t* __restrict__ keep) {
-  static_assert((NT == K0_THREADS || NT == K0_THREADS_SMALL) && (E == 4 || E == 8 || E == 16), "pre-pass shapes");
+  static_assert((NT == K0_THREADS || NT == K0_THREADS_SMALL || NT == K0_THREADS_PAIR) && (E == 4 || E == 8 || E == 16), "pre-pass shapes");
   constexpr int TILE = NT * E;                      // elements of the LDS-resident sort tile
   constexpr int NW = NT / 64;                       // waves of the workgroup
-  __shared__ long long sh_ll[K0_THREADS];           // (scratch sized for either shape: a 1 024-word bitset lives here in phase 3)
-  __shared__ int sh_i[K0_THREADS];
-  __shared__ unsigned long long sh_bits_lds[1024];  // fill-group bitset, W <= 1024 words
-  __shared__ unsigned long long sh_st_lds[1028];    // phase 1: the min reduction; phase 3: group starts, n + 1 <= 65 536 bits
+  constexpr int NI = (8 * NW > 32) ? 8 * NW : 32;   // ints of scratch: eight per wave (the statistics), the tie program's 17
+  static_assert(3 * NW <= K0_WORDS && TPROG_WIN * 2 + 2048 * 4 + TPROG_LIST * 4 <= (TILE + TILE / 2) * 8, "pre-pass scratch");
+  __shared__ long long sh_ll[K0_WORDS];             // phase 3: the bitset of the groups of >= 2 rows; three words per wave at the end
+  __shared__ int sh_i[NI];
+  __shared__ unsigned long long sh_bits_lds[K0_WORDS];  // fill-group bitset, W <= 1024 words
+  __shared__ unsigned long long sh_st_lds[K0_WORDS + 4];    // phase 1: the min reduction; phase 3: group starts, n + 1 <= 65 536 bits
   unsigned long long* const sh_bits = WIDE ? pv.k0_bits + (size_t)blockIdx.x * 2 * (size_t)(pv.Wp + 1) : sh_bits_lds;
   unsigned long long* const sh_st = WIDE ? sh_bits + (pv.Wp + 1) : sh_st_lds;
-  __shared__ unsigned long long sh_sort[TILE + TILE / 2];  // 48 KB: the sort tile, later the rec staging area
-  __shared__ uint16_t sh_bigpre[1024];              // phase 3: tie groups of >= 2 rows that start in the words before w
+  __shared__ unsigned long long sh_sort[TILE + TILE / 2];  // 48 KB (96 KB: E = 8 with 1 024 threads): the sort tile, later the rec staging area
+  __shared__ uint16_t sh_bigpre[K0_WORDS];          // phase 3: tie groups of >= 2 rows that start in the words before w
+  static_assert(NT != K0_THREADS_PAIR ||
+                sizeof(sh_ll) + sizeof(sh_i) + sizeof(sh_bits_lds) + sizeof(sh_st_lds) + sizeof(sh_sort) + sizeof(sh_bigpre) <= (size_t)K0_LDS_PAIR_MAX,
+                "two workgroups of the pair shape share a CU's 160 KB of LDS");
   unsigned long long* sh_tk = sh_sort;                                      // sort tile: keys
   uint32_t* sh_ti = reinterpret_cast<uint32_t*>(sh_sort + TILE);         // sort tile: row indices
   uint32_t* rec_s = reinterpret_cast<uint32_t*>(sh_sort);                   // after the sort: rec by row
@@ -783,48 +797,56 @@ __device__ __forceinline__ void k0_prepare_body(const PrepView& pv, const double
     // below them; the column is then sorted again with three-word elements (full key, row) and the bitset is made from
     // those.  Equal full keys are in row order either way: the row is part of the word.
     sort_pass(std::true_type{});
+    // The sorted WORD decides most positions by itself: neighbours whose 48-bit prefixes differ are in order and start
+    // a new group, and the cna rows in front (kept out of the sort, listed in idx) are one group, the fill group, below
+    // every sorted value.  Only a position whose prefix equals a neighbour's gathers its full key -- its own, for its
+    // successor's compare as much as for its own; a continuous column gathers nothing.
     int inv = 0;
     for (int base0 = 0; base0 <= ((n >> 6) << 6); base0 += NT * K0_UB) {
-      // two dependent loads per position (the sorted word, then the value of its row): issued K0_UB positions at a time
-      uint32_t rowv[K0_UB], rowp[K0_UB];
+      // the sorted word, then -- where a prefix repeats -- the value of its row: issued K0_UB positions at a time
+      unsigned long long wv[K0_UB], we[K0_UB];   // we: the word next to the wave (first lane: in front, last lane: behind)
       double vv[K0_UB], vp[K0_UB];
+      bool samep[K0_UB], need[K0_UB];            // the prefix equals the predecessor's; the full key is wanted
 #pragma unroll
       for (int u = 0; u < K0_UB; ++u) {
         const int k = base0 + u * NT + tid;
-        // (the ascending order: the cna rows kept out of the sort, listed in idx by the key pass, then the sorted words)
-        // (one load either way: the low half of a sorted word or a listed row, both below 65 536)
-        const auto row_at = [&](int q) -> uint32_t {
-          const uint32_t* w = (q < cna) ? idx + q : reinterpret_cast<const uint32_t*>(keys + (q - cna));
-          return *w & 0xFFFFu;
-        };
-        rowv[u] = (k < n) ? row_at(k) : 0u;
-        rowp[u] = (lane == 0 && k > 0 && k < n) ? row_at(k - 1) : 0u;   // a wave's first lane: its predecessor too
+        const int ke = (lane == 0) ? k - 1 : k + 1;
+        wv[u] = (k >= cna && k < n) ? keys[k - cna] : 0ull;
+        we[u] = ((lane == 0 || lane == 63) && k >= cna && k < n && ke >= cna && ke < n) ? keys[ke - cna] : 0ull;
       }
 #pragma unroll
       for (int u = 0; u < K0_UB; ++u) {
         const int k = base0 + u * NT + tid;
-        vv[u] = (k < n) ? col[rowv[u]] : 0.0;
-        vp[u] = (lane == 0 && k > 0 && k < n) ? col[rowp[u]] : 0.0;
+        const unsigned long long p = wv[u] >> 16;
+        unsigned long long pp = __shfl_up(p, 1, 64), pn = __shfl_down(p, 1, 64);
+        if (lane == 0) pp = we[u] >> 16;
+        if (lane == 63) pn = we[u] >> 16;
+        const bool sorted = k >= cna && k < n;                  // the position holds a sorted word
+        samep[u] = sorted && k > cna && pp == p;
+        need[u] = samep[u] || (sorted && k + 1 < n && pn == p);
+        vv[u] = need[u] ? col[(uint32_t)wv[u] & 0xFFFFu] : 0.0;
+        vp[u] = (lane == 0 && samep[u]) ? col[(uint32_t)we[u] & 0xFFFFu] : 0.0;   // a wave's first lane: its predecessor too
       }
 #pragma unroll
       for (int u = 0; u < K0_UB; ++u) {
         if (base0 + u * NT <= ((n >> 6) << 6)) {   // (uniform over the workgroup)
           const int k = base0 + u * NT + tid;
           unsigned long long fk = 0ull;
-          if (k < n) {
+          if (need[u]) {
             double v = vv[u];
             if (v != v || mask_excluded(ms, v)) v = fill;
             fk = sortable_key(v);
-            if (k >= cna) idx[k] = rowv[u];
           }
-          unsigned long long prev = __shfl_up(fk, 1, 64);
-          if (lane == 0 && k > 0 && k < n) {
+          if (k >= cna && k < n) idx[k] = (uint32_t)wv[u] & 0xFFFFu;
+          unsigned long long prev = __shfl_up(fk, 1, 64);   // (read only where samep: the predecessor gathered its key then)
+          if (lane == 0 && samep[u]) {
             double v = vp[u];
             if (v != v || mask_excluded(ms, v)) v = fill;
             prev = sortable_key(v);
           }
-          const bool st = (k <= n) && (k == 0 || k == n || prev != fk);
-          inv |= (k > 0 && k < n && prev > fk) ? 1 : 0;
+          // k < cna: inside the fill group; k == cna: the first sorted value, above fill (cna > 0 only when fill < min)
+          const bool st = (k <= n) && (k == 0 || k == n || (k >= cna && (!samep[u] || prev != fk)));
+          inv |= (samep[u] && prev > fk) ? 1 : 0;
           const unsigned long long b = __ballot(st);
           if (lane == 0 && (k >> 6) <= (n >> 6)) sh_st[k >> 6] = b;
         }
@@ -1098,6 +1120,14 @@ __global__ void __launch_bounds__(K0_THREADS, ICIKT_K0_WAVES_SMALL)   // (bounds
 k0_prepare_small(PrepView pv, const double* __restrict__ X, int64_t ld, int col_begin, const MaskSpec ms, uint8_t* __restrict__ keep) {
   k0_prepare_body<false, K0_THREADS_SMALL, K0_TILE / K0_THREADS_SMALL>(pv, X, ld, col_begin, ms, keep);
 }
+// two columns in flight on a CU: 512 threads x 8 elements, the 4 096-element tile.  Compiled for four waves per SIMD -- two
+// workgroups of eight waves on a CU's four SIMDs -- so it may use 128 VGPRs, and it must not spill: a spilled build of two
+// workgroups per CU (64 VGPRs) was what lost 8 % on single-round launches.  Every column length: 9 000 present values
+// are two full tiles, a 1 024-element sub-tile and one merge level more through the global scratch than large8 needs.
+__global__ void __launch_bounds__(K0_THREADS_PAIR, ICIKT_K0_MIN_WAVES)
+k0_prepare_pair(PrepView pv, const double* __restrict__ X, int64_t ld, int col_begin, const MaskSpec ms, uint8_t* __restrict__ keep) {
+  k0_prepare_body<false, K0_THREADS_PAIR, K0_TILE / K0_THREADS_PAIR>(pv, X, ld, col_begin, ms, keep);
+}
 
 // ------------------------------------------------------------------------------------------------
 // K0x: rebuild rec / hirow / tgroups of a column from its order and gflag
@@ -1262,14 +1292,16 @@ k0_mask(PrepView pv, const double* __restrict__ X, int64_t ld, int col_begin) {
 // (every launcher first drops whatever error an earlier, unrelated HIP call of the calling thread left behind: the
 //  hipGetLastError() after the launch must report THIS launch)
 hipError_t launch_k0(const PrepView& pv, const double* dX, int64_t ld, int col_begin, int ncols, const MaskSpec* msp,
-                     uint8_t* keep, int small_shape, hipStream_t s) {
+                     uint8_t* keep, int shape, hipStream_t s) {
   (void)hipGetLastError();
   MaskSpec ms{};
   if (msp) ms = *msp;
   if (pv.wide)
     hipLaunchKernelGGL(k0_prepare_wide, dim3(ncols), dim3(K0_THREADS), 0, s, pv, dX, ld, col_begin, ms, keep);
-  else if (small_shape)   // 4 waves per column: fits beside a running pair kernel (the later chunks of the pipelined host path)
+  else if (shape == 1)   // 4 waves per column: fits beside a running pair kernel (the later chunks of the pipelined host path)
     hipLaunchKernelGGL(k0_prepare_small, dim3(ncols), dim3(K0_THREADS_SMALL), 0, s, pv, dX, ld, col_begin, ms, keep);
+  else if (shape == 2)   // 8 waves per column, two columns per CU
+    hipLaunchKernelGGL(k0_prepare_pair, dim3(ncols), dim3(K0_THREADS_PAIR), 0, s, pv, dX, ld, col_begin, ms, keep);
   else if (pv.npow2 >= 2 * K0_TILE)
     hipLaunchKernelGGL(k0_prepare_large8, dim3(ncols), dim3(K0_THREADS), 0, s, pv, dX, ld, col_begin, ms, keep);
   else

@@ -126,7 +126,7 @@ def one_case(ctx, rng, case):
     if FAM:
         env = {"np": "", "pend": "", "half": rng.choice(["", "", "", "0", "1"]), "tgmax": rng.choice(["", "", "-1", "300"])}
     if R4:
-        env["k0"] = rng.choice(["", "0", "1"])
+        env["k0"] = rng.choice(["", "0", "1", "2"])
         # round 4, second half: the joint-tie modes of long tie groups (list / count / row) and SOLO steps, forced apart
         env["list"] = rng.choice(["", "", "0", "2", "20"])
         env["solo"] = rng.choice(["", "", "0"])
