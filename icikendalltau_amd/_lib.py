@@ -30,7 +30,8 @@ HEADERS = [os.path.join(_ROOT, "include", "icikt.h"), os.path.join(_PKG, "csrc",
            os.path.join(_PKG, "csrc", "icikt_wave.h"), os.path.join(_PKG, "csrc", "icikt_host.h"),
            os.path.join(_PKG, "csrc", "icikt_transfer.h"), os.path.join(_PKG, "csrc", "icikt_colsort.h"),
            os.path.join(_PKG, "csrc", "icikt_blocks.h"), os.path.join(_PKG, "csrc", "icikt_select.h"),
-           os.path.join(_PKG, "csrc", "icikt_keys.h"), os.path.join(_PKG, "csrc", "icikt_k0plan.h")]
+           os.path.join(_PKG, "csrc", "icikt_keys.h"), os.path.join(_PKG, "csrc", "icikt_k0plan.h"),
+           os.path.join(_PKG, "csrc", "icikt_k1plan.h")]
 
 # include/icikt.h
 SUCCESS = 0

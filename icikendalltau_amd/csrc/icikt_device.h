@@ -7,28 +7,14 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "icikt_k1plan.h"   // ColStats, and the pair kernel's LDS layout and option word (K1_*, k1_*, ICIKT_CNT_BYTES)
+
 namespace icikt {
 
 constexpr int ICIKT_PERSPECTIVE_LOCAL_ = 0;  // == ICIKT_PERSPECTIVE_LOCAL
 constexpr int ICIKT_CNT_FIELDS_ = 11;        // == ICIKT_CNT_FIELDS
 
-// Per-column result of the pre-pass (K0).
-struct ColStats {
-  int32_t nna;       // missing rows
-  int32_t ngroups;   // distinct values after the fill (unique(), kendallc.cpp:234-235)
-  int32_t tfill;     // size of the fill group (missing rows + rows equal to min-0.1); 0 if nna == 0
-  int32_t maxgroup;  // largest tie group: size << 16 | its first ascending position
-  uint32_t s0, s1, s2;  // count_rank_tie sums in wrapping int32: t(t-1), t(t-1)(t-2), t(t-1)(2t+5)
-  uint32_t ntg;      // tie groups of size >= 2 (length of the column's tgroups list)
-  long long e0, e1, e2;  // the same sums exactly
-  double fill;           // min - 0.1
-  int32_t nexcl;         // rows excluded by the caller's global_na rule (MaskSpec): exclude_loc of R/utils.R:1-23.
-                         // == nna unless the data hold NaN and NaN is not in global_na
-  int32_t flags;         // bit 0 COL_ODD_TIE: some tie group of >= 2 rows starts at an ODD ascending position;
-                         // bits 8..31: what STREAMING the column costs a pair kernel task, in half hot steps (2 per 64-row hot
-                         // step, 3 per MIXED / SOLO / GROUP step): the cost-weighted pair blocks of the multi-device driver
-};
-constexpr int COL_ODD_TIE = 1;
+constexpr int COL_ODD_TIE = 1;   // ColStats::flags
 __host__ __device__ inline uint32_t col_stream_cost(const ColStats& st) { return (uint32_t)st.flags >> 8; }
 
 // tie-program entry: rows of the step | kind << 7 | closes << 9 | n0 << 10 (MIXED: rows of its first sub-step)
@@ -70,12 +56,6 @@ struct PairRaw {
 
 constexpr int K1_CNT_MIN_GROUPS = 8;        // columns too long for the half-wave kernels: girow is written, and count mode used, above this many tie groups
 constexpr uint16_t GIROW_NONE = 0xFFFFu;   // PrepView::girow: the row is its own tie group
-// bytes of a counter of count mode (k1_pairs): 2 -- two to a dword, twice the tie groups per LDS byte -- or 4 (a build
-// option for measurements: -DICIKT_CNT_BYTES=4)
-#ifndef ICIKT_CNT_BYTES
-#define ICIKT_CNT_BYTES 2
-#endif
-static_assert(ICIKT_CNT_BYTES == 2 || ICIKT_CNT_BYTES == 4, "counter width");
 
 // Device pointers + sizes of the prepared matrix (HBM layout).
 static_assert(sizeof(ColStats) == 72, "ColStats is 9 words of a column's meta record");
@@ -148,54 +128,6 @@ struct PrepView {
   uint32_t* hi32;                 // [S][n_pad]  per row: last position of its tie group
   unsigned long long* k0_bits;    // [chunk][2][Wp + 1]  K0's group-start and fill bitsets (LDS holds them up to 65 535 rows)
 };
-
-// one pair per wave: bytes of the counts of `seen` (loc 64 x 16 x u8, lb 64 x u32, hist 64 x u32, locg 64 x 4 x u16)
-constexpr int K1_TL_BYTES = 1024 + 256 + 256 + 512 + 64;   // (+ 64: the closed-form tail reuses the area as a u16 prefix over Wp <= 1 025 words)
-
-// half-wave kernels: bytes of a pair's prefix slots (32 lanes x one aligned slot of 8 u16 -- 16 u16 above 8 words per
-// lane)
-__host__ __device__ inline int k1_half_pre(int half_items) { return 32 * (half_items > 8 ? 16 : 8) * 2; }
-
-// half-wave K1 kernels exist for 1..7, 9, 11, 13 and 15 words per lane of a half's prefix rebuild: n <= 30 656 (the packed
-// in-step compares of those kernels need positions -- the guard position 64 W included -- below 2^15).  An EVEN number of
-// words per lane from 8 on puts the lanes' words at a stride of 64 / 128 bytes, an 8- / 16-way LDS bank conflict per read
-// (8 words measured at half the speed of one pair per wave), so such columns run the next odd kernel.  (Round 2 measured
-// 11 and 13 words per lane at 2 waves per SIMD -- the LDS state with `pend` allowed no more -- and did not keep them;
-// without `pend` they run 4 waves per SIMD.)
-constexpr int ICIKT_HALF_ITEMS_MAX = 15;
-__host__ __device__ inline int k1_half_items(int Wp) {
-  const int hi = (Wp + 31) >> 5;
-  return (hi >= 8 && (hi & 1) == 0) ? hi + 1 : hi;
-}
-
-// Stride (in 64-bit words) of a pair's LDS / pend arrays in K1, shared by the kernel and the host plan.  The
-// arrays are padded so that the hot steps' prefix rebuilds run without predicates:
-//  * half-wave kernels: 32 lanes x half_items words;
-//  * one pair per wave: the Wp words, rounded up to a multiple of 8 (two words are read at a time, and the u16 array
-//    `ppre` of that length must end on a 16-byte boundary; an owner of the two-level counts has 16 words whatever the
-//    length, and the owners past the last word own nothing).
-__host__ __device__ inline int k1_lds_stride(int Wp, int half_items) {
-  if (half_items > 0) return 32 * half_items;
-  return (Wp + 7) & ~7;
-}
-
-// The pair kernel's option word (`opts` of launch_k1 and k1_pairs; one int as a kernel argument): packed by the host's
-// launch plan (plan_k1, launch_pair_tasks in icikt_capi.cpp), read by the kernel, both through the names below
-// (a flag is tested as `opts & K1_OPT_...`, a field read through its accessor).
-constexpr int K1_OPT_HALF = 1;          // bit 0: half-wave hot step (one pair per 32-lane half, 32-row sub-steps)
-constexpr int K1_OPT_ROW_ONLY = 2;      // bit 1: row mode only (joint ties of a long group neither from a list nor from counters)
-constexpr int K1_OPT_HALF_LAYOUT = 4;   // bit 2: two long-column pairs of a whole-wave kernel take the singleton region in the
-                                        // half layout (one pair per 32-lane half, 32-row sub-steps, the half-wave in-step chain)
-constexpr int K1_OPT_NO_SOLO = 8;       // bit 3: no SOLO steps
-constexpr int K1_OPT_SEG_SHIFT = 4;     // bits 4..5: log2 of the segments a half-wave task is cut in (1, 2 or 4)
-constexpr int K1_OPT_LIST_SHIFT = 8, K1_OPT_LIST_MASK = 0x3FF;   // bits 8..17: list mode's reach, in tie groups of the gathered column
-constexpr int K1_OPT_CNT_SHIFT = 18;    // bits 18 and up: entries of a pair's counter table (count mode); 0: none
-__host__ __device__ constexpr int k1_opt_segments(int opts) { return 1 << ((opts >> K1_OPT_SEG_SHIFT) & 3); }
-__host__ __device__ constexpr int k1_opt_tg_list(int opts) { return (opts >> K1_OPT_LIST_SHIFT) & K1_OPT_LIST_MASK; }
-__host__ __device__ constexpr int k1_opt_cnt_cap(int opts) { return opts >> K1_OPT_CNT_SHIFT; }
-__host__ __device__ constexpr int k1_opt_pack_segments(int split) { return (split == 4 ? 2 : split == 2 ? 1 : 0) << K1_OPT_SEG_SHIFT; }
-__host__ __device__ constexpr int k1_opt_pack_tg_list(int tg_list) { return tg_list << K1_OPT_LIST_SHIFT; }
-__host__ __device__ constexpr int k1_opt_pack_cnt_cap(int entries) { return entries << K1_OPT_CNT_SHIFT; }
 
 // ms: cells to exclude while reading dX (nullptr: NaN = missing, nothing else); keep: optional [n_samp][n] bytes,
 // 1 = not excluded (the reference's `keep = t(!exclude_loc)`, R/kendalltau.R:417)

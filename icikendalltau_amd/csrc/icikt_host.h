@@ -16,6 +16,7 @@
 #include "icikt_blocks.h"
 #include "icikt_device.h"
 #include "icikt_k0plan.h"
+#include "icikt_k1plan.h"
 #include "icikt_keys.h"
 #include "icikt_transfer.h"
 
@@ -208,25 +209,9 @@ struct icikt_ctx {
     DevBuf<unsigned long long> keys, red;
   } diag;
 
-  // launch-plan overrides of the pair kernel (icikt_debug_set_plan; -1 = the library's choice)
-  struct PlanOverride {
-    int np = -1, pend = -1, wpb = -1, half = -1, grid_mult = -1, grid_cap = -1, hyb = -1;
-    bool has_tgmax = false;
-    int tgmax = 0;
-    int waves = -1;     // half-wave kernels: waves per CU the counter tables may cost the launch down to (default: none)
-    int merge = -1;     // pipelined host entries: 1 = the pairs in ONE launch behind the last chunk, 0 = a launch per chunk, whatever the pair count
-    int split = -1;     // half-wave kernels: segments per task (1 | 2 | 4), whatever the launch's size
-    int solo = -1;      // 0: SOLO steps of the tie program run as MIXED steps (with the in-step chains)
-    int list = -1;      // list mode (range counts per listed tie group) up to this many tie groups: count mode takes over above
-    long long tkblock = -1;   // icikt_topk_*, icikt_edges_*, icikt_class_medians_*, icikt_quantiles_*: pairs a block (whole combn rows, or a slice of the class list) may hold (default: the library's budget)
-    int medlds = -1;          // icikt_class_medians_*, icikt_class_matrix_*: partners up to which the select kernel gathers a sample's keys into LDS (default: MEDIAN_STAGE_MAX)
-    int qbatch = -1;          // icikt_quantiles_*: targets the select runs per batch (default: QUANT_BATCH_MAX)
-    long long padjtile = -1;  // icikt_padjust_*, icikt_anosim_*: keys of a wave's tile of the sort (default: padj_tile's choice)
-    long long anoperms = -1;  // icikt_anosim_*: labellings per upload (default: ANO_BATCH_BYTES of labels)
-    int anostrip = -1;        // icikt_anosim_*: columns of a workgroup of the permutation kernel (default: ANO_STRIP_DEFAULT)
-    int hcgrid = -1;          // icikt_hclust_*: workgroups of the rescan kernel (default: min(S, HCLUST_GRID_MAX))
-    bool verbose = false;
-  } plan_ov;
+  // launch-plan overrides of the pair kernel (icikt_debug_set_plan; icikt_k1plan.h)
+  using PlanOverride = icikt::host::PlanOverride;
+  PlanOverride plan_ov;
 
   // timing
   // per kernel id a pool of HIP event pairs: several timed launches per step accumulate without a host stall
