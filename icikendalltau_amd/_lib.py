@@ -25,7 +25,8 @@ SOURCES = [os.path.join(_PKG, "csrc", f) for f in ("icikt_kernels.hip", "icikt_p
                                                        "icikt_padjust.hip", "icikt_capi_padjust.cpp",
                                                        "icikt_mst.hip", "icikt_capi_mst.cpp",
                                                        "icikt_hclust.hip", "icikt_capi_hclust.cpp",
-                                                       "icikt_anosim.hip", "icikt_capi_anosim.cpp")]
+                                                       "icikt_anosim.hip", "icikt_capi_anosim.cpp",
+                                                       "icikt_cross.hip", "icikt_capi_cross.cpp")]
 HEADERS = [os.path.join(_ROOT, "include", "icikt.h"), os.path.join(_PKG, "csrc", "icikt_device.h"),
            os.path.join(_PKG, "csrc", "icikt_wave.h"), os.path.join(_PKG, "csrc", "icikt_host.h"),
            os.path.join(_PKG, "csrc", "icikt_transfer.h"), os.path.join(_PKG, "csrc", "icikt_colsort.h"),
@@ -93,6 +94,7 @@ EXPORTS = (
     "icikt_mst_f64", "icikt_mst_in", "icikt_mst_csc",
     "icikt_hclust_f64", "icikt_hclust_in", "icikt_hclust_csc",
     "icikt_anosim_f64", "icikt_anosim_in", "icikt_anosim_csc",
+    "icikt_cross_f64", "icikt_cross_in",
 )
 
 # icikt_input: the caller's matrix as a typed, strided view (ICIKT_DTYPE_*, ICIKT_ORDER_*)
@@ -391,6 +393,11 @@ def lib():
                                    ctypes.c_double, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]
     L.icikt_anosim_f64.argtypes = [c_vp, c_vp, c_i64, c_i64, c_i64, c_vp, c_int, c_int, c_int, c_int, c_u32, c_vp, c_int,
                                    c_vp, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]
+    # (two matrices: the twins are spelled out)
+    cross_tail = [c_i64, c_i64, c_i64, c_vp, c_int, c_int, c_int, c_int, c_int, c_u32, c_int, c_vp, c_vp, c_vp, c_vp, c_vp,
+                  c_vp]
+    L.icikt_cross_f64.argtypes = [c_vp, c_vp, c_i64, c_vp, c_i64] + cross_tail
+    L.icikt_cross_in.argtypes = [c_vp, ctypes.POINTER(InputView), ctypes.POINTER(InputView)] + cross_tail
     L.icikt_multi_rank_phase_ms.argtypes = [c_vp, c_int, ctypes.POINTER(ctypes.c_double)]
     L.icikt_multi_ranks_used.argtypes = [c_vp]
     L.icikt_debug_step_stats.argtypes = [c_vp, c_vp, c_int]
@@ -694,6 +701,47 @@ class Context:
         self._chk(fn(self._h, *xargs, *gna[1:], k, *codes, int(bool(continuity)), flags, int(bool(scale_max)), _ptr(idx),
                      _ptr(vals), _ptr(n_valid), _ptr(mx), _ptr(rc5)), fname)
         return idx, vals, n_valid, float(mx[0]), rc5
+
+    def cross(self, query, reference, k=None, want_matrix=True, global_na=None, perspective="global",
+              alternative="two.sided", continuity=False, flags: int = 0, scale_max=True):
+        """Every column of `query` (n_feat x Sq) with every column of `reference` (n_feat x Sr) and nothing else
+        (icikt_cross_in): the two matrices are read where they lie (input_view; they may differ in dtype and order; a
+        sparse matrix is densified), global_na as matrix() takes it, applied to both.  want_matrix: the five Sq x Sr
+        matrices; k: every query's k reference columns with the largest raw, in topk()'s order (raw descending by the
+        doubles' bits, ties by the smaller reference index, an NA pair is no partner).  Returns (out5 [5, Sq, Sr]: cor,
+        raw, pvalue, taumax, completeness, or None; idx [Sq, k] int32 reference column indices, -1 padded, or None;
+        vals5 [5, Sq, k], NA_real_ padded, or None; n_valid [Sq] or None; max_taumax: the largest taumax of the
+        rectangle, cor's denominator; reason_counts [5] over the rectangle).  A column that occurs in both matrices is a
+        partner like any other.  The argument checks are the library's: a bad k, more than 65 535 columns in all or
+        no output at all raises IciktError."""
+        def dense(X):
+            return csc_view(X).toarray() if is_sparse(X) else X
+        if self.f64_entries:
+            query, reference = (np.asfortranarray(dense(X), dtype=np.float64) for X in (query, reference))
+        qa, qv, n_feat, Sq, flags = _view_arg(dense(query), flags)
+        ra, rv, n_feat_r, Sr, flags = _view_arg(dense(reference), flags)
+        if n_feat != n_feat_r:
+            raise ValueError(f"`query` has {n_feat} rows and `reference` {n_feat_r}: the two must share their features")
+        gna, codes, mx, rc5 = _select_args(global_na, perspective, alternative)
+        alloc = pinned_empty if (flags & FLAG_HOST_PINNED) else np.empty
+        total = Sq + (Sq & 1) + Sr
+        fits = total <= TOPK_MAX_SAMPLES      # (the library refuses the others before it writes)
+        out5 = alloc((5, Sq, Sr) if fits else (5, 0, 0), dtype=np.float64) if want_matrix else None
+        idx = vals = n_valid = None
+        kk = 0
+        if k is not None:
+            kk = int(k)
+            room = kk if 0 <= kk <= TOPK_MAX else 0
+            idx = alloc((Sq, room), dtype=np.int32)
+            vals = alloc((5, Sq, room), dtype=np.float64)
+            n_valid = np.zeros(Sq, dtype=np.int32)
+        if self.f64_entries:
+            fn, fname, xargs = lib().icikt_cross_f64, "icikt_cross_f64", (_ptr(qa), qv.ld, _ptr(ra), rv.ld)
+        else:
+            fn, fname, xargs = lib().icikt_cross_in, "icikt_cross_in", (ctypes.byref(qv), ctypes.byref(rv))
+        self._chk(fn(self._h, *xargs, n_feat, Sq, Sr, *gna[1:], kk, *codes, int(bool(continuity)), flags,
+                     int(bool(scale_max)), _ptr(out5), _ptr(idx), _ptr(vals), _ptr(n_valid), _ptr(mx), _ptr(rc5)), fname)
+        return out5, idx, vals, n_valid, float(mx[0]), rc5
 
     def class_medians(self, X, cls=None, n_class=1, global_na=None, perspective="global", alternative="two.sided",
                       continuity=False, flags: int = 0, scale_max=True):

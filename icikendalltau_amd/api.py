@@ -65,6 +65,13 @@ class HipEngine:
         return self._select_ctx().topk(data_matrix, k, global_na, perspective, alternative, continuity,
                                        self.flags | flags, scale_max)
 
+    def cross(self, query, reference, k=None, want_matrix=True, global_na=None, perspective="global",
+              alternative="two.sided", continuity=False, flags=0, scale_max=True):
+        """The query x reference rectangle, its matrices and / or every query's k best reference columns, on the device
+        (icikt_cross_f64): Context.cross' contract."""
+        return self._select_ctx().cross(query, reference, k, want_matrix, global_na, perspective, alternative,
+                                        continuity, self.flags | flags, scale_max)
+
     def edges(self, data_matrix, min_raw=None, max_pvalue=None, min_completeness=None, absolute=False, max_edges=0,
               global_na=None, perspective="global", alternative="two.sided", continuity=False, flags=0, scale_max=True):
         """Every pair past the bounds, compacted on the device (icikt_edges_f64): Context.edges' contract."""
@@ -802,6 +809,124 @@ def ici_kendalltau_topk(data_matrix, k, global_na=(float("nan"), float("inf"), 0
     for q, key in enumerate(_TOPK_KEYS):
         res[key] = vals[q]
     res["n_valid"] = n_valid
+    res["max_taumax"] = max_taumax
+    res["run_time"] = t_diff
+    return res
+
+
+# --------------------------------------------------------------------------------------------------
+# ici_kendalltau_cross: query samples against a reference cohort (R's cor(x, y) for ICI-Kt; no counterpart in the
+# reference)
+# --------------------------------------------------------------------------------------------------
+def _cross_topk_numpy(mats5, k):
+    """The selection of icikt_cross_f64 from five Sq x Sr matrices (cor, raw, pvalue, taumax, completeness): per query
+    row the reference columns whose raw is not NA, by raw descending in the order of the doubles' bits (-0.0 below
+    +0.0), ties by the smaller index; padding -1 / NA_real_.  Returns (idx [Sq, k], vals5 [5, Sq, k], n_valid [Sq])."""
+    mats5 = [np.ascontiguousarray(m, dtype=np.float64) for m in mats5]
+    raw = mats5[1]
+    Sq, Sr = raw.shape
+    idx = np.full((Sq, k), -1, dtype=np.int32)
+    vals = np.empty((5, Sq, k), dtype=np.float64)
+    vals.view(np.uint64)[...] = _NA_REAL_BITS
+    n_valid = np.zeros(Sq, dtype=np.int32)
+    bits = raw.view(np.uint64)
+    sign = (bits >> np.uint64(63)).astype(bool)
+    key = np.where(sign, ~bits, bits | np.uint64(1 << 63))
+    refs = np.arange(Sr)
+    for q in range(Sq):
+        cand = refs[~np.isnan(raw[q])]
+        sel = cand[np.lexsort((cand, ~key[q, cand]))[:k]]     # ~key ascending = key descending, then the index
+        m = len(sel)
+        n_valid[q] = m
+        idx[q, :m] = sel
+        for f in range(5):
+            vals[f, q, :m] = mats5[f][q, sel]
+    return idx, vals, n_valid
+
+
+def _cross_numpy(eng, query, reference, global_na, perspective, scale_max, alternative, continuity):
+    """The rectangle on an engine without a cross method (the CPU tests' checker engines): ``ici_kendalltau`` on the
+    stacked matrix with ``include_only`` = the rectangle's pairs -- so ``cor`` is scaled by the rectangle's largest
+    taumax -- and the [query, reference] block of its matrices.  Returns (mats5 [5, Sq, Sr], max_taumax, run_time)."""
+    Sq, Sr = query.shape[1], reference.shape[1]
+    if Sq == 0 or Sr == 0:
+        return np.empty((5, Sq, Sr)), -math.inf, 0.0
+    stacked = np.hstack([np.asarray(query, dtype=np.float64), np.asarray(reference, dtype=np.float64)])
+    qn, rn = [f"q{i}" for i in range(Sq)], [f"r{j}" for j in range(Sr)]     # (the callers' names may repeat across the two)
+    full = ici_kendalltau(stacked, global_na=global_na, perspective=perspective, scale_max=scale_max, diag_good=True,
+                          include_only=[list(np.repeat(qn, Sr)), rn * Sq], alternative=alternative,
+                          continuity=continuity, colnames=qn + rn, engine=eng)
+    mats5 = np.stack([np.asarray(full[key])[:Sq, Sq:] for key in _TOPK_KEYS])
+    have = _na_rm(mats5[3].ravel())
+    return mats5, (float(have.max()) if have.size else -math.inf), full["run_time"]
+
+
+def ici_kendalltau_cross(query, reference, k=None, return_matrix=True, global_na=(float("nan"), float("inf"), 0),
+                         perspective="global", scale_max=True, alternative="two.sided", continuity=False,
+                         query_names=None, reference_names=None, engine=None):
+    """ICI-Kendall-tau of every sample (column) of ``query`` with every sample of ``reference`` -- a new batch against
+    a reference cohort -- and nothing else: no pair within either matrix is computed.
+
+    ``query`` (features x Sq) and ``reference`` (features x Sr) share their rows; column names are required for both
+    (``query_names=`` / ``reference_names=`` for bare ndarrays).  ``global_na``, ``perspective``, ``alternative`` and
+    ``continuity`` are ``ici_kendalltau``'s and apply to both matrices.  float32 and integer matrices of either memory
+    order are read where they lie; a sparse matrix is densified on the host (``toarray()``).  On the HIP engine the
+    rectangle runs on the device (icikt_cross_f64); Sq + Sr is at most 65 535 (one less when Sq is odd).
+
+    ``cor`` is ``raw`` over the largest ``taumax`` of the rectangle's pairs when ``scale_max`` -- what
+    ``ici_kendalltau(include_only=<those pairs>)`` scales by -- else ``raw``.  With ``k`` (an integer in 1 .. 256) every
+    query gets its ``k`` reference samples with the largest ``raw``: ``raw`` descending, ties by the smaller reference
+    index; a pair whose ``raw`` is NA is no partner.  A sample that occurs in both matrices is a partner like any other
+    (it is usually its own nearest reference sample).  The reference's warning is raised once per pair of reasons 2-4.
+
+    Returns a dict.  With ``return_matrix``: ``cor, raw, pvalue, taumax, completeness`` as Sq x Sr tables, rows the
+    query samples.  With ``k``: ``indices`` (Sq x k reference column indices, -1 where a query has fewer than k
+    partners), ``neighbors`` (their names, None padded), ``topk_cor, topk_raw, topk_pvalue, topk_taumax,
+    topk_completeness`` (Sq x k, NA padded) and ``n_valid`` (Sq); ``formats.cross_topk_to_csr`` turns them into a
+    sparse graph.  Always: ``query_names``, ``reference_names``, ``max_taumax`` and ``run_time``.  An empty ``query``
+    or ``reference`` gives empty tables.
+    """
+    if k is not None:
+        if isinstance(k, (bool, np.bool_)) or not isinstance(k, (int, np.integer)) or not 1 <= int(k) <= _lib.TOPK_MAX:
+            raise ValueError(f"`k` must be None or an integer in 1 .. {_lib.TOPK_MAX}")
+        k = int(k)
+    elif not return_matrix:
+        raise ValueError("nothing to return: give `k`, or leave `return_matrix` set")
+    query, qnames = _as_matrix(query, query_names, "query", keep_dtype=True)
+    reference, rnames = _as_matrix(reference, reference_names, "reference", keep_dtype=True)
+    if query.shape[0] != reference.shape[0]:
+        raise ValueError(f"`query` has {query.shape[0]} rows (features) and `reference` has {reference.shape[0]}: "
+                         "the two must share their rows")
+    Sq, Sr = query.shape[1], reference.shape[1]
+    eng = engine or _default_engine()
+    out5 = idx = vals = n_valid = None
+    if hasattr(eng, "cross"):
+        if _host_masks(global_na):
+            query, _ = _mask_on_host(query, global_na)
+            reference, global_na = _mask_on_host(reference, global_na)
+        t1 = time.perf_counter()
+        out5, idx, vals, n_valid, max_taumax, rcounts = eng.cross(query, reference, k, return_matrix, global_na, perspective,
+                                                                   alternative, continuity, 0, scale_max)
+        t_diff = time.perf_counter() - t1
+        _warn_pairs(rcounts)
+    else:
+        out5, max_taumax, t_diff = _cross_numpy(eng, query, reference, global_na, perspective, scale_max, alternative,
+                                                continuity)
+        if k is not None:
+            idx, vals, n_valid = _cross_topk_numpy(out5, k)
+    res = {}
+    if return_matrix:
+        for f, key in enumerate(_TOPK_KEYS):
+            res[key] = pd.DataFrame(out5[f], index=list(qnames), columns=list(rnames)) if pd is not None else out5[f]
+    if k is not None:
+        names_arr = np.asarray(list(rnames) + [None], dtype=object)
+        res["indices"] = idx
+        res["neighbors"] = names_arr[idx]    # (-1 picks the None behind the names)
+        for f, key in enumerate(_TOPK_KEYS):
+            res["topk_" + key] = vals[f]
+        res["n_valid"] = n_valid
+    res["query_names"] = list(qnames)
+    res["reference_names"] = list(rnames)
     res["max_taumax"] = max_taumax
     res["run_time"] = t_diff
     return res

@@ -1,8 +1,9 @@
 // icikt_blocks.h -- which pairs a selection entry (icikt_topk_*, icikt_edges_*, icikt_class_medians_*,
 // icikt_class_matrix_*, icikt_quantiles_*, icikt_padjust_*, icikt_mst_*, icikt_anosim_*, icikt_hclust_*) computes, and
 // in which blocks: whole rows of the combn triangle (all nine), or slices of the within-class pair list
-// (icikt_class_medians_* with several classes).  Plain C++, no device header: tests/test_blocks_host.py compiles it
-// alone.  Host memory is O(S) for the classes and O(block) for a slice.
+// (icikt_class_medians_* with several classes), or whole query rows of the query x reference rectangle (icikt_cross_*).
+// Plain C++, no device header: tests/test_blocks_host.py and tests/test_cross_blocks_host.py compile it alone.  Host
+// memory is O(S) for the classes and O(block) for a slice or a run of rectangle rows.
 #ifndef ICIKT_BLOCKS_H
 #define ICIKT_BLOCKS_H
 
@@ -36,6 +37,25 @@ inline std::vector<std::pair<int, int>> cut_rows(int64_t S, int64_t budget) {
   }
   return blocks;
 }
+
+// query rows [a, b) of the Sq x Sr rectangle per block (Sr pairs a row): the largest run from a within the budget, at
+// least one row; a run of several rows ends on an even row, for cut_rows' reason
+inline std::vector<std::pair<int, int>> cut_rect_rows(int64_t Sq, int64_t Sr, int64_t budget) {
+  std::vector<std::pair<int, int>> blocks;
+  if (Sr <= 0) return blocks;
+  const int64_t fit = std::max<int64_t>(1, budget / Sr);
+  int64_t a = 0;
+  while (a < Sq) {
+    int64_t b = std::min(Sq, a + fit);
+    if (b < Sq && (b & 1) && b - a >= 2) --b;
+    blocks.emplace_back((int)a, (int)b);
+    a = b;
+  }
+  return blocks;
+}
+// the device column of reference column 0: the query columns come first, and the reference starts on an even column
+// (the pre-pass's tables are interleaved in blocks of two columns), behind one padding column when Sq is odd
+inline int64_t rect_ref_col(int64_t Sq) { return Sq + (Sq & 1); }
 
 // the members of the classes, class by class in class-index order, ascending sample index inside a class
 struct ClassRuns {
@@ -112,7 +132,8 @@ inline ClassIndex class_index(const int32_t* cls, int64_t S) {
 }
 
 // one block of a call: pairs [begin, begin + count) of the call's pair order -- rows [row_first, row_last) of the
-// combn triangle, or (pi != null) a slice of the class list as sample indices, valid until the next block is asked for
+// combn triangle, or (pi != null) a slice of the class list as sample indices, or (pi != null, row_last > row_first)
+// query rows [row_first, row_last) of the rectangle as device columns; pi / pj are valid until the next block is asked for
 struct PairBlock {
   int64_t begin = 0, count = 0;
   int row_first = 0, row_last = 0;
@@ -143,6 +164,21 @@ class PairBlocks {
     p.block_max = std::max<int64_t>(1, std::min(total, p.budget_));
     return p;
   }
+  // whole query rows of the Sq x Sr rectangle, pair p = q * Sr + r of the call's order, `budget` pairs (2^30 at most)
+  // per block of several rows (cut_rect_rows).  A block's pi / pj are (q, rect_ref_col(Sq) + r), generated into the
+  // block's host vectors as next() is called: sorted by (pi, pj), so the task list pairs the rows 2a and 2a + 1 over
+  // every reference column (build_units' sorted branch)
+  static PairBlocks rect(int64_t Sq, int64_t Sr, int64_t budget) {
+    PairBlocks p;
+    p.rect_ = true;
+    p.Sq_ = Sq;
+    p.Sr_ = Sr;
+    p.total = Sq * Sr;
+    p.rows_ = cut_rect_rows(Sq, Sr, std::min<int64_t>(budget, (int64_t)1 << 30));
+    p.n_blocks = (int64_t)p.rows_.size();
+    for (const auto& b : p.rows_) p.block_max = std::max(p.block_max, (int64_t)(b.second - b.first) * Sr);
+    return p;
+  }
   int64_t S = 0, total = 0, n_blocks = 0, block_max = 1;   // S: of rows(); block_max: the largest block's pairs (at least 1)
   // the next block into *b; false behind the last one
   bool next(PairBlock* b) {
@@ -150,6 +186,19 @@ class PairBlocks {
     if (cr_) {
       next_slice(*cr_, &cur_, budget_, &pi_, &pj_);
       *b = PairBlock{done_, (int64_t)pi_.size(), 0, 0, pi_.data(), pj_.data()};
+    } else if (rect_) {
+      const int first = rows_[at_].first, last = rows_[at_].second;
+      const size_t count = (size_t)(last - first) * (size_t)Sr_;
+      const int32_t col0 = (int32_t)rect_ref_col(Sq_);
+      pi_.resize(count);
+      pj_.resize(count);
+      size_t p = 0;
+      for (int q = first; q < last; ++q)
+        for (int32_t r = 0; r < (int32_t)Sr_; ++r, ++p) {
+          pi_[p] = (int32_t)q;
+          pj_[p] = col0 + r;
+        }
+      *b = PairBlock{(int64_t)first * Sr_, (int64_t)count, first, last, pi_.data(), pj_.data()};
     } else {
       const int first = rows_[at_].first, last = rows_[at_].second;
       *b = PairBlock{row_offset(S, first), row_offset(S, last) - row_offset(S, first), first, last, nullptr, nullptr};
@@ -163,6 +212,8 @@ class PairBlocks {
   std::vector<std::pair<int, int>> rows_;
   const ClassRuns* cr_ = nullptr;
   PairCursor cur_;
+  bool rect_ = false;
+  int64_t Sq_ = 0, Sr_ = 0;
   int64_t budget_ = 0, at_ = 0, done_ = 0;
   std::vector<int32_t> pi_, pj_;
 };

@@ -734,7 +734,10 @@ int upload_and_prepare(icikt_ctx* c, const MatrixSrc& X, int64_t n_feat, int64_t
   };
   c->chunk_col_end.clear();
   c->xfer.csc_pending = false;
-  const size_t nel = (size_t)std::max<int64_t>(n_feat * n_samp, 1);
+  // (X.dst_col > 0: the view is one of several sources of the device matrix and lands at that column; its caller has
+  //  reserved d_X for all of them before the first upload -- a reserve that grows drops what the buffer holds)
+  const int64_t at = X.dst_col;
+  const size_t nel = (size_t)std::max<int64_t>(n_feat * (at + n_samp), 1);
   HIPCHK(c, c->d_X.reserve(nel));
   int rc = timer_begin(c, ICIKT_K_PREPARE, flags);
   if (rc) return rc;
@@ -775,7 +778,7 @@ int upload_and_prepare(icikt_ctx* c, const MatrixSrc& X, int64_t n_feat, int64_t
     for (int64_t c0 = col_begin, step = first_chunk; c0 < col_end && e == hipSuccess && rc == 0; c0 += step, step = chunk, ++k) {
       const int64_t nc = std::min<int64_t>(step, col_end - c0);
       hipEvent_t ev = nullptr;
-      e = up.copy(k, c->d_X.p + (size_t)c0 * (size_t)n_feat, c0, nc, &ev);
+      e = up.copy(k, c->d_X.p + (size_t)(at + c0) * (size_t)n_feat, c0, nc, &ev);
       if (pipelined) {
         // the chunk's pre-pass on the pre-pass stream; an event of its own tells the pair kernel's stream when
         if (e == hipSuccess) e = hipStreamWaitEvent(c->prep_stream, ev, 0);
@@ -786,7 +789,7 @@ int upload_and_prepare(icikt_ctx* c, const MatrixSrc& X, int64_t n_feat, int64_t
         //  LONGER, 11.76 against 11.61 ms staged, 11.24 against 11.13 pinned (profiles/r04_ab_pipe_k0.log) -- both kernels
         //  are bound by vector issue, so overlapping them gains nothing, and the small shape takes 0.80 ms for the 1 024
         //  columns where the large one takes 0.65.)
-        if (e == hipSuccess) rc = chunk_prepass(c0, c0 + nc, c->prep_stream);
+        if (e == hipSuccess) rc = chunk_prepass(at + c0, at + c0 + nc, c->prep_stream);
         if ((size_t)k >= c->ev_chunk.size()) {
           hipEvent_t ne = nullptr;
           if (e == hipSuccess) e = hipEventCreateWithFlags(&ne, hipEventDisableTiming);
@@ -798,7 +801,7 @@ int upload_and_prepare(icikt_ctx* c, const MatrixSrc& X, int64_t n_feat, int64_t
         if (e == hipSuccess && rc == 0 && on_chunk) rc = (*on_chunk)((size_t)k, c0 + nc);
       } else {
         if (e == hipSuccess) e = hipStreamWaitEvent(c->stream, ev, 0);
-        if (e == hipSuccess) rc = chunk_prepass(c0, c0 + nc, nullptr);
+        if (e == hipSuccess) rc = chunk_prepass(at + c0, at + c0 + nc, nullptr);
       }
     }
     if (e == hipSuccess && rc == 0) e = up.finish();   // (a CSC view: the scatter kernel's error record comes back behind the last chunk)
@@ -820,7 +823,7 @@ int upload_and_prepare(icikt_ctx* c, const MatrixSrc& X, int64_t n_feat, int64_t
       if (rc) { if (pipelined) (void)hipStreamSynchronize(c->prep_stream); return rc; }
     }
   } else if (ncols > 0 && prepass == kPrepassFull) {
-    rc = prepare_launch(c, c->d_X.p, n_feat, col_begin, col_end);  // n_feat == 0: statistics of empty columns
+    rc = prepare_launch(c, c->d_X.p, n_feat, at + col_begin, at + col_end);  // n_feat == 0: statistics of empty columns
     if (rc) return rc;
   }
   return timer_end(c, ICIKT_K_PREPARE, flags);

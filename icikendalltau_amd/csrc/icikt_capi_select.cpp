@@ -1,6 +1,6 @@
 // icikt_capi_select.cpp -- the host side the nine selection entries share (icikt_topk_*, icikt_edges_*,
 // icikt_class_medians_*, icikt_class_matrix_*, icikt_quantiles_*, icikt_padjust_*, icikt_mst_*, icikt_anosim_*,
-// icikt_hclust_*; declared in icikt_host.h): their common checks, the run of a call's blocks through the pair engine,
+// icikt_hclust_*; declared in icikt_host.h) and icikt_cross_* runs its rectangle through: their common checks, the run of a call's blocks through the pair engine,
 // and the steps several of them take over the one set of key planes (icikt_ctx::sel) -- the fold that keeps a block's
 // raw as keys, the radix sort, the download of d_red.  The driver allocates nothing of size S^2: each block's records
 // are folded by the entry's kernel before the next block overwrites them.
@@ -85,16 +85,21 @@ int select_run(SelectCall& s, PairBlocks& blocks, const SelectSteps& steps) {
       };
       // a call that is one block takes the matrix entries' way in: copies, pre-pass and pair kernel pipelined by
       // column chunks (upload_prepare_pairs); several blocks: the matrix first, then block after block
-      const bool one = blocks.n_blocks == 1;
+      // (an entry with an upload step of its own brings the matrix first and takes the second way)
+      const bool one = blocks.n_blocks == 1 && !steps.upload;
       r = advance();
       if (!r && one) r = set_pairs();
       if (r) return r;
-      r = prepare_alloc(c, s.n_feat, s.n_samp, s.n_samp, s.n_samp);
-      if (r) return r;
-      c->k0_mask = &s.ms;
-      c->k0_keep = nullptr;
-      r = one ? upload_prepare_pairs(c, s.X, s.n_feat, s.n_samp, flags)
-              : upload_and_prepare(c, s.X, s.n_feat, s.n_samp, 0, s.n_samp, flags);
+      if (steps.upload) {
+        r = steps.upload();
+      } else {
+        r = prepare_alloc(c, s.n_feat, s.n_samp, s.n_samp, s.n_samp);
+        if (r) return r;
+        c->k0_mask = &s.ms;
+        c->k0_keep = nullptr;
+        r = one ? upload_prepare_pairs(c, s.X, s.n_feat, s.n_samp, flags)
+                : upload_and_prepare(c, s.X, s.n_feat, s.n_samp, 0, s.n_samp, flags);
+      }
       c->k0_mask = nullptr;
       if (r) return r;
       c->prepared = true;

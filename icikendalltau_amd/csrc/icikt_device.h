@@ -1,5 +1,5 @@
 // icikt_device.h -- structures, layouts and launcher declarations shared by the device units (icikt_prepass.hip,
-// icikt_kernels.hip, icikt_epilogue.hip, icikt_cor.hip, icikt_diag.hip, icikt_topk.hip, icikt_edges.hip, icikt_medians.hip, icikt_quantiles.hip, icikt_classmat.hip, icikt_padjust.hip, icikt_mst.hip, icikt_hclust.hip, icikt_anosim.hip) and the C-ABI
+// icikt_kernels.hip, icikt_epilogue.hip, icikt_cor.hip, icikt_diag.hip, icikt_topk.hip, icikt_edges.hip, icikt_medians.hip, icikt_quantiles.hip, icikt_classmat.hip, icikt_padjust.hip, icikt_mst.hip, icikt_hclust.hip, icikt_anosim.hip, icikt_cross.hip) and the C-ABI
 // host side (icikt_capi*.cpp, icikt_multi.cpp).  Internal; the public boundary is include/icikt.h.
 #ifndef ICIKT_DEVICE_H
 #define ICIKT_DEVICE_H
@@ -165,6 +165,20 @@ hipError_t launch_topk_merge(const TopkLists& L, const double* out4, int S, int 
 // idx [S][k] (-1 padded), out5k [5][S][k] (NA_real_ padded), n_valid [S] (may be null); red: launch_out_stats' record
 hipError_t launch_topk_finish(const TopkLists& L, const unsigned long long* red, int S, int scale_max, int32_t* idx,
                               double* out5k, int32_t* n_valid, hipStream_t s);
+// ---- query x reference rectangle (icikt_cross.hip) ----
+// out4: the records of query rows [row_first, row_first + n_rows) of the Sq x Sr rectangle, query-major.  Writes the
+// rows' final lists: idx [Sq][k] (-1 padded), planes 1 .. 4 of planes [5][Sq][k] (NA_real_ padded), n_valid [Sq].
+hipError_t launch_cross_topk(const double* out4, int Sr, int k, int row_first, int n_rows, long long Sq, int32_t* idx,
+                             double* planes, int32_t* n_valid, hipStream_t s);
+// out4: the records of pairs [begin, begin + count) of the rectangle's P pairs -> planes 1 .. 4 of planes [5][P]
+hipError_t launch_cross_planes(const double* out4, long long count, long long begin, long long P, double* planes,
+                               hipStream_t s);
+// plane 0 (cor) of planes [5][P] from plane 1 (raw) and red, launch_out_stats' record, once it is final; idx (may be
+// null): [P], a negative entry marks a padding slot (NA_real_)
+hipError_t launch_cross_cor(const unsigned long long* red, int scale_max, const int32_t* idx, long long P, double* planes,
+                            hipStream_t s);
+// n cells of NaN: the padding column behind an odd number of query columns
+hipError_t launch_cross_pad(double* col, int n, hipStream_t s);
 // ---- pairs past a threshold, compacted in combn order (icikt_edges.hip) ----
 struct EdgeRule {              // == icikt_edge_rule: a NaN bound is no bound
   double min_raw, max_pvalue, min_completeness;

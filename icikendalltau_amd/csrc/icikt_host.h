@@ -127,6 +127,13 @@ struct icikt_ctx {
     DevBuf<double> vals, out;
   } topk;
 
+  // query x reference rectangle (icikt_cross_f64): the five planes [5][Sq Sr] when the matrices are asked for, and the
+  // queries' lists (idx [Sq][k], out [5][Sq][k], n_valid [Sq])
+  struct CrossBufs {
+    DevBuf<double> planes, out;
+    DevBuf<int32_t> idx, n_valid;
+  } cross;
+
   // pairs past a threshold (icikt_edges_f64): a block's ballot words, tile counts and tile bases, the running total
   // (word 0 of `total`), the degrees and the planes of the kept edges
   struct EdgeBufs {
@@ -285,7 +292,7 @@ int check_pair_args(icikt_ctx* c, const char* who, const MatrixSrc& X, int64_t n
                     const int32_t* pi, const int32_t* pj, int64_t* n_pairs, const void* out, bool out5,
                     int perspective, int alternative);
 
-// ---- the selection entries (icikt_topk_*, icikt_edges_*, icikt_class_medians_*, icikt_quantiles_*, icikt_class_matrix_*, icikt_padjust_*, icikt_mst_*, icikt_anosim_*, icikt_hclust_*): one driver, icikt_capi_select.cpp ----
+// ---- the selection entries (icikt_topk_*, icikt_edges_*, icikt_class_medians_*, icikt_quantiles_*, icikt_class_matrix_*, icikt_padjust_*, icikt_mst_*, icikt_anosim_*, icikt_hclust_*) and icikt_cross_*: one driver, icikt_capi_select.cpp ----
 // (the blocks a call runs in: icikt_blocks.h; DESIGN.md "adding a selection entry")
 // the arguments the entries share
 struct SelectArgs {
@@ -307,6 +314,8 @@ struct SelectCall {
 };
 // what an entry adds to the driver's call sequence, all on c->stream
 struct SelectSteps {
+  std::function<int()> upload;                        // (optional) the entry brings the device matrix and its pre-pass itself -- icikt_cross_*:
+                                                      // two sources -- in place of the driver's upload of s.X; the blocks then run one after the other
   std::function<int()> start;                         // its own device state, before the first block
   std::function<int(const PairBlock&)> fold;          // its kernel over the block that is in c->d_out4 / c->d_reasons (the
                                                       // driver has run launch_out_stats_accum inside the same timer pair)

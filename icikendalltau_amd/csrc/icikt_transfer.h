@@ -95,6 +95,7 @@ struct MatrixSrc {
   bool sparse = false, null = false;         // null: the caller passed no view at all (the entry checks say so)
   icikt_input v{};                           // dense: element type, order, leading dimension in elements
   icikt_csc_input s{};                       // sparse
+  int64_t dst_col = 0;                       // the device column its column 0 lands at (icikt_cross_*: the second of two sources of one device matrix)
   MatrixSrc() = default;
   MatrixSrc(const icikt_input& d) : v(d) {}  // (a dense view converts: the callers that only know dense matrices)
   static MatrixSrc dense(const icikt_input* p) { MatrixSrc m; if (p) m.v = *p; else m.null = true; return m; }

@@ -7,6 +7,7 @@
 * ``cor_matrix_2_long_df`` / ``long_df_2_cor_matrix``: the reference's converters between the square result
   matrices and the long data.frame storage form (R/reshaping.R:15-68).
 * ``topk_to_csr``: the result of ``ici_kendalltau_topk`` as a sparse samples x samples kNN graph (needs scipy).
+* ``cross_topk_to_csr``: the top-k lists of ``ici_kendalltau_cross`` as a sparse query x reference graph (needs scipy).
 * ``edges_to_coo``: the result of ``ici_kendalltau_edges`` as a sparse samples x samples matrix (needs scipy).
 * ``mst_to_linkage`` / ``mst_cut``: the result of ``ici_kendalltau_mst`` as a ``scipy.cluster.hierarchy`` linkage matrix
   (single linkage), and as the network's component labels at any cut-off (neither needs scipy).
@@ -265,6 +266,30 @@ def topk_to_csr(result, value="cor"):
     real = np.arange(k)[None, :] < n_valid[:, None]
     indptr = np.concatenate([[0], np.cumsum(n_valid)])
     return sp.csr_matrix((vals[real], idx[real].astype(np.int32), indptr), shape=(S, S))
+
+
+def cross_topk_to_csr(result, value="cor", n_reference=None):
+    """The top-k part of the dict ``ici_kendalltau_cross`` returns (called with ``k``) as an Sq x Sr
+    ``scipy.sparse.csr_matrix``: row q holds ``result[value]`` of query q's partners at their reference column indices
+    (in the list's order); padded slots are dropped, so the matrix has ``sum(n_valid)`` stored entries.  Sr is taken from
+    ``result["reference_names"]`` unless ``n_reference`` gives it.  scipy is optional for the package and needed
+    here."""
+    try:
+        import scipy.sparse as sp
+    except ImportError as e:
+        raise ImportError("cross_topk_to_csr needs scipy (optional for icikendalltau_amd, required for this converter)") from e
+    if value not in ("cor", "raw", "pvalue", "taumax", "completeness"):
+        raise ValueError("`value` must be one of cor, raw, pvalue, taumax, completeness")
+    if "indices" not in result:
+        raise ValueError("the result holds no top-k lists: call ici_kendalltau_cross with `k`")
+    idx = np.asarray(result["indices"])
+    vals = np.asarray(result["topk_" + value], dtype=np.float64)
+    n_valid = np.asarray(result["n_valid"], dtype=np.int64)
+    Sq, k = idx.shape
+    Sr = int(n_reference) if n_reference is not None else len(result["reference_names"])
+    real = np.arange(k)[None, :] < n_valid[:, None]
+    indptr = np.concatenate([[0], np.cumsum(n_valid)])
+    return sp.csr_matrix((vals[real], idx[real].astype(np.int32), indptr), shape=(Sq, Sr))
 
 
 # --------------------------------------------------------------------------------------------------

@@ -679,6 +679,44 @@ int icikt_anosim_f64(icikt_ctx *ctx, const double *X, int64_t n_feat, int64_t n_
                      int64_t *n_pairs, int64_t *w2, int64_t *nw, int64_t *n_ge, int64_t *n_undefined,
                      int64_t *class_w2, int64_t *class_nw, double *max_taumax, int64_t *reason_counts);
 
+/* ---- query samples against a reference cohort: the query x reference rectangle ---------------------------------------
+ *
+ * Every column of Q (n_feat x n_query, leading dimension ld_query) with every column of R (n_feat x n_reference,
+ * ld_reference): pair (q, r) is column q of Q with column r of R, and the call's pair order is query-major,
+ * p = q n_reference + r.  No pair within Q or within R is computed.  global_na, perspective, alternative and continuity
+ * apply to both matrices, as in icikt_matrix_f64.  A column that occurs in both matrices is a partner like any other.
+ *   values       a pair's raw, pvalue, taumax and completeness are bit for bit what icikt_matrix_f64 reports for the same
+ *                two columns of the stacked matrix [Q R] with the explicit pair list (q, n_query + r);
+ *                cor = scale_max ? raw / max(taumax, na.rm = TRUE) : raw, the maximum over the RECTANGLE (-Inf when no
+ *                pair has a taumax): what icikt_matrix_f64 scales by when that list is its pair list
+ *   out5         (optional) [5][n_query][n_reference]: cor, raw, pvalue, taumax, completeness.  Device memory for the
+ *                planes: 40 bytes per pair of the rectangle
+ *   top-k        (optional: any of idx, out5k, n_valid; then 1 <= k <= ICIKT_TOPK_MAX) every query's k reference columns
+ *                with the largest raw in icikt_topk_f64's strict order -- raw descending by the doubles' bits (-0.0 below
+ *                +0.0), ties by the smaller reference index; a pair whose raw is NA is no partner.  idx [n_query][k]:
+ *                reference column indices 0 .. n_reference - 1, -1 padded; out5k [5][n_query][k]: the five values,
+ *                R's NA_real_ padded; n_valid [n_query]: real partners per query
+ *   max_taumax   (optional) the scale's denominator; reason_counts (optional): [5] pairs of the rectangle per reason code
+ * At least one output must be given.  n_query + n_reference, plus one when n_query is odd (the device matrix holds the
+ * query columns, a padding column that makes the reference start on an even column, then the reference), is at most
+ * ICIKT_TOPK_MAX_SAMPLES (ICIKT_E_INVALID beyond, the message names the limit); n_feat as icikt_topk_f64 takes it.
+ * n_query == 0 or n_reference == 0: an empty result (every list padding), no error.  Device memory beside the planes:
+ * the prepared matrix of all columns, one block's buffers (whole query rows within the tkblock budget) and
+ * 44 n_query k bytes of lists.  The state the call leaves behind (none) and the refusal of bad arguments before
+ * anything -- the context or an output -- is touched: as icikt_topk_f64.  With ICIKT_FLAG_TIMING the folds are accounted
+ * under ICIKT_K_EPILOGUE.
+ * icikt_cross_in: the same on typed views of the two matrices (icikt_input, below), which may differ in element type
+ * and order. */
+int icikt_cross_f64(icikt_ctx *ctx, const double *Q, int64_t ld_query, const double *R, int64_t ld_reference,
+                    int64_t n_feat, int64_t n_query, int64_t n_reference, const double *global_na, int n_global_na,
+                    int k, int perspective, int alternative, int continuity, uint32_t flags, int scale_max,
+                    double *out5, int32_t *idx, double *out5k, int32_t *n_valid, double *max_taumax,
+                    int64_t *reason_counts);
+int icikt_cross_in(icikt_ctx *ctx, const icikt_input *Q, const icikt_input *R, int64_t n_feat, int64_t n_query,
+                   int64_t n_reference, const double *global_na, int n_global_na, int k, int perspective,
+                   int alternative, int continuity, uint32_t flags, int scale_max, double *out5, int32_t *idx,
+                   double *out5k, int32_t *n_valid, double *max_taumax, int64_t *reason_counts);
+
 /* ---- several GPUs behind one call (what the R glue binds when n_gpu > 1) ----------------------
  *
  * Replaces the reference's worker fan-out, computation$split_fun(split_comparisons, ici_split, ...)
