@@ -477,14 +477,32 @@ def _matrix_call(fn, handle, chk, X, global_na, pi, pj, perspective, alternative
     return out5, (keep.view(np.bool_) if keep is not None else None), rc5
 
 
-def _select_args(global_na, perspective, alternative):
-    """What the nine selection entries (topk, edges, class_medians, class_matrix, quantiles, padjust, mst, anosim,
-    hclust) share: the arguments (global_na, n_global_na) -- valid while the first element, the array behind them, is
-    alive --, (perspective, alternative) as codes, the max_taumax cell and reason_counts [5]."""
-    gna = np.ascontiguousarray([] if global_na is None else np.atleast_1d(global_na), dtype=np.float64)
-    persp = PERSPECTIVE.get(perspective, perspective if isinstance(perspective, int) else -1)
-    return ((gna, _ptr(gna) if gna.size else None, int(gna.size)), (persp, ALTERNATIVE.get(alternative, ALT_OTHER)),
-            np.full(1, -np.inf), np.zeros(5, dtype=np.int64))
+class _SelectCall:
+    """What the ten selection entries (topk, cross, edges, class_medians, class_matrix, quantiles, padjust, mst, hclust,
+    anosim) share around their own arguments.  An instance holds a resolved entry (what Context._entry returns; the
+    array behind its arguments stays alive with it), n_samp and flags as that entry sees them, and alloc: the allocator
+    of the result arrays that are pinned when the call says so.  Calling it makes the checked call fn(ctx, <X>,
+    global_na, n_global_na, *before, perspective, alternative, continuity, flags[, scale_max], *after, max_taumax,
+    reason_counts) and returns (max_taumax, reason_counts [5]); scale_max None: the entry has no such argument."""
+
+    def __init__(self, ctx, entry):
+        self.ctx = ctx
+        self.fn, self.fname, self.xargs, _n_feat, self.n_samp, self.flags, self._keep = entry
+        self.alloc = pinned_empty if (self.flags & FLAG_HOST_PINNED) else np.empty
+
+    def tree_room(self):
+        """The S - 1 slots of mst's edges and hclust's merges (the library refuses more samples before it writes)."""
+        return max(self.n_samp - 1, 0) if self.n_samp <= TOPK_MAX_SAMPLES else 0
+
+    def __call__(self, global_na, perspective, alternative, continuity, scale_max, before=(), after=()):
+        gna = np.ascontiguousarray([] if global_na is None else np.atleast_1d(global_na), dtype=np.float64)
+        persp = PERSPECTIVE.get(perspective, perspective if isinstance(perspective, int) else -1)
+        scale = () if scale_max is None else (int(bool(scale_max)),)
+        mx, rc5 = np.full(1, -np.inf), np.zeros(5, dtype=np.int64)
+        self.ctx._chk(self.fn(self.ctx._h, *self.xargs, _ptr(gna) if gna.size else None, int(gna.size), *before, persp,
+                              ALTERNATIVE.get(alternative, ALT_OTHER), int(bool(continuity)), self.flags, *scale, *after,
+                              _ptr(mx), _ptr(rc5)), self.fname)
+        return float(mx[0]), rc5
 
 
 def _class_arg(cls, n_samp):
@@ -691,16 +709,13 @@ class Context:
         padded; vals5 [5, S, k]: cor, raw, pvalue, taumax, completeness, NA_real_ padded; n_valid [S]; max_taumax;
         reason_counts [5]).  A column's partners are ordered by raw descending (by the doubles' bits: -0.0 below +0.0),
         ties by the smaller index.  The argument checks are the library's: a bad k or perspective raises IciktError."""
-        fn, fname, xargs, n_feat, n_samp, flags, _keep = self._entry("topk", X, flags)
+        sel = _SelectCall(self, self._entry("topk", X, flags))
         k = int(k)
-        gna, codes, mx, rc5 = _select_args(global_na, perspective, alternative)
-        alloc = pinned_empty if (flags & FLAG_HOST_PINNED) else np.empty
-        idx = alloc((n_samp, max(k, 0)), dtype=np.int32)
-        vals = alloc((5, n_samp, max(k, 0)), dtype=np.float64)
-        n_valid = np.zeros(n_samp, dtype=np.int32)
-        self._chk(fn(self._h, *xargs, *gna[1:], k, *codes, int(bool(continuity)), flags, int(bool(scale_max)), _ptr(idx),
-                     _ptr(vals), _ptr(n_valid), _ptr(mx), _ptr(rc5)), fname)
-        return idx, vals, n_valid, float(mx[0]), rc5
+        idx = sel.alloc((sel.n_samp, max(k, 0)), dtype=np.int32)
+        vals = sel.alloc((5, sel.n_samp, max(k, 0)), dtype=np.float64)
+        n_valid = np.zeros(sel.n_samp, dtype=np.int32)
+        return idx, vals, n_valid, *sel(global_na, perspective, alternative, continuity, scale_max, (k,),
+                                        (_ptr(idx), _ptr(vals), _ptr(n_valid)))
 
     def cross(self, query, reference, k=None, want_matrix=True, global_na=None, perspective="global",
               alternative="two.sided", continuity=False, flags: int = 0, scale_max=True):
@@ -722,26 +737,24 @@ class Context:
         ra, rv, n_feat_r, Sr, flags = _view_arg(dense(reference), flags)
         if n_feat != n_feat_r:
             raise ValueError(f"`query` has {n_feat} rows and `reference` {n_feat_r}: the two must share their features")
-        gna, codes, mx, rc5 = _select_args(global_na, perspective, alternative)
-        alloc = pinned_empty if (flags & FLAG_HOST_PINNED) else np.empty
+        if self.f64_entries:
+            fn, fname, xargs = lib().icikt_cross_f64, "icikt_cross_f64", (_ptr(qa), qv.ld, _ptr(ra), rv.ld)
+        else:
+            fn, fname, xargs = lib().icikt_cross_in, "icikt_cross_in", (ctypes.byref(qv), ctypes.byref(rv))
+        sel = _SelectCall(self, (fn, fname, (*xargs, n_feat, Sq, Sr), n_feat, Sq, flags, (qa, qv, ra, rv)))
         total = Sq + (Sq & 1) + Sr
         fits = total <= TOPK_MAX_SAMPLES      # (the library refuses the others before it writes)
-        out5 = alloc((5, Sq, Sr) if fits else (5, 0, 0), dtype=np.float64) if want_matrix else None
+        out5 = sel.alloc((5, Sq, Sr) if fits else (5, 0, 0), dtype=np.float64) if want_matrix else None
         idx = vals = n_valid = None
         kk = 0
         if k is not None:
             kk = int(k)
             room = kk if 0 <= kk <= TOPK_MAX else 0
-            idx = alloc((Sq, room), dtype=np.int32)
-            vals = alloc((5, Sq, room), dtype=np.float64)
+            idx = sel.alloc((Sq, room), dtype=np.int32)
+            vals = sel.alloc((5, Sq, room), dtype=np.float64)
             n_valid = np.zeros(Sq, dtype=np.int32)
-        if self.f64_entries:
-            fn, fname, xargs = lib().icikt_cross_f64, "icikt_cross_f64", (_ptr(qa), qv.ld, _ptr(ra), rv.ld)
-        else:
-            fn, fname, xargs = lib().icikt_cross_in, "icikt_cross_in", (ctypes.byref(qv), ctypes.byref(rv))
-        self._chk(fn(self._h, *xargs, n_feat, Sq, Sr, *gna[1:], kk, *codes, int(bool(continuity)), flags,
-                     int(bool(scale_max)), _ptr(out5), _ptr(idx), _ptr(vals), _ptr(n_valid), _ptr(mx), _ptr(rc5)), fname)
-        return out5, idx, vals, n_valid, float(mx[0]), rc5
+        return out5, idx, vals, n_valid, *sel(global_na, perspective, alternative, continuity, scale_max, (kk,),
+                                              (_ptr(out5), _ptr(idx), _ptr(vals), _ptr(n_valid)))
 
     def class_medians(self, X, cls=None, n_class=1, global_na=None, perspective="global", alternative="two.sided",
                       continuity=False, flags: int = 0, scale_max=True):
@@ -751,14 +764,12 @@ class Context:
         them.  Returns (med2 [2, S]: cor, raw -- NA_real_ for a sample without a valid partner; n_valid [S];
         max_taumax: the largest taumax of the COMPUTED pairs, cor's denominator; reason_counts [5] over those pairs).
         The argument checks are the library's: a class index out of range or a bad perspective raises IciktError."""
-        fn, fname, xargs, n_feat, n_samp, flags, _keep = self._entry("class_medians", X, flags)
-        cls_a = _class_arg(cls, n_samp)
-        gna, codes, mx, rc5 = _select_args(global_na, perspective, alternative)
-        med2 = np.empty((2, n_samp), dtype=np.float64)
-        n_valid = np.zeros(n_samp, dtype=np.int32)
-        self._chk(fn(self._h, *xargs, *gna[1:], _ptr(cls_a), int(n_class), *codes, int(bool(continuity)), flags,
-                     int(bool(scale_max)), _ptr(med2), _ptr(n_valid), _ptr(mx), _ptr(rc5)), fname)
-        return med2, n_valid, float(mx[0]), rc5
+        sel = _SelectCall(self, self._entry("class_medians", X, flags))
+        cls_a = _class_arg(cls, sel.n_samp)
+        med2 = np.empty((2, sel.n_samp), dtype=np.float64)
+        n_valid = np.zeros(sel.n_samp, dtype=np.int32)
+        return med2, n_valid, *sel(global_na, perspective, alternative, continuity, scale_max,
+                                   (_ptr(cls_a), int(n_class)), (_ptr(med2), _ptr(n_valid)))
 
     def class_matrix(self, X, cls=None, n_class=1, global_na=None, perspective="global", alternative="two.sided",
                      continuity=False, flags: int = 0, scale_max=True):
@@ -769,18 +780,16 @@ class Context:
         [S, n_class]; max_taumax: the largest taumax of ALL pairs, cor's denominator; reason_counts [5] over all
         pairs).  The arrays are views of the library's layout, the sample index fastest.  The argument checks are the
         library's: a class index out of range, more than 65 535 classes or a bad perspective raises IciktError."""
-        fn, fname, xargs, n_feat, n_samp, flags, _keep = self._entry("class_matrix", X, flags)
-        cls_a = _class_arg(cls, n_samp)
+        sel = _SelectCall(self, self._entry("class_matrix", X, flags))
+        cls_a = _class_arg(cls, sel.n_samp)
         if cls_a is None:
             n_class = 1
         n_class = int(n_class)
         room = n_class if 1 <= n_class <= 65535 else 1    # (the library refuses the others before it writes)
-        gna, codes, mx, rc5 = _select_args(global_na, perspective, alternative)
-        med2 = np.empty((2, room, n_samp), dtype=np.float64)
-        n_valid = np.zeros((room, n_samp), dtype=np.int32)
-        self._chk(fn(self._h, *xargs, *gna[1:], _ptr(cls_a), n_class, *codes, int(bool(continuity)), flags,
-                     int(bool(scale_max)), _ptr(med2), _ptr(n_valid), _ptr(mx), _ptr(rc5)), fname)
-        return med2.transpose(0, 2, 1), n_valid.T, float(mx[0]), rc5
+        med2 = np.empty((2, room, sel.n_samp), dtype=np.float64)
+        n_valid = np.zeros((room, sel.n_samp), dtype=np.int32)
+        return med2.transpose(0, 2, 1), n_valid.T, *sel(global_na, perspective, alternative, continuity, scale_max,
+                                                        (_ptr(cls_a), n_class), (_ptr(med2), _ptr(n_valid)))
 
     def quantiles(self, X, probs=(), breaks=None, cls=None, n_class=1, global_na=None, perspective="global",
                   alternative="two.sided", continuity=False, flags: int = 0, scale_max=True):
@@ -793,25 +802,23 @@ class Context:
         quantile interpolates; n_valid, n_na [n_group] int64; hist [n_group, n_bins] int64; outside [n_group, 2]:
         values below the first and above the last break; max_taumax; reason_counts [5]).  The argument checks are the
         library's: a bad prob, break, class index or perspective raises IciktError."""
-        fn, fname, xargs, n_feat, n_samp, flags, _keep = self._entry("quantiles", X, flags)
-        cls_a = _class_arg(cls, n_samp)
+        sel = _SelectCall(self, self._entry("quantiles", X, flags))
+        cls_a = _class_arg(cls, sel.n_samp)
         probs_a = np.ascontiguousarray(np.atleast_1d(np.asarray(probs, dtype=np.float64)).ravel())
         breaks_a = np.empty(0) if breaks is None else np.ascontiguousarray(np.atleast_1d(breaks), dtype=np.float64).ravel()
         n_probs, n_breaks = int(probs_a.size), int(breaks_a.size)
         n_group = 1 if cls_a is None else 3
-        gna, codes, mx, rc5 = _select_args(global_na, perspective, alternative)
         q2 = np.empty((2, n_group, n_probs), dtype=np.float64)
         order2 = np.empty((n_group, n_probs, 2), dtype=np.float64)
         n_valid = np.zeros(n_group, dtype=np.int64)
         n_na = np.zeros(n_group, dtype=np.int64)
         hist = np.zeros((n_group, max(n_breaks - 1, 0)), dtype=np.int64)
         outside = np.zeros((n_group, 2), dtype=np.int64)
-        self._chk(fn(self._h, *xargs, *gna[1:], _ptr(cls_a), int(n_class), *codes, int(bool(continuity)), flags,
-                     int(bool(scale_max)), _ptr(probs_a) if n_probs else None, n_probs,
-                     _ptr(breaks_a) if n_breaks else None, n_breaks, _ptr(q2) if n_probs else None,
-                     _ptr(order2) if n_probs else None, _ptr(n_valid), _ptr(n_na),
-                     _ptr(hist) if n_breaks > 1 else None, _ptr(outside), _ptr(mx), _ptr(rc5)), fname)
-        return q2, order2, n_valid, n_na, hist, outside, float(mx[0]), rc5
+        return q2, order2, n_valid, n_na, hist, outside, *sel(
+            global_na, perspective, alternative, continuity, scale_max, (_ptr(cls_a), int(n_class)),
+            (_ptr(probs_a) if n_probs else None, n_probs, _ptr(breaks_a) if n_breaks else None, n_breaks,
+             _ptr(q2) if n_probs else None, _ptr(order2) if n_probs else None, _ptr(n_valid), _ptr(n_na),
+             _ptr(hist) if n_breaks > 1 else None, _ptr(outside)))
 
     def padjust(self, X, method, alpha, max_table=0, global_na=None, perspective="global", alternative="two.sided",
                 continuity=False, flags: int = 0):
@@ -825,24 +832,23 @@ class Context:
         adjusted values, t = min(n_table, max_table); n_table: ALL distinct values, so n_table > max_table says the
         table is truncated (call again with room); max_taumax; reason_counts [5]).  The argument checks are the
         library's: a bad method, alpha or perspective raises IciktError."""
-        fn, fname, xargs, n_feat, n_samp, flags, _keep = self._entry("padjust", X, flags)
+        sel = _SelectCall(self, self._entry("padjust", X, flags))
         code = ADJUST.get(method, method if isinstance(method, (int, np.integer)) else -1)
         alpha_a = np.ascontiguousarray(np.atleast_1d(np.asarray(alpha, dtype=np.float64)).ravel())
         n_alpha = int(alpha_a.size)
         max_table = int(max_table)
-        room = max(0, min(max_table, n_samp * (n_samp - 1) // 2))   # (no more distinct p-values than pairs)
-        gna, codes, mx, rc5 = _select_args(global_na, perspective, alternative)
+        room = max(0, min(max_table, sel.n_samp * (sel.n_samp - 1) // 2))   # (no more distinct p-values than pairs)
         n_tests = np.zeros(2, dtype=np.int64)
         n_rej = np.zeros(max(n_alpha, 1), dtype=np.int64)
         cutoff = np.empty(max(n_alpha, 1), dtype=np.float64)
         table = np.empty((2, room), dtype=np.float64) if room else None
         n_table = np.zeros(1, dtype=np.int64)
-        self._chk(fn(self._h, *xargs, *gna[1:], *codes, int(bool(continuity)), flags, int(code),
-                     _ptr(alpha_a) if n_alpha else None, n_alpha, room if max_table >= 0 else max_table, _ptr(n_tests),
-                     _ptr(n_rej), _ptr(cutoff), _ptr(table), _ptr(n_table), _ptr(mx), _ptr(rc5)), fname)
+        tail = sel(global_na, perspective, alternative, continuity, None, (),
+                   (int(code), _ptr(alpha_a) if n_alpha else None, n_alpha, room if max_table >= 0 else max_table,
+                    _ptr(n_tests), _ptr(n_rej), _ptr(cutoff), _ptr(table), _ptr(n_table)))
         t = min(int(n_table[0]), room)
         table = table[:, :t] if room else np.empty((2, 0), dtype=np.float64)
-        return n_tests, n_rej[:n_alpha], cutoff[:n_alpha], table, int(n_table[0]), float(mx[0]), rc5
+        return n_tests, n_rej[:n_alpha], cutoff[:n_alpha], table, int(n_table[0]), *tail
 
     def mst(self, X, min_raw=None, global_na=None, perspective="global", alternative="two.sided", continuity=False,
             flags: int = 0, scale_max=True):
@@ -855,9 +861,8 @@ class Context:
         component [S] int32: the components of the candidate graph, numbered in order of their smallest sample;
         n_components; n_rounds: the Boruvka rounds run; max_taumax; reason_counts [5]) with n_tree + n_components == S.
         The argument checks are the library's: a bad perspective raises IciktError."""
-        fn, fname, xargs, n_feat, n_samp, flags, _keep = self._entry("mst", X, flags)
-        gna, codes, mx, rc5 = _select_args(global_na, perspective, alternative)
-        room = max(n_samp - 1, 0) if n_samp <= TOPK_MAX_SAMPLES else 0   # (the library refuses more samples before it writes)
+        sel = _SelectCall(self, self._entry("mst", X, flags))
+        n_samp, room = sel.n_samp, sel.tree_room()
         ti = np.empty(max(room, 1), dtype=np.int32)
         tj = np.empty(max(room, 1), dtype=np.int32)
         vals = np.empty((5, max(room, 1)), dtype=np.float64)
@@ -865,12 +870,12 @@ class Context:
         n_tree = np.zeros(1, dtype=np.int64)
         n_comp = np.zeros(1, dtype=np.int64)
         n_rounds = np.zeros(1, dtype=np.int32)
-        self._chk(fn(self._h, *xargs, *gna[1:], *codes, int(bool(continuity)), flags, int(bool(scale_max)),
-                     float("nan") if min_raw is None else float(min_raw), _ptr(ti), _ptr(tj), _ptr(vals), _ptr(n_tree),
-                     _ptr(component), _ptr(n_comp), _ptr(n_rounds), _ptr(mx), _ptr(rc5)), fname)
+        tail = sel(global_na, perspective, alternative, continuity, scale_max, (),
+                   (float("nan") if min_raw is None else float(min_raw), _ptr(ti), _ptr(tj), _ptr(vals), _ptr(n_tree),
+                    _ptr(component), _ptr(n_comp), _ptr(n_rounds)))
         m = int(n_tree[0])
         # (the library's planes are room apart: one row of vals each when room >= 1)
-        return (ti[:m], tj[:m], vals[:, :m], component[:n_samp], int(n_comp[0]), int(n_rounds[0]), float(mx[0]), rc5)
+        return ti[:m], tj[:m], vals[:, :m], component[:n_samp], int(n_comp[0]), int(n_rounds[0]), *tail
 
     def hclust(self, X, method="complete", min_raw=None, global_na=None, perspective="global", alternative="two.sided",
                continuity=False, flags: int = 0, scale_max=True):
@@ -886,11 +891,10 @@ class Context:
         clusters that are left, numbered in order of their smallest sample; n_components; max_taumax; reason_counts
         [5]) with n_merges + n_components == S.  The argument checks are the library's: an unknown method or a bad
         perspective raises IciktError."""
-        fn, fname, xargs, n_feat, n_samp, flags, _keep = self._entry("hclust", X, flags)
-        gna, codes, mx, rc5 = _select_args(global_na, perspective, alternative)
+        sel = _SelectCall(self, self._entry("hclust", X, flags))
         code = HCLUST.get(method, -1) if isinstance(method, str) else int(method)
-        room = max(n_samp - 1, 0) if n_samp <= TOPK_MAX_SAMPLES else 0   # (the library refuses more samples before it writes)
-        ma = np.empty(max(room, 1), dtype=np.int32)
+        n_samp, room = sel.n_samp, sel.tree_room()
+        ma =np.empty(max(room, 1), dtype=np.int32)
         mb = np.empty(max(room, 1), dtype=np.int32)
         msize = np.empty(max(room, 1), dtype=np.int32)
         mraw = np.empty(max(room, 1), dtype=np.float64)
@@ -898,11 +902,11 @@ class Context:
         component = np.zeros(max(n_samp, 1), dtype=np.int32)
         n_merges = np.zeros(1, dtype=np.int64)
         n_comp = np.zeros(1, dtype=np.int64)
-        self._chk(fn(self._h, *xargs, *gna[1:], *codes, int(bool(continuity)), flags, int(bool(scale_max)), code,
-                     float("nan") if min_raw is None else float(min_raw), _ptr(ma), _ptr(mb), _ptr(msize), _ptr(mraw),
-                     _ptr(mcor), _ptr(n_merges), _ptr(component), _ptr(n_comp), _ptr(mx), _ptr(rc5)), fname)
+        tail = sel(global_na, perspective, alternative, continuity, scale_max, (),
+                   (code, float("nan") if min_raw is None else float(min_raw), _ptr(ma), _ptr(mb), _ptr(msize), _ptr(mraw),
+                    _ptr(mcor), _ptr(n_merges), _ptr(component), _ptr(n_comp)))
         m = int(n_merges[0])
-        return (ma[:m], mb[:m], msize[:m], mraw[:m], mcor[:m], component[:n_samp], int(n_comp[0]), float(mx[0]), rc5)
+        return ma[:m], mb[:m], msize[:m], mraw[:m], mcor[:m], component[:n_samp], int(n_comp[0]), *tail
 
     def anosim(self, X, cls=None, n_class=1, perm_cls=None, global_na=None, perspective="global",
                alternative="two.sided", continuity=False, flags: int = 0):
@@ -916,7 +920,8 @@ class Context:
         [n_class] int64: the observed sums per class; max_taumax; reason_counts [5]).  api.anosim_statistic turns a
         (M, w2, nw) into the statistic.  The argument checks are the library's: a label out of range, more than 65 535 classes or a
         bad perspective raises IciktError."""
-        fn, fname, xargs, n_feat, n_samp, flags, _keep = self._entry("anosim", X, flags)
+        sel = _SelectCall(self, self._entry("anosim", X, flags))
+        n_samp = sel.n_samp
         cls_a = _class_arg(cls, n_samp)
         if cls_a is None:
             n_class = 1
@@ -930,7 +935,6 @@ class Context:
             n_perm = int(perm_a.shape[0])
         room = n_class if 1 <= n_class <= 65535 else 1    # (the library refuses the others before it writes)
         n_lab = 1 + (n_perm if n_perm <= ANOSIM_MAX_PERM else 0)
-        gna, codes, mx, rc5 = _select_args(global_na, perspective, alternative)
         n_pairs = np.zeros(2, dtype=np.int64)
         w2 = np.zeros(n_lab, dtype=np.int64)
         nw = np.zeros(n_lab, dtype=np.int64)
@@ -938,10 +942,10 @@ class Context:
         n_undef = np.zeros(1, dtype=np.int64)
         class_w2 = np.zeros(room, dtype=np.int64)
         class_nw = np.zeros(room, dtype=np.int64)
-        self._chk(fn(self._h, *xargs, *gna[1:], *codes, int(bool(continuity)), flags, _ptr(cls_a), n_class,
-                     _ptr(perm_a) if n_perm else None, n_perm, _ptr(n_pairs), _ptr(w2), _ptr(nw), _ptr(n_ge),
-                     _ptr(n_undef), _ptr(class_w2), _ptr(class_nw), _ptr(mx), _ptr(rc5)), fname)
-        return n_pairs, w2, nw, int(n_ge[0]), int(n_undef[0]), class_w2, class_nw, float(mx[0]), rc5
+        tail = sel(global_na, perspective, alternative, continuity, None, (),
+                   (_ptr(cls_a), n_class, _ptr(perm_a) if n_perm else None, n_perm, _ptr(n_pairs), _ptr(w2), _ptr(nw),
+                    _ptr(n_ge), _ptr(n_undef), _ptr(class_w2), _ptr(class_nw)))
+        return n_pairs, w2, nw, int(n_ge[0]), int(n_undef[0]), class_w2, class_nw, *tail
 
     def edges(self, X, min_raw=None, max_pvalue=None, min_completeness=None, absolute=False, max_edges=0,
               global_na=None, perspective="global", alternative="two.sided", continuity=False, flags: int = 0,
@@ -952,26 +956,24 @@ class Context:
         [5, m]: cor, raw, pvalue, taumax, completeness; n_edges: ALL matching pairs; degree [S] int64 or None;
         max_taumax; reason_counts [5]) with m = min(n_edges, max_edges): max_edges = 0 only counts, and n_edges >
         max_edges says the list is truncated (call again with room).  The argument checks are the library's."""
-        fn, fname, xargs, n_feat, n_samp, flags, _keep = self._entry("edges", X, flags)
+        sel = _SelectCall(self, self._entry("edges", X, flags))
+        n_samp = sel.n_samp
         max_edges = int(max_edges)
         rule = edge_rule(min_raw, max_pvalue, min_completeness, absolute)
-        gna, codes, mx, rc5 = _select_args(global_na, perspective, alternative)
         room = max(0, min(max_edges, n_samp * (n_samp - 1) // 2))   # (the library writes no slot past the triangle)
-        alloc = pinned_empty if (flags & FLAG_HOST_PINNED) else np.empty
-        ei = alloc(room, dtype=np.int32) if room else None
-        ej = alloc(room, dtype=np.int32) if room else None
-        vals = alloc((5, room), dtype=np.float64) if room else None
+        ei = sel.alloc(room, dtype=np.int32) if room else None
+        ej = sel.alloc(room, dtype=np.int32) if room else None
+        vals = sel.alloc((5, room), dtype=np.float64) if room else None
         n_edges = np.zeros(1, dtype=np.int64)
         degree = np.zeros(n_samp, dtype=np.int64) if want_degree else None
-        self._chk(fn(self._h, *xargs, *gna[1:], ctypes.byref(rule), *codes, int(bool(continuity)), flags,
-                     int(bool(scale_max)), room if max_edges >= 0 else max_edges, _ptr(ei), _ptr(ej), _ptr(vals),
-                     _ptr(n_edges), _ptr(degree), _ptr(mx), _ptr(rc5)), fname)
+        tail = sel(global_na, perspective, alternative, continuity, scale_max, (ctypes.byref(rule),),
+                   (room if max_edges >= 0 else max_edges, _ptr(ei), _ptr(ej), _ptr(vals), _ptr(n_edges), _ptr(degree)))
         m = min(int(n_edges[0]), room)
         if room:
             ei, ej, vals = ei[:m], ej[:m], vals[:, :m]
         else:
             ei, ej, vals = np.empty(0, np.int32), np.empty(0, np.int32), np.empty((5, 0), np.float64)
-        return ei, ej, vals, int(n_edges[0]), degree, float(mx[0]), rc5
+        return ei, ej, vals, int(n_edges[0]), degree, *tail
 
     def pairs_complete(self, X, pi, pj, alternative="two.sided", continuity=False, flags: int = 0,
                        want_counts: bool = False):

@@ -453,6 +453,17 @@ def _recycle(a: Sequence, n: int):
     return [a[i % len(a)] for i in range(n)]
 
 
+def _no_comparisons(include_arg="include_only"):
+    """The refusal of a call without a pair to compute (R/kendalltau.R:240-247)."""
+    return ValueError(f"No comparisons to do. Check the list of column names in `{include_arg}` vs those in the samples.")
+
+
+def _need_pairs(n_sample):
+    """All pairs of the upper triangle: fewer than two samples have none."""
+    if n_sample < 2:
+        raise _no_comparisons()
+
+
 def setup_comparisons(samples, include_only=None, diag_good=True, ncore=1, include_arg="include_only"):
     """Pair list in utils::combn order with include_only filtering; returns (i, j, core) 0-based arrays."""
     n_sample = len(samples)
@@ -505,8 +516,7 @@ def setup_comparisons(samples, include_only=None, diag_good=True, ncore=1, inclu
 
     n_todo = len(pi)
     if n_todo == 0:
-        raise ValueError("No comparisons to do. Check the list of column names in "
-                         f"`{include_arg}` vs those in the samples.")  # R/kendalltau.R:240-247
+        raise _no_comparisons(include_arg)
     n_each = int(math.ceil(n_todo / ncore))
     core = (np.arange(n_todo) // n_each + 1).astype(np.int32)  # rep(seq(1, ncore), each = n_each)
     return pi, pj, core
@@ -594,6 +604,68 @@ def _max_taumax(taumax, where):
     return float(have.max()) if have.size else -math.inf
 
 
+# -- what the selection entries (ici_kendalltau_topk ... ici_kendalltau_anosim below) share ----------------------
+_TOPK_KEYS = ("cor", "raw", "pvalue", "taumax", "completeness")
+_NA_REAL_BITS = np.uint64(0x7FF00000000007A2)   # R's NA_real_: what the library pads with
+
+
+def _select_input(data_matrix, colnames):
+    """The matrix of a selection entry after the input checks, read where it lies: (matrix, names, n_sample)."""
+    data_matrix, names = _as_matrix(data_matrix, colnames, "data_matrix", keep_dtype=True, keep_sparse=True)
+    return data_matrix, names, data_matrix.shape[1]
+
+
+def _int_arg(value, lo, hi, message):
+    """An integer in lo .. hi that is no bool, as an int; anything else is refused with `message`."""
+    if isinstance(value, (bool, np.bool_)) or not isinstance(value, (int, np.integer)) or not lo <= int(value) <= hi:
+        raise ValueError(message)
+    return int(value)
+
+
+def _timed(call):
+    """The engine call(s) of a selection entry, timed together, and the warnings of their pairs: (the last call's result
+    without its reason_counts, seconds)."""
+    t1 = time.perf_counter()
+    *out, rcounts = call()
+    t_diff = time.perf_counter() - t1
+    _warn_pairs(rcounts)
+    return out, t_diff
+
+
+def _on_device(eng, data_matrix, global_na, call):
+    """_timed(call(X, global_na)) with the matrix and global_na as the engine's selection methods take them: masked on
+    the host when the list is longer than the device rule, otherwise the caller's matrix where it lies."""
+    X, global_na = _mask_on_host(data_matrix, global_na)
+    X = _for_engine(X, eng, fortran=False)
+    return _timed(lambda: call(X, global_na))
+
+
+def _from_full(eng, data_matrix, names, global_na, perspective, scale_max, alternative, continuity, include_only=None,
+               where=None):
+    """The numpy route of an engine without the entry's method (the CPU tests' checker engines): ici_kendalltau on the
+    whole matrix.  Returns (the five S x S planes in _TOPK_KEYS' order, run_time, max_taumax over the pairs `where`
+    selects: the upper triangle unless given)."""
+    full = ici_kendalltau(data_matrix, global_na=global_na, perspective=perspective, scale_max=scale_max, diag_good=True,
+                          include_only=include_only, alternative=alternative, continuity=continuity, colnames=names,
+                          engine=eng)
+    if where is None:
+        where = np.triu_indices(len(names), k=1)
+    return [np.asarray(full[key]) for key in _TOPK_KEYS], full["run_time"], _max_taumax(full["taumax"], where)
+
+
+def _na_filled(shape):
+    """A float64 array filled with R's NA_real_."""
+    a = np.empty(shape, dtype=np.float64)
+    a.view(np.uint64)[...] = _NA_REAL_BITS
+    return a
+
+
+def _put_values(res, vals5, prefix=""):
+    """The five value columns of a selection into the result dict."""
+    for q, key in enumerate(_TOPK_KEYS):
+        res[prefix + key] = vals5[q]
+
+
 def _named_matrix(values: np.ndarray, names):
     if pd is not None:
         return pd.DataFrame(values, index=list(names), columns=list(names))
@@ -639,9 +711,7 @@ def ici_kendalltau(data_matrix, global_na=(float("nan"), float("inf"), 0), persp
         # kernels, scale_and_reshape, one copy of the five matrices back.  All pairs of the upper triangle need no
         # pair list at all; include_only / diag_good = FALSE hand over the filtered list.
         if include_only is None and diag_good:
-            if n_sample < 2:
-                raise ValueError("No comparisons to do. Check the list of column names in "
-                                 "`include_only` vs those in the samples.")  # R/kendalltau.R:240-247
+            _need_pairs(n_sample)
             pi = pj = None
         else:
             pi, pj, _core = setup_comparisons(names, include_only, diag_good, ncore=ncore)
@@ -733,8 +803,32 @@ def ici_kendalltau(data_matrix, global_na=(float("nan"), float("inf"), 0), persp
 # --------------------------------------------------------------------------------------------------
 # ici_kendalltau_topk: every sample's k nearest partners (no counterpart in the reference)
 # --------------------------------------------------------------------------------------------------
-_TOPK_KEYS = ("cor", "raw", "pvalue", "taumax", "completeness")
-_NA_REAL_BITS = np.uint64(0x7FF00000000007A2)   # R's NA_real_: what the library pads with
+def _best_per_row(mats5, k, skip_own):
+    """Per row of five matrices (cor, raw, pvalue, taumax, completeness) the k columns whose raw is not NA -- without the
+    row's own index when skip_own --, by raw descending in the order of the doubles' bits (-0.0 below +0.0), ties by the
+    smaller index; padding -1 / NA_real_.  Returns (idx [rows, k], vals5 [5, rows, k], n_valid [rows])."""
+    mats5 = [np.ascontiguousarray(m, dtype=np.float64) for m in mats5]
+    raw = mats5[1]
+    n_rows, n_cols = raw.shape
+    idx = np.full((n_rows, k), -1, dtype=np.int32)
+    vals = _na_filled((5, n_rows, k))
+    n_valid = np.zeros(n_rows, dtype=np.int32)
+    bits = raw.view(np.uint64)
+    sign = (bits >> np.uint64(63)).astype(bool)
+    key = np.where(sign, ~bits, bits | np.uint64(1 << 63))
+    cols = np.arange(n_cols)
+    for r in range(n_rows):
+        ok = ~np.isnan(raw[r])
+        if skip_own:
+            ok[r] = False
+        cand = cols[ok]
+        sel = cand[np.lexsort((cand, ~key[r, cand]))[:k]]     # ~key ascending = key descending, then the index
+        m = len(sel)
+        n_valid[r] = m
+        idx[r, :m] = sel
+        for q in range(5):
+            vals[q, r, :m] = mats5[q][r, sel]
+    return idx, vals, n_valid
 
 
 def _topk_numpy(mats5, k):
@@ -742,29 +836,7 @@ def _topk_numpy(mats5, k):
     engines without a topk method (the CPU tests' checker engines).  Per column: partners j != c whose raw is not NA,
     by raw descending in the order of the doubles' bits (-0.0 below +0.0), ties by the smaller index; padding -1 /
     NA_real_.  Returns (idx [S, k], vals5 [5, S, k], n_valid [S])."""
-    mats5 = [np.ascontiguousarray(m, dtype=np.float64) for m in mats5]
-    raw = mats5[1]
-    S = raw.shape[0]
-    idx = np.full((S, k), -1, dtype=np.int32)
-    vals = np.empty((5, S, k), dtype=np.float64)
-    vals.view(np.uint64)[...] = _NA_REAL_BITS
-    n_valid = np.zeros(S, dtype=np.int32)
-    bits = raw.view(np.uint64)
-    sign = (bits >> np.uint64(63)).astype(bool)
-    key = np.where(sign, ~bits, bits | np.uint64(1 << 63))
-    partners = np.arange(S)
-    for c in range(S):
-        ok = ~np.isnan(raw[c])
-        ok[c] = False
-        cand = partners[ok]
-        order = np.lexsort((cand, ~key[c, cand]))[:k]     # ~key ascending = key descending, then the index
-        sel = cand[order]
-        m = len(sel)
-        n_valid[c] = m
-        idx[c, :m] = sel
-        for q in range(5):
-            vals[q, c, :m] = mats5[q][c, sel]
-    return idx, vals, n_valid
+    return _best_per_row(mats5, k, skip_own=True)
 
 
 def ici_kendalltau_topk(data_matrix, k, global_na=(float("nan"), float("inf"), 0), perspective="global", scale_max=True,
@@ -782,32 +854,21 @@ def ici_kendalltau_topk(data_matrix, k, global_na=(float("nan"), float("inf"), 0
     than k partners), ``neighbors`` (their names, None padded), ``cor, raw, pvalue, taumax, completeness`` (S x k, NA
     padded), ``n_valid`` (S), ``max_taumax`` and ``run_time``.  ``formats.topk_to_csr`` turns it into a sparse graph.
     """
-    if isinstance(k, (bool, np.bool_)) or not isinstance(k, (int, np.integer)) or not 1 <= int(k) <= _lib.TOPK_MAX:
-        raise ValueError(f"`k` must be an integer in 1 .. {_lib.TOPK_MAX}")
-    k = int(k)
-    data_matrix, names = _as_matrix(data_matrix, colnames, "data_matrix", keep_dtype=True, keep_sparse=True)
-    n_sample = data_matrix.shape[1]
-    if n_sample < 2:
-        raise ValueError("No comparisons to do. Check the list of column names in "
-                         "`include_only` vs those in the samples.")  # R/kendalltau.R:240-247
+    k = _int_arg(k, 1, _lib.TOPK_MAX, f"`k` must be an integer in 1 .. {_lib.TOPK_MAX}")
+    data_matrix, names, n_sample = _select_input(data_matrix, colnames)
+    _need_pairs(n_sample)
     eng = engine or _default_engine()
     if hasattr(eng, "topk"):
-        X, global_na = _mask_on_host(data_matrix, global_na)
-        t1 = time.perf_counter()
-        idx, vals, n_valid, max_taumax, rcounts = eng.topk(_for_engine(X, eng, fortran=False), k, global_na, perspective,
-                                                           alternative, continuity, 0, scale_max)
-        t_diff = time.perf_counter() - t1
-        _warn_pairs(rcounts)
+        (idx, vals, n_valid, max_taumax), t_diff = _on_device(
+            eng, data_matrix, global_na,
+            lambda X, gna: eng.topk(X, k, gna, perspective, alternative, continuity, 0, scale_max))
     else:
-        full = ici_kendalltau(data_matrix, global_na=global_na, perspective=perspective, scale_max=scale_max,
-                              diag_good=True, alternative=alternative, continuity=continuity, colnames=names, engine=eng)
-        t_diff = full["run_time"]
-        idx, vals, n_valid = _topk_numpy([np.asarray(full[key]) for key in _TOPK_KEYS], k)
-        max_taumax = _max_taumax(full["taumax"], np.triu_indices(n_sample, k=1))
+        mats5, t_diff, max_taumax = _from_full(eng, data_matrix, names, global_na, perspective, scale_max, alternative,
+                                               continuity)
+        idx, vals, n_valid = _topk_numpy(mats5, k)
     names_arr = np.asarray(list(names) + [None], dtype=object)
     res = {"indices": idx, "neighbors": names_arr[idx]}    # (-1 picks the None behind the names)
-    for q, key in enumerate(_TOPK_KEYS):
-        res[key] = vals[q]
+    _put_values(res, vals)
     res["n_valid"] = n_valid
     res["max_taumax"] = max_taumax
     res["run_time"] = t_diff
@@ -822,26 +883,7 @@ def _cross_topk_numpy(mats5, k):
     """The selection of icikt_cross_f64 from five Sq x Sr matrices (cor, raw, pvalue, taumax, completeness): per query
     row the reference columns whose raw is not NA, by raw descending in the order of the doubles' bits (-0.0 below
     +0.0), ties by the smaller index; padding -1 / NA_real_.  Returns (idx [Sq, k], vals5 [5, Sq, k], n_valid [Sq])."""
-    mats5 = [np.ascontiguousarray(m, dtype=np.float64) for m in mats5]
-    raw = mats5[1]
-    Sq, Sr = raw.shape
-    idx = np.full((Sq, k), -1, dtype=np.int32)
-    vals = np.empty((5, Sq, k), dtype=np.float64)
-    vals.view(np.uint64)[...] = _NA_REAL_BITS
-    n_valid = np.zeros(Sq, dtype=np.int32)
-    bits = raw.view(np.uint64)
-    sign = (bits >> np.uint64(63)).astype(bool)
-    key = np.where(sign, ~bits, bits | np.uint64(1 << 63))
-    refs = np.arange(Sr)
-    for q in range(Sq):
-        cand = refs[~np.isnan(raw[q])]
-        sel = cand[np.lexsort((cand, ~key[q, cand]))[:k]]     # ~key ascending = key descending, then the index
-        m = len(sel)
-        n_valid[q] = m
-        idx[q, :m] = sel
-        for f in range(5):
-            vals[f, q, :m] = mats5[f][q, sel]
-    return idx, vals, n_valid
+    return _best_per_row(mats5, k, skip_own=False)
 
 
 def _cross_numpy(eng, query, reference, global_na, perspective, scale_max, alternative, continuity):
@@ -853,12 +895,10 @@ def _cross_numpy(eng, query, reference, global_na, perspective, scale_max, alter
         return np.empty((5, Sq, Sr)), -math.inf, 0.0
     stacked = np.hstack([np.asarray(query, dtype=np.float64), np.asarray(reference, dtype=np.float64)])
     qn, rn = [f"q{i}" for i in range(Sq)], [f"r{j}" for j in range(Sr)]     # (the callers' names may repeat across the two)
-    full = ici_kendalltau(stacked, global_na=global_na, perspective=perspective, scale_max=scale_max, diag_good=True,
-                          include_only=[list(np.repeat(qn, Sr)), rn * Sq], alternative=alternative,
-                          continuity=continuity, colnames=qn + rn, engine=eng)
-    mats5 = np.stack([np.asarray(full[key])[:Sq, Sq:] for key in _TOPK_KEYS])
-    have = _na_rm(mats5[3].ravel())
-    return mats5, (float(have.max()) if have.size else -math.inf), full["run_time"]
+    block = (slice(0, Sq), slice(Sq, None))
+    mats5, run_time, max_taumax = _from_full(eng, stacked, qn + rn, global_na, perspective, scale_max, alternative,
+                                             continuity, include_only=[list(np.repeat(qn, Sr)), rn * Sq], where=block)
+    return np.stack([m[block] for m in mats5]), max_taumax, run_time
 
 
 def ici_kendalltau_cross(query, reference, k=None, return_matrix=True, global_na=(float("nan"), float("inf"), 0),
@@ -887,9 +927,7 @@ def ici_kendalltau_cross(query, reference, k=None, return_matrix=True, global_na
     or ``reference`` gives empty tables.
     """
     if k is not None:
-        if isinstance(k, (bool, np.bool_)) or not isinstance(k, (int, np.integer)) or not 1 <= int(k) <= _lib.TOPK_MAX:
-            raise ValueError(f"`k` must be None or an integer in 1 .. {_lib.TOPK_MAX}")
-        k = int(k)
+        k = _int_arg(k, 1, _lib.TOPK_MAX, f"`k` must be None or an integer in 1 .. {_lib.TOPK_MAX}")
     elif not return_matrix:
         raise ValueError("nothing to return: give `k`, or leave `return_matrix` set")
     query, qnames = _as_matrix(query, query_names, "query", keep_dtype=True)
@@ -900,15 +938,12 @@ def ici_kendalltau_cross(query, reference, k=None, return_matrix=True, global_na
     Sq, Sr = query.shape[1], reference.shape[1]
     eng = engine or _default_engine()
     out5 = idx = vals = n_valid = None
-    if hasattr(eng, "cross"):
-        if _host_masks(global_na):
-            query, _ = _mask_on_host(query, global_na)
-            reference, global_na = _mask_on_host(reference, global_na)
-        t1 = time.perf_counter()
-        out5, idx, vals, n_valid, max_taumax, rcounts = eng.cross(query, reference, k, return_matrix, global_na, perspective,
-                                                                   alternative, continuity, 0, scale_max)
-        t_diff = time.perf_counter() - t1
-        _warn_pairs(rcounts)
+    if hasattr(eng, "cross"):   # (two matrices, handed over as they are: the parts of _on_device that fit)
+        query, _ = _mask_on_host(query, global_na)
+        reference, global_na = _mask_on_host(reference, global_na)
+        (out5, idx, vals, n_valid, max_taumax), t_diff = _timed(
+            lambda: eng.cross(query, reference, k, return_matrix, global_na, perspective, alternative, continuity, 0,
+                              scale_max))
     else:
         out5, max_taumax, t_diff = _cross_numpy(eng, query, reference, global_na, perspective, scale_max, alternative,
                                                 continuity)
@@ -922,8 +957,7 @@ def ici_kendalltau_cross(query, reference, k=None, return_matrix=True, global_na
         names_arr = np.asarray(list(rnames) + [None], dtype=object)
         res["indices"] = idx
         res["neighbors"] = names_arr[idx]    # (-1 picks the None behind the names)
-        for f, key in enumerate(_TOPK_KEYS):
-            res["topk_" + key] = vals[f]
+        _put_values(res, vals, "topk_")
         res["n_valid"] = n_valid
     res["query_names"] = list(qnames)
     res["reference_names"] = list(rnames)
@@ -946,6 +980,20 @@ def _r_median_pair(a, b):
     return float(np.array([0x7FF8000000000000], dtype=np.uint64).view(np.float64)[0]) if math.isnan(s) else s
 
 
+def _median_cell(cor, raw, s, partners):
+    """(med_cor, med_raw) of sample s over its partners (at least one): the middle one of their raw values sorted
+    ascending (a zero counts as +0), or R's mean of the two middle ones, and the same rule on the cor cells of the
+    partners that supplied those raw values."""
+    v = len(partners)
+    order = np.argsort(raw[s, partners] + 0.0, kind="stable")
+    mid = partners[order[[(v - 1) // 2, v // 2]]]       # (twice the same partner when v is odd)
+    cell = []
+    for mat in (cor, raw):
+        a, b = float(mat[s, mid[0]]) + 0.0, float(mat[s, mid[1]]) + 0.0
+        cell.append(a if v & 1 else _r_median_pair(a, b))
+    return cell
+
+
 def _class_medians_numpy(cor, raw, cls):
     """The reduction of icikt_class_medians_f64 from full S x S cor and raw matrices, for engines without a
     class_medians method (the CPU tests' checker engines).  The partners of sample s are the other samples of its class
@@ -957,22 +1005,15 @@ def _class_medians_numpy(cor, raw, cls):
     raw = np.ascontiguousarray(raw, dtype=np.float64)
     cls = np.asarray(cls)
     S = raw.shape[0]
-    med2 = np.empty((2, S), dtype=np.float64)
-    med2.view(np.uint64)[...] = _NA_REAL_BITS
+    med2 = _na_filled((2, S))
     n_valid = np.zeros(S, dtype=np.int32)
     for s in range(S):
         ok = (cls == cls[s]) & ~np.isnan(raw[s])
         ok[s] = False
         partners = np.nonzero(ok)[0]
-        v = len(partners)
-        n_valid[s] = v
-        if v == 0:
-            continue
-        order = np.argsort(raw[s, partners] + 0.0, kind="stable")
-        mid = partners[order[[(v - 1) // 2, v // 2]]]       # (twice the same partner when v is odd)
-        for q, mat in ((1, raw), (0, cor)):
-            a, b = float(mat[s, mid[0]]) + 0.0, float(mat[s, mid[1]]) + 0.0
-            med2[q, s] = a if v & 1 else _r_median_pair(a, b)
+        n_valid[s] = len(partners)
+        if len(partners):
+            med2[0, s], med2[1, s] = _median_cell(cor, raw, s, partners)
     return med2, n_valid
 
 
@@ -996,21 +1037,14 @@ def ici_kendalltau_medians(data_matrix, sample_classes=None, global_na=(float("n
     column order), ``med_cor``, ``med_raw``, ``n_valid`` (S each), ``max_taumax`` (-inf when no pair was computed) and
     ``run_time``.
     """
-    data_matrix, names = _as_matrix(data_matrix, colnames, "data_matrix", keep_dtype=True, keep_sparse=True)
-    n_sample = data_matrix.shape[1]
+    data_matrix, names, n_sample = _select_input(data_matrix, colnames)
     levels, cls = _class_levels(sample_classes, n_sample, "all")
-    if n_sample < 2:
-        raise ValueError("No comparisons to do. Check the list of column names in "
-                         "`include_only` vs those in the samples.")  # R/kendalltau.R:240-247
+    _need_pairs(n_sample)
     eng = engine or _default_engine()
     if hasattr(eng, "class_medians"):
-        X, global_na = _mask_on_host(data_matrix, global_na)
-        t1 = time.perf_counter()
-        med2, n_valid, max_taumax, rcounts = eng.class_medians(_for_engine(X, eng, fortran=False), cls, len(levels),
-                                                               global_na, perspective, alternative, continuity, 0,
-                                                               scale_max)
-        t_diff = time.perf_counter() - t1
-        _warn_pairs(rcounts)
+        (med2, n_valid, max_taumax), t_diff = _on_device(
+            eng, data_matrix, global_na,
+            lambda X, gna: eng.class_medians(X, cls, len(levels), gna, perspective, alternative, continuity, 0, scale_max))
     else:
         # the within-class pairs, class by class, combn order inside a class
         first, second = [], []
@@ -1020,20 +1054,13 @@ def ici_kendalltau_medians(data_matrix, sample_classes=None, global_na=(float("n
             first.extend(names[i] for i in members[a])
             second.extend(names[i] for i in members[b])
         if first:
-            full = ici_kendalltau(data_matrix, global_na=global_na, perspective=perspective, scale_max=scale_max,
-                                  diag_good=True, include_only=[first, second], alternative=alternative,
-                                  continuity=continuity, colnames=names, engine=eng)
-            t_diff = full["run_time"]
-            cor, raw, taumax = (np.asarray(full[key], dtype=np.float64) for key in ("cor", "raw", "taumax"))
-            med2, n_valid = _class_medians_numpy(cor, raw, cls)
             same = (cls[:, None] == cls[None, :]) & np.triu(np.ones((n_sample, n_sample), dtype=bool), k=1)
-            max_taumax = _max_taumax(taumax, same)
+            mats5, t_diff, max_taumax = _from_full(eng, data_matrix, names, global_na, perspective, scale_max,
+                                                   alternative, continuity, include_only=[first, second], where=same)
+            med2, n_valid = _class_medians_numpy(mats5[0], mats5[1], cls)
         else:   # singletons alone: nothing to compute
-            t_diff = 0.0
-            med2 = np.empty((2, n_sample), dtype=np.float64)
-            med2.view(np.uint64)[...] = _NA_REAL_BITS
-            n_valid = np.zeros(n_sample, dtype=np.int32)
-            max_taumax = -math.inf
+            t_diff, max_taumax = 0.0, -math.inf
+            med2, n_valid = _na_filled((2, n_sample)), np.zeros(n_sample, dtype=np.int32)
     labels = [levels[k] for k in cls]
     return {"sample_id": list(names), "sample_class": labels, "med_cor": med2[0], "med_raw": med2[1],
             "n_valid": n_valid, "max_taumax": max_taumax, "run_time": t_diff}
@@ -1053,8 +1080,7 @@ def _class_matrix_numpy(cor, raw, cls, n_class):
     raw = np.ascontiguousarray(raw, dtype=np.float64)
     cls = np.asarray(cls)
     S = raw.shape[0]
-    med2 = np.empty((2, S, n_class), dtype=np.float64)
-    med2.view(np.uint64)[...] = _NA_REAL_BITS
+    med2 = _na_filled((2, S, n_class))
     n_valid = np.zeros((S, n_class), dtype=np.int32)
     members = [cls == c for c in range(n_class)]
     for s in range(S):
@@ -1062,15 +1088,9 @@ def _class_matrix_numpy(cor, raw, cls, n_class):
         valid[s] = False
         for c in range(n_class):
             partners = np.nonzero(members[c] & valid)[0]
-            v = len(partners)
-            n_valid[s, c] = v
-            if v == 0:
-                continue
-            order = np.argsort(raw[s, partners] + 0.0, kind="stable")
-            mid = partners[order[[(v - 1) // 2, v // 2]]]       # (twice the same partner when v is odd)
-            for q, mat in ((1, raw), (0, cor)):
-                a, b = float(mat[s, mid[0]]) + 0.0, float(mat[s, mid[1]]) + 0.0
-                med2[q, s, c] = a if v & 1 else _r_median_pair(a, b)
+            n_valid[s, c] = len(partners)
+            if len(partners):
+                med2[0, s, c], med2[1, s, c] = _median_cell(cor, raw, s, partners)
     return med2, n_valid
 
 
@@ -1106,30 +1126,20 @@ def ici_kendalltau_class_matrix(data_matrix, sample_classes, global_na=(float("n
     of the class with the largest ``med_raw`` among the cells with a partner, ties to the earlier class, None without
     one), ``max_taumax`` and ``run_time``.
     """
-    data_matrix, names = _as_matrix(data_matrix, colnames, "data_matrix", keep_dtype=True, keep_sparse=True)
-    n_sample = data_matrix.shape[1]
+    data_matrix, names, n_sample = _select_input(data_matrix, colnames)
     if sample_classes is None:
         raise ValueError("`sample_classes` must give one class per column")
     levels, cls = _class_levels(sample_classes, n_sample, "all")
-    if n_sample < 2:
-        raise ValueError("No comparisons to do. Check the list of column names in "
-                         "`include_only` vs those in the samples.")  # R/kendalltau.R:240-247
+    _need_pairs(n_sample)
     eng = engine or _default_engine()
     if hasattr(eng, "class_matrix"):
-        X, global_na = _mask_on_host(data_matrix, global_na)
-        t1 = time.perf_counter()
-        med2, n_valid, max_taumax, rcounts = eng.class_matrix(_for_engine(X, eng, fortran=False), cls, len(levels),
-                                                              global_na, perspective, alternative, continuity, 0,
-                                                              scale_max)
-        t_diff = time.perf_counter() - t1
-        _warn_pairs(rcounts)
+        (med2, n_valid, max_taumax), t_diff = _on_device(
+            eng, data_matrix, global_na,
+            lambda X, gna: eng.class_matrix(X, cls, len(levels), gna, perspective, alternative, continuity, 0, scale_max))
     else:
-        full = ici_kendalltau(data_matrix, global_na=global_na, perspective=perspective, scale_max=scale_max,
-                              diag_good=True, alternative=alternative, continuity=continuity, colnames=names, engine=eng)
-        t_diff = full["run_time"]
-        cor, raw = (np.asarray(full[key], dtype=np.float64) for key in ("cor", "raw"))
-        med2, n_valid = _class_matrix_numpy(cor, raw, cls, len(levels))
-        max_taumax = _max_taumax(full["taumax"], np.triu_indices(n_sample, k=1))
+        mats5, t_diff, max_taumax = _from_full(eng, data_matrix, names, global_na, perspective, scale_max, alternative,
+                                               continuity)
+        med2, n_valid = _class_matrix_numpy(mats5[0], mats5[1], cls, len(levels))
     labels = [levels[k] for k in cls]
     return {"sample_id": list(names), "sample_class": labels, "classes": list(levels), "med_cor": med2[0],
             "med_raw": med2[1], "n_valid": n_valid, "nearest_class": _nearest_class(med2[1], n_valid, levels),
@@ -1175,10 +1185,7 @@ def _quantiles_numpy(cor, raw, cls, probs, breaks):
         members = [np.ones(r.shape[0], dtype=bool), same, ~same]
     G, n_probs = len(members), probs.shape[0]
     n_bins = 0 if breaks is None else len(breaks) - 1
-    q2 = np.empty((2, G, n_probs), dtype=np.float64)
-    order2 = np.empty((G, n_probs, 2), dtype=np.float64)
-    q2.view(np.uint64)[...] = _NA_REAL_BITS
-    order2.view(np.uint64)[...] = _NA_REAL_BITS
+    q2, order2 = _na_filled((2, G, n_probs)), _na_filled((G, n_probs, 2))
     n_valid, n_na = np.zeros(G, dtype=np.int64), np.zeros(G, dtype=np.int64)
     hist, outside = np.zeros((G, n_bins), dtype=np.int64), np.zeros((G, 2), dtype=np.int64)
     for g, member in enumerate(members):
@@ -1226,16 +1233,13 @@ def ici_kendalltau_quantiles(data_matrix, probs=(0, 0.25, 0.5, 0.75, 1), breaks=
     ``quantile_cor``, ``quantile_raw`` (n_group x n_probs), ``n_valid``, ``n_na`` (n_group), ``breaks`` (None without
     a histogram), ``counts`` (n_group x n_bins), ``n_below``, ``n_above``, ``max_taumax`` and ``run_time``.
     """
-    data_matrix, names = _as_matrix(data_matrix, colnames, "data_matrix", keep_dtype=True, keep_sparse=True)
-    n_sample = data_matrix.shape[1]
+    data_matrix, names, n_sample = _select_input(data_matrix, colnames)
     if sample_classes is None:
         levels, cls, groups = ["all"], None, ["all"]
     else:
         levels, cls = _class_levels(sample_classes, n_sample, "all")
         groups = ["all", "within", "between"]
-    if n_sample < 2:
-        raise ValueError("No comparisons to do. Check the list of column names in "
-                         "`include_only` vs those in the samples.")  # R/kendalltau.R:240-247
+    _need_pairs(n_sample)
     probs_a = np.atleast_1d(np.asarray(probs, dtype=np.float64)).ravel()
     if probs_a.shape[0] > _lib.QUANTILE_MAX_PROBS or not np.all((probs_a >= 0) & (probs_a <= 1)):
         raise ValueError(f"`probs` must be at most {_lib.QUANTILE_MAX_PROBS} values in [0, 1]")
@@ -1253,20 +1257,14 @@ def ici_kendalltau_quantiles(data_matrix, probs=(0, 0.25, 0.5, 0.75, 1), breaks=
             raise ValueError(f"`breaks` must be 2 .. {_lib.HIST_MAX_BINS + 1} finite, strictly increasing bin edges")
     eng = engine or _default_engine()
     if hasattr(eng, "quantiles"):
-        X, global_na = _mask_on_host(data_matrix, global_na)
-        t1 = time.perf_counter()
-        q2, _order2, n_valid, n_na, hist, outside, max_taumax, rcounts = eng.quantiles(
-            _for_engine(X, eng, fortran=False), probs_a, breaks_a, cls, len(levels), global_na, perspective, alternative,
-            continuity, 0, scale_max)
-        t_diff = time.perf_counter() - t1
-        _warn_pairs(rcounts)
+        (q2, _order2, n_valid, n_na, hist, outside, max_taumax), t_diff = _on_device(
+            eng, data_matrix, global_na,
+            lambda X, gna: eng.quantiles(X, probs_a, breaks_a, cls, len(levels), gna, perspective, alternative,
+                                         continuity, 0, scale_max))
     else:
-        full = ici_kendalltau(data_matrix, global_na=global_na, perspective=perspective, scale_max=scale_max,
-                              diag_good=True, alternative=alternative, continuity=continuity, colnames=names, engine=eng)
-        t_diff = full["run_time"]
-        cor, raw, taumax = (np.asarray(full[key], dtype=np.float64) for key in ("cor", "raw", "taumax"))
-        q2, _order2, n_valid, n_na, hist, outside = _quantiles_numpy(cor, raw, cls, probs_a, breaks_a)
-        max_taumax = _max_taumax(taumax, np.triu(np.ones((n_sample, n_sample), dtype=bool), k=1))
+        mats5, t_diff, max_taumax = _from_full(eng, data_matrix, names, global_na, perspective, scale_max, alternative,
+                                               continuity)
+        q2, _order2, n_valid, n_na, hist, outside = _quantiles_numpy(mats5[0], mats5[1], cls, probs_a, breaks_a)
     return {"probs": probs_a, "group": groups, "quantile_cor": q2[0], "quantile_raw": q2[1], "n_valid": n_valid,
             "n_na": n_na, "breaks": breaks_a, "counts": hist, "n_below": outside[:, 0].copy(),
             "n_above": outside[:, 1].copy(), "max_taumax": max_taumax, "run_time": t_diff}
@@ -1290,27 +1288,38 @@ def _edge_bound(value, name):
     return float(value)
 
 
+def _candidate_triangle(mats5, min_raw, absolute=False):
+    """The upper triangle of five full S x S matrices (cor, raw, pvalue, taumax, completeness) in combn order -- row-
+    major: i ascending, then j ascending -- and its candidate pairs: raw not NA, and raw (abs(raw) with absolute) >=
+    min_raw when that is not None, as a plain comparison of doubles.  Returns (iu: the triangle's indices; tri5 [5, P]:
+    the planes there; ok [P]: the candidates)."""
+    mats5 = [np.ascontiguousarray(m, dtype=np.float64) for m in mats5]
+    S = mats5[1].shape[0]
+    iu = np.triu_indices(S, k=1)
+    tri5 = np.stack([m[iu] for m in mats5]) if S > 1 else np.empty((5, 0))
+    raw = tri5[1]
+    with np.errstate(invalid="ignore"):
+        ok = ~np.isnan(raw)
+        if min_raw is not None:
+            ok &= (np.abs(raw) if absolute else raw) >= min_raw
+    return iu, tri5, ok
+
+
 def _edges_numpy(mats5, min_raw, max_pvalue, min_completeness, absolute):
     """The selection of icikt_edges_f64 from five full S x S matrices (cor, raw, pvalue, taumax, completeness), for
     engines without an edges method (the CPU tests' checker engines): the upper triangle in combn order, raw not NA and
     every bound that is not None, as plain comparisons of doubles.  Returns (ei, ej, vals5 [5, m], degree [S]): all of
     the matching pairs."""
-    mats5 = [np.ascontiguousarray(m, dtype=np.float64) for m in mats5]
-    S = mats5[1].shape[0]
-    iu = np.triu_indices(S, k=1)             # row-major upper triangle: i ascending, then j ascending
-    raw, pvalue, comp = mats5[1][iu], mats5[2][iu], mats5[4][iu]
+    S = np.shape(mats5[1])[0]
+    iu, tri5, ok = _candidate_triangle(mats5, min_raw, absolute)
     with np.errstate(invalid="ignore"):
-        ok = ~np.isnan(raw)
-        if min_raw is not None:
-            ok &= (np.abs(raw) if absolute else raw) >= min_raw
         if max_pvalue is not None:
-            ok &= pvalue <= max_pvalue
+            ok &= tri5[2] <= max_pvalue
         if min_completeness is not None:
-            ok &= comp >= min_completeness
+            ok &= tri5[4] >= min_completeness
     ei, ej = iu[0][ok].astype(np.int32), iu[1][ok].astype(np.int32)
-    vals = np.stack([m[iu][ok] for m in mats5]) if S > 1 else np.empty((5, 0))
     degree = np.bincount(ei, minlength=S).astype(np.int64) + np.bincount(ej, minlength=S).astype(np.int64)
-    return ei, ej, vals, degree
+    return ei, ej, tri5[:, ok], degree
 
 
 def ici_kendalltau_edges(data_matrix, min_raw=None, max_pvalue=None, min_completeness=None, absolute=False,
@@ -1340,43 +1349,33 @@ def ici_kendalltau_edges(data_matrix, min_raw=None, max_pvalue=None, min_complet
     min_raw = _edge_bound(min_raw, "min_raw")
     max_pvalue = _edge_bound(max_pvalue, "max_pvalue")
     min_completeness = _edge_bound(min_completeness, "min_completeness")
-    if max_edges is not None and (isinstance(max_edges, (bool, np.bool_)) or not isinstance(max_edges, (int, np.integer))
-                                  or int(max_edges) < 0):
-        raise ValueError("`max_edges` must be a non-negative integer or None")
-    data_matrix, names = _as_matrix(data_matrix, colnames, "data_matrix", keep_dtype=True, keep_sparse=True)
-    n_sample = data_matrix.shape[1]
-    if n_sample < 2:
-        raise ValueError("No comparisons to do. Check the list of column names in "
-                         "`include_only` vs those in the samples.")  # R/kendalltau.R:240-247
+    if max_edges is not None:
+        max_edges = _int_arg(max_edges, 0, math.inf, "`max_edges` must be a non-negative integer or None")
+    data_matrix, names, n_sample = _select_input(data_matrix, colnames)
+    _need_pairs(n_sample)
     total = n_sample * (n_sample - 1) // 2
     eng = engine or _default_engine()
     if hasattr(eng, "edges"):
-        X, global_na = _mask_on_host(data_matrix, global_na)
-        Xe = _for_engine(X, eng, fortran=False)
-        room = min(total, max(EDGES_DEFAULT_CAPACITY, EDGES_CAPACITY_PER_SAMPLE * n_sample)) if max_edges is None else int(max_edges)
-        t1 = time.perf_counter()
-        out = eng.edges(Xe, min_raw, max_pvalue, min_completeness, absolute, room, global_na, perspective, alternative,
-                        continuity, 0, scale_max)
-        if max_edges is None and out[3] > room:   # the second call is exact: the count does not depend on the room
-            out = eng.edges(Xe, min_raw, max_pvalue, min_completeness, absolute, out[3], global_na, perspective,
-                            alternative, continuity, 0, scale_max)
-        t_diff = time.perf_counter() - t1
-        ei, ej, vals, n_edges, degree, max_taumax, rcounts = out
-        _warn_pairs(rcounts)
+        room = min(total, max(EDGES_DEFAULT_CAPACITY, EDGES_CAPACITY_PER_SAMPLE * n_sample)) if max_edges is None else max_edges
+
+        def call(X, gna):
+            out = eng.edges(X, min_raw, max_pvalue, min_completeness, absolute, room, gna, perspective, alternative,
+                            continuity, 0, scale_max)
+            if max_edges is None and out[3] > room:   # the second call is exact: the count does not depend on the room
+                out = eng.edges(X, min_raw, max_pvalue, min_completeness, absolute, out[3], gna, perspective, alternative,
+                                continuity, 0, scale_max)
+            return out
+        (ei, ej, vals, n_edges, degree, max_taumax), t_diff = _on_device(eng, data_matrix, global_na, call)
     else:
-        full = ici_kendalltau(data_matrix, global_na=global_na, perspective=perspective, scale_max=scale_max,
-                              diag_good=True, alternative=alternative, continuity=continuity, colnames=names, engine=eng)
-        t_diff = full["run_time"]
-        ei, ej, vals, degree = _edges_numpy([np.asarray(full[key]) for key in _TOPK_KEYS], min_raw, max_pvalue,
-                                            min_completeness, absolute)
+        mats5, t_diff, max_taumax = _from_full(eng, data_matrix, names, global_na, perspective, scale_max, alternative,
+                                               continuity)
+        ei, ej, vals, degree = _edges_numpy(mats5, min_raw, max_pvalue, min_completeness, absolute)
         n_edges = int(ei.shape[0])
         if max_edges is not None:
-            ei, ej, vals = ei[:int(max_edges)], ej[:int(max_edges)], vals[:, :int(max_edges)]
-        max_taumax = _max_taumax(full["taumax"], np.triu_indices(n_sample, k=1))
+            ei, ej, vals = ei[:max_edges], ej[:max_edges], vals[:, :max_edges]
     names_arr = np.asarray(list(names), dtype=object)
     res = {"s1": names_arr[ei], "s2": names_arr[ej], "i": ei, "j": ej}
-    for q, key in enumerate(_TOPK_KEYS):
-        res[key] = vals[q]
+    _put_values(res, vals)
     res["n_edges"] = int(n_edges)
     res["degree"] = degree
     res["max_taumax"] = max_taumax
@@ -1412,14 +1411,9 @@ def _mst_numpy(mats5, min_raw):
     raw not NA, and raw >= min_raw when that is not None -- in the strict edge order, np.lexsort by raw descending (-0
     equal to +0) and then by the combn index, merged by union-find.  Returns (ti, tj, vals5 [5, n_tree], component [S],
     n_components)."""
-    mats5 = [np.ascontiguousarray(m, dtype=np.float64) for m in mats5]
-    S = mats5[1].shape[0]
-    iu = np.triu_indices(S, k=1)             # row-major upper triangle: the combn order
-    raw = mats5[1][iu]
-    with np.errstate(invalid="ignore"):
-        ok = ~np.isnan(raw)
-        if min_raw is not None:
-            ok &= raw >= min_raw
+    S = np.shape(mats5[1])[0]
+    iu, tri5, ok = _candidate_triangle(mats5, min_raw)
+    raw = tri5[1]
     cand = np.flatnonzero(ok)                # combn indices, ascending
     order = cand[np.lexsort((cand, -(raw[cand] + 0.0)))]   # (+ 0.0: -0 sorts as +0)
     parent = list(range(S))
@@ -1441,9 +1435,8 @@ def _mst_numpy(mats5, min_raw):
             picked.append(e)
     picked = np.asarray(picked, dtype=np.int64)
     ti, tj = ii[picked].astype(np.int32), jj[picked].astype(np.int32)
-    vals = np.stack([m[iu][picked] for m in mats5]) if S > 1 else np.empty((5, 0))
     component, n_comp = _mst_components(parent)
-    return ti, tj, vals, component, n_comp
+    return ti, tj, tri5[:, picked], component, n_comp
 
 
 def ici_kendalltau_mst(data_matrix, min_raw=None, global_na=(float("nan"), float("inf"), 0), perspective="global",
@@ -1474,29 +1467,20 @@ def ici_kendalltau_mst(data_matrix, min_raw=None, global_na=(float("nan"), float
     it.
     """
     min_raw = _edge_bound(min_raw, "min_raw")
-    data_matrix, names = _as_matrix(data_matrix, colnames, "data_matrix", keep_dtype=True, keep_sparse=True)
-    n_sample = data_matrix.shape[1]
-    if n_sample < 2:
-        raise ValueError("No comparisons to do. Check the list of column names in "
-                         "`include_only` vs those in the samples.")  # R/kendalltau.R:240-247
+    data_matrix, names, n_sample = _select_input(data_matrix, colnames)
+    _need_pairs(n_sample)
     eng = engine or _default_engine()
     if hasattr(eng, "mst"):
-        X, global_na = _mask_on_host(data_matrix, global_na)
-        t1 = time.perf_counter()
-        ti, tj, vals, component, n_comp, _n_rounds, max_taumax, rcounts = eng.mst(
-            _for_engine(X, eng, fortran=False), min_raw, global_na, perspective, alternative, continuity, 0, scale_max)
-        t_diff = time.perf_counter() - t1
-        _warn_pairs(rcounts)
+        (ti, tj, vals, component, n_comp, _n_rounds, max_taumax), t_diff = _on_device(
+            eng, data_matrix, global_na,
+            lambda X, gna: eng.mst(X, min_raw, gna, perspective, alternative, continuity, 0, scale_max))
     else:
-        full = ici_kendalltau(data_matrix, global_na=global_na, perspective=perspective, scale_max=scale_max,
-                              diag_good=True, alternative=alternative, continuity=continuity, colnames=names, engine=eng)
-        t_diff = full["run_time"]
-        ti, tj, vals, component, n_comp = _mst_numpy([np.asarray(full[key]) for key in _TOPK_KEYS], min_raw)
-        max_taumax = _max_taumax(full["taumax"], np.triu_indices(n_sample, k=1))
+        mats5, t_diff, max_taumax = _from_full(eng, data_matrix, names, global_na, perspective, scale_max, alternative,
+                                               continuity)
+        ti, tj, vals, component, n_comp = _mst_numpy(mats5, min_raw)
     names_arr = np.asarray(list(names), dtype=object)
     res = {"s1": names_arr[ti], "s2": names_arr[tj], "i": ti, "j": tj}
-    for q, key in enumerate(_TOPK_KEYS):
-        res[key] = vals[q]
+    _put_values(res, vals)
     res["n_tree"] = int(ti.shape[0])
     res["component"] = component
     res["n_components"] = int(n_comp)
@@ -1595,27 +1579,17 @@ def ici_kendalltau_hclust(data_matrix, method="complete", min_raw=None, global_n
     if method not in HCLUST_METHODS:
         raise ValueError("`method` must be complete, average or single")
     min_raw = _edge_bound(min_raw, "min_raw")
-    data_matrix, names = _as_matrix(data_matrix, colnames, "data_matrix", keep_dtype=True, keep_sparse=True)
-    n_sample = data_matrix.shape[1]
-    if n_sample < 2:
-        raise ValueError("No comparisons to do. Check the list of column names in "
-                         "`include_only` vs those in the samples.")  # R/kendalltau.R:240-247
+    data_matrix, names, n_sample = _select_input(data_matrix, colnames)
+    _need_pairs(n_sample)
     eng = engine or _default_engine()
     if hasattr(eng, "hclust"):
-        X, global_na = _mask_on_host(data_matrix, global_na)
-        t1 = time.perf_counter()
-        ma, mb, msize, mraw, mcor, component, n_comp, max_taumax, rcounts = eng.hclust(
-            _for_engine(X, eng, fortran=False), method, min_raw, global_na, perspective, alternative, continuity, 0,
-            scale_max)
-        t_diff = time.perf_counter() - t1
-        _warn_pairs(rcounts)
+        (ma, mb, msize, mraw, mcor, component, n_comp, max_taumax), t_diff = _on_device(
+            eng, data_matrix, global_na,
+            lambda X, gna: eng.hclust(X, method, min_raw, gna, perspective, alternative, continuity, 0, scale_max))
     else:
-        full = ici_kendalltau(data_matrix, global_na=global_na, perspective=perspective, scale_max=scale_max,
-                              diag_good=True, alternative=alternative, continuity=continuity, colnames=names, engine=eng)
-        t_diff = full["run_time"]
-        ma, mb, msize, mraw, component, n_comp = _hclust_numpy([np.asarray(full[key]) for key in _TOPK_KEYS], method,
-                                                               min_raw)
-        max_taumax = _max_taumax(full["taumax"], np.triu_indices(n_sample, k=1))
+        mats5, t_diff, max_taumax = _from_full(eng, data_matrix, names, global_na, perspective, scale_max, alternative,
+                                               continuity)
+        ma, mb, msize, mraw, component, n_comp = _hclust_numpy(mats5, method, min_raw)
         mcor = mraw / max_taumax if scale_max else mraw.copy()
     return {"merge_a": ma, "merge_b": mb, "size": msize, "raw": mraw, "cor": mcor, "n_merges": int(ma.shape[0]),
             "component": component, "n_components": int(n_comp), "method": method,
@@ -1674,8 +1648,7 @@ def _padjust_numpy(pvalue_matrix, method, alpha):
         adj = np.minimum.accumulate(((float(m) / j) * p)[::-1])[::-1]
     adj = np.minimum(1.0, adj)
     n_rejected = np.array([int(np.count_nonzero(adj <= a)) for a in alpha], dtype=np.int64)
-    p_cutoff = np.empty(alpha.shape[0], dtype=np.float64)
-    p_cutoff.view(np.uint64)[...] = _NA_REAL_BITS
+    p_cutoff = _na_filled(alpha.shape[0])
     for a, n in enumerate(n_rejected):
         if n > 0:
             p_cutoff[a] = p[n - 1]
@@ -1717,37 +1690,29 @@ def ici_kendalltau_padjust(data_matrix, method="BH", alpha=0.05, max_table=None,
     """
     method = _padjust_method(method)
     alpha_a = _padjust_alpha(alpha)
-    if max_table is not None and (isinstance(max_table, (bool, np.bool_)) or not isinstance(max_table, (int, np.integer))
-                                  or int(max_table) < 0):
-        raise ValueError("`max_table` must be a non-negative integer or None")
-    data_matrix, names = _as_matrix(data_matrix, colnames, "data_matrix", keep_dtype=True, keep_sparse=True)
-    n_sample = data_matrix.shape[1]
-    if n_sample < 2:
-        raise ValueError("No comparisons to do. Check the list of column names in "
-                         "`include_only` vs those in the samples.")  # R/kendalltau.R:240-247
+    if max_table is not None:
+        max_table = _int_arg(max_table, 0, math.inf, "`max_table` must be a non-negative integer or None")
+    data_matrix, names, n_sample = _select_input(data_matrix, colnames)
+    _need_pairs(n_sample)
     total = n_sample * (n_sample - 1) // 2
     eng = engine or _default_engine()
     if hasattr(eng, "padjust"):
-        X, global_na = _mask_on_host(data_matrix, global_na)
-        Xe = _for_engine(X, eng, fortran=False)
-        room = min(total, PADJUST_DEFAULT_TABLE) if max_table is None else int(max_table)
-        t1 = time.perf_counter()
-        out = eng.padjust(Xe, method, alpha_a, room, global_na, perspective, alternative, continuity, 0)
-        if max_table is None and out[4] > room:   # the second call is exact: the count does not depend on the room
-            out = eng.padjust(Xe, method, alpha_a, out[4], global_na, perspective, alternative, continuity, 0)
-        t_diff = time.perf_counter() - t1
-        n_tests, n_rejected, p_cutoff, table, n_table, max_taumax, rcounts = out
+        room = min(total, PADJUST_DEFAULT_TABLE) if max_table is None else max_table
+
+        def call(X, gna):
+            out = eng.padjust(X, method, alpha_a, room, gna, perspective, alternative, continuity, 0)
+            if max_table is None and out[4] > room:   # the second call is exact: the count does not depend on the room
+                out = eng.padjust(X, method, alpha_a, out[4], gna, perspective, alternative, continuity, 0)
+            return out
+        (n_tests, n_rejected, p_cutoff, table, n_table, max_taumax), t_diff = _on_device(eng, data_matrix, global_na, call)
         table_p, table_adj = table[0], table[1]
-        _warn_pairs(rcounts)
     else:
-        full = ici_kendalltau(data_matrix, global_na=global_na, perspective=perspective, scale_max=True, diag_good=True,
-                              alternative=alternative, continuity=continuity, colnames=names, engine=eng)
-        t_diff = full["run_time"]
-        n_tests, n_rejected, p_cutoff, table_p, table_adj = _padjust_numpy(np.asarray(full["pvalue"]), method, alpha_a)
+        mats5, t_diff, max_taumax = _from_full(eng, data_matrix, names, global_na, perspective, True, alternative,
+                                               continuity)
+        n_tests, n_rejected, p_cutoff, table_p, table_adj = _padjust_numpy(mats5[2], method, alpha_a)
         n_table = int(table_p.shape[0])
         if max_table is not None:
-            table_p, table_adj = table_p[:int(max_table)], table_adj[:int(max_table)]
-        max_taumax = _max_taumax(full["taumax"], np.triu_indices(n_sample, k=1))
+            table_p, table_adj = table_p[:max_table], table_adj[:max_table]
     return {"method": method, "alpha": alpha_a, "n_tests": int(n_tests[0]), "n_na": int(n_tests[1]),
             "n_rejected": n_rejected, "p_cutoff": p_cutoff, "table_p": table_p, "table_adjusted": table_adj,
             "n_table": int(n_table), "max_taumax": max_taumax, "run_time": t_diff}
@@ -1780,8 +1745,7 @@ def ici_kendalltau_significant(data_matrix, alpha=0.05, method="BH", min_raw=Non
     if n_rejected == 0:
         none_i = np.empty(0, dtype=np.int32)
         res = {"s1": np.empty(0, dtype=object), "s2": np.empty(0, dtype=object), "i": none_i, "j": none_i.copy()}
-        for key in _TOPK_KEYS:
-            res[key] = np.empty(0, dtype=np.float64)
+        _put_values(res, np.empty((5, 0), dtype=np.float64))
         res.update(n_edges=0, degree=np.zeros(data_matrix.shape[1], dtype=np.int64), max_taumax=adj["max_taumax"],
                    run_time=adj["run_time"], adjusted=np.empty(0, dtype=np.float64))
     else:
@@ -1921,29 +1885,21 @@ def ici_kendalltau_anosim(data_matrix, sample_classes, permutations=999, seed=No
     without one), ``within_mean_rank``, ``between_mean_rank``, ``sums`` (the integers: ``w2``, ``nw`` [1 + n_perm],
     index 0 the observed labelling, ``class_w2``, ``class_nw``), ``sample_id``, ``max_taumax`` and ``run_time``.
     """
-    data_matrix, names = _as_matrix(data_matrix, colnames, "data_matrix", keep_dtype=True, keep_sparse=True)
-    n_sample = data_matrix.shape[1]
+    data_matrix, names, n_sample = _select_input(data_matrix, colnames)
     if sample_classes is None:
         raise ValueError("`sample_classes` must give one class per column")
     levels, cls = _class_levels(sample_classes, n_sample, "all")
-    if n_sample < 2:
-        raise ValueError("No comparisons to do. Check the list of column names in "
-                         "`include_only` vs those in the samples.")  # R/kendalltau.R:240-247
+    _need_pairs(n_sample)
     perms = anosim_permutations(cls, permutations, seed, strata)
     eng = engine or _default_engine()
     if hasattr(eng, "anosim"):
-        X, global_na = _mask_on_host(data_matrix, global_na)
-        t1 = time.perf_counter()
-        n_pairs, w2, nw, n_ge, n_undef, class_w2, class_nw, max_taumax, rcounts = eng.anosim(
-            _for_engine(X, eng, fortran=False), cls, len(levels), perms, global_na, perspective, alternative, continuity, 0)
-        t_diff = time.perf_counter() - t1
-        _warn_pairs(rcounts)
+        (n_pairs, w2, nw, n_ge, n_undef, class_w2, class_nw, max_taumax), t_diff = _on_device(
+            eng, data_matrix, global_na,
+            lambda X, gna: eng.anosim(X, cls, len(levels), perms, gna, perspective, alternative, continuity, 0))
     else:
-        full = ici_kendalltau(data_matrix, global_na=global_na, perspective=perspective, scale_max=True, diag_good=True,
-                              alternative=alternative, continuity=continuity, colnames=names, engine=eng)
-        t_diff = full["run_time"]
-        n_pairs, w2, nw, n_ge, n_undef, class_w2, class_nw = _anosim_numpy(np.asarray(full["raw"]), cls, len(levels), perms)
-        max_taumax = _max_taumax(full["taumax"], np.triu_indices(n_sample, k=1))
+        mats5, t_diff, max_taumax = _from_full(eng, data_matrix, names, global_na, perspective, True, alternative,
+                                               continuity)
+        n_pairs, w2, nw, n_ge, n_undef, class_w2, class_nw = _anosim_numpy(mats5[1], cls, len(levels), perms)
     M, n_perm = int(n_pairs[0]), int(perms.shape[0])
     na = _na_real()
     as_float = lambda f: na if f is None else float(f)   # noqa: E731  (Fraction -> float rounds correctly, once)
