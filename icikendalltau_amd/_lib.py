@@ -15,7 +15,8 @@ _PKG = os.path.dirname(os.path.abspath(__file__))
 _ROOT = os.path.dirname(_PKG)
 LIB_PATH = os.environ.get("ICIKT_LIB") or os.path.join(_PKG, "libicikt_hip.so")  # ICIKT_LIB: A/B of builds (tools)
 SOURCES = [os.path.join(_PKG, "csrc", f) for f in ("icikt_kernels.hip", "icikt_prepass.hip", "icikt_epilogue.hip",
-                                                       "icikt_capi.cpp", "icikt_capi_cor.cpp", "icikt_capi_diag.cpp",
+                                                       "icikt_capi.cpp", "icikt_pipeline.cpp", "icikt_capi_cor.cpp",
+                                                       "icikt_capi_diag.cpp",
                                                        "icikt_multi.cpp", "icikt_transfer.cpp", "icikt_cor.hip", "icikt_topk.hip",
                                                        "icikt_capi_topk.cpp", "icikt_edges.hip", "icikt_capi_edges.cpp",
                                                        "icikt_diag.hip", "icikt_ingest.hip", "icikt_sparse.hip",

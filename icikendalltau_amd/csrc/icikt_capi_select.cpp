@@ -54,12 +54,7 @@ int select_run(SelectCall& s, PairBlocks& blocks, const SelectSteps& steps) {
   // device-resident calls start over afterwards (icikt_run_dev: ICIKT_E_STATE, icikt_num_pairs: -1)
   auto leave = [&](int r) {
     r = end_call(c, s.who, r);
-    c->prepared = false;
-    c->raw_valid = false;
-    c->n_pairs = -1;
-    c->pairs_nsamp = -1;
-    c->wpb = 0;
-    c->combn_S = -1;
+    forget_prepared(c);
     return r;
   };
   const PinnedScope scope(c, flags);

@@ -1,6 +1,7 @@
-// icikt_host.h -- host-side internals shared by the entry files of one device (icikt_capi.cpp: the pair engine,
-// icikt_capi_cor.cpp: cor_fast, icikt_capi_diag.cpp: the missing-value diagnostics) and icikt_multi.cpp (several
-// devices, RCCL).  Internal; the public boundary is include/icikt.h.
+// icikt_host.h -- host-side internals shared by the entry files of one device (icikt_capi.cpp: the pair engine's
+// entries, icikt_pipeline.cpp: its copies, pre-pass and pair launches, icikt_capi_cor.cpp: cor_fast,
+// icikt_capi_diag.cpp: the missing-value diagnostics) and icikt_multi.cpp (several devices, RCCL).  Internal; the
+// public boundary is include/icikt.h.
 #ifndef ICIKT_HOST_H
 #define ICIKT_HOST_H
 
@@ -260,6 +261,19 @@ int timer_end(icikt_ctx* c, int k, uint32_t flags);
       return icikt::host::fail((c), ICIKT_E_HIP, std::string(#call) + ": " + hipGetErrorString(e__)); \
   } while (0)
 
+// The end of a call that left its own scratch columns and pair list in the context, nothing of the caller's (the
+// selection entries, icikt_pairs_complete_*): forget the prepared state and the pair list.  The device-resident calls
+// start over (icikt_run_dev: ICIKT_E_STATE until icikt_prepare_dev and a pair list; icikt_num_pairs: -1).
+inline void forget_prepared(icikt_ctx* c) {
+  c->prepared = false;
+  c->raw_valid = false;
+  c->n_pairs = -1;
+  c->pairs_nsamp = -1;
+  c->wpb = 0;
+  c->combn_S = -1;
+}
+
+// ---- what enqueues copies, the pre-pass and the pair launches (icikt_pipeline.cpp) ----
 // Allocate the prepared state of an n_feat x n_samp matrix for alloc_cols >= n_samp columns (sort scratch for
 // sort_cols columns at a time) and set c->pv.  No kernel is launched.
 int prepare_alloc(icikt_ctx* c, int64_t n_feat, int64_t n_samp, int64_t alloc_cols, int64_t sort_cols);
@@ -269,9 +283,8 @@ int prepare_launch(icikt_ctx* c, const double* dX, int64_t ld, int64_t col_begin
 // keeps the full n_feat x n_samp layout (leading dimension n_feat) in c->d_X.  prepare_alloc() must have run.
 // pipelined: the pre-pass launches go to c->prep_stream, one event per chunk in c->ev_chunk / c->chunk_col_end; the
 // caller makes c->stream wait for them (per chunk, or for the last one), and synchronises c->copy_stream before it
-// returns to ITS caller.  prepass: what runs over a chunk once it has arrived -- the full pre-pass (K0), the
-// mask-only one of pairwise_completeness (k0_mask: meta alone must be allocated, mask_alloc), or nothing.
-enum { kPrepassNone = 0, kPrepassFull = 1, kPrepassMask = 2 };
+// returns to ITS caller.  prepass: what runs over a chunk once it has arrived (kPrepass*, icikt_k0plan.h, which also
+// says how many columns a chunk holds).
 // Allocate c->pv for the missing-row bitsets alone (meta; no order / rec / sort scratch).  Leaves the context unprepared.
 int mask_alloc(icikt_ctx* c, int64_t n_feat, int64_t n_samp);
 int upload_and_prepare(icikt_ctx* c, const MatrixSrc& X, int64_t n_feat, int64_t n_samp, int64_t col_begin,
@@ -286,6 +299,12 @@ int upload_prepare_pairs(icikt_ctx* c, const MatrixSrc& X, int64_t n_feat, int64
 int make_mask_spec(icikt_ctx* c, const double* global_na, int n_global_na, icikt::MaskSpec* ms);
 // Build the pair kernel's task list on the host now (prepare_alloc and a pair list must be in place).
 void prebuild_units(icikt_ctx* c);
+// The context's host pair list (h_pi / h_pj, n_pairs) onto the device; reserves d_raw for it.
+int upload_pairs(icikt_ctx* c);
+// The counts step of icikt_run_dev: the pair kernel -- the wide one, or the plan's over the whole task list (rebuilt and
+// uploaded when the plan or the pair list changed) -- over the prepared matrix and the pair list, inside an
+// ICIKT_K_PAIRS timer pair; leaves the counts in c->d_raw (raw_valid).
+int run_counts(icikt_ctx* c, uint32_t flags);
 // The arguments the pair and matrix entries share, `who` prefixing the message: shape, null matrix, pair list (none: all
 // pairs, *n_pairs set), null output (out5: needed for any column, out4: for any pair), perspective and alternative.
 int check_pair_args(icikt_ctx* c, const char* who, const MatrixSrc& X, int64_t n_feat, int64_t n_samp,

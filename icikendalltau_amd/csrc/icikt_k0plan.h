@@ -1,8 +1,11 @@
-// icikt_k0plan.h -- which shape of the pre-pass kernel (icikt_prepass.hip) a launch takes.  Host arithmetic only: no
+// icikt_k0plan.h -- which shape of the pre-pass kernel (icikt_prepass.hip) a launch takes, and how many columns of a
+// host matrix one launch covers (a chunk of upload_and_prepare, icikt_pipeline.cpp).  Host arithmetic only: no
 // device header, so tests/k0plan_print.cpp compiles it with the host compiler alone.  Part of icikt_host.h.
 #ifndef ICIKT_K0PLAN_H
 #define ICIKT_K0PLAN_H
 
+#include <algorithm>
+#include <cstddef>
 #include <cstdint>
 
 namespace icikt {
@@ -39,6 +42,45 @@ inline int k0_pick_shape(int64_t n, int64_t columns, int cus) {
 inline int k0_launch_shape(int k0_override, int64_t n, int64_t columns, int cus) {
   if (k0_override == K0_SHAPE_LARGE || k0_override == K0_SHAPE_SMALL || k0_override == K0_SHAPE_PAIR) return k0_override;
   return k0_pick_shape(n, columns, cus);
+}
+
+// What runs over the columns of a chunk of a host matrix once they are on the device (upload_and_prepare): the full
+// pre-pass (K0), the mask-only one of pairwise_completeness (k0_mask: meta alone must be allocated, mask_alloc), or
+// nothing (icikt_pairs_complete_f64 sorts masked copies, not the columns).
+enum { kPrepassNone = 0, kPrepassFull = 1, kPrepassMask = 2 };
+
+// how the caller's matrix lies in host memory, as far as the chunk width goes
+enum : int {
+  K0_VIEW_COL = 0,      // column-major, any element type
+  K0_VIEW_ROW = 1,      // row-major: a chunk is n_feat runs of `chunk` cells of elem_bytes each
+  K0_VIEW_SPARSE = 2,   // CSC
+};
+constexpr size_t kRowRunBytes = 512;               // a row-major chunk: runs of at least this many bytes ...
+constexpr size_t kRowHalfMax = (size_t)64 << 20;   // ... while a half of the staging blocks stays within this
+
+// Columns of a chunk of upload_and_prepare: what one H2D copy and one pre-pass launch cover (pipelined: one pair-kernel
+// launch too) of an n_feat x n_samp matrix (n_feat > 0) on a device of `cus` CUs.  view, elem_bytes: K0_VIEW_*, and the
+// bytes of a cell of a row-major view; prepass: kPrepass*; sort_chunk: the columns the sort scratch holds (prepare_alloc).
+inline int64_t k0_chunk_columns(int64_t n_feat, int64_t n_samp, int cus, bool pipelined, int view, size_t elem_bytes,
+                                int prepass, int sort_chunk) {
+  const size_t col_bytes = (size_t)n_feat * sizeof(double);
+  // ~8 MB per chunk (an even number of columns: K0 ranges need not be even, but keeps chunks aligned)
+  int64_t chunk = std::max<int64_t>(2, (int64_t)(((size_t)8 << 20) / std::max<size_t>(col_bytes, 1)) & ~(int64_t)1);
+  // pipelined: a chunk is also what one pre-pass launch and one pair-kernel launch cover.  A pre-pass launch takes
+  // the time of ONE column's sort up to a workgroup per CU, so chunks of fewer columns only lengthen the chain of
+  // pre-pass launches the last pair-kernel launch waits for (c4: ten chunks of 104 columns finished their pre-pass
+  // 1.4 ms after the last copy, four chunks of 256 right behind it)
+  if (pipelined) chunk = std::max<int64_t>(chunk, std::min<int64_t>(cus, (n_samp / 4) & ~(int64_t)1));
+  // A row-major view gives the chunk as n_feat runs of `chunk` cells, and 8 MB of a tall matrix are few columns (four
+  // float64 columns at 262 144 rows: runs of 32 bytes).  The host's packing rate grows with the run up to about 512
+  // bytes (DESIGN.md section 11 has the figures), so a row-major chunk is at least that wide where a half of the
+  // staging blocks stays within 64 MB.
+  if (view == K0_VIEW_ROW) {
+    const size_t es = elem_bytes;
+    chunk = std::max<int64_t>(chunk, (int64_t)std::min(kRowRunBytes / es, std::max<size_t>(1, kRowHalfMax / ((size_t)n_feat * es))));
+  }
+  if (prepass == kPrepassFull) chunk = std::min<int64_t>(chunk, std::max(1, sort_chunk));
+  return chunk;
 }
 
 }  // namespace host

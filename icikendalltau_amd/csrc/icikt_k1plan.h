@@ -1,9 +1,10 @@
 // icikt_k1plan.h -- the pair kernel's launch plan (k1_pairs): the LDS layout and the option word the
 // kernel and the plan share, the plan itself (plan_k1), the verdict on the prepared columns' tie structure (tie_verdict),
-// the task list (combn_pairs, build_units) and the grid of a launch (k1_grid).  Host arithmetic only: no device header,
+// the task list (combn_pairs, build_units), its slices by column chunk for the pipelined host entries (combn_chunk_units,
+// order_units_by_chunk) and the grid of a launch (k1_grid).  Host arithmetic only: no device header,
 // so tests/k1plan_print.cpp compiles it with the host compiler alone (tests/test_k1plan_host.py).  Part of
 // icikt_device.h -- the shared layout keeps its __host__ __device__ there through ICIKT_HD -- and of icikt_host.h;
-// icikt_capi.cpp holds the callers, which fill the context, talk to the device and print the verbose lines.
+// icikt_pipeline.cpp holds the callers, which fill the context, talk to the device and print the verbose lines.
 #ifndef ICIKT_K1PLAN_H
 #define ICIKT_K1PLAN_H
 
@@ -302,7 +303,7 @@ inline K1Plan plan_k1(int n, int Wp, int64_t n_pairs, int n_cu, const PlanOverri
 // average fewer than 32 rows per group -- run their tie steps one pair after the other whatever shares the wave, and one
 // pair per wave then has twice the waves to hide a step's latency: 50 000 x 512 columns of ~10-row groups 123 -> 88 ms;
 // columns of long groups share their gathers and keep two pairs per wave, 75 against 113 ms).  st: the statistics of the
-// columns read back (matrix_tied, icikt_capi.cpp: up to 64 of them, once per prepared matrix) of n rows each; long_cols:
+// columns read back (matrix_tied, icikt_pipeline.cpp: up to 64 of them, once per prepared matrix) of n rows each; long_cols:
 // too long for the half-wave kernels.
 struct TieVerdict {
   int tied_state, ntg_hint, group_hint;          // as icikt_ctx keeps them (icikt_host.h)
@@ -415,6 +416,68 @@ inline void build_units(const std::vector<int32_t>& h_pi, const std::vector<int3
       }
     }
   }
+}
+
+// The pipelined host entries launch the pair kernel once per column chunk, over the tasks whose LAST column arrived
+// with that chunk.  Two producers of those slices, one rule -- for the full triangle they give the same lists
+// (tests/test_k1plan_host.py):
+
+// All pairs of the upper triangle of S columns: a chunk's tasks are arithmetic.  The tasks whose last column lies in
+// [cb, ce), as (p0, p1 | -1), written at u (the caller's pinned staging buffer: no host copy of the pair list is ever
+// made); returns their count.  Order inside a chunk: gathered block, then streamed column (the order build_units gives:
+// a block's rec table stays in cache); np == 2: a task is the two pairs (2a, j), (2a + 1, j) that share their streamed
+// column j, the pair (2a, 2a + 1) runs alone; np == 1: i, then j.
+inline size_t combn_chunk_units(int64_t S, int64_t cb, int64_t ce, int np, int32_t* u) {
+  auto pidx = [S](int64_t i, int64_t j) { return (int32_t)(i * (2 * S - i - 1) / 2 + (j - i - 1)); };
+  size_t nt = 0;
+  if (np == 2) {
+    for (int64_t a2 = 0; a2 < ce; a2 += 2) {          // gathered block: columns a2, a2 + 1
+      const int64_t c1 = a2 + 1;
+      for (int64_t j = std::max(cb, a2 + 1); j < ce; ++j) {
+        if (j == c1) { u[2 * nt] = pidx(a2, c1); u[2 * nt + 1] = -1; }
+        else { u[2 * nt] = pidx(a2, j); u[2 * nt + 1] = pidx(c1, j); }
+        ++nt;
+      }
+    }
+  } else {
+    for (int64_t i = 0; i < ce; ++i)
+      for (int64_t j = std::max(cb, i + 1); j < ce; ++j) { u[2 * nt] = pidx(i, j); u[2 * nt + 1] = -1; ++nt; }
+  }
+  return nt;
+}
+
+// Any pair list (pi[p], pj[p]): its task list `units` (build_units) reordered by the chunk of a task's last column
+// (a stable counting sort: inside a chunk the cache-friendly order stays).  Columns [.., chunk_col_end[q]) have arrived
+// with chunk q; the tasks of chunk q end up at [first[q], first[q + 1]) -- first has nchunks + 1 entries.
+inline void order_units_by_chunk(std::vector<int32_t>& units, const int32_t* pi, const int32_t* pj,
+                                 const std::vector<int64_t>& chunk_col_end, std::vector<int>& first) {
+  const size_t nchunks = chunk_col_end.size();
+  first.assign(nchunks + 1, 0);
+  if (nchunks == 0) return;
+  const int T = (int)(units.size() / 2);
+  std::vector<int32_t> col_chunk((size_t)std::max<int64_t>(chunk_col_end.back(), 0), 0);
+  size_t k = 0;
+  for (size_t col = 0; col < col_chunk.size(); ++col) {
+    while (k + 1 < nchunks && (int64_t)col >= chunk_col_end[k]) ++k;
+    col_chunk[col] = (int32_t)k;
+  }
+  std::vector<int32_t> tchunk((size_t)T);
+  for (int t = 0; t < T; ++t) {
+    const int32_t p0 = units[2 * (size_t)t], p1 = units[2 * (size_t)t + 1];
+    int32_t col = std::max(pi[p0], pj[p0]);
+    if (p1 >= 0) col = std::max(col, std::max(pi[p1], pj[p1]));
+    tchunk[(size_t)t] = (size_t)col < col_chunk.size() ? col_chunk[(size_t)col] : (int32_t)(nchunks - 1);
+    first[(size_t)tchunk[(size_t)t] + 1] += 1;
+  }
+  for (size_t q = 0; q < nchunks; ++q) first[q + 1] += first[q];
+  std::vector<int> fill(first.begin(), first.end() - 1);
+  std::vector<int32_t> sorted((size_t)T * 2);
+  for (int t = 0; t < T; ++t) {
+    const int d = fill[(size_t)tchunk[(size_t)t]]++;
+    sorted[2 * (size_t)d] = units[2 * (size_t)t];
+    sorted[2 * (size_t)d + 1] = units[2 * (size_t)t + 1];
+  }
+  units.swap(sorted);
 }
 
 // The grid of one launch of the pair kernel over `count` tasks.

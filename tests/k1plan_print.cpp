@@ -7,6 +7,10 @@
 //                                                            -> [tied_state, ntg_hint, group_hint]
 //   combn S BEGIN END                                        the pairs of a combn range -> [[pi ...], [pj ...]]
 //   units NP P pi[P] pj[P]                                   the task list -> [p0, p1, p0, p1, ...]
+//   chunkunits S NP K end[K]                                 the full triangle's tasks by the chunk of their last column, from
+//                                                            combn_chunk_units called chunk after chunk (columns
+//                                                            [end[q-1], end[q]) arrive with chunk q) -> [first[K+1], units]
+//   chunkorder NP P pi[P] pj[P] K end[K]                     the same shape from build_units followed by order_units_by_chunk
 //   grid NP HALF_ITEMS WPB SPLIT OPTS COUNT PER_CU NCU GRIDMULT GRIDCAP
 //                                                            the grid of a launch -> [split, opts, blocks, persistent]
 #include <cstdio>
@@ -84,6 +88,45 @@ int main() {
       kp::build_units(pi, pj, P, np, u);
       print_ints(u);
       std::printf("\n");
+    } else if (cmd == "chunkunits" || cmd == "chunkorder") {
+      std::vector<int32_t> u;
+      std::vector<int> first;
+      std::vector<int64_t> ends;
+      auto read_ends = [&ends]() {
+        long long K;
+        if (!(std::cin >> K) || K < 0) return false;
+        ends.resize((size_t)K);
+        for (auto& e : ends) if (!(std::cin >> e)) return false;
+        return true;
+      };
+      if (cmd == "chunkunits") {
+        long long S;
+        int np;
+        if (!(std::cin >> S >> np) || S < 0 || !read_ends()) return 2;
+        u.resize((size_t)(S * (S - 1) / 2 + S + 8) * 2);   // (the staging buffer's capacity: upload_prepare_pairs)
+        first.assign(1, 0);
+        int64_t cb = 0;
+        for (const int64_t ce : ends) {
+          first.push_back(first.back() + (int)kp::combn_chunk_units(S, cb, ce, np, u.data() + 2 * (size_t)first.back()));
+          cb = ce;
+        }
+        u.resize(2 * (size_t)first.back());
+      } else {
+        int np;
+        long long P;
+        if (!(std::cin >> np >> P) || P < 0) return 2;
+        std::vector<int32_t> pi((size_t)P), pj((size_t)P);
+        for (auto& x : pi) if (!(std::cin >> x)) return 2;
+        for (auto& x : pj) if (!(std::cin >> x)) return 2;
+        if (!read_ends()) return 2;
+        kp::build_units(pi, pj, P, np, u);
+        kp::order_units_by_chunk(u, pi.data(), pj.data(), ends, first);
+      }
+      std::printf("[");
+      print_ints(std::vector<int32_t>(first.begin(), first.end()));
+      std::printf(", ");
+      print_ints(u);
+      std::printf("]\n");
     } else if (cmd == "grid") {
       kp::K1Plan pl{};
       int count, per_cu, n_cu, mult, cap;

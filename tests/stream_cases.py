@@ -19,7 +19,7 @@ SENTINEL = -7.0
 NAN_RATE = 0.08
 MAX_FEATURES = 65535                       # ICIKT_MAX_FEATURES: longer columns run the plain 32-bit path, exact integers
 
-# column length -> the launch family or the edge it stands for (csrc/icikt_capi.cpp: plan_k1, matrix_tied, icikt_run_dev)
+# column length -> the launch family or the edge it stands for (csrc/icikt_k1plan.h: plan_k1; icikt_pipeline.cpp: matrix_tied, run_counts)
 LENGTHS = {
     40: "short columns, half-wave kernels",
     700: "short columns, half-wave kernels",

@@ -42,7 +42,7 @@ TRUE, DECOY = "true", "decoy"
 
 def run_dev_synchronises(n):
     """include/icikt.h, "Stream contract": the first icikt_run_dev behind a pre-pass reads the column statistics back
-    for columns of 14 273 to 65 535 rows (csrc/icikt_capi.cpp: matrix_tied; k1_half_items(Wp) >= 9, not wide)."""
+    for columns of 14 273 to 65 535 rows (csrc/icikt_pipeline.cpp: matrix_tied; k1_half_items(Wp) >= 9, not wide)."""
     return 14272 < n <= 65535
 
 

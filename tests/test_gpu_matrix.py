@@ -302,8 +302,32 @@ def test_pipelined_host_path(plan_ctx):
         assert all(np.array_equal(a, b, equal_nan=True) for a, b in zip(ref_lst, got)), plan
         got = plan_ctx.matrix(X, (float("nan"),))
         assert all(np.array_equal(a, b, equal_nan=True) for a, b in zip(ref_mat, got)), plan
+    # an odd column count (the last gathered block has one column; chunks of 116, 116 and 69 columns), a launch per chunk
+    # (merge=0) and one launch behind the last chunk (merge=1)
+    S3 = 301
+    X3 = np.asfortranarray(np.concatenate([X, np.round(X[:, :1] * 3)], axis=1))
+    assert X3.shape == (n, S3)
+    rng3 = np.random.default_rng(13)
+    iu, ju = np.triu_indices(S3, k=0)
+    sel = rng3.permutation(len(iu))[:5000]
+    qi3 = np.where(rng3.random(len(sel)) < 0.5, iu[sel], ju[sel]).astype(np.int32)
+    qj3 = np.where(qi3 == iu[sel], ju[sel], iu[sel]).astype(np.int32)
+    assert S3 - 1 in qi3 or S3 - 1 in qj3
+    plan_ctx.debug_set_plan({"pipe": 0})
+    ref_all = plan_ctx.pairs(X3, perspective="global")
+    ref_lst = plan_ctx.pairs(X3, qi3, qj3, "local")
+    ref_mat = plan_ctx.matrix(X3, (float("nan"),))
+    for plan in ({"pipe": 1, "merge": 0}, {"pipe": 1, "merge": 1}, {"pipe": 1, "merge": 0, "np": 1},
+                 {"pipe": 1, "merge": 1, "np": 1}):
+        plan_ctx.debug_set_plan(plan)
+        got = plan_ctx.pairs(X3, perspective="global")
+        assert all(np.array_equal(a, b, equal_nan=True) for a, b in zip(ref_all, got)), plan
+        got = plan_ctx.pairs(X3, qi3, qj3, "local")
+        assert all(np.array_equal(a, b, equal_nan=True) for a, b in zip(ref_lst, got)), plan
+        got = plan_ctx.matrix(X3, (float("nan"),))
+        assert all(np.array_equal(a, b, equal_nan=True) for a, b in zip(ref_mat, got)), plan
     # long columns: the persistent kernel (pend in global memory) launched once per chunk
-    n2, S2 = 40000, 60                                   # 19 MB in chunks of 26 columns
+    n2, S2 = 40000, 60                                  # 19 MB in chunks of 26 columns
     X2 = np.asfortranarray(rng.standard_normal((n2, S2)))
     X2[rng.random((n2, S2)) < 0.03] = np.nan
     X2[:, 3] = np.round(X2[:, 3] * 20)

@@ -1,6 +1,6 @@
 """The long-column pair kernels under -m gpu: pairs on the whole wave (k1_pairs<1, 0> / <2, 0>: one pair, or two one after
 the other), a persistent grid whose waves FETCH many tasks in order from per-XCD counters and re-initialise their LDS
-state per task (icikt_capi.cpp: launch_pair_tasks; icikt_kernels.hip: the task loop of k1_pairs).  The natural plan of
+state per task (icikt_pipeline.cpp: launch_pair_tasks; icikt_kernels.hip: the task loop of k1_pairs).  The natural plan of
 the small matrices an oracle can afford gives every wave at most one task, so the grid is capped through
 icikt_debug_set_plan("gridcap=...") -- every wave then runs ten or more tasks back to back -- plus one natural-plan
 case with more tasks than resident waves, the c4b configuration (Bernoulli(0.1) missingness,

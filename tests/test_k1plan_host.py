@@ -11,7 +11,11 @@ cases are generated here, in a fixed order:
   plan_sha256  per (plan key, CUs) the SHA-256 of the printed rows of the whole grid;
   tied, combn, units, grid   the printed values of the other cases, in full.
 Beside equality with the fixture the tests assert what must hold whatever the plan decides: the LDS a plan asks for,
-the task list's invariants, the verdict on either side of its thresholds and the grid's arithmetic."""
+the task list's invariants, the verdict on either side of its thresholds and the grid's arithmetic.
+
+The task slices of the pipelined host entries (combn_chunk_units, order_units_by_chunk: the tasks by the chunk in which
+their last column arrives) have their cases and their fixture, tests/golden/pipeline_parent.json, at the end of the
+file; how that fixture was recorded is said there."""
 import hashlib
 import json
 import os
@@ -245,10 +249,15 @@ def run_sections(prog):
 
 
 @pytest.fixture(scope="module")
-def got(tmp_path_factory):
+def prog(tmp_path_factory):
     out = str(tmp_path_factory.mktemp("k1plan") / "k1plan_print")
     compile_printer(SRC, out)
-    return run_sections(out)
+    return out
+
+
+@pytest.fixture(scope="module")
+def got(prog):
+    return run_sections(prog)
 
 
 @pytest.fixture(scope="module")
@@ -360,3 +369,151 @@ def test_grid(got, golden):
     assert [json.loads(l) for l in got["grid"]] == golden["grid"]
     for (case, want), l in zip(GRID_CASES, got["grid"]):
         assert json.loads(l) == want, case
+
+
+# ---- the pipelined host entries' task slices: tasks by the chunk in which their last column arrives ----
+# tests/golden/pipeline_parent.json holds what the code printed while it stood inline in upload_prepare_pairs
+# (icikt_capi.cpp): that function's chunk callback for the full triangle and its counting sort over build_units' list were
+# compiled as they were into a stand-alone program beside the parent's icikt_k1plan.h, and run once on the cases below.
+#   triangle_sha256   {"chunkunits" | "chunkorder": SHA-256 of the rows of every triangle case, in triangle_cases() order}
+#   chunkorder        {"<list>@np<np>@<ends>": [first, units]} of the explicit lists
+PIPE_GOLDEN = os.path.join(ROOT, "tests", "golden", "pipeline_parent.json")
+TRIANGLE_S = range(2, 42)
+
+
+def chunk_ends(S):
+    """Ways to cut S columns into chunks, as the chunks' ends (the last one is S): a single chunk, one-column chunks,
+    even and odd widths, an odd first chunk ahead of even ones, uneven thirds."""
+    pats = [[S], list(range(1, S + 1))]
+    pats += [list(range(w, S, w)) + [S] for w in (2, 4, 6, 16, 3, 5, 7, 15)]
+    pats += [list(range(1, S, 2)) + [S], list(range(3, S, 4)) + [S], sorted({max(1, S // 3), max(1, S // 2), S})]
+    out = []
+    for p in pats:
+        if p not in out:
+            out.append(p)
+    return out
+
+
+def triangle_cases():
+    return [(S, np_, ends) for S in TRIANGLE_S for np_ in (1, 2) for ends in chunk_ends(S)]
+
+
+def explicit_lists():
+    """name -> (pi, pj, S): a subset of the pairs i <= j of S columns -- self pairs among them -- each in either
+    orientation, shuffled: build_units takes its unsorted branch."""
+    L = {}
+    for S, per_mille, seed in ((7, 1000, 3), (12, 600, 5), (20, 500, 7), (33, 350, 11)):
+        iu, ju = np.triu_indices(S, k=0)
+        pi, pj, x = [], [], seed
+        for i, j in zip(iu, ju):
+            x = (1103515245 * x + 12345) % (1 << 31)
+            if (x >> 8) % 1000 >= per_mille:
+                continue
+            x = (1103515245 * x + 12345) % (1 << 31)
+            i, j = (int(j), int(i)) if (x >> 8) & 1 else (int(i), int(j))
+            pi.append(i)
+            pj.append(j)
+        L[f"list{S}"] = (*shuffled(pi, pj, seed), S)
+    return L
+
+
+def explicit_ends(S):
+    return [[S], list(range(1, S + 1)), list(range(2, S, 2)) + [S], list(range(5, S, 5)) + [S], list(range(1, S, 2)) + [S]]
+
+
+def explicit_cases():
+    return [(name, np_, ends) for name, (_, _, S) in explicit_lists().items() for np_ in (1, 2) for ends in explicit_ends(S)]
+
+
+def chunkorder_line(np_, pi, pj, ends):
+    return " ".join(str(v) for v in ["chunkorder", np_, len(pi), *pi, *pj, len(ends), *ends])
+
+
+def chunk_lines():
+    """{section: lines}, in the order of the program's output."""
+    lists = explicit_lists()
+    tri = {S: combn_ref(S, 0, S * (S - 1) // 2) for S in TRIANGLE_S}
+    return {
+        "tri_units": [" ".join(str(v) for v in ["chunkunits", S, np_, len(ends), *ends]) for S, np_, ends in triangle_cases()],
+        "tri_order": [chunkorder_line(np_, *tri[S], ends) for S, np_, ends in triangle_cases()],
+        "tri_build": [" ".join(str(v) for v in ["units", np_, len(tri[S][0]), *tri[S][0], *tri[S][1]])
+                      for S in TRIANGLE_S for np_ in (1, 2)],
+        "list_order": [chunkorder_line(np_, *lists[name][:2], ends) for name, np_, ends in explicit_cases()],
+        "list_build": [" ".join(str(v) for v in ["units", np_, len(lists[name][0]), *lists[name][0], *lists[name][1]])
+                       for name in lists for np_ in (1, 2)],
+    }
+
+
+def run_chunk_sections(prog):
+    sections = chunk_lines()
+    r = subprocess.run([prog], input="\n".join(l for ls in sections.values() for l in ls) + "\n", capture_output=True, text=True)
+    assert r.returncode == 0, r.stderr[-2000:]
+    out = r.stdout.split("\n")
+    assert out[-1] == "" and len(out) - 1 == sum(len(ls) for ls in sections.values())
+    got, at = {}, 0
+    for name, ls in sections.items():
+        got[name] = out[at:at + len(ls)]
+        at += len(ls)
+    return got
+
+
+@pytest.fixture(scope="module")
+def chunks(prog):
+    return run_chunk_sections(prog)
+
+
+@pytest.fixture(scope="module")
+def pipe_golden():
+    with open(PIPE_GOLDEN) as f:
+        return json.load(f)
+
+
+def by_chunk(units, pi, pj, ends):
+    """[first, units] as the rule states it: the tasks of build_units' list whose last column lies in [ends[q-1],
+    ends[q]), chunk after chunk, in build_units' order inside a chunk."""
+    groups = [[] for _ in ends]
+    for t in zip(units[0::2], units[1::2]):
+        last = max(max(pi[p], pj[p]) for p in t if p >= 0)
+        groups[next(q for q, e in enumerate(ends) if last < e)].append(t)
+    first = [0]
+    for g in groups:
+        first.append(first[-1] + len(g))
+    return [first, [p for g in groups for t in g for p in t]]
+
+
+def test_triangle_slices_one_rule(chunks, pipe_golden):
+    """For the full triangle the arithmetic producer (combn_chunk_units, chunk after chunk) and the sorting one
+    (build_units + order_units_by_chunk) print the same values, the parent's; and those are the rule's: a permutation
+    of build_units' list, every task in the chunk of its last column, build_units' order inside a chunk."""
+    cases = triangle_cases()
+    assert len(cases) >= 800
+    assert chunks["tri_units"] == chunks["tri_order"]
+    assert digest(chunks["tri_units"]) == pipe_golden["triangle_sha256"]["chunkunits"]
+    assert digest(chunks["tri_order"]) == pipe_golden["triangle_sha256"]["chunkorder"]
+    built = {(S, np_): json.loads(l) for (S, np_), l in zip(((S, np_) for S in TRIANGLE_S for np_ in (1, 2)), chunks["tri_build"])}
+    shapes = set()
+    for (S, np_, ends), row in zip(cases, chunks["tri_units"]):
+        pi, pj = combn_ref(S, 0, S * (S - 1) // 2)
+        assert json.loads(row) == by_chunk(built[(S, np_)], pi, pj, ends), (S, np_, ends)
+        shapes |= {"single"} if len(ends) == 1 else set()
+        shapes |= {"columns"} if len(ends) == S and S > 1 else set()
+        shapes |= {"odd"} if any(e % 2 for e in ends[:-1]) else set()
+        shapes |= {"even"} if len(ends) > 1 and not any(e % 2 for e in ends[:-1]) else set()
+    assert shapes == {"single", "columns", "odd", "even"}
+
+
+def test_explicit_list_slices(chunks, pipe_golden):
+    lists = explicit_lists()
+    for name, (pi, pj, S) in lists.items():
+        assert any(i > j for i, j in zip(pi, pj)) and any(i < j for i, j in zip(pi, pj)) and any(i == j for i, j in zip(pi, pj))
+        assert list(zip(pi, pj)) != sorted(zip(pi, pj)), name          # the unsorted branch of build_units
+    built = {(name, np_): json.loads(l) for (name, np_), l in zip(((n_, p_) for n_ in lists for p_ in (1, 2)), chunks["list_build"])}
+    assert len(pipe_golden["chunkorder"]) == len(explicit_cases())
+    for (name, np_, ends), row in zip(explicit_cases(), chunks["list_order"]):
+        pi, pj, _ = lists[name]
+        got = json.loads(row)
+        assert got == pipe_golden["chunkorder"][f"{name}@np{np_}@{'-'.join(str(e) for e in ends)}"], (name, np_, ends)
+        assert got == by_chunk(built[(name, np_)], pi, pj, ends), (name, np_, ends)
+        assert len(got[0]) == len(ends) + 1 and got[0][-1] * 2 == len(got[1])
+    for name in lists:   # two pairs per wave do pair up some of a shuffled list
+        assert len(built[(name, 2)]) < len(built[(name, 1)]), name
