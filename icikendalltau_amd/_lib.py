@@ -96,6 +96,7 @@ EXPORTS = (
     "icikt_hclust_f64", "icikt_hclust_in", "icikt_hclust_csc",
     "icikt_anosim_f64", "icikt_anosim_in", "icikt_anosim_csc",
     "icikt_cross_f64", "icikt_cross_in",
+    "icikt_ref_prepare_f64", "icikt_ref_prepare_in", "icikt_ref_cross_f64", "icikt_ref_cross_in", "icikt_ref_info",
 )
 
 # icikt_input: the caller's matrix as a typed, strided view (ICIKT_DTYPE_*, ICIKT_ORDER_*)
@@ -399,6 +400,13 @@ def lib():
                   c_vp]
     L.icikt_cross_f64.argtypes = [c_vp, c_vp, c_i64, c_vp, c_i64] + cross_tail
     L.icikt_cross_in.argtypes = [c_vp, ctypes.POINTER(InputView), ctypes.POINTER(InputView)] + cross_tail
+    ref_prepare_tail = [c_i64, c_i64, c_i64, c_vp, c_int, c_u32]
+    L.icikt_ref_prepare_f64.argtypes = [c_vp, c_vp, c_i64] + ref_prepare_tail
+    L.icikt_ref_prepare_in.argtypes = [c_vp, ctypes.POINTER(InputView)] + ref_prepare_tail
+    ref_cross_tail = [c_i64, c_i64, c_int, c_vp, c_int, c_int, c_int, c_int, c_u32, c_int] + [c_vp] * 8
+    L.icikt_ref_cross_f64.argtypes = [c_vp, c_vp, c_i64] + ref_cross_tail
+    L.icikt_ref_cross_in.argtypes = [c_vp, ctypes.POINTER(InputView)] + ref_cross_tail
+    L.icikt_ref_info.argtypes = [c_vp, c_vp, c_vp, c_vp]
     L.icikt_multi_rank_phase_ms.argtypes = [c_vp, c_int, ctypes.POINTER(ctypes.c_double)]
     L.icikt_multi_ranks_used.argtypes = [c_vp]
     L.icikt_debug_step_stats.argtypes = [c_vp, c_vp, c_int]
@@ -756,6 +764,78 @@ class Context:
             n_valid = np.zeros(Sq, dtype=np.int32)
         return out5, idx, vals, n_valid, *sel(global_na, perspective, alternative, continuity, scale_max, (kk,),
                                               (_ptr(out5), _ptr(idx), _ptr(vals), _ptr(n_valid)))
+
+    def _cross_view(self, X, flags):
+        """(array, view, n_feat, n_samp, flags) of one matrix of cross / prepare_reference / cross_prepared: read where
+        it lies, a sparse matrix densified; with f64_entries an F-ordered float64 copy."""
+        if is_sparse(X):
+            X = csc_view(X).toarray()
+        if self.f64_entries:
+            X = np.asfortranarray(X, dtype=np.float64)
+        return _view_arg(X, flags)
+
+    def prepare_reference(self, reference, query_capacity, global_na=None, flags: int = 0):
+        """Upload and pre-pass `reference` (n_feat x Sr) once and keep it on this context (icikt_ref_prepare_in), with
+        room for batches of up to `query_capacity` query columns: cross_prepared() then brings a batch alone.  global_na
+        as matrix() takes it; it is recorded and applies to every batch.  Any other call on this context that computes
+        pairs drops the reference (cross_prepared raises afterwards): give a reference that is to stay a context of its
+        own.  The argument checks are the library's: a capacity below 1, or more than 65 535 columns in all, raises
+        IciktError."""
+        ra, rv, n_feat, Sr, flags = self._cross_view(reference, flags)
+        gna = np.ascontiguousarray([] if global_na is None else np.atleast_1d(global_na), dtype=np.float64)
+        tail = (n_feat, Sr, int(query_capacity), _ptr(gna) if gna.size else None, int(gna.size), flags)
+        if self.f64_entries:
+            self._chk(lib().icikt_ref_prepare_f64(self._h, _ptr(ra), rv.ld, *tail), "icikt_ref_prepare_f64")
+        else:
+            self._chk(lib().icikt_ref_prepare_in(self._h, ctypes.byref(rv), *tail), "icikt_ref_prepare_in")
+
+    def reference_info(self):
+        """(n_feat, n_reference, query_capacity) of the prepared reference; raises IciktError when there is none."""
+        a, b, c = ctypes.c_int64(0), ctypes.c_int64(0), ctypes.c_int64(0)
+        self._chk(lib().icikt_ref_info(self._h, ctypes.byref(a), ctypes.byref(b), ctypes.byref(c)), "icikt_ref_info")
+        return a.value, b.value, c.value
+
+    def cross_prepared(self, query, k=None, want_matrix=True, ref_cls=None, n_class=0, perspective="global",
+                       alternative="two.sided", continuity=False, flags: int = 0, scale_max=True):
+        """cross() of `query` (n_feat x Sq) against the reference prepare_reference() left on this context
+        (icikt_ref_cross_in): only the batch is uploaded and pre-passed, under the recorded global_na.  k and
+        want_matrix as cross() takes them.  ref_cls: a class index in 0 .. n_class - 1 per reference column; with it
+        the call also reduces every query's median to every class on the device.  Returns cross()'s six items and then
+        (med2 [2, Sq, n_class]: cor, raw -- NA_real_ for a cell without a valid partner -- or None; n_valid [Sq,
+        n_class] or None), views of the library's layout with the query index fastest.  The argument checks are the
+        library's: no prepared reference, other rows than the reference's, a batch wider than the capacity, a class
+        index out of range raise IciktError, and a refused call leaves the reference as it was."""
+        qa, qv, n_feat, Sq, flags = self._cross_view(query, flags)
+        _, Sr, _cap = self.reference_info()
+        if self.f64_entries:
+            fn, fname, xargs = lib().icikt_ref_cross_f64, "icikt_ref_cross_f64", (_ptr(qa), qv.ld)
+        else:
+            fn, fname, xargs = lib().icikt_ref_cross_in, "icikt_ref_cross_in", (ctypes.byref(qv),)
+        alloc = pinned_empty if (flags & FLAG_HOST_PINNED) else np.empty
+        out5 = alloc((5, Sq, Sr), dtype=np.float64) if want_matrix else None
+        idx = vals = n_valid = cls_a = med2 = cls_n_valid = None
+        kk = 0
+        if k is not None:
+            kk = int(k)
+            room = kk if 0 <= kk <= TOPK_MAX else 0    # (the library refuses the others before it writes)
+            idx = alloc((Sq, room), dtype=np.int32)
+            vals = alloc((5, Sq, room), dtype=np.float64)
+            n_valid = np.zeros(Sq, dtype=np.int32)
+        n_class = int(n_class)
+        if ref_cls is not None:
+            cls_a = np.ascontiguousarray(ref_cls, dtype=np.int32)
+            if cls_a.shape != (Sr,):
+                raise ValueError("ref_cls must give one class per reference column")
+            room = n_class if 1 <= n_class <= 65535 else 1
+            med2 = np.empty((2, room, Sq), dtype=np.float64)
+            cls_n_valid = np.zeros((room, Sq), dtype=np.int32)
+        persp = PERSPECTIVE.get(perspective, perspective if isinstance(perspective, int) else -1)
+        mx, rc5 = np.full(1, -np.inf), np.zeros(5, dtype=np.int64)
+        self._chk(fn(self._h, *xargs, n_feat, Sq, kk, _ptr(cls_a), n_class, persp, ALTERNATIVE.get(alternative, ALT_OTHER),
+                     int(bool(continuity)), flags, int(bool(scale_max)), _ptr(out5), _ptr(idx), _ptr(vals), _ptr(n_valid),
+                     _ptr(med2), _ptr(cls_n_valid), _ptr(mx), _ptr(rc5)), fname)
+        return (out5, idx, vals, n_valid, float(mx[0]), rc5,
+                None if med2 is None else med2.transpose(0, 2, 1), None if cls_n_valid is None else cls_n_valid.T)
 
     def class_medians(self, X, cls=None, n_class=1, global_na=None, perspective="global", alternative="two.sided",
                       continuity=False, flags: int = 0, scale_max=True):

@@ -72,6 +72,18 @@ class HipEngine:
         return self._select_ctx().cross(query, reference, k, want_matrix, global_na, perspective, alternative,
                                         continuity, self.flags | flags, scale_max)
 
+    def prepare_reference(self, reference, query_capacity, global_na=None):
+        """A reference uploaded and pre-passed once, on a context of ITS OWN on the device of the selection entries
+        (icikt_ref_prepare_f64) -- no other entry of this engine can displace it.  Returns the _lib.Context: its
+        cross_prepared() takes the batches, its close() frees the reference."""
+        ctx = _lib.Context(self._select_ctx().device)
+        try:
+            ctx.prepare_reference(reference, query_capacity, global_na, self.flags)
+        except Exception:
+            ctx.close()
+            raise
+        return ctx
+
     def edges(self, data_matrix, min_raw=None, max_pvalue=None, min_completeness=None, absolute=False, max_edges=0,
               global_na=None, perspective="global", alternative="two.sided", continuity=False, flags=0, scale_max=True):
         """Every pair past the bounds, compacted on the device (icikt_edges_f64): Context.edges' contract."""
@@ -901,9 +913,165 @@ def _cross_numpy(eng, query, reference, global_na, perspective, scale_max, alter
     return np.stack([m[block] for m in mats5]), max_taumax, run_time
 
 
-def ici_kendalltau_cross(query, reference, k=None, return_matrix=True, global_na=(float("nan"), float("inf"), 0),
+def _cross_class_numpy(cor, raw, cls, n_class):
+    """The class reduction of icikt_ref_cross_f64 from the Sq x Sr cor and raw matrices of a rectangle, for engines
+    without a prepared reference (the CPU tests' checker engines).  The partners of cell (q, c) are the reference
+    columns r with cls[r] == c whose raw with q is not NA -- there is no own sample on a rectangle; the medians are
+    _median_cell's.  Returns (med2 [2, Sq, n_class]: cor, raw; n_valid [Sq, n_class])."""
+    cor = np.ascontiguousarray(cor, dtype=np.float64)
+    raw = np.ascontiguousarray(raw, dtype=np.float64)
+    cls = np.asarray(cls)
+    Sq = raw.shape[0]
+    med2 = _na_filled((2, Sq, n_class))
+    n_valid = np.zeros((Sq, n_class), dtype=np.int32)
+    members = [cls == c for c in range(n_class)]
+    for q in range(Sq):
+        valid = ~np.isnan(raw[q])
+        for c in range(n_class):
+            partners = np.nonzero(members[c] & valid)[0]
+            n_valid[q, c] = len(partners)
+            if len(partners):
+                med2[0, q, c], med2[1, q, c] = _median_cell(cor, raw, q, partners)
+    return med2, n_valid
+
+
+def _global_na_rule(global_na):
+    """What a global_na list excludes, whatever its order or repeats: (NA, Inf, the finite values)."""
+    vals = [float(v) for v in np.atleast_1d(np.asarray([] if global_na is None else global_na, dtype=np.float64))]
+    return (any(math.isnan(v) for v in vals), any(math.isinf(v) for v in vals),
+            frozenset(v for v in vals if math.isfinite(v)))
+
+
+_CROSS_GLOBAL_NA = (float("nan"), float("inf"), 0)   # ici_kendalltau_cross' default, told from a caller's value by identity
+
+
+class PreparedReference:
+    """A reference cohort kept ready for batch after batch of ``ici_kendalltau_cross`` (``prepare_reference`` makes it).
+
+    On the HIP engine the reference is uploaded and pre-passed once and stays on the device, on a context of its own, so
+    no other call can displace it; ``close()`` (or leaving a ``with`` block) frees it.  On an engine without a prepared
+    reference (the CPU tests' checker engines) it holds the host matrix and every batch takes the numpy route.  It
+    carries what a batch needs beside its own columns: ``reference_names``, ``global_na``, ``class_levels`` and
+    ``class_codes`` (None without classes), ``n_feat``, ``n_reference`` and ``query_capacity``."""
+
+    def __init__(self, engine, reference, names, query_capacity, global_na, levels, codes):
+        self.engine = engine
+        self.reference_names = list(names)
+        self.n_feat, self.n_reference = reference.shape
+        self.query_capacity = int(query_capacity)
+        self.global_na = global_na
+        self.class_levels = None if levels is None else list(levels)
+        self.class_codes = codes
+        self._matrix = self._ctx = None
+        if hasattr(engine, "prepare_reference"):
+            masked, self._device_na = _mask_on_host(reference, global_na)
+            self._ctx = engine.prepare_reference(masked, self.query_capacity, self._device_na)
+        else:
+            self._matrix = np.asarray(reference, dtype=np.float64)
+
+    def close(self):
+        """Free the device copy (a closed reference takes no more batches)."""
+        if self._ctx is not None:
+            self._ctx.close()
+        self._ctx = self._matrix = None
+        self.engine = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+        return False
+
+    def _batch(self, query, k, want_matrix, want_classes, perspective, scale_max, alternative, continuity):
+        """One batch of at most query_capacity columns: (out5, idx, vals, n_valid, max_taumax, med2, cls_n_valid, seconds),
+        the tables as Context.cross_prepared returns them."""
+        if self.engine is None:
+            raise ValueError("this PreparedReference has been closed")
+        n_class = len(self.class_levels) if want_classes else 0
+        if self._ctx is not None:
+            query, _ = _mask_on_host(query, self.global_na)
+            (out5, idx, vals, n_valid, max_taumax, med2, cls_n_valid), t_diff = _timed(
+                lambda: _rcounts_last(self._ctx.cross_prepared(
+                    query, k, want_matrix, self.class_codes if want_classes else None, n_class, perspective, alternative,
+                    continuity, getattr(self.engine, "flags", 0), scale_max)))
+            return out5, idx, vals, n_valid, max_taumax, med2, cls_n_valid, t_diff
+        out5, max_taumax, t_diff = _cross_numpy(self.engine, query, self._matrix, self.global_na, perspective, scale_max,
+                                                alternative, continuity)
+        idx = vals = n_valid = med2 = cls_n_valid = None
+        if k is not None:
+            idx, vals, n_valid = _cross_topk_numpy(out5, k)
+        if want_classes:
+            med2, cls_n_valid = _cross_class_numpy(out5[0], out5[1], self.class_codes, n_class)
+        return out5, idx, vals, n_valid, max_taumax, med2, cls_n_valid, t_diff
+
+
+def _rcounts_last(items):
+    """Context.cross_prepared's tuple with reason_counts moved to the end, where _timed takes it from."""
+    out5, idx, vals, n_valid, max_taumax, rcounts, med2, cls_n_valid = items
+    return out5, idx, vals, n_valid, max_taumax, med2, cls_n_valid, rcounts
+
+
+def prepare_reference(reference, query_capacity=1024, global_na=(float("nan"), float("inf"), 0), reference_names=None,
+                      reference_classes=None, engine=None):
+    """Keep ``reference`` (features x Sr) ready for ``ici_kendalltau_cross``: on the HIP engine it is uploaded and
+    pre-passed here, once, and every later batch brings its own columns alone (icikt_ref_prepare_f64).
+
+    ``query_capacity`` (an integer of at least 1) is the widest batch the device copy takes in one call; its memory is
+    allocated here and never grows, and a wider batch is split by ``ici_kendalltau_cross``.  Sr + query_capacity is at
+    most 65 535 (one less for each of the two that is odd).  ``global_na`` is recorded and applies to every batch.
+    ``reference_names`` as ``ici_kendalltau_cross`` takes them; ``reference_classes`` gives one label per reference
+    column and makes every batch return the class tables.  Returns a ``PreparedReference``; close it, or use it in a
+    ``with`` block, to free the device memory."""
+    query_capacity = _int_arg(query_capacity, 1, _lib.TOPK_MAX_SAMPLES,
+                              f"`query_capacity` must be an integer in 1 .. {_lib.TOPK_MAX_SAMPLES}")
+    reference, rnames = _as_matrix(reference, reference_names, "reference", keep_dtype=True)
+    levels = codes = None
+    if reference_classes is not None:
+        try:
+            levels, codes = _class_levels(reference_classes, reference.shape[1], "all")
+        except ValueError:
+            raise ValueError("`reference_classes` must give one class per column of `reference`") from None
+    return PreparedReference(engine or _default_engine(), reference, rnames, query_capacity, global_na, levels, codes)
+
+
+def _cross_prepared(query, prepared, k, return_matrix, perspective, scale_max, alternative, continuity):
+    """ici_kendalltau_cross against a PreparedReference: the batch in capacity-sized parts, stitched."""
+    Sq, cap = query.shape[1], prepared.query_capacity
+    classes = prepared.class_levels is not None
+    parts = [prepared._batch(query[:, a:a + cap], k, return_matrix, classes, perspective, scale_max, alternative, continuity)
+             for a in range(0, max(Sq, 1), cap)]
+    widths = [min(cap, Sq - a) for a in range(0, max(Sq, 1), cap)]
+    max_taumax = max(p[4] for p in parts)
+    t_diff = sum(p[7] for p in parts)
+
+    def stitch(item, axis):
+        return parts[0][item] if len(parts) == 1 else np.concatenate([p[item] for p in parts], axis=axis)
+
+    out5 = stitch(0, 1) if return_matrix else None
+    idx, vals, n_valid = (stitch(1, 0), stitch(2, 1), stitch(3, 0)) if k is not None else (None, None, None)
+    med2, cls_n_valid = (stitch(5, 1), stitch(6, 0)) if classes else (None, None)
+    if scale_max and len(parts) > 1:
+        # every part scaled cor by ITS largest taumax: the parts below the call's are scaled again, from raw
+        a = 0
+        for p, w in zip(parts, widths):
+            if p[4] != max_taumax:
+                rows = slice(a, a + w)
+                for planes in (out5, vals):
+                    if planes is not None:
+                        ok = ~np.isnan(planes[1][rows])
+                        planes[0][rows][ok] = planes[1][rows][ok] / max_taumax
+                if classes:   # an odd cell's median is one pair's cor; an even cell's two quotients are not kept
+                    odd, even = (cls_n_valid[rows] & 1) == 1, (cls_n_valid[rows] > 0) & ((cls_n_valid[rows] & 1) == 0)
+                    med2[0][rows][odd] = med2[1][rows][odd] / max_taumax + 0.0
+                    med2[0][rows][even] = med2[0][rows][even] * (p[4] / max_taumax)
+            a += w
+    return out5, idx, vals, n_valid, max_taumax, med2, cls_n_valid, t_diff
+
+
+def ici_kendalltau_cross(query, reference, k=None, return_matrix=True, global_na=_CROSS_GLOBAL_NA,
                          perspective="global", scale_max=True, alternative="two.sided", continuity=False,
-                         query_names=None, reference_names=None, engine=None):
+                         query_names=None, reference_names=None, reference_classes=None, engine=None):
     """ICI-Kendall-tau of every sample (column) of ``query`` with every sample of ``reference`` -- a new batch against
     a reference cohort -- and nothing else: no pair within either matrix is computed.
 
@@ -919,26 +1087,67 @@ def ici_kendalltau_cross(query, reference, k=None, return_matrix=True, global_na
     index; a pair whose ``raw`` is NA is no partner.  A sample that occurs in both matrices is a partner like any other
     (it is usually its own nearest reference sample).  The reference's warning is raised once per pair of reasons 2-4.
 
+    ``reference`` may be a ``PreparedReference`` (``prepare_reference``): the names, ``global_na`` and the classes are
+    then its own -- ``reference_names`` and ``reference_classes`` are refused, and so is a ``global_na`` that differs
+    from the one it was prepared with -- and only the batch crosses to the device.  A batch wider than its
+    ``query_capacity`` is split into capacity-sized calls and stitched; with ``scale_max`` ``cor`` is then scaled again,
+    from ``raw``, by the largest ``max_taumax`` of the parts, and ``class_med_cor`` likewise (an even cell's value by
+    the ratio of the two scales, which can differ from an unsplit call's in the last bit).  Everything derived from
+    ``raw`` alone -- ``raw``, ``pvalue``, ``taumax``, ``completeness``, the top-k selection, ``class_med_raw``,
+    ``class_n_valid``, ``nearest_class`` -- does not depend on the split.
+
+    ``reference_classes`` (one label per reference column; with a plain matrix the reference is prepared for this one
+    call) adds every query's median to every class: the partners of cell (q, c) are the reference samples of class c
+    whose pair with q has a ``raw`` that is not NA, ``class_med_raw`` is R's ``median(raw, na.rm = TRUE)`` over them and
+    ``class_med_cor`` the same over ``cor``; a cell without a partner is NA.
+
     Returns a dict.  With ``return_matrix``: ``cor, raw, pvalue, taumax, completeness`` as Sq x Sr tables, rows the
     query samples.  With ``k``: ``indices`` (Sq x k reference column indices, -1 where a query has fewer than k
     partners), ``neighbors`` (their names, None padded), ``topk_cor, topk_raw, topk_pvalue, topk_taumax,
     topk_completeness`` (Sq x k, NA padded) and ``n_valid`` (Sq); ``formats.cross_topk_to_csr`` turns them into a
-    sparse graph.  Always: ``query_names``, ``reference_names``, ``max_taumax`` and ``run_time``.  An empty ``query``
-    or ``reference`` gives empty tables.
+    sparse graph.  With classes: ``class_med_cor``, ``class_med_raw`` and ``class_n_valid`` (Sq x C tables, the class
+    levels as columns), ``class_levels`` and ``nearest_class`` (per query the label of the class with the largest
+    ``class_med_raw`` among the cells with a partner, ties to the earlier class, None without one).  Always:
+    ``query_names``, ``reference_names``, ``max_taumax`` and ``run_time``.  An empty ``query`` or ``reference`` gives
+    empty tables.
     """
     if k is not None:
         k = _int_arg(k, 1, _lib.TOPK_MAX, f"`k` must be None or an integer in 1 .. {_lib.TOPK_MAX}")
-    elif not return_matrix:
+    elif not return_matrix and reference_classes is None and not (isinstance(reference, PreparedReference)
+                                                                  and reference.class_levels is not None):
         raise ValueError("nothing to return: give `k`, or leave `return_matrix` set")
     query, qnames = _as_matrix(query, query_names, "query", keep_dtype=True)
-    reference, rnames = _as_matrix(reference, reference_names, "reference", keep_dtype=True)
-    if query.shape[0] != reference.shape[0]:
-        raise ValueError(f"`query` has {query.shape[0]} rows (features) and `reference` has {reference.shape[0]}: "
+    prepared = reference if isinstance(reference, PreparedReference) else None
+    eng = engine or (prepared.engine if prepared is not None else _default_engine())
+    out5 = idx = vals = n_valid = med2 = cls_n_valid = None
+    if prepared is not None:
+        if reference_names is not None or reference_classes is not None:
+            raise ValueError("`reference_names` and `reference_classes` belong to the PreparedReference: give them to "
+                             "prepare_reference")
+        if global_na is not _CROSS_GLOBAL_NA and _global_na_rule(global_na) != _global_na_rule(prepared.global_na):
+            raise ValueError("`global_na` differs from the one the PreparedReference was prepared with")
+        if engine is not None and engine is not prepared.engine:
+            raise ValueError("`engine` differs from the PreparedReference's")
+    else:
+        reference, rnames = _as_matrix(reference, reference_names, "reference", keep_dtype=True)
+    n_ref_rows = prepared.n_feat if prepared is not None else reference.shape[0]
+    if query.shape[0] != n_ref_rows:
+        raise ValueError(f"`query` has {query.shape[0]} rows (features) and `reference` has {n_ref_rows}: "
                          "the two must share their rows")
-    Sq, Sr = query.shape[1], reference.shape[1]
-    eng = engine or _default_engine()
-    out5 = idx = vals = n_valid = None
-    if hasattr(eng, "cross"):   # (two matrices, handed over as they are: the parts of _on_device that fit)
+    Sq = query.shape[1]
+    if prepared is None and reference_classes is not None:
+        # a labelled plain matrix: prepared for this one call, with room for the whole batch
+        Sr = reference.shape[1]
+        room = _lib.TOPK_MAX_SAMPLES - Sr - (Sr & 1)
+        cap = max(1, min(Sq, room - (room & 1)))
+        with prepare_reference(reference, cap, global_na, rnames, reference_classes, eng) as temp:
+            return ici_kendalltau_cross(query, temp, k, return_matrix, perspective=perspective, scale_max=scale_max,
+                                        alternative=alternative, continuity=continuity, query_names=qnames, engine=eng)
+    if prepared is not None:
+        rnames = prepared.reference_names
+        out5, idx, vals, n_valid, max_taumax, med2, cls_n_valid, t_diff = _cross_prepared(
+            query, prepared, k, return_matrix, perspective, scale_max, alternative, continuity)
+    elif hasattr(eng, "cross"):   # (two matrices, handed over as they are: the parts of _on_device that fit)
         query, _ = _mask_on_host(query, global_na)
         reference, global_na = _mask_on_host(reference, global_na)
         (out5, idx, vals, n_valid, max_taumax), t_diff = _timed(
@@ -959,6 +1168,16 @@ def ici_kendalltau_cross(query, reference, k=None, return_matrix=True, global_na
         res["neighbors"] = names_arr[idx]    # (-1 picks the None behind the names)
         _put_values(res, vals, "topk_")
         res["n_valid"] = n_valid
+    if med2 is not None:
+        levels = prepared.class_levels
+
+        def table(values):
+            return pd.DataFrame(values, index=list(qnames), columns=list(levels)) if pd is not None else values
+        res["class_med_cor"] = table(med2[0])
+        res["class_med_raw"] = table(med2[1])
+        res["class_n_valid"] = table(cls_n_valid)
+        res["class_levels"] = list(levels)
+        res["nearest_class"] = _nearest_class(med2[1], cls_n_valid, levels)
     res["query_names"] = list(qnames)
     res["reference_names"] = list(rnames)
     res["max_taumax"] = max_taumax

@@ -56,6 +56,9 @@ inline std::vector<std::pair<int, int>> cut_rect_rows(int64_t Sq, int64_t Sr, in
 // the device column of reference column 0: the query columns come first, and the reference starts on an even column
 // (the pre-pass's tables are interleaved in blocks of two columns), behind one padding column when Sq is odd
 inline int64_t rect_ref_col(int64_t Sq) { return Sq + (Sq & 1); }
+// the mirror layout of a reference that stays prepared (icikt_ref_*): the reference columns come first, and the query
+// batch starts on an even column, behind one padding column when Sr is odd -- the device column of query column 0
+inline int64_t ref_query_col(int64_t Sr) { return Sr + (Sr & 1); }
 
 // the members of the classes, class by class in class-index order, ascending sample index inside a class
 struct ClassRuns {
@@ -133,7 +136,7 @@ inline ClassIndex class_index(const int32_t* cls, int64_t S) {
 
 // one block of a call: pairs [begin, begin + count) of the call's pair order -- rows [row_first, row_last) of the
 // combn triangle, or (pi != null) a slice of the class list as sample indices, or (pi != null, row_last > row_first)
-// query rows [row_first, row_last) of the rectangle as device columns; pi / pj are valid until the next block is asked for
+// query rows [row_first, row_last) of the rectangle as device columns (either layout); pi / pj are valid until the next block is asked for
 struct PairBlock {
   int64_t begin = 0, count = 0;
   int row_first = 0, row_last = 0;
@@ -179,6 +182,14 @@ class PairBlocks {
     for (const auto& b : p.rows_) p.block_max = std::max(p.block_max, (int64_t)(b.second - b.first) * Sr);
     return p;
   }
+  // the same rectangle, the same cut and the same pair order over the mirror layout (the reference first, icikt_ref_*):
+  // a block's pi / pj are (ref_query_col(Sr) + q, r) -- the query is still the first column of a pair and the list is
+  // still sorted by (pi, pj), with pi > pj
+  static PairBlocks rect_ref_first(int64_t Sq, int64_t Sr, int64_t budget) {
+    PairBlocks p = rect(Sq, Sr, budget);
+    p.ref_first_ = true;
+    return p;
+  }
   int64_t S = 0, total = 0, n_blocks = 0, block_max = 1;   // S: of rows(); block_max: the largest block's pairs (at least 1)
   // the next block into *b; false behind the last one
   bool next(PairBlock* b) {
@@ -189,13 +200,13 @@ class PairBlocks {
     } else if (rect_) {
       const int first = rows_[at_].first, last = rows_[at_].second;
       const size_t count = (size_t)(last - first) * (size_t)Sr_;
-      const int32_t col0 = (int32_t)rect_ref_col(Sq_);
+      const int32_t row0 = ref_first_ ? (int32_t)ref_query_col(Sr_) : 0, col0 = ref_first_ ? 0 : (int32_t)rect_ref_col(Sq_);
       pi_.resize(count);
       pj_.resize(count);
       size_t p = 0;
       for (int q = first; q < last; ++q)
         for (int32_t r = 0; r < (int32_t)Sr_; ++r, ++p) {
-          pi_[p] = (int32_t)q;
+          pi_[p] = row0 + (int32_t)q;
           pj_[p] = col0 + r;
         }
       *b = PairBlock{(int64_t)first * Sr_, (int64_t)count, first, last, pi_.data(), pj_.data()};
@@ -212,7 +223,7 @@ class PairBlocks {
   std::vector<std::pair<int, int>> rows_;
   const ClassRuns* cr_ = nullptr;
   PairCursor cur_;
-  bool rect_ = false;
+  bool rect_ = false, ref_first_ = false;
   int64_t Sq_ = 0, Sr_ = 0;
   int64_t budget_ = 0, at_ = 0, done_ = 0;
   std::vector<int32_t> pi_, pj_;

@@ -1,11 +1,14 @@
-// icikt_cross.hip -- the folds of the query x reference rectangle (icikt_cross_f64, host side: icikt_capi_cross.cpp).
+// icikt_cross.hip -- the folds of the query x reference rectangle (icikt_cross_f64, icikt_ref_cross_f64; host side:
+// icikt_capi_cross.cpp).
 //
 // The pair engine runs the rectangle in blocks of whole query rows; a block's out4 records are query-major, so the Sr
 // records of a query lie one behind the other and are all there.  k_cross_topk therefore selects a query's k best
 // reference columns in ONE pass over its row and writes the final lists: no list survives a block, nothing is merged
 // at the end.  k_cross_planes turns a block's records into the four value planes at the block's place.  cor needs the
 // largest taumax of the whole rectangle (word 0 of d_red), which is final only behind the last block: k_cross_cor
-// fills that plane then.  No kernel here waits for another workgroup, and none uses a global atomic.
+// fills that plane then.  With class labels on the reference, k_cross_class finds the two middle raw of every (query,
+// class) cell inside the row's own block -- a radix select over the class's records of the row (icikt_select.h) -- and
+// k_cross_class_cor turns them into the medians behind the last block.  No kernel here waits for another workgroup, and none uses a global atomic.
 //
 // The order of a list is icikt_topk.hip's, STRICT: raw descending in the total order of the sortable key (-0.0 below
 // +0.0), ties by the smaller reference index.  The threshold test, the compaction and the sort all go through
@@ -14,7 +17,9 @@
 
 #include <cstdint>
 
+#include "icikt_colsort.h"
 #include "icikt_device.h"
+#include "icikt_select.h"
 
 namespace icikt {
 
@@ -183,7 +188,76 @@ k_cross_pad(double* __restrict__ col, int n) {
   if (t < n) col[t] = __longlong_as_double(0x7FF8000000000000ll);
 }
 
+// The class fold (icikt_ref_cross_*: a labelled reference).  One workgroup per cell (query row blockIdx.x of the block,
+// class blockIdx.y).  Class c is member[first[c] .. first[c + 1]), reference columns; key t of the cell is the raw of the
+// row's record of member[first[c] + t] as a sortable key (colsort::cor_key: NA_KEY for an NA pair, a zero as +0).  The
+// row's records are all in this block, so the cell is final here: cells [2][C][Sq] takes its lower and its upper middle
+// KEY (k_cross_class_cor turns them into values once the scale is known), n_valid [C][Sq] its partners.  stage: keys the
+// LDS buffer takes (<= MEDIAN_STAGE_MAX); a larger cell re-reads the member list and the records in every pass.
+__global__ void __launch_bounds__(colsort::CT)
+k_cross_class(const double* __restrict__ out4, const int32_t* __restrict__ member, const int32_t* __restrict__ first, int Sr,
+              int n_class, int row_first, long long Sq, int stage, unsigned long long* __restrict__ cells,
+              int32_t* __restrict__ n_valid) {
+  __shared__ unsigned long long s_keys[MEDIAN_STAGE_MAX];
+  __shared__ sel::Scratch s_sel;
+  const int tid = threadIdx.x;
+  const int c = (int)blockIdx.y;
+  if (c >= n_class) return;
+  const double* __restrict__ row = out4 + 4 * (size_t)blockIdx.x * (size_t)Sr;
+  const int f0 = first[c];
+  const int T = first[c + 1] - f0;
+  const bool staged = T <= stage;
+  auto load = [&](int t) -> unsigned long long { return colsort::cor_key(row[4 * (size_t)member[f0 + t]]); };
+  if (staged)
+    for (int t = tid; t < T; t += colsort::CT) s_keys[t] = load(t);
+  __syncthreads();
+  auto key_at = [&](int t) -> unsigned long long { return staged ? s_keys[t] : load(t); };
+
+  unsigned long long lower = 0ull, upper = 0ull;
+  const int v = sel::middle_keys(T, key_at, s_sel, &lower, &upper);
+  if (tid != 0) return;
+  const size_t plane = (size_t)Sq * (size_t)n_class, cell = (size_t)c * (size_t)Sq + (size_t)row_first + blockIdx.x;
+  cells[cell] = v ? lower : 0ull;
+  cells[plane + cell] = v ? upper : 0ull;
+  n_valid[cell] = v;
+}
+
+// cells [2][n_cells]: the middle keys k_cross_class left -> (med_cor, med_raw) in their place, once red is final; a
+// cell without a partner is NA_real_.  The values are sel::median_values', as in k_class_select.
+__global__ void __launch_bounds__(256)
+k_cross_class_cor(const unsigned long long* __restrict__ red, int scale_max, const int32_t* __restrict__ n_valid,
+                  long long n_cells, unsigned long long* cells) {
+  const long long t = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (t >= n_cells) return;
+  const int v = n_valid[t];
+  double med_cor = cx_na(), med_raw = cx_na();
+  if (v > 0) sel::median_values(cells[t], cells[n_cells + t], v, red[0], scale_max, &med_cor, &med_raw);
+  cells[t] = (unsigned long long)__double_as_longlong(med_cor);
+  cells[n_cells + t] = (unsigned long long)__double_as_longlong(med_raw);
+}
+
 }  // namespace
+
+hipError_t launch_cross_class(const double* out4, const int32_t* member, const int32_t* first, int Sr, int n_class,
+                              int row_first, int n_rows, long long Sq, int stage, double* med2, int32_t* n_valid,
+                              hipStream_t s) {
+  if (Sr < 1 || n_class < 1 || n_class > CLASS_MATRIX_MAX_CLASSES || row_first < 0 || n_rows < 1 ||
+      (long long)row_first + n_rows > Sq || stage < 0 || stage > MEDIAN_STAGE_MAX)
+    return hipErrorInvalidValue;
+  (void)hipGetLastError();
+  hipLaunchKernelGGL(k_cross_class, dim3((unsigned)n_rows, (unsigned)n_class), dim3(colsort::CT), 0, s, out4, member, first,
+                     Sr, n_class, row_first, Sq, stage, reinterpret_cast<unsigned long long*>(med2), n_valid);
+  return hipGetLastError();
+}
+
+hipError_t launch_cross_class_cor(const unsigned long long* red, int scale_max, const int32_t* n_valid, long long n_cells,
+                                  double* med2, hipStream_t s) {
+  if (n_cells <= 0) return hipSuccess;
+  (void)hipGetLastError();
+  hipLaunchKernelGGL(k_cross_class_cor, dim3((unsigned)((n_cells + 255) / 256)), dim3(256), 0, s, red, scale_max, n_valid,
+                     n_cells, reinterpret_cast<unsigned long long*>(med2));
+  return hipGetLastError();
+}
 
 hipError_t launch_cross_topk(const double* out4, int Sr, int k, int row_first, int n_rows, long long Sq, int32_t* idx,
                              double* planes, int32_t* n_valid, hipStream_t s) {

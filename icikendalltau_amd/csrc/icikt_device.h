@@ -179,6 +179,16 @@ hipError_t launch_cross_cor(const unsigned long long* red, int scale_max, const 
                             hipStream_t s);
 // n cells of NaN: the padding column behind an odd number of query columns
 hipError_t launch_cross_pad(double* col, int n, hipStream_t s);
+// The class fold of a labelled reference.  out4: the records of query rows [row_first, row_first + n_rows), as
+// launch_cross_topk takes them; member [Sr]: the reference columns sorted stably by class; first [n_class + 1]: class c
+// is member[first[c] .. first[c + 1]).  Leaves every (row, class) cell's two middle keys in med2 [2][n_class][Sq] and
+// its partners in n_valid [n_class][Sq]; stage as launch_median_select takes it.  launch_cross_class_cor, once red
+// (launch_out_stats' record) is final: med2 becomes (cor, raw), NA_real_ for a cell without partners; n_cells = n_class Sq
+hipError_t launch_cross_class(const double* out4, const int32_t* member, const int32_t* first, int Sr, int n_class,
+                              int row_first, int n_rows, long long Sq, int stage, double* med2, int32_t* n_valid,
+                              hipStream_t s);
+hipError_t launch_cross_class_cor(const unsigned long long* red, int scale_max, const int32_t* n_valid, long long n_cells,
+                                  double* med2, hipStream_t s);
 // ---- pairs past a threshold, compacted in combn order (icikt_edges.hip) ----
 struct EdgeRule {              // == icikt_edge_rule: a NaN bound is no bound
   double min_raw, max_pvalue, min_completeness;

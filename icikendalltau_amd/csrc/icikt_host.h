@@ -129,11 +129,22 @@ struct icikt_ctx {
   } topk;
 
   // query x reference rectangle (icikt_cross_f64): the five planes [5][Sq Sr] when the matrices are asked for, and the
-  // queries' lists (idx [Sq][k], out [5][Sq][k], n_valid [Sq])
+  // queries' lists (idx [Sq][k], out [5][Sq][k], n_valid [Sq]); with class labels on the reference (icikt_ref_cross_f64)
+  // the reference columns sorted by class with each class's range, and the results per (class, query) cell
   struct CrossBufs {
-    DevBuf<double> planes, out;
-    DevBuf<int32_t> idx, n_valid;
+    DevBuf<double> planes, out, med2;
+    DevBuf<int32_t> idx, n_valid, member, first, cls_n_valid;
   } cross;
+
+  // a reference that stays prepared (icikt_ref_prepare_f64): device columns [0, n_reference) of d_X and of the prepared
+  // state hold the reference, pre-passed under `ms`; the query batches of icikt_ref_cross_f64 land at
+  // ref_query_col(n_reference).  Dropped (valid = false) by whatever replaces the prepared state: prepare_alloc,
+  // mask_alloc, forget_prepared.
+  struct RefState {
+    bool valid = false;
+    int64_t n_feat = 0, n_reference = 0, capacity = 0;
+    icikt::MaskSpec ms{};
+  } ref;
 
   // pairs past a threshold (icikt_edges_f64): a block's ballot words, tile counts and tile bases, the running total
   // (word 0 of `total`), the degrees and the planes of the kept edges
@@ -263,8 +274,10 @@ int timer_end(icikt_ctx* c, int k, uint32_t flags);
 
 // The end of a call that left its own scratch columns and pair list in the context, nothing of the caller's (the
 // selection entries, icikt_pairs_complete_*): forget the prepared state and the pair list.  The device-resident calls
-// start over (icikt_run_dev: ICIKT_E_STATE until icikt_prepare_dev and a pair list; icikt_num_pairs: -1).
+// start over (icikt_run_dev: ICIKT_E_STATE until icikt_prepare_dev and a pair list; icikt_num_pairs: -1), and a
+// prepared reference is gone (icikt_ref_cross_*: ICIKT_E_STATE).
 inline void forget_prepared(icikt_ctx* c) {
+  c->ref.valid = false;   // (icikt_ref_cross_* alone puts it back: its blocks run beside the reference's tables)
   c->prepared = false;
   c->raw_valid = false;
   c->n_pairs = -1;
@@ -295,6 +308,9 @@ int upload_and_prepare(icikt_ctx* c, const MatrixSrc& X, int64_t n_feat, int64_t
 // Leaves the pair kernel's counts in c->d_raw (raw_valid): the caller runs the epilogue (icikt_run_dev with
 // ICIKT_FLAG_REUSE_COUNTS).
 int upload_prepare_pairs(icikt_ctx* c, const MatrixSrc& X, int64_t n_feat, int64_t n_samp, uint32_t flags);
+// The tie verdict (matrix_tied) on the first min(64, pv.n_samp) prepared columns now, where a plan asks for one: it is
+// kept until the next prepare_launch.  Waits for c->stream when it reads the statistics back.
+void settle_tie_verdict(icikt_ctx* c);
 // global_na values (NaN = NA, +-Inf = Inf, anything else compared with ==) -> the pre-pass's exclusion rule
 int make_mask_spec(icikt_ctx* c, const double* global_na, int n_global_na, icikt::MaskSpec* ms);
 // Build the pair kernel's task list on the host now (prepare_alloc and a pair list must be in place).

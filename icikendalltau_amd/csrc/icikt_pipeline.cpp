@@ -26,6 +26,7 @@ namespace icikt {
 namespace host {
 
 int prepare_alloc(icikt_ctx* c, int64_t n_feat, int64_t n_samp, int64_t alloc_cols, int64_t sort_cols) {
+  c->ref.valid = false;   // the tables are laid out anew: a prepared reference is gone
   c->prepared = false;
   c->raw_valid = false;
   PrepView pv{};
@@ -101,6 +102,7 @@ int prepare_alloc(icikt_ctx* c, int64_t n_feat, int64_t n_samp, int64_t alloc_co
 }
 
 int mask_alloc(icikt_ctx* c, int64_t n_feat, int64_t n_samp) {
+  c->ref.valid = false;
   c->prepared = false;
   c->raw_valid = false;
   PrepView pv{};
@@ -170,6 +172,8 @@ static bool matrix_tied(icikt_ctx* c, int64_t ncols_ready, hipEvent_t ready) {
                                   long_cols ? (c->tied_state ? "one pair per wave" : "two pairs per wave") : (c->tied_state ? "half-wave kernels" : "whole-wave kernels"));
   return c->tied_state != 0;
 }
+
+void settle_tie_verdict(icikt_ctx* c) { (void)matrix_tied(c, c->pv.n_samp, nullptr); }
 
 // the host copies of a combn range (the device arrays were filled by a kernel)
 static void ensure_host_pairs(icikt_ctx* c) {

@@ -717,6 +717,57 @@ int icikt_cross_in(icikt_ctx *ctx, const icikt_input *Q, const icikt_input *R, i
                    int alternative, int continuity, uint32_t flags, int scale_max, double *out5, int32_t *idx,
                    double *out5k, int32_t *n_valid, double *max_taumax, int64_t *reason_counts);
 
+/* ---- a reference cohort that stays prepared: batch after batch against the same reference ------------------------------
+ *
+ * icikt_cross_f64 uploads and pre-passes the reference with every call.  icikt_ref_prepare_f64 does that ONCE and leaves
+ * the reference on the context; icikt_ref_cross_f64 then brings a batch of query columns alone and computes the same
+ * rectangle, bit for bit.  The device matrix is the mirror of icikt_cross_f64's: the reference in columns
+ * 0 .. n_reference - 1, one all-missing padding column when n_reference is odd, the batch from there on.
+ *
+ * icikt_ref_prepare_f64: R (n_feat x n_reference, leading dimension ld_reference), n_reference >= 1; global_na as
+ * icikt_matrix_f64 takes it -- the rule is recorded and applies to every batch.  query_capacity >= 1 is the largest batch
+ * the context will take: device memory for the reference and that many query columns is allocated here, once, and
+ * never grows (0 is no way to say "unbounded": ICIKT_E_INVALID).  n_reference + query_capacity, plus one for each of
+ * the two that is odd, is at most ICIKT_TOPK_MAX_SAMPLES (ICIKT_E_INVALID beyond, the message names the limit); n_feat
+ * as icikt_topk_f64 takes it.  A second call replaces the reference.  icikt_run_dev answers ICIKT_E_STATE afterwards: the
+ * prepared state is the reference's, not the device-resident calls'.
+ * WHAT DROPS THE REFERENCE: every call that replaces the context's prepared state -- icikt_prepare_*, every host entry
+ * that computes pairs or a missingness (icikt_pairs_*, icikt_matrix_*, icikt_pairs_complete_*, icikt_missingness_*,
+ * the selection entries, icikt_cross_*), and an icikt_ref_cross_* that fails after its argument checks.  The next
+ * icikt_ref_cross_* then returns ICIKT_E_STATE; it never reads tables another call has rewritten.  A caller that wants
+ * the reference kept gives it a context of its own.
+ *
+ * icikt_ref_cross_f64: Q (n_feat x n_query, ld_query) against the prepared reference; n_feat must be the reference's and
+ * n_query at most query_capacity (ICIKT_E_INVALID, the context and the reference stay as they are); no prepared
+ * reference: ICIKT_E_STATE.  k, perspective ... scale_max, out5, idx, out5k, n_valid, max_taumax, reason_counts and
+ * every refusal: as icikt_cross_f64, with n_reference the prepared one.  The call takes no global_na.
+ *   ref_cls      (optional) [n_reference] a class index in 0 .. n_class - 1 per reference column, 1 <= n_class <= 65535;
+ *                classes may be empty.  A class index outside the range is ICIKT_E_INVALID before anything is touched.
+ *   cls_med2     (optional, needs ref_cls) [2][n_class][n_query], the query index fastest: med_cor and med_raw of cell
+ *                (q, c).  The partners of the cell are the reference columns r of class c whose raw with q is not NA -- a
+ *                column that occurs in both matrices is a partner like any other.  med_raw is R's median(raw, na.rm =
+ *                TRUE) over them (a zero counts as +0; an even count: the correctly rounded mean of the two middle
+ *                values); med_cor is the same rule on the cor cells of those one or two middle pairs (raw over the
+ *                rectangle's largest taumax when scale_max, each quotient rounded first).  No partner: R's NA_real_
+ *   cls_n_valid  (optional, needs ref_cls) [n_class][n_query] partners per cell
+ * At least one output must be given.  n_query == 0: the empty result of icikt_cross_f64.  Device memory beside
+ * icikt_cross_f64's: 20 n_query n_class bytes of cells and 4 n_reference bytes of member list (and 4 (n_class + 1)).
+ * icikt_ref_info: the prepared reference's shape (any pointer may be null); ICIKT_E_STATE when there is none.
+ * The _in twins: the same on a typed view of the matrix (icikt_input, below). */
+int icikt_ref_prepare_f64(icikt_ctx *ctx, const double *R, int64_t ld_reference, int64_t n_feat, int64_t n_reference,
+                          int64_t query_capacity, const double *global_na, int n_global_na, uint32_t flags);
+int icikt_ref_prepare_in(icikt_ctx *ctx, const icikt_input *R, int64_t n_feat, int64_t n_reference,
+                         int64_t query_capacity, const double *global_na, int n_global_na, uint32_t flags);
+int icikt_ref_cross_f64(icikt_ctx *ctx, const double *Q, int64_t ld_query, int64_t n_feat, int64_t n_query, int k,
+                        const int32_t *ref_cls, int n_class, int perspective, int alternative, int continuity,
+                        uint32_t flags, int scale_max, double *out5, int32_t *idx, double *out5k, int32_t *n_valid,
+                        double *cls_med2, int32_t *cls_n_valid, double *max_taumax, int64_t *reason_counts);
+int icikt_ref_cross_in(icikt_ctx *ctx, const icikt_input *Q, int64_t n_feat, int64_t n_query, int k,
+                       const int32_t *ref_cls, int n_class, int perspective, int alternative, int continuity,
+                       uint32_t flags, int scale_max, double *out5, int32_t *idx, double *out5k, int32_t *n_valid,
+                       double *cls_med2, int32_t *cls_n_valid, double *max_taumax, int64_t *reason_counts);
+int icikt_ref_info(icikt_ctx *ctx, int64_t *n_feat, int64_t *n_reference, int64_t *query_capacity);
+
 /* ---- several GPUs behind one call (what the R glue binds when n_gpu > 1) ----------------------
  *
  * Replaces the reference's worker fan-out, computation$split_fun(split_comparisons, ici_split, ...)
