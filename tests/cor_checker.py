@@ -5,6 +5,9 @@ the AS 89 Edgeworth series (10 <= n < 1290, no ties) and Spearman's continuity c
 takes the front end's own restatement (icikendalltau_amd.api).  The series itself is pinned elsewhere, as DESIGN.md
 section 9 says: tests/spearman_exact.py holds ``api._prho`` and the device to the exact permutation distribution at
 n = 10 .. 16 within AS 89's own error, and to the t tail at n = 1289; the continuity correction stays unpinned.
+The t tail itself (every Pearson p-value, Spearman's with ties or at n >= 1290) is held here to scipy's betainc only at
+the rho the data happens to have; tests/t_tail_exact.py holds ``api.cor_test_pvalue`` and the device to a series at
+400 digits on the designed (n, rho) lattice of tests/cor_lattice.py.
 
 For ill-conditioned data (large offsets, extreme scales, a pair's rows far from its column's mean) scipy is no
 reference: ``exact_pearson`` is, Pearson's rho of the given doubles in exact integer arithmetic, rounded once."""
@@ -102,7 +105,7 @@ def spearman_pvalue(rho, n, alternative, continuity, ties):
 def pearson_pvalue(rho, n, alternative):
     """cor.test's Pearson p-value at rho over n rows (t = sqrt(n - 2) rho / sqrt(1 - rho^2), df = n - 2)."""
     with np.errstate(divide="ignore", invalid="ignore"):
-        t = float(np.sqrt(np.float64(n - 2)) * rho / np.sqrt(np.float64(1 - rho * rho)))
+        t = float(np.sqrt(np.float64(n - 2)) * rho / np.sqrt(np.float64((1 - rho) * (1 + rho))))
     return t_pvalue(t, n - 2, alternative)
 
 
