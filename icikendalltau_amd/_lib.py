@@ -27,13 +27,14 @@ SOURCES = [os.path.join(_PKG, "csrc", f) for f in ("icikt_kernels.hip", "icikt_p
                                                        "icikt_mst.hip", "icikt_capi_mst.cpp",
                                                        "icikt_hclust.hip", "icikt_capi_hclust.cpp",
                                                        "icikt_anosim.hip", "icikt_capi_anosim.cpp",
+                                                       "icikt_permanova.hip", "icikt_capi_permanova.cpp",
                                                        "icikt_cross.hip", "icikt_capi_cross.cpp")]
 HEADERS = [os.path.join(_ROOT, "include", "icikt.h"), os.path.join(_PKG, "csrc", "icikt_device.h"),
            os.path.join(_PKG, "csrc", "icikt_wave.h"), os.path.join(_PKG, "csrc", "icikt_host.h"),
            os.path.join(_PKG, "csrc", "icikt_transfer.h"), os.path.join(_PKG, "csrc", "icikt_colsort.h"),
            os.path.join(_PKG, "csrc", "icikt_blocks.h"), os.path.join(_PKG, "csrc", "icikt_select.h"),
            os.path.join(_PKG, "csrc", "icikt_keys.h"), os.path.join(_PKG, "csrc", "icikt_k0plan.h"),
-           os.path.join(_PKG, "csrc", "icikt_k1plan.h")]
+           os.path.join(_PKG, "csrc", "icikt_k1plan.h"), os.path.join(_PKG, "csrc", "icikt_fixed.h")]
 
 # include/icikt.h
 SUCCESS = 0
@@ -56,6 +57,7 @@ ADJUST = {"bonferroni": 0, "holm": 1, "hochberg": 2, "BH": 3}   # ICIKT_ADJUST_*
 ADJUST_MAX_ALPHA = 16         # ICIKT_ADJUST_MAX_ALPHA: alphas per call of icikt_padjust_*
 HCLUST = {"complete": 0, "average": 1, "single": 2}   # ICIKT_HCLUST_*: linkage methods of icikt_hclust_*
 ANOSIM_MAX_PERM = 1000000     # ICIKT_ANOSIM_MAX_PERM: labellings per call of icikt_anosim_* beside the observed one
+PERMANOVA_MAX_CELLS = 1 << 26  # ICIKT_PERMANOVA_MAX_CELLS: (1 + n_perm) n_class of icikt_permanova_*
 MASK_VALS = 32                # distinct finite global_na values of the device-side exclusion rule (icikt_device.h)
 MAX_FEATURES = 65535          # the tuned kernels
 MAX_FEATURES_WIDE = 262144    # the plain 32-bit path (exact integer arithmetic)
@@ -95,6 +97,7 @@ EXPORTS = (
     "icikt_mst_f64", "icikt_mst_in", "icikt_mst_csc",
     "icikt_hclust_f64", "icikt_hclust_in", "icikt_hclust_csc",
     "icikt_anosim_f64", "icikt_anosim_in", "icikt_anosim_csc",
+    "icikt_permanova_f64", "icikt_permanova_in", "icikt_permanova_csc",
     "icikt_cross_f64", "icikt_cross_in",
     "icikt_ref_prepare_f64", "icikt_ref_prepare_in", "icikt_ref_cross_f64", "icikt_ref_cross_in", "icikt_ref_info",
 )
@@ -395,6 +398,8 @@ def lib():
                                    ctypes.c_double, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]
     L.icikt_anosim_f64.argtypes = [c_vp, c_vp, c_i64, c_i64, c_i64, c_vp, c_int, c_int, c_int, c_int, c_u32, c_vp, c_int,
                                    c_vp, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]
+    L.icikt_permanova_f64.argtypes = [c_vp, c_vp, c_i64, c_i64, c_i64, c_vp, c_int, c_int, c_int, c_int, c_u32, c_vp,
+                                      c_int, c_vp, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]
     # (two matrices: the twins are spelled out)
     cross_tail = [c_i64, c_i64, c_i64, c_vp, c_int, c_int, c_int, c_int, c_int, c_u32, c_int, c_vp, c_vp, c_vp, c_vp, c_vp,
                   c_vp]
@@ -412,13 +417,15 @@ def lib():
     L.icikt_debug_step_stats.argtypes = [c_vp, c_vp, c_int]
     # the *_in twins: (ctx, const icikt_input*, n_feat, n_samp, ...) where the _f64 entry has (ctx, X, n_feat, n_samp, ld, ...)
     for nm in ("pairs", "matrix", "pairs_complete", "missingness", "cor_pairs", "col_medians", "censor_counts",
-               "rank_order", "topk", "edges", "class_medians", "quantiles", "class_matrix", "padjust", "mst", "hclust", "anosim"):
+               "rank_order", "topk", "edges", "class_medians", "quantiles", "class_matrix", "padjust", "mst", "hclust", "anosim",
+               "permanova"):
         f64 = getattr(L, f"icikt_{nm}_f64").argtypes
         getattr(L, f"icikt_{nm}_in").argtypes = [c_vp, ctypes.POINTER(InputView), c_i64, c_i64] + list(f64[5:])
     L.icikt_convert_dev.argtypes = [c_vp, c_vp, c_int, c_int, c_i64, c_i64, c_i64, c_vp, c_i64]
     # the *_csc twins: (ctx, const icikt_csc_input*, n_feat, n_samp, ...)
     for nm in ("pairs", "matrix", "missingness", "col_medians", "censor_counts", "rank_order", "topk", "edges",
-               "class_medians", "quantiles", "class_matrix", "padjust", "mst", "hclust", "anosim"):
+               "class_medians", "quantiles", "class_matrix", "padjust", "mst", "hclust", "anosim",
+               "permanova"):
         f64 = getattr(L, f"icikt_{nm}_f64").argtypes
         getattr(L, f"icikt_{nm}_csc").argtypes = [c_vp, ctypes.POINTER(CscInput), c_i64, c_i64] + list(f64[5:])
     L.icikt_scatter_csc_dev.argtypes = [c_vp, c_vp, c_vp, c_vp, c_int, c_int, ctypes.c_double, c_i64, c_i64, c_vp, c_i64]
@@ -487,8 +494,8 @@ def _matrix_call(fn, handle, chk, X, global_na, pi, pj, perspective, alternative
 
 
 class _SelectCall:
-    """What the ten selection entries (topk, cross, edges, class_medians, class_matrix, quantiles, padjust, mst, hclust,
-    anosim) share around their own arguments.  An instance holds a resolved entry (what Context._entry returns; the
+    """What the eleven selection entries (topk, cross, edges, class_medians, class_matrix, quantiles, padjust, mst, hclust,
+    anosim, permanova) share around their own arguments.  An instance holds a resolved entry (what Context._entry returns; the
     array behind its arguments stays alive with it), n_samp and flags as that entry sees them, and alloc: the allocator
     of the result arrays that are pinned when the call says so.  Calling it makes the checked call fn(ctx, <X>,
     global_na, n_global_na, *before, perspective, alternative, continuity, flags[, scale_max], *after, max_taumax,
@@ -1027,6 +1034,44 @@ class Context:
                    (_ptr(cls_a), n_class, _ptr(perm_a) if n_perm else None, n_perm, _ptr(n_pairs), _ptr(w2), _ptr(nw),
                     _ptr(n_ge), _ptr(n_undef), _ptr(class_w2), _ptr(class_nw)))
         return n_pairs, w2, nw, int(n_ge[0]), int(n_undef[0]), class_w2, class_nw, *tail
+
+    def permanova(self, X, cls=None, n_class=1, perm_cls=None, global_na=None, perspective="global",
+                  alternative="two.sided", continuity=False, flags: int = 0):
+        """PERMANOVA's integer sums of the classes under the dissimilarity 1 - raw, on the device
+        (icikt_permanova_f64): all pairs are computed, their (1 - raw)^2 turned into the fixed-point integers q
+        (csrc/icikt_fixed.h) and summed there per class and labelling.  cls, n_class, perm_cls, X and global_na as
+        anosim() takes them.  Returns (n_pairs [2] int64: values, NA pairs; Q: the sum of q over all values, a Python
+        int; class_q [1 + n_perm, n_class] of Python ints (dtype object): A_c of every labelling, row 0 the observed
+        one, all 0 when there is an NA pair; max_taumax; reason_counts [5]).  The limbs of the C ABI are combined here:
+        A = hi 2^32 + lo.  api.permanova_statistic turns (S, Q, a row of class_q, the row's class sizes) into the
+        statistic.  The argument checks are the library's: a label out of range, more than 65 535 classes, more than
+        PERMANOVA_MAX_CELLS cells or a bad perspective raises IciktError."""
+        sel = _SelectCall(self, self._entry("permanova", X, flags))
+        n_samp = sel.n_samp
+        cls_a = _class_arg(cls, n_samp)
+        if cls_a is None:
+            n_class = 1
+        n_class = int(n_class)
+        if perm_cls is None:
+            perm_a, n_perm = None, 0
+        else:
+            perm_a = np.ascontiguousarray(perm_cls, dtype=np.int32)
+            if perm_a.ndim != 2 or perm_a.shape[1] != n_samp:
+                raise ValueError("perm_cls must be [n_perm, S]: one class per column in every row")
+            n_perm = int(perm_a.shape[0])
+        room = n_class if 1 <= n_class <= 65535 else 1    # (the library refuses the others before it writes)
+        n_lab = 1 + (n_perm if n_perm <= ANOSIM_MAX_PERM else 0)
+        if n_lab * room > PERMANOVA_MAX_CELLS:
+            n_lab = 1
+        n_pairs = np.zeros(2, dtype=np.int64)
+        q_total = np.zeros(2, dtype=np.int64)
+        bins_lo = np.zeros((n_lab, room), dtype=np.int64)
+        bins_hi = np.zeros((n_lab, room), dtype=np.int64)
+        tail = sel(global_na, perspective, alternative, continuity, None, (),
+                   (_ptr(cls_a), n_class, _ptr(perm_a) if n_perm else None, n_perm, _ptr(n_pairs), _ptr(q_total),
+                    _ptr(bins_lo), _ptr(bins_hi)))
+        class_q = bins_hi.astype(object) * (1 << 32) + bins_lo.astype(object)
+        return n_pairs, (int(q_total[1]) << 32) + int(q_total[0]), class_q, *tail
 
     def edges(self, X, min_raw=None, max_pvalue=None, min_completeness=None, absolute=False, max_edges=0,
               global_na=None, perspective="global", alternative="two.sided", continuity=False, flags: int = 0,

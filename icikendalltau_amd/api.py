@@ -138,6 +138,13 @@ class HipEngine:
         return self._select_ctx().anosim(data_matrix, cls, n_class, perm_cls, global_na, perspective, alternative,
                                          continuity, self.flags | flags)
 
+    def permanova(self, data_matrix, cls=None, n_class=1, perm_cls=None, global_na=None, perspective="global",
+                  alternative="two.sided", continuity=False, flags=0):
+        """PERMANOVA's fixed-point sums per class of the observed labelling and of every permutation, on the device
+        (icikt_permanova_f64): Context.permanova's arguments and result."""
+        return self._select_ctx().permanova(data_matrix, cls, n_class, perm_cls, global_na, perspective, alternative,
+                                            continuity, self.flags | flags)
+
     def cor_pairs(self, X, pi, pj, method, pairwise, alternative, continuity):
         """cor_fast's pairs on the device (icikt_cor_pairs_f64): (out3: rho, p-value, n_values; reasons)."""
         return self.ctx.cor_pairs(X, pi, pj, method, pairwise, alternative, continuity)
@@ -2137,6 +2144,196 @@ def ici_kendalltau_anosim(data_matrix, sample_classes, permutations=999, seed=No
                within_mean_rank=as_float(Fraction(W2, 2 * nW) if nW else None),
                between_mean_rank=as_float(Fraction(M * (M + 1) - W2, 2 * (M - nW)) if M > nW else None),
                sums={"w2": w2, "nw": nw, "class_w2": class_w2, "class_nw": class_nw},
+               sample_id=list(names), max_taumax=max_taumax, run_time=t_diff)
+    return res
+
+
+# --------------------------------------------------------------------------------------------------
+# ici_kendalltau_permanova: PERMANOVA (Anderson 2001; vegan::adonis2, skbio's permanova) of the classes on the squared
+# dissimilarities (1 - raw)^2, summed as fixed-point integers (csrc/icikt_fixed.h)
+# --------------------------------------------------------------------------------------------------
+PERMANOVA_FRAC_BITS = 50   # fixed::FRAC_BITS: q = (1 - raw)^2 2^50, rounded half to even
+
+
+def _permanova_quantise(raw):
+    """fixed::quantise (csrc/icikt_fixed.h) on an array of raw values without NaN, as int64: -0 is +0, d = 1.0 - raw and
+    e = d * d in double, one rounding each, q = rint(ldexp(e, 50))."""
+    d = 1.0 - (np.asarray(raw, dtype=np.float64) + 0.0)
+    return np.rint(np.ldexp(d * d, PERMANOVA_FRAC_BITS)).astype(np.int64)
+
+
+class PermanovaStatistic(tuple):
+    """(F, r2, ss_total, ss_within, ss_among, df_among, df_within) of one labelling: exact ``Fraction``s and ints.  F is
+    None where it is undefined and ``math.inf`` when SS_W = 0 < SS_A; r2 is None when SS_T = 0."""
+    __slots__ = ()
+    F = property(lambda self: self[0])
+    r2 = property(lambda self: self[1])
+    ss_total = property(lambda self: self[2])
+    ss_within = property(lambda self: self[3])
+    ss_among = property(lambda self: self[4])
+    df_among = property(lambda self: self[5])
+    df_within = property(lambda self: self[6])
+
+
+def _permanova_ss_within(A, sizes):
+    """SS_W = sum_c A_c / (n_c 2^50) over the classes with a sample, as one Fraction over the sizes' common multiple."""
+    used = [(int(a), int(n)) for a, n in zip(A, sizes) if int(n) > 0]
+    L = math.lcm(*(n for _, n in used)) if used else 1
+    return Fraction(sum(a * (L // n) for a, n in used), L << PERMANOVA_FRAC_BITS)
+
+
+def permanova_statistic(S, Q, A, sizes):
+    """PERMANOVA's pseudo-F of one labelling, exactly, from the integers of icikt_permanova_f64: S samples, Q the sum of
+    q over all pairs, A [n_class] the sums within each class and sizes [n_class] the labelling's class sizes.  With C'
+    the classes that have a sample: SS_T = Q / (S 2^50), SS_W = sum_c A_c / (n_c 2^50), SS_A = SS_T - SS_W,
+    F = (SS_A / (C' - 1)) / (SS_W / (S - C')) and R2 = SS_A / SS_T.  F is None (undefined) when C' < 2, S <= C' or
+    SS_T = 0, and ``math.inf`` when SS_W = 0 < SS_A.  Returns a ``PermanovaStatistic``."""
+    S, Q = int(S), int(Q)
+    n_used = sum(1 for n in sizes if int(n) > 0)
+    ss_t = Fraction(Q, S << PERMANOVA_FRAC_BITS) if S > 0 else Fraction(0)
+    ss_w = _permanova_ss_within(A, sizes)
+    ss_a = ss_t - ss_w
+    df_a, df_w = n_used - 1, S - n_used
+    if n_used < 2 or df_w <= 0 or ss_t == 0:
+        F = None
+    elif ss_w == 0:
+        F = math.inf          # (SS_A = SS_T > 0 here)
+    else:
+        F = (ss_a / df_a) / (ss_w / df_w)
+    return PermanovaStatistic((F, ss_a / ss_t if ss_t != 0 else None, ss_t, ss_w, ss_a, df_a, df_w))
+
+
+def _permanova_compare(S, Q, class_q, labellings, n_class):
+    """(the observed labelling's PermanovaStatistic, the permutations' F [n_perm] -- Fraction, None or inf --, n_ge,
+    n_undefined) from the integers of every labelling; labellings [1 + n_perm, S], row 0 the observed one.  A
+    permutation with the observed class sizes is compared by SS_W alone (S, C' and SS_T are shared: F falls as SS_W
+    grows), any other through its F; both exactly."""
+    sizes = [np.bincount(lab, minlength=n_class) for lab in labellings]
+    obs = permanova_statistic(S, Q, class_q[0], sizes[0])
+    Fs, n_ge, n_undef = [], 0, 0
+    for a, sz in zip(class_q[1:], sizes[1:]):
+        if np.array_equal(sz, sizes[0]):
+            if obs.F is None:
+                f, ge = None, False
+            else:
+                ss_w = _permanova_ss_within(a, sz)
+                ge = ss_w <= obs.ss_within
+                f = math.inf if ss_w == 0 else ((obs.ss_total - ss_w) / obs.df_among) / (ss_w / obs.df_within)
+        else:
+            f = permanova_statistic(S, Q, a, sz).F
+            ge = f is not None and obs.F is not None and f >= obs.F
+        Fs.append(f)
+        n_undef += f is None
+        n_ge += bool(ge)
+    return obs, Fs, n_ge, n_undef
+
+
+def _permanova_numpy(raw, cls, n_class, perms):
+    """The integers of icikt_permanova_f64 from a full S x S raw matrix, for engines without a permanova method (the CPU
+    tests' checker engines): (n_pairs [2], Q, class_q [1 + n_perm, n_class] of Python ints).  The sums are taken limb by
+    limb in int64, as the device takes them."""
+    raw = np.asarray(raw, dtype=np.float64)
+    S = raw.shape[0]
+    iu, ju = np.triu_indices(S, k=1)
+    v = raw[iu, ju]
+    ok = ~np.isnan(v)
+    n_na = int((~ok).sum())
+    q = _permanova_quantise(v[ok])
+    lo, hi = q & 0xFFFFFFFF, q >> 32
+    labs = np.vstack([np.asarray(cls, dtype=np.int64)[None, :], np.asarray(perms, dtype=np.int64).reshape(-1, S)])
+    class_q = np.zeros((labs.shape[0], n_class), dtype=object)
+    if n_na == 0:
+        for l, lab in enumerate(labs):
+            same = lab[iu] == lab[ju]
+            a_lo, a_hi = np.zeros(n_class, dtype=np.int64), np.zeros(n_class, dtype=np.int64)
+            np.add.at(a_lo, lab[iu][same], lo[same])
+            np.add.at(a_hi, lab[iu][same], hi[same])
+            class_q[l] = a_hi.astype(object) * (1 << 32) + a_lo.astype(object)
+    return (np.array([int(ok.sum()), n_na], dtype=np.int64), (int(hi.sum()) << 32) + int(lo.sum()), class_q)
+
+
+def ici_kendalltau_permanova(data_matrix, sample_classes, permutations=999, seed=None, strata=None, return_perms=True,
+                             global_na=(float("nan"), float("inf"), 0), perspective="global",
+                             alternative="two.sided", continuity=False, colnames=None, engine=None):
+    """Do the class labels of the samples (columns) explain the structure of their ICI-Kendall-tau correlations:
+    PERMANOVA (Anderson 2001; ``vegan::adonis2``, ``skbio.stats.distance.permanova``) on the dissimilarity ``1 - raw``,
+    with its permutation test -- without the S x S matrices ``ici_kendalltau`` returns.  It is the test to report beside
+    ``ici_kendalltau_anosim``, which is the more sensitive of the two to unequal dispersion (Anderson & Walsh 2013).
+
+    ``sample_classes`` gives one label per column (required; the levels are ``ici_kendalltau_class_matrix``'s).  The sums
+    of squares partition the squared dissimilarities: ``ss_total`` is their sum over all pairs divided by S,
+    ``ss_within`` the sum over the classes of the within-class pairs' sum divided by the class size, ``ss_among`` the
+    difference; ``statistic`` is the pseudo-F ``(ss_among / df_among) / (ss_within / df_within)`` and ``r2`` is
+    ``ss_among / ss_total``, the share of the structure the labels explain.  F is NA with fewer than two classes, with
+    only singleton classes or when every dissimilarity is 0, and Inf when the classes have no spread at all.
+
+    EXACTNESS.  Every ``(1 - raw)^2`` is turned into an integer multiple of 2^-50 by one fixed rule (two double
+    operations and a rounding to even), and everything after that is integer and rational arithmetic: the result is a
+    pure function of the input and the labellings, and every double below comes from a fraction by one correctly
+    rounded conversion.  F values are compared exactly, so no margin like vegan's ``sqrt(.Machine$double.eps)`` is
+    subtracted.
+
+    EVERY PAIR IS NEEDED.  With a pair whose ``raw`` is NA (``n_na > 0``) the class weights have no meaning: nothing is
+    imputed and no pair is dropped; every statistic is NA, and one warning says so.  ``ici_kendalltau_medians`` gives
+    ``n_valid`` per column, which finds the columns to leave out.
+
+    THE PERMUTATIONS are ``ici_kendalltau_anosim``'s (``anosim_permutations``): the same ``seed`` and ``strata`` give both
+    tests the same labellings; an integer array [n_perm, S] of class codes is used as given (its class sizes may differ
+    from the observed ones).  ``pvalue`` is ``(1 + n_ge) / (1 + n_perm)`` with ``n_ge`` the labellings whose F is defined
+    and ``>=`` the observed F; ``n_undefined`` labellings have no F and do not count.  ``(1 + n_perm)`` times the number of
+    classes is at most 2^26.  The other arguments are ``ici_kendalltau``'s (column names are required).
+
+    Returns a dict: ``statistic``, ``r2``, ``pvalue``; ``ss_total``, ``ss_within``, ``ss_among``; ``df_among``,
+    ``df_within``; ``n_permutations``, ``n_ge``, ``n_undefined``, ``perm_statistic`` ([n_perm], NA where undefined; only
+    with ``return_perms``); ``n_valid``, ``n_na``; ``class_levels``, ``class_size``, ``class_ss`` (per class the
+    within-class sum divided by the class size, NA for a class without a sample); ``sums`` (the integers: ``q_total`` and
+    ``class_q`` [1 + n_perm, n_class], row 0 the observed labelling); ``sample_id``, ``max_taumax`` and ``run_time``.
+    """
+    data_matrix, names, n_sample = _select_input(data_matrix, colnames)
+    if sample_classes is None:
+        raise ValueError("`sample_classes` must give one class per column")
+    levels, cls = _class_levels(sample_classes, n_sample, "all")
+    _need_pairs(n_sample)
+    perms = anosim_permutations(cls, permutations, seed, strata)
+    n_class, n_perm = len(levels), int(perms.shape[0])
+    if (1 + n_perm) * n_class > _lib.PERMANOVA_MAX_CELLS:
+        raise ValueError(f"(1 + permutations) x classes must be at most {_lib.PERMANOVA_MAX_CELLS}")
+    if perms.size and (perms.min() < 0 or perms.max() >= n_class):
+        raise ValueError("`permutations` holds a class code outside 0 .. n_class - 1")
+    eng = engine or _default_engine()
+    if hasattr(eng, "permanova"):
+        (n_pairs, Q, class_q, max_taumax), t_diff = _on_device(
+            eng, data_matrix, global_na,
+            lambda X, gna: eng.permanova(X, cls, n_class, perms, gna, perspective, alternative, continuity, 0))
+    else:
+        mats5, t_diff, max_taumax = _from_full(eng, data_matrix, names, global_na, perspective, True, alternative,
+                                               continuity)
+        n_pairs, Q, class_q = _permanova_numpy(mats5[1], cls, n_class, perms)
+    S, n_na = n_sample, int(n_pairs[1])
+    na = _na_real()
+    as_float = lambda f: na if f is None else float(f)   # noqa: E731  (Fraction -> float rounds correctly, once)
+    sizes = np.bincount(cls, minlength=n_class).astype(np.int64)
+    if n_na > 0:
+        warnings.warn(f"PERMANOVA needs every pair and {n_na} of them have no raw value: every statistic is NA.  "
+                      "`ici_kendalltau_medians` returns `n_valid` per column, which finds the columns to leave out.",
+                      RuntimeWarning, stacklevel=2)
+        n_used = int((sizes > 0).sum())
+        obs = PermanovaStatistic((None, None, None, None, None, n_used - 1, S - n_used))
+        Fs, n_ge, n_undef = [None] * n_perm, 0, n_perm
+        class_ss = _na_filled(n_class)
+    else:
+        obs, Fs, n_ge, n_undef = _permanova_compare(S, Q, class_q, np.vstack([cls[None, :], perms]), n_class)
+        class_ss = np.array([as_float(Fraction(int(a), int(n) << PERMANOVA_FRAC_BITS) if n else None)
+                             for a, n in zip(class_q[0], sizes)], dtype=np.float64)
+    res = {"statistic": as_float(obs.F), "r2": as_float(obs.r2),
+           "pvalue": na if obs.F is None else float(Fraction(1 + n_ge, 1 + n_perm)),
+           "ss_total": as_float(obs.ss_total), "ss_within": as_float(obs.ss_within), "ss_among": as_float(obs.ss_among),
+           "df_among": int(obs.df_among), "df_within": int(obs.df_within),
+           "n_permutations": n_perm, "n_ge": int(n_ge), "n_undefined": int(n_undef)}
+    if return_perms:
+        res["perm_statistic"] = np.array([as_float(f) for f in Fs], dtype=np.float64)
+    res.update(n_valid=int(n_pairs[0]), n_na=n_na, class_levels=list(levels), class_size=sizes, class_ss=class_ss,
+               sums={"q_total": int(Q), "class_q": class_q},
                sample_id=list(names), max_taumax=max_taumax, run_time=t_diff)
     return res
 

@@ -1,5 +1,5 @@
 // icikt_device.h -- structures, layouts and launcher declarations shared by the device units (icikt_prepass.hip,
-// icikt_kernels.hip, icikt_epilogue.hip, icikt_cor.hip, icikt_diag.hip, icikt_topk.hip, icikt_edges.hip, icikt_medians.hip, icikt_quantiles.hip, icikt_classmat.hip, icikt_padjust.hip, icikt_mst.hip, icikt_hclust.hip, icikt_anosim.hip, icikt_cross.hip) and the C-ABI
+// icikt_kernels.hip, icikt_epilogue.hip, icikt_cor.hip, icikt_diag.hip, icikt_topk.hip, icikt_edges.hip, icikt_medians.hip, icikt_quantiles.hip, icikt_classmat.hip, icikt_padjust.hip, icikt_mst.hip, icikt_hclust.hip, icikt_anosim.hip, icikt_permanova.hip, icikt_cross.hip) and the C-ABI
 // host side (icikt_capi*.cpp, icikt_multi.cpp).  Internal; the public boundary is include/icikt.h.
 #ifndef ICIKT_DEVICE_H
 #define ICIKT_DEVICE_H
@@ -301,6 +301,25 @@ hipError_t launch_anosim_classes(const unsigned long long* r2, const int32_t* cl
 // columns of a workgroup, ANO_STRIP_MIN .. ANO_STRIP_MAX
 hipError_t launch_anosim_perm(const unsigned long long* r2, const uint16_t* labT, int S, int n_groups, int strip,
                               int count_nw, unsigned long long* w2, unsigned long long* nw, hipStream_t s);
+// ---- PERMANOVA: the sums of squared dissimilarities (1 - raw)^2 per class and labelling (icikt_permanova.hip) ----
+// (the label plane, ANO_PB, the strip and the batch keys are ANOSIM's; a run of rows is the kernel file's own, 1 024)
+constexpr int PMV_T_NA = 0, PMV_T_LO = 1, PMV_T_HI = 2, PMV_TOTALS = 3;   // the words of launch_pmv_quant's totals
+constexpr int PMV_LDS_CLASSES = 2048;     // classes up to which k_pmv_classes keeps a labelling's bins in LDS (16 bytes each)
+// kept: the whole combn plane launch_median_keep writes (n keys).  q[e] = fixed::quantise_key(kept[e]) (icikt_fixed.h: 0
+// for NA_KEY); totals[PMV_T_NA] += the NA_KEY pairs, totals[PMV_T_LO] / [PMV_T_HI] += the low 32 bits / the rest of
+// every q.  The caller zeroes totals.
+hipError_t launch_pmv_quant(const unsigned long long* kept, long long n, unsigned long long* q,
+                            unsigned long long* totals, hipStream_t s);
+// labT as launch_anosim_perm takes it.  colsum_lo / colsum_hi [n_groups][S][ANO_PB] (zeroed by the caller) += the low 32
+// bits / the rest of partial sums of q over the pairs (i, j), i < j, whose samples share a class under the labelling,
+// at column j's slot: sum = hi 2^32 + lo
+hipError_t launch_pmv_perm(const unsigned long long* q, const uint16_t* labT, int S, int n_groups, int strip,
+                           unsigned long long* colsum_lo, unsigned long long* colsum_hi, hipStream_t s);
+// bins_lo / bins_hi [n_lab][n_class] (zeroed by the caller) += colsum_lo / colsum_hi of every column at the column's
+// class under labelling l < n_lab; every label of labT must be below n_class
+hipError_t launch_pmv_classes(const uint16_t* labT, const unsigned long long* colsum_lo,
+                              const unsigned long long* colsum_hi, int S, int n_class, long long n_lab,
+                              unsigned long long* bins_lo, unsigned long long* bins_hi, hipStream_t s);
 // ---- quantiles and histogram of all pairs (icikt_quantiles.hip) ----
 constexpr int QUANT_MAX_BINS = 1024;    // == ICIKT_HIST_MAX_BINS: k_quant_fold stages 1 025 breaks and 2 x 1 026 counters in LDS
 constexpr int QUANT_HEAD = 4;           // words of a counted group before its bins: n_valid, n_na, below, above

@@ -220,6 +220,12 @@ struct icikt_ctx {
     DevBuf<uint16_t> labels;
   } ano;
 
+  // PERMANOVA (icikt_permanova_f64): a batch of labellings (ano.labels), the two limbs of its columns' sums and of its
+  // bins, and the call's totals (NA pairs, Q's limbs); the keys and their fixed-point values are in sel (kept, plane_a)
+  struct PermanovaBufs {
+    DevBuf<unsigned long long> colsum_lo, colsum_hi, bins_lo, bins_hi, totals;
+  } pmv;
+
   // missing-value diagnostics (icikt_col_medians_f64, icikt_censor_counts_f64, icikt_rank_order_f64)
   struct DiagBufs {
     DevBuf<double> median, medrank, out;

@@ -679,6 +679,47 @@ int icikt_anosim_f64(icikt_ctx *ctx, const double *X, int64_t n_feat, int64_t n_
                      int64_t *n_pairs, int64_t *w2, int64_t *nw, int64_t *n_ge, int64_t *n_undefined,
                      int64_t *class_w2, int64_t *class_nw, double *max_taumax, int64_t *reason_counts);
 
+/* ---- PERMANOVA: the sums of squared dissimilarities per class, of the observed labelling and of permutations ---------
+ *
+ * The test of class separation that is reported beside (or instead of) ANOSIM: Anderson 2001, vegan::adonis2,
+ * skbio.stats.distance.permanova, on the dissimilarity 1 - raw.  The triangle runs as in icikt_anosim_f64; a pair is a
+ * VALUE iff its raw is not NA.  A value's squared dissimilarity is summed as the integer
+ *   q = llrint(ldexp(e, 50)),  e = d * d,  d = 1.0 - raw   (IEEE double, one rounding each; round half to even),
+ * raw the double of the pair's key (-0 is +0): 0 <= q <= 2^52.  This quantisation is the only inexact step and it is a
+ * fixed function of raw (csrc/icikt_fixed.h); everything behind it is an integer sum.  This entry returns integers
+ * only; the statistic -- SS_T = Q / (n_samp 2^50), SS_W = sum_c A_c / (n_c 2^50) with n_c the labelling's class sizes,
+ * pseudo-F, R2, and the exact comparison of labellings -- is the caller's, in rational arithmetic.
+ *   cls, n_class, perm_cls, n_perm   as icikt_anosim_f64; additionally (1 + n_perm) n_class <=
+ *                ICIKT_PERMANOVA_MAX_CELLS (the bins come back to the host: 16 bytes per cell in the caller's arrays
+ *                and as many in the library's until the call has succeeded)
+ *   n_pairs      [2] the values and the NA pairs
+ *   q_total      [2] Q, the sum of q over all values, as two limbs: Q = q_total[1] 2^32 + q_total[0]
+ *   bins_lo, bins_hi   [(1 + n_perm)][n_class] row-major: A_c of labelling l -- the sum of q over the pairs whose two
+ *                samples both have class c under l -- is bins_hi[l n_class + c] 2^32 + bins_lo[l n_class + c].  THE LIMB
+ *                RULE: A = hi 2^32 + lo with 0 <= lo < 2^63 and 0 <= hi < 2^52; lo is a sum of low 32-bit halves and
+ *                may exceed 2^32.  Row 0 is the observed labelling, row 1 + t permutation t; a class without a sample
+ *                has 0
+ * WITH AN NA PAIR (n_pairs[1] > 0) no labelling is summed and every bin is 0: the 1 / n_c weights have no meaning on
+ * an incomplete class, nothing is imputed and no pair is dropped.  q_total is then the sum over the values, and the
+ * labels are still checked.  n_samp of 0 or 1 gives zero sums; it is no error.
+ * All outputs but max_taumax and reason_counts (as icikt_topk_f64, over all pairs) are required.  A bad n_class, a label
+ * of cls out of range, a negative or too large n_perm, too many cells, n_perm > 0 with a null perm_cls, a null output:
+ * ICIKT_E_INVALID before anything -- the context or an output -- is touched; a label of perm_cls out of range:
+ * ICIKT_E_INVALID with the outputs untouched.  n_samp <= ICIKT_TOPK_MAX_SAMPLES; n_feat, global_na and the state the
+ * call leaves behind (none): as icikt_topk_f64.  The result is a pure function of the input and the labellings, whatever
+ * the block cut, the batch, the strip or the grid.
+ * Device memory: the prepared matrix, one block's buffers, 16 bytes per pair of the triangle for the kept keys and
+ * their q (n_samp = 65 535: 34 GB), and per labelling of a batch 18 n_samp bytes of labels and column sums and
+ * 16 n_class bytes of bins (the largest of them at most 64 MB per batch unless the anoperms plan key says otherwise).
+ * With ICIKT_FLAG_TIMING the keep, quantisation, permutation and class kernels are accounted under ICIKT_K_EPILOGUE.
+ * icikt_permanova_in / icikt_permanova_csc: the same on a typed view / a CSC view of the matrix (below). */
+#define ICIKT_PERMANOVA_MAX_CELLS (1ll << 26)
+int icikt_permanova_f64(icikt_ctx *ctx, const double *X, int64_t n_feat, int64_t n_samp, int64_t ld,
+                        const double *global_na, int n_global_na, int perspective, int alternative, int continuity,
+                        uint32_t flags, const int32_t *cls, int n_class, const int32_t *perm_cls, int64_t n_perm,
+                        int64_t *n_pairs, int64_t *q_total, int64_t *bins_lo, int64_t *bins_hi, double *max_taumax,
+                        int64_t *reason_counts);
+
 /* ---- query samples against a reference cohort: the query x reference rectangle ---------------------------------------
  *
  * Every column of Q (n_feat x n_query, leading dimension ld_query) with every column of R (n_feat x n_reference,
@@ -946,6 +987,11 @@ int icikt_anosim_in(icikt_ctx *ctx, const icikt_input *X, int64_t n_feat, int64_
                     const int32_t *cls, int n_class, const int32_t *perm_cls, int64_t n_perm, int64_t *n_pairs,
                     int64_t *w2, int64_t *nw, int64_t *n_ge, int64_t *n_undefined, int64_t *class_w2,
                     int64_t *class_nw, double *max_taumax, int64_t *reason_counts);
+int icikt_permanova_in(icikt_ctx *ctx, const icikt_input *X, int64_t n_feat, int64_t n_samp, const double *global_na,
+                       int n_global_na, int perspective, int alternative, int continuity, uint32_t flags,
+                       const int32_t *cls, int n_class, const int32_t *perm_cls, int64_t n_perm, int64_t *n_pairs,
+                       int64_t *q_total, int64_t *bins_lo, int64_t *bins_hi, double *max_taumax,
+                       int64_t *reason_counts);
 int icikt_matrix_in(icikt_ctx *ctx, const icikt_input *X, int64_t n_feat, int64_t n_samp, const double *global_na,
                     int n_global_na, const int32_t *pi, const int32_t *pj, int64_t n_pairs, int perspective,
                     int alternative, int continuity, uint32_t flags, int scale_max, int diag_good, double *out5,
@@ -1029,6 +1075,11 @@ int icikt_anosim_csc(icikt_ctx *ctx, const icikt_csc_input *X, int64_t n_feat, i
                      const int32_t *cls, int n_class, const int32_t *perm_cls, int64_t n_perm, int64_t *n_pairs,
                      int64_t *w2, int64_t *nw, int64_t *n_ge, int64_t *n_undefined, int64_t *class_w2,
                      int64_t *class_nw, double *max_taumax, int64_t *reason_counts);
+int icikt_permanova_csc(icikt_ctx *ctx, const icikt_csc_input *X, int64_t n_feat, int64_t n_samp,
+                        const double *global_na, int n_global_na, int perspective, int alternative, int continuity,
+                        uint32_t flags, const int32_t *cls, int n_class, const int32_t *perm_cls, int64_t n_perm,
+                        int64_t *n_pairs, int64_t *q_total, int64_t *bins_lo, int64_t *bins_hi, double *max_taumax,
+                        int64_t *reason_counts);
 int icikt_missingness_csc(icikt_ctx *ctx, const icikt_csc_input *X, int64_t n_feat, int64_t n_samp, const int32_t *pi,
                           const int32_t *pj, int64_t n_pairs, int64_t *missingness);
 int icikt_col_medians_csc(icikt_ctx *ctx, const icikt_csc_input *X, int64_t n_feat, int64_t n_samp,
@@ -1068,7 +1119,8 @@ int icikt_selftest(icikt_ctx *ctx);
  * select runs per batch of eight passes, 1 .. 32), padjtile (icikt_padjust_*: the keys of a tile of the sort, the run one
  * wave counts and scatters in order, 1 .. 2^30; raised when the plane would have more than 65 536 tiles; icikt_anosim_* sorts with
  * the same tile), anoperms (icikt_anosim_*: the labellings per upload, 1 .. 2^20; the permutation kernel takes them 16 at a
- * time), anostrip (icikt_anosim_*: the columns of the triangle a workgroup of the permutation kernel owns, 1 .. 4096), hcgrid (icikt_hclust_*: the workgroups of the
+ * time), anostrip (icikt_anosim_*: the columns of the triangle a workgroup of the permutation kernel owns, 1 .. 4096; anoperms and anostrip
+ * apply to icikt_permanova_* as well), hcgrid (icikt_hclust_*: the workgroups of the
  * kernel that rescans the listed rows of a step, 1 .. 256; default min(n_samp, 256)), verbose (0 | 1: print the chosen
  * plan to stderr). */
 int icikt_debug_set_plan(icikt_ctx *ctx, const char *spec);
