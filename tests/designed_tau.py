@@ -1,7 +1,9 @@
 """Input matrices whose ICI-Kendall-tau is known in closed form from integers, and the answers of the five selection
-entries (topk, edges, class_medians, class_matrix, quantiles) on them.  Plain numpy: no GPU, no oracle, no S x S matrix
-from the library.  Used by tests/test_designed_tau_host.py (against the CPU oracle and the brute-force checkers) and by
-tests/test_gpu_designed_tau.py (against the kernels).
+entries (topk, edges, class_medians, class_matrix, quantiles) on them, and of the seven later ones (anosim, permanova,
+padjust's sorted p-values, mst on +-base columns, the rectangle of cross with its top-k and class table; hclust's
+reference is tests/hclust_checker.brute_hclust on Design.raw).  Plain numpy and Python ints: no GPU, no oracle, no S x S
+matrix from the library.  Used by tests/test_designed_tau_host.py (against the CPU oracle and the brute-force checkers)
+and by tests/test_gpu_designed_tau.py and tests/test_gpu_designed_tau_entries.py (against the kernels).
 
 n rows, m = n (n - 1) / 2 pairs of rows, the base column 1, 2, ..., n (not from 0: the default global_na takes 0 as
 missing).  Two families of complete columns without ties:
@@ -144,25 +146,36 @@ def reversals(S, n, seed=0, params=None, signs=None, values=None, flip=0.5, n_al
     return _assemble("reversals", n, S, seed, col, lambda L: L * (L - 1) // 2, p, s, n_all_missing, n_constant)
 
 
+def valid_columns(d):
+    """the design's valid columns alone: no NA pair (PERMANOVA sums per class only then)"""
+    good = d.kind == VALID
+    return Design(d.family, np.asfortranarray(d.X[:, good]), d.kind[good], d.sign[good], d.disc[good], d.param[good])
+
+
 # ---- top-k -----------------------------------------------------------------------------------------------------------
 
-def topk(d, k):
-    """(idx [S, k] int32, -1 padded; num [S, k] int32 of the chosen; raw [S, k], NA_real_ padded; n_valid [S]): per
-    sample the k valid partners of largest num, ties by the smaller partner index"""
-    S = d.S
-    key = np.where(d.valid, -d.num.astype(np.int64), np.int64(_FAR))
+def _topk(d, num, valid, k):
+    """topk over the rows of any [rows, partners] block of numerators"""
+    S = num.shape[0]
+    key = np.where(valid, -num.astype(np.int64), np.int64(_FAR))
     order = np.argsort(key, axis=1, kind="stable")[:, :k]            # stable: equal num keep index order
     kk = order.shape[1]
-    have = np.minimum(d.valid.sum(axis=1), k).astype(np.int32)
+    have = np.minimum(valid.sum(axis=1), k).astype(np.int32)
     take = np.arange(kk)[None, :] < have[:, None]
     idx = np.full((S, k), -1, dtype=np.int32)
     nums = np.zeros((S, k), dtype=np.int32)
     raw = na_filled((S, k))
     rows = np.arange(S)[:, None]
     idx[:, :kk] = np.where(take, order, -1)
-    nums[:, :kk] = np.where(take, d.num[rows, order], 0)
-    raw[:, :kk][take] = d.value(d.num[rows, order][take])
+    nums[:, :kk] = np.where(take, num[rows, order], 0)
+    raw[:, :kk][take] = d.value(num[rows, order][take])
     return idx, nums, raw, have
+
+
+def topk(d, k):
+    """(idx [S, k] int32, -1 padded; num [S, k] int32 of the chosen; raw [S, k], NA_real_ padded; n_valid [S]): per
+    sample the k valid partners of largest num, ties by the smaller partner index"""
+    return _topk(d, d.num, d.valid, k)
 
 
 # ---- edges -----------------------------------------------------------------------------------------------------------
@@ -193,19 +206,17 @@ def _median_float(d, lo, hi, v):
     return out
 
 
-def class_matrix(d, cls=None, n_class=1):
-    """dict of [S, n_class] arrays for the cells (s, c): n_valid; lo, hi: the numerators of ranks (v - 1) >> 1 and
-    v >> 1 among the cell's valid partners ascending; k_in: the rank of lo inside its run of equal numerators; run: that
-    run's length; med: the median as float64 (== med_raw == med_cor), NA_real_ where n_valid == 0"""
-    S = d.S
-    cls = np.zeros(S, dtype=np.int64) if cls is None else np.asarray(cls)
+def _class_cells(d, num, valid, cls, n_class):
+    """class_matrix over the rows of any [rows, partners] block of numerators; cls: a class per partner"""
+    S = num.shape[0]
+    cls = np.asarray(cls)
     out = {k: np.zeros((S, n_class), dtype=np.int32) for k in ("n_valid", "lo", "hi", "k_in", "run")}
     for c in range(n_class):
         mem = np.nonzero(cls == c)[0]
         if mem.size == 0:
             continue
-        sub = np.where(d.valid[:, mem], d.num[:, mem], _FAR)
-        v = d.valid[:, mem].sum(axis=1).astype(np.int32)
+        sub = np.where(valid[:, mem], num[:, mem], _FAR)
+        v = valid[:, mem].sum(axis=1).astype(np.int32)
         sub.sort(axis=1)
         rows = np.arange(S)
         have = v > 0
@@ -218,6 +229,14 @@ def class_matrix(d, cls=None, n_class=1):
         out["run"][:, c] = np.where(have, (sub == lo[:, None]).sum(axis=1), 0)
     out["med"] = _median_float(d, out["lo"], out["hi"], out["n_valid"])
     return out
+
+
+def class_matrix(d, cls=None, n_class=1):
+    """dict of [S, n_class] arrays for the cells (s, c): n_valid; lo, hi: the numerators of ranks (v - 1) >> 1 and
+    v >> 1 among the cell's valid partners ascending; k_in: the rank of lo inside its run of equal numerators; run: that
+    run's length; med: the median as float64 (== med_raw == med_cor), NA_real_ where n_valid == 0"""
+    cls = np.zeros(d.S, dtype=np.int64) if cls is None else np.asarray(cls)
+    return _class_cells(d, d.num, d.valid, cls, n_class)
 
 
 def class_medians(d, cls=None):
@@ -293,3 +312,271 @@ def histogram(d, break_nums, cls=None, counts=None):
         outside[g] = per[0], per[len(bn)]
         hist[g] = per[1:len(bn)]
     return hist, outside
+
+
+# ---- the triangle as integers (anosim, permanova, padjust) -----------------------------------------------------------
+
+def triangle(d):
+    """(i, j int32, k int32) of the VALID pairs i < j in combn order, k = num + m in 0 .. 2 m; n_na: the other pairs of
+    the triangle.  Kept on the design: every reference below starts from it."""
+    if getattr(d, "_tri", None) is None:
+        iu, ju = np.triu_indices(d.S, k=1)
+        ok = d.valid[iu, ju]
+        i, j = iu[ok].astype(np.int32), ju[ok].astype(np.int32)
+        d._tri = (i, j, d.num[i, j] + np.int32(d.m), int(ok.shape[0] - i.shape[0]))
+    return d._tri
+
+
+def class_hist(d, lab, n_class):
+    """[n_class, 2 m + 1] int64: the valid pairs i < j whose two samples both have class c under the labelling `lab`,
+    per numerator (column num + m)"""
+    i, j, k, _n_na = triangle(d)
+    lab = np.asarray(lab, dtype=np.int64)
+    width = 2 * d.m + 1
+    li = lab[i]
+    same = li == lab[j]
+    return np.bincount(li[same] * width + k[same], minlength=n_class * width).reshape(n_class, width)
+
+
+def _labellings(d, cls, labellings):
+    cls = np.asarray(cls, dtype=np.int64)
+    perms = np.asarray(labellings, dtype=np.int64).reshape(-1, d.S)
+    return cls, perms, [cls] + list(perms)
+
+
+def anosim(d, cls, n_class, labellings):
+    """tests/anosim_checker.brute_anosim's dict (without r2, i, j) from the integers.  A value's doubled rank in
+    descending num is 2 * above + cnt + 1, `above` the values of larger num and cnt those equal to it: the checker's
+    below + upto + 1.  w2 and nw of a labelling are histogram . table and the histogram's sum."""
+    from tests import anosim_checker as ac
+    cls, perms, labs = _labellings(d, cls, labellings)
+    _i, _j, k, n_na = triangle(d)
+    M = int(k.shape[0])
+    cnt = np.bincount(k, minlength=2 * d.m + 1).astype(np.int64)
+    above = np.cumsum(cnt[::-1])[::-1] - cnt
+    r2 = 2 * above + cnt + 1                                         # (at most 2 M < 2^26: the sums below stay in int64)
+    assert M == 0 or int(np.dot(cnt, r2)) == M * (M + 1)
+    w2, nw = np.zeros(len(labs), dtype=np.int64), np.zeros(len(labs), dtype=np.int64)
+    for q, lab in enumerate(labs):
+        h = class_hist(d, lab, n_class)
+        if q == 0:
+            class_w2, class_nw = h @ r2, h.sum(axis=1)
+        w2[q], nw[q] = int(np.dot(h.sum(axis=0), r2)), int(h.sum())
+    obs = ac.statistic(M, w2[0], nw[0])
+    stats = [ac.statistic(M, a, b) for a, b in zip(w2[1:], nw[1:])]
+    n_ge = 0 if obs is None else sum(1 for f in stats if f is not None and f >= obs)
+    W2, nW = int(w2[0]), int(nw[0])
+    F = ac.Fraction
+    return {
+        "n_pairs": np.array([M, n_na], dtype=np.int64), "w2": w2, "nw": nw, "n_ge": n_ge,
+        "n_undefined": sum(1 for f in stats if f is None), "class_w2": class_w2, "class_nw": class_nw,
+        "statistic": ac.to_double(obs),
+        "pvalue": ac.na_real() if obs is None else float(F(1 + n_ge, 1 + len(stats))),
+        "perm_statistic": np.array([ac.to_double(f) for f in stats], dtype=np.float64),
+        "class_mean_rank": np.array([ac.to_double(F(int(a), 2 * int(b)) if b else None)
+                                     for a, b in zip(class_w2, class_nw)], dtype=np.float64),
+        "within_mean_rank": ac.to_double(F(W2, 2 * nW) if nW else None),
+        "between_mean_rank": ac.to_double(F(M * (M + 1) - W2, 2 * (M - nW)) if M > nW else None),
+    }
+
+
+def q_table(d):
+    """q per numerator, index num + m: tests/permanova_checker.quantise(num / m) in Python ints (dtype object)"""
+    from tests.permanova_checker import quantise
+    return np.array([quantise(float(d.value(v))) for v in range(-d.m, d.m + 1)], dtype=object)
+
+
+def permanova(d, cls, n_class, labellings):
+    """tests/permanova_checker.brute_permanova's dict (without "exact") from the integers: q is a function of num
+    alone, so Q and every A_c are histogram . table in Python ints.  With an NA pair every A_c is 0."""
+    from tests import permanova_checker as pc
+    cls, perms, labs = _labellings(d, cls, labellings)
+    _i, _j, k, n_na = triangle(d)
+    table = q_table(d)
+    cnt = np.bincount(k, minlength=2 * d.m + 1)
+    used = np.nonzero(cnt)[0]
+    Q = sum(int(cnt[v]) * table[v] for v in used)
+    class_q, sizes = [], []
+    for lab in labs:
+        sizes.append([int(v) for v in np.bincount(lab, minlength=n_class)])
+        if n_na:
+            class_q.append([0] * n_class)
+            continue
+        h = class_hist(d, lab, n_class)[:, used].astype(object)
+        class_q.append([int(v) for v in h @ table[used]])
+    S = d.S
+    if n_na == 0:
+        stats = [pc.statistic(S, Q, A, size) for A, size in zip(class_q, sizes)]
+    else:
+        n_used = sum(1 for n in sizes[0] if n > 0)
+        stats = [(None, None, None, None, None, n_used - 1, S - n_used)] * len(labs)
+    obs, Fs = stats[0], [s[0] for s in stats[1:]]
+    n_ge = 0 if obs[0] is None else sum(1 for f in Fs if f is not None and f >= obs[0])
+    return {
+        "n_pairs": np.array([int(k.shape[0]), n_na], dtype=np.int64), "q_total": Q, "class_q": class_q, "sizes": sizes,
+        "n_ge": n_ge, "n_undefined": sum(1 for f in Fs if f is None),
+        "statistic": pc.to_double(obs[0]), "r2": pc.to_double(obs[1]),
+        "pvalue": pc.na_real() if obs[0] is None else float(pc.Fraction(1 + n_ge, len(labs))),
+        "ss_total": pc.to_double(obs[2]), "ss_within": pc.to_double(obs[3]), "ss_among": pc.to_double(obs[4]),
+        "df_among": obs[5], "df_within": obs[6],
+        "perm_statistic": np.array([pc.to_double(f) for f in Fs], dtype=np.float64),
+        "class_size": np.array(sizes[0], dtype=np.int64),
+        "class_ss": np.array([pc.to_double(pc.Fraction(a, n * pc.SCALE) if (n and n_na == 0) else None)
+                              for a, n in zip(class_q[0], sizes[0])], dtype=np.float64),
+    }
+
+
+# ---- p.adjust --------------------------------------------------------------------------------------------------------
+
+def pvalue_keys(d, one_sided=False):
+    """(keys: the distinct num -- |num| unless one_sided -- of the valid pairs, ascending; count per key; (i, j) of
+    the first pair in combn order that has each key; n_na)"""
+    i, j, k, n_na = triangle(d)
+    key = k.astype(np.int64) - d.m
+    if not one_sided:
+        key = np.abs(key)
+    keys, first, count = np.unique(key, return_index=True, return_counts=True)
+    return keys, count, i[first], j[first], n_na
+
+
+def sorted_pvalues(d, p_of_key, one_sided=False):
+    """(the tests' p-values ascending, a zero as +0; n_na): np.repeat of one p per distinct |num| (num when one_sided)
+    by its count.  p_of_key: a p-value per key of pvalue_keys, in its order -- the p-value itself has no closed form
+    here and comes from outside."""
+    _keys, count, _i, _j, n_na = pvalue_keys(d, one_sided)
+    p = np.asarray(p_of_key, dtype=np.float64) + 0.0
+    assert p.shape == count.shape and not np.isnan(p).any()
+    order = np.argsort(p, kind="stable")
+    return np.repeat(p[order], count[order]), n_na
+
+
+def unscanned(p, method):
+    """the product a method's scan runs over, per sorted position: m p, (m + 1 - j) p or (m / j) p, capped at 1 -- the
+    adjusted value BEFORE the running maximum or minimum (tests/padjust_checker.adjust_sorted_fast's operations)"""
+    m = p.shape[0]
+    if method == "bonferroni":
+        u = float(m) * p
+    elif method in ("holm", "hochberg"):
+        u = np.arange(m, 0, -1).astype(np.float64) * p
+    else:
+        u = (float(m) / np.arange(1, m + 1).astype(np.float64)) * p
+    return np.minimum(1.0, u)
+
+
+def _runs(p):
+    """(start, length) of the runs of equal p in the sorted p-values"""
+    start = np.nonzero(np.concatenate([[True], p[1:] != p[:-1]]))[0]
+    return start, np.diff(np.concatenate([start, [p.shape[0]]]))
+
+
+def cuts_in_runs(p, method, alphas):
+    """per alpha "inside", "edge" or None.  Equal p-values have equal adjusted values, so n_rejected never ends inside a
+    run of equal p; what differs inside a run is the unscanned product.  "inside": some run of equal p holds products
+    on both sides of alpha, so the running maximum or minimum alone decides where the whole run falls; "edge": no run
+    does, and 0 < n_rejected < m: the products change sides where two runs meet; None: neither."""
+    from tests.padjust_checker import adjust_sorted_fast
+    adj, u = adjust_sorted_fast(p, method), unscanned(p, method)
+    start, length = _runs(p)
+    out = []
+    for a in alphas:
+        n = int(np.sum(adj <= a))
+        below = np.add.reduceat((u <= a).astype(np.int64), start)
+        if np.any((below > 0) & (below < length)):
+            out.append("inside")
+        else:
+            out.append("edge" if 0 < n < p.shape[0] else None)
+    return out
+
+
+def alpha_inside_a_run(p, method):
+    """a level that the unscanned products of the longest run of equal p straddle: the product at the run's middle
+    (inside a run they fall strictly from place to place for holm, hochberg and BH while below the cap of 1).  None when
+    no run has two products (bonferroni: m p is one value per run)."""
+    u = unscanned(p, method)
+    start, length = _runs(p)
+    last = start + length - 1
+    ok = u[start] != u[last]
+    if not ok.any():
+        return None
+    r = int(np.argmax(np.where(ok, length, 0)))
+    mid = int(start[r] + length[r] // 2)
+    return float(u[mid]) if u[mid] < u[start[r]] else float(u[last[r]])
+
+
+# ---- spanning forest -------------------------------------------------------------------------------------------------
+
+def is_two_valued(d):
+    ok = d.kind == VALID
+    return bool(ok.any() and np.all(d.disc[ok] == d.disc[ok][0]))
+
+
+def mst_two_valued(d):
+    """tests/mst_checker.brute_mst's tuple in O(S) when every valid column is +-base: raw is +1 inside a sign group and
+    -1 across.  Under the strict order (larger raw, then smaller combn index) the +1 edges come first, by (i, j):
+    Kruskal takes every (g, x) from a group's smallest column g and nothing else inside the group, and the two stars
+    come out in combn order.  Of the -1 edges the first in combn order, (the first valid column, the first column of
+    the other sign), joins the two.  An NA column has no edge: a component of its own.  Every other design:
+    brute_mst(d.raw)."""
+    if not is_two_valued(d):
+        from tests.mst_checker import brute_mst
+        return brute_mst(d.raw)
+    good = np.nonzero(d.kind == VALID)[0]
+    first = d.sign[good[0]]
+    groups = [good[d.sign[good] == first], good[d.sign[good] != first]]
+    edges_ = sorted((int(g[0]), int(x)) for g in groups if len(g) for x in g[1:])
+    if len(groups[1]):
+        edges_.append((int(good[0]), int(groups[1][0])))
+    ti = np.array([a for a, _b in edges_], dtype=np.int32)
+    tj = np.array([b for _a, b in edges_], dtype=np.int32)
+    component = np.empty(d.S, dtype=np.int32)                          # numbered by their smallest sample
+    n_comp, tree = 0, -1
+    for s in range(d.S):
+        if d.kind[s] == VALID and tree >= 0:
+            component[s] = tree
+            continue
+        if d.kind[s] == VALID:
+            tree = n_comp
+        component[s] = n_comp
+        n_comp += 1
+    assert len(ti) + n_comp == d.S
+    return ti, tj, component, n_comp
+
+
+# ---- the rectangle: the first Sq columns as the query, the rest as the reference ----------------------------------------
+
+class Rect:
+    """Q [n, Sq], R [n, Sr] F-ordered; num, valid [Sq, Sr]: no diagonal on a rectangle, a pair is valid iff neither
+    column is an NA column; raw [Sq, Sr]: num / m, NaN where not valid; reasons [Sq, Sr]"""
+
+    def __init__(self, d, Sq):
+        assert 0 < Sq < d.S
+        self.d, self.Sq, self.Sr = d, Sq, d.S - Sq
+        self.Q, self.R = np.asfortranarray(d.X[:, :Sq]), np.asfortranarray(d.X[:, Sq:])
+        self.num, self.valid = d.num[:Sq, Sq:], d.valid[:Sq, Sq:]
+        self.raw = np.where(self.valid, self.num / float(d.m), np.nan)
+        self.reasons = d.reasons()[:Sq, Sq:]
+
+    def reason_counts(self):
+        return np.bincount(self.reasons.ravel(), minlength=5).astype(np.int64)
+
+    def max_taumax(self):
+        return 1.0 if self.valid.any() else -np.inf
+
+
+def rect(d, Sq):
+    return Rect(d, Sq)
+
+
+def cross_topk(d, Sq, k):
+    """topk's tuple for the rectangle: per query the k valid reference columns of largest num, ties by the smaller
+    reference index; idx counts from the reference's first column"""
+    r = rect(d, Sq)
+    return _topk(d, r.num, r.valid, k)
+
+
+def cross_class_table(d, Sq, ref_cls, n_class):
+    """class_matrix's dict for the rectangle: cell (q, c) over the reference columns of class c that are valid with q"""
+    r = rect(d, Sq)
+    ref_cls = np.asarray(ref_cls)
+    assert ref_cls.shape == (r.Sr,)
+    return _class_cells(d, r.num, r.valid, ref_cls, n_class)

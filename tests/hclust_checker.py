@@ -22,8 +22,14 @@ def _key_matrix(V):
     return K
 
 
-def brute_hclust(raw_matrix, method, min_raw=None):
-    """(ma, mb, msize int32 [n_merges]; mraw float64 [n_merges]; component int32 [S]; n_components)"""
+def average_update(na, wa, nb, wb):
+    """the rule's average: two products, two sums, one division in Python floats, each rounded once"""
+    return (na * wa + nb * wb) / (na + nb)
+
+
+def brute_hclust(raw_matrix, method, min_raw=None, average=average_update):
+    """(ma, mb, msize int32 [n_merges]; mraw float64 [n_merges]; component int32 [S]; n_components).  `average`: the
+    update of average linkage; another one only for a test that shows a design can tell the two apart."""
     assert method in METHODS
     with np.errstate(invalid="ignore"):
         V = np.array(raw_matrix, dtype=np.float64) + 0.0        # (+ 0.0: -0 becomes +0)
@@ -57,7 +63,7 @@ def brute_hclust(raw_matrix, method, min_raw=None):
             elif method == "single":
                 w = max(wa, wb)
             else:
-                w = (na * wa + nb * wb) / (na + nb) + 0.0
+                w = average(na, wa, nb, wb) + 0.0
             V[a, k] = V[k, a] = w
         V[b, :] = V[:, b] = np.nan                              # slot b is no cluster any more
         K[b, :] = K[:, b] = 0

@@ -78,11 +78,9 @@ def outputs_from_sorted(p, n_na, method, alphas=ALPHAS, fast=True):
         else:
             p_cutoff.view(np.uint64)[a] = NA_REAL_BITS
     most = int(n_rejected.max()) if len(alphas) else 0
-    table_p, table_adj = [], []
-    for i in range(most):
-        if i == 0 or p[i] != p[i - 1]:
-            table_p.append(p[i])
-            table_adj.append(adj[i])
+    first = np.ones(most, dtype=bool)                   # position i opens a run: i == 0 or p[i] != p[i - 1]
+    first[1:] = p[1:most] != p[:max(most - 1, 0)]
+    table_p, table_adj = p[:most][first], adj[:most][first]
     return {"n_tests": np.array([m, n_na], dtype=np.int64), "n_rejected": n_rejected, "p_cutoff": p_cutoff,
             "table_p": np.array(table_p, dtype=np.float64), "table_adjusted": np.array(table_adj, dtype=np.float64),
             "n_table": len(table_p), "sorted_p": p, "adjusted": adj}

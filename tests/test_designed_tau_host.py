@@ -1,20 +1,27 @@
 """tests/designed_tau.py tied to the two references the project already trusts: its closed-form tau against the CPU
 oracle BITWISE (both families, both perspectives, with an all-NaN and a constant column), its per-code reason counts
 against the oracle's, and its closed-form answers of the five selection entries against the brute-force checkers fed the
-closed-form matrices."""
+closed-form matrices.  Below those, the references of the seven later entries (anosim, permanova, padjust, mst, cross and
+its class table) against their checkers at S = 130, and the mutation of hclust's average update that the designs of
+the GPU test must keep showing."""
+import math
 import warnings
+from fractions import Fraction
 
 import numpy as np
 import pytest
 
 from icikendalltau_amd import api
 from oracle import oracle as O
+from tests import anosim_checker, cross_checker, hclust_checker, mst_checker, padjust_checker, permanova_checker
 from tests import designed_tau as dt
 from tests.classmat_checker import brute_class_matrix
+from tests.cross_class_checker import brute_cross_class
 from tests.edges_checker import brute_edges
 from tests.medians_checker import brute_medians
 from tests.oracle_engine import OracleEngine
 from tests.quantiles_checker import PROBS, brute_quantiles
+from tests.test_gpu_designed_tau import _design as _gpu_design      # the S = 130 designs the GPU tests use
 from tests.topk_checker import brute_topk
 
 FAMILIES = {"swaps": dt.swaps, "reversals": dt.reversals}
@@ -151,3 +158,193 @@ def test_quantiles_and_histogram_against_the_checker(design):
         assert np.array_equal(bits(q), bits(rq2[1])) and np.array_equal(bits(q), bits(rq2[0]))
         assert np.array_equal(bits(d.value(ord_num))[:, :, 0][n_valid > 0], bits(order2)[:, :, 0][n_valid > 0])
     assert n_na[1] == 1 and n_valid[1] + n_valid[2] == n_valid[0]      # the NA class's one pair is a within pair
+
+
+# ---- the seven later entries: anosim, permanova, padjust, mst, hclust, cross and its class table -----------------------
+# S = 130 on the designs of tests/test_gpu_designed_tau_entries.py, each new reference against the brute-force checker
+# fed the closed-form matrix (or, for the p-values and the rectangle, the CPU oracle's).
+
+KEYS130 = ["two-valued", "two-valued-half", "swaps40", "reversals41", "reversals41-wide"]
+
+
+def _same_item(a, b, name):
+    if isinstance(a, np.ndarray) and a.dtype == np.float64:
+        assert np.array_equal(bits(a), bits(np.asarray(b, dtype=np.float64))), name
+    elif isinstance(a, float):
+        assert bits(np.array([a]))[0] == bits(np.array([b]))[0], name
+    elif isinstance(a, np.ndarray):
+        assert np.array_equal(a, b), name
+    else:
+        assert a == b, name
+
+
+def _four_classes(d, seed, na_class):
+    cls = np.random.default_rng(seed).integers(0, 3, d.S).astype(np.int32)
+    if na_class:
+        cls[d.kind != dt.VALID] = 3
+    else:
+        cls[::9] = 3
+    return cls, 4
+
+
+@pytest.mark.parametrize("na", [True, False])
+@pytest.mark.parametrize("key", KEYS130)
+def test_anosim_and_permanova_against_the_checkers(key, na):
+    d = _gpu_design(key) if na else dt.valid_columns(_gpu_design(key))
+    for na_class in (True, False):
+        cls, n_class = _four_classes(d, 5, na_class and na)
+        perms = anosim_checker.documented_permutations(cls, 7, seed=11)
+        got, want = dt.anosim(d, cls, n_class, perms), anosim_checker.brute_anosim(d.raw, cls, n_class, perms)
+        for name in got:
+            _same_item(got[name], want[name], name)
+        assert got["n_pairs"][0] > 0 and (got["n_pairs"][1] > 0) == na and want["exact"][0] is not None
+        got, want = dt.permanova(d, cls, n_class, perms), permanova_checker.brute_permanova(d.raw, cls, n_class, perms)
+        for name in got:
+            _same_item(got[name], want[name], name)
+        assert got["q_total"] > 0 and (want["exact"][0][0] is None) == na
+        if not na:
+            assert all(any(row) for row in got["class_q"])
+    if key.startswith("two-valued"):
+        table = dt.q_table(d)
+        assert table[0] == 2 ** 52 and table[2 * d.m] == 0           # raw = -1 and +1: the ends of q's range
+
+
+def _oracle_pvalues(d, perspective, alternative):
+    iu, ju = np.triu_indices(d.S, k=1)
+    out, _cnt, _rsn = O.ici_pairs(d.X, iu.astype(np.int32), ju.astype(np.int32), perspective=perspective,
+                                  alternative=alternative, want_counts=False)
+    plane = np.full((d.S, d.S), np.nan)
+    plane[iu, ju] = out[:, 1]
+    return plane
+
+
+@pytest.mark.parametrize("alternative", ["two.sided", "greater"])
+@pytest.mark.parametrize("key", KEYS130)
+def test_sorted_pvalues_against_the_checker(key, alternative):
+    d = _gpu_design(key)
+    one_sided = alternative != "two.sided"
+    plane = _oracle_pvalues(d, "global", alternative)
+    i, j, k, n_na = dt.triangle(d)
+    keys, count, fi, fj, _n_na = dt.pvalue_keys(d, one_sided)
+    num = k.astype(np.int64) - d.m
+    at = np.searchsorted(keys, num if one_sided else np.abs(num))
+    p_of_key = plane[fi, fj]
+    assert not np.isnan(p_of_key).any()
+    assert np.array_equal(bits(plane[i, j]), bits(p_of_key[at]))      # p is a function of the key alone on the design
+    assert count.sum() == len(i) and count.max() >= 100
+    p, got_na = dt.sorted_pvalues(d, p_of_key, one_sided)
+    want, want_na = padjust_checker.sorted_tests(plane)
+    assert got_na == want_na == n_na and np.array_equal(bits(p), bits(want))
+    kinds = set()
+    for method in padjust_checker.METHODS:
+        fast = padjust_checker.outputs_from_sorted(p, n_na, method)
+        slow = padjust_checker.outputs_from_sorted(p, n_na, method, fast=False)
+        for name in fast:
+            _same_item(fast[name], slow[name], name)
+        # equal p-values have equal adjusted values: every cut lies between two runs
+        n = fast["n_rejected"]
+        inner = n[(n > 0) & (n < len(p))]
+        assert np.all(p[inner - 1] != p[inner])
+        kinds |= set(dt.cuts_in_runs(p, method, padjust_checker.ALPHAS))
+        a_in = dt.alpha_inside_a_run(p, method)
+        assert (a_in is None) == (method == "bonferroni")
+        if a_in is not None:   # a level inside a run's unscanned products: the whole run still falls on one side
+            assert 0.0 < a_in <= 1.0 and dt.cuts_in_runs(p, method, (a_in,)) == ["inside"]
+            n_in = padjust_checker.outputs_from_sorted(p, n_na, method, (a_in,), fast=False)["n_rejected"][0]
+            assert n_in in (0, len(p)) or p[n_in - 1] != p[n_in]
+    print(key, alternative, "cuts at the five levels", kinds)
+    if key == "reversals41-wide":
+        assert "edge" in kinds
+
+
+@pytest.mark.parametrize("S", [130, 257, 520])
+def test_mst_two_valued_against_kruskal(S):
+    for n_na in ((0, 3) if S == 130 else (0,)):
+        rng = np.random.default_rng(S)
+        signs = np.where(rng.random(S - n_na) < 0.4, -1, 1)
+        d = dt.swaps(S, 24, seed=S, params=np.zeros(S - n_na, dtype=np.int64), signs=signs, n_all_missing=n_na // 3,
+                     n_constant=n_na - n_na // 3)
+        assert dt.is_two_valued(d) and set(np.unique(d.num[d.valid]).tolist()) == {-d.m, d.m}
+        ti, tj, component, n_comp = dt.mst_two_valued(d)
+        rti, rtj, rcomponent, rn = mst_checker.brute_mst(d.raw)
+        assert np.array_equal(ti, rti) and np.array_equal(tj, rtj) and np.array_equal(component, rcomponent) and n_comp == rn
+        assert n_comp == 1 + n_na and int(np.sum(d.num[ti, tj] < 0)) == 1
+        if S == 130:
+            assert mst_checker.verify_forest(d.raw, ti, tj, component) == n_comp
+    d = _gpu_design("two-valued")
+    got, want = dt.mst_two_valued(d), mst_checker.brute_mst(d.raw)
+    assert all(np.array_equal(a, b) for a, b in zip(got, want))
+    assert mst_checker.verify_forest(d.raw, got[0], got[1], got[2]) == 10
+    assert not dt.is_two_valued(_gpu_design("swaps40"))
+    got, want = dt.mst_two_valued(_gpu_design("swaps40")), mst_checker.brute_mst(_gpu_design("swaps40").raw)
+    assert all(np.array_equal(a, b) for a, b in zip(got, want))
+
+
+@pytest.mark.parametrize("perspective", ["global", "local"])
+@pytest.mark.parametrize("key", KEYS130)
+def test_rectangle_against_the_checkers(key, perspective):
+    d = _gpu_design(key)
+    Sq = 7
+    r = dt.rect(d, Sq)
+    pi, pj = cross_checker.rect_pairs(Sq, r.Sr)
+    out, _cnt, rsn = O.ici_pairs(d.X, pi, pj, perspective=perspective, want_counts=False)
+    raw, p, taumax, comp = (np.ascontiguousarray(out[:, f].reshape(Sq, r.Sr)) for f in range(4))
+    assert np.array_equal(rsn.reshape(Sq, r.Sr), r.reasons) and np.array_equal(np.isnan(raw), ~r.valid)
+    assert np.array_equal(bits(raw[r.valid]), bits(r.raw[r.valid])) and np.all(taumax[r.valid] == 1.0)
+    assert np.array_equal(np.bincount(rsn, minlength=5), r.reason_counts())
+    rect5 = [raw, raw, p, taumax, comp]
+    assert cross_checker.max_taumax(rect5) == r.max_taumax()
+    for k in (1, 7, r.Sr):
+        idx, nums, topraw, n_valid = dt.cross_topk(d, Sq, k)
+        ridx, rvals, rn = cross_checker.brute_cross_topk(rect5, k)
+        assert np.array_equal(idx, ridx) and np.array_equal(n_valid, rn) and np.array_equal(bits(topraw), bits(rvals[1]))
+    ref_cls = np.random.default_rng(3).integers(0, 3, r.Sr).astype(np.int32)
+    ref_cls[ref_cls == 2] = 3                                          # class 2 empty
+    ref_cls[d.kind[Sq:] != dt.VALID] = 4                               # a class of NA columns alone
+    cm = dt.cross_class_table(d, Sq, ref_cls, 5)
+    med2, n_valid = brute_cross_class(rect5, ref_cls, 5)
+    assert np.array_equal(cm["n_valid"], n_valid)
+    assert np.array_equal(bits(cm["med"]), bits(med2[1])) and np.array_equal(bits(cm["med"]), bits(med2[0]))
+    assert np.all(n_valid[:, [2, 4]] == 0) and np.all(bits(cm["med"][:, [2, 4]]) == dt.NA_REAL_BITS)
+
+
+# ---- a mutation that must keep failing: average linkage with one product fused into the sum --------------------------
+
+def _round(x):
+    return float(x)                     # Fraction -> float rounds once, to nearest even
+
+
+def _contracted(which):
+    """average_update with one product kept exact inside the sum (a fused multiply-add): four roundings, not five"""
+    def update(na, wa, nb, wb):
+        if which == "first":
+            s = _round(Fraction(na) * Fraction(wa) + Fraction(nb * wb))
+        else:
+            s = _round(Fraction(na * wa) + Fraction(nb) * Fraction(wb))
+        return s / (na + nb)
+    return update
+
+
+AVERAGE_DESIGNS = {
+    "rev24-520": lambda: dt.reversals(520, 24, seed=3),      # the GPU test's design for average linkage
+    "reversals41-wide": lambda: _gpu_design("reversals41-wide"),
+    "swaps40": lambda: _gpu_design("swaps40"),
+}
+
+
+@pytest.mark.parametrize("which", ["first", "second"])
+@pytest.mark.parametrize("key", list(AVERAGE_DESIGNS))
+def test_a_contracted_average_update_shows_on_the_designs(key, which):
+    """The guard that the designs of the GPU test can see an hc_update that the compiler contracted: DESIGN.md section
+    22 records a build that did.  If a design is changed, it must be changed to one for which this still holds."""
+    d = AVERAGE_DESIGNS[key]()
+    want = hclust_checker.brute_hclust(d.raw, "average")
+    got = hclust_checker.brute_hclust(d.raw, "average", average=_contracted(which))
+    n = min(len(want[0]), len(got[0]))
+    order = int(np.sum((want[0][:n] != got[0][:n]) | (want[1][:n] != got[1][:n])))
+    heights = int(np.sum(bits(want[3][:n]) != bits(got[3][:n])))
+    print(key, which, "merges that differ", order, "heights that differ", heights)
+    assert order + heights > 0
+    if key == "rev24-520" and which == "first":
+        assert order > 0                                               # the merge order itself changes
+    assert math.isfinite(want[3][0])

@@ -1,0 +1,594 @@
+"""The seven later selection entries (padjust, mst, hclust, anosim, cross, the prepared reference with its class table,
+permanova) on designed matrices whose ICI-Kendall-tau is known in closed form from integers (tests/designed_tau.py).
+Their own test files feed a brute-force checker with Context.matrix or Context.cross of the same input: the library is
+its own source of values there, on Gaussian columns whose tau clusters round 0.  Here the reference needs no S x S matrix
+from the library, so it reaches the key space (raw = -1 and +1, runs of thousands of equal keys), the accumulator bounds
+and the sizes (S = 2 049 ... 5 795, the triangle cut in two by the driver) that those files cannot.
+
+Every test first asserts that Context.pairs gives the closed form BITWISE on the first 2 000 combn pairs of its input
+(_closed_form_pairs).  From there integers compare as integers and doubles by their bits.  The p-value has no closed
+form: a p-value plane is compared with Context.pairs on the same pairs, and padjust's sorted p-values are one
+Context.pairs p-value per distinct numerator, repeated by its count.  hclust's reference is
+tests/hclust_checker.brute_hclust on the closed-form matrix, which is independent of the library."""
+import numpy as np
+import pytest
+
+from icikendalltau_amd import _lib
+from tests import designed_tau as dt
+from tests import test_gpu_designed_tau as base
+from tests.anosim_checker import documented_permutations
+from tests.cross_checker import rect_pairs
+from tests.hclust_checker import brute_hclust
+from tests.mst_checker import brute_mst
+from tests.padjust_checker import ALPHAS, METHODS, outputs_from_sorted
+from tests.test_gpu_designed_tau import CONFIGS, NA, ONE, _classes, _closed_form_pairs, _no_plan_override, _pvalues, _timed, bits
+from tests.test_gpu_medians import _five_classes
+
+pytestmark = pytest.mark.gpu
+
+KEYS130 = ["two-valued", "two-valued-half", "swaps40", "reversals41", "reversals41-wide"]
+PERSPECTIVES = ("global", "local")
+MEDIAN_STAGE_MAX = 4096         # icikt_medians.hip: the keys of a cell that stage in LDS
+PMV_ROW_RUN = 1024              # icikt_permanova.hip: the rows of one workgroup's run in k_pmv_perm
+PMV_LDS_CLASSES = 2048          # the classes whose bins k_pmv_classes keeps in LDS
+_REF = {}
+
+
+def _plus_minus(S, n, seed, split=None):
+    """every column +-base, no NA column: seeded signs, or + for the columns below `split` and - from there"""
+    if split is None:
+        signs = np.where(np.random.default_rng(seed).random(S) < 0.4, -1, 1)
+    else:
+        signs = np.where(np.arange(S) < split, 1, -1)
+    return dt.swaps(S, n, seed=seed, params=np.zeros(S, dtype=np.int64), signs=signs)
+
+
+_MORE = {
+    "rev24-520": lambda: dt.reversals(520, 24, seed=3),
+    "rev24-2051": lambda: dt.reversals(2051, 24, seed=3),
+    "rev24-5795": lambda: dt.reversals(5795, 24, seed=5),
+    # three prefix lengths (the whole column reversed is the base with the other sign) and two signs: four values of
+    # raw, each shared by a thousand or more of a query's partners
+    "rev24-4104": lambda: dt.reversals(4104, 24, seed=6, values=[0, 9, 24], flip=0.3),
+    "halves-2049": lambda: _plus_minus(2049, 24, 7, split=1024),
+    "plus-minus-5794": lambda: _plus_minus(5794, 24, 9),
+}
+
+
+def _design(key):
+    """the designs of tests/test_gpu_designed_tau.py, this file's own, and "<key>/valid": a design's valid columns alone"""
+    if key not in base._DESIGN:
+        if key in _MORE:
+            base._DESIGN[key] = _MORE[key]()
+        elif key.endswith("/valid"):
+            base._DESIGN[key] = dt.valid_columns(base._design(key[:-len("/valid")]))
+    return base._design(key)
+
+
+def _checked(ctx, key, perspectives=PERSPECTIVES):
+    _design(key)
+    return _closed_form_pairs(ctx, key, perspectives)
+
+
+def _ref(key, make):
+    if key not in _REF:
+        _REF[key] = make()
+    return _REF[key]
+
+
+def _layout(d, key, classes):
+    """the class layouts of tests/test_gpu_designed_tau.py; on a "/valid" design the same classes of the columns kept"""
+    if key.endswith("/valid"):
+        full = _design(key[:-len("/valid")])
+        cls, n_class = _classes(full, classes)
+        return np.ascontiguousarray(cls[full.kind == dt.VALID]), n_class
+    return _classes(d, classes)
+
+
+# ---- anosim and permanova --------------------------------------------------------------------------------------------
+
+def _assert_anosim(got, ref, d):
+    n_pairs, w2, nw, n_ge, n_undef, class_w2, class_nw, mx, rc5 = got
+    print("M, n_na", n_pairs.tolist(), ref["n_pairs"].tolist(), "labellings", len(w2), "differing w2", int(np.sum(w2 != ref["w2"])),
+          "nw", int(np.sum(nw != ref["nw"])), "n_ge", n_ge, ref["n_ge"], "n_undefined", n_undef, ref["n_undefined"])
+    assert np.array_equal(n_pairs, ref["n_pairs"])
+    assert np.array_equal(w2, ref["w2"]) and np.array_equal(nw, ref["nw"])
+    assert n_ge == ref["n_ge"] and n_undef == ref["n_undefined"]
+    assert np.array_equal(class_w2, ref["class_w2"]) and np.array_equal(class_nw, ref["class_nw"])
+    assert mx == d.max_taumax() and np.array_equal(rc5, d.reason_counts())
+
+
+def _assert_permanova(got, ref, d):
+    n_pairs, Q, class_q, mx, rc5 = got
+    want = np.array(ref["class_q"], dtype=object).reshape(class_q.shape)
+    print("values, n_na", n_pairs.tolist(), ref["n_pairs"].tolist(), "Q", Q, ref["q_total"], "cells", class_q.size,
+          "non-zero", int(np.count_nonzero(want)), "differing cells", int(np.sum(class_q != want)))
+    assert np.array_equal(n_pairs, ref["n_pairs"])
+    assert isinstance(Q, int) and Q == ref["q_total"]
+    assert class_q.tolist() == ref["class_q"]
+    assert mx == d.max_taumax() and np.array_equal(rc5, d.reason_counts())
+
+
+def _small_labels(d, key, classes):
+    cls, n_class = _layout(d, key, classes)
+    return cls, n_class, documented_permutations(cls, 33, seed=13)
+
+
+@pytest.mark.parametrize("classes", ["interleaved", "na-class"])
+@pytest.mark.parametrize("key", KEYS130)
+def test_anosim(hip_ctx, key, classes):
+    d = _checked(hip_ctx, key)
+    cls, n_class, perms = _small_labels(d, key, classes)
+    ref = _ref(("anosim", key, classes), lambda: dt.anosim(d, cls, n_class, perms))
+    cnt = dt.group_counts(d)[0][0]
+    if key.startswith("two-valued"):      # two runs of thousands of equal keys, at the two ends of the key space
+        assert np.count_nonzero(cnt) == 2 and cnt[0] >= 3000 and cnt[2 * d.m] >= 3000
+    assert ref["n_pairs"][1] > 0 and ref["n_undefined"] == 0 and 0 < ref["nw"][0] < ref["n_pairs"][0]
+    for perspective in PERSPECTIVES:
+        _assert_anosim(hip_ctx.anosim(d.X, cls, n_class, perms, None, perspective), ref, d)
+    _assert_anosim(hip_ctx.anosim(d.X, cls, n_class, None), dt.anosim(d, cls, n_class, perms[:0]), d)
+
+
+@pytest.mark.parametrize("key", ["two-valued", "reversals41-wide"])
+def test_anosim_under_another_plan(plan_ctx, key):
+    d = _checked(plan_ctx, key, ("global",))
+    cls, n_class, perms = _small_labels(d, key, "interleaved")
+    ref = _ref(("anosim", key, "interleaved"), lambda: dt.anosim(d, cls, n_class, perms))
+    plan_ctx.debug_set_plan("anostrip=64,anoperms=3,tkblock=1")
+    _assert_anosim(plan_ctx.anosim(d.X, cls, n_class, perms), ref, d)
+
+
+@pytest.mark.parametrize("key", [k + v for k in KEYS130 for v in ("/valid", "")])
+def test_permanova(hip_ctx, key):
+    """"/valid": no NA pair, so every class is summed; the whole design has NA columns: Q alone, every A_c zero"""
+    d = _checked(hip_ctx, key)
+    for classes in (("interleaved",) if key.endswith("/valid") else ("interleaved", "na-class")):
+        cls, n_class, perms = _small_labels(d, key, classes)
+        ref = _ref(("permanova", key, classes), lambda: dt.permanova(d, cls, n_class, perms))
+        if key.endswith("/valid"):
+            assert ref["n_pairs"][1] == 0 and sum(ref["class_q"][0]) > 0 and ref["n_undefined"] == 0
+            if key.startswith("two-valued"):     # only q = 0 and q = 2^52 are summed
+                table = dt.q_table(d)
+                assert table[0] == 1 << 52 and table[2 * d.m] == 0 and ref["q_total"] % (1 << 52) == 0
+                assert all(a % (1 << 52) == 0 for row in ref["class_q"] for a in row)
+        else:
+            assert ref["n_pairs"][1] > 0 and not any(any(row) for row in ref["class_q"]) and ref["q_total"] > 0
+        for perspective in PERSPECTIVES:
+            _assert_permanova(hip_ctx.permanova(d.X, cls, n_class, perms, None, perspective), ref, d)
+
+
+@pytest.mark.parametrize("key", ["two-valued/valid", "reversals41-wide/valid"])
+def test_permanova_under_another_plan(plan_ctx, key):
+    d = _checked(plan_ctx, key, ("global",))
+    cls, n_class, perms = _small_labels(d, key, "interleaved")
+    ref = _ref(("permanova", key, "interleaved"), lambda: dt.permanova(d, cls, n_class, perms))
+    plan_ctx.debug_set_plan("anostrip=64,anoperms=3,tkblock=1")
+    _assert_permanova(plan_ctx.permanova(d.X, cls, n_class, perms), ref, d)
+
+
+# ---- padjust ---------------------------------------------------------------------------------------------------------
+
+def _sorted_p(ctx, d, perspective, alternative):
+    """one Context.pairs p-value per distinct numerator (|num| for "two.sided"), repeated by its count"""
+    one_sided = alternative != "two.sided"
+    keys, count, fi, fj, _n_na = dt.pvalue_keys(d, one_sided)
+    out, _cnt, _rsn = ctx.pairs(d.X, fi, fj, perspective=perspective, alternative=alternative, want_counts=False)
+    p, n_na = dt.sorted_pvalues(d, out[:, 1], one_sided)
+    return p, n_na, count
+
+
+def _assert_padjust(got, ref, d, max_table):
+    n_tests, n_rej, cutoff, table, n_table, mx, rc5 = got
+    t = min(ref["n_table"], max_table)
+    print("n_tests", n_tests.tolist(), "n_rejected", n_rej.tolist(), ref["n_rejected"].tolist(), "n_table", n_table,
+          ref["n_table"], "differing", int(np.sum(bits(cutoff) != bits(ref["p_cutoff"]))),
+          int(np.sum(bits(table[0]) != bits(ref["table_p"][:t]))) if table.shape[1] == t else "shape")
+    assert np.array_equal(n_tests, ref["n_tests"]) and np.array_equal(n_rej, ref["n_rejected"])
+    assert np.array_equal(bits(cutoff), bits(ref["p_cutoff"]))
+    assert n_table == ref["n_table"] and table.shape == (2, t)
+    assert np.array_equal(bits(table[0]), bits(ref["table_p"][:t]))
+    assert np.array_equal(bits(table[1]), bits(ref["table_adjusted"][:t]))
+    assert mx == d.max_taumax() and np.array_equal(rc5, d.reason_counts())
+
+
+def _padjust_case(ctx, d, p, n_na, method, perspective, alternative, label=None, short_table=False):
+    """the five ALPHAS and, where a run of equal p has more than one unscanned product, a level inside the longest one;
+    returns how each level's cut meets the runs"""
+    a_in = dt.alpha_inside_a_run(p, method)
+    alphas = ALPHAS + (() if a_in is None else (a_in,))
+    ref = outputs_from_sorted(p, n_na, method, alphas)
+    kinds = dt.cuts_in_runs(p, method, alphas)
+    if a_in is not None:
+        assert kinds[-1] == "inside"
+    rooms = (ref["n_table"], ref["n_table"] + 5) + ((ref["n_table"] // 2,) if short_table else ())
+    for room in rooms:
+        call = lambda: ctx.padjust(d.X, method, alphas, room, None, perspective, alternative)   # noqa: E731
+        got = call() if label is None else _timed(label, call)
+        _assert_padjust(got, ref, d, room)
+    return kinds
+
+
+@pytest.mark.parametrize("alternative", ["two.sided", "greater"])
+@pytest.mark.parametrize("key", KEYS130)
+def test_padjust(hip_ctx, key, alternative):
+    d = _checked(hip_ctx, key)
+    kinds = set()
+    for perspective in PERSPECTIVES:
+        p, n_na, count = _sorted_p(hip_ctx, d, perspective, alternative)
+        assert count.max() >= 100 and len(p) + n_na == d.S * (d.S - 1) // 2      # hundreds of pairs share a p
+        for method in METHODS:
+            kinds |= set(_padjust_case(hip_ctx, d, p, n_na, method, perspective, alternative, short_table=True))
+    print(key, alternative, "cuts", kinds)
+    assert "inside" in kinds                               # the scan alone decided where a whole run of equal p falls
+    if alternative == "greater" or key == "reversals41-wide":
+        assert "edge" in kinds                             # and a cut where two runs meet, 0 < n_rejected < m
+
+
+# ---- mst -------------------------------------------------------------------------------------------------------------
+
+def _assert_mst(ctx, got, ref, d, perspective="global", pvalues=True):
+    ri, rj, rcomp, rn = ref
+    ti, tj, vals, component, n_comp, n_rounds, mx, rc5 = got
+    print("S", d.S, "n_tree", len(ti), len(ri), "n_components", n_comp, rn, "n_rounds", n_rounds,
+          "differing edges", int(np.sum((ti != ri) | (tj != rj))) if len(ti) == len(ri) else "length")
+    assert len(ti) + n_comp == d.S and np.array_equal(ti, ri) and np.array_equal(tj, rj)
+    assert np.array_equal(component, rcomp) and n_comp == rn
+    raw = d.value(d.num[ri, rj])
+    assert vals.shape == (5, len(ri))
+    assert np.array_equal(bits(vals[1]), bits(raw)) and np.array_equal(bits(vals[0]), bits(raw))
+    assert np.all(bits(vals[3:5]) == ONE)
+    if pvalues and len(ri):
+        assert np.array_equal(bits(vals[2]), bits(_pvalues(ctx, d, ri, rj, perspective)))
+    assert mx == d.max_taumax() and np.array_equal(rc5, d.reason_counts())
+
+
+def _value_that_hundreds_equal(d, key):
+    """the largest numerator that 200 pairs equal; on reversals41-wide, whose hundreds of distinct values are shared by
+    fewer pairs each, its most frequent one"""
+    cnt = dt.group_counts(d)[0][0]
+    floor = 30 if key == "reversals41-wide" else 200
+    t = int(np.max(np.nonzero(cnt >= floor)[0])) - d.m
+    print(key, "bound", t, "/", d.m, "pairs equal to it", int(cnt[t + d.m]))
+    assert cnt[t + d.m] >= (30 if key == "reversals41-wide" else 200)
+    return t
+
+
+@pytest.mark.parametrize("key", KEYS130)
+def test_mst(hip_ctx, key):
+    d = _checked(hip_ctx, key)
+    ref = _ref(("mst", key), lambda: brute_mst(d.raw))
+    if key.startswith("two-valued"):
+        closed = dt.mst_two_valued(d)
+        assert dt.is_two_valued(d) and all(np.array_equal(a, b) for a, b in zip(closed, ref))
+        assert int(np.sum(d.num[ref[0], ref[1]] < 0)) == 1            # one bridge of raw = -1 between the sign groups
+    t = _value_that_hundreds_equal(d, key)
+    bound = _ref(("mst", key, t), lambda: brute_mst(d.raw, float(d.value(t))))
+    above = brute_mst(d.raw, float(d.value(t + 1)))
+    print(key, "min_raw", t, "/", d.m, "components without a bound, on the value, above it", ref[3], bound[3], above[3])
+    assert ref[3] <= bound[3] <= above[3]
+    for perspective, scale_max in CONFIGS:
+        _assert_mst(hip_ctx, hip_ctx.mst(d.X, None, None, perspective, "two.sided", False, 0, scale_max), ref, d, perspective)
+        _assert_mst(hip_ctx, hip_ctx.mst(d.X, float(d.value(t)), None, perspective, "two.sided", False, 0, scale_max), bound,
+                    d, perspective)
+
+
+# ---- hclust ----------------------------------------------------------------------------------------------------------
+
+def _assert_hclust(got, ref, d):
+    ra, rb, rsize, rraw, rcomp, rn = ref
+    ma, mb, msize, mraw, mcor, component, n_comp, mx, rc5 = got
+    same_len = len(ma) == len(ra)
+    print("S", d.S, "n_merges", len(ma), len(ra), "n_components", n_comp, rn,
+          "differing merges", int(np.sum((ma != ra) | (mb != rb))) if same_len else "length",
+          "differing heights", int(np.sum(bits(mraw) != bits(rraw))) if same_len else "length")
+    assert len(ma) + n_comp == d.S
+    assert np.array_equal(ma, ra) and np.array_equal(mb, rb) and np.array_equal(msize, rsize)
+    assert np.array_equal(bits(mraw), bits(rraw)) and np.array_equal(bits(mcor), bits(rraw))     # taumax == 1
+    assert np.array_equal(component, rcomp) and n_comp == rn
+    assert mx == d.max_taumax() and np.array_equal(rc5, d.reason_counts())
+
+
+@pytest.mark.parametrize("method", ["complete", "average", "single"])
+@pytest.mark.parametrize("key", KEYS130)
+def test_hclust(hip_ctx, key, method):
+    d = _checked(hip_ctx, key)
+    ref = _ref(("hclust", key, method), lambda: brute_hclust(d.raw, method))
+    t = _value_that_hundreds_equal(d, key)
+    bound = brute_hclust(d.raw, method, float(d.value(t)))
+    print(key, method, "min_raw", t, "/", d.m, "merges", len(ref[0]), len(bound[0]))
+    assert len(ref[0]) > 100 and 0 < len(bound[0]) <= len(ref[0])
+    for perspective, scale_max in CONFIGS:
+        _assert_hclust(hip_ctx.hclust(d.X, method, None, None, perspective, "two.sided", False, 0, scale_max), ref, d)
+    _assert_hclust(hip_ctx.hclust(d.X, method, float(d.value(t))), bound, d)
+
+
+# ---- cross and the prepared reference ----------------------------------------------------------------------------------
+
+@pytest.fixture(scope="module")
+def ref_ctx():
+    """the prepared reference's context: every other call on a context drops its reference"""
+    ctx = _lib.Context(0)
+    yield ctx
+    ctx.close()
+
+
+def _assert_rect(ctx, got, r, k, perspective, planes=True):
+    """Context.cross' six items against the rectangle's integers"""
+    out5, idx, vals, n_valid, mx, rc5 = got
+    d, Sq, Sr = r.d, r.Sq, r.Sr
+    pi, pj = rect_pairs(Sq, Sr)
+    pairs, rsn = _ref(("rectangle's pairs", id(d), Sq, perspective),
+                      lambda: ctx.pairs(d.X, pi, pj, perspective=perspective, want_counts=False)[::2])
+    assert np.array_equal(rsn.reshape(Sq, Sr), r.reasons)
+    pv = pairs.reshape(Sq, Sr, 4)
+    if planes:
+        ok = r.valid
+        assert out5.shape == (5, Sq, Sr) and np.all(np.isnan(out5[:, ~ok]))
+        want = d.value(r.num)
+        assert np.array_equal(bits(out5[1][ok]), bits(want[ok])) and np.array_equal(bits(out5[0][ok]), bits(want[ok]))
+        assert np.all(bits(out5[3][ok]) == ONE) and np.all(bits(out5[4][ok]) == ONE)
+        assert np.array_equal(bits(out5[2][ok]), bits(np.ascontiguousarray(pv[:, :, 1])[ok]))
+    if k is not None:
+        ridx, _nums, rraw, rn = dt.cross_topk(d, Sq, k)
+        print("Sq", Sq, "Sr", Sr, "k", k, "differing partners", int(np.sum(idx != ridx)))
+        assert np.array_equal(n_valid, rn) and np.array_equal(idx, ridx)
+        assert np.array_equal(bits(vals[1]), bits(rraw)) and np.array_equal(bits(vals[0]), bits(rraw))
+        sel = ridx >= 0
+        assert np.all(bits(vals[3:5])[:, sel] == ONE) and np.all(bits(vals)[:, ~sel] == NA)
+        rows = np.repeat(np.arange(Sq), k).reshape(Sq, k)
+        assert np.array_equal(bits(vals[2][sel]), bits(np.ascontiguousarray(pv[:, :, 1])[rows[sel], ridx[sel]]))
+    assert mx == r.max_taumax() and np.array_equal(rc5, r.reason_counts())
+
+
+def _assert_class_table(got, cm):
+    med2, n_valid = got[6], got[7]
+    print("cells", n_valid.size, "differing", int(np.sum(bits(med2[1]) != bits(cm["med"]))))
+    assert np.array_equal(n_valid, cm["n_valid"])
+    assert np.array_equal(bits(med2[1]), bits(cm["med"])) and np.array_equal(bits(med2[0]), bits(cm["med"]))
+
+
+def _ref_classes(d, Sq):
+    """the reference columns' classes of the interleaved layout with the NA columns moved into class 2 -- a class of NA
+    columns alone -- and one more class index that no column has: an empty class"""
+    cls, n_class = _classes(d, "na-class")
+    return np.ascontiguousarray(cls[Sq:]), n_class + 1
+
+
+@pytest.mark.parametrize("Sq", [5, 8])
+@pytest.mark.parametrize("key", ["two-valued", "swaps40", "reversals41", "reversals41-wide"])
+def test_cross_and_cross_prepared(hip_ctx, ref_ctx, key, Sq):
+    d = _checked(hip_ctx, key)
+    r = dt.rect(d, Sq)
+    ref_cls, n_class = _ref_classes(d, Sq)
+    cm = dt.cross_class_table(d, Sq, ref_cls, n_class)
+    sizes = np.bincount(ref_cls, minlength=n_class)
+    assert sizes[2] > 0 and np.all(d.kind[Sq:][ref_cls == 2] != dt.VALID) and sizes[-1] == 0
+    assert np.all(cm["n_valid"][:, [2, -1]] == 0) and np.all(bits(cm["med"][:, [2, -1]]) == NA)
+    even = (cm["n_valid"] > 0) & (cm["n_valid"] % 2 == 0)
+    print(key, Sq, "even cells: edge of a run", int((even & (cm["k_in"] + 1 == cm["run"])).sum()), "inside",
+          int((even & (cm["k_in"] + 1 < cm["run"])).sum()))
+    _idx, nums, _raw, n_valid = dt.cross_topk(d, Sq, 7)
+    tied = (n_valid == 7) & ((r.valid & (r.num >= nums[:, 6][:, None])).sum(axis=1) > 7)
+    print(key, Sq, "queries with more than k candidates equal to or above the k-th", int(tied.sum()))
+    if key != "reversals41-wide":
+        assert tied.any()                                     # the reference index alone decides the k-th place
+    ref_ctx.prepare_reference(r.R, 8)
+    for perspective, scale_max in CONFIGS:
+        for k in (1, 7, r.Sr):
+            got = hip_ctx.cross(r.Q, r.R, k, k == 7, None, perspective, "two.sided", False, 0, scale_max)
+            _assert_rect(hip_ctx, got, r, k, perspective, planes=k == 7)
+            prepared = ref_ctx.cross_prepared(r.Q, k, k == 7, ref_cls, n_class, perspective, "two.sided", False, 0, scale_max)
+            _assert_rect(hip_ctx, prepared[:6], r, k, perspective, planes=k == 7)
+            _assert_class_table(prepared, cm)
+
+
+# ---- at the sizes where the kernels change behaviour (the natural plan) ------------------------------------------------
+
+def test_2049_samples_anosim(hip_ctx, monkeypatch):
+    """2 098 176 pairs: more than 2 048 x 1 024; nine strips of 256 columns and eight runs of 256 rows of k_anosim_perm"""
+    _no_plan_override(monkeypatch)
+    d = _checked(hip_ctx, "rev24-2049", ("global",))
+    assert d.S * (d.S - 1) // 2 > 2048 * 1024
+    cls, n_class = _five_classes(d.S)
+    perms = documented_permutations(cls, 33, seed=13)
+    ref = _timed("S=2049 anosim, the reference", lambda: dt.anosim(d, cls, n_class, perms))
+    _assert_anosim(_timed("S=2049 anosim", lambda: hip_ctx.anosim(d.X, cls, n_class, perms)), ref, d)
+
+
+def test_2051_samples_anosim_and_permanova(hip_ctx, monkeypatch):
+    """No NA column, so PERMANOVA sums every class; S - 1 = 2 050 rows above the last column: three runs of
+    k_pmv_perm's 1 024 rows meet in the column sums (S = 2 049 has exactly two), nine runs of k_anosim_perm's 256"""
+    _no_plan_override(monkeypatch)
+    d = _checked(hip_ctx, "rev24-2051", ("global",))
+    assert d.S * (d.S - 1) // 2 > 2048 * 1024 and d.S - 1 > PMV_ROW_RUN * 2 and d.S - 1 > 256 * 8
+    cls, n_class = _five_classes(d.S)
+    perms = documented_permutations(cls, 33, seed=13)
+    ref = _timed("S=2051 permanova, the reference", lambda: dt.permanova(d, cls, n_class, perms))
+    assert ref["n_pairs"][1] == 0 and all(all(row) for row in ref["class_q"])
+    _assert_permanova(_timed("S=2051 permanova", lambda: hip_ctx.permanova(d.X, cls, n_class, perms)), ref, d)
+    ref = _timed("S=2051 anosim, the reference", lambda: dt.anosim(d, cls, n_class, perms))
+    _assert_anosim(_timed("S=2051 anosim", lambda: hip_ctx.anosim(d.X, cls, n_class, perms)), ref, d)
+
+
+def test_2049_samples_permanova_with_na_columns(hip_ctx, monkeypatch):
+    _no_plan_override(monkeypatch)
+    d = _checked(hip_ctx, "rev24-2049", ("global",))
+    cls, n_class = _five_classes(d.S)
+    perms = documented_permutations(cls, 5, seed=13)
+    ref = dt.permanova(d, cls, n_class, perms)
+    assert ref["n_pairs"][1] == 2 * d.S - 3 and ref["q_total"] > 0 and not any(any(row) for row in ref["class_q"])
+    _assert_permanova(_timed("S=2049 permanova, NA columns", lambda: hip_ctx.permanova(d.X, cls, n_class, perms)), ref, d)
+
+
+def test_2049_samples_permanova_at_the_accumulator_bound(hip_ctx, monkeypatch):
+    """Columns 0 ... 1 023 are +base, the others -base.  For a column j >= 1 024 the first run of k_pmv_perm's rows is
+    1 024 values of raw = -1, q = 2^52 each: acc = 2^62, the bound written at the top of icikt_permanova.hip, and Q is
+    1 024 x 1 025 x 2^52, about 2^72, across both limbs.  One class; then two classes, class 0 the columns below 1 536,
+    which still holds the whole first run of 512 columns, with five other labellings."""
+    _no_plan_override(monkeypatch)
+    d = _checked(hip_ctx, "halves-2049", ("global",))
+    table = dt.q_table(d)
+    q_of = table[(d.num[:PMV_ROW_RUN, :] + d.m)]                           # the first run of every column
+    assert table[0] == 1 << 52 and table[2 * d.m] == 0
+    one = np.zeros(d.S, dtype=np.int32)
+    two = (np.arange(d.S) >= 1536).astype(np.int32)
+    for cls, n_class, n_perm in ((one, 1, 0), (two, 2, 5)):
+        acc = [int(q_of[cls[:PMV_ROW_RUN] == cls[j], j].sum()) for j in (PMV_ROW_RUN, 1535, d.S - 1)]
+        print("classes", n_class, "acc of the first run of columns 1024, 1535, 2048:", acc)
+        assert acc[0] == acc[1] == 1 << 62                                    # acc = 2^62 reached
+        perms = documented_permutations(cls, n_perm, seed=13)
+        ref = dt.permanova(d, cls, n_class, perms)
+        assert ref["q_total"] == 1024 * 1025 * (1 << 52) and ref["n_pairs"].tolist() == [d.S * (d.S - 1) // 2, 0]
+        assert ref["class_q"][0] == ([ref["q_total"]] if n_class == 1 else [1024 * 512 * (1 << 52), 0])
+        got = _timed("S=2049 permanova at acc = 2^62, %d class(es)" % n_class,
+                     lambda: hip_ctx.permanova(d.X, cls, n_class, perms if n_perm else None))
+        _assert_permanova(got, ref, d)
+
+
+def test_4098_samples_permanova_bins_in_global_memory(hip_ctx, monkeypatch):
+    """2 049 classes of two samples: more than the 2 048 classes whose bins fit in LDS, so k_pmv_classes adds to its
+    bins in global memory, and every bin of the observed labelling holds the q of its one pair"""
+    _no_plan_override(monkeypatch)
+    d = _checked(hip_ctx, "rev24-4098", ("global",))
+    n_class = d.S // 2
+    assert n_class > PMV_LDS_CLASSES and (d.kind == dt.VALID).all()
+    cls = np.random.default_rng(12).permutation(np.repeat(np.arange(n_class), 2)).astype(np.int32)
+    perms = documented_permutations(cls, 3, seed=13)
+    ref = _timed("S=4098 permanova, the reference", lambda: dt.permanova(d, cls, n_class, perms))
+    table = dt.q_table(d)
+    first = np.array([np.nonzero(cls == c)[0] for c in range(n_class)])
+    assert ref["class_q"][0] == [int(table[d.num[a, b] + d.m]) for a, b in first]
+    print("non-zero bins of the observed labelling", sum(1 for a in ref["class_q"][0] if a), "of", n_class)
+    assert sum(1 for a in ref["class_q"][0] if a) > 0.9 * n_class
+    _assert_permanova(_timed("S=4098 permanova, 2049 classes", lambda: hip_ctx.permanova(d.X, cls, n_class, perms)), ref, d)
+
+
+def test_2049_samples_padjust(hip_ctx, monkeypatch):
+    """2 098 176 pairs: chip-wide scans over about 2 000 chunks of 1 024 keys, runs of equal p tens of thousands long"""
+    _no_plan_override(monkeypatch)
+    d = _checked(hip_ctx, "rev24-2049", ("global",))
+    assert d.S * (d.S - 1) // 2 > 2048 * 1024
+    p, n_na, count = _sorted_p(hip_ctx, d, "global", "two.sided")
+    assert count.max() > 10 * 1024
+    kinds = set()
+    for method in METHODS:
+        kinds |= set(_padjust_case(hip_ctx, d, p, n_na, method, "global", "two.sided", "S=2049 padjust " + method))
+    print("cuts", kinds)
+    assert "inside" in kinds
+
+
+def test_2049_samples_mst(hip_ctx, monkeypatch):
+    """Boruvka rounds over 2 098 176 pairs with a few hundred distinct keys: the combn index decides nearly every edge"""
+    _no_plan_override(monkeypatch)
+    d = _checked(hip_ctx, "rev24-2049", ("global",))
+    assert d.S * (d.S - 1) // 2 > 2048 * 1024
+    ref = _timed("S=2049 mst, the reference", lambda: brute_mst(d.raw))
+    assert len(np.unique(d.num[d.valid])) < 600 and ref[3] == 3
+    _assert_mst(hip_ctx, _timed("S=2049 mst", lambda: hip_ctx.mst(d.X)), ref, d)
+
+
+@pytest.mark.parametrize("method", ["complete", "average", "single"])
+def test_520_samples_hclust(hip_ctx, monkeypatch, method):
+    """ceil(520 / 256) = 3 merge workgroups, the last with a tail of 8 slots.  tests/test_designed_tau_host.py shows
+    that an average update with one product fused into the sum changes the merge order on this design."""
+    _no_plan_override(monkeypatch)
+    d = _checked(hip_ctx, "rev24-520", ("global",))
+    assert d.S > 2 * 256 and d.S % 256 != 0
+    ref = _timed("S=520 hclust %s, the reference" % method, lambda: brute_hclust(d.raw, method))
+    assert len(ref[0]) == d.S - 1
+    _assert_hclust(_timed("S=520 hclust " + method, lambda: hip_ctx.hclust(d.X, method)), ref, d)
+
+
+def test_4099_reference_columns_cross(hip_ctx, ref_ctx, monkeypatch):
+    """Sq = 5 against Sr = 4 099.  k = 256: with 24 rows a query has thousands of partners equal to its k-th, so flush
+    after flush of k_cross_topk is decided by the reference index.  A class of 4 097 members re-reads its keys past
+    MEDIAN_STAGE_MAX, one of 4 096 is the largest that stages; classes of 1 and 2, and an empty class."""
+    _no_plan_override(monkeypatch)
+    d = _checked(hip_ctx, "rev24-4104", ("global",))
+    Sq, k = 5, 256
+    r = dt.rect(d, Sq)
+    assert r.Sr == 4099 and r.valid.all()
+    _idx, nums, _raw, n_valid = dt.cross_topk(d, Sq, k)
+    equal_kth = (r.num == nums[:, k - 1][:, None]).sum(axis=1)
+    beyond = (r.num >= nums[:, k - 1][:, None]).sum(axis=1)
+    print("partners equal to the k-th", equal_kth.tolist(), "at or above it", beyond.tolist())
+    assert np.all(n_valid == k) and np.all(beyond > k) and equal_kth.max() > 1000     # more than k candidates equal to the k-th
+    got = _timed("Sq=5 Sr=4099 cross", lambda: hip_ctx.cross(r.Q, r.R, k))
+    _assert_rect(hip_ctx, got, r, k, "global")
+    ref_ctx.prepare_reference(r.R, Sq)
+    order = np.random.default_rng(21).permutation(r.Sr)
+    for sizes in ((4097, 1, 0, 1), (4096, 2, 0, 1)):
+        ref_cls = np.empty(r.Sr, dtype=np.int32)
+        ref_cls[order] = np.repeat(np.arange(4), sizes)
+        assert np.bincount(ref_cls, minlength=4).tolist() == list(sizes)
+        assert (sizes[0] > MEDIAN_STAGE_MAX) == (sizes[0] == 4097)                    # class size > MEDIAN_STAGE_MAX
+        cm = dt.cross_class_table(d, Sq, ref_cls, 4)
+        assert cm["n_valid"][0].tolist() == list(sizes) and np.all(bits(cm["med"][:, 2]) == NA)
+        got = _timed("Sq=5 Sr=4099 cross_prepared, class of %d" % sizes[0],
+                     lambda: ref_ctx.cross_prepared(r.Q, k, True, ref_cls, 4))
+        _assert_rect(hip_ctx, got[:6], r, k, "global")
+        _assert_class_table(got, cm)
+
+
+def _cut_in_two(d):
+    S = d.S
+    total = S * (S - 1) // 2
+    assert total > 1 << 24                                # pairs > 2^24 = kTriangleBlockPairs: the driver cuts the triangle
+    assert S > 5794 or (S - 1) * (S - 2) // 2 <= 1 << 24  # (5 794 is the smallest S at which it does)
+    return total
+
+
+def test_5794_samples_anosim(hip_ctx, monkeypatch):
+    _no_plan_override(monkeypatch)
+    d = _checked(hip_ctx, "rev24-5794", ("global",))
+    _cut_in_two(d)
+    cls, n_class = _five_classes(d.S)
+    perms = documented_permutations(cls, 4, seed=13)
+    ref = _timed("S=5794 anosim, the reference", lambda: dt.anosim(d, cls, n_class, perms))
+    _assert_anosim(_timed("S=5794 anosim", lambda: hip_ctx.anosim(d.X, cls, n_class, perms)), ref, d)
+
+
+@pytest.mark.parametrize("method", ["BH", "holm"])
+def test_5794_samples_padjust(hip_ctx, monkeypatch, method):
+    _no_plan_override(monkeypatch)
+    d = _checked(hip_ctx, "rev24-5794", ("global",))
+    _cut_in_two(d)
+    p, n_na, _count = _ref("sorted p of rev24-5794", lambda: _sorted_p(hip_ctx, d, "global", "two.sided"))
+    kinds = _padjust_case(hip_ctx, d, p, n_na, method, "global", "two.sided", "S=5794 padjust " + method)
+    assert "inside" in kinds
+
+
+def test_5794_samples_permanova_with_na_columns(hip_ctx, monkeypatch):
+    _no_plan_override(monkeypatch)
+    d = _checked(hip_ctx, "rev24-5794", ("global",))
+    total = _cut_in_two(d)
+    cls, n_class = _five_classes(d.S)
+    perms = documented_permutations(cls, 2, seed=13)
+    ref = _timed("S=5794 permanova, the reference", lambda: dt.permanova(d, cls, n_class, perms))
+    assert ref["n_pairs"].sum() == total and ref["n_pairs"][1] == 2 * d.S - 3
+    _assert_permanova(_timed("S=5794 permanova, NA columns", lambda: hip_ctx.permanova(d.X, cls, n_class, perms)), ref, d)
+
+
+def test_5795_samples_permanova(hip_ctx, monkeypatch):
+    """no NA column, so the classes are summed across the block cut"""
+    _no_plan_override(monkeypatch)
+    d = _checked(hip_ctx, "rev24-5795", ("global",))
+    _cut_in_two(d)
+    cls, n_class = _five_classes(d.S)
+    perms = documented_permutations(cls, 4, seed=13)
+    ref = _timed("S=5795 permanova, the reference", lambda: dt.permanova(d, cls, n_class, perms))
+    assert ref["n_pairs"][1] == 0 and all(all(row) for row in ref["class_q"])
+    _assert_permanova(_timed("S=5795 permanova", lambda: hip_ctx.permanova(d.X, cls, n_class, perms)), ref, d)
+    base._DESIGN.pop("rev24-5795")
+
+
+def test_5794_samples_mst(hip_ctx, monkeypatch):
+    """every column +-base, no NA column: the closed-form forest -- two stars and one bridge -- across the block cut"""
+    _no_plan_override(monkeypatch)
+    d = _checked(hip_ctx, "plus-minus-5794", ("global",))
+    _cut_in_two(d)
+    assert dt.is_two_valued(d)
+    ref = dt.mst_two_valued(d)
+    assert ref[3] == 1 and int(np.sum(d.num[ref[0], ref[1]] < 0)) == 1
+    _assert_mst(hip_ctx, _timed("S=5794 mst", lambda: hip_ctx.mst(d.X)), ref, d)
+    base._DESIGN.pop("plus-minus-5794")
