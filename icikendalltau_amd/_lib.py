@@ -34,7 +34,8 @@ HEADERS = [os.path.join(_ROOT, "include", "icikt.h"), os.path.join(_PKG, "csrc",
            os.path.join(_PKG, "csrc", "icikt_transfer.h"), os.path.join(_PKG, "csrc", "icikt_colsort.h"),
            os.path.join(_PKG, "csrc", "icikt_blocks.h"), os.path.join(_PKG, "csrc", "icikt_select.h"),
            os.path.join(_PKG, "csrc", "icikt_keys.h"), os.path.join(_PKG, "csrc", "icikt_k0plan.h"),
-           os.path.join(_PKG, "csrc", "icikt_k1plan.h"), os.path.join(_PKG, "csrc", "icikt_fixed.h")]
+           os.path.join(_PKG, "csrc", "icikt_k1plan.h"), os.path.join(_PKG, "csrc", "icikt_fixed.h"),
+           os.path.join(_PKG, "csrc", "icikt_labels.h")]
 
 # include/icikt.h
 SUCCESS = 0
@@ -522,14 +523,34 @@ class _SelectCall:
 
 
 def _class_arg(cls, n_samp):
-    """cls of class_medians, class_matrix, quantiles and anosim as the library takes it: None (one class), or a
-    contiguous int32 class index per column."""
+    """cls of class_medians, class_matrix, quantiles, anosim and permanova as the library takes it: None (one class), or
+    a contiguous int32 class index per column."""
     if cls is None:
         return None
     cls_a = np.ascontiguousarray(cls, dtype=np.int32)
     if cls_a.shape != (n_samp,):
         raise ValueError("cls must give one class per column")
     return cls_a
+
+
+def _labellings_arg(cls, n_class, perm_cls, n_samp):
+    """cls, n_class and perm_cls of anosim and permanova as the library takes them, and the room their results need:
+    (cls_a, n_class, perm_a, n_perm, room, n_lab) with room the classes and n_lab the labellings the library may write
+    (it refuses what is past its limits before it writes: the arrays are then of one class, one labelling)."""
+    cls_a = _class_arg(cls, n_samp)
+    if cls_a is None:
+        n_class = 1
+    n_class = int(n_class)
+    if perm_cls is None:
+        perm_a, n_perm = None, 0
+    else:
+        perm_a = np.ascontiguousarray(perm_cls, dtype=np.int32)
+        if perm_a.ndim != 2 or perm_a.shape[1] != n_samp:
+            raise ValueError("perm_cls must be [n_perm, S]: one class per column in every row")
+        n_perm = int(perm_a.shape[0])
+    room = n_class if 1 <= n_class <= 65535 else 1
+    n_lab = 1 + (n_perm if n_perm <= ANOSIM_MAX_PERM else 0)
+    return cls_a, n_class, perm_a, n_perm, room, n_lab
 
 
 class Context:
@@ -1009,20 +1030,7 @@ class Context:
         (M, w2, nw) into the statistic.  The argument checks are the library's: a label out of range, more than 65 535 classes or a
         bad perspective raises IciktError."""
         sel = _SelectCall(self, self._entry("anosim", X, flags))
-        n_samp = sel.n_samp
-        cls_a = _class_arg(cls, n_samp)
-        if cls_a is None:
-            n_class = 1
-        n_class = int(n_class)
-        if perm_cls is None:
-            perm_a, n_perm = None, 0
-        else:
-            perm_a = np.ascontiguousarray(perm_cls, dtype=np.int32)
-            if perm_a.ndim != 2 or perm_a.shape[1] != n_samp:
-                raise ValueError("perm_cls must be [n_perm, S]: one class per column in every row")
-            n_perm = int(perm_a.shape[0])
-        room = n_class if 1 <= n_class <= 65535 else 1    # (the library refuses the others before it writes)
-        n_lab = 1 + (n_perm if n_perm <= ANOSIM_MAX_PERM else 0)
+        cls_a, n_class, perm_a, n_perm, room, n_lab = _labellings_arg(cls, n_class, perm_cls, sel.n_samp)
         n_pairs = np.zeros(2, dtype=np.int64)
         w2 = np.zeros(n_lab, dtype=np.int64)
         nw = np.zeros(n_lab, dtype=np.int64)
@@ -1047,20 +1055,7 @@ class Context:
         statistic.  The argument checks are the library's: a label out of range, more than 65 535 classes, more than
         PERMANOVA_MAX_CELLS cells or a bad perspective raises IciktError."""
         sel = _SelectCall(self, self._entry("permanova", X, flags))
-        n_samp = sel.n_samp
-        cls_a = _class_arg(cls, n_samp)
-        if cls_a is None:
-            n_class = 1
-        n_class = int(n_class)
-        if perm_cls is None:
-            perm_a, n_perm = None, 0
-        else:
-            perm_a = np.ascontiguousarray(perm_cls, dtype=np.int32)
-            if perm_a.ndim != 2 or perm_a.shape[1] != n_samp:
-                raise ValueError("perm_cls must be [n_perm, S]: one class per column in every row")
-            n_perm = int(perm_a.shape[0])
-        room = n_class if 1 <= n_class <= 65535 else 1    # (the library refuses the others before it writes)
-        n_lab = 1 + (n_perm if n_perm <= ANOSIM_MAX_PERM else 0)
+        cls_a, n_class, perm_a, n_perm, room, n_lab = _labellings_arg(cls, n_class, perm_cls, sel.n_samp)
         if n_lab * room > PERMANOVA_MAX_CELLS:
             n_lab = 1
         n_pairs = np.zeros(2, dtype=np.int64)

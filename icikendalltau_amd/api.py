@@ -2050,6 +2050,33 @@ def anosim_permutations(codes, permutations=999, seed=None, strata=None):
     return out
 
 
+def _labellings_input(data_matrix, colnames, sample_classes, permutations, seed, strata):
+    """The start of the two permutation tests: the matrix and its names, the required classes as levels and codes, at
+    least two samples, the labellings to compare with.  Returns (data_matrix, names, n_sample, levels, cls, perms)."""
+    data_matrix, names, n_sample = _select_input(data_matrix, colnames)
+    if sample_classes is None:
+        raise ValueError("`sample_classes` must give one class per column")
+    levels, cls = _class_levels(sample_classes, n_sample, "all")
+    _need_pairs(n_sample)
+    return data_matrix, names, n_sample, levels, cls, anosim_permutations(cls, permutations, seed, strata)
+
+
+def _as_float(f):
+    """A Fraction or an int as a double, None as NA (Fraction -> float rounds correctly, once)."""
+    return _na_real() if f is None else float(f)
+
+
+def _labellings_result(head, counts, before_perms, perm_stats, after_perms, levels, own, names, max_taumax, t_diff):
+    """The result dict of the two permutation tests, in its order; counts: (n_perm, n_ge, n_undefined); perm_stats: the
+    permutations' statistics as fractions (None: not asked for), between what the test puts before and after them."""
+    n_perm, n_ge, n_undef = counts
+    res = dict(head, n_permutations=n_perm, n_ge=int(n_ge), n_undefined=int(n_undef), **before_perms)
+    if perm_stats is not None:
+        res["perm_statistic"] = np.array([_as_float(f) for f in perm_stats], dtype=np.float64)
+    res.update(after_perms, class_levels=list(levels), **own, sample_id=list(names), max_taumax=max_taumax, run_time=t_diff)
+    return res
+
+
 def _anosim_numpy(raw, cls, n_class, perms):
     """The sums of icikt_anosim_f64 from a full S x S raw matrix, for engines without an anosim method (the CPU tests'
     checker engines): (n_pairs [2], w2, nw [1 + n_perm], n_ge, n_undefined, class_w2, class_nw [n_class])."""
@@ -2111,12 +2138,8 @@ def ici_kendalltau_anosim(data_matrix, sample_classes, permutations=999, seed=No
     without one), ``within_mean_rank``, ``between_mean_rank``, ``sums`` (the integers: ``w2``, ``nw`` [1 + n_perm],
     index 0 the observed labelling, ``class_w2``, ``class_nw``), ``sample_id``, ``max_taumax`` and ``run_time``.
     """
-    data_matrix, names, n_sample = _select_input(data_matrix, colnames)
-    if sample_classes is None:
-        raise ValueError("`sample_classes` must give one class per column")
-    levels, cls = _class_levels(sample_classes, n_sample, "all")
-    _need_pairs(n_sample)
-    perms = anosim_permutations(cls, permutations, seed, strata)
+    data_matrix, names, n_sample, levels, cls, perms = _labellings_input(data_matrix, colnames, sample_classes,
+                                                                         permutations, seed, strata)
     eng = engine or _default_engine()
     if hasattr(eng, "anosim"):
         (n_pairs, w2, nw, n_ge, n_undef, class_w2, class_nw, max_taumax), t_diff = _on_device(
@@ -2127,25 +2150,18 @@ def ici_kendalltau_anosim(data_matrix, sample_classes, permutations=999, seed=No
                                                continuity)
         n_pairs, w2, nw, n_ge, n_undef, class_w2, class_nw = _anosim_numpy(mats5[1], cls, len(levels), perms)
     M, n_perm = int(n_pairs[0]), int(perms.shape[0])
-    na = _na_real()
-    as_float = lambda f: na if f is None else float(f)   # noqa: E731  (Fraction -> float rounds correctly, once)
     obs = anosim_statistic(M, w2[0], nw[0])
     W2, nW = int(w2[0]), int(nw[0])
-    res = {"statistic": as_float(obs),
-           "pvalue": na if obs is None else float(Fraction(1 + int(n_ge), 1 + n_perm)),
-           "n_permutations": n_perm, "n_ge": int(n_ge), "n_undefined": int(n_undef), "n_valid": M,
-           "n_na": int(n_pairs[1])}
-    if return_perms:
-        res["perm_statistic"] = np.array([as_float(anosim_statistic(M, a, b)) for a, b in zip(w2[1:], nw[1:])],
-                                         dtype=np.float64)
-    res.update(class_levels=list(levels),
-               class_mean_rank=np.array([as_float(Fraction(int(a), 2 * int(b)) if b else None)
-                                         for a, b in zip(class_w2, class_nw)], dtype=np.float64),
-               within_mean_rank=as_float(Fraction(W2, 2 * nW) if nW else None),
-               between_mean_rank=as_float(Fraction(M * (M + 1) - W2, 2 * (M - nW)) if M > nW else None),
-               sums={"w2": w2, "nw": nw, "class_w2": class_w2, "class_nw": class_nw},
-               sample_id=list(names), max_taumax=max_taumax, run_time=t_diff)
-    return res
+    return _labellings_result(
+        {"statistic": _as_float(obs), "pvalue": _na_real() if obs is None else float(Fraction(1 + int(n_ge), 1 + n_perm))},
+        (n_perm, n_ge, n_undef), {"n_valid": M, "n_na": int(n_pairs[1])},
+        [anosim_statistic(M, a, b) for a, b in zip(w2[1:], nw[1:])] if return_perms else None, {}, levels,
+        {"class_mean_rank": np.array([_as_float(Fraction(int(a), 2 * int(b)) if b else None)
+                                      for a, b in zip(class_w2, class_nw)], dtype=np.float64),
+         "within_mean_rank": _as_float(Fraction(W2, 2 * nW) if nW else None),
+         "between_mean_rank": _as_float(Fraction(M * (M + 1) - W2, 2 * (M - nW)) if M > nW else None),
+         "sums": {"w2": w2, "nw": nw, "class_w2": class_w2, "class_nw": class_nw}},
+        names, max_taumax, t_diff)
 
 
 # --------------------------------------------------------------------------------------------------
@@ -2289,12 +2305,8 @@ def ici_kendalltau_permanova(data_matrix, sample_classes, permutations=999, seed
     within-class sum divided by the class size, NA for a class without a sample); ``sums`` (the integers: ``q_total`` and
     ``class_q`` [1 + n_perm, n_class], row 0 the observed labelling); ``sample_id``, ``max_taumax`` and ``run_time``.
     """
-    data_matrix, names, n_sample = _select_input(data_matrix, colnames)
-    if sample_classes is None:
-        raise ValueError("`sample_classes` must give one class per column")
-    levels, cls = _class_levels(sample_classes, n_sample, "all")
-    _need_pairs(n_sample)
-    perms = anosim_permutations(cls, permutations, seed, strata)
+    data_matrix, names, n_sample, levels, cls, perms = _labellings_input(data_matrix, colnames, sample_classes,
+                                                                         permutations, seed, strata)
     n_class, n_perm = len(levels), int(perms.shape[0])
     if (1 + n_perm) * n_class > _lib.PERMANOVA_MAX_CELLS:
         raise ValueError(f"(1 + permutations) x classes must be at most {_lib.PERMANOVA_MAX_CELLS}")
@@ -2310,8 +2322,6 @@ def ici_kendalltau_permanova(data_matrix, sample_classes, permutations=999, seed
                                                continuity)
         n_pairs, Q, class_q = _permanova_numpy(mats5[1], cls, n_class, perms)
     S, n_na = n_sample, int(n_pairs[1])
-    na = _na_real()
-    as_float = lambda f: na if f is None else float(f)   # noqa: E731  (Fraction -> float rounds correctly, once)
     sizes = np.bincount(cls, minlength=n_class).astype(np.int64)
     if n_na > 0:
         warnings.warn(f"PERMANOVA needs every pair and {n_na} of them have no raw value: every statistic is NA.  "
@@ -2323,19 +2333,16 @@ def ici_kendalltau_permanova(data_matrix, sample_classes, permutations=999, seed
         class_ss = _na_filled(n_class)
     else:
         obs, Fs, n_ge, n_undef = _permanova_compare(S, Q, class_q, np.vstack([cls[None, :], perms]), n_class)
-        class_ss = np.array([as_float(Fraction(int(a), int(n) << PERMANOVA_FRAC_BITS) if n else None)
+        class_ss = np.array([_as_float(Fraction(int(a), int(n) << PERMANOVA_FRAC_BITS) if n else None)
                              for a, n in zip(class_q[0], sizes)], dtype=np.float64)
-    res = {"statistic": as_float(obs.F), "r2": as_float(obs.r2),
-           "pvalue": na if obs.F is None else float(Fraction(1 + n_ge, 1 + n_perm)),
-           "ss_total": as_float(obs.ss_total), "ss_within": as_float(obs.ss_within), "ss_among": as_float(obs.ss_among),
-           "df_among": int(obs.df_among), "df_within": int(obs.df_within),
-           "n_permutations": n_perm, "n_ge": int(n_ge), "n_undefined": int(n_undef)}
-    if return_perms:
-        res["perm_statistic"] = np.array([as_float(f) for f in Fs], dtype=np.float64)
-    res.update(n_valid=int(n_pairs[0]), n_na=n_na, class_levels=list(levels), class_size=sizes, class_ss=class_ss,
-               sums={"q_total": int(Q), "class_q": class_q},
-               sample_id=list(names), max_taumax=max_taumax, run_time=t_diff)
-    return res
+    return _labellings_result(
+        {"statistic": _as_float(obs.F), "r2": _as_float(obs.r2),
+         "pvalue": _na_real() if obs.F is None else float(Fraction(1 + n_ge, 1 + n_perm)),
+         "ss_total": _as_float(obs.ss_total), "ss_within": _as_float(obs.ss_within), "ss_among": _as_float(obs.ss_among),
+         "df_among": int(obs.df_among), "df_within": int(obs.df_within)},
+        (n_perm, n_ge, n_undef), {}, Fs if return_perms else None, {"n_valid": int(n_pairs[0]), "n_na": n_na}, levels,
+        {"class_size": sizes, "class_ss": class_ss, "sums": {"q_total": int(Q), "class_q": class_q}},
+        names, max_taumax, t_diff)
 
 
 # --------------------------------------------------------------------------------------------------

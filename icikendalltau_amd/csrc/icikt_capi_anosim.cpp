@@ -67,18 +67,10 @@ int anosim_src(icikt_ctx* c, const MatrixSrc& X, int64_t n_feat, int64_t n_samp,
   icikt::host::SelectCall call{c, "anosim", X, n_feat, n_samp, A.shared, {}};
   int rc = icikt::host::select_check_shape(call, "the pairs of the triangle are indexed in 32 bits, a label is a halfword");
   if (rc) return rc;
-  if (A.cls && A.n_class < 1) return fail(c, ICIKT_E_INVALID, "anosim: n_class must be at least 1");
-  if (A.cls && A.n_class > ICIKT_ANOSIM_MAX_CLASSES)
-    return fail(c, ICIKT_E_INVALID, "anosim: n_class exceeds 65535 (a label travels as a halfword)");
+  rc = icikt::host::select_check_labellings(call, A.cls, A.n_class, ICIKT_ANOSIM_MAX_CLASSES, "a label travels as a halfword",
+                                            A.perm_cls, A.n_perm);
+  if (rc) return rc;
   const int C = A.cls ? A.n_class : 1;   // a null cls: one class, n_class ignored
-  if (A.cls)
-    for (int64_t s = 0; s < n_samp; ++s)
-      if (A.cls[s] < 0 || A.cls[s] >= A.n_class)
-        return fail(c, ICIKT_E_INVALID, "anosim: cls[" + std::to_string(s) + "] = " + std::to_string(A.cls[s]) +
-                                            " is outside 0 .. n_class - 1 (n_class = " + std::to_string(A.n_class) + ")");
-  if (A.n_perm < 0) return fail(c, ICIKT_E_INVALID, "anosim: n_perm must not be negative");
-  if (A.n_perm > ICIKT_ANOSIM_MAX_PERM) return fail(c, ICIKT_E_INVALID, "anosim: n_perm exceeds ICIKT_ANOSIM_MAX_PERM (1000000)");
-  if (A.n_perm > 0 && !A.perm_cls) return fail(c, ICIKT_E_INVALID, "anosim: null perm_cls with n_perm > 0");
   if (!A.n_pairs) return fail(c, ICIKT_E_INVALID, "anosim: null output (n_pairs)");
   if (!A.w2) return fail(c, ICIKT_E_INVALID, "anosim: null output (w2)");
   if (!A.nw) return fail(c, ICIKT_E_INVALID, "anosim: null output (nw)");
@@ -92,7 +84,6 @@ int anosim_src(icikt_ctx* c, const MatrixSrc& X, int64_t n_feat, int64_t n_samp,
   const int64_t S = n_samp;
   const int64_t P = S > 1 ? S * (S - 1) / 2 : 0;
   const int64_t n_lab = 1 + A.n_perm;     // the observed labelling, then the permutations
-  constexpr int PB = icikt::ANO_PB;
   int64_t M = 0;
   std::vector<int64_t> w2, nw, cw2, cnw;  // per labelling; per class.  The outputs are written once nothing can fail any more
   try {
@@ -128,13 +119,10 @@ int anosim_src(icikt_ctx* c, const MatrixSrc& X, int64_t n_feat, int64_t n_samp,
   PairBlocks blocks = PairBlocks::rows(S, budget);
   const long long tile = icikt::padj_tile(P, c->plan_ov.padjtile > 0 ? c->plan_ov.padjtile : 0);
   const int strip = c->plan_ov.anostrip > 0 ? c->plan_ov.anostrip : icikt::ANO_STRIP_DEFAULT;
-  // labellings per upload: the plan key, else what ANO_BATCH_BYTES of halfwords hold, in whole groups of PB
-  int64_t batch = c->plan_ov.anoperms > 0
-                      ? (int64_t)c->plan_ov.anoperms
-                      : std::max<int64_t>(PB, icikt::ANO_BATCH_BYTES / (2 * S) / PB * PB);
-  batch = std::min<int64_t>(std::min<int64_t>(batch, icikt::ANO_PERMS_MAX), n_lab);
-  const int64_t groups_max = (batch + PB - 1) / PB;
-  const size_t lab_words = (size_t)groups_max * (size_t)S * PB;
+  icikt::host::Labellings labs;      // a labelling costs an upload its labels: 2 S bytes
+  rc = icikt::host::select_labellings_begin(call, A.cls, A.n_class, A.perm_cls, A.n_perm, 2 * S, &labs);
+  if (rc) return rc;
+  const size_t sums = (size_t)labs.plan.groups_max * icikt::ANO_PB;   // a batch's sums, in whole groups
 
   auto& ab = c->ano;
   auto& ws = c->sel;   // kept, plane_a, plane_b: the keys, their sorted copy, the ranks; the sort's scratch is select_sort's
@@ -145,22 +133,14 @@ int anosim_src(icikt_ctx* c, const MatrixSrc& X, int64_t n_feat, int64_t n_samp,
   HIPCHK(c, ws.dhist.reserve(8 * 256));
   HIPCHK(c, ab.class_sums.reserve(2 * (size_t)C));
   HIPCHK(c, ab.cls.reserve((size_t)S));
-  HIPCHK(c, ab.labels.reserve(lab_words));
-  HIPCHK(c, ab.w2.reserve((size_t)groups_max * PB));
-  HIPCHK(c, ab.nw.reserve((size_t)groups_max * PB));
+  HIPCHK(c, ab.w2.reserve(sums));
+  HIPCHK(c, ab.nw.reserve(sums));
   const uint32_t flags = A.shared.flags;
 
-  std::vector<uint16_t> stage;      // one batch as the device takes it: [groups][S][PB]
-  std::vector<int32_t> obs_cls;     // the observed labelling (a null cls: zeros)
-  std::vector<int64_t> size_of;     // a labelling's class sizes while it is staged
   std::vector<unsigned long long> h_w2, h_nw, h_class;
   try {
-    stage.assign(lab_words, 0);
-    obs_cls.assign((size_t)S, 0);
-    if (A.cls) std::copy(A.cls, A.cls + S, obs_cls.begin());
-    size_of.assign((size_t)C, 0);
-    h_w2.resize((size_t)groups_max * PB);
-    h_nw.resize((size_t)groups_max * PB);
+    h_w2.resize(sums);
+    h_nw.resize(sums);
     h_class.resize(2 * (size_t)C);
   } catch (const std::bad_alloc&) {
     return fail(c, ICIKT_E_NOMEM, "anosim: host allocation failed");
@@ -171,7 +151,7 @@ int anosim_src(icikt_ctx* c, const MatrixSrc& X, int64_t n_feat, int64_t n_samp,
     HIPCHK(c, hipMemsetAsync(ws.total.p, 0, sizeof(unsigned long long), c->stream));
     HIPCHK(c, hipMemsetAsync(ws.dhist.p, 0, 8 * 256 * sizeof(unsigned long long), c->stream));
     HIPCHK(c, hipMemsetAsync(ab.class_sums.p, 0, 2 * (size_t)C * sizeof(unsigned long long), c->stream));
-    return icikt::host::upload_sync(c, ab.cls.p, obs_cls.data(), (size_t)S * sizeof(int32_t));
+    return icikt::host::upload_sync(c, ab.cls.p, labs.obs.data(), (size_t)S * sizeof(int32_t));
   };
   // a block's raw values as sortable keys, before the next block overwrites them
   steps.fold = [&](const icikt::host::PairBlock& b) -> int { return icikt::host::select_keep_raw(c, b); };
@@ -206,68 +186,29 @@ int anosim_src(icikt_ctx* c, const MatrixSrc& X, int64_t n_feat, int64_t n_samp,
       HIPCHK(c, hipMemcpyAsync(h_class.data(), ab.class_sums.p, 2 * (size_t)C * sizeof(unsigned long long),
                                hipMemcpyDeviceToHost, c->stream));
     }
-    // ---- the labellings, batch by batch: staged and checked on the host while the batch before runs ----
-    int64_t in_flight = -1, in_flight_n = 0;   // first labelling and count of the batch whose kernel has been launched
-    auto collect = [&]() -> int {
-      if (in_flight < 0) return ICIKT_SUCCESS;
-      if (device) {
-        const size_t words = (size_t)((in_flight_n + PB - 1) / PB) * PB;
-        HIPCHK(c, hipMemcpyAsync(h_w2.data(), ab.w2.p, words * sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream));
-        if (count_nw)
-          HIPCHK(c, hipMemcpyAsync(h_nw.data(), ab.nw.p, words * sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream));
-        HIPCHK(c, hipStreamSynchronize(c->stream));
-        for (int64_t l = 0; l < in_flight_n; ++l) {
-          w2[(size_t)(in_flight + l)] = (int64_t)h_w2[(size_t)l];
-          if (count_nw) nw[(size_t)(in_flight + l)] = (int64_t)h_nw[(size_t)l];
-        }
-      }
-      in_flight = -1;
+    // ---- the labellings (select_labellings): W2 of every one, and nW where the class sizes do not give it ----
+    icikt::host::LabellingSteps per_batch;
+    per_batch.launch = [&](int64_t groups, int64_t) -> int {
+      const size_t words = (size_t)groups * icikt::ANO_PB;
+      HIPCHK(c, hipMemsetAsync(ab.w2.p, 0, words * sizeof(unsigned long long), c->stream));
+      HIPCHK(c, hipMemsetAsync(ab.nw.p, 0, words * sizeof(unsigned long long), c->stream));
+      HIPCHK(c, icikt::launch_anosim_perm(ranks, c->labels.p, (int)S, (int)groups, strip, count_nw ? 1 : 0, ab.w2.p, ab.nw.p,
+                                          c->stream));
       return ICIKT_SUCCESS;
     };
-    for (int64_t q0 = 0; q0 < n_lab; q0 += batch) {
-      const int64_t nb = std::min<int64_t>(batch, n_lab - q0);
-      const int64_t groups = (nb + PB - 1) / PB;
-      // (collect() reads the sums of the batch before, not the labels: the stage may be refilled while its kernel runs,
-      // the upload below is what waits for it)
+    per_batch.collect = [&](int64_t q0, int64_t nb) -> int {
+      const size_t words = (size_t)((nb + icikt::ANO_PB - 1) / icikt::ANO_PB) * icikt::ANO_PB;
+      HIPCHK(c, hipMemcpyAsync(h_w2.data(), ab.w2.p, words * sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream));
+      if (count_nw)
+        HIPCHK(c, hipMemcpyAsync(h_nw.data(), ab.nw.p, words * sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream));
+      HIPCHK(c, hipStreamSynchronize(c->stream));
       for (int64_t l = 0; l < nb; ++l) {
-        const int64_t q = q0 + l;
-        const int32_t* lab = q == 0 ? obs_cls.data() : A.perm_cls + (size_t)(q - 1) * (size_t)S;
-        uint16_t* out = stage.data() + (size_t)(l / PB) * (size_t)S * PB + (size_t)(l % PB);
-        int64_t within = 0;              // pairs of samples that share a class: the sum over the classes of C(size, 2)
-        for (int64_t s = 0; s < S; ++s) {
-          const int32_t v = lab[s];
-          if (v < 0 || v >= C) {
-            for (int64_t t = 0; t < s; ++t) size_of[(size_t)lab[t]] = 0;
-            return fail(c, ICIKT_E_INVALID, "anosim: perm_cls[" + std::to_string(q - 1) + "][" + std::to_string(s) + "] = " +
-                                                std::to_string(v) + " is outside 0 .. n_class - 1 (n_class = " +
-                                                std::to_string(C) + ")");
-          }
-          out[(size_t)s * PB] = (uint16_t)v;
-          within += size_of[(size_t)v]++;
-        }
-        for (int64_t s = 0; s < S; ++s) size_of[(size_t)lab[s]] = 0;
-        if (device && !count_nw) nw[(size_t)q] = within;
+        w2[(size_t)(q0 + l)] = (int64_t)h_w2[(size_t)l];
+        if (count_nw) nw[(size_t)(q0 + l)] = (int64_t)h_nw[(size_t)l];
       }
-      for (int64_t l = nb; l < groups * PB; ++l) {   // the last group's unused slots: labelling 0s, their sums ignored
-        uint16_t* out = stage.data() + (size_t)(l / PB) * (size_t)S * PB + (size_t)(l % PB);
-        for (int64_t s = 0; s < S; ++s) out[(size_t)s * PB] = 0;
-      }
-      r = collect();
-      if (r) return r;
-      if (!device) continue;
-      r = icikt::host::upload_sync(c, ab.labels.p, stage.data(), (size_t)groups * (size_t)S * PB * sizeof(uint16_t));
-      if (!r) r = icikt::host::timer_begin(c, ICIKT_K_EPILOGUE, flags);
-      if (r) return r;
-      HIPCHK(c, hipMemsetAsync(ab.w2.p, 0, (size_t)groups * PB * sizeof(unsigned long long), c->stream));
-      HIPCHK(c, hipMemsetAsync(ab.nw.p, 0, (size_t)groups * PB * sizeof(unsigned long long), c->stream));
-      HIPCHK(c, icikt::launch_anosim_perm(ranks, ab.labels.p, (int)S, (int)groups, strip, count_nw ? 1 : 0, ab.w2.p, ab.nw.p,
-                                          c->stream));
-      r = icikt::host::timer_end(c, ICIKT_K_EPILOGUE, flags);
-      if (r) return r;
-      in_flight = q0;
-      in_flight_n = nb;
-    }
-    r = collect();
+      return ICIKT_SUCCESS;
+    };
+    r = icikt::host::select_labellings(call, labs, device, device && !count_nw ? nw.data() : nullptr, per_batch);
     if (r) return r;
     HIPCHK(c, hipStreamSynchronize(c->stream));   // (the per-class sums, when no batch ran behind them)
     if (device)

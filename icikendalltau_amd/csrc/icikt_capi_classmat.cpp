@@ -37,15 +37,9 @@ int classmat_src(icikt_ctx* c, const MatrixSrc& X, int64_t n_feat, int64_t n_sam
   icikt::host::SelectCall call{c, "class_matrix", X, n_feat, n_samp, A.shared, {}};
   int rc = icikt::host::select_check_shape(call, "the pairs of the triangle are indexed in 32 bits");
   if (rc) return rc;
-  if (A.cls && A.n_class < 1) return fail(c, ICIKT_E_INVALID, "class_matrix: n_class must be at least 1");
-  if (A.cls && A.n_class > icikt::CLASS_MATRIX_MAX_CLASSES)
-    return fail(c, ICIKT_E_INVALID, "class_matrix: n_class exceeds 65535 (the classes are the second dimension of the "
-                                    "select kernel's grid)");
-  if (A.cls)
-    for (int64_t s = 0; s < n_samp; ++s)
-      if (A.cls[s] < 0 || A.cls[s] >= A.n_class)
-        return fail(c, ICIKT_E_INVALID, "class_matrix: cls[" + std::to_string(s) + "] = " + std::to_string(A.cls[s]) +
-                                            " is outside 0 .. n_class - 1 (n_class = " + std::to_string(A.n_class) + ")");
+  rc = icikt::host::select_check_classes(call, A.cls, A.n_class, icikt::CLASS_MATRIX_MAX_CLASSES,
+                                         "the classes are the second dimension of the select kernel's grid");
+  if (rc) return rc;
   if (n_samp > 0 && !A.med2) return fail(c, ICIKT_E_INVALID, "class_matrix: null output (med2)");
   rc = icikt::host::select_check_args(call);
   if (rc || n_samp == 0) return rc;

@@ -56,10 +56,7 @@ int cross_check_outputs(icikt_ctx* c, const std::string& who, const CrossArgs& A
     if (A.n_class < 1 || A.n_class > icikt::CLASS_MATRIX_MAX_CLASSES)
       return fail(c, ICIKT_E_INVALID, who + ": n_class must be in 1 .. 65535 (the classes are the second dimension of the "
                                             "class kernel's grid)");
-    for (int64_t r = 0; r < Sr; ++r)
-      if (A.ref_cls[r] < 0 || A.ref_cls[r] >= A.n_class)
-        return fail(c, ICIKT_E_INVALID, who + ": ref_cls[" + std::to_string(r) + "] = " + std::to_string(A.ref_cls[r]) +
-                                            " is outside 0 .. n_class - 1 (n_class = " + std::to_string(A.n_class) + ")");
+    return icikt::host::check_labels(c, who.c_str(), "ref_cls", A.ref_cls, Sr, A.n_class);
   }
   return ICIKT_SUCCESS;
 }

@@ -37,12 +37,8 @@ int medians_src(icikt_ctx* c, const MatrixSrc& X, int64_t n_feat, int64_t n_samp
   icikt::host::SelectCall call{c, "class_medians", X, n_feat, n_samp, A.shared, {}};
   int rc = icikt::host::select_check_shape(call, "a class's pairs are indexed from 32-bit positions");
   if (rc) return rc;
-  if (A.cls && A.n_class < 1) return fail(c, ICIKT_E_INVALID, "class_medians: n_class must be at least 1");
-  if (A.cls)
-    for (int64_t s = 0; s < n_samp; ++s)
-      if (A.cls[s] < 0 || A.cls[s] >= A.n_class)
-        return fail(c, ICIKT_E_INVALID, "class_medians: cls[" + std::to_string(s) + "] = " + std::to_string(A.cls[s]) +
-                                            " is outside 0 .. n_class - 1 (n_class = " + std::to_string(A.n_class) + ")");
+  rc = icikt::host::select_check_classes(call, A.cls, A.n_class);
+  if (rc) return rc;
   if (n_samp > 0 && !A.med2) return fail(c, ICIKT_E_INVALID, "class_medians: null output (med2)");
   rc = icikt::host::select_check_args(call);
   if (rc || n_samp == 0) return rc;

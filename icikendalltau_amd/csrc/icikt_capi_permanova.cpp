@@ -58,21 +58,10 @@ int permanova_src(icikt_ctx* c, const MatrixSrc& X, int64_t n_feat, int64_t n_sa
   icikt::host::SelectCall call{c, "permanova", X, n_feat, n_samp, A.shared, {}};
   int rc = icikt::host::select_check_shape(call, "the pairs of the triangle are indexed in 32 bits, a label is a halfword");
   if (rc) return rc;
-  if (A.cls && A.n_class < 1) return fail(c, ICIKT_E_INVALID, "permanova: n_class must be at least 1");
-  if (A.cls && A.n_class > ICIKT_ANOSIM_MAX_CLASSES)
-    return fail(c, ICIKT_E_INVALID, "permanova: n_class exceeds 65535 (a label travels as a halfword)");
+  rc = icikt::host::select_check_labellings(call, A.cls, A.n_class, ICIKT_ANOSIM_MAX_CLASSES, "a label travels as a halfword",
+                                            A.perm_cls, A.n_perm, ICIKT_PERMANOVA_MAX_CELLS);
+  if (rc) return rc;
   const int C = A.cls ? A.n_class : 1;   // a null cls: one class, n_class ignored
-  if (A.cls)
-    for (int64_t s = 0; s < n_samp; ++s)
-      if (A.cls[s] < 0 || A.cls[s] >= A.n_class)
-        return fail(c, ICIKT_E_INVALID, "permanova: cls[" + std::to_string(s) + "] = " + std::to_string(A.cls[s]) +
-                                            " is outside 0 .. n_class - 1 (n_class = " + std::to_string(A.n_class) + ")");
-  if (A.n_perm < 0) return fail(c, ICIKT_E_INVALID, "permanova: n_perm must not be negative");
-  if (A.n_perm > ICIKT_ANOSIM_MAX_PERM)
-    return fail(c, ICIKT_E_INVALID, "permanova: n_perm exceeds ICIKT_ANOSIM_MAX_PERM (1000000)");
-  if ((1 + A.n_perm) * (int64_t)C > ICIKT_PERMANOVA_MAX_CELLS)
-    return fail(c, ICIKT_E_INVALID, "permanova: (1 + n_perm) n_class exceeds ICIKT_PERMANOVA_MAX_CELLS (67108864)");
-  if (A.n_perm > 0 && !A.perm_cls) return fail(c, ICIKT_E_INVALID, "permanova: null perm_cls with n_perm > 0");
   if (!A.n_pairs) return fail(c, ICIKT_E_INVALID, "permanova: null output (n_pairs)");
   if (!A.q_total) return fail(c, ICIKT_E_INVALID, "permanova: null output (q_total)");
   if (!A.bins_lo) return fail(c, ICIKT_E_INVALID, "permanova: null output (bins_lo)");
@@ -83,7 +72,6 @@ int permanova_src(icikt_ctx* c, const MatrixSrc& X, int64_t n_feat, int64_t n_sa
   const int64_t S = n_samp;
   const int64_t P = S > 1 ? S * (S - 1) / 2 : 0;
   const int64_t n_lab = 1 + A.n_perm;     // the observed labelling, then the permutations
-  constexpr int PB = icikt::ANO_PB;
   unsigned long long h_tot[icikt::PMV_TOTALS] = {0ull, 0ull, 0ull};
   std::vector<unsigned long long> blo, bhi;   // [n_lab][C].  The outputs are written once nothing can fail any more
   try {
@@ -109,36 +97,21 @@ int permanova_src(icikt_ctx* c, const MatrixSrc& X, int64_t n_feat, int64_t n_sa
 
   PairBlocks blocks = PairBlocks::rows(S, budget);
   const int strip = c->plan_ov.anostrip > 0 ? c->plan_ov.anostrip : icikt::ANO_STRIP_DEFAULT;
-  // labellings per upload: the plan key, else what ANO_BATCH_BYTES hold of the largest of a labelling's labels (2 S
-  // bytes), column sums (16 S) and bins (16 C), in whole groups of PB
-  const int64_t per_lab = 16 * std::max<int64_t>(S, C);
-  int64_t batch = c->plan_ov.anoperms > 0 ? (int64_t)c->plan_ov.anoperms
-                                          : std::max<int64_t>(PB, icikt::ANO_BATCH_BYTES / per_lab / PB * PB);
-  batch = std::min<int64_t>(std::min<int64_t>(batch, icikt::ANO_PERMS_MAX), n_lab);
-  const int64_t groups_max = (batch + PB - 1) / PB;
-  const size_t lab_words = (size_t)groups_max * (size_t)S * PB;
+  // a labelling costs an upload the largest of its labels (2 S bytes), column sums (16 S) and bins (16 C)
+  icikt::host::Labellings labs;
+  rc = icikt::host::select_labellings_begin(call, A.cls, A.n_class, A.perm_cls, A.n_perm, 16 * std::max<int64_t>(S, C), &labs);
+  if (rc) return rc;
 
   auto& pb = c->pmv;
   auto& ws = c->sel;   // kept, plane_a: the keys, their fixed-point values
   HIPCHK(c, ws.kept.reserve((size_t)std::max<int64_t>(P, 1)));
   HIPCHK(c, ws.plane_a.reserve((size_t)std::max<int64_t>(P, 1)));
   HIPCHK(c, pb.totals.reserve(icikt::PMV_TOTALS));
-  HIPCHK(c, c->ano.labels.reserve(lab_words));
-  HIPCHK(c, pb.colsum_lo.reserve(lab_words));
-  HIPCHK(c, pb.colsum_hi.reserve(lab_words));
-  HIPCHK(c, pb.bins_lo.reserve((size_t)batch * (size_t)C));
-  HIPCHK(c, pb.bins_hi.reserve((size_t)batch * (size_t)C));
+  HIPCHK(c, pb.colsum_lo.reserve(labs.plan.stage_words));
+  HIPCHK(c, pb.colsum_hi.reserve(labs.plan.stage_words));
+  HIPCHK(c, pb.bins_lo.reserve((size_t)labs.plan.batch * (size_t)C));
+  HIPCHK(c, pb.bins_hi.reserve((size_t)labs.plan.batch * (size_t)C));
   const uint32_t flags = A.shared.flags;
-
-  std::vector<uint16_t> stage;      // one batch as the device takes it: [groups][S][PB]
-  std::vector<int32_t> obs_cls;     // the observed labelling (a null cls: zeros)
-  try {
-    stage.assign(lab_words, 0);
-    obs_cls.assign((size_t)S, 0);
-    if (A.cls) std::copy(A.cls, A.cls + S, obs_cls.begin());
-  } catch (const std::bad_alloc&) {
-    return fail(c, ICIKT_E_NOMEM, "permanova: host allocation failed");
-  }
 
   icikt::host::SelectSteps steps;
   steps.start = [&]() -> int {
@@ -159,60 +132,28 @@ int permanova_src(icikt_ctx* c, const MatrixSrc& X, int64_t n_feat, int64_t n_sa
     HIPCHK(c, hipStreamSynchronize(c->stream));
     if (h_tot[icikt::PMV_T_NA] > (unsigned long long)P) return fail(c, ICIKT_E_STATE, "permanova: more NA pairs than pairs");
     const bool device = P > 0 && h_tot[icikt::PMV_T_NA] == 0ull;   // an NA pair: nothing is summed, the labels are still checked
-    // ---- the labellings, batch by batch: staged and checked on the host while the batch before runs ----
-    int64_t in_flight = -1, in_flight_n = 0;   // first labelling and count of the batch whose kernels have been launched
-    auto collect = [&]() -> int {
-      if (in_flight < 0) return ICIKT_SUCCESS;
-      const size_t at = (size_t)in_flight * (size_t)C, cells = (size_t)in_flight_n * (size_t)C;
-      HIPCHK(c, hipMemcpyAsync(blo.data() + at, pb.bins_lo.p, cells * sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream));
-      HIPCHK(c, hipMemcpyAsync(bhi.data() + at, pb.bins_hi.p, cells * sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream));
-      HIPCHK(c, hipStreamSynchronize(c->stream));
-      in_flight = -1;
-      return ICIKT_SUCCESS;
-    };
-    for (int64_t q0 = 0; q0 < n_lab; q0 += batch) {
-      const int64_t nb = std::min<int64_t>(batch, n_lab - q0);
-      const int64_t groups = (nb + PB - 1) / PB;
-      // (collect() reads the bins of the batch before, not the labels: the stage may be refilled while its kernels run,
-      // the upload below is what waits for them)
-      for (int64_t l = 0; l < nb; ++l) {
-        const int64_t q = q0 + l;
-        const int32_t* lab = q == 0 ? obs_cls.data() : A.perm_cls + (size_t)(q - 1) * (size_t)S;
-        uint16_t* out = stage.data() + (size_t)(l / PB) * (size_t)S * PB + (size_t)(l % PB);
-        for (int64_t s = 0; s < S; ++s) {
-          const int32_t v = lab[s];
-          if (v < 0 || v >= C)
-            return fail(c, ICIKT_E_INVALID, "permanova: perm_cls[" + std::to_string(q - 1) + "][" + std::to_string(s) +
-                                                "] = " + std::to_string(v) + " is outside 0 .. n_class - 1 (n_class = " +
-                                                std::to_string(C) + ")");
-          out[(size_t)s * PB] = (uint16_t)v;
-        }
-      }
-      for (int64_t l = nb; l < groups * PB; ++l) {   // the last group's unused slots: labelling 0s, their sums ignored
-        uint16_t* out = stage.data() + (size_t)(l / PB) * (size_t)S * PB + (size_t)(l % PB);
-        for (int64_t s = 0; s < S; ++s) out[(size_t)s * PB] = 0;
-      }
-      r = collect();
-      if (r) return r;
-      if (!device) continue;
-      const size_t words = (size_t)groups * (size_t)S * PB;
-      r = icikt::host::upload_sync(c, c->ano.labels.p, stage.data(), words * sizeof(uint16_t));
-      if (!r) r = icikt::host::timer_begin(c, ICIKT_K_EPILOGUE, flags);
-      if (r) return r;
+    // ---- the labellings (select_labellings): the bins of every one ----
+    icikt::host::LabellingSteps per_batch;
+    per_batch.launch = [&](int64_t groups, int64_t nb) -> int {
+      const size_t words = (size_t)groups * (size_t)S * icikt::ANO_PB;
       HIPCHK(c, hipMemsetAsync(pb.colsum_lo.p, 0, words * sizeof(unsigned long long), c->stream));
       HIPCHK(c, hipMemsetAsync(pb.colsum_hi.p, 0, words * sizeof(unsigned long long), c->stream));
       HIPCHK(c, hipMemsetAsync(pb.bins_lo.p, 0, (size_t)nb * (size_t)C * sizeof(unsigned long long), c->stream));
       HIPCHK(c, hipMemsetAsync(pb.bins_hi.p, 0, (size_t)nb * (size_t)C * sizeof(unsigned long long), c->stream));
-      HIPCHK(c, icikt::launch_pmv_perm(ws.plane_a.p, c->ano.labels.p, (int)S, (int)groups, strip, pb.colsum_lo.p,
-                                       pb.colsum_hi.p, c->stream));
-      HIPCHK(c, icikt::launch_pmv_classes(c->ano.labels.p, pb.colsum_lo.p, pb.colsum_hi.p, (int)S, C, (long long)nb,
-                                          pb.bins_lo.p, pb.bins_hi.p, c->stream));
-      r = icikt::host::timer_end(c, ICIKT_K_EPILOGUE, flags);
-      if (r) return r;
-      in_flight = q0;
-      in_flight_n = nb;
-    }
-    return collect();
+      HIPCHK(c, icikt::launch_pmv_perm(ws.plane_a.p, c->labels.p, (int)S, (int)groups, strip, pb.colsum_lo.p, pb.colsum_hi.p,
+                                       c->stream));
+      HIPCHK(c, icikt::launch_pmv_classes(c->labels.p, pb.colsum_lo.p, pb.colsum_hi.p, (int)S, C, (long long)nb, pb.bins_lo.p,
+                                          pb.bins_hi.p, c->stream));
+      return ICIKT_SUCCESS;
+    };
+    per_batch.collect = [&](int64_t q0, int64_t nb) -> int {
+      const size_t at = (size_t)q0 * (size_t)C, cells = (size_t)nb * (size_t)C;
+      HIPCHK(c, hipMemcpyAsync(blo.data() + at, pb.bins_lo.p, cells * sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream));
+      HIPCHK(c, hipMemcpyAsync(bhi.data() + at, pb.bins_hi.p, cells * sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream));
+      HIPCHK(c, hipStreamSynchronize(c->stream));
+      return ICIKT_SUCCESS;
+    };
+    return icikt::host::select_labellings(call, labs, device, nullptr, per_batch);
   };
   rc = icikt::host::select_run(call, blocks, steps);
   if (!rc) write_outputs();

@@ -134,12 +134,8 @@ int quantiles_src(icikt_ctx* c, const MatrixSrc& X, int64_t n_feat, int64_t n_sa
   icikt::host::SelectCall call{c, "quantiles", X, n_feat, n_samp, A.shared, {}};
   int rc = icikt::host::select_check_shape(call, "a pair's columns are recomputed from its index in the triangle");
   if (rc) return rc;
-  if (A.cls && A.n_class < 1) return fail(c, ICIKT_E_INVALID, "quantiles: n_class must be at least 1");
-  if (A.cls)
-    for (int64_t s = 0; s < n_samp; ++s)
-      if (A.cls[s] < 0 || A.cls[s] >= A.n_class)
-        return fail(c, ICIKT_E_INVALID, "quantiles: cls[" + std::to_string(s) + "] = " + std::to_string(A.cls[s]) +
-                                            " is outside 0 .. n_class - 1 (n_class = " + std::to_string(A.n_class) + ")");
+  rc = icikt::host::select_check_classes(call, A.cls, A.n_class);
+  if (rc) return rc;
   if (A.n_probs < 0 || A.n_probs > ICIKT_QUANTILE_MAX_PROBS)
     return fail(c, ICIKT_E_INVALID, "quantiles: n_probs must be in 0 .. ICIKT_QUANTILE_MAX_PROBS (32)");
   if (A.n_probs > 0 && !A.probs) return fail(c, ICIKT_E_INVALID, "quantiles: null probs");

@@ -1,9 +1,10 @@
-// icikt_capi_select.cpp -- the host side the nine selection entries share (icikt_topk_*, icikt_edges_*,
+// icikt_capi_select.cpp -- the host side the ten selection entries share (icikt_topk_*, icikt_edges_*,
 // icikt_class_medians_*, icikt_class_matrix_*, icikt_quantiles_*, icikt_padjust_*, icikt_mst_*, icikt_anosim_*,
-// icikt_hclust_*; declared in icikt_host.h) and icikt_cross_* runs its rectangle through: their common checks, the run of a call's blocks through the pair engine,
+// icikt_hclust_*, icikt_permanova_*; declared in icikt_host.h) and icikt_cross_* runs its rectangle through: their common checks, the run of a call's blocks through the pair engine,
 // and the steps several of them take over the one set of key planes (icikt_ctx::sel) -- the fold that keeps a block's
-// raw as keys, the radix sort, the download of d_red.  The driver allocates nothing of size S^2: each block's records
-// are folded by the entry's kernel before the next block overwrites them.
+// raw as keys, the radix sort, the download of d_red -- and, for the two permutation tests, the check of the class
+// labels and the batches of labellings (select_labellings).  The driver allocates nothing of size S^2: each block's
+// records are folded by the entry's kernel before the next block overwrites them.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -158,6 +159,92 @@ int select_sort(icikt_ctx* c, int64_t P, long long tile, const unsigned long lon
   *sorted = a;
   *spare = b;
   return ICIKT_SUCCESS;
+}
+
+static_assert(ICIKT_ANOSIM_MAX_PERM == 1000000 && ICIKT_PERMANOVA_MAX_CELLS == 67108864, "the messages below spell the header's limits out");
+
+static int bad_label(icikt_ctx* c, const char* who, const std::string& name, int64_t s, int32_t v, int64_t n_class) {
+  return fail(c, ICIKT_E_INVALID, std::string(who) + ": " + name + "[" + std::to_string(s) + "] = " + std::to_string(v) +
+                                      " is outside 0 .. n_class - 1 (n_class = " + std::to_string(n_class) + ")");
+}
+
+int check_labels(icikt_ctx* c, const char* who, const std::string& name, const int32_t* lab, int64_t n, int64_t n_class) {
+  const int64_t s = first_bad_label(lab, n, n_class);
+  return s < n ? bad_label(c, who, name, s, lab[s], n_class) : ICIKT_SUCCESS;
+}
+
+int select_check_classes(const SelectCall& s, const int32_t* cls, int n_class, int class_cap, const char* cap_why) {
+  if (!cls) return ICIKT_SUCCESS;
+  if (n_class < 1) return fail(s.c, ICIKT_E_INVALID, std::string(s.who) + ": n_class must be at least 1");
+  if (class_cap > 0 && n_class > class_cap)
+    return fail(s.c, ICIKT_E_INVALID, std::string(s.who) + ": n_class exceeds " + std::to_string(class_cap) + " (" + cap_why + ")");
+  return check_labels(s.c, s.who, "cls", cls, s.n_samp, n_class);
+}
+
+int select_check_labellings(const SelectCall& s, const int32_t* cls, int n_class, int class_cap, const char* cap_why,
+                            const int32_t* perm_cls, int64_t n_perm, int64_t cell_cap) {
+  const int rc = select_check_classes(s, cls, n_class, class_cap, cap_why);
+  if (rc) return rc;
+  const std::string who = s.who;
+  if (n_perm < 0) return fail(s.c, ICIKT_E_INVALID, who + ": n_perm must not be negative");
+  if (n_perm > ICIKT_ANOSIM_MAX_PERM) return fail(s.c, ICIKT_E_INVALID, who + ": n_perm exceeds ICIKT_ANOSIM_MAX_PERM (1000000)");
+  if (cell_cap > 0 && (1 + n_perm) * (int64_t)(cls ? n_class : 1) > cell_cap)
+    return fail(s.c, ICIKT_E_INVALID, who + ": (1 + n_perm) n_class exceeds ICIKT_PERMANOVA_MAX_CELLS (67108864)");
+  if (n_perm > 0 && !perm_cls) return fail(s.c, ICIKT_E_INVALID, who + ": null perm_cls with n_perm > 0");
+  return ICIKT_SUCCESS;
+}
+
+int select_labellings_begin(const SelectCall& s, const int32_t* cls, int n_class, const int32_t* perm_cls, int64_t n_perm,
+                            int64_t bytes_per_lab, Labellings* L) {
+  L->perm_cls = perm_cls;
+  L->S = s.n_samp;
+  L->n_class = cls ? n_class : 1;   // a null cls: one class, n_class ignored
+  L->n_lab = 1 + n_perm;            // the observed labelling, then the permutations
+  L->plan = label_batches(L->S, L->n_lab, bytes_per_lab, s.c->plan_ov.anoperms);
+  try {
+    L->stage.assign(L->plan.stage_words, 0);
+    L->obs.assign((size_t)L->S, 0);
+    if (cls) std::copy(cls, cls + L->S, L->obs.begin());
+    L->size_of.assign((size_t)L->n_class, 0);
+  } catch (const std::bad_alloc&) {
+    return fail(s.c, ICIKT_E_NOMEM, std::string(s.who) + ": host allocation failed");
+  }
+  HIPCHK(s.c, s.c->labels.reserve(L->plan.stage_words));
+  return ICIKT_SUCCESS;
+}
+
+int select_labellings(const SelectCall& s, Labellings& L, bool device, int64_t* within, const LabellingSteps& steps) {
+  icikt_ctx* const c = s.c;
+  constexpr int PB = ANO_PB;
+  int64_t in_flight = -1, in_flight_n = 0;   // first labelling and count of the batch whose kernels have been launched
+  auto collect = [&]() -> int {
+    if (in_flight < 0) return ICIKT_SUCCESS;
+    const int64_t q0 = in_flight;
+    in_flight = -1;
+    return steps.collect(q0, in_flight_n);
+  };
+  for (int64_t q0 = 0; q0 < L.n_lab; q0 += L.plan.batch) {
+    const int64_t nb = std::min<int64_t>(L.plan.batch, L.n_lab - q0);
+    const int64_t groups = (nb + PB - 1) / PB;
+    // (a collect reads the sums of the batch before, not the labels: the stage may be refilled while its kernels run,
+    // the upload below is what waits for them)
+    const BadLabel bad = stage_labellings(L.obs.data(), L.perm_cls, L.S, L.n_class, q0, nb, L.stage.data(),
+                                          within ? within + q0 : nullptr, L.size_of.data());
+    if (bad.q >= 0) return bad_label(c, s.who, "perm_cls[" + std::to_string(bad.q - 1) + "]", bad.s, bad.value, L.n_class);
+    int r = collect();
+    if (r) return r;
+    if (!device) continue;
+    r = upload_sync(c, c->labels.p, L.stage.data(), (size_t)groups * (size_t)L.S * PB * sizeof(uint16_t));
+    if (!r) r = timer_begin(c, ICIKT_K_EPILOGUE, s.A.flags);
+    if (r) return r;
+    r = steps.launch(groups, nb);
+    if (r) return r;
+    r = timer_end(c, ICIKT_K_EPILOGUE, s.A.flags);
+    if (r) return r;
+    in_flight = q0;
+    in_flight_n = nb;
+  }
+  return collect();
 }
 
 }  // namespace host

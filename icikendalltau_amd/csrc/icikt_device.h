@@ -8,6 +8,7 @@
 #include <stdint.h>
 
 #include "icikt_k1plan.h"   // ColStats, and the pair kernel's LDS layout and option word (K1_*, k1_*, ICIKT_CNT_BYTES)
+#include "icikt_labels.h"   // ANO_PB, ANO_PERMS_MAX, ANO_BATCH_BYTES: the label plane and its batches
 
 namespace icikt {
 
@@ -278,11 +279,8 @@ hipError_t launch_hc_pick(const int32_t* nn, const unsigned long long* nnkey, in
 hipError_t launch_hc_merge(unsigned long long* W, int32_t* nn, unsigned long long* nnkey, const int32_t* alive,
                            int32_t* list, int32_t* state, int method, int S, hipStream_t s);
 // ---- ANOSIM: class separation under 1 - raw with its permutation test (icikt_anosim.hip) ----
-constexpr int ANO_PB = 16;                // labellings a workgroup of the permutation kernel takes side by side
 constexpr int ANO_ROW_RUN = 256;          // rows of a workgroup's run
 constexpr int ANO_STRIP_MIN = 1, ANO_STRIP_MAX = 4096, ANO_STRIP_DEFAULT = 256;   // columns of a workgroup's strip (anostrip)
-constexpr long long ANO_PERMS_MAX = 1 << 20;        // labellings per upload (anoperms)
-constexpr long long ANO_BATCH_BYTES = 64ll << 20;   // ... and the bytes of labels an upload holds when no key says otherwise
 // kept: the whole combn plane launch_median_keep writes (n keys).  *total += the keys that are not NA_KEY; dhist [8][256]
 // += the keys (NA_KEY included) per digit and digit value.  The caller zeroes total and dhist.
 hipError_t launch_anosim_count(const unsigned long long* kept, long long n, unsigned long long* total,
@@ -302,7 +300,7 @@ hipError_t launch_anosim_classes(const unsigned long long* r2, const int32_t* cl
 hipError_t launch_anosim_perm(const unsigned long long* r2, const uint16_t* labT, int S, int n_groups, int strip,
                               int count_nw, unsigned long long* w2, unsigned long long* nw, hipStream_t s);
 // ---- PERMANOVA: the sums of squared dissimilarities (1 - raw)^2 per class and labelling (icikt_permanova.hip) ----
-// (the label plane, ANO_PB, the strip and the batch keys are ANOSIM's; a run of rows is the kernel file's own, 1 024)
+// (the label plane and the batch keys are icikt_labels.h's, the strip is ANOSIM's; a run of rows is the kernel file's own, 1 024)
 constexpr int PMV_T_NA = 0, PMV_T_LO = 1, PMV_T_HI = 2, PMV_TOTALS = 3;   // the words of launch_pmv_quant's totals
 constexpr int PMV_LDS_CLASSES = 2048;     // classes up to which k_pmv_classes keeps a labelling's bins in LDS (16 bytes each)
 // kept: the whole combn plane launch_median_keep writes (n keys).  q[e] = fixed::quantise_key(kept[e]) (icikt_fixed.h: 0

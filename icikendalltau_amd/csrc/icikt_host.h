@@ -163,6 +163,8 @@ struct icikt_ctx {
   struct SelectWork {
     DevBuf<unsigned long long> kept, plane_a, plane_b, counts, agg, total, dhist;
   } sel;
+  // the label plane of the permutation-test entries: one batch of labellings as halfwords (select_labellings)
+  DevBuf<uint16_t> labels;
 
   // per-sample medians within classes (icikt_class_medians_f64): the samples' places in their classes (MedianClasses)
   // and the results; the computed pairs' keys are in sel.kept
@@ -212,16 +214,16 @@ struct icikt_ctx {
     DevBuf<icikt::HcMerge> rec;
   } hc;
 
-  // ANOSIM (icikt_anosim_f64): the observed labelling and its per-class sums, a batch of labellings and their sums; the
-  // keys, their sorted copy and the doubled ranks are in sel (kept, plane_a, plane_b)
+  // ANOSIM (icikt_anosim_f64): the observed labelling and its per-class sums, and the sums of a batch of labellings
+  // (the batch itself: labels); the keys, their sorted copy and the doubled ranks are in sel (kept, plane_a, plane_b)
   struct AnosimBufs {
     DevBuf<unsigned long long> class_sums, w2, nw;
     DevBuf<int32_t> cls;
-    DevBuf<uint16_t> labels;
   } ano;
 
-  // PERMANOVA (icikt_permanova_f64): a batch of labellings (ano.labels), the two limbs of its columns' sums and of its
-  // bins, and the call's totals (NA pairs, Q's limbs); the keys and their fixed-point values are in sel (kept, plane_a)
+  // PERMANOVA (icikt_permanova_f64): the two limbs of the columns' sums and of the bins of a batch of labellings (the
+  // batch itself: labels), and the call's totals (NA pairs, Q's limbs); the keys and their fixed-point values are in
+  // sel (kept, plane_a)
   struct PermanovaBufs {
     DevBuf<unsigned long long> colsum_lo, colsum_hi, bins_lo, bins_hi, totals;
   } pmv;
@@ -333,7 +335,7 @@ int check_pair_args(icikt_ctx* c, const char* who, const MatrixSrc& X, int64_t n
                     const int32_t* pi, const int32_t* pj, int64_t* n_pairs, const void* out, bool out5,
                     int perspective, int alternative);
 
-// ---- the selection entries (icikt_topk_*, icikt_edges_*, icikt_class_medians_*, icikt_quantiles_*, icikt_class_matrix_*, icikt_padjust_*, icikt_mst_*, icikt_anosim_*, icikt_hclust_*) and icikt_cross_*: one driver, icikt_capi_select.cpp ----
+// ---- the selection entries (icikt_topk_*, icikt_edges_*, icikt_class_medians_*, icikt_quantiles_*, icikt_class_matrix_*, icikt_padjust_*, icikt_mst_*, icikt_anosim_*, icikt_hclust_*, icikt_permanova_*) and icikt_cross_*: one driver, icikt_capi_select.cpp ----
 // (the blocks a call runs in: icikt_blocks.h; DESIGN.md "adding a selection entry")
 // the arguments the entries share
 struct SelectArgs {
@@ -387,6 +389,43 @@ int select_download_red(icikt_ctx* c, unsigned long long* red);
 // timer pair: the caller's is around the sort and its own kernels.
 int select_sort(icikt_ctx* c, int64_t P, long long tile, const unsigned long long* h_dhist, unsigned long long* a,
                 unsigned long long* b, unsigned long long** sorted, unsigned long long** spare);
+
+// ---- class labels, and the labellings of the permutation-test entries (icikt_labels.h holds what needs no device) ----
+// every label of `name` [n] (cls, ref_cls, perm_cls[q]) inside 0 .. n_class - 1, `who` prefixing the message
+int check_labels(icikt_ctx* c, const char* who, const std::string& name, const int32_t* lab, int64_t n, int64_t n_class);
+// cls of an entry (null: one class, nothing is checked): n_class at least 1, at most class_cap (0: no cap; cap_why is
+// the entry's reason for it), then check_labels over the call's n_samp
+int select_check_classes(const SelectCall& s, const int32_t* cls, int n_class, int class_cap = 0, const char* cap_why = "");
+// ... and the permutations behind it: n_perm in 0 .. ICIKT_ANOSIM_MAX_PERM, (1 + n_perm) classes within cell_cap
+// (ICIKT_PERMANOVA_MAX_CELLS; 0: no cap), perm_cls where n_perm > 0.  The labels of perm_cls are select_labellings'.
+int select_check_labellings(const SelectCall& s, const int32_t* cls, int n_class, int class_cap, const char* cap_why,
+                            const int32_t* perm_cls, int64_t n_perm, int64_t cell_cap = 0);
+// The labellings of a call with n_samp > 0, made before select_run: the observed one first (a null cls: zeros), then
+// the n_perm rows of perm_cls; plan says how many an upload takes (label_batches: bytes_per_lab and the anoperms key).
+// Reserves c->labels for a batch.
+struct Labellings {
+  const int32_t* perm_cls = nullptr;
+  int64_t S = 0, n_class = 1, n_lab = 1;
+  LabelBatches plan{};
+  std::vector<int32_t> obs;      // the observed labelling
+  std::vector<uint16_t> stage;   // one batch as the device takes it: [groups][S][ANO_PB]
+  std::vector<int64_t> size_of;  // stage_labellings' class sizes
+};
+int select_labellings_begin(const SelectCall& s, const int32_t* cls, int n_class, const int32_t* perm_cls, int64_t n_perm,
+                            int64_t bytes_per_lab, Labellings* L);
+// what an entry does per batch, on c->stream
+struct LabellingSteps {
+  std::function<int(int64_t groups, int64_t nb)> launch;   // its kernels over the nb labellings (`groups` groups of ANO_PB) in
+                                                           // c->labels, inside the driver's ICIKT_K_EPILOGUE timer pair
+  std::function<int(int64_t q0, int64_t nb)> collect;      // download and wait for the sums of the launched batch, labellings
+                                                           // [q0, q0 + nb) of the call
+};
+// The labellings batch by batch, from an entry's finish step.  Per batch: staged and checked on the host
+// (stage_labellings, while the batch before runs: a bad label fails the call as "who: perm_cls[q][s] = v is outside
+// ..."), the batch before collected, the stage uploaded (which is what waits for that batch's kernels), steps.launch.
+// The last batch is collected at the end.  device == false: the labels are checked all the same, nothing is uploaded,
+// launched or collected.  within (optional, [n_lab]): every labelling's pairs of samples that share a class.
+int select_labellings(const SelectCall& s, Labellings& L, bool device, int64_t* within, const LabellingSteps& steps);
 
 }  // namespace host
 }  // namespace icikt

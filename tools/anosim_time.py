@@ -18,6 +18,7 @@
      after the calls (the context keeps its buffers: the low-water mark).
 
     python tools/anosim_time.py [--repeats 20] [--out profiles/anosim_time.log]
+    python tools/anosim_time.py --old-calls 0  # the device legs only (an A/B of two builds: ICIKT_LIB)
     python tools/anosim_time.py --quick        # tiny shapes: a rehearsal of the script, not a measurement
 """
 import argparse
@@ -78,6 +79,7 @@ def free_gb():
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--repeats", type=int, default=20)
+    ap.add_argument("--old-calls", type=int, default=3, help="calls of route (a); 0: the device legs only")
     ap.add_argument("--out", default=None)
     ap.add_argument("--quick", action="store_true", help="tiny shapes: rehearses the script, measures nothing")
     a = ap.parse_args()
@@ -94,19 +96,23 @@ def main():
     T = _lib.FLAG_TIMING
 
     log(f"\n## 1. S = {S}, n = {n} ({P} pairs), {n_class} classes of {S // n_class}, {n_perm} permutations, F-ordered float64")
-    ta = []
-    for _ in range(3):
+    ta, old = [], None
+    for _ in range(a.old_calls):
         t0 = time.perf_counter()
         old = old_route(ctx, X, cls, perms)
         ta.append(time.perf_counter() - t0)
         log(f"  (a) one call: {ta[-1] * 1e3:10.1f} ms")
     tb, sh_full, new = timed(ctx, lambda: ctx.anosim(X, cls, n_class, perms, flags=T), a.repeats, 2)
-    same = bool(old[0] == new[0][0] and np.array_equal(old[1], new[1]) and np.array_equal(old[2], new[2]))
-    sa, sb = stats(ta), stats(tb)
-    log(f"  (a) Context.matrix + numpy ranks and masked sums (3 calls, no warm-up): {fmt(sa)}")
+    sb = stats(tb)
+    same = "route (a) was not run"
+    if old is not None:
+        equal = old[0] == new[0][0] and np.array_equal(old[1], new[1]) and np.array_equal(old[2], new[2])
+        same = f"M, W2, nW of all {1 + n_perm} labellings {'equal' if equal else 'DIFFER'}"
+        log(f"  (a) Context.matrix + numpy ranks and masked sums ({a.old_calls} calls, no warm-up): {fmt(stats(ta))}")
     log(f"  (b) Context.anosim ({a.repeats} calls after 2 warm-up calls):               {fmt(sb)}   "
-        f"M, W2, nW of all {1 + n_perm} labellings {'equal' if same else 'DIFFER'}; n_ge {new[3]}, n_undefined {new[4]}")
-    log(f"  new route {sa[0] / sb[0]:.1f}x the old one's speed at the median")
+        f"{same}; n_ge {new[3]}, n_undefined {new[4]}")
+    if old is not None:
+        log(f"  new route {stats(ta)[0] / sb[0]:.1f}x the old one's speed at the median")
 
     log("\n## 2. time shares of (b), ms per call (medians; ICIKT_FLAG_TIMING)")
     t0p, sh_none, _o = timed(ctx, lambda: ctx.anosim(X, cls, n_class, None, flags=T), a.repeats, 2)
