@@ -28,6 +28,7 @@ SOURCES = [os.path.join(_PKG, "csrc", f) for f in ("icikt_kernels.hip", "icikt_p
                                                        "icikt_hclust.hip", "icikt_capi_hclust.cpp",
                                                        "icikt_anosim.hip", "icikt_capi_anosim.cpp",
                                                        "icikt_permanova.hip", "icikt_capi_permanova.cpp",
+                                                       "icikt_permdisp.hip", "icikt_capi_permdisp.cpp",
                                                        "icikt_cross.hip", "icikt_capi_cross.cpp")]
 HEADERS = [os.path.join(_ROOT, "include", "icikt.h"), os.path.join(_PKG, "csrc", "icikt_device.h"),
            os.path.join(_PKG, "csrc", "icikt_wave.h"), os.path.join(_PKG, "csrc", "icikt_host.h"),
@@ -59,6 +60,7 @@ ADJUST_MAX_ALPHA = 16         # ICIKT_ADJUST_MAX_ALPHA: alphas per call of icikt
 HCLUST = {"complete": 0, "average": 1, "single": 2}   # ICIKT_HCLUST_*: linkage methods of icikt_hclust_*
 ANOSIM_MAX_PERM = 1000000     # ICIKT_ANOSIM_MAX_PERM: labellings per call of icikt_anosim_* beside the observed one
 PERMANOVA_MAX_CELLS = 1 << 26  # ICIKT_PERMANOVA_MAX_CELLS: (1 + n_perm) n_class of icikt_permanova_*
+PERMDISP_MAX_CELLS = 1 << 26   # ICIKT_PERMDISP_MAX_CELLS: n_samp n_class of icikt_permdisp_*
 MASK_VALS = 32                # distinct finite global_na values of the device-side exclusion rule (icikt_device.h)
 MAX_FEATURES = 65535          # the tuned kernels
 MAX_FEATURES_WIDE = 262144    # the plain 32-bit path (exact integer arithmetic)
@@ -99,6 +101,7 @@ EXPORTS = (
     "icikt_hclust_f64", "icikt_hclust_in", "icikt_hclust_csc",
     "icikt_anosim_f64", "icikt_anosim_in", "icikt_anosim_csc",
     "icikt_permanova_f64", "icikt_permanova_in", "icikt_permanova_csc",
+    "icikt_permdisp_f64", "icikt_permdisp_in", "icikt_permdisp_csc",
     "icikt_cross_f64", "icikt_cross_in",
     "icikt_ref_prepare_f64", "icikt_ref_prepare_in", "icikt_ref_cross_f64", "icikt_ref_cross_in", "icikt_ref_info",
 )
@@ -401,6 +404,8 @@ def lib():
                                    c_vp, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]
     L.icikt_permanova_f64.argtypes = [c_vp, c_vp, c_i64, c_i64, c_i64, c_vp, c_int, c_int, c_int, c_int, c_u32, c_vp,
                                       c_int, c_vp, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]
+    L.icikt_permdisp_f64.argtypes = [c_vp, c_vp, c_i64, c_i64, c_i64, c_vp, c_int, c_int, c_int, c_int, c_u32, c_vp,
+                                     c_int, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]
     # (two matrices: the twins are spelled out)
     cross_tail = [c_i64, c_i64, c_i64, c_vp, c_int, c_int, c_int, c_int, c_int, c_u32, c_int, c_vp, c_vp, c_vp, c_vp, c_vp,
                   c_vp]
@@ -419,14 +424,14 @@ def lib():
     # the *_in twins: (ctx, const icikt_input*, n_feat, n_samp, ...) where the _f64 entry has (ctx, X, n_feat, n_samp, ld, ...)
     for nm in ("pairs", "matrix", "pairs_complete", "missingness", "cor_pairs", "col_medians", "censor_counts",
                "rank_order", "topk", "edges", "class_medians", "quantiles", "class_matrix", "padjust", "mst", "hclust", "anosim",
-               "permanova"):
+               "permanova", "permdisp"):
         f64 = getattr(L, f"icikt_{nm}_f64").argtypes
         getattr(L, f"icikt_{nm}_in").argtypes = [c_vp, ctypes.POINTER(InputView), c_i64, c_i64] + list(f64[5:])
     L.icikt_convert_dev.argtypes = [c_vp, c_vp, c_int, c_int, c_i64, c_i64, c_i64, c_vp, c_i64]
     # the *_csc twins: (ctx, const icikt_csc_input*, n_feat, n_samp, ...)
     for nm in ("pairs", "matrix", "missingness", "col_medians", "censor_counts", "rank_order", "topk", "edges",
                "class_medians", "quantiles", "class_matrix", "padjust", "mst", "hclust", "anosim",
-               "permanova"):
+               "permanova", "permdisp"):
         f64 = getattr(L, f"icikt_{nm}_f64").argtypes
         getattr(L, f"icikt_{nm}_csc").argtypes = [c_vp, ctypes.POINTER(CscInput), c_i64, c_i64] + list(f64[5:])
     L.icikt_scatter_csc_dev.argtypes = [c_vp, c_vp, c_vp, c_vp, c_int, c_int, ctypes.c_double, c_i64, c_i64, c_vp, c_i64]
@@ -495,8 +500,8 @@ def _matrix_call(fn, handle, chk, X, global_na, pi, pj, perspective, alternative
 
 
 class _SelectCall:
-    """What the eleven selection entries (topk, cross, edges, class_medians, class_matrix, quantiles, padjust, mst, hclust,
-    anosim, permanova) share around their own arguments.  An instance holds a resolved entry (what Context._entry returns; the
+    """What the twelve selection entries (topk, cross, edges, class_medians, class_matrix, quantiles, padjust, mst, hclust,
+    anosim, permanova, permdisp) share around their own arguments.  An instance holds a resolved entry (what Context._entry returns; the
     array behind its arguments stays alive with it), n_samp and flags as that entry sees them, and alloc: the allocator
     of the result arrays that are pinned when the call says so.  Calling it makes the checked call fn(ctx, <X>,
     global_na, n_global_na, *before, perspective, alternative, continuity, flags[, scale_max], *after, max_taumax,
@@ -551,6 +556,15 @@ def _labellings_arg(cls, n_class, perm_cls, n_samp):
     room = n_class if 1 <= n_class <= 65535 else 1
     n_lab = 1 + (n_perm if n_perm <= ANOSIM_MAX_PERM else 0)
     return cls_a, n_class, perm_a, n_perm, room, n_lab
+
+
+def _limbs_to_ints(lo, hi):
+    """hi 2^32 + lo of two int64 arrays of non-negative limbs (lo < 2^48) as an object array of Python ints.  While every
+    hi is below 2^30 the sum fits 63 bits and is taken in int64: one conversion of the table instead of three passes of
+    Python arithmetic over it."""
+    if hi.size == 0 or (int(hi.max()) < (1 << 30) and int(lo.max()) < (1 << 48)):
+        return ((hi << 32) + lo).astype(object)
+    return hi.astype(object) * (1 << 32) + lo.astype(object)
 
 
 class Context:
@@ -1067,6 +1081,29 @@ class Context:
                     _ptr(bins_lo), _ptr(bins_hi)))
         class_q = bins_hi.astype(object) * (1 << 32) + bins_lo.astype(object)
         return n_pairs, (int(q_total[1]) << 32) + int(q_total[0]), class_q, *tail
+
+    def permdisp(self, X, cls=None, n_class=1, global_na=None, perspective="global", alternative="two.sided",
+                 continuity=False, flags: int = 0):
+        """PERMDISP's integer table of the classes under the dissimilarity 1 - raw, on the device (icikt_permdisp_f64):
+        all pairs are computed, their (1 - raw)^2 turned into PERMANOVA's fixed-point integers q (csrc/icikt_fixed.h)
+        and summed there per sample and class.  cls, n_class, X and global_na as class_matrix() takes them.  Returns
+        (n_pairs [2] int64: values, NA pairs; Q: the sum of q over all values, a Python int; T [S, n_class] of Python
+        ints (dtype object): T[i][c] the sum of q_ij over the samples j != i of class c, as summed also when a pair is
+        NA (it adds 0); max_taumax; reason_counts [5]).  The limbs of the C ABI are combined here: T = hi 2^32 + lo.
+        api.permdisp_distance and api.permdisp_statistic turn the table into the distances to the class centroids and
+        their ANOVA F.  The argument checks are the library's: a label out of range, more than 65 535 classes, more
+        than PERMDISP_MAX_CELLS cells or a bad perspective raises IciktError."""
+        sel = _SelectCall(self, self._entry("permdisp", X, flags))
+        cls_a = _class_arg(cls, sel.n_samp)
+        n_class = int(n_class) if cls_a is not None else 1
+        room = n_class if 1 <= n_class <= 65535 and sel.n_samp * n_class <= PERMDISP_MAX_CELLS else 1
+        n_pairs = np.zeros(2, dtype=np.int64)
+        q_total = np.zeros(2, dtype=np.int64)
+        t_lo = np.zeros((sel.n_samp, room), dtype=np.int64)
+        t_hi = np.zeros((sel.n_samp, room), dtype=np.int64)
+        tail = sel(global_na, perspective, alternative, continuity, None, (),
+                   (_ptr(cls_a), n_class, _ptr(n_pairs), _ptr(q_total), _ptr(t_lo), _ptr(t_hi)))
+        return n_pairs, (int(q_total[1]) << 32) + int(q_total[0]), _limbs_to_ints(t_lo, t_hi), *tail
 
     def edges(self, X, min_raw=None, max_pvalue=None, min_completeness=None, absolute=False, max_edges=0,
               global_na=None, perspective="global", alternative="two.sided", continuity=False, flags: int = 0,

@@ -145,6 +145,13 @@ class HipEngine:
         return self._select_ctx().permanova(data_matrix, cls, n_class, perm_cls, global_na, perspective, alternative,
                                             continuity, self.flags | flags)
 
+    def permdisp(self, data_matrix, cls=None, n_class=1, global_na=None, perspective="global", alternative="two.sided",
+                 continuity=False, flags=0):
+        """PERMDISP's fixed-point sums of every sample to every class, on the device (icikt_permdisp_f64):
+        Context.permdisp's arguments and result."""
+        return self._select_ctx().permdisp(data_matrix, cls, n_class, global_na, perspective, alternative, continuity,
+                                           self.flags | flags)
+
     def cor_pairs(self, X, pi, pj, method, pairwise, alternative, continuity):
         """cor_fast's pairs on the device (icikt_cor_pairs_f64): (out3: rho, p-value, n_values; reasons)."""
         return self.ctx.cor_pairs(X, pi, pj, method, pairwise, alternative, continuity)
@@ -2342,6 +2349,264 @@ def ici_kendalltau_permanova(data_matrix, sample_classes, permutations=999, seed
          "df_among": int(obs.df_among), "df_within": int(obs.df_within)},
         (n_perm, n_ge, n_undef), {}, Fs if return_perms else None, {"n_valid": int(n_pairs[0]), "n_na": n_na}, levels,
         {"class_size": sizes, "class_ss": class_ss, "sums": {"q_total": int(Q), "class_q": class_q}},
+        names, max_taumax, t_diff)
+
+
+# --------------------------------------------------------------------------------------------------
+# ici_kendalltau_permdisp: PERMDISP (Anderson 2006; vegan::betadisper + permutest) of the classes: every sample's
+# distance to the class centroids from the integer table of icikt_permdisp_f64
+# --------------------------------------------------------------------------------------------------
+_PERMDISP_LIMB = 24   # bits of a limb of the permutation stage: 65 535 of them in a bin stay exact in a double
+
+
+def permdisp_distance(X, n):
+    """The distance of a sample to the centroid of a class of n samples from the integer X = n T - A of the table
+    (D^2 = X / (n^2 2^50)): the correctly rounded double of sqrt(|X|) / (n 2^25).  With R = |X| / (n^2 2^50), e chosen
+    so that floor(R 4^e) has 127 or 128 bits and m its integer square root (64 bits), m' = 2 m when R 4^e is the
+    integer m^2 and 2 m + 1 otherwise: the sticky bit makes the one conversion of m' / 2^(e + 1) round correctly."""
+    X, n = abs(int(X)), int(n)
+    if n < 1:
+        raise ValueError("a centroid needs a class with a sample")
+    if X == 0:
+        return 0.0
+    den = (n * n) << PERMANOVA_FRAC_BITS
+    e = (127 - (X.bit_length() - den.bit_length())) // 2
+    while True:
+        num, d = (X << (2 * e), den) if e >= 0 else (X, den << (-2 * e))
+        N, rest = divmod(num, d)
+        bits_n = N.bit_length()
+        if bits_n < 127:
+            e += 1
+        elif bits_n > 128:
+            e -= 1
+        else:
+            break
+    m = math.isqrt(N)
+    m2 = 2 * m if (rest == 0 and m * m == N) else 2 * m + 1
+    return float(Fraction(m2, 1 << (e + 1)) if e + 1 >= 0 else Fraction(m2 << -(e + 1)))
+
+
+class PermdispStatistic(tuple):
+    """(F, ss_among, ss_within, df_among, df_within) of one labelling: exact ``Fraction``s and ints.  F is None where
+    it is undefined and ``math.inf`` when SS_W = 0 < SS_A."""
+    __slots__ = ()
+    F = property(lambda self: self[0])
+    ss_among = property(lambda self: self[1])
+    ss_within = property(lambda self: self[2])
+    df_among = property(lambda self: self[3])
+    df_within = property(lambda self: self[4])
+
+
+def _permdisp_ints(values):
+    """values (doubles, ints or Fractions) as integers over one denominator: (ints, D) with values[i] = ints[i] / D."""
+    fr = [Fraction(v) if not isinstance(v, (float, np.floating)) else Fraction(*float(v).as_integer_ratio()) for v in values]
+    D = math.lcm(*(f.denominator for f in fr)) if fr else 1
+    return [f.numerator * (D // f.denominator) for f in fr], D
+
+
+def _permdisp_anova(S, tot, sq, G, sizes):
+    """The one-way ANOVA of S integers with sum tot and sum of squares sq whose class sums are G and class sizes
+    `sizes`, exactly: (F, SS_A, SS_W, df_among, df_within) in the integers' own unit.  F is None with fewer than two
+    classes that have a sample, with S <= C' or when all values are equal, and inf when SS_W = 0 < SS_A."""
+    used = [(int(g), int(n)) for g, n in zip(G, sizes) if int(n) > 0]
+    L = math.lcm(*(n for _, n in used)) if used else 1
+    val = Fraction(sum(g * g * (L // n) for g, n in used), L)      # sum_c G_c^2 / n_c
+    ss_a = val - Fraction(tot * tot, S)
+    ss_w = sq - val
+    df_a, df_w = len(used) - 1, S - len(used)
+    if df_a < 1 or df_w <= 0 or S * sq == tot * tot:
+        F = None
+    elif ss_w == 0:
+        F = math.inf
+    else:
+        F = (ss_a * df_w) / (ss_w * df_a)
+    return F, ss_a, ss_w, df_a, df_w
+
+
+def permdisp_statistic(values, labels, n_class):
+    """The one-way ANOVA F of `values` (one per sample: doubles are taken as the rationals they are) over the classes
+    `labels` (codes in 0 .. n_class - 1), exactly: with C' the classes that have a sample, F = (SS_A / (C' - 1)) /
+    (SS_W / (S - C')).  F is None (undefined) when C' < 2, when S <= C' or when all values are equal, and ``math.inf``
+    when SS_W = 0 < SS_A.  Returns a ``PermdispStatistic``."""
+    V, D = _permdisp_ints(values)
+    lab = [int(c) for c in labels]
+    if len(lab) != len(V):
+        raise ValueError("`labels` must give one class per value")
+    G, sizes = [0] * int(n_class), [0] * int(n_class)
+    for v, c in zip(V, lab):
+        G[c] += v
+        sizes[c] += 1
+    F, ss_a, ss_w, df_a, df_w = _permdisp_anova(len(V), sum(V), sum(v * v for v in V), G, sizes)
+    return PermdispStatistic((F, ss_a / (D * D), ss_w / (D * D), df_a, df_w))
+
+
+def _permdisp_permute(residuals, labellings, n_class, F_obs):
+    """permutest's stage on the host: the exact ANOVA F of the residuals under every labelling [n_perm, S] (permuting
+    residuals over fixed labels is permuting labels over fixed residuals).  The class sums are taken limb by limb
+    through ``np.bincount`` -- limbs of 24 bits, at most 65 535 of them in a bin, are exact in a double -- and combined
+    as Python ints.  Returns (the F of every labelling -- Fraction, None or inf --, n_ge: those that are defined and
+    >= F_obs, compared exactly; n_undefined)."""
+    R, _D = _permdisp_ints(residuals)
+    S = len(R)
+    labellings = np.asarray(labellings, dtype=np.int64).reshape(-1, S)
+    tot, sq = sum(R), sum(v * v for v in R)
+    off = 1 << max((abs(v).bit_length() for v in R), default=0)          # R + off >= 0
+    n_limb = max(1, -(-(off.bit_length() + 1) // _PERMDISP_LIMB))
+    mask = (1 << _PERMDISP_LIMB) - 1
+    limbs = [np.array([((v + off) >> (_PERMDISP_LIMB * k)) & mask for v in R], dtype=np.float64) for k in range(n_limb)]
+    Fs, n_ge, n_undef = [], 0, 0
+    step = max(1, (1 << 22) // max(n_class, S))
+    for a in range(0, labellings.shape[0], step):
+        labs = labellings[a:a + step]
+        m = labs.shape[0]
+        at = (labs + (np.arange(m, dtype=np.int64) * n_class)[:, None]).ravel()
+        sizes = np.bincount(at, minlength=m * n_class).reshape(m, n_class)
+        G = -(sizes.astype(object) * off)
+        for k, limb in enumerate(limbs):
+            part = np.bincount(at, weights=np.tile(limb, m), minlength=m * n_class).astype(np.int64).reshape(m, n_class)
+            G = G + part.astype(object) * (1 << (_PERMDISP_LIMB * k))
+        for g, sz in zip(G, sizes):
+            f = _permdisp_anova(S, tot, sq, g, sz)[0]
+            Fs.append(f)
+            n_undef += f is None
+            n_ge += f is not None and F_obs is not None and f >= F_obs
+    return Fs, int(n_ge), int(n_undef)
+
+
+def _permdisp_numpy(raw, cls, n_class):
+    """The integers of icikt_permdisp_f64 from a full S x S raw matrix, for engines without a permdisp method (the CPU
+    tests' checker engines): (n_pairs [2], Q, T [S, n_class] of Python ints).  A pair without a value adds 0; the sums
+    are taken limb by limb in int64, as the device takes them."""
+    raw = np.asarray(raw, dtype=np.float64)
+    S = raw.shape[0]
+    iu, ju = np.triu_indices(S, k=1)
+    v = raw[iu, ju]
+    ok = ~np.isnan(v)
+    q = np.zeros((S, S), dtype=np.int64)
+    q[iu[ok], ju[ok]] = _permanova_quantise(v[ok])
+    q = q + q.T
+    onehot = (np.asarray(cls, dtype=np.int64)[:, None] == np.arange(n_class, dtype=np.int64)[None, :]).astype(np.int64)
+    t_lo, t_hi = (q & 0xFFFFFFFF) @ onehot, (q >> 32) @ onehot
+    up = q[iu, ju]
+    return (np.array([int(ok.sum()), int((~ok).sum())], dtype=np.int64),
+            (int((up >> 32).sum()) << 32) + int((up & 0xFFFFFFFF).sum()),
+            t_hi.astype(object) * (1 << 32) + t_lo.astype(object))
+
+
+def _permdisp_centroids(T, cls, n_class):
+    """From the table: (sizes [C], A [C] Python ints, X [S, C] object array of n_c T[i][c] - A_c, 0 in the columns of
+    empty classes)."""
+    S = T.shape[0]
+    sizes = np.bincount(cls, minlength=n_class).astype(np.int64)
+    A = []
+    for c in range(n_class):
+        twice = sum(int(T[i, c]) for i in np.flatnonzero(cls == c))
+        if twice % 2:
+            raise RuntimeError("ici_kendalltau_permdisp: a class's within-class sum is odd: the table is not symmetric")
+        A.append(twice // 2)
+    n_obj = np.array([int(n) for n in sizes], dtype=object)
+    X = T * n_obj[None, :] - np.array(A, dtype=object)[None, :] if S else np.zeros((0, n_class), dtype=object)
+    X[:, sizes == 0] = 0
+    return sizes, A, X
+
+
+def ici_kendalltau_permdisp(data_matrix, sample_classes, permutations=999, seed=None, strata=None, return_perms=True,
+                            global_na=(float("nan"), float("inf"), 0), perspective="global", alternative="two.sided",
+                            continuity=False, colnames=None, engine=None):
+    """Are the classes of the samples (columns) equally dispersed under ICI-Kendall-tau: PERMDISP (Anderson 2006;
+    ``vegan::betadisper(type = "centroid")`` with ``permutest``) on the dissimilarity ``1 - raw`` -- without the S x S
+    matrices ``ici_kendalltau`` returns and without a PCoA.  It is the test to run beside ``ici_kendalltau_permanova``
+    (Anderson & Walsh 2013): a significant PERMANOVA means "the classes differ in location" only when their
+    dispersions are homogeneous.
+
+    ``sample_classes`` gives one label per column (required; the levels are ``ici_kendalltau_class_matrix``'s).  With
+    ``d^2 = (1 - raw)^2`` the squared distance of sample i to the centroid of class c, in the full principal-coordinate
+    space (real axes minus imaginary axes), is ``(1 / n_c) sum_{j in c} d^2_ij - (1 / n_c^2) sum_{j<k in c} d^2_jk``: it
+    needs distances only.  ``distances`` is every sample's distance to its own class centroid (``sqrt(abs(.))``, as
+    vegan takes it; ``n_negative`` counts the samples whose squared distance is negative, the sign that the
+    dissimilarity is not Euclidean there) -- the multivariate outlier screen --, ``centroid_distance`` [S x C] the
+    distance to every class centroid (NA for a class without a sample) and ``nearest_centroid`` the index into
+    ``class_levels`` of the class with the smallest squared distance in absolute value, compared exactly, ties to the
+    earlier class.  A sample BELONGS to its own class's centroid, as in ``betadisper``; this differs from
+    ``ici_kendalltau_class_matrix``, where a sample is not its own partner.  ``statistic`` is the one-way ANOVA F of
+    ``distances`` over the classes, ``class_mean_distance`` vegan's "average distance to centroid".
+
+    EXACTNESS.  Every ``(1 - raw)^2`` is PERMANOVA's integer multiple of 2^-50, every squared distance an integer over
+    ``n_c^2 2^50``, every distance its correctly rounded square root (``permdisp_distance``); F is computed from those
+    doubles as the rationals they are (``permdisp_statistic``).  The result is a pure function of the input and the
+    labellings.
+
+    THE PERMUTATION TEST is ``permutest.betadisper``'s: the residuals ``distances - class_mean_distance[class]`` (one
+    IEEE subtraction each) are permuted, which is the same as permuting the labels over the fixed residuals.  The
+    labellings are ``ici_kendalltau_anosim``'s (``anosim_permutations``): the same ``seed`` and ``strata`` give all three
+    tests the same labellings; an integer array [n_perm, S] of class codes is used as given.  ``pvalue`` is
+    ``(1 + n_ge) / (1 + n_perm)`` with ``n_ge`` the labellings whose F is defined and ``>=`` the observed F, compared
+    exactly; ``n_undefined`` labellings have no F and do not count.  This stage runs on the host.
+
+    EVERY PAIR IS NEEDED.  With a pair whose ``raw`` is NA (``n_na > 0``) no centroid has a meaning: every statistic,
+    distance and centroid cell is NA (``nearest_centroid`` -1, ``n_negative`` 0), one warning says so, and the integer
+    table is still returned as summed (an NA pair adds 0).  S times the number of classes is at most 2^26.  The other
+    arguments are ``ici_kendalltau``'s (column names are required).
+
+    Returns a dict: ``statistic``, ``pvalue``, ``df_among``, ``df_within``, ``ss_among``, ``ss_within``;
+    ``n_permutations``, ``n_ge``, ``n_undefined``, ``perm_statistic`` ([n_perm], NA where undefined; only with
+    ``return_perms``); ``distances`` [S], ``class_mean_distance``, ``class_size``, ``class_levels``;
+    ``centroid_distance`` [S, C], ``nearest_centroid`` [S]; ``n_negative``, ``n_valid``, ``n_na``; ``sums`` (the
+    integers: ``q_total``, ``t`` [S, C] and ``class_q`` [C], the within-class sums derived from it); ``sample_id``,
+    ``max_taumax`` and ``run_time``.
+    """
+    data_matrix, names, n_sample, levels, cls, perms = _labellings_input(data_matrix, colnames, sample_classes,
+                                                                         permutations, seed, strata)
+    n_class, n_perm = len(levels), int(perms.shape[0])
+    if n_sample * n_class > _lib.PERMDISP_MAX_CELLS:
+        raise ValueError(f"samples x classes must be at most {_lib.PERMDISP_MAX_CELLS}")
+    if perms.size and (perms.min() < 0 or perms.max() >= n_class):
+        raise ValueError("`permutations` holds a class code outside 0 .. n_class - 1")
+    eng = engine or _default_engine()
+    if hasattr(eng, "permdisp"):
+        (n_pairs, Q, T, max_taumax), t_diff = _on_device(
+            eng, data_matrix, global_na,
+            lambda X, gna: eng.permdisp(X, cls, n_class, gna, perspective, alternative, continuity, 0))
+    else:
+        mats5, t_diff, max_taumax = _from_full(eng, data_matrix, names, global_na, perspective, True, alternative,
+                                               continuity)
+        n_pairs, Q, T = _permdisp_numpy(mats5[1], cls, n_class)
+    S, n_na = n_sample, int(n_pairs[1])
+    sizes, A, X = _permdisp_centroids(T, cls, n_class)
+    n_used = int((sizes > 0).sum())
+    if n_na > 0:
+        warnings.warn(f"PERMDISP needs every pair and {n_na} of them have no raw value: every statistic and distance is "
+                      "NA.  `ici_kendalltau_medians` returns `n_valid` per column, which finds the columns to leave out.",
+                      RuntimeWarning, stacklevel=2)
+        obs = PermdispStatistic((None, None, None, n_used - 1, S - n_used))
+        Fs, n_ge, n_undef = [None] * n_perm, 0, n_perm
+        z, means, zc = _na_filled(S), _na_filled(n_class), _na_filled((S, n_class))
+        nearest, n_negative = np.full(S, -1, dtype=np.int32), 0
+    else:
+        used = np.flatnonzero(sizes > 0)
+        zc = _na_filled((S, n_class))
+        for c in used:
+            n_c = int(sizes[c])
+            zc[:, c] = [permdisp_distance(x, n_c) for x in X[:, c]]
+        z = zc[np.arange(S), cls]
+        n_negative = int(sum(1 for i in range(S) if X[i, cls[i]] < 0))
+        w_sq = math.lcm(*(int(sizes[c]) ** 2 for c in used))
+        keys = np.abs(X[:, used]) * np.array([w_sq // int(sizes[c]) ** 2 for c in used], dtype=object)[None, :]
+        nearest = used[np.argmin(keys, axis=1)].astype(np.int32)     # (the first of equal keys: the earlier class)
+        zi, D = _permdisp_ints(z)
+        means = _na_filled(n_class)
+        for c in used:
+            means[c] = float(Fraction(sum(zi[i] for i in np.flatnonzero(cls == c)), D * int(sizes[c])))
+        obs = permdisp_statistic(z, cls, n_class)
+        Fs, n_ge, n_undef = _permdisp_permute(z - means[cls], perms, n_class, obs.F)
+    return _labellings_result(
+        {"statistic": _as_float(obs.F), "pvalue": _na_real() if obs.F is None else float(Fraction(1 + n_ge, 1 + n_perm)),
+         "df_among": int(obs.df_among), "df_within": int(obs.df_within), "ss_among": _as_float(obs.ss_among),
+         "ss_within": _as_float(obs.ss_within)},
+        (n_perm, n_ge, n_undef), {}, Fs if return_perms else None,
+        {"distances": z, "class_mean_distance": means, "class_size": sizes}, levels,
+        {"centroid_distance": zc, "nearest_centroid": nearest, "n_negative": n_negative, "n_valid": int(n_pairs[0]),
+         "n_na": n_na, "sums": {"q_total": int(Q), "t": T, "class_q": np.array(A, dtype=object)}},
         names, max_taumax, t_diff)
 
 

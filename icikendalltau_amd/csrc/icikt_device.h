@@ -1,5 +1,5 @@
 // icikt_device.h -- structures, layouts and launcher declarations shared by the device units (icikt_prepass.hip,
-// icikt_kernels.hip, icikt_epilogue.hip, icikt_cor.hip, icikt_diag.hip, icikt_topk.hip, icikt_edges.hip, icikt_medians.hip, icikt_quantiles.hip, icikt_classmat.hip, icikt_padjust.hip, icikt_mst.hip, icikt_hclust.hip, icikt_anosim.hip, icikt_permanova.hip, icikt_cross.hip) and the C-ABI
+// icikt_kernels.hip, icikt_epilogue.hip, icikt_cor.hip, icikt_diag.hip, icikt_topk.hip, icikt_edges.hip, icikt_medians.hip, icikt_quantiles.hip, icikt_classmat.hip, icikt_padjust.hip, icikt_mst.hip, icikt_hclust.hip, icikt_anosim.hip, icikt_permanova.hip, icikt_permdisp.hip, icikt_cross.hip) and the C-ABI
 // host side (icikt_capi*.cpp, icikt_multi.cpp).  Internal; the public boundary is include/icikt.h.
 #ifndef ICIKT_DEVICE_H
 #define ICIKT_DEVICE_H
@@ -318,6 +318,16 @@ hipError_t launch_pmv_perm(const unsigned long long* q, const uint16_t* labT, in
 hipError_t launch_pmv_classes(const uint16_t* labT, const unsigned long long* colsum_lo,
                               const unsigned long long* colsum_hi, int S, int n_class, long long n_lab,
                               unsigned long long* bins_lo, unsigned long long* bins_hi, hipStream_t s);
+// ---- PERMDISP: every sample's sum of squared dissimilarities to every class (icikt_permdisp.hip) ----
+constexpr long long DISP_MAX_CELLS = 1ll << 26;   // == ICIKT_PERMDISP_MAX_CELLS: S n_class, 16 bytes a cell
+// kept: the whole combn(S, 2) plane launch_median_keep writes; cls [S]: a class in 0 .. n_class - 1 per sample (checked
+// by the host).  t_lo / t_hi [S][n_class] = the low 32 bits / the rest of q = fixed::quantise_key(key) summed over the
+// partners t != s of class c: T = hi 2^32 + lo.  Every cell is written (above PMV_LDS_CLASSES classes the table is
+// zeroed here and added to).  totals (PMV_T_*, zeroed by the caller) += the NA_KEY pairs and the limbs of every q, each
+// pair once: launch_pmv_quant's totals
+hipError_t launch_disp_table(const unsigned long long* kept, const int32_t* cls, int S, int n_class,
+                             unsigned long long* t_lo, unsigned long long* t_hi, unsigned long long* totals,
+                             hipStream_t s);
 // ---- quantiles and histogram of all pairs (icikt_quantiles.hip) ----
 constexpr int QUANT_MAX_BINS = 1024;    // == ICIKT_HIST_MAX_BINS: k_quant_fold stages 1 025 breaks and 2 x 1 026 counters in LDS
 constexpr int QUANT_HEAD = 4;           // words of a counted group before its bins: n_valid, n_na, below, above

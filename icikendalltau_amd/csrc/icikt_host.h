@@ -228,6 +228,13 @@ struct icikt_ctx {
     DevBuf<unsigned long long> colsum_lo, colsum_hi, bins_lo, bins_hi, totals;
   } pmv;
 
+  // PERMDISP (icikt_permdisp_f64): the class of every sample, the two limbs of the S x n_class table and the call's
+  // totals (NA pairs, Q's limbs); the keys are in sel.kept
+  struct PermdispBufs {
+    DevBuf<unsigned long long> t_lo, t_hi, totals;
+    DevBuf<int32_t> cls;
+  } disp;
+
   // missing-value diagnostics (icikt_col_medians_f64, icikt_censor_counts_f64, icikt_rank_order_f64)
   struct DiagBufs {
     DevBuf<double> median, medrank, out;
@@ -335,7 +342,7 @@ int check_pair_args(icikt_ctx* c, const char* who, const MatrixSrc& X, int64_t n
                     const int32_t* pi, const int32_t* pj, int64_t* n_pairs, const void* out, bool out5,
                     int perspective, int alternative);
 
-// ---- the selection entries (icikt_topk_*, icikt_edges_*, icikt_class_medians_*, icikt_quantiles_*, icikt_class_matrix_*, icikt_padjust_*, icikt_mst_*, icikt_anosim_*, icikt_hclust_*, icikt_permanova_*) and icikt_cross_*: one driver, icikt_capi_select.cpp ----
+// ---- the selection entries (icikt_topk_*, icikt_edges_*, icikt_class_medians_*, icikt_quantiles_*, icikt_class_matrix_*, icikt_padjust_*, icikt_mst_*, icikt_anosim_*, icikt_hclust_*, icikt_permanova_*, icikt_permdisp_*) and icikt_cross_*: one driver, icikt_capi_select.cpp ----
 // (the blocks a call runs in: icikt_blocks.h; DESIGN.md "adding a selection entry")
 // the arguments the entries share
 struct SelectArgs {

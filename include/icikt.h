@@ -720,6 +720,41 @@ int icikt_permanova_f64(icikt_ctx *ctx, const double *X, int64_t n_feat, int64_t
                         int64_t *n_pairs, int64_t *q_total, int64_t *bins_lo, int64_t *bins_hi, double *max_taumax,
                         int64_t *reason_counts);
 
+/* ---- PERMDISP: every sample's sum of squared dissimilarities to every class -------------------------------------------
+ *
+ * The test that belongs beside PERMANOVA (Anderson & Walsh 2013): are the classes' dispersions homogeneous -- Anderson
+ * 2006, vegan::betadisper(type = "centroid") with permutest -- on the dissimilarity 1 - raw.  The triangle runs as in
+ * icikt_permanova_f64 and a pair's q is the same integer (csrc/icikt_fixed.h; a pair that is no value adds 0), so
+ * n_pairs and q_total are bit for bit icikt_permanova_f64's on the same input.  This entry returns the table
+ *   T[i][c] = sum of q_ij over the samples j != i with cls[j] = c      (0 for a class without a sample)
+ * and nothing else: with n_c the class sizes and A_c = 1/2 sum_{i in c} T[i][c] (the within-class pairs' sum), the
+ * squared distance of sample i to the centroid of class c in the full principal-coordinate space is
+ *   D2(i, c) = (n_c T[i][c] - A_c) / (n_c^2 2^50),
+ * a signed integer over a constant; the distances, their ANOVA F and the permutation test are the caller's, in integers
+ * and rational arithmetic.
+ *   cls, n_class   as icikt_class_matrix_f64 (a null cls: one class, n_class ignored); n_class <=
+ *                  ICIKT_ANOSIM_MAX_CLASSES and n_samp n_class <= ICIKT_PERMDISP_MAX_CELLS (16 bytes per cell in the
+ *                  caller's arrays, as many in the library's until the call has succeeded and on the device)
+ *   n_pairs        [2] the values and the NA pairs
+ *   q_total        [2] Q, the sum of q over all values: Q = q_total[1] 2^32 + q_total[0]
+ *   t_lo, t_hi     [n_samp][n_class] row-major: T[i][c] = t_hi[i n_class + c] 2^32 + t_lo[i n_class + c].  THE LIMB RULE
+ *                  of icikt_permanova_f64: 0 <= lo < 2^48 and 0 <= hi < 2^36 here; lo may exceed 2^32
+ * AN NA PAIR adds 0 and the table is returned as summed; n_pairs[1] > 0 tells the caller that no centroid has a
+ * meaning.  n_samp of 0 or 1 gives zero sums; it is no error.
+ * All outputs but max_taumax and reason_counts (as icikt_topk_f64, over all pairs) are required.  A bad n_class, a label
+ * out of range, too many cells, a null output: ICIKT_E_INVALID before anything -- the context or an output -- is
+ * touched.  n_samp <= ICIKT_TOPK_MAX_SAMPLES; n_feat, global_na and the state the call leaves behind (none): as
+ * icikt_topk_f64.  The result is a pure function of the input, whatever the block cut or the grid.
+ * Device memory: the prepared matrix, one block's buffers, 8 bytes per pair of the triangle for the kept keys
+ * (n_samp = 65 535: 17 GB) and 16 n_samp n_class + 4 n_samp bytes of table and labels.
+ * With ICIKT_FLAG_TIMING the keep and the table kernel are accounted under ICIKT_K_EPILOGUE.
+ * icikt_permdisp_in / icikt_permdisp_csc: the same on a typed view / a CSC view of the matrix (below). */
+#define ICIKT_PERMDISP_MAX_CELLS (1ll << 26)
+int icikt_permdisp_f64(icikt_ctx *ctx, const double *X, int64_t n_feat, int64_t n_samp, int64_t ld,
+                       const double *global_na, int n_global_na, int perspective, int alternative, int continuity,
+                       uint32_t flags, const int32_t *cls, int n_class, int64_t *n_pairs, int64_t *q_total,
+                       int64_t *t_lo, int64_t *t_hi, double *max_taumax, int64_t *reason_counts);
+
 /* ---- query samples against a reference cohort: the query x reference rectangle ---------------------------------------
  *
  * Every column of Q (n_feat x n_query, leading dimension ld_query) with every column of R (n_feat x n_reference,
@@ -992,6 +1027,10 @@ int icikt_permanova_in(icikt_ctx *ctx, const icikt_input *X, int64_t n_feat, int
                        const int32_t *cls, int n_class, const int32_t *perm_cls, int64_t n_perm, int64_t *n_pairs,
                        int64_t *q_total, int64_t *bins_lo, int64_t *bins_hi, double *max_taumax,
                        int64_t *reason_counts);
+int icikt_permdisp_in(icikt_ctx *ctx, const icikt_input *X, int64_t n_feat, int64_t n_samp, const double *global_na,
+                      int n_global_na, int perspective, int alternative, int continuity, uint32_t flags,
+                      const int32_t *cls, int n_class, int64_t *n_pairs, int64_t *q_total, int64_t *t_lo,
+                      int64_t *t_hi, double *max_taumax, int64_t *reason_counts);
 int icikt_matrix_in(icikt_ctx *ctx, const icikt_input *X, int64_t n_feat, int64_t n_samp, const double *global_na,
                     int n_global_na, const int32_t *pi, const int32_t *pj, int64_t n_pairs, int perspective,
                     int alternative, int continuity, uint32_t flags, int scale_max, int diag_good, double *out5,
@@ -1080,6 +1119,10 @@ int icikt_permanova_csc(icikt_ctx *ctx, const icikt_csc_input *X, int64_t n_feat
                         uint32_t flags, const int32_t *cls, int n_class, const int32_t *perm_cls, int64_t n_perm,
                         int64_t *n_pairs, int64_t *q_total, int64_t *bins_lo, int64_t *bins_hi, double *max_taumax,
                         int64_t *reason_counts);
+int icikt_permdisp_csc(icikt_ctx *ctx, const icikt_csc_input *X, int64_t n_feat, int64_t n_samp,
+                       const double *global_na, int n_global_na, int perspective, int alternative, int continuity,
+                       uint32_t flags, const int32_t *cls, int n_class, int64_t *n_pairs, int64_t *q_total,
+                       int64_t *t_lo, int64_t *t_hi, double *max_taumax, int64_t *reason_counts);
 int icikt_missingness_csc(icikt_ctx *ctx, const icikt_csc_input *X, int64_t n_feat, int64_t n_samp, const int32_t *pi,
                           const int32_t *pj, int64_t n_pairs, int64_t *missingness);
 int icikt_col_medians_csc(icikt_ctx *ctx, const icikt_csc_input *X, int64_t n_feat, int64_t n_samp,
