@@ -31,8 +31,14 @@
  * reference's own known answers (tests/testthat/test-kendall-tau.R:5-59), its
  * snapshot (tests/testthat/_snaps/kendall-tau.md:1-17), README.md:140-153,255-258
  * and the vignette numbers, via an exact emulation of R's RNG (oracle/rrng.py).
- * Unpinned by any reference fixture (code reading only): Q1 (t0/2), Q2 (int32 wrap),
- * perspective="local" on real data beyond completeness.
+ * Q1 (t0/2), Q2 (int32 wrap) and perspective="local", once held by code reading only,
+ * are pinned by the COMPILED reference: src/kendallc.cpp itself builds against a
+ * stand-in for Rcpp (rcpp_standin/Rcpp.h, ref_wrap.cpp, `make ref`), and
+ * tests/test_oracle_vs_reference.py holds this file to it -- tau, tau_max and
+ * completeness bit for bit, the twelve counts exact, p within 2 E_CPU scaled units --
+ * on a designed lattice; tests/golden/reference_ici_kt.npz carries its answers to
+ * machines without the reference (tests/test_reference_golden.py).  What remains a
+ * reading is the stand-in.
  */
 #include <math.h>
 #include <stdint.h>
