@@ -1,7 +1,7 @@
 """Input matrices whose ICI-Kendall-tau is known in closed form from integers, and the answers of the five selection
-entries (topk, edges, class_medians, class_matrix, quantiles) on them, and of the seven later ones (anosim, permanova,
-padjust's sorted p-values, mst on +-base columns, the rectangle of cross with its top-k and class table; hclust's
-reference is tests/hclust_checker.brute_hclust on Design.raw).  Plain numpy and Python ints: no GPU, no oracle, no S x S
+entries (topk, edges, class_medians, class_matrix, quantiles) on them, and of the eight later ones (anosim, permanova,
+permdisp's table, padjust's sorted p-values, mst on +-base columns, the rectangle of cross with its top-k and class
+table; hclust's reference is tests/hclust_checker.brute_hclust on Design.raw).  Plain numpy and Python ints: no GPU, no oracle, no S x S
 matrix from the library.  Used by tests/test_designed_tau_host.py (against the CPU oracle and the brute-force checkers)
 and by tests/test_gpu_designed_tau.py and tests/test_gpu_designed_tau_entries.py (against the kernels).
 
@@ -424,6 +424,83 @@ def permanova(d, cls, n_class, labellings):
         "class_ss": np.array([pc.to_double(pc.Fraction(a, n * pc.SCALE) if (n and n_na == 0) else None)
                               for a, n in zip(class_q[0], sizes[0])], dtype=np.float64),
     }
+
+
+# ---- permdisp --------------------------------------------------------------------------------------------------------
+
+_PERMDISP_ROWS = 256          # samples summed at a time: planes of [256, S] int64, never [S, S]
+
+
+def _permdisp_sweep(d, cls, n_class):
+    """(t_lo, t_hi [S, n_class] int64, both [2 m + 1] int64: the ordered valid pairs (a, b) per numerator, index
+    num + m).  q is looked up per numerator (q_table; a pair that is not valid looks up one more entry, a 0); the
+    columns are taken class by class (a stable sort of the labels), so one np.add.reduceat over the classes that have a
+    sample sums every cell of a block of rows, whatever n_class is.  A cell has at most S - 1 < 2^16 limbs below 2^32:
+    every sum is below 2^48."""
+    S, m = d.S, d.m
+    cls = np.asarray(cls, dtype=np.int64)
+    assert cls.shape == (S,) and (S == 0 or (cls.min() >= 0 and cls.max() < n_class)) and S < 1 << 16
+    table = [int(v) for v in q_table(d)] + [0]
+    no_value = np.int32(2 * m + 1)
+    limbs = (np.array([v & 0xFFFFFFFF for v in table], dtype=np.int64), np.array([v >> 32 for v in table], dtype=np.int64))
+    order = np.argsort(cls, kind="stable")
+    sizes = np.bincount(cls, minlength=n_class)
+    used = np.nonzero(sizes)[0]
+    starts = (np.cumsum(sizes) - sizes)[used]                        # strictly increasing: reduceat sums whole classes
+    out = (np.zeros((S, n_class), dtype=np.int64), np.zeros((S, n_class), dtype=np.int64))
+    both = np.zeros(2 * m + 2, dtype=np.int64)
+    for a in range(0, S, _PERMDISP_ROWS):
+        rows = slice(a, min(a + _PERMDISP_ROWS, S))
+        k = np.take(np.where(d.valid[rows], d.num[rows] + np.int32(m), no_value), order, axis=1)
+        both += np.bincount(k.ravel(), minlength=2 * m + 2)
+        for limb, t in zip(limbs, out):
+            t[rows, used] = np.add.reduceat(limb.take(k), starts, axis=1)
+    assert all(int(t.max(initial=0)) < 1 << 48 for t in out)
+    return out[0], out[1], both[:2 * m + 1]
+
+
+def permdisp_limbs(d, cls, n_class):
+    """(t_lo, t_hi [S, n_class] int64): per sample i and class c the sums of the low and of the high 32 bits of q over
+    the samples j of class c whose pair with i is valid -- the two planes icikt_permdisp_f64 returns"""
+    return _permdisp_sweep(d, cls, n_class)[:2]
+
+
+def limbs_to_ints(lo, hi):
+    """hi 2^32 + lo as an object array of Python ints; in int64 where that cannot overflow"""
+    if hi.size == 0 or int(hi.max()) < 1 << 30:
+        return ((hi << 32) + lo).astype(object)                      # (below 2^62 + 2^48)
+    return hi.astype(object) * (1 << 32) + lo.astype(object)
+
+
+def permdisp_table(d, cls, n_class):
+    """tests/permdisp_checker.brute_table's tuple (n_values, n_na, Q, T, A, sizes) from the integers; T [S, n_class] is
+    an object array of Python ints where the checker has a list of lists (T.tolist() is that list).  A pair that is
+    not valid adds 0 and counts in n_na, and the table stays AS SUMMED when there is one (PERMANOVA's reference zeroes
+    its class sums then).  Q is the pairs' histogram over the numerators times q_table, apart from the limb planes;
+    A_c is half the sum of column c over the members of c."""
+    S, m = d.S, d.m
+    cls = np.asarray(cls, dtype=np.int64)
+    t_lo, t_hi, both = _permdisp_sweep(d, cls, n_class)               # both: every pair twice, (a, b) and (b, a)
+    T = limbs_to_ints(t_lo, t_hi)
+    table = q_table(d)
+    assert np.all(both % 2 == 0)
+    n_val = int(both.sum()) // 2
+    Q = sum(int(both[v]) // 2 * table[v] for v in np.nonzero(both)[0])
+    assert 2 * Q == (int(t_hi.sum()) << 32) + int(t_lo.sum())        # (the planes' totals: below 2^63 and 2^51)
+    A = [0] * n_class
+    for c in np.unique(cls):
+        twice = int(T[cls == c, c].sum())
+        assert twice % 2 == 0
+        A[int(c)] = twice // 2
+    return n_val, S * (S - 1) // 2 - n_val, Q, T, A, [int(v) for v in np.bincount(cls, minlength=n_class)]
+
+
+def permdisp(d, cls, n_class, labellings):
+    """tests/permdisp_checker.brute_permdisp's dict: permdisp_table, then the checker's own tail (distances by 120-digit
+    square roots, the ANOVA and the permutation test in Fractions)"""
+    from tests.permdisp_checker import permdisp_tail
+    n_val, n_na, Q, T, A, sizes = permdisp_table(d, cls, n_class)
+    return permdisp_tail((n_val, n_na, Q, T.tolist(), A, sizes), cls, n_class, labellings)
 
 
 # ---- p.adjust --------------------------------------------------------------------------------------------------------

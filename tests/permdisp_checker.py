@@ -101,10 +101,17 @@ def brute_table(raw, cls, n_class):
 def brute_permdisp(raw, cls, n_class, perms):
     """A dict of everything icikt_permdisp_f64 and the front end return, from `raw` [S, S], the observed class codes [S],
     n_class and the labellings to compare with [n_perm, S]."""
+    return permdisp_tail(brute_table(raw, cls, n_class), cls, n_class, perms)
+
+
+def permdisp_tail(table, cls, n_class, perms):
+    """brute_permdisp from its table on: `table` is brute_table's tuple (n_values, n_na, Q, T [S][n_class], A [n_class],
+    sizes [n_class]) in Python ints, from whatever summed it (tests/designed_tau.permdisp_table sums it from a design's
+    integers); everything behind it -- the distances, the ANOVA and the permutation test -- is this function's."""
     cls = [int(v) for v in cls]
     S = len(cls)
     perms = [[int(v) for v in row] for row in np.asarray(perms, dtype=np.int64).reshape(-1, S)]
-    n_val, n_na, Q, T, A, sizes = brute_table(raw, cls, n_class)
+    n_val, n_na, Q, T, A, sizes = table
     for c in range(n_class):
         assert 2 * A[c] == sum(T[i][c] for i in range(S) if cls[i] == c)
     used = [c for c in range(n_class) if sizes[c] > 0]

@@ -2,8 +2,9 @@
 oracle BITWISE (both families, both perspectives, with an all-NaN and a constant column), its per-code reason counts
 against the oracle's, and its closed-form answers of the five selection entries against the brute-force checkers fed the
 closed-form matrices.  Below those, the references of the seven later entries (anosim, permanova, padjust, mst, cross and
-its class table) against their checkers at S = 130, and the mutation of hclust's average update that the designs of
-the GPU test must keep showing."""
+its class table) against their checkers at S = 130, permdisp's table and dict against its checker with what the large
+GPU tests presuppose about their inputs, and the mutations that the designs of the GPU tests must keep showing: two
+replayed defects of permdisp's sweep and hclust's contracted average update."""
 import math
 import warnings
 from fractions import Fraction
@@ -21,7 +22,9 @@ from tests.edges_checker import brute_edges
 from tests.medians_checker import brute_medians
 from tests.oracle_engine import OracleEngine
 from tests.quantiles_checker import PROBS, brute_quantiles
+from tests import test_gpu_designed_tau as gpu_base
 from tests.test_gpu_designed_tau import _design as _gpu_design      # the S = 130 designs the GPU tests use
+from tests.test_gpu_designed_tau_entries import _design as _entries_design, _layout as _entries_layout   # and the later ones
 from tests.topk_checker import brute_topk
 
 FAMILIES = {"swaps": dt.swaps, "reversals": dt.reversals}
@@ -306,6 +309,126 @@ def test_rectangle_against_the_checkers(key, perspective):
     assert np.array_equal(cm["n_valid"], n_valid)
     assert np.array_equal(bits(cm["med"]), bits(med2[1])) and np.array_equal(bits(cm["med"]), bits(med2[0]))
     assert np.all(n_valid[:, [2, 4]] == 0) and np.all(bits(cm["med"][:, [2, 4]]) == dt.NA_REAL_BITS)
+
+
+# ---- permdisp: the reference against the checker, what the GPU tests presuppose, and two defects replayed --------------
+
+@pytest.mark.parametrize("classes", ["interleaved", "na-class"])
+@pytest.mark.parametrize("na", [True, False])
+@pytest.mark.parametrize("key", KEYS130)
+def test_permdisp_against_the_checker(key, na, classes):
+    from tests import permdisp_checker
+    d = _entries_design(key if na else key + "/valid")
+    cls, n_class = _entries_layout(d, key if na else key + "/valid", classes)
+    perms = permdisp_checker.documented_permutations(cls, 7, seed=11)
+    n_val, n_na, Q, T, A, sizes = dt.permdisp_table(d, cls, n_class)
+    want = permdisp_checker.brute_table(d.raw, cls, n_class)
+    assert T.dtype == object and T.shape == (d.S, n_class) and all(type(v) is int for v in T.ravel())
+    assert (n_val, n_na, Q, T.tolist(), A, sizes) == want
+    assert (n_na > 0) == na and Q > 0 and all(type(v) is int for v in [n_val, n_na, Q] + A + sizes)
+    lo, hi = dt.permdisp_limbs(d, cls, n_class)
+    assert lo.dtype == hi.dtype == np.int64 and np.array_equal(dt.limbs_to_ints(lo, hi), T)
+    got, ref = dt.permdisp(d, cls, n_class, perms), permdisp_checker.brute_permdisp(d.raw, cls, n_class, perms)
+    assert set(got) == set(ref)
+    for name in got:
+        if name not in ("exact", "x", "residuals"):
+            _same_item(got[name], ref[name], name)
+    assert got["exact"] == ref["exact"] and got["x"] == ref["x"] and (na or got["residuals"] == ref["residuals"])
+    assert (ref["exact"][0][0] is None) == na
+    pv = dt.permanova(d, cls, n_class, perms)
+    assert Q == pv["q_total"] and np.array_equal(pv["n_pairs"], [n_val, n_na])
+    if na:   # the table is as summed; PERMANOVA's class sums are not
+        assert any(A) and not any(pv["class_q"][0]) and T[d.kind == dt.VALID].any() and not T[d.kind != dt.VALID].any()
+    else:
+        assert A == pv["class_q"][0]
+
+
+def test_the_inputs_of_the_large_permdisp_tests_are_what_they_presuppose():
+    from tests.test_gpu_medians import _five_classes
+    d = _entries_design("rev24-5794")
+    cls, n_class = _five_classes(d.S)
+    lo, hi = dt.permdisp_limbs(d, cls, n_class)
+    good = d.kind == dt.VALID
+    print("cells of valid samples", lo[good].size, "lo-limb sums from", int(lo[good].min()).bit_length(), "to",
+          int(lo.max()).bit_length(), "bits, hi up to", int(hi.max()).bit_length(), "bits")
+    assert good.sum() == d.S - 2 and lo[good].min() >= 1 << 32 and not lo[~good].any() and not hi[~good].any()
+    assert lo.max() < 1 << 48 and hi.max() < 1 << 36                                  # icikt_permdisp.hip's bounds
+    d = _entries_design("halves-2049")
+    T = dt.permdisp_table(d, np.zeros(d.S, dtype=np.int32), 1)[3]
+    assert T[:1024, 0].tolist() == [1025 << 52] * 1024 and T[1024:, 0].tolist() == [1024 << 52] * 1025
+
+
+def _lost_carry(d, cls, n_class):
+    """a cell's lo limb kept modulo 2^32"""
+    lo, hi = dt.permdisp_limbs(d, cls, n_class)
+    return lo & 0xFFFFFFFF, hi
+
+
+def _column_role_one_to_the_right(d, cls, n_class):
+    """k_disp_table's column role (the partners t < s of sample s) reading the pair (t, s + 1) in place of (t, s): the
+    next key of row t in the kept plane -- behind the row's last pair (s = S - 1) that is the first pair of row t + 1,
+    (t + 1, t + 2), and behind the plane nothing (no value).  The row role (t > s) is as it was.  The sweep is
+    dt.permdisp_limbs on the planes so read."""
+    import copy
+    S = d.S
+    num, valid = d.num.copy(), d.valid.copy()
+    low = np.tril(np.ones((S, S), dtype=bool), -1)
+    for plane, src in ((num, d.num), (valid, d.valid)):
+        below = np.empty_like(src)
+        below[:-1] = src[1:]                                           # [s, t] <- [s + 1, t] == (t, s + 1)
+        below[-1] = 0
+        below[-1, :S - 2] = src[np.arange(1, S - 1), np.arange(2, S)]  # [S - 1, t] <- (t + 1, t + 2)
+        plane[low] = below[low]
+    read = copy.copy(d)
+    read.num, read.valid = num, valid
+    return dt.permdisp_limbs(read, cls, n_class)
+
+
+def _cells(lo, hi):
+    """hi 2^32 + lo in int64: the designs' hi sums stay below 2^31 - 2^16 (1 025 x 2^20 is the largest)"""
+    assert hi.max() < (1 << 31) - (1 << 16) and lo.max() < 1 << 48
+    return (hi << 32) + lo
+
+
+def _replay_labels(key):
+    from tests.test_gpu_designed_tau_entries import PMV_LDS_CLASSES, _classes_of_two
+    from tests.test_gpu_medians import _five_classes
+    d = _entries_design(key)
+    if d.S == 130:
+        return _entries_layout(d, key, "interleaved")
+    if key == "halves-2049":
+        return (np.arange(d.S) >= 1024).astype(np.int32), 2
+    if key == "rev24-4098":
+        return _classes_of_two(d.S, PMV_LDS_CLASSES), PMV_LDS_CLASSES
+    return _five_classes(d.S)
+
+
+REPLAY_DESIGNS = KEYS130 + ["rev24-2049", "halves-2049", "rev24-4098", "rev24-5794"]
+
+
+@pytest.mark.parametrize("key", REPLAY_DESIGNS)
+def test_two_replayed_permdisp_defects_show_on_the_designs(key):
+    """The guard that the designs of the GPU tests can see (a) a carry lost between a cell's limbs and (b) a column
+    role that reads its neighbour's pair.  (a) cannot show where every q is 0 or 2^52 (lo limb 0); (b) cannot show in a
+    row of a two-valued design whose neighbour has the same sign and kind.  That is why every size also runs a design
+    of prefix reversals, on which both change most rows of the table."""
+    d = _entries_design(key)
+    cls, n_class = _replay_labels(key)
+    lo, hi = dt.permdisp_limbs(d, cls, n_class)
+    T, carry, shifted = (_cells(*planes) for planes in ((lo, hi), _lost_carry(d, cls, n_class),
+                                                         _column_role_one_to_the_right(d, cls, n_class)))
+    rows_carry = np.nonzero((carry != T).any(axis=1))[0]
+    rows_shift = np.nonzero((shifted != T).any(axis=1))[0]
+    print(key, "rows of the table that change: lost carry", len(rows_carry), "column role", len(rows_shift), "of", d.S)
+    if dt.is_two_valued(d):
+        assert len(rows_carry) == 0 and not lo.any()
+        nxt = np.arange(d.S) + 1
+        may = (nxt == d.S) | (d.sign != d.sign[np.minimum(nxt, d.S - 1)]) | (d.kind != d.kind[np.minimum(nxt, d.S - 1)])
+        assert len(rows_shift) > 0 and may[rows_shift].all() and not may.all()
+    else:
+        assert len(rows_carry) > d.S // 2 and len(rows_shift) > d.S // 2
+    if key in ("rev24-4098", "rev24-5794"):
+        gpu_base._DESIGN.pop(key, None)                               # (a third of a gigabyte; the GPU tests build it again)
 
 
 # ---- a mutation that must keep failing: average linkage with one product fused into the sum --------------------------

@@ -1,5 +1,5 @@
-"""The seven later selection entries (padjust, mst, hclust, anosim, cross, the prepared reference with its class table,
-permanova) on designed matrices whose ICI-Kendall-tau is known in closed form from integers (tests/designed_tau.py).
+"""The eight later selection entries (padjust, mst, hclust, anosim, cross, the prepared reference with its class table,
+permanova, permdisp) on designed matrices whose ICI-Kendall-tau is known in closed form from integers (tests/designed_tau.py).
 Their own test files feed a brute-force checker with Context.matrix or Context.cross of the same input: the library is
 its own source of values there, on Gaussian columns whose tau clusters round 0.  Here the reference needs no S x S matrix
 from the library, so it reaches the key space (raw = -1 and +1, runs of thousands of equal keys), the accumulator bounds
@@ -46,6 +46,7 @@ def _plus_minus(S, n, seed, split=None):
 _MORE = {
     "rev24-520": lambda: dt.reversals(520, 24, seed=3),
     "rev24-2051": lambda: dt.reversals(2051, 24, seed=3),
+    "rev24-4100": lambda: dt.reversals(4100, 24, seed=8),
     "rev24-5795": lambda: dt.reversals(5795, 24, seed=5),
     # three prefix lengths (the whole column reversed is the base with the other sign) and two signs: four values of
     # raw, each shared by a thousand or more of a query's partners
@@ -83,6 +84,24 @@ def _layout(d, key, classes):
         cls, n_class = _classes(full, classes)
         return np.ascontiguousarray(cls[full.kind == dt.VALID]), n_class
     return _classes(d, classes)
+
+
+def _classes_of_two(S, n_class, seed=12):
+    """a seeded permutation of repeat(arange(n_class), 2); where 2 n_class < S the samples left over go one each to
+    the first classes (S = 4 098 with 2 048 classes: two classes of three)"""
+    assert 0 <= S - 2 * n_class <= n_class
+    labels = np.concatenate([np.repeat(np.arange(n_class), 2), np.arange(S - 2 * n_class)])
+    return np.random.default_rng(seed).permutation(labels).astype(np.int32)
+
+
+THREE_OF_2049 = (0, 1000, 2048)
+
+
+def _three_labels(S, layout):
+    """the labels of 2 049 declared classes of which three have samples: "sorted" into three blocks, or interleaved"""
+    used = np.array(THREE_OF_2049, dtype=np.int32)
+    assert S % 3 == 0
+    return np.repeat(used, S // 3) if layout == "sorted" else np.ascontiguousarray(used[np.arange(S) % 3])
 
 
 # ---- anosim and permanova --------------------------------------------------------------------------------------------
@@ -164,6 +183,138 @@ def test_permanova_under_another_plan(plan_ctx, key):
     ref = _ref(("permanova", key, "interleaved"), lambda: dt.permanova(d, cls, n_class, perms))
     plan_ctx.debug_set_plan("anostrip=64,anoperms=3,tkblock=1")
     _assert_permanova(plan_ctx.permanova(d.X, cls, n_class, perms), ref, d)
+
+
+# ---- permdisp --------------------------------------------------------------------------------------------------------
+
+def _assert_permdisp(got, ref, d, key=None):
+    """Context.permdisp's five items against dt.permdisp_table's tuple: the two tables are object arrays of Python ints
+    and are compared in one call.  key: the design's, to count its reasons once for all the tests that use it."""
+    n_pairs, Q, T, mx, rc5 = got
+    n_val, n_na, Q_ref, T_ref, _A, _sizes = ref
+    same = T == T_ref if T.shape == T_ref.shape else np.zeros(1, dtype=bool)
+    print("values, n_na", n_pairs.tolist(), [n_val, n_na], "Q", Q, Q_ref, "cells", T.size, "non-zero", int(np.count_nonzero(T_ref)),
+          "differing cells", int(same.size - np.count_nonzero(same)))
+    assert n_pairs.dtype == np.int64 and n_pairs.tolist() == [n_val, n_na]
+    assert isinstance(Q, int) and Q == Q_ref
+    assert T.dtype == object and T_ref.dtype == object and set(map(type, T.ravel())) <= {int}
+    assert T.shape == T_ref.shape and same.dtype == bool and same.all()
+    want_rc5 = d.reason_counts() if key is None else _ref(("reason_counts", key), d.reason_counts)
+    assert mx == d.max_taumax() and np.array_equal(rc5, want_rc5)
+
+
+def _na_rows_are_zero(d, ref, got):
+    """with NA columns: their rows of the table are all zero -- the all-missing column's and the constant one's --, every
+    other row is as summed, and n_na is the pairs that an NA column is part of"""
+    k = int(np.sum(d.kind != dt.VALID))
+    good = d.kind == dt.VALID
+    assert k > 0 and (d.kind == dt.ALL_MISSING).any()
+    assert ref[1] == d.S * (d.S - 1) // 2 - (d.S - k) * (d.S - k - 1) // 2 == got[0][1]
+    for T in (ref[3], got[2]):
+        assert not T[~good].any() and all(row.any() for row in T[good])
+    assert ref[2] > 0
+
+
+@pytest.mark.parametrize("classes", ["interleaved", "na-class"])
+@pytest.mark.parametrize("key", [k + v for k in KEYS130 for v in ("/valid", "")])
+def test_permdisp(hip_ctx, key, classes):
+    """"/valid": no NA pair; the whole design has NA columns, and the table is as summed all the same (PERMANOVA's class
+    sums are zero there)"""
+    d = _checked(hip_ctx, key)
+    cls, n_class = _layout(d, key, classes)
+    ref = _ref(("permdisp", key, classes), lambda: dt.permdisp_table(d, cls, n_class))
+    assert ref[5][2] == (0 if key.endswith("/valid") or classes == "interleaved" else int(np.sum(d.kind != dt.VALID)))
+    assert not ref[3][:, [c for c in range(n_class) if ref[5][c] == 0]].any()          # an empty class: 0 for every sample
+    if key.startswith("two-valued"):          # only q = 0 and q = 2^52 are summed: every cell counts its raw = -1 partners
+        table = dt.q_table(d)
+        assert table[0] == 1 << 52 and table[2 * d.m] == 0 and all(v % (1 << 52) == 0 for v in ref[3].ravel())
+        assert max(ref[3].ravel()) >= 20 << 52
+    for perspective in PERSPECTIVES:
+        got = hip_ctx.permdisp(d.X, cls, n_class, None, perspective)
+        _assert_permdisp(got, ref, d)
+        if key.endswith("/valid"):
+            assert ref[1] == 0 and got[0][1] == 0 and all(row.any() for row in got[2])
+        else:
+            _na_rows_are_zero(d, ref, got)
+
+
+@pytest.mark.parametrize("spec", ["tkblock=1", "tkblock=1000"])
+@pytest.mark.parametrize("key", ["two-valued", "reversals41-wide/valid"])
+def test_permdisp_under_another_plan(plan_ctx, key, spec):
+    """tkblock=1: the kept plane is written by one block of the triangle per row"""
+    d = _checked(plan_ctx, key, ("global",))
+    cls, n_class = _layout(d, key, "interleaved")
+    ref = _ref(("permdisp", key, "interleaved"), lambda: dt.permdisp_table(d, cls, n_class))
+    plan_ctx.debug_set_plan(spec)
+    _assert_permdisp(plan_ctx.permdisp(d.X, cls, n_class), ref, d)
+
+
+def _front_end(d, cls, n_perm=33, seed=13):
+    """api.ici_kendalltau_permdisp on the design with the labels "c<class>", its warnings, and the codes the front end
+    gives those labels: the classes that have a sample, renumbered in order"""
+    import warnings
+    from icikendalltau_amd import api
+    levels, codes = np.unique(cls, return_inverse=True)
+    assert len(levels) <= 10                               # (the labels sort as the classes do)
+    with warnings.catch_warnings(record=True) as w:
+        warnings.simplefilter("always")
+        got = api.ici_kendalltau_permdisp(d.X, ["c%d" % c for c in cls], permutations=n_perm, seed=seed,
+                                          colnames=["s%d" % i for i in range(d.S)])
+    assert got["class_levels"] == ["c%d" % c for c in levels] and got["n_permutations"] == n_perm
+    return got, [str(x.message) for x in w], codes.astype(np.int32), len(levels)
+
+
+def _assert_front_end(got, ref, d):
+    from tests.test_gpu_permdisp import _assert_front
+    _assert_front(got, (None, d.max_taumax(), None), ref)
+
+
+@pytest.mark.parametrize("key", [k + "/valid" for k in KEYS130])
+def test_permdisp_front_end(hip_ctx, key):
+    """no NA pair: the statistic is defined (the checker's F on the five designs: 94.94, 51.18, 31.61, 15.14, 16.995)"""
+    d = _checked(hip_ctx, key, ("global",))
+    cls, _n = _layout(d, key, "interleaved")
+    got, warned, codes, n_class = _front_end(d, cls)
+    ref = _ref(("permdisp front", key), lambda: dt.permdisp(d, codes, n_class, documented_permutations(codes, 33, 13)))
+    print(key, "F", ref["statistic"], "p", ref["pvalue"], "n_ge", ref["n_ge"], "n_negative", ref["n_negative"])
+    assert ref["n_pairs"][1] == 0 and ref["exact"][0][0] is not None and np.isfinite(ref["statistic"]) and ref["statistic"] > 10
+    assert ref["n_undefined"] == 0 and (ref["df_among"], ref["df_within"]) == (4, d.S - 5)
+    assert not any("PERMDISP needs every pair" in m for m in warned)
+    _assert_front_end(got, ref, d)
+
+
+def test_permdisp_front_end_with_na_columns(hip_ctx):
+    key = "reversals41"
+    d = _checked(hip_ctx, key, ("global",))
+    cls, _n = _layout(d, key, "interleaved")
+    got, warned, codes, n_class = _front_end(d, cls)
+    ref = dt.permdisp(d, codes, n_class, documented_permutations(codes, 33, 13))
+    assert ref["n_pairs"][1] > 0 and sum(1 for m in warned if "PERMDISP needs every pair" in m) == 1
+    _assert_front_end(got, ref, d)
+    from tests.test_gpu_permdisp import FLOATS
+    for name in FLOATS:
+        assert np.all(bits(got[name]) == NA), name
+    assert np.all(got["nearest_centroid"] == -1) and got["n_undefined"] == 33 and got["n_ge"] == 0 and got["n_negative"] == 0
+    assert got["sums"]["t"].any() and not got["sums"]["t"][d.kind != dt.VALID].any()    # the table is as summed
+
+
+def test_permdisp_front_end_when_every_own_class_distance_is_zero(hip_ctx):
+    """two-valued-half/valid with the column's sign as its class: every raw inside a class is +1, q = 0, so every sample
+    sits on its own class's centroid; F is NA ("all values equal") for the observed labelling and every permutation"""
+    key = "two-valued-half/valid"
+    d = _checked(hip_ctx, key, ("global",))
+    cls = (d.sign < 0).astype(np.int32)
+    assert dt.is_two_valued(d) and 0 < cls.sum() < d.S
+    got, warned, codes, n_class = _front_end(d, cls)
+    assert n_class == 2 and np.array_equal(codes, cls) and not any("PERMDISP needs every pair" in m for m in warned)
+    ref = dt.permdisp(d, codes, n_class, documented_permutations(codes, 33, 13))
+    assert ref["n_pairs"][1] == 0 and ref["class_q"] == [0, 0] and all(row[c] == 0 for row, c in zip(ref["t"], cls))
+    assert np.all(bits(ref["distances"]) == 0) and ref["exact"][0][0] is None and bits(ref["statistic"])[0] == NA
+    assert ref["n_undefined"] == 33 and ref["n_negative"] == 0 and ref["n_ge"] == 0
+    assert all(row[1 - c] == ref["class_size"][1 - c] << 52 for row, c in zip(ref["t"], cls))   # raw = -1 with the other class
+    _assert_front_end(got, ref, d)
+    assert got["n_undefined"] == got["n_permutations"] == 33 and got["n_negative"] == 0
+    assert np.all(bits(got["distances"]) == 0) and bits(got["statistic"])[0] == NA
 
 
 # ---- padjust ---------------------------------------------------------------------------------------------------------
@@ -579,7 +730,26 @@ def test_5795_samples_permanova(hip_ctx, monkeypatch):
     ref = _timed("S=5795 permanova, the reference", lambda: dt.permanova(d, cls, n_class, perms))
     assert ref["n_pairs"][1] == 0 and all(all(row) for row in ref["class_q"])
     _assert_permanova(_timed("S=5795 permanova", lambda: hip_ctx.permanova(d.X, cls, n_class, perms)), ref, d)
+
+
+def test_5795_samples_permdisp(hip_ctx, monkeypatch):
+    """no NA column.  The same plane and the same q as PERMANOVA's: n_pairs and Q are its, and A_c = 1/2 sum_{i in c}
+    T[i][c] is its class sum of the observed labelling"""
+    _no_plan_override(monkeypatch)
+    d = _checked(hip_ctx, "rev24-5795", ("global",))
+    _cut_in_two(d)
+    cls, n_class = _five_classes(d.S)
+    ref = _timed("S=5795 permdisp, the reference", lambda: dt.permdisp_table(d, cls, n_class))
+    assert ref[1] == 0 and all(ref[4]) and all(row.all() for row in ref[3])
+    got = _timed("S=5795 permdisp", lambda: hip_ctx.permdisp(d.X, cls, n_class))
+    _assert_permdisp(got, ref, d, "rev24-5795")
+    p_pairs, p_Q, p_class_q, _mx, _rc5 = _timed("S=5795 permanova, observed labelling",
+                                                lambda: hip_ctx.permanova(d.X, cls, n_class, None))
+    assert np.array_equal(got[0], p_pairs) and got[1] == p_Q
+    twice = [sum(got[2][cls == c, c]) for c in range(n_class)]
+    assert all(v % 2 == 0 for v in twice) and [v // 2 for v in twice] == list(p_class_q[0]) == ref[4]
     base._DESIGN.pop("rev24-5795")
+    _REF.pop(("reason_counts", "rev24-5795"), None)
 
 
 def test_5794_samples_mst(hip_ctx, monkeypatch):
@@ -592,3 +762,120 @@ def test_5794_samples_mst(hip_ctx, monkeypatch):
     assert ref[3] == 1 and int(np.sum(d.num[ref[0], ref[1]] < 0)) == 1
     _assert_mst(hip_ctx, _timed("S=5794 mst", lambda: hip_ctx.mst(d.X)), ref, d)
     base._DESIGN.pop("plus-minus-5794")
+
+
+# ---- permdisp at those sizes: k_disp_table's partner loop, its two bin paths, the wave's shortcut and the block cut -------
+
+def _permdisp_at_size(ctx, key, cls, n_class, label, check=None):
+    """the reference, `check` on the reference BEFORE the library is called, the call, the comparison"""
+    d = _design(key)
+    ref = _timed(label + ", the reference", lambda: dt.permdisp_table(d, cls, n_class))
+    if check is not None:
+        check(ref)
+    got = _timed(label, lambda: ctx.permdisp(d.X, cls, n_class))
+    _assert_permdisp(got, ref, d, key)
+    return got, ref
+
+
+def test_2049_samples_permdisp_with_na_columns(hip_ctx, monkeypatch):
+    """nine trips of k_disp_table's loop over 256 partners, the last with one; an all-missing and a constant column"""
+    _no_plan_override(monkeypatch)
+    d = _checked(hip_ctx, "rev24-2049", ("global",))
+    assert -(-d.S // 256) == 9 and sorted(d.kind[d.kind != dt.VALID].tolist()) == [dt.ALL_MISSING, dt.CONSTANT]
+    cls, n_class = _five_classes(d.S)
+    got, ref = _permdisp_at_size(hip_ctx, "rev24-2049", cls, n_class, "S=2049 permdisp, NA columns")
+    assert ref[1] == 2 * d.S - 3
+    _na_rows_are_zero(d, ref, got)
+
+
+@pytest.mark.parametrize("labels", ["one", "two-sorted", "two-interleaved"])
+def test_2049_samples_permdisp_at_the_wave_bound(hip_ctx, monkeypatch, labels):
+    """Columns 0 ... 1 023 are +base, the 1 025 others -base: raw = -1 across, q = 2^52, hi limb 2^20 and lo limb 0.
+    Class-sorted (one class, or two split at 1 024 = 16 waves) every full wave of partners holds one class and takes the
+    shortcut: a wave of 64 partners of the other sign sums hi to 64 x 2^20 = 2^26, the bound of a wave's sum written
+    at the top of icikt_permdisp.hip, with equality.  Interleaved, every wave holds both classes and each lane adds its
+    own limbs: the same matrix through the other path."""
+    _no_plan_override(monkeypatch)
+    d = _checked(hip_ctx, "halves-2049", ("global",))
+    S, cut = d.S, 1024
+    table = dt.q_table(d)
+    assert table[0] == 1 << 52 and table[2 * d.m] == 0 and np.all(d.num[:cut, cut:] == -d.m)
+    assert np.all(d.num[:cut, :cut][~np.eye(cut, dtype=bool)] == d.m)
+    assert 64 * (table[0] >> 32) == 1 << 26 and table[0] & 0xFFFFFFFF == 0 and cut % 64 == 0           # a full wave's hi sum
+    cls = {"one": np.zeros(S, dtype=np.int32), "two-sorted": (np.arange(S) >= cut).astype(np.int32),
+           "two-interleaved": (np.arange(S) % 2).astype(np.int32)}[labels]
+    n_class = 1 if labels == "one" else 2
+
+    def check(ref):
+        T = ref[3]
+        lo, hi = dt.permdisp_limbs(d, cls, n_class)
+        assert not lo.any() and ref[1] == 0 and ref[2] == cut * (S - cut) << 52
+        if labels == "one":
+            assert all(T[i, 0] == (S - cut) << 52 for i in range(cut)) and all(T[i, 0] == cut << 52 for i in range(cut, S))
+        elif labels == "two-sorted":        # a + sample's cell of the - class, and the other way round; the own class: 0
+            assert all(T[i, 1] == 1025 << 52 and T[i, 0] == 0 for i in range(cut))
+            assert all(T[i, 0] == 1024 << 52 and T[i, 1] == 0 for i in range(cut, S))
+            assert np.all(hi[:cut, 1] == 1025 << 20) and ref[4] == [0, 0]
+        else:                               # per class the partners of the other sign, 512 or 513 of them
+            other = np.array([[np.sum(cls[cut:] == c) for c in (0, 1)], [np.sum(cls[:cut] == c) for c in (0, 1)]])
+            assert np.array_equal(T, (other[(np.arange(S) >= cut).astype(int)]).astype(object) * (1 << 52))
+            assert sorted(other.ravel().tolist()) == [512, 512, 512, 513]
+
+    _permdisp_at_size(hip_ctx, "halves-2049", cls, n_class, "S=2049 permdisp at a wave's 2^26, " + labels, check)
+
+
+@pytest.mark.parametrize("key,n_class", [("rev24-4098", PMV_LDS_CLASSES), ("rev24-4100", PMV_LDS_CLASSES + 2)])
+def test_permdisp_either_side_of_the_classes_that_fit_in_lds(hip_ctx, monkeypatch, key, n_class):
+    """Classes of two samples (S = 4 098: two of three).  2 048 classes: the bins fill k_disp_table's 32 KB of LDS;
+    2 050: they are the sample's own row of the table in global memory, added to with global atomics.  17 trips of the
+    partner loop, and rows of the triangle thousands of pairs apart in the column role."""
+    _no_plan_override(monkeypatch)
+    d = _checked(hip_ctx, key, ("global",))
+    assert (n_class <= PMV_LDS_CLASSES) == (key == "rev24-4098") and (d.kind == dt.VALID).all()
+    cls = _classes_of_two(d.S, n_class)
+    sizes = np.bincount(cls, minlength=n_class)
+    assert sizes.min() == 2 and sizes.max() == (3 if key == "rev24-4098" else 2)
+
+    def check(ref):
+        table = dt.q_table(d)
+        assert ref[1] == 0 and np.count_nonzero(ref[3]) > 0.9 * ref[3].size
+        pairs = [np.nonzero(cls == c)[0] for c in range(n_class) if sizes[c] == 2]
+        assert [ref[4][c] for c in range(n_class) if sizes[c] == 2] == [int(table[d.num[a, b] + d.m]) for a, b in pairs]
+
+    _permdisp_at_size(hip_ctx, key, cls, n_class, "S=%d permdisp, %d classes" % (d.S, n_class), check)
+    if key == "rev24-4100":
+        base._DESIGN.pop(key)
+        _REF.pop(("reason_counts", key), None)
+
+
+@pytest.mark.parametrize("layout", ["sorted", "interleaved"])
+def test_4098_samples_permdisp_global_bins_that_accumulate(hip_ctx, monkeypatch, layout):
+    """2 049 declared classes, so the bins are in global memory, and three of them used by 1 366 samples each: a cell
+    collects up to 1 366 values through global atomics (a class of two samples gets at most two).  Sorted into three
+    blocks, the waves of one class add their sums with one atomic per limb; interleaved, every lane adds its own."""
+    _no_plan_override(monkeypatch)
+    d = _checked(hip_ctx, "rev24-4098", ("global",))
+    n_class = PMV_LDS_CLASSES + 1
+    cls = _three_labels(d.S, layout)
+    assert np.bincount(cls, minlength=n_class)[list(THREE_OF_2049)].tolist() == [1366] * 3
+
+    def check(ref):
+        lo, hi = dt.permdisp_limbs(d, cls, n_class)
+        used = lo[:, list(THREE_OF_2049)]
+        print("lo-limb sums of the used cells: min", int(used.min()).bit_length(), "max", int(used.max()).bit_length(), "bits")
+        assert used.min() >= 1 << 32 and ref[1] == 0                   # every used cell carries out of 32 bits
+        assert np.count_nonzero(lo) == np.count_nonzero(hi) == 3 * d.S
+
+    got, _ref_ = _permdisp_at_size(hip_ctx, "rev24-4098", cls, n_class, "S=4098 permdisp, 3 of 2049 classes, " + layout, check)
+    assert np.count_nonzero(got[2]) == 3 * d.S and got[2][:, list(THREE_OF_2049)].all()     # an unused class: 0 in every row
+
+
+def test_5794_samples_permdisp_with_na_columns(hip_ctx, monkeypatch):
+    """the kept plane written by two blocks of the triangle; 23 trips of the partner loop; NA columns"""
+    _no_plan_override(monkeypatch)
+    d = _checked(hip_ctx, "rev24-5794", ("global",))
+    total = _cut_in_two(d)
+    cls, n_class = _five_classes(d.S)
+    got, ref = _permdisp_at_size(hip_ctx, "rev24-5794", cls, n_class, "S=5794 permdisp, NA columns")
+    assert ref[0] + ref[1] == total and ref[1] == 2 * d.S - 3
+    _na_rows_are_zero(d, ref, got)
