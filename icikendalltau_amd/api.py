@@ -1017,7 +1017,7 @@ class PreparedReference:
             idx, vals, n_valid = _cross_topk_numpy(out5, k)
         if want_classes:
             med2, cls_n_valid = _cross_class_numpy(out5[0], out5[1], self.class_codes, n_class)
-        return out5, idx, vals, n_valid, max_taumax, med2, cls_n_valid, t_diff
+        return out5 if want_matrix else None, idx, vals, n_valid, max_taumax, med2, cls_n_valid, t_diff
 
 
 def _rcounts_last(items):
@@ -1075,10 +1075,24 @@ def _cross_prepared(query, prepared, k, return_matrix, perspective, scale_max, a
                     if planes is not None:
                         ok = ~np.isnan(planes[1][rows])
                         planes[0][rows][ok] = planes[1][rows][ok] / max_taumax
-                if classes:   # an odd cell's median is one pair's cor; an even cell's two quotients are not kept
+                if classes:   # an odd cell's median is one pair's cor; an even cell's two quotients are not kept:
+                    # its median is reduced again, on the host, from the part's raw (asked for if the call kept none)
                     odd, even = (cls_n_valid[rows] & 1) == 1, (cls_n_valid[rows] > 0) & ((cls_n_valid[rows] & 1) == 0)
                     med2[0][rows][odd] = med2[1][rows][odd] / max_taumax + 0.0
-                    med2[0][rows][even] = med2[0][rows][even] * (p[4] / max_taumax)
+                    if even.any():
+                        part5 = p[0]
+                        if part5 is None:   # (its pairs were warned about the first time; the five planes of this
+                            with warnings.catch_warnings():   # one part exist only until its even cells are reduced)
+                                warnings.simplefilter("ignore")
+                                again = prepared._batch(query[:, a:a + w], None, True, False, perspective, False,
+                                                        alternative, continuity)
+                            part5, t_diff = again[0], t_diff + again[7]
+                        part_raw = np.ascontiguousarray(part5[1], dtype=np.float64)
+                        part_cor, ok = np.full(part_raw.shape, np.nan), ~np.isnan(part_raw)
+                        part_cor[ok] = part_raw[ok] / max_taumax
+                        host = _cross_class_numpy(part_cor, part_raw, prepared.class_codes,
+                                                  len(prepared.class_levels))[0]
+                        med2[0][rows][even] = host[0][even]
             a += w
     return out5, idx, vals, n_valid, max_taumax, med2, cls_n_valid, t_diff
 
@@ -1105,9 +1119,9 @@ def ici_kendalltau_cross(query, reference, k=None, return_matrix=True, global_na
     then its own -- ``reference_names`` and ``reference_classes`` are refused, and so is a ``global_na`` that differs
     from the one it was prepared with -- and only the batch crosses to the device.  A batch wider than its
     ``query_capacity`` is split into capacity-sized calls and stitched; with ``scale_max`` ``cor`` is then scaled again,
-    from ``raw``, by the largest ``max_taumax`` of the parts, and ``class_med_cor`` likewise (an even cell's value by
-    the ratio of the two scales, which can differ from an unsplit call's in the last bit).  Everything derived from
-    ``raw`` alone -- ``raw``, ``pvalue``, ``taumax``, ``completeness``, the top-k selection, ``class_med_raw``,
+    from ``raw``, by the largest ``max_taumax`` of the parts, and ``class_med_cor`` likewise (an even cell's median is
+    reduced again on the host from the part's ``raw``), so a split call gives an unsplit call's bits.  Everything derived
+    from ``raw`` alone -- ``raw``, ``pvalue``, ``taumax``, ``completeness``, the top-k selection, ``class_med_raw``,
     ``class_n_valid``, ``nearest_class`` -- does not depend on the split.
 
     ``reference_classes`` (one label per reference column; with a plain matrix the reference is prepared for this one

@@ -17,8 +17,15 @@ taumax = 1 for every pair, so cor == raw bit for bit and max_taumax == 1.0.  An 
 (reason 1, all missing), a constant column with every other partner (reason 3, a single unique value); the other pairs
 are untouched by them.
 
-All ordering and counting is done on the integers num, where ties are exact; a float appears only as num / m, or as
-R's mean() / quantile(type = 7) of two such values (tests/medians_checker.r_mean2, tests/quantiles_checker.type7)."""
+A third family, `censored` (class Censored, which has the formulas): tied, left-censored columns, on which taumax,
+completeness and max_taumax differ from 1 and from each other, cor from raw, and "local" from "global".  There
+raw = num / den and taumax = plus / den with a den that varies per pair under "local".
+
+All ordering and counting is done on integers, where ties are exact: Design.key, which is num itself on swaps and
+reversals and the exact dense rank of |num| / den, signed, on the censored family; Design.value(key) is the float64
+raw.  A float appears only as that one division, as one more division by an entry's max_taumax (cor), or as R's mean()
+/ quantile(type = 7) of two such values (tests/medians_checker.r_mean2, tests/quantiles_checker.type7)."""
+import dataclasses
 import math
 
 import numpy as np
@@ -47,16 +54,36 @@ class Design:
     column; raw [S, S] float64: num / m, NaN where not valid."""
 
     def __init__(self, family, X, kind, sign, disc, param):
-        self.family, self.X, self.kind, self.sign, self.disc, self.param = family, X, kind, sign, disc, param
-        self.n, self.S = X.shape
-        self.m = self.n * (self.n - 1) // 2
+        self.family, self.sign, self.disc, self.param = family, sign, disc, param
+        self._set_columns(X, kind)
         d, s = disc.astype(np.int32), sign.astype(np.int32)           # (every operand stays below 2^11)
         num = (np.int32(self.m) - 2 * np.abs(d[:, None] - d[None, :])) * s[:, None] * s[None, :]
+        self.num = np.where(self.valid, num, np.int32(0))
+
+    def _set_columns(self, X, kind):
+        """what every family shares: X, kind, n, S, m, valid, and the caches of raw and of the triangle"""
+        self.X, self.kind = X, kind
+        self.n, self.S = X.shape
+        self.m = self.n * (self.n - 1) // 2
         ok = kind == VALID
         self.valid = ok[:, None] & ok[None, :]
         np.fill_diagonal(self.valid, False)
-        self.num = np.where(self.valid, num, np.int32(0))
-        self._raw = None
+        self._raw = self._tri = None
+        return ok
+
+    def columns(self, which):
+        """the design of the columns `which` alone"""
+        return Design(self.family, np.asfortranarray(self.X[:, which]), self.kind[which], self.sign[which], self.disc[which],
+                      self.param[which])
+
+    @property
+    def key(self):
+        """[S, S] int32, the integers that order raw exactly, in -K .. K with key(-raw) == -key(raw): here num itself"""
+        return self.num
+
+    @property
+    def K(self):
+        return self.m
 
     @property
     def raw(self):
@@ -64,9 +91,37 @@ class Design:
             self._raw = np.where(self.valid, self.num / float(self.m), np.nan)
         return self._raw
 
-    def value(self, num):
-        """the float64 raw (== cor) of integer numerators"""
-        return np.asarray(num, dtype=np.float64) / float(self.m)
+    def value(self, key):
+        """the float64 raw of integer keys (here the numerators: num / m)"""
+        return np.asarray(key, dtype=np.float64) / float(self.m)
+
+    def under(self, perspective):
+        """the design as a perspective sees it: complete columns look the same under both"""
+        return self
+
+    def taumax(self, a, b):
+        return np.ones(np.broadcast(a, b).shape)
+
+    def completeness(self, a, b):
+        return np.ones(np.broadcast(a, b).shape)
+
+    def pvalue_id(self, a, b, one_sided=False):
+        """an integer per pair that the p-value is a function of: num (|num| two-sided); n and the ties are constant"""
+        v = self.num[a, b].astype(np.int64)
+        return v if one_sided else np.abs(v)
+
+    def planes(self, mask=None, scale_max=True, pvalue=None):
+        """[5, S, S]: cor, raw, pvalue, taumax, completeness as the library's matrices have them, NaN where the pair is
+        not valid and on the diagonal.  cor is raw / max_taumax(mask) under scale_max; pvalue: an [S, S] plane from
+        outside (it has no closed form), else NaN."""
+        out = np.full((5, self.S, self.S), np.nan)
+        a, b = np.nonzero(self.valid)
+        out[1] = self.raw
+        out[0][a, b] = cor_value(self.raw[a, b], self.max_taumax(mask), scale_max)
+        if pvalue is not None:
+            out[2][a, b] = pvalue[a, b]
+        out[3][a, b], out[4][a, b] = self.taumax(a, b), self.completeness(a, b)
+        return out
 
     def reasons(self):
         """[S, S] int32 reason code per pair: 1 with an all-NaN column, else 3 with a constant one, else 0"""
@@ -80,8 +135,14 @@ class Design:
         iu, ju = np.triu_indices(self.S, k=1)
         return np.bincount(self.reasons()[iu, ju], minlength=5).astype(np.int64)
 
-    def max_taumax(self):
-        return 1.0 if self.valid.any() else -np.inf
+    def max_taumax(self, mask=None):
+        """the largest taumax of the valid pairs (of those in `mask` [S, S]); -inf when there is none"""
+        return 1.0 if (self.valid if mask is None else self.valid & mask).any() else -np.inf
+
+
+def cor_value(raw, mx, scale_max=True):
+    """cor of a float64 raw: one more float64 division by the entry's max_taumax, or raw itself"""
+    return np.asarray(raw, dtype=np.float64) / mx if scale_max else np.asarray(raw, dtype=np.float64)
 
 
 def _assemble(family, n, S, seed, cols, disc_of, params, signs, n_all_missing, n_constant):
@@ -146,10 +207,342 @@ def reversals(S, n, seed=0, params=None, signs=None, values=None, flip=0.5, n_al
     return _assemble("reversals", n, S, seed, col, lambda L: L * (L - 1) // 2, p, s, n_all_missing, n_constant)
 
 
+# ---- the third family: tied, left-censored columns -------------------------------------------------------------------
+
+COUNT_FIELDS = ("n", "missing", "dis", "ntie", "xtie", "ytie", "x0", "x1", "y0", "y1", "tot")
+_BOTTOM = {}
+
+
+def _sgn(v):
+    return (v > 0) - (v < 0)
+
+
+def _bottom_tables(lib, B0):
+    """(cmd, cpd [2, L, L]; J, U [L, L]) over pairs of library subsets, by a plain count over the row pairs of the
+    bottom block: concordant minus discordant, concordant plus discordant (the row pairs tied in neither column), the
+    size of the intersection and of the union.  Index 0: every row kept; 1: the rows of the intersection dropped (what
+    the local perspective does to rows missing in both columns).  A row of the subset holds 0, below every base value."""
+    if (lib, B0) not in _BOTTOM:
+        L = len(lib)
+        cmd, cpd = np.zeros((2, L, L), dtype=np.int32), np.zeros((2, L, L), dtype=np.int32)
+        J, U = np.zeros((L, L), dtype=np.int32), np.zeros((L, L), dtype=np.int32)
+        filled = [[0 if r in set(A) else r + 1 for r in range(B0)] for A in lib]
+        for p, A in enumerate(lib):
+            for q, B in enumerate(lib):
+                both = set(A) & set(B)
+                J[p, q], U[p, q] = len(both), len(set(A) | set(B))
+                for drop in (0, 1):
+                    rows = [r for r in range(B0) if not (drop and r in both)]
+                    va, vb = [filled[p][r] for r in rows], [filled[q][r] for r in rows]
+                    for x in range(len(rows)):
+                        for y in range(x + 1, len(rows)):
+                            s = _sgn(va[x] - va[y]) * _sgn(vb[x] - vb[y])
+                            cmd[drop, p, q] += s
+                            cpd[drop, p, q] += abs(s)
+        _BOTTOM[(lib, B0)] = cmd, cpd, J, U
+    return _BOTTOM[(lib, B0)]
+
+
+@dataclasses.dataclass
+class _Columns:
+    """what the views of one censored design share: the shape, the libraries, and how each column was made"""
+    n: int
+    B0: int
+    c: int
+    t: int
+    h: int
+    variant: str
+    lib: tuple           # the c-subsets of the bottom block
+    states: np.ndarray   # [n_states, h] int8
+    X: np.ndarray
+    kind: np.ndarray
+    sign: np.ndarray
+    st: np.ndarray       # per column: its state's index, its subset's index
+    lb: np.ndarray
+
+
+class Censored(Design):
+    """A design of tied, left-censored columns as ONE perspective sees it (under(perspective) gives the other).
+    n = B0 + 2 h rows.  Rows 0 .. B0 - 1 are the bottom block, base values 1 .. B0; the c rows of the column's library
+    subset M_a are NaN there (variant "nan") or 0.5 (variant "ties": the same integers, nothing missing).  Rows
+    B0 + 2 p, B0 + 2 p + 1 are the adjacent pair p of the upper part, base values B0 + 2 p + 1 and + 2: in order
+    (state +1), exchanged (-1) or both the lower value (0, exactly t of the h); a column sign -1 reflects the upper part
+    alone, v -> B0 + n + 1 - v.  The reference's fill (min - 0.1) keeps the NaN rows one tie group below everything.
+
+    For a pair (a, b): j = |M_a & M_b|, u = |M_a | M_b|, drop = j under "local" on NaN columns and 0 otherwise,
+    n_eff = n - drop, tot = C(n_eff, 2), c' = c - drop, xtie = ytie = t + C(c', 2), den = tot - xtie (so
+    sqrt((tot - xtie)(tot - ytie)) == den exactly),
+      num  = (B0 - drop) 2 h + cmd(M_a, M_b, drop) + sign_a sign_b (C(2 h, 2) - h + s_a . s_b)
+      plus = (B0 - drop) 2 h + cpd(M_a, M_b, drop) +               (C(2 h, 2) - h + |s_a| . |s_b|)
+    raw = num / den, taumax = plus / den (one float64 division each), completeness = 1 - (u - drop) / n_eff, and the
+    eleven counts follow (counts()).  All of it is a function of the two columns' (state, subset, sign), so the integers
+    are kept as tables over the distinct such types.
+
+    key [S, S] int32: the dense rank of |num| / den among the design's distinct fractions (compared as fractions), with
+    the sign of num, 0 for num == 0; K the largest; value(key) the float64 num / den.  den varies under "local", so
+    num alone does not order raw there."""
+
+    def __init__(self, cols, perspective):
+        from fractions import Fraction
+        assert perspective in ("global", "local")
+        c = self.cols = cols
+        self.family, self.perspective, self.sign = "censored", perspective, c.sign
+        self.disc = self.param = None                                     # (the other families' parameters)
+        self._views = {perspective: self}
+        ok = self._set_columns(c.X, c.kind)
+        n, B0, cc, t, h = c.n, c.B0, c.c, c.t, c.h
+        local = perspective == "local" and c.variant == "nan"
+        trip = np.stack([c.st, c.lb, c.sign.astype(np.int64)], axis=1)[ok]
+        if len(trip):
+            types, ty = np.unique(trip, axis=0, return_inverse=True)
+        else:
+            types, ty = np.zeros((0, 3), dtype=np.int64), np.zeros(0, dtype=np.int64)
+        T = len(types)
+        St = c.states[types[:, 0]].astype(np.int32)                       # [T, h]
+        sg = types[:, 2].astype(np.int32)
+        la = types[:, 1]
+        cmd, cpd, J, U = _bottom_tables(c.lib, B0)
+        take = lambda a: a[la][:, la]                                     # noqa: E731
+        self._j, self._u = take(J).astype(np.int8), take(U).astype(np.int8)
+        self._drop = self._j.copy() if local else np.zeros((T, T), dtype=np.int8)
+        self._adot = (np.abs(St) @ np.abs(St).T).astype(np.int8)
+        drop = self._drop.astype(np.int32)
+        upper = h * (2 * h - 1) - h
+        both = (B0 - drop) * (2 * h)
+        self._num = both + take(cmd[1 if local else 0]) + (sg[:, None] * sg[None, :]) * (np.int32(upper) + St @ St.T)
+        self._plus = both + take(cpd[1 if local else 0]) + np.int32(upper) + self._adot
+        # what depends on drop alone
+        dr = np.arange(cc + 1, dtype=np.int64)
+        self.by_drop = {"n_eff": n - dr, "tot": (n - dr) * (n - dr - 1) // 2, "c1": cc - dr}
+        self.by_drop["xtie"] = t + self.by_drop["c1"] * (self.by_drop["c1"] - 1) // 2
+        self.by_drop["den"] = self.by_drop["tot"] - self.by_drop["xtie"]
+        assert self.by_drop["den"].min() > 0
+        # the key: fractions |num| / den ranked exactly, over the codes |num| (c + 1) + drop that occur
+        code = np.abs(self._num).astype(np.int64) * (cc + 1) + drop
+        present = np.nonzero(np.bincount(code.ravel(), minlength=1))[0]
+        fraction_of = {int(v): Fraction(int(v) // (cc + 1), int(self.by_drop["den"][int(v) % (cc + 1)])) for v in present}
+        fr = sorted(set(fraction_of.values()) | {Fraction(0)})
+        rank_of = {f: r for r, f in enumerate(fr)}                        # Fraction(0) has rank 0
+        self._K = len(fr) - 1
+        lut = np.zeros(int(code.max(initial=0)) + 1, dtype=np.int32)
+        for v in present:
+            lut[v] = rank_of[fraction_of[int(v)]]
+        self._key = lut[code] * np.sign(self._num).astype(np.int32)
+        pos = np.array([float(f.numerator) / float(f.denominator) for f in fr])    # equal fractions: equal quotients
+        self.values = np.concatenate([-pos[:0:-1], pos])                  # index K + key
+        self.distinct_doubles = bool(np.all(np.diff(self.values) > 0))
+        # per sample: its type, T for an NA column -- a padded row and column of the tables
+        self.ty = np.full(self.S, T, dtype=np.int64)
+        self.ty[ok] = ty
+        self.num = self._matrix(self._num)
+        self._keym = self._matrix(self._key)
+
+    def _matrix(self, table, dtype=np.int32):
+        """[S, S] from a [T, T] table: 0 where the pair is not valid"""
+        T = table.shape[0]
+        pad = np.zeros((T + 1, T + 1), dtype=dtype)
+        pad[:T, :T] = table
+        out = pad[self.ty[:, None], self.ty[None, :]]
+        out[~self.valid] = 0
+        return out
+
+    def _of(self, table, a, b):
+        """the table's entries for pairs (a, b); for an NA column some entry: the caller masks those pairs"""
+        last = table.shape[0] - 1
+        return table[np.minimum(self.ty[a], last), np.minimum(self.ty[b], last)]
+
+    key = property(lambda self: self._keym)
+    K = property(lambda self: self._K)
+
+    @property
+    def raw(self):
+        if self._raw is None:
+            self._raw = np.where(self.valid, self.value(self._keym), np.nan)
+        return self._raw
+
+    def value(self, key):
+        return self.values[np.asarray(key, dtype=np.int64) + self._K]
+
+    def under(self, perspective):
+        if perspective not in self._views:
+            self._views[perspective] = Censored(self.cols, perspective)
+            self._views[perspective]._views = self._views
+        return self._views[perspective]
+
+    def columns(self, which):
+        """the design of the columns `which` alone, under the same perspective"""
+        c = self.cols
+        return Censored(dataclasses.replace(c, X=np.asfortranarray(c.X[:, which]), kind=c.kind[which], sign=c.sign[which],
+                                            st=c.st[which], lb=c.lb[which]), self.perspective)
+
+    # -- the integers of pairs (a, b): index arrays of valid pairs
+    def plus(self, a, b):
+        return self._of(self._plus, a, b).astype(np.int64)
+
+    def drop(self, a, b):
+        return self._of(self._drop, a, b).astype(np.int64)
+
+    def den(self, a, b):
+        return self.by_drop["den"][self.drop(a, b)]
+
+    def n_eff(self, a, b):
+        return self.by_drop["n_eff"][self.drop(a, b)]
+
+    def missing(self, a, b):
+        if self.cols.variant != "nan":
+            return np.zeros(np.broadcast(a, b).shape, dtype=np.int64)
+        return self._of(self._u, a, b).astype(np.int64) - self.drop(a, b)
+
+    def taumax(self, a, b):
+        return self.plus(a, b).astype(np.float64) / self.den(a, b).astype(np.float64)
+
+    def completeness(self, a, b):
+        """the float64 expression 1.0 - missing / n_eff"""
+        return 1.0 - self.missing(a, b).astype(np.float64) / self.n_eff(a, b).astype(np.float64)
+
+    def counts(self, a, b):
+        """[P, 11] int64 in COUNT_FIELDS order"""
+        c = self.cols
+        dr = self.drop(a, b)
+        j = self._of(self._j, a, b).astype(np.int64)
+        num, plus = self.num[a, b].astype(np.int64), self.plus(a, b)
+        c1, xt = self.by_drop["c1"][dr], self.by_drop["xtie"][dr]
+        ntie = (j - dr) * (j - dr - 1) // 2 + self._of(self._adot, a, b).astype(np.int64) + 2 * c.t - c.h
+        # tie groups: one of c' rows and t of two.  x0 is the reference's sum of g (g - 1)(g - 2) HALVED (it divides
+        # t0 by two, kendallc.cpp's count_rank_tie); a group of two adds nothing to it and 2 * 1 * 9 to x1
+        x0, x1 = c1 * (c1 - 1) * (c1 - 2) // 2, c1 * (c1 - 1) * (2 * c1 + 5) + 18 * c.t
+        assert np.all((plus - num) % 2 == 0)
+        return np.stack([self.by_drop["n_eff"][dr], self.missing(a, b), (plus - num) // 2, ntie, xt, xt, x0, x1, x0, x1,
+                         self.by_drop["tot"][dr]], axis=-1)
+
+    def pvalue_id(self, a, b, one_sided=False):
+        """one integer per distinct (num, den, n_eff) -- (|num|, den, n_eff) two-sided: den and n_eff follow from drop"""
+        v = self.num[a, b].astype(np.int64)
+        return (v if one_sided else np.abs(v)) * (self.cols.c + 1) + self.drop(a, b)
+
+    def max_taumax(self, mask=None, columns=None):
+        """the exact maximum of the fractions plus / den over the valid pairs (of those in `mask`, or of those among
+        the columns `columns`), as its float64"""
+        from fractions import Fraction
+        if mask is None:        # from the type table alone: a cell counts when both types occur (its own twice)
+            T = self._plus.shape[0]
+            ty = self.ty if columns is None else self.ty[np.asarray(columns)]
+            cnt = np.bincount(ty[ty < T], minlength=T)
+            there = (cnt[:, None] > 0) & (cnt[None, :] > 0)
+            there[np.arange(T), np.arange(T)] = cnt >= 2
+            best = None
+            for dr in range(self.cols.c + 1):
+                sel = there & (self._drop == dr)
+                if sel.any():
+                    f = Fraction(int(self._plus[sel].max()), int(self.by_drop["den"][dr]))
+                    best = f if best is None or f > best else best
+            return -np.inf if best is None else float(best.numerator) / float(best.denominator)
+        ok = self.valid & mask
+        a, b = np.nonzero(ok)
+        if len(a) == 0:
+            return -np.inf
+        T1 = self._plus.shape[0] + 1
+        cells = np.unique(self.ty[a] * T1 + self.ty[b])
+        ta, tb = cells // T1, cells % T1
+        pd = np.unique(np.stack([self._plus[ta, tb].astype(np.int64), self.by_drop["den"][self._drop[ta, tb]]], axis=1),
+                       axis=0)
+        best = max(Fraction(int(p), int(q)) for p, q in pd)
+        return float(best.numerator) / float(best.denominator)
+
+
+def censored(S, n, B0, c, t, seed=0, variant="nan", perspective="global", n_lib=20, n_states=None, distinct=True,
+             own_state=False, twin=True, flip=0.5, n_all_missing=0, n_constant=0, max_overlap=None):
+    """S columns of the censored family (class Censored).  The valid columns draw their (state, subset) from n_states
+    seeded state vectors and n_lib seeded c-subsets of the bottom block: without replacement when `distinct` (no two
+    columns alike), else with.  own_state: every column has a state of its own (no two columns tie the same pairs, so
+    no taumax is 1 under either perspective, the twin's apart).  twin: the second valid column is then given the first
+    one's (state, subset) -- the one pair of the design with taumax == 1, and it lies in the first block of the
+    triangle.  signs with P(-1) = flip.  The NA columns go to seeded positions, as in the other families.  max_overlap: no two library subsets share more rows
+    than that (then taumax == 1 under "local" needs identical subsets, as under "global")."""
+    import itertools
+    h = (n - B0) // 2
+    assert n == B0 + 2 * h and n <= 200 and 0 <= t <= h and 0 < c < B0 and variant in ("nan", "ties")
+    rng = np.random.default_rng(seed + 7919)
+    subsets = list(itertools.combinations(range(B0), c))
+    if max_overlap is None:
+        lib = tuple(subsets[i] for i in sorted(rng.choice(len(subsets), size=min(n_lib, len(subsets)), replace=False)))
+    else:   # no two subsets share more than max_overlap rows: with c - max_overlap >= 2 a NaN tie group survives "local"
+        lib = []
+        for i in rng.permutation(len(subsets)):
+            if len(lib) < n_lib and all(len(set(subsets[i]) & set(m)) <= max_overlap for m in lib):
+                lib.append(subsets[i])
+        assert len(lib) == n_lib
+        lib = tuple(sorted(lib))
+    n_cols = S - n_all_missing - n_constant
+    if n_states is None:
+        n_states = n_cols if own_state else -(-n_cols // len(lib)) + 1
+    assert math.comb(h, t) >= n_states
+    states, zero_sets = [], set()
+    while len(states) < n_states:                                         # no two states tie the same t pairs
+        s = rng.choice([-1, 1], size=h)
+        zeros = tuple(sorted(rng.choice(h, size=t, replace=False).tolist()))
+        if zeros in zero_sets:
+            continue
+        zero_sets.add(zeros)
+        s[list(zeros)] = 0
+        states.append(s)
+    states = np.array(states, dtype=np.int8).reshape(n_states, h)
+    n_combo = n_states * len(lib)
+    assert not distinct or n_combo >= n_cols
+    if own_state:
+        assert n_states >= n_cols
+        combo = np.arange(n_cols) * len(lib) + rng.choice(len(lib), size=n_cols)
+    else:
+        combo = rng.choice(n_combo, size=n_cols, replace=not distinct)
+    if twin and n_cols > 1:
+        combo[1] = combo[0]
+    signs = np.where(rng.random(n_cols) < flip, -1, 1)
+    if twin and n_cols > 1:
+        signs[1] = signs[0]
+
+    kind = np.zeros(S, dtype=np.int32)
+    where = np.random.default_rng(seed).choice(S, size=n_all_missing + n_constant, replace=False)
+    kind[where[:n_all_missing]] = ALL_MISSING
+    kind[where[n_all_missing:]] = CONSTANT
+    good = np.nonzero(kind == VALID)[0]
+    X = np.empty((n, S), order="F")
+    cols = _Columns(n, B0, c, t, h, variant, lib, states, X, kind, np.zeros(S, dtype=np.int32), np.zeros(S, dtype=np.int64),
+                    np.zeros(S, dtype=np.int64))
+    X[:, kind == ALL_MISSING] = np.nan
+    X[:, kind == CONSTANT] = 2.5
+    low = B0 + 1 + 2 * np.arange(h, dtype=np.float64)                     # the lower base value of each adjacent pair
+    for col, q, sg in zip(good, combo, signs):
+        st, lb = int(q) // len(lib), int(q) % len(lib)
+        s = states[st]
+        x = np.arange(1, n + 1, dtype=np.float64)
+        x[B0::2] = np.where(s == -1, low + 1, low)
+        x[B0 + 1::2] = np.where(s == 1, low + 1, low)
+        if sg < 0:
+            x[B0:] = B0 + n + 1 - x[B0:]
+        x[list(lib[lb])] = np.nan if variant == "nan" else 0.5
+        X[:, col] = x
+        cols.st[col], cols.lb[col], cols.sign[col] = st, lb, sg
+    return Censored(cols, perspective)
+
+
 def valid_columns(d):
     """the design's valid columns alone: no NA pair (PERMANOVA sums per class only then)"""
-    good = d.kind == VALID
-    return Design(d.family, np.asfortranarray(d.X[:, good]), d.kind[good], d.sign[good], d.disc[good], d.param[good])
+    return d.columns(np.nonzero(d.kind == VALID)[0])
+
+
+def carried(d, a, b, mx, scale_max=True, pvalue=None):
+    """[5, *a.shape]: cor, raw, pvalue, taumax, completeness that an entry carries for the pairs (a, b); where b < 0 (no
+    partner) NA_real_.  mx: the entry's max_taumax, cor's divisor under scale_max; pvalue: an array like a from outside,
+    else that plane is left NaN."""
+    a, b = np.broadcast_arrays(np.asarray(a), np.asarray(b))
+    out = na_filled((5,) + a.shape)
+    sel = b >= 0
+    aa, bb = a[sel], b[sel]
+    raw = d.value(d.key[aa, bb])
+    out[1][sel], out[0][sel] = raw, cor_value(raw, mx, scale_max)
+    out[2][sel] = np.nan if pvalue is None else np.asarray(pvalue)[sel]
+    out[3][sel], out[4][sel] = d.taumax(aa, bb), d.completeness(aa, bb)
+    return out
 
 
 # ---- top-k -----------------------------------------------------------------------------------------------------------
@@ -175,29 +568,40 @@ def _topk(d, num, valid, k):
 def topk(d, k):
     """(idx [S, k] int32, -1 padded; num [S, k] int32 of the chosen; raw [S, k], NA_real_ padded; n_valid [S]): per
     sample the k valid partners of largest num, ties by the smaller partner index"""
-    return _topk(d, d.num, d.valid, k)
+    return _topk(d, d.key, d.valid, k)
 
 
 # ---- edges -----------------------------------------------------------------------------------------------------------
 
-def edges(d, min_num, absolute=False):
+def edges(d, min_num, absolute=False, also=None):
     """(ei, ej int32 in combn order; num [n_edges] int32; raw [n_edges]; n_edges; degree [S] int64): the valid pairs
     with num >= min_num (|num| with absolute).  raw >= min_num / m is the same rule: x -> x / m is strictly monotone on
-    integers this small."""
-    val = np.abs(d.num) if absolute else d.num
+    integers this small.  On a design whose key is not num, min_num and the third item are keys.  also: a symmetric
+    [S, S] bool mask that a pair must pass as well (a bound on completeness or on the p-value)."""
+    val = np.abs(d.key) if absolute else d.key
     ok = d.valid & (val >= min_num)
+    if also is not None:
+        ok &= also
     degree = ok.sum(axis=1).astype(np.int64)
     ei, ej = np.nonzero(np.triu(ok, 1))                               # row-major upper triangle == combn order
-    nums = d.num[ei, ej]
+    nums = d.key[ei, ej]
     return ei.astype(np.int32), ej.astype(np.int32), nums, d.value(nums), int(ei.shape[0]), degree
 
 
 # ---- class medians / class matrix ------------------------------------------------------------------------------------
 
-def _median_float(d, lo, hi, v):
+def median_cor(d, cells, mx):
+    """med_cor of class_matrix's or class_medians' dict under scale_max: the median of raw / mx, mx the entry's
+    max_taumax.  Division by a positive constant keeps the order, so the two middle values are those of raw."""
+    return _median_float(d, cells["lo"], cells["hi"], cells["n_valid"], mx)
+
+
+def _median_float(d, lo, hi, v, mx=None):
     """R's median from the two middle numerators: lo / m for an odd count, else mean() of lo / m and hi / m"""
     out = na_filled(lo.shape)
     a, b = d.value(lo), d.value(hi)
+    if mx is not None:
+        a, b = a / mx, b / mx
     flat_o, flat_a, flat_b, flat_v = out.reshape(-1), a.reshape(-1), b.reshape(-1), v.reshape(-1)
     odd = (flat_v & 1) == 1
     flat_o[odd] = flat_a[odd] + 0.0
@@ -236,7 +640,7 @@ def class_matrix(d, cls=None, n_class=1):
     v >> 1 among the cell's valid partners ascending; k_in: the rank of lo inside its run of equal numerators; run: that
     run's length; med: the median as float64 (== med_raw == med_cor), NA_real_ where n_valid == 0"""
     cls = np.zeros(d.S, dtype=np.int64) if cls is None else np.asarray(cls)
-    return _class_cells(d, d.num, d.valid, cls, n_class)
+    return _class_cells(d, d.key, d.valid, cls, n_class)
 
 
 def class_medians(d, cls=None):
@@ -251,7 +655,7 @@ def class_medians(d, cls=None):
 def group_counts(d, cls=None):
     """(cnt [G, 2 m + 1] int64: the pairs i < j of a group per numerator, cnt[g, num + m]; n_valid [G]; n_na [G]);
     G = 1 (all pairs) or, with cls, 3 (all, within-class, between-class)"""
-    S, m = d.S, d.m
+    S, m = d.S, d.K
     off = ~np.eye(S, dtype=bool)
     masks = [off]
     if cls is not None:
@@ -263,7 +667,7 @@ def group_counts(d, cls=None):
     n_valid, n_na = np.zeros(G, dtype=np.int64), np.zeros(G, dtype=np.int64)
     for g, mask in enumerate(masks):
         ok = mask & d.valid
-        both = np.bincount(d.num[ok].astype(np.int64) + m, minlength=2 * m + 1)     # every pair twice: (a, b), (b, a)
+        both = np.bincount(d.key[ok].astype(np.int64) + m, minlength=2 * m + 1)     # every pair twice: (a, b), (b, a)
         assert np.all(both % 2 == 0)
         cnt[g] = both // 2
         n_valid[g] = int(ok.sum()) // 2
@@ -271,9 +675,10 @@ def group_counts(d, cls=None):
     return cnt, n_valid, n_na
 
 
-def quantiles(d, probs, cls=None, counts=None):
+def quantiles(d, probs, cls=None, counts=None, mx=None):
     """(q [G, n_probs]: the type-7 quantile (== quantile_raw == quantile_cor); order2 [G, n_probs, 2]; ord_num
-    [G, n_probs, 2] int64: the numerators of the two order statistics; n_valid, n_na [G])"""
+    [G, n_probs, 2] int64: the numerators of the two order statistics; n_valid, n_na [G]).  mx: q is quantile_cor under
+    scale_max, the type-7 quantile of the two order statistics each divided by mx (order2 stays raw)."""
     cnt, n_valid, n_na = group_counts(d, cls) if counts is None else counts
     probs = np.asarray(probs, dtype=np.float64).reshape(-1)
     G = cnt.shape[0]
@@ -287,11 +692,11 @@ def quantiles(d, probs, cls=None, counts=None):
         for k, p in enumerate(probs):
             index = 1.0 + float(v - 1) * float(p)
             lo, hi = int(math.floor(index)), int(math.ceil(index))
-            na_, nb_ = (int(np.searchsorted(cum, r - 1, side="right")) - d.m for r in (lo, hi))   # rank r, 1-based
+            na_, nb_ = (int(np.searchsorted(cum, r - 1, side="right")) - d.K for r in (lo, hi))   # rank r, 1-based
             a, b = float(d.value(na_)) + 0.0, float(d.value(nb_)) + 0.0
             ord_num[g, k] = na_, nb_
             order2[g, k] = a, b
-            q[g, k] = type7(a, b, index, float(lo))
+            q[g, k] = type7(a, b, index, float(lo)) if mx is None else type7(a / mx + 0.0, b / mx + 0.0, index, float(lo))
     return q, order2, ord_num, n_valid, n_na
 
 
@@ -301,7 +706,7 @@ def histogram(d, break_nums, cls=None, counts=None):
     cnt, _n_valid, _n_na = group_counts(d, cls) if counts is None else counts
     bn = np.asarray(break_nums, dtype=np.int64)
     assert bn.ndim == 1 and bn.shape[0] >= 2 and np.all(np.diff(bn) > 0)
-    nums = np.arange(-d.m, d.m + 1)
+    nums = np.arange(-d.K, d.K + 1)
     slot = np.searchsorted(bn, nums, side="right")            # 0 below, 1 + k in bin k, len(bn) at or above the last break
     slot[nums == bn[-1]] = len(bn) - 1
     G = cnt.shape[0]
@@ -323,7 +728,7 @@ def triangle(d):
         iu, ju = np.triu_indices(d.S, k=1)
         ok = d.valid[iu, ju]
         i, j = iu[ok].astype(np.int32), ju[ok].astype(np.int32)
-        d._tri = (i, j, d.num[i, j] + np.int32(d.m), int(ok.shape[0] - i.shape[0]))
+        d._tri = (i, j, d.key[i, j] + np.int32(d.K), int(ok.shape[0] - i.shape[0]))
     return d._tri
 
 
@@ -332,7 +737,7 @@ def class_hist(d, lab, n_class):
     per numerator (column num + m)"""
     i, j, k, _n_na = triangle(d)
     lab = np.asarray(lab, dtype=np.int64)
-    width = 2 * d.m + 1
+    width = 2 * d.K + 1
     li = lab[i]
     same = li == lab[j]
     return np.bincount(li[same] * width + k[same], minlength=n_class * width).reshape(n_class, width)
@@ -352,7 +757,7 @@ def anosim(d, cls, n_class, labellings):
     cls, perms, labs = _labellings(d, cls, labellings)
     _i, _j, k, n_na = triangle(d)
     M = int(k.shape[0])
-    cnt = np.bincount(k, minlength=2 * d.m + 1).astype(np.int64)
+    cnt = np.bincount(k, minlength=2 * d.K + 1).astype(np.int64)
     above = np.cumsum(cnt[::-1])[::-1] - cnt
     r2 = 2 * above + cnt + 1                                         # (at most 2 M < 2^26: the sums below stay in int64)
     assert M == 0 or int(np.dot(cnt, r2)) == M * (M + 1)
@@ -383,7 +788,7 @@ def anosim(d, cls, n_class, labellings):
 def q_table(d):
     """q per numerator, index num + m: tests/permanova_checker.quantise(num / m) in Python ints (dtype object)"""
     from tests.permanova_checker import quantise
-    return np.array([quantise(float(d.value(v))) for v in range(-d.m, d.m + 1)], dtype=object)
+    return np.array([quantise(float(d.value(v))) for v in range(-d.K, d.K + 1)], dtype=object)
 
 
 def permanova(d, cls, n_class, labellings):
@@ -393,7 +798,7 @@ def permanova(d, cls, n_class, labellings):
     cls, perms, labs = _labellings(d, cls, labellings)
     _i, _j, k, n_na = triangle(d)
     table = q_table(d)
-    cnt = np.bincount(k, minlength=2 * d.m + 1)
+    cnt = np.bincount(k, minlength=2 * d.K + 1)
     used = np.nonzero(cnt)[0]
     Q = sum(int(cnt[v]) * table[v] for v in used)
     class_q, sizes = [], []
@@ -437,7 +842,7 @@ def _permdisp_sweep(d, cls, n_class):
     columns are taken class by class (a stable sort of the labels), so one np.add.reduceat over the classes that have a
     sample sums every cell of a block of rows, whatever n_class is.  A cell has at most S - 1 < 2^16 limbs below 2^32:
     every sum is below 2^48."""
-    S, m = d.S, d.m
+    S, m = d.S, d.K
     cls = np.asarray(cls, dtype=np.int64)
     assert cls.shape == (S,) and (S == 0 or (cls.min() >= 0 and cls.max() < n_class)) and S < 1 << 16
     table = [int(v) for v in q_table(d)] + [0]
@@ -451,7 +856,7 @@ def _permdisp_sweep(d, cls, n_class):
     both = np.zeros(2 * m + 2, dtype=np.int64)
     for a in range(0, S, _PERMDISP_ROWS):
         rows = slice(a, min(a + _PERMDISP_ROWS, S))
-        k = np.take(np.where(d.valid[rows], d.num[rows] + np.int32(m), no_value), order, axis=1)
+        k = np.take(np.where(d.valid[rows], d.key[rows] + np.int32(m), no_value), order, axis=1)
         both += np.bincount(k.ravel(), minlength=2 * m + 2)
         for limb, t in zip(limbs, out):
             t[rows, used] = np.add.reduceat(limb.take(k), starts, axis=1)
@@ -478,7 +883,7 @@ def permdisp_table(d, cls, n_class):
     not valid adds 0 and counts in n_na, and the table stays AS SUMMED when there is one (PERMANOVA's reference zeroes
     its class sums then).  Q is the pairs' histogram over the numerators times q_table, apart from the limb planes;
     A_c is half the sum of column c over the members of c."""
-    S, m = d.S, d.m
+    S, m = d.S, d.K
     cls = np.asarray(cls, dtype=np.int64)
     t_lo, t_hi, both = _permdisp_sweep(d, cls, n_class)               # both: every pair twice, (a, b) and (b, a)
     T = limbs_to_ints(t_lo, t_hi)
@@ -507,12 +912,10 @@ def permdisp(d, cls, n_class, labellings):
 
 def pvalue_keys(d, one_sided=False):
     """(keys: the distinct num -- |num| unless one_sided -- of the valid pairs, ascending; count per key; (i, j) of
-    the first pair in combn order that has each key; n_na)"""
-    i, j, k, n_na = triangle(d)
-    key = k.astype(np.int64) - d.m
-    if not one_sided:
-        key = np.abs(key)
-    keys, first, count = np.unique(key, return_index=True, return_counts=True)
+    the first pair in combn order that has each key; n_na).  On the censored family the key is Design.pvalue_id: one
+    integer per distinct (num, den, n_eff), what the p-value is a function of there."""
+    i, j, _k, n_na = triangle(d)
+    keys, first, count = np.unique(d.pvalue_id(i, j, one_sided), return_index=True, return_counts=True)
     return keys, count, i[first], j[first], n_na
 
 
@@ -583,6 +986,8 @@ def alpha_inside_a_run(p, method):
 # ---- spanning forest -------------------------------------------------------------------------------------------------
 
 def is_two_valued(d):
+    if d.disc is None:
+        return False
     ok = d.kind == VALID
     return bool(ok.any() and np.all(d.disc[ok] == d.disc[ok][0]))
 
@@ -629,15 +1034,18 @@ class Rect:
         assert 0 < Sq < d.S
         self.d, self.Sq, self.Sr = d, Sq, d.S - Sq
         self.Q, self.R = np.asfortranarray(d.X[:, :Sq]), np.asfortranarray(d.X[:, Sq:])
-        self.num, self.valid = d.num[:Sq, Sq:], d.valid[:Sq, Sq:]
-        self.raw = np.where(self.valid, self.num / float(d.m), np.nan)
+        self.num, self.valid = d.key[:Sq, Sq:], d.valid[:Sq, Sq:]
+        self.raw = np.where(self.valid, d.value(self.num), np.nan)
         self.reasons = d.reasons()[:Sq, Sq:]
 
     def reason_counts(self):
         return np.bincount(self.reasons.ravel(), minlength=5).astype(np.int64)
 
-    def max_taumax(self):
-        return 1.0 if self.valid.any() else -np.inf
+    def max_taumax(self, queries=None):
+        """the largest taumax of the rectangle alone (of the rows `queries` of it): not of the stacked triangle"""
+        mask = np.zeros((self.d.S, self.d.S), dtype=bool)
+        mask[np.arange(self.Sq) if queries is None else np.asarray(queries), self.Sq:] = True
+        return self.d.max_taumax(mask)
 
 
 def rect(d, Sq):

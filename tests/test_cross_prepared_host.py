@@ -190,14 +190,45 @@ def test_a_batch_over_the_capacity_is_split_and_stitched(signal, scale_max):
     assert len(set(firsts)) > 1 and max(firsts) == one["max_taumax"]       # the parts do scale differently
     assert list(parts) == list(one)
     for key in one:
-        if key in ("class_med_cor", "run_time"):
+        if key == "run_time":
             continue
-        _same(parts[key], one[key], key)       # cor and topk_cor among them: scaled again, from raw
+        _same(parts[key], one[key], key)       # cor, topk_cor and class_med_cor among them: scaled again, from raw
     a, b = np.asarray(parts["class_med_cor"]), np.asarray(one["class_med_cor"])
-    assert np.array_equal(np.isnan(a), np.isnan(b))
-    assert np.allclose(a[~np.isnan(a)], b[~np.isnan(b)], rtol=4 * np.finfo(float).eps, atol=0)
-    odd = (np.asarray(one["class_n_valid"]) & 1) == 1
-    assert np.array_equal(bits(a)[odd], bits(b)[odd])
+    assert np.array_equal(bits(a), bits(b))    # even cells too: reduced again from the part's raw
+
+
+def _recorded(call, *args, **kw):
+    with warnings.catch_warnings(record=True) as w:
+        warnings.simplefilter("always")
+        # the reference's own warnings, one per offending pair (numpy's, of the host route's divisions, are not counted)
+        return call(*args, **kw), [str(x.message) for x in w if str(x.message).startswith("Warning:")]
+
+
+@pytest.mark.parametrize("k", [None, 5])
+def test_a_split_batch_without_its_matrix_reduces_even_cells_again(signal, k):
+    """return_matrix=False, classes, scale_max and parts whose maximum is below the call's: no part kept its matrix, so
+    the parts with even cells are asked for theirs once more.  class_med_cor equals the unsplit call's bits, and the
+    pairs of the constant query column are warned about once, as in the unsplit call."""
+    Q, R, qn, rn, rl = signal
+    eng = OracleEngine()
+    kw = dict(k=k, return_matrix=False, scale_max=True, query_names=qn)
+    with api.prepare_reference(R, Q.shape[1], reference_names=rn, reference_classes=rl, engine=eng) as whole:
+        one, warned_one = _recorded(api.ici_kendalltau_cross, Q, whole, **kw)
+    asked = []
+    with api.prepare_reference(R, 4, reference_names=rn, reference_classes=rl, engine=eng) as narrow:
+        batch = narrow._batch
+        narrow._batch = lambda *a: (asked.append(a[2]), batch(*a))[1]       # a[2]: want_matrix
+        parts, warned_parts = _recorded(api.ici_kendalltau_cross, Q, narrow, **kw)
+    n_parts = -(-Q.shape[1] // 4)
+    assert asked[:n_parts] == [False] * n_parts and 0 < asked[n_parts:].count(True) == len(asked) - n_parts < n_parts
+    assert "raw" not in parts and list(parts) == list(one)
+    even = (np.asarray(one["class_n_valid"]) > 0) & ((np.asarray(one["class_n_valid"]) & 1) == 0)
+    assert even.sum() >= 20
+    for key in one:
+        if key != "run_time":
+            _same(parts[key], one[key], key)
+    assert np.array_equal(bits(np.asarray(parts["class_med_cor"])), bits(np.asarray(one["class_med_cor"])))
+    assert len(warned_one) > 0 and sorted(warned_parts) == sorted(warned_one)
 
 
 # ---- refusals ------------------------------------------------------------------------------------------------------

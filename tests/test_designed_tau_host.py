@@ -4,7 +4,8 @@ against the oracle's, and its closed-form answers of the five selection entries 
 closed-form matrices.  Below those, the references of the seven later entries (anosim, permanova, padjust, mst, cross and
 its class table) against their checkers at S = 130, permdisp's table and dict against its checker with what the large
 GPU tests presuppose about their inputs, and the mutations that the designs of the GPU tests must keep showing: two
-replayed defects of permdisp's sweep and hclust's contracted average update."""
+replayed defects of permdisp's sweep and hclust's contracted average update.  At the end the censored family: against
+the oracle, by direct counting, against the checkers, and five replayed defects of scaling, carrying and perspective."""
 import math
 import warnings
 from fractions import Fraction
@@ -471,3 +472,255 @@ def test_a_contracted_average_update_shows_on_the_designs(key, which):
     if key == "rev24-520" and which == "first":
         assert order > 0                                               # the merge order itself changes
     assert math.isfinite(want[3][0])
+
+
+# ---- the third family: tied, left-censored columns -------------------------------------------------------------------
+# taumax != 1, completeness != 1, cor != raw, den varying per pair under "local": what the two families above cannot show.
+
+from tests import epilogue_checker as E          # noqa: E402
+
+CENSORED_SHAPES = {41: (41, 7, 2, 4), 64: (64, 8, 3, 5)}                 # n: (n, B0, c, t)
+CENS130 = ["cens64", "cens64-ties", "cens64-apart"]                     # the S = 130 designs of the GPU files
+
+
+def _ulp_of_fraction(got, num, den):
+    """|got - num / den| in units of the spacing of doubles at num / den, exactly"""
+    exact = Fraction(int(num), int(den))
+    return abs(Fraction(float(got)) - exact) / Fraction(float(np.spacing(float(exact) or 1.0)))
+
+
+@pytest.mark.parametrize("na", [True, False])
+@pytest.mark.parametrize("variant", ["nan", "ties"])
+@pytest.mark.parametrize("perspective", ["global", "local"])
+@pytest.mark.parametrize("n", [41, 64])
+def test_censored_closed_form_is_the_oracle(n, perspective, variant, na):
+    d = dt.censored(14, *CENSORED_SHAPES[n], seed=3, variant=variant, n_lib=4, n_all_missing=1 if na else 0,
+                    n_constant=1 if na else 0).under(perspective)
+    S = d.S
+    assert d.n <= 200 and d.distinct_doubles                              # distinct fractions are distinct doubles
+    iu, ju = np.triu_indices(S, k=1)
+    out, cnt, rsn = O.ici_pairs(d.X, iu.astype(np.int32), ju.astype(np.int32), perspective=perspective)
+    assert np.array_equal(rsn, d.reasons()[iu, ju]) and np.array_equal(np.bincount(rsn, minlength=5), d.reason_counts())
+    ok = rsn == 0
+    a, b = iu[ok], ju[ok]
+    assert np.array_equal(ok, d.valid[iu, ju]) and len(a) >= 66
+    counts = d.counts(a, b)
+    assert np.array_equal(cnt[ok][:, :11], counts)                        # all eleven counts
+    tot, xtie, ntie, dis = counts[:, 10], counts[:, 4], counts[:, 3], counts[:, 2]
+    assert np.array_equal(d.plus(a, b), tot - 2 * xtie + ntie) and np.array_equal(d.num[a, b], tot - 2 * xtie + ntie - 2 * dis)
+    assert np.array_equal(d.den(a, b), tot - xtie) and np.array_equal(d.n_eff(a, b), counts[:, 0])
+    assert np.array_equal(bits(out[ok, 0]), bits(d.raw[a, b])) and np.array_equal(bits(out[ok, 2]), bits(d.taumax(a, b)))
+    assert np.array_equal(bits(d.raw[a, b]), bits(d.num[a, b] / d.den(a, b).astype(np.float64)))     # one division
+    tm = d.taumax(a, b)
+    assert tm.max() == d.max_taumax() == 1.0 and np.sum(tm < 1.0) > 50 and tm.min() > 0.99
+    assert np.all(d.taumax(a, b)[(d.cols.st[a] == d.cols.st[b]) & (d.cols.lb[a] == d.cols.lb[b])] == 1.0)
+    # completeness: the oracle divides in long double and rounds twice, the closed form is 1.0 - missing / n_eff
+    miss, ne = d.missing(a, b), d.n_eff(a, b)
+    for got in (out[ok, 3], d.completeness(a, b)):
+        assert max(_ulp_of_fraction(g, e - m_, e) for g, m_, e in zip(got, miss, ne)) <= 1
+    two = (ne & (ne - 1)) == 0
+    assert np.array_equal(bits(out[ok, 3][two]), bits(d.completeness(a, b)[two]))
+    assert two.all() == (n == 64 and (perspective == "global" or variant == "ties"))
+    assert (miss.max() > 0) == (variant == "nan") and (variant == "ties" or d.completeness(a, b).max() < 1.0 or perspective == "local")
+    # the p-value: one per distinct (num, den, n_eff) -- per (|num|, den, n_eff) two-sided --, and the exact epilogue's
+    for alternative, one_sided in (("two.sided", False), ("greater", True)):
+        pv = O.ici_pairs(d.X, a.astype(np.int32), b.astype(np.int32), perspective=perspective, alternative=alternative,
+                         want_counts=False)[0]
+        ids, first, inv = np.unique(d.pvalue_id(a, b, one_sided), return_index=True, return_inverse=True)
+        assert np.array_equal(bits(pv[:, 1]), bits(pv[first, 1][inv])) and 20 <= len(ids) < len(a)
+        worst = E.check_call(pv, counts, alternative, False, 2 * E.E_CPU["cases"])
+        assert worst["tau"] <= 0.5 and worst["tau_max"] <= 0.5 and worst["completeness"] <= 1.0    # correctly rounded
+    # the matrices as the front end scales them
+    names = [f"s{i}" for i in range(S)]
+    for scale_max in (True, False):
+        with warnings.catch_warnings():
+            warnings.simplefilter("ignore")
+            full = api.ici_kendalltau(d.X, perspective=perspective, scale_max=scale_max, colnames=names, engine=OracleEngine())
+        want = d.planes(None, scale_max)
+        for k, name in ((0, "cor"), (1, "raw"), (3, "taumax")):
+            got = np.asarray(full[name])
+            assert np.array_equal(bits(got[d.valid]), bits(want[k][d.valid])), (name, scale_max)
+            assert np.all(np.isnan(got[~d.valid & ~np.eye(S, dtype=bool)]))
+
+
+def test_censored_formulas_by_counting():
+    """num, plus and all eleven counts of the censored family by the definition, on a 9-row and a 10-row example: every
+    row pair compared in both columns after the reference's fill (tests/epilogue_checker.pair_counts, plain numpy)"""
+    for shape in ((9, 3, 1, 1), (10, 4, 2, 1)):
+        for variant in ("nan", "ties"):
+            d0 = dt.censored(12, *shape, seed=5, variant=variant, n_lib=3, n_states=3, distinct=False, twin=False)
+            for perspective in ("global", "local"):
+                d = d0.under(perspective)
+                for a in range(d.S):
+                    for b in range(d.S):
+                        if a == b:
+                            continue
+                        x, y = d.X[:, a], d.X[:, b]
+                        assert E.pair_counts(x, y, perspective) == tuple(d.counts(a, b).tolist()), (shape, variant, a, b)
+                        keep = ~(np.isnan(x) & np.isnan(y)) if perspective == "local" else np.ones(len(x), dtype=bool)
+                        fx, fy = (np.where(np.isnan(v), np.nanmin(v) - 0.1, v)[keep] for v in (x, y))
+                        r, s = np.triu_indices(len(fx), k=1)
+                        conc = np.sign(fx[r] - fx[s]) * np.sign(fy[r] - fy[s])
+                        assert int(conc.sum()) == d.num[a, b] and int(np.abs(conc).sum()) == d.plus(a, b)
+                assert np.array_equal(d.key, d.key.T) and np.array_equal(np.sign(d.key), np.sign(d.num))
+                order = np.argsort(d.key[d.valid], kind="stable")
+                fr = [Fraction(int(p), int(q)) for p, q in zip(d.num[d.valid][order], d.den(*np.nonzero(d.valid))[order])]
+                ks = d.key[d.valid][order]
+                assert all((f1 < f2) == (k1 < k2) for f1, f2, k1, k2 in zip(fr, fr[1:], ks, ks[1:]))   # key orders the fractions
+
+
+def _cens_classes(d):
+    return gpu_base._classes(d, "interleaved")
+
+
+def _oracle_plane(d, perspective, column=1, alternative="two.sided"):
+    iu, ju = np.triu_indices(d.S, k=1)
+    out = O.ici_pairs(d.X, iu.astype(np.int32), ju.astype(np.int32), perspective=perspective, alternative=alternative,
+                      want_counts=False)[0]
+    plane = np.full((d.S, d.S), np.nan)
+    plane[iu, ju] = plane[ju, iu] = out[:, column]
+    return plane
+
+
+@pytest.mark.parametrize("perspective", ["global", "local"])
+@pytest.mark.parametrize("key", CENS130)
+def test_censored_entries_against_the_checkers(key, perspective):
+    """every closed-form entry answer on the S = 130 censored designs against its brute-force checker fed the design's
+    five matrices (the p-value plane is the CPU oracle's)"""
+    d = _gpu_design(key).under(perspective)
+    assert d.n <= 200 and d.distinct_doubles
+    S = d.S
+    pplane = _oracle_plane(d, perspective)
+    cls, n_class = _cens_classes(d)
+    same = cls[:, None] == cls[None, :]
+    mx_all, mx_in = d.max_taumax(), d.max_taumax(same)
+    assert np.array_equal(bits(_oracle_plane(d, perspective, 0)[d.valid]), bits(d.raw[d.valid]))
+    assert np.array_equal(bits(_oracle_plane(d, perspective, 2)[d.valid]), bits(d.taumax(*np.nonzero(d.valid))))
+    for scale_max in (True, False):
+        m5 = d.planes(None, scale_max, pplane)
+        rows = np.arange(S)[:, None]
+        for k in (1, 7, S + 4):
+            idx, _keys, raw, n_valid = dt.topk(d, k)
+            ridx, rvals, rn = brute_topk(m5, k)
+            assert np.array_equal(idx, ridx) and np.array_equal(n_valid, rn)
+            want = dt.carried(d, rows, idx, mx_all, scale_max, pplane[rows, np.maximum(idx, 0)])
+            assert np.array_equal(bits(want), bits(rvals)) and np.array_equal(bits(raw), bits(rvals[1]))
+        cnt = dt.group_counts(d)[0][0]
+        t = int(np.argmax(cnt)) - d.K                                      # the key most pairs equal
+        comp = d.planes()[4]
+        c0 = float(np.unique(comp[d.valid])[-2]) if len(np.unique(comp[d.valid])) > 1 else 1.0
+        p0 = float(np.sort(pplane[d.valid])[int(d.valid.sum()) // 2])       # a value of the p plane itself
+        for absolute in (False, True):
+            for also, kw in ((None, {}), ((comp >= c0) & (pplane <= p0), {"min_completeness": c0, "max_pvalue": p0})):
+                ei, ej, _keys, raw, n_edges, degree = dt.edges(d, t, absolute, also)
+                rei, rej, rvals, rn, rdeg = brute_edges(m5, min_raw=float(d.value(t)), absolute=absolute, **kw)
+                assert n_edges == rn > 0 and np.array_equal(ei, rei) and np.array_equal(ej, rej) and np.array_equal(degree, rdeg)
+                assert np.array_equal(bits(dt.carried(d, ei, ej, mx_all, scale_max, pplane[ei, ej])), bits(rvals))
+        for c, nc in ((None, 1), (cls, n_class)):
+            cm = dt.class_matrix(d, c, nc)
+            med2, n_valid = brute_class_matrix(m5, c, nc)
+            assert np.array_equal(cm["n_valid"], n_valid) and np.array_equal(bits(cm["med"]), bits(med2[1]))
+            assert np.array_equal(bits(dt.median_cor(d, cm, mx_all) if scale_max else cm["med"]), bits(med2[0]))
+            own = dt.class_medians(d, c)
+            rule = mx_all if c is None else mx_in                            # class_medians: the within-class pairs' maximum
+            med2, n_valid = brute_medians(d.planes(None if c is None else same, scale_max), c)
+            assert np.array_equal(own["n_valid"], n_valid) and np.array_equal(bits(own["med"]), bits(med2[1]))
+            assert np.array_equal(bits(dt.median_cor(d, own, rule) if scale_max else own["med"]), bits(med2[0]))
+        counts = dt.group_counts(d, cls)
+        vals = np.nonzero(counts[0][0])[0] - d.K
+        bn = vals[1:-1:3]
+        q, order2, _ord, n_valid, n_na = dt.quantiles(d, PROBS, cls, counts)
+        qc = dt.quantiles(d, PROBS, cls, counts, mx_all)[0] if scale_max else q
+        hist, outside = dt.histogram(d, bn, cls, counts)
+        rq2, rorder2, rnv, rna, rhist, rout = brute_quantiles(m5, cls, PROBS, d.value(bn))
+        assert np.array_equal(hist, rhist) and np.array_equal(outside, rout) and np.array_equal(n_valid, rnv)
+        assert np.array_equal(bits(order2), bits(rorder2)) and np.array_equal(bits(q), bits(rq2[1]))
+        assert np.array_equal(bits(qc), bits(rq2[0]))
+        # the rectangle: its own maximum, not the stacked triangle's
+        for Sq in (5, 8):
+            r = dt.rect(d, Sq)
+            mx_r = r.max_taumax()
+            mask = np.zeros((S, S), dtype=bool)
+            mask[:Sq, Sq:] = True
+            rect5 = np.ascontiguousarray(d.planes(mask, scale_max, pplane)[:, :Sq, Sq:])
+            assert cross_checker.max_taumax(rect5) == mx_r
+            for k in (1, 7, r.Sr):
+                idx, _keys, topraw, n_valid = dt.cross_topk(d, Sq, k)
+                ridx, rvals, rn = cross_checker.brute_cross_topk(rect5, k)
+                assert np.array_equal(idx, ridx) and np.array_equal(n_valid, rn)
+                qrows = np.arange(Sq)[:, None]
+                want = dt.carried(d, qrows, np.where(idx >= 0, idx + Sq, -1), mx_r, scale_max, pplane[qrows, np.maximum(idx, 0) + Sq])
+                assert np.array_equal(bits(want), bits(rvals))
+            ref_cls = np.ascontiguousarray(gpu_base._classes(d, "na-class")[0][Sq:])
+            cm = dt.cross_class_table(d, Sq, ref_cls, n_class)
+            med2, n_valid = brute_cross_class(rect5, ref_cls, n_class)
+            assert np.array_equal(cm["n_valid"], n_valid) and np.array_equal(bits(cm["med"]), bits(med2[1]))
+            assert np.array_equal(bits(dt.median_cor(d, cm, mx_r) if scale_max else cm["med"]), bits(med2[0]))
+    # the entries that take raw alone: ranks, quantised dissimilarities, sorted p-values, the forest
+    perms = anosim_checker.documented_permutations(cls, 7, seed=11)
+    got, want = dt.anosim(d, cls, n_class, perms), anosim_checker.brute_anosim(d.raw, cls, n_class, perms)
+    for name in got:
+        _same_item(got[name], want[name], name)
+    for dd in (d, dt.valid_columns(d)):
+        c2 = cls if dd is d else np.ascontiguousarray(cls[d.kind == dt.VALID])
+        p2 = anosim_checker.documented_permutations(c2, 7, seed=11)
+        got, want = dt.permanova(dd, c2, n_class, p2), permanova_checker.brute_permanova(dd.raw, c2, n_class, p2)
+        for name in got:
+            _same_item(got[name], want[name], name)
+        from tests import permdisp_checker
+        n_val, n_na, Q, T, A, sizes = dt.permdisp_table(dd, c2, n_class)
+        assert (n_val, n_na, Q, T.tolist(), A, sizes) == permdisp_checker.brute_table(dd.raw, c2, n_class)
+    for alternative, one_sided in (("two.sided", False), ("greater", True)):
+        plane = _oracle_plane(d, perspective, 1, alternative)
+        i, j, _k, n_na = dt.triangle(d)
+        keys, count, fi, fj, _n = dt.pvalue_keys(d, one_sided)
+        at = np.searchsorted(keys, d.pvalue_id(i, j, one_sided))
+        assert np.array_equal(bits(plane[i, j]), bits(plane[fi, fj][at]))     # p is a function of (num, den, n_eff) alone
+        p, got_na = dt.sorted_pvalues(d, plane[fi, fj], one_sided)
+        want, want_na = padjust_checker.sorted_tests(np.where(np.triu(np.ones(plane.shape, dtype=bool), 1), plane, np.nan))
+        assert got_na == want_na == n_na and np.array_equal(bits(p), bits(want))
+    print(key, perspective, "max_taumax: all", mx_all, "within-class", mx_in, "rectangles", dt.rect(d, 5).max_taumax(),
+          dt.rect(d, 8).max_taumax(), "distinct keys", d.K)
+
+
+@pytest.mark.parametrize("key", CENS130)
+def test_replayed_defects_show_on_the_censored_designs(key):
+    """Five defects restated in numpy on the entry references (not the kernels); each must change the answer on every
+    S = 130 censored design of the GPU files, under both perspectives.  Cells counted over: top-7 of every sample (cor by
+    the all-pairs maximum), class_medians (the within-class maximum), class_matrix (all pairs) and the 8-query rectangle
+    (its own maximum).  (d) cannot show on the ties-only variant, where nothing is missing and the perspectives agree:
+    it is asserted to be 0 there."""
+    d0 = _gpu_design(key)
+    S, Sq = d0.S, 8
+    cls, n_class = gpu_base._labels_that_split_the_maximum(d0) if key == "cens64-apart" else _cens_classes(d0)
+    same = cls[:, None] == cls[None, :]
+    rows = np.arange(S)[:, None]
+    differ = lambda x, y: int(np.sum(bits(x) != bits(y)))               # noqa: E731
+    for perspective in ("global", "local"):
+        d, g = d0.under(perspective), d0.under("global")
+        mx_all, mx_in = d.max_taumax(), d.max_taumax(same)
+        idx = dt.topk(d, 7)[0]
+        top = dt.carried(d, rows, idx, mx_all)
+        own, cm = dt.class_medians(d, cls), dt.class_matrix(d, cls, n_class)
+        r = dt.rect(d, Sq)
+        mx_r = r.max_taumax()
+        rraw = r.raw[r.valid]
+        last = max(int(i) for i in np.nonzero(np.triu(d.valid, 1).any(axis=1))[0])      # a row per block: the last block
+        mask = np.zeros((S, S), dtype=bool)
+        mask[last, last + 1:] = True
+        mx_last = d.max_taumax(mask)
+        n = {
+            "a": differ(top[0], top[1]) + differ(dt.median_cor(d, own, mx_in), own["med"])
+                 + differ(dt.median_cor(d, cm, mx_all), cm["med"]) + differ(dt.cor_value(rraw, mx_r), rraw),
+            "b": differ(dt.median_cor(d, own, mx_all), dt.median_cor(d, own, mx_in))
+                 + differ(dt.median_cor(d, cm, mx_in), dt.median_cor(d, cm, mx_all))
+                 + differ(dt.cor_value(rraw, mx_all), dt.cor_value(rraw, mx_r)),
+            "c": differ(top[3], top[4]),
+            "d": int(np.sum(dt.topk(g, 7)[0] != idx)) + differ(dt.carried(g, rows, idx, g.max_taumax()), top),
+            "e": differ(dt.carried(d, rows, idx, mx_last)[0], top[0]) + differ(dt.median_cor(d, cm, mx_last), dt.median_cor(d, cm, mx_all)),
+        }
+        print(key, perspective, "cells that change under the replayed defects", n, "max_taumax all / within / rectangle / last block",
+              mx_all, mx_in, mx_r, mx_last)
+        assert n["a"] > 0 and n["b"] > 0 and n["c"] > 0 and n["e"] > 0
+        if perspective == "local":
+            assert (n["d"] > 0) == (key != "cens64-ties")

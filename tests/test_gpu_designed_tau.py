@@ -4,7 +4,10 @@ the library and no oracle run, so it reaches the key space and the sizes that th
 
 Every test first asserts that Context.pairs gives the closed form BITWISE on the first 2 000 combn pairs of its input
 (_closed_form_pairs).  From there every float an entry returns -- raw, cor, taumax, medians, order statistics,
-quantiles -- is compared bitwise with num / m, and every index, count and ordering with the integers."""
+quantiles -- is compared bitwise with num / m, and every index, count and ordering with the integers.
+
+The censored family (test_censored_*, at the end) has taumax, completeness and max_taumax below 1: there the
+precondition also holds taumax, completeness and the counts, and every carried plane and cor's divisor is compared."""
 import time
 
 import numpy as np
@@ -62,6 +65,13 @@ def _design(key):
             "rev24-2049": lambda: dt.reversals(2049, 24, seed=3, n_all_missing=1, n_constant=1),
             "rev24-4098": lambda: dt.reversals(4098, 24, seed=4),
             "rev24-5794": lambda: dt.reversals(5794, 24, seed=5, n_all_missing=1, n_constant=1),
+            # tied, left-censored columns (64 rows: a bottom block of 8 with 3 NaN, 28 adjacent pairs of which 5 are
+            # tied).  No two columns alike but the first two valid ones: the one pair with taumax == 1, in the first block
+            "cens64": lambda: dt.censored(130, 64, 8, 3, 5, seed=1, n_lib=6, max_overlap=1, n_all_missing=1, n_constant=1),
+            "cens64-ties": lambda: dt.censored(130, 64, 8, 3, 5, seed=1, variant="ties", n_lib=6, max_overlap=1, n_all_missing=1, n_constant=1),
+            # no two columns alike at all: every taumax is below 1, so cor != raw under every entry's rule
+            "cens64-apart": lambda: dt.censored(130, 64, 8, 3, 5, seed=2, own_state=True, twin=False, n_all_missing=2, n_constant=1),
+            "cens64-2049": lambda: dt.censored(2049, 64, 8, 3, 5, seed=3, n_lib=56, n_all_missing=1, n_constant=1),
         }[key]()
     return _DESIGN[key]
 
@@ -74,6 +84,10 @@ def _closed_form_pairs(ctx, key, perspectives=("global", "local")):
             continue
         pi, pj = combn_pairs(d.S)
         pi, pj = pi[:2000], pj[:2000]
+        if isinstance(d, dt.Censored):
+            _censored_pairs(ctx, d.under(perspective), key, perspective, pi, pj)
+            _PAIRS_OK.add((key, perspective))
+            continue
         out, _cnt, rsn = ctx.pairs(d.X, pi, pj, perspective=perspective, want_counts=False)
         ok = d.valid[pi, pj]
         want = d.value(d.num[pi, pj])
@@ -86,6 +100,76 @@ def _closed_form_pairs(ctx, key, perspectives=("global", "local")):
         assert np.all(np.isnan(out[~ok]))
         _PAIRS_OK.add((key, perspective))
     return d
+
+
+def _censored_pairs(ctx, dv, key, perspective, pi, pj):
+    """the precondition on the censored family: raw and taumax bitwise, the eleven counts and the reasons exact,
+    completeness bitwise the float64 expression 1.0 - missing / n_eff and within 1 ulp of the fraction, the p-value
+    within the device bound of tests/epilogue_checker.check_call (4 E_CPU) of the exact epilogue on the design's counts"""
+    from fractions import Fraction
+    from tests import epilogue_checker as E
+    out, cnt, rsn = ctx.pairs(dv.X, pi, pj, perspective=perspective)
+    ok = dv.valid[pi, pj]
+    a, b = pi[ok], pj[ok]
+    counts = dv.counts(a, b)
+    diff = {name: int(np.sum(bits(out[ok, col]) != bits(want))) for name, col, want in
+            (("raw", 0, dv.raw[a, b]), ("taumax", 2, dv.taumax(a, b)), ("completeness", 3, dv.completeness(a, b)))}
+    bad_counts = int(np.sum((cnt[ok][:, :11] != counts).any(axis=1)))
+    first = np.nonzero(bits(out[ok, 0]) != bits(dv.raw[a, b]))[0][:3]
+    print(key, perspective, "pairs checked", len(pi), "valid", int(ok.sum()), "bits that differ", diff, "count records", bad_counts,
+          [(int(dv.num[a[q], b[q]]), int(dv.den(a[q], b[q])), float(out[ok, 0][q]).hex()) for q in first])
+    assert np.array_equal(rsn, dv.reasons()[pi, pj]) and np.all(np.isnan(out[~ok]))
+    assert bad_counts == 0
+    assert diff["raw"] == 0 and diff["taumax"] == 0 and diff["completeness"] == 0
+    miss, ne = dv.missing(a, b), dv.n_eff(a, b)
+    for g, m_, e in set(zip(out[ok, 3].tolist(), miss.tolist(), ne.tolist())):
+        exact = Fraction(e - m_, e)
+        assert abs(Fraction(g) - exact) <= Fraction(float(np.spacing(float(exact))))
+    worst = E.check_call(out[ok], counts, "two.sided", False, 4 * E.E_CPU["cases"], f"{key} {perspective}")
+    print(key, perspective, "worst scaled p error", worst["p"])
+
+
+def _p_of(ctx, dv, perspective):
+    """p(a, b) for index arrays of valid pairs: one Context.pairs p-value per distinct (|num|, den, n_eff) of the design,
+    looked up per pair -- the p-value has no closed form"""
+    cache = dv.__dict__.setdefault("_p_table", {})
+    if perspective not in cache:
+        keys, _count, fi, fj, _n_na = dt.pvalue_keys(dv)
+        cache[perspective] = keys, _pvalues(ctx, dv, fi, fj, perspective)
+    keys, p = cache[perspective]
+
+    def look(a, b):
+        a, b = np.asarray(a), np.asarray(b)
+        return p[np.searchsorted(keys, dv.pvalue_id(np.minimum(a, b), np.maximum(a, b)))]
+    return look
+
+
+def _labels_that_split_the_maximum(d0):
+    """two classes such that every pair at the largest taumax, under either perspective, lies across them: the
+    within-class maximum is then strictly below the all-pairs one (a 2-colouring of those few pairs)"""
+    S = d0.S
+    near = [[] for _ in range(S)]
+    for perspective in ("global", "local"):
+        d = d0.under(perspective)
+        a, b = np.nonzero(np.triu(d.valid, 1))
+        tm = d.taumax(a, b)
+        for x, y in zip(a[tm == tm.max()], b[tm == tm.max()]):
+            near[x].append(int(y))
+            near[y].append(int(x))
+    colour = np.full(S, -1, dtype=np.int32)
+    for s in range(S):
+        if colour[s] >= 0:
+            continue
+        colour[s] = s % 2 if not near[s] else 0
+        todo = [s]
+        while todo:
+            x = todo.pop()
+            for y in near[x]:
+                assert colour[y] != colour[x], "the pairs at the maximum have an odd cycle"
+                if colour[y] < 0:
+                    colour[y] = 1 - colour[x]
+                    todo.append(y)
+    return colour, 2
 
 
 def _classes(d, kind):
@@ -407,3 +491,130 @@ def test_5794_samples_cut_the_triangle(hip_ctx, monkeypatch):
     got = _timed("S=5794 class_matrix", lambda: hip_ctx.class_matrix(d.X))
     _assert_class_matrix(got, d, dt.class_matrix(d))
     assert got[3].sum() == total
+
+
+# ---- the censored family: taumax, completeness and cor differ from each other, from raw and from 1 ---------------------
+
+CENS130 = ["cens64", "cens64-ties", "cens64-apart"]
+
+
+@pytest.mark.parametrize("spec", ["tkblock=1", "tkblock=4200"])
+@pytest.mark.parametrize("key", CENS130)
+def test_censored_selection_entries(plan_ctx, key, spec):
+    """topk, edges, class_medians, class_matrix and quantiles on tied, left-censored columns: every carried plane bitwise
+    (cor by the entry's own divisor, taumax and completeness each in its place), under a row per block and under a
+    triangle cut in the middle (8 385 pairs in blocks of at most 4 200)"""
+    ctx = plan_ctx
+    d0 = _closed_form_pairs(ctx, key)
+    S = d0.S
+    cls, n_class = _classes(d0, "interleaved")
+    same = cls[:, None] == cls[None, :]
+    rows = np.arange(S)[:, None]
+    ctx.debug_set_plan(spec)
+    seen = {}
+    for perspective, scale_max in CONFIGS:
+        d = d0.under(perspective)
+        p_of = _p_of(ctx, d, perspective)
+        tail = (None, perspective, "two.sided", False, 0, scale_max)
+        mx_all, mx_in, rc5 = d.max_taumax(), d.max_taumax(same), d.reason_counts()
+        # top-k
+        k = 7
+        idx, keys, _raw, n_valid = dt.topk(d, k)
+        tied = (d.valid & (d.key >= keys[:, k - 1][:, None])).sum(axis=1) > k
+        gidx, vals, gn, mx, grc = ctx.topk(d.X, k, *tail)
+        want = dt.carried(d, rows, idx, mx_all, scale_max, p_of(np.broadcast_to(rows, idx.shape), np.maximum(idx, 0)))
+        print(key, spec, perspective, scale_max, "topk: tied across the k-th", int(tied.sum()), "planes differing",
+              [int(np.sum(bits(vals[q]) != bits(want[q]))) for q in range(5)], "max_taumax", mx, mx_all, mx_in)
+        assert tied.sum() >= 10 and np.array_equal(gidx, idx) and np.array_equal(gn, n_valid)
+        assert np.array_equal(bits(vals), bits(want)) and mx == mx_all and np.array_equal(grc, rc5)
+        seen[(perspective, scale_max)] = vals[0].copy()
+        # edges: the key most pairs equal, a completeness many pairs equal, a p-value of the table
+        cnt = dt.group_counts(d)[0][0]
+        t = int(np.argmax(cnt)) - d.K
+        a, b = np.nonzero(d.valid)
+        comp, pp = np.full((S, S), np.nan), np.full((S, S), np.nan)
+        comp[a, b], pp[a, b] = d.completeness(a, b), p_of(a, b)
+        cvals, ccnt = np.unique(comp[a, b], return_counts=True)
+        c0 = float(cvals[np.argmax(ccnt)])
+        p0 = float(np.sort(pp[a, b])[len(a) // 2])                         # a value of the p table itself
+        for also, bounds in ((None, (None, None)), ((comp >= c0) & (pp <= p0), (p0, c0))):
+            for absolute in (False, True):
+                ei, ej, _k, _r, n_edges, degree = dt.edges(d, t, absolute, also)
+                gi, gj, vals, gn, gdeg, mx, grc = ctx.edges(d.X, float(d.value(t)), bounds[0], bounds[1], absolute, n_edges, *tail)
+                assert gn == n_edges > 0 and np.array_equal(gi, ei) and np.array_equal(gj, ej) and np.array_equal(gdeg, degree)
+                assert np.array_equal(bits(vals), bits(dt.carried(d, ei, ej, mx_all, scale_max, p_of(ei, ej))))
+                assert mx == mx_all and np.array_equal(grc, rc5)
+        on_bounds = int(np.sum(d.valid & (comp == c0))) // 2, int(np.sum(d.valid & (pp == p0))) // 2
+        print("edges: pairs on the key", int(cnt[t + d.K]), "on min_completeness", on_bounds[0], "on max_pvalue", on_bounds[1])
+        assert cnt[t + d.K] >= 100 and on_bounds[0] >= 100 and on_bounds[1] >= 1
+        # medians: class_medians scales by the within-class pairs' maximum, class_matrix by all pairs', on the same labels
+        own, cm = dt.class_medians(d, cls), dt.class_matrix(d, cls, n_class)
+        med2, gn, mx, grc = ctx.class_medians(d.X, cls, n_class, *tail)
+        assert np.array_equal(gn, own["n_valid"]) and np.array_equal(bits(med2[1]), bits(own["med"]))
+        assert np.array_equal(bits(med2[0]), bits(dt.median_cor(d, own, mx_in) if scale_max else own["med"]))
+        assert mx == mx_in and np.array_equal(grc, _rc5(d, cls))
+        med2, gn, mx, grc = ctx.class_matrix(d.X, cls, n_class, *tail)
+        assert np.array_equal(gn, cm["n_valid"]) and np.array_equal(bits(med2[1]), bits(cm["med"]))
+        assert np.array_equal(bits(med2[0]), bits(dt.median_cor(d, cm, mx_all) if scale_max else cm["med"]))
+        assert mx == mx_all and np.array_equal(grc, rc5)
+        # quantiles and histogram
+        counts = dt.group_counts(d, cls)
+        bn = (np.nonzero(counts[0][0])[0] - d.K)[1:-1:3]
+        q, order2, _o, nv, nna = dt.quantiles(d, PROBS, cls, counts)
+        qc = dt.quantiles(d, PROBS, cls, counts, mx_all)[0] if scale_max else q
+        hist, outside = dt.histogram(d, bn, cls, counts)
+        q2, go2, gnv, gna, gh, gout, mx, grc = ctx.quantiles(d.X, PROBS, d.value(bn), cls, n_class, *tail)
+        assert np.array_equal(gnv, nv) and np.array_equal(gna, nna) and np.array_equal(gh, hist) and np.array_equal(gout, outside)
+        assert np.array_equal(bits(go2), bits(order2)) and np.array_equal(bits(q2[1]), bits(q)) and np.array_equal(bits(q2[0]), bits(qc))
+        assert mx == mx_all and np.array_equal(grc, rc5)
+        if key == "cens64-apart":            # labels under which the two rules differ on this design too
+            cls2, n2 = _labels_that_split_the_maximum(d0)
+            in2 = d.max_taumax(cls2[:, None] == cls2[None, :])
+            assert in2 < mx_all
+            own, cm = dt.class_medians(d, cls2), dt.class_matrix(d, cls2, n2)
+            med2, gn, mx, grc = ctx.class_medians(d.X, cls2, n2, *tail)
+            assert mx == in2 and np.array_equal(bits(med2[1]), bits(own["med"]))
+            assert np.array_equal(bits(med2[0]), bits(dt.median_cor(d, own, in2) if scale_max else own["med"]))
+            med2, gn, mx, grc = ctx.class_matrix(d.X, cls2, n2, *tail)
+            assert mx == mx_all and np.array_equal(bits(med2[1]), bits(cm["med"]))
+            assert np.array_equal(bits(med2[0]), bits(dt.median_cor(d, cm, mx_all) if scale_max else cm["med"]))
+    dg = d0.under("global")
+    if key in ("cens64", "cens64-ties"):     # the one pair with taumax == 1 lies across two classes, in the first block
+        assert dg.max_taumax() == 1.0 > dg.max_taumax(same) and dg.taumax(0, 1) == 1.0
+    if key == "cens64-apart":                # every taumax below 1: scale_max changes cor under every rule
+        assert dg.max_taumax() < 1.0 and not np.array_equal(bits(seen[("global", True)]), bits(seen[("global", False)]))
+        assert not np.array_equal(bits(seen[("local", True)]), bits(seen[("local", False)]))
+    if key != "cens64-ties":                 # the perspectives differ
+        assert not np.array_equal(bits(seen[("global", False)]), bits(seen[("local", False)]))
+
+
+def test_2049_samples_censored_topk_and_edges(hip_ctx):
+    """2 098 176 pairs of censored columns under the natural plan, global"""
+    d = _closed_form_pairs(hip_ctx, "cens64-2049", ("global",))
+    p_of = _p_of(hip_ctx, d, "global")
+    rows = np.arange(d.S)[:, None]
+    mx_all = d.max_taumax()
+    idx, _k, _r, n_valid = _timed("S=2049 censored topk, the reference", lambda: dt.topk(d, 5))
+    gidx, vals, gn, mx, rc5 = _timed("S=2049 censored topk", lambda: hip_ctx.topk(d.X, 5))
+    assert np.array_equal(gidx, idx) and np.array_equal(gn, n_valid) and mx == mx_all == 1.0
+    want = dt.carried(d, rows, idx, mx_all, True, p_of(np.broadcast_to(rows, idx.shape), np.maximum(idx, 0)))
+    assert np.array_equal(bits(vals), bits(want)) and np.array_equal(rc5, d.reason_counts())
+    t = d.K - 3
+    ei, ej, _k, _r, n_edges, degree = _timed("S=2049 censored edges, the reference", lambda: dt.edges(d, t))
+    gi, gj, vals, gn, gdeg, mx, rc5 = _timed("S=2049 censored edges", lambda: hip_ctx.edges(d.X, float(d.value(t)), max_edges=n_edges))
+    print("edges", n_edges)
+    assert gn == n_edges > 100 and np.array_equal(gi, ei) and np.array_equal(gj, ej) and np.array_equal(gdeg, degree)
+    assert np.array_equal(bits(vals), bits(dt.carried(d, ei, ej, mx_all, True, p_of(ei, ej)))) and mx == mx_all
+
+
+def test_2049_samples_censored_quantiles(hip_ctx):
+    """the second trip of k_quant_count's tile loop on keys with runs of tens of thousands; the one pair with taumax == 1
+    is the first of the triangle, so q_cor == q_raw only if the divisor is the maximum of ALL pairs"""
+    d = _closed_form_pairs(hip_ctx, "cens64-2049", ("global",))
+    cls, n_class = _five_classes(d.S)
+    counts = _timed("S=2049 censored quantiles, the reference's counts", lambda: dt.group_counts(d, cls))
+    assert counts[0][0].max() > 10 * 1024 and d.max_taumax() == 1.0 == d.taumax(0, 1)
+    assert d.max_taumax(columns=np.arange(1, d.S)) < 1.0
+    bn = (np.nonzero(counts[0][0])[0] - d.K)[1:-1:3]
+    got = _timed("S=2049 censored quantiles", lambda: hip_ctx.quantiles(d.X, PROBS, d.value(bn), cls, n_class))
+    _assert_quantiles(got, d, cls, PROBS, bn, counts)

@@ -9,7 +9,8 @@ Every test first asserts that Context.pairs gives the closed form BITWISE on the
 (_closed_form_pairs).  From there integers compare as integers and doubles by their bits.  The p-value has no closed
 form: a p-value plane is compared with Context.pairs on the same pairs, and padjust's sorted p-values are one
 Context.pairs p-value per distinct numerator, repeated by its count.  hclust's reference is
-tests/hclust_checker.brute_hclust on the closed-form matrix, which is independent of the library."""
+tests/hclust_checker.brute_hclust on the closed-form matrix, which is independent of the library.  The censored family
+(test_censored_*, at the end) adds taumax, completeness and max_taumax below 1 and perspectives that differ."""
 import numpy as np
 import pytest
 
@@ -53,6 +54,9 @@ _MORE = {
     "rev24-4104": lambda: dt.reversals(4104, 24, seed=6, values=[0, 9, 24], flip=0.3),
     "halves-2049": lambda: _plus_minus(2049, 24, 7, split=1024),
     "plus-minus-5794": lambda: _plus_minus(5794, 24, 9),
+    # tied, left-censored columns; no two alike but columns 0 and 1, the one pair with taumax == 1.  No column is
+    # reflected: every raw is positive (0.96 .. 1), and the largest 15 % of the values connect every sample
+    "cens64-5795": lambda: dt.censored(5795, 64, 8, 3, 5, seed=5, n_lib=56, flip=0.0),
 }
 
 
@@ -879,3 +883,227 @@ def test_5794_samples_permdisp_with_na_columns(hip_ctx, monkeypatch):
     got, ref = _permdisp_at_size(hip_ctx, "rev24-5794", cls, n_class, "S=5794 permdisp, NA columns")
     assert ref[0] + ref[1] == total and ref[1] == 2 * d.S - 3
     _na_rows_are_zero(d, ref, got)
+
+
+# ---- the censored family: taumax, completeness and cor differ from each other, from raw and from 1 ---------------------
+
+CENS130 = ["cens64", "cens64-ties", "cens64-apart"]
+
+
+def _first_part_holds_the_maximum(d, Sq):
+    """the design's columns reordered: query 0 has a partner at the largest taumax of all pairs, the other queries have
+    none, and neither has the reference: the rectangle's maximum lies in the first stitched part alone"""
+    a, b = np.nonzero(d.valid)
+    tm = np.full((d.S, d.S), -np.inf)
+    tm[a, b] = d.taumax(a, b)
+    row_max = tm.max(axis=1)
+    top = row_max.max()
+    q0 = int(np.argmax(row_max == top))
+    rest = np.nonzero((row_max < top) & (d.kind == dt.VALID))[0][:Sq - 1]
+    assert len(rest) == Sq - 1
+    queries = np.concatenate([[q0], rest])
+    return d.columns(np.concatenate([queries, np.setdiff1d(np.arange(d.S), queries)]))
+
+
+@pytest.mark.parametrize("spec", ["tkblock=1", "tkblock=4200"])
+@pytest.mark.parametrize("key", CENS130)
+def test_censored_mst_and_cross(plan_ctx, ref_ctx, key, spec):
+    """the tree's five values per edge, and the rectangle with its top-k and class table, scaled by the rectangle's own
+    maximum -- below the stacked triangle's on the designs with a twin pair among the queries -- and, from a prepared
+    reference with room for 3 of the 8 queries (the front end stitches three parts), rescaled across the parts"""
+    ctx = plan_ctx
+    d0 = _checked(ctx, key)
+    S, Sq, k = d0.S, 8, 7
+    ctx.debug_set_plan(spec)
+    for perspective, scale_max in CONFIGS:
+        d = d0.under(perspective)
+        p_of = base._p_of(ctx, d, perspective)
+        tail = (None, perspective, "two.sided", False, 0, scale_max)
+        mx_all, rc5 = d.max_taumax(), d.reason_counts()
+        ref = _ref(("mst", key, perspective), lambda: brute_mst(d.raw))
+        ti, tj, vals, component, n_comp, _rounds, mx, grc = ctx.mst(d.X, None, *tail)
+        assert np.array_equal(ti, ref[0]) and np.array_equal(tj, ref[1]) and np.array_equal(component, ref[2]) and n_comp == ref[3]
+        want = dt.carried(d, ref[0], ref[1], mx_all, scale_max, p_of(ref[0], ref[1]))
+        print(key, spec, perspective, scale_max, "mst planes differing", [int(np.sum(bits(vals[q]) != bits(want[q]))) for q in range(5)])
+        assert np.array_equal(bits(vals), bits(want)) and mx == mx_all and np.array_equal(grc, rc5)
+        # the rectangle
+        dd = _first_part_holds_the_maximum(d, Sq) if key == "cens64-apart" else d
+        pp = p_of if dd is d else base._p_of(ctx, dd, perspective)
+        r = dt.rect(dd, Sq)
+        mx_r = r.max_taumax()
+        parts = [r.max_taumax(np.arange(q, min(q + 3, Sq))) for q in range(0, Sq, 3)]
+        print("max_taumax: triangle", dd.max_taumax(), "rectangle", mx_r, "stitched parts", parts)
+        if key == "cens64-apart":
+            assert parts[0] == mx_r and max(parts[1:]) < mx_r
+        elif perspective == "global":
+            assert mx_r < dd.max_taumax() == 1.0                      # both twins are queries
+        qa, ra = np.nonzero(r.valid)
+        want5 = np.full((5, Sq, r.Sr), np.nan)
+        want5[:, qa, ra] = dt.carried(dd, qa, ra + Sq, mx_r, scale_max, pp(qa, ra + Sq))
+        idx, _keys, _raw, n_valid = dt.cross_topk(dd, Sq, k)
+        qrows = np.arange(Sq)[:, None]
+        wantk = dt.carried(dd, qrows, np.where(idx >= 0, idx + Sq, -1), mx_r, scale_max,
+                           pp(np.broadcast_to(qrows, idx.shape), np.maximum(idx, 0) + Sq))
+        ref_cls, n_class = _ref_classes(dd, Sq)
+        cm = dt.cross_class_table(dd, Sq, ref_cls, n_class)
+        got = ctx.cross(r.Q, r.R, k, True, *tail)
+        ref_ctx.prepare_reference(r.R, Sq)
+        prepared = ref_ctx.cross_prepared(r.Q, k, True, ref_cls, n_class, perspective, "two.sided", False, 0, scale_max)
+        for out5, gidx, vals, gn, mx, grc in (got, prepared[:6]):
+            ok = r.valid
+            assert np.all(np.isnan(out5[:, ~ok])) and np.array_equal(bits(out5[:, ok]), bits(want5[:, ok]))
+            assert np.array_equal(gidx, idx) and np.array_equal(gn, n_valid) and np.array_equal(bits(vals), bits(wantk))
+            assert mx == mx_r and np.array_equal(grc, r.reason_counts())
+        med2, gnv = prepared[6], prepared[7]
+        assert np.array_equal(gnv, cm["n_valid"]) and np.array_equal(bits(med2[1]), bits(cm["med"]))
+        assert np.array_equal(bits(med2[0]), bits(dt.median_cor(dd, cm, mx_r) if scale_max else cm["med"]))
+        # the front end against a reference prepared with room for 3 of the 8 queries: three stitched parts
+        from icikendalltau_amd import api
+        levels = np.unique(ref_cls)
+        import warnings
+        with warnings.catch_warnings(), api.prepare_reference(r.R, 3, reference_names=["r%d" % i for i in range(r.Sr)],
+                                                              reference_classes=["c%d" % c for c in ref_cls]) as kept:
+            warnings.simplefilter("ignore")
+            res = api.ici_kendalltau_cross(r.Q, kept, k, True, perspective=perspective, scale_max=scale_max,
+                                           query_names=["q%d" % i for i in range(Sq)])
+        assert res["class_levels"] == ["c%d" % c for c in levels] and len(levels) < 10 and res["max_taumax"] == mx_r
+        for f, name in enumerate(("cor", "raw", "pvalue", "taumax", "completeness")):
+            got5, gotk = np.asarray(res[name], dtype=np.float64), np.asarray(res["topk_" + name], dtype=np.float64)
+            assert np.array_equal(bits(got5[ok]), bits(want5[f][ok])), name
+            assert np.array_equal(bits(gotk), bits(wantk[f])), name
+        assert np.array_equal(np.asarray(res["indices"]), idx) and np.array_equal(np.asarray(res["class_n_valid"]), cm["n_valid"][:, levels])
+        med_cor = (dt.median_cor(dd, cm, mx_r) if scale_max else cm["med"])[:, levels]
+        got_raw, got_cor = (np.asarray(res[q], dtype=np.float64) for q in ("class_med_raw", "class_med_cor"))
+        print("stitched class table: cells", got_cor.size, "med_cor differing", int(np.sum(bits(got_cor) != bits(med_cor))))
+        assert np.array_equal(bits(got_raw), bits(cm["med"][:, levels]))
+        assert np.array_equal(bits(got_cor), bits(med_cor))
+        # and without the matrix: no part keeps its raw, so a part below the call's maximum is asked for it once more
+        with warnings.catch_warnings(record=True) as told, api.prepare_reference(
+                r.R, 3, reference_names=["r%d" % i for i in range(r.Sr)], reference_classes=["c%d" % c for c in ref_cls]) as kept:
+            warnings.simplefilter("always")
+            asked, batch = [], kept._batch
+            kept._batch = lambda *a: (asked.append(a[2]), batch(*a))[1]                 # a[2]: want_matrix
+            res = api.ici_kendalltau_cross(r.Q, kept, None, False, perspective=perspective, scale_max=scale_max,
+                                           query_names=["q%d" % i for i in range(Sq)])
+        again = asked[3:]
+        told = [str(x.message) for x in told if str(x.message).startswith("Warning:")]
+        print("split without the matrix: parts asked again", len(again), "warnings", len(told))
+        assert asked[:3] == [False] * 3 and (len(again) == 2 and all(again)) == (key == "cens64-apart" and scale_max)
+        assert "raw" not in res and res["max_taumax"] == mx_r
+        assert len(told) == r.reason_counts()[2:].sum() > 0       # one per pair with a constant column, asked again or not
+        assert np.array_equal(bits(np.asarray(res["class_med_cor"], dtype=np.float64)), bits(med_cor))
+        assert np.array_equal(bits(np.asarray(res["class_med_raw"], dtype=np.float64)), bits(cm["med"][:, levels]))
+
+
+@pytest.mark.parametrize("key", CENS130)
+def test_censored_entries_of_raw_alone(hip_ctx, key):
+    """anosim, permanova, permdisp, padjust and hclust take raw (or the p-value) alone; on censored columns the two
+    perspectives give different matrices, max_taumax is not 1 and raw has ties"""
+    d0 = _checked(hip_ctx, key)
+    for perspective in PERSPECTIVES:
+        d = d0.under(perspective)
+        cls, n_class, perms = _small_labels(d, key, "interleaved")
+        _assert_anosim(hip_ctx.anosim(d.X, cls, n_class, perms, None, perspective), dt.anosim(d, cls, n_class, perms), d)
+        _assert_permanova(hip_ctx.permanova(d.X, cls, n_class, perms, None, perspective), dt.permanova(d, cls, n_class, perms), d)
+        _assert_permdisp(hip_ctx.permdisp(d.X, cls, n_class, None, perspective), dt.permdisp_table(d, cls, n_class), d)
+        v = dt.valid_columns(d)
+        vcls = np.ascontiguousarray(cls[d.kind == dt.VALID])
+        vperms = documented_permutations(vcls, 33, seed=13)
+        ref = dt.permanova(v, vcls, n_class, vperms)
+        assert ref["n_pairs"][1] == 0 and sum(ref["class_q"][0]) > 0
+        _assert_permanova(hip_ctx.permanova(v.X, vcls, n_class, vperms, None, perspective), ref, v)
+        keys, count, fi, fj, _n_na = dt.pvalue_keys(d)
+        p, n_na = dt.sorted_pvalues(d, base._pvalues(hip_ctx, d, fi, fj, perspective))
+        for method in ("BH", "holm"):
+            _padjust_case(hip_ctx, d, p, n_na, method, perspective, "two.sided")
+        for method in ("complete", "average", "single"):
+            _assert_hclust_raw(hip_ctx.hclust(d.X, method, None, None, perspective), brute_hclust(d.raw, method), d)
+
+
+def _assert_hclust_raw(got, ref, d):
+    """_assert_hclust where taumax != 1: the heights of cor are those of raw, each divided by max_taumax (the tree is
+    built on raw; one more float64 division per height)"""
+    ra, rb, rsize, rraw, rcomp, rn = ref
+    ma, mb, msize, mraw, mcor, component, n_comp, mx, rc5 = got
+    assert np.array_equal(ma, ra) and np.array_equal(mb, rb) and np.array_equal(msize, rsize)
+    assert np.array_equal(bits(mraw), bits(rraw)) and np.array_equal(component, rcomp) and n_comp == rn
+    assert mx == d.max_taumax() and np.array_equal(rc5, d.reason_counts())
+    print("hclust cor heights differing from raw / max_taumax", int(np.sum(bits(mcor) != bits(rraw / mx))), "of", len(rraw))
+    assert np.array_equal(bits(mcor), bits(rraw / mx))
+
+
+# ---- the censored family at the sizes where the kernels change behaviour (the natural plan, global) -------------------
+
+def test_2049_samples_censored_padjust(hip_ctx, monkeypatch):
+    _no_plan_override(monkeypatch)
+    d = _checked(hip_ctx, "cens64-2049", ("global",))
+    p, n_na, count = _sorted_p(hip_ctx, d, "global", "two.sided")
+    assert count.max() > 10 * 1024 and len(p) + n_na == d.S * (d.S - 1) // 2
+    kinds = _padjust_case(hip_ctx, d, p, n_na, "BH", "global", "two.sided", "S=2049 censored padjust BH")
+    assert "inside" in kinds
+    base._DESIGN.pop("cens64-2049")
+
+
+def _censored_cut_in_two(ctx):
+    """cens64-5795 with what the four tests below presuppose: the driver cuts the triangle, the largest taumax (1, the
+    pair (0, 1)) lies in the first block and every pair of the second block is strictly below it"""
+    d = _checked(ctx, "cens64-5795", ("global",))
+    S = d.S
+    _cut_in_two(d)
+    first_rows = int(np.searchsorted(np.cumsum(S - 1 - np.arange(S)), 1 << 24, side="right"))   # whole rows within 2^24 pairs
+    later = _ref("cens64-5795 later blocks", lambda: d.max_taumax(columns=np.arange(first_rows, S)))
+    mx = _ref("cens64-5795 max", d.max_taumax)
+    print("rows of the first block", first_rows, "max_taumax", mx, "of the later rows", later)
+    assert 1 < first_rows < S - 2 and d.taumax(0, 1) == mx == 1.0 and later < 1.0
+    assert d.max_taumax(columns=np.arange(1, S)) < 1.0                     # no other pair reaches it
+    return d
+
+
+def test_5795_samples_censored_class_matrix(hip_ctx, monkeypatch):
+    """med_cor == med_raw (a division by 1.0) only if the divisor comes from the first block"""
+    _no_plan_override(monkeypatch)
+    d = _censored_cut_in_two(hip_ctx)
+    cls, n_class = _five_classes(d.S)
+    cm = _timed("S=5795 censored class_matrix, the reference", lambda: dt.class_matrix(d, cls, n_class))
+    med2, n_valid, mx, rc5 = _timed("S=5795 censored class_matrix", lambda: hip_ctx.class_matrix(d.X, cls, n_class))
+    assert np.array_equal(n_valid, cm["n_valid"]) and np.array_equal(bits(med2[1]), bits(cm["med"]))
+    assert np.array_equal(bits(med2[0]), bits(dt.median_cor(d, cm, 1.0))) and mx == 1.0
+    assert np.array_equal(rc5, _ref(("reason_counts", "cens64-5795"), d.reason_counts))
+
+
+def test_5795_samples_censored_anosim(hip_ctx, monkeypatch):
+    _no_plan_override(monkeypatch)
+    d = _censored_cut_in_two(hip_ctx)
+    cls, n_class = _five_classes(d.S)
+    perms = documented_permutations(cls, 4, seed=13)
+    ref = _timed("S=5795 censored anosim, the reference", lambda: dt.anosim(d, cls, n_class, perms))
+    _assert_anosim(_timed("S=5795 censored anosim", lambda: hip_ctx.anosim(d.X, cls, n_class, perms)), ref, d)
+
+
+def test_5795_samples_censored_permanova(hip_ctx, monkeypatch):
+    _no_plan_override(monkeypatch)
+    d = _censored_cut_in_two(hip_ctx)
+    cls, n_class = _five_classes(d.S)
+    perms = documented_permutations(cls, 4, seed=13)
+    ref = _timed("S=5795 censored permanova, the reference", lambda: dt.permanova(d, cls, n_class, perms))
+    assert ref["n_pairs"][1] == 0 and all(all(row) for row in ref["class_q"])
+    _assert_permanova(_timed("S=5795 censored permanova", lambda: hip_ctx.permanova(d.X, cls, n_class, perms)), ref, d)
+
+
+def test_5795_samples_censored_mst(hip_ctx, monkeypatch):
+    """tests/mst_checker.brute_mst as the reference.  It is given the 15 % largest values alone: Kruskal takes the edges
+    in the strict order, so when those already connect every sample (asserted) the forest is the unbounded one"""
+    _no_plan_override(monkeypatch)
+    d = _censored_cut_in_two(hip_ctx)
+    cnt = dt.group_counts(d)[0][0]
+    above = np.cumsum(cnt[::-1])
+    t = d.K - int(np.searchsorted(above, 0.15 * above[-1]))
+    ref = _timed("S=5795 censored mst, the reference", lambda: brute_mst(d.raw, float(d.value(t))))
+    assert ref[3] == 1 and len(ref[0]) == d.S - 1
+    ti, tj, vals, component, n_comp, _rounds, mx, rc5 = _timed("S=5795 censored mst", lambda: hip_ctx.mst(d.X))
+    assert np.array_equal(ti, ref[0]) and np.array_equal(tj, ref[1]) and np.array_equal(component, ref[2]) and n_comp == 1
+    want = dt.carried(d, ref[0], ref[1], 1.0, True, base._p_of(hip_ctx, d, "global")(ref[0], ref[1]))
+    print("mst planes differing", [int(np.sum(bits(vals[q]) != bits(want[q]))) for q in range(5)])
+    assert np.array_equal(bits(vals), bits(want)) and mx == 1.0
+    base._DESIGN.pop("cens64-5795")
+    _REF.pop(("reason_counts", "cens64-5795"), None)
