@@ -29,6 +29,7 @@ SOURCES = [os.path.join(_PKG, "csrc", f) for f in ("icikt_kernels.hip", "icikt_p
                                                        "icikt_anosim.hip", "icikt_capi_anosim.cpp",
                                                        "icikt_permanova.hip", "icikt_capi_permanova.cpp",
                                                        "icikt_permdisp.hip", "icikt_capi_permdisp.cpp",
+                                                       "icikt_pcoa.hip", "icikt_capi_pcoa.cpp",
                                                        "icikt_cross.hip", "icikt_capi_cross.cpp")]
 HEADERS = [os.path.join(_ROOT, "include", "icikt.h"), os.path.join(_PKG, "csrc", "icikt_device.h"),
            os.path.join(_PKG, "csrc", "icikt_wave.h"), os.path.join(_PKG, "csrc", "icikt_host.h"),
@@ -36,7 +37,7 @@ HEADERS = [os.path.join(_ROOT, "include", "icikt.h"), os.path.join(_PKG, "csrc",
            os.path.join(_PKG, "csrc", "icikt_blocks.h"), os.path.join(_PKG, "csrc", "icikt_select.h"),
            os.path.join(_PKG, "csrc", "icikt_keys.h"), os.path.join(_PKG, "csrc", "icikt_k0plan.h"),
            os.path.join(_PKG, "csrc", "icikt_k1plan.h"), os.path.join(_PKG, "csrc", "icikt_fixed.h"),
-           os.path.join(_PKG, "csrc", "icikt_labels.h")]
+           os.path.join(_PKG, "csrc", "icikt_labels.h"), os.path.join(_PKG, "csrc", "icikt_ritz.h")]
 
 # include/icikt.h
 SUCCESS = 0
@@ -61,6 +62,8 @@ HCLUST = {"complete": 0, "average": 1, "single": 2}   # ICIKT_HCLUST_*: linkage 
 ANOSIM_MAX_PERM = 1000000     # ICIKT_ANOSIM_MAX_PERM: labellings per call of icikt_anosim_* beside the observed one
 PERMANOVA_MAX_CELLS = 1 << 26  # ICIKT_PERMANOVA_MAX_CELLS: (1 + n_perm) n_class of icikt_permanova_*
 PERMDISP_MAX_CELLS = 1 << 26   # ICIKT_PERMDISP_MAX_CELLS: n_samp n_class of icikt_permdisp_*
+PCOA_MAX_K = 64                # ICIKT_PCOA_MAX_K: eigenpairs per call of icikt_pcoa_*
+PCOA_MAX_BASIS = 512           # ICIKT_PCOA_MAX_BASIS: basis columns of icikt_pcoa_*
 MASK_VALS = 32                # distinct finite global_na values of the device-side exclusion rule (icikt_device.h)
 MAX_FEATURES = 65535          # the tuned kernels
 MAX_FEATURES_WIDE = 262144    # the plain 32-bit path (exact integer arithmetic)
@@ -102,6 +105,7 @@ EXPORTS = (
     "icikt_anosim_f64", "icikt_anosim_in", "icikt_anosim_csc",
     "icikt_permanova_f64", "icikt_permanova_in", "icikt_permanova_csc",
     "icikt_permdisp_f64", "icikt_permdisp_in", "icikt_permdisp_csc",
+    "icikt_pcoa_f64", "icikt_pcoa_in", "icikt_pcoa_csc", "icikt_pcoa_apply_dev",
     "icikt_cross_f64", "icikt_cross_in",
     "icikt_ref_prepare_f64", "icikt_ref_prepare_in", "icikt_ref_cross_f64", "icikt_ref_cross_in", "icikt_ref_info",
 )
@@ -406,6 +410,9 @@ def lib():
                                       c_int, c_vp, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]
     L.icikt_permdisp_f64.argtypes = [c_vp, c_vp, c_i64, c_i64, c_i64, c_vp, c_int, c_int, c_int, c_int, c_u32, c_vp,
                                      c_int, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]
+    L.icikt_pcoa_f64.argtypes = [c_vp, c_vp, c_i64, c_i64, c_i64, c_vp, c_int, c_int, c_int, c_int, c_u32, c_int,
+                                 ctypes.c_double, c_int, c_vp] + [c_vp] * 13
+    L.icikt_pcoa_apply_dev.argtypes = [c_vp, c_vp, c_vp, c_i64, c_int, c_vp]
     # (two matrices: the twins are spelled out)
     cross_tail = [c_i64, c_i64, c_i64, c_vp, c_int, c_int, c_int, c_int, c_int, c_u32, c_int, c_vp, c_vp, c_vp, c_vp, c_vp,
                   c_vp]
@@ -424,14 +431,14 @@ def lib():
     # the *_in twins: (ctx, const icikt_input*, n_feat, n_samp, ...) where the _f64 entry has (ctx, X, n_feat, n_samp, ld, ...)
     for nm in ("pairs", "matrix", "pairs_complete", "missingness", "cor_pairs", "col_medians", "censor_counts",
                "rank_order", "topk", "edges", "class_medians", "quantiles", "class_matrix", "padjust", "mst", "hclust", "anosim",
-               "permanova", "permdisp"):
+               "permanova", "permdisp", "pcoa"):
         f64 = getattr(L, f"icikt_{nm}_f64").argtypes
         getattr(L, f"icikt_{nm}_in").argtypes = [c_vp, ctypes.POINTER(InputView), c_i64, c_i64] + list(f64[5:])
     L.icikt_convert_dev.argtypes = [c_vp, c_vp, c_int, c_int, c_i64, c_i64, c_i64, c_vp, c_i64]
     # the *_csc twins: (ctx, const icikt_csc_input*, n_feat, n_samp, ...)
     for nm in ("pairs", "matrix", "missingness", "col_medians", "censor_counts", "rank_order", "topk", "edges",
                "class_medians", "quantiles", "class_matrix", "padjust", "mst", "hclust", "anosim",
-               "permanova", "permdisp"):
+               "permanova", "permdisp", "pcoa"):
         f64 = getattr(L, f"icikt_{nm}_f64").argtypes
         getattr(L, f"icikt_{nm}_csc").argtypes = [c_vp, ctypes.POINTER(CscInput), c_i64, c_i64] + list(f64[5:])
     L.icikt_scatter_csc_dev.argtypes = [c_vp, c_vp, c_vp, c_vp, c_int, c_int, ctypes.c_double, c_i64, c_i64, c_vp, c_i64]
@@ -500,8 +507,8 @@ def _matrix_call(fn, handle, chk, X, global_na, pi, pj, perspective, alternative
 
 
 class _SelectCall:
-    """What the twelve selection entries (topk, cross, edges, class_medians, class_matrix, quantiles, padjust, mst, hclust,
-    anosim, permanova, permdisp) share around their own arguments.  An instance holds a resolved entry (what Context._entry returns; the
+    """What the thirteen selection entries (topk, cross, edges, class_medians, class_matrix, quantiles, padjust, mst, hclust,
+    anosim, permanova, permdisp, pcoa) share around their own arguments.  An instance holds a resolved entry (what Context._entry returns; the
     array behind its arguments stays alive with it), n_samp and flags as that entry sees them, and alloc: the allocator
     of the result arrays that are pinned when the call says so.  Calling it makes the checked call fn(ctx, <X>,
     global_na, n_global_na, *before, perspective, alternative, continuity, flags[, scale_max], *after, max_taumax,
@@ -1104,6 +1111,53 @@ class Context:
         tail = sel(global_na, perspective, alternative, continuity, None, (),
                    (_ptr(cls_a), n_class, _ptr(n_pairs), _ptr(q_total), _ptr(t_lo), _ptr(t_hi)))
         return n_pairs, (int(q_total[1]) << 32) + int(q_total[0]), _limbs_to_ints(t_lo, t_hi), *tail
+
+    def pcoa_apply_dev(self, d_G: int, d_V: int, n_samp: int, b: int, d_W: int):
+        """icikt_pcoa_apply_dev: W = G V on DEVICE arrays (G row-major [S, S]; V and W [b, S], a block's column c in row
+        c), asynchronous on the context's stream."""
+        self._chk(lib().icikt_pcoa_apply_dev(self._h, ctypes.c_void_p(d_G or 0), ctypes.c_void_p(d_V or 0), n_samp, b,
+                                             ctypes.c_void_p(d_W or 0)), "icikt_pcoa_apply_dev")
+
+    def pcoa(self, X, k=10, tol=1e-8, max_basis=None, seed=0, return_gower=False, global_na=None, perspective="global",
+             alternative="two.sided", continuity=False, flags: int = 0, start=None):
+        """The principal coordinates of the samples under the dissimilarity 1 - raw, on the device (icikt_pcoa_f64): all
+        pairs are computed, their (1 - raw)^2 turned into PERMANOVA's fixed-point integers q (csrc/icikt_fixed.h), the
+        Gower-centred S x S table G built from them and its k algebraically largest eigenpairs found there by a block
+        Krylov iteration -- no S x S matrix reaches the host unless return_gower asks for G.  tol: the iteration stops
+        when every residual |G y - theta y| is within tol |G|_F; max_basis: the most basis columns (None: min(S, max(8 k,
+        128)); at most PCOA_MAX_BASIS); the start block [k, S] is `start`, or standard normals of
+        numpy.random.default_rng(seed).  X and global_na as matrix() takes them.  Returns (n_pairs [2] int64: values, NA
+        pairs; Q: the sum of q over all values, a Python int; R [S] of Python ints (dtype object): the row sums of q;
+        eigenvalues [k], descending; vectors [S, k], orthonormal columns, each with its component of largest magnitude
+        positive; residuals [k]; frobenius: |G|_F; min_ritz: the smallest Ritz value of the last projected problem;
+        n_basis; n_apply; converged; G [S, S] or None; max_taumax; reason_counts [5]).  With an NA pair every double is
+        NA_real_ and the integers are as summed.  The argument checks are the library's: fewer than two samples, a k
+        outside 1 .. min(S - 1, PCOA_MAX_K), a tol that is not positive or a max_basis below k raises IciktError."""
+        sel = _SelectCall(self, self._entry("pcoa", X, flags))
+        S, k = sel.n_samp, int(k)
+        room = k if 1 <= k <= PCOA_MAX_K else 1
+        if start is None:
+            start = np.random.default_rng(seed).standard_normal((room, max(S, 1)))
+        start = np.ascontiguousarray(start, dtype=np.float64)
+        if start.shape != (room, max(S, 1)):
+            raise ValueError("start must be [k, S]: one row per column of the start block")
+        n_pairs = np.zeros(2, dtype=np.int64)
+        q_total = np.zeros(2, dtype=np.int64)
+        row_lo = np.zeros(max(S, 1), dtype=np.int64)
+        row_hi = np.zeros(max(S, 1), dtype=np.int64)
+        eigenvalues = np.zeros(room, dtype=np.float64)
+        vectors = sel.alloc((room, max(S, 1)), dtype=np.float64)
+        residuals = np.zeros(room, dtype=np.float64)
+        frobenius, min_ritz = np.zeros(1, dtype=np.float64), np.zeros(1, dtype=np.float64)
+        solver = np.zeros(3, dtype=np.int64)
+        gower = sel.alloc((max(S, 1), max(S, 1)), dtype=np.float64) if return_gower else None
+        tail = sel(global_na, perspective, alternative, continuity, None, (),
+                   (k, float(tol), 0 if max_basis is None else (int(max_basis) if int(max_basis) > 0 else -1), _ptr(start), _ptr(n_pairs), _ptr(q_total),
+                    _ptr(row_lo), _ptr(row_hi), _ptr(eigenvalues), _ptr(vectors), _ptr(residuals), _ptr(frobenius),
+                    _ptr(min_ritz), _ptr(solver), _ptr(gower)))
+        return (n_pairs, (int(q_total[1]) << 32) + int(q_total[0]), _limbs_to_ints(row_lo[:S], row_hi[:S]), eigenvalues,
+                vectors[:, :S].T, residuals, float(frobenius[0]), float(min_ritz[0]), int(solver[0]), int(solver[1]),
+                bool(solver[2]), gower, *tail)
 
     def edges(self, X, min_raw=None, max_pvalue=None, min_completeness=None, absolute=False, max_edges=0,
               global_na=None, perspective="global", alternative="two.sided", continuity=False, flags: int = 0,

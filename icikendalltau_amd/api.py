@@ -152,6 +152,13 @@ class HipEngine:
         return self._select_ctx().permdisp(data_matrix, cls, n_class, global_na, perspective, alternative, continuity,
                                            self.flags | flags)
 
+    def pcoa(self, data_matrix, k=10, tol=1e-8, max_basis=None, seed=0, return_gower=False, global_na=None,
+             perspective="global", alternative="two.sided", continuity=False, flags=0):
+        """The k largest eigenpairs of the Gower-centred table of (1 - raw)^2, found on the device (icikt_pcoa_f64):
+        Context.pcoa's arguments and result."""
+        return self._select_ctx().pcoa(data_matrix, k, tol, max_basis, seed, return_gower, global_na, perspective,
+                                       alternative, continuity, self.flags | flags)
+
     def cor_pairs(self, X, pi, pj, method, pairwise, alternative, continuity):
         """cor_fast's pairs on the device (icikt_cor_pairs_f64): (out3: rho, p-value, n_values; reasons)."""
         return self.ctx.cor_pairs(X, pi, pj, method, pairwise, alternative, continuity)
@@ -2622,6 +2629,142 @@ def ici_kendalltau_permdisp(data_matrix, sample_classes, permutations=999, seed=
         {"centroid_distance": zc, "nearest_centroid": nearest, "n_negative": n_negative, "n_valid": int(n_pairs[0]),
          "n_na": n_na, "sums": {"q_total": int(Q), "t": T, "class_q": np.array(A, dtype=object)}},
         names, max_taumax, t_diff)
+
+
+# --------------------------------------------------------------------------------------------------
+# ici_kendalltau_pcoa: the principal coordinates of the samples under 1 - raw (classical scaling, Gower 1966): the
+# largest eigenpairs of the Gower-centred table of PERMANOVA's integers
+# --------------------------------------------------------------------------------------------------
+def _pcoa_sign(vectors):
+    """The sign rule on the columns of `vectors` [S, k], in place: a column's component of largest magnitude is
+    positive, the smallest index deciding among equal magnitudes (numpy's argmax takes the first)."""
+    for a in range(vectors.shape[1]):
+        col = vectors[:, a]
+        if col.size and col[int(np.argmax(np.abs(col)))] < 0:
+            col *= -1.0
+    return vectors
+
+
+def _pcoa_gower(raw):
+    """The integers and the centred table of icikt_pcoa_f64 from a full S x S raw matrix: (n_pairs [2], Q, R [S] of
+    Python ints, G [S, S] or None with an NA pair).  q is PERMANOVA's (`_permanova_quantise`), the row sums are taken
+    limb by limb in int64, the means are Python's correctly rounded int / int, and
+    G = -0.5 * ((q 2^-50 - (m_i + m_j)) + m-bar), one numpy operation -- one rounding -- each."""
+    raw = np.asarray(raw, dtype=np.float64)
+    S = raw.shape[0]
+    iu, ju = np.triu_indices(S, k=1)
+    ok = ~np.isnan(raw[iu, ju])
+    n_na = int((~ok).sum())
+    q = np.zeros((S, S), dtype=np.int64)
+    q[iu[ok], ju[ok]] = _permanova_quantise(raw[iu[ok], ju[ok]])
+    q = q + q.T
+    R = _lib._limbs_to_ints((q & 0xFFFFFFFF).sum(axis=1), (q >> 32).sum(axis=1))
+    T = sum(int(r) for r in R)
+    n_pairs = np.array([int(ok.sum()), n_na], dtype=np.int64)
+    if n_na > 0:
+        return n_pairs, T // 2, R, None
+    m = np.array([int(r) / (S << PERMANOVA_FRAC_BITS) for r in R], dtype=np.float64)
+    grand = T / ((S * S) << PERMANOVA_FRAC_BITS)
+    e = np.ldexp(q.astype(np.float64), -PERMANOVA_FRAC_BITS)
+    G = -0.5 * ((e - (m[:, None] + m[None, :])) + grand)
+    return n_pairs, T // 2, R, G
+
+
+def _pcoa_numpy(raw, k):
+    """icikt_pcoa_f64's result from a full S x S raw matrix with numpy.linalg.eigh, for engines without a pcoa method
+    (the CPU tests' checker engines): Context.pcoa's tuple without max_taumax and reason_counts.  The whole spectrum is
+    computed, so n_basis is S, n_apply 0 and the call has always converged."""
+    n_pairs, Q, R, G = _pcoa_gower(raw)
+    S = len(R)
+    if G is None:
+        return (n_pairs, Q, R, _na_filled(k), _na_filled((S, k)), _na_filled(k), _na_real(), _na_real(), 0, 0, False, None)
+    w, V = np.linalg.eigh(G)
+    lam = w[::-1][:k].copy()
+    vec = _pcoa_sign(np.ascontiguousarray(V[:, ::-1][:, :k]))
+    res = np.linalg.norm(G @ vec - vec * lam, axis=0)
+    return (n_pairs, Q, R, lam, vec, res, float(np.linalg.norm(G)), float(w[0]), S, 0, True, G)
+
+
+def ici_kendalltau_pcoa(data_matrix, k=10, tol=1e-8, max_basis=None, seed=0, return_gower=False,
+                        global_na=(float("nan"), float("inf"), 0), perspective="global", alternative="two.sided",
+                        continuity=False, colnames=None, engine=None):
+    """The ordination of the samples (columns) under ICI-Kendall-tau: principal coordinates analysis (classical
+    scaling, Gower 1966; ``vegan::wcmdscale``, ``skbio.stats.ordination.pcoa``) on the dissimilarity ``1 - raw``, with
+    the share of inertia per axis -- without the S x S matrices ``ici_kendalltau`` returns.  It decomposes exactly the
+    inertia ``ici_kendalltau_permanova`` partitions (``total_inertia`` is its ``ss_total``) and draws the space
+    ``ici_kendalltau_permdisp`` measures its distances in.
+
+    The rule.  Every ``(1 - raw)^2`` is PERMANOVA's integer multiple of 2^-50; the row and grand means of those squared
+    dissimilarities are correctly rounded doubles of integer ratios; ``G = -0.5 (d^2 - row mean - column mean + grand
+    mean)``, in a fixed order of four double operations, is the Gower-centred table, symmetric to the bit.  The result
+    is the ``k`` algebraically largest eigenvalues of G, descending, with orthonormal eigenvectors: ``coordinates[:, a] =
+    vectors[:, a] * sqrt(eigenvalues[a])`` where the eigenvalue is positive, else 0; ``proportion = eigenvalues /
+    total_inertia`` with ``total_inertia = trace(G)``, from the integers; ``n_positive`` counts the positive eigenvalues
+    among the k.  A vector's component of largest magnitude is positive (the smallest index decides among equal
+    magnitudes), so an axis does not flip between runs.
+
+    THE SOLVER is a block Krylov iteration with full reorthogonalisation and Rayleigh-Ritz on the device, from a start
+    block of ``numpy.random.default_rng(seed)`` normals: it stops when every residual ``|G y - lambda y|`` is within
+    ``tol |G|_F``, or when the basis holds ``max_basis`` columns (default ``min(S, max(8 k, 128))``, at most 512) -- then
+    the best pairs so far are returned with ``converged = False``, ``residuals`` as they are and one warning.  With
+    ``max_basis = S`` the basis spans the space and the call always converges.  Every floating-point sum on the device
+    has a fixed order: the same input and seed give the same bits.  ``min_ritz``, the smallest Ritz value of the last
+    projected problem, estimates (from above) the most negative eigenvalue of G: how far the dissimilarity is from
+    Euclidean.
+
+    EVERY PAIR IS NEEDED.  With a pair whose ``raw`` is NA (``n_na > 0``) the centring has no meaning: every double is
+    NA, one warning says so, and the integers are still returned.  ``1 <= k <= min(S - 1, 64)``; S is at least 2 and at
+    most 65 535.  The other arguments are ``ici_kendalltau``'s (column names are required).
+
+    Returns a dict: ``coordinates`` [S, k], ``eigenvalues`` [k], ``proportion`` [k], ``vectors`` [S, k],
+    ``total_inertia``, ``n_positive``; ``residuals`` [k], ``frobenius``, ``min_ritz``, ``n_basis``, ``n_apply``,
+    ``converged``; ``n_valid``, ``n_na``; ``sums`` (the integers: ``q_total`` and ``row_q`` [S]); ``gower`` ([S, S], only
+    with ``return_gower``); ``sample_id``, ``max_taumax`` and ``run_time``.
+    """
+    data_matrix, names, n_sample = _select_input(data_matrix, colnames)
+    if n_sample < 2:
+        raise ValueError("ici_kendalltau_pcoa needs at least 2 samples")
+    k = _int_arg(k, 1, min(n_sample - 1, _lib.PCOA_MAX_K), "`k` must be an integer in 1 .. min(S - 1, 64)")
+    if isinstance(tol, (bool, np.bool_)) or not isinstance(tol, (int, float, np.integer, np.floating)) \
+            or not (float(tol) > 0.0 and math.isfinite(float(tol))):
+        raise ValueError("`tol` must be a positive number")
+    if max_basis is not None:
+        max_basis = _int_arg(max_basis, k, 2 ** 31 - 1, "`max_basis` must be None or an integer that is at least k")
+    eng = engine or _default_engine()
+    if hasattr(eng, "pcoa"):
+        (n_pairs, Q, R, lam, vec, res, frob, min_ritz, n_basis, n_apply, converged, G, max_taumax), t_diff = _on_device(
+            eng, data_matrix, global_na,
+            lambda X, gna: eng.pcoa(X, k, float(tol), max_basis, seed, bool(return_gower), gna, perspective, alternative,
+                                    continuity, 0))
+    else:
+        mats5, t_diff, max_taumax = _from_full(eng, data_matrix, names, global_na, perspective, True, alternative,
+                                               continuity)
+        n_pairs, Q, R, lam, vec, res, frob, min_ritz, n_basis, n_apply, converged, G = _pcoa_numpy(mats5[1], k)
+    S, n_na = n_sample, int(n_pairs[1])
+    if n_na > 0:
+        warnings.warn(f"PCoA needs every pair and {n_na} of them have no raw value: every eigenvalue and coordinate is "
+                      "NA.  `ici_kendalltau_medians` returns `n_valid` per column, which finds the columns to leave out.",
+                      RuntimeWarning, stacklevel=2)
+        total, coords, prop, n_positive = _na_real(), _na_filled((S, k)), _na_filled(k), 0
+        G = _na_filled((S, S)) if return_gower else None
+    else:
+        if not converged:
+            warnings.warn(f"PCoA has not converged within {int(n_basis)} basis columns: the largest residual is "
+                          f"{float(np.max(res)):.3g} against tol |G|_F = {float(tol) * frob:.3g}.  Raise `max_basis` (at "
+                          "most 512, or S), or loosen `tol`.", RuntimeWarning, stacklevel=2)
+        total = float(Fraction(int(Q), S << PERMANOVA_FRAC_BITS))
+        pos = lam > 0
+        coords = np.where(pos[None, :], vec * np.sqrt(np.where(pos, lam, 0.0))[None, :], 0.0)
+        prop = lam / total if total != 0 else _na_filled(k)
+        n_positive = int(pos.sum())
+    out = {"coordinates": coords, "eigenvalues": lam, "proportion": prop, "vectors": vec, "total_inertia": total,
+           "n_positive": n_positive, "residuals": res, "frobenius": frob, "min_ritz": min_ritz, "n_basis": int(n_basis),
+           "n_apply": int(n_apply), "converged": bool(converged), "n_valid": int(n_pairs[0]), "n_na": n_na,
+           "sums": {"q_total": int(Q), "row_q": R}}
+    if return_gower:
+        out["gower"] = G
+    out.update({"sample_id": np.asarray(list(names), dtype=object), "max_taumax": max_taumax, "run_time": t_diff})
+    return out
 
 
 # --------------------------------------------------------------------------------------------------

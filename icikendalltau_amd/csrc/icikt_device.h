@@ -328,6 +328,37 @@ constexpr long long DISP_MAX_CELLS = 1ll << 26;   // == ICIKT_PERMDISP_MAX_CELLS
 hipError_t launch_disp_table(const unsigned long long* kept, const int32_t* cls, int S, int n_class,
                              unsigned long long* t_lo, unsigned long long* t_hi, unsigned long long* totals,
                              hipStream_t s);
+// ---- PCoA: principal coordinates of the samples under 1 - raw (icikt_pcoa.hip) ----
+// Blocks of vectors are column-major with the leading dimension S: X[i + S c].  Every floating-point sum below has a
+// fixed order for a given shape; the only atomic is the integer NA count of launch_pcoa_rows.
+constexpr int PCOA_MAX_BLOCK = 64;        // == ICIKT_PCOA_MAX_K: columns of a block
+constexpr int PCOA_MAX_BASIS = 512;       // == ICIKT_PCOA_MAX_BASIS
+// kept: the whole combn(S, 2) plane launch_median_keep writes.  row_lo / row_hi [S] = the low 32 bits / the rest of
+// q = fixed::quantise_key(key) summed over the partners t != s (R = hi 2^32 + lo), every cell written;
+// totals[PMV_T_NA] (zeroed by the caller) += the NA_KEY pairs, each pair once
+hipError_t launch_pcoa_rows(const unsigned long long* kept, int S, unsigned long long* row_lo, unsigned long long* row_hi,
+                            unsigned long long* totals, hipStream_t s);
+// G [S][S] = -0.5 * (((double)q 2^-50 - (mean[i] + mean[j])) + grand[0]), q = 0 on the diagonal: every cell written.
+// The plane must hold no NA_KEY (it would count as q = 0)
+hipError_t launch_pcoa_centre(const unsigned long long* kept, const double* mean, const double* grand, int S, double* G,
+                              hipStream_t s);
+// W [S x b] = G V, 1 <= b <= PCOA_MAX_BLOCK; G is read once
+hipError_t launch_pcoa_apply(const double* G, const double* V, int S, int b, double* W, hipStream_t s);
+// C [L x b] (C[l + ldc c]) = Q^T W for Q [S x L] and W [S x b]
+hipError_t launch_pcoa_qtw(const double* Q, int L, const double* W, int S, int b, int ldc, double* C, hipStream_t s);
+// Out [S x b] = A Z, or with subtract Out -= A Z, for A [S x L] and Z [L x b] (Z[l + ldz c]); l ascending
+hipError_t launch_pcoa_axz(const double* A, int L, const double* Z, int ldz, int S, int b, int subtract, double* Out,
+                           hipStream_t s);
+// out[c] = the sum of squares of X[0 .. n) + ld c, c < cols; out[0] = the sum of x [n]
+hipError_t launch_pcoa_sumsq(const double* X, int n, long long ld, int cols, double* out, hipStream_t s);
+hipError_t launch_pcoa_sum(const double* x, int n, double* out, hipStream_t s);
+// x [n] /= sqrt(sumsq[0]) and flag[0] = 1; with sumsq[0] below thr2 (or 0) x = 0 and flag[0] = 0
+hipError_t launch_pcoa_scale(double* x, int n, const double* sumsq, double thr2, int32_t* flag, hipStream_t s);
+// out[c] = |GY_c - theta[c] Y_c|^2, c < k
+hipError_t launch_pcoa_resid(const double* GY, const double* Y, const double* theta, int S, int k, double* out,
+                             hipStream_t s);
+// every column of Y [S x k]: negated iff its component of largest magnitude (the smallest index among equals) is negative
+hipError_t launch_pcoa_sign(double* Y, int S, int k, hipStream_t s);
 // ---- quantiles and histogram of all pairs (icikt_quantiles.hip) ----
 constexpr int QUANT_MAX_BINS = 1024;    // == ICIKT_HIST_MAX_BINS: k_quant_fold stages 1 025 breaks and 2 x 1 026 counters in LDS
 constexpr int QUANT_HEAD = 4;           // words of a counted group before its bins: n_valid, n_na, below, above

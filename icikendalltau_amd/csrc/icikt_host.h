@@ -235,6 +235,15 @@ struct icikt_ctx {
     DevBuf<int32_t> cls;
   } disp;
 
+  // PCoA (icikt_pcoa_f64): the two limbs of the row sums and the NA count, the means, the centred S x S table, the
+  // Krylov basis with its image under the table (S x max_basis each), a block's scratch, the Ritz vectors with their
+  // image, and the small buffers (coefficients, Ritz coefficients and values, norms, flags); the keys are in sel.kept
+  struct PcoaBufs {
+    DevBuf<unsigned long long> row_lo, row_hi, totals;
+    DevBuf<double> mean, table, basis, image, block, y, gy, coef, z, small;
+    DevBuf<int32_t> flags;
+  } pcoa;
+
   // missing-value diagnostics (icikt_col_medians_f64, icikt_censor_counts_f64, icikt_rank_order_f64)
   struct DiagBufs {
     DevBuf<double> median, medrank, out;

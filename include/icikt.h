@@ -755,6 +755,59 @@ int icikt_permdisp_f64(icikt_ctx *ctx, const double *X, int64_t n_feat, int64_t 
                        uint32_t flags, const int32_t *cls, int n_class, int64_t *n_pairs, int64_t *q_total,
                        int64_t *t_lo, int64_t *t_hi, double *max_taumax, int64_t *reason_counts);
 
+/* ---- PCoA: the principal coordinates of the samples under 1 - raw -------------------------------------------------------
+ *
+ * The ordination every quality-control report draws first (classical scaling, Gower 1966; vegan::wcmdscale,
+ * skbio.stats.ordination.pcoa) on the dissimilarity 1 - raw, without an S x S matrix on the host.  The triangle runs as
+ * in icikt_permanova_f64 and a pair's q is the same integer (csrc/icikt_fixed.h), so n_pairs and q_total are bit for
+ * bit icikt_permanova_f64's.  With e^_ij = q_ij 2^-50 (e^_ii = 0), the row sums R_i = sum_j q_ij and T = sum_i R_i = 2 Q
+ * as integers, m_i = R_i / (S 2^50) and m-bar = T / (S^2 2^50) each one correctly rounded double, the centred table is
+ *   G_ij = -0.5 * ((e^_ij - (m_i + m_j)) + m-bar)        (these four double operations, each rounded once)
+ * and the call returns the k algebraically largest eigenvalues of G, descending, with orthonormal eigenvectors; a
+ * vector's component of largest magnitude is positive (the smallest index among equal magnitudes decides).  The pairs
+ * are found by a block Krylov iteration with full reorthogonalisation and Rayleigh-Ritz from the caller's start block;
+ * every floating-point sum has a fixed order, so the result is a pure function of the input and the start block,
+ * whatever the block cut, the call before or the stream.  The work is bounded: there is no restart.
+ *   k            1 .. min(n_samp - 1, ICIKT_PCOA_MAX_K); n_samp >= 2
+ *   tol          > 0: the iteration stops when every |G y - theta y|_2 <= tol |G|_F
+ *   max_basis    the most basis columns; 0: min(n_samp, max(8 k, 128)); else >= k.  Capped at ICIKT_PCOA_MAX_BASIS and
+ *                at n_samp; with max_basis = n_samp the basis spans the space and the call converges
+ *   start        [k][n_samp]: column a of the start block is start[a n_samp + i]; finite, k independent columns
+ *                (ICIKT_E_INVALID otherwise).  The library draws nothing itself
+ *   n_pairs      [2] the values and the NA pairs
+ *   q_total      [2] Q = q_total[1] 2^32 + q_total[0], the sum of q over all values
+ *   row_lo, row_hi [n_samp]: R_i = row_hi[i] 2^32 + row_lo[i] (the limb rule of icikt_permanova_f64; lo may exceed 2^32)
+ *   eigenvalues  [k]; vectors [k][n_samp]: component i of vector a is vectors[a n_samp + i]
+ *   residuals    [k] |G y - theta y|_2 of the returned pairs; frobenius: |G|_F
+ *   min_ritz     the smallest Ritz value of the last projected problem: an estimate (from above) of the most negative
+ *                eigenvalue of G, which says how non-Euclidean the dissimilarity is
+ *   solver       [3] n_basis: the basis columns used; n_apply: the applications of G to a block; converged: 1 or 0 (the
+ *                basis filled up first: the best pairs so far are returned with the residuals as they are)
+ *   gower        [n_samp][n_samp] G itself, or null: not returned
+ * AN NA PAIR (n_pairs[1] > 0) makes every double -- eigenvalues, vectors, residuals, frobenius, min_ritz, gower -- R's
+ * NA_real_ and solver zero; the integers are returned as summed.
+ * All outputs but gower, max_taumax and reason_counts (as icikt_topk_f64, over all pairs) are required.  A bad n_samp,
+ * k, tol or max_basis, a null start block, a null output: ICIKT_E_INVALID before anything -- the context or an output --
+ * is touched.  n_samp <= ICIKT_TOPK_MAX_SAMPLES; n_feat, global_na and the state the call leaves behind (none): as
+ * icikt_topk_f64.
+ * Device memory: the prepared matrix, one block's buffers, 8 bytes per pair of the triangle for the kept keys,
+ * 8 n_samp^2 for G (n_samp = 65 535: 34 GB) and 16 n_samp max_basis + 8 n_samp (64 + 2 k) for the basis, its image,
+ * a block and the Ritz vectors.  With ICIKT_FLAG_TIMING the keep and every kernel of the entry are accounted under
+ * ICIKT_K_EPILOGUE.
+ * icikt_pcoa_in / icikt_pcoa_csc: the same on a typed view / a CSC view of the matrix (below). */
+#define ICIKT_PCOA_MAX_K 64
+#define ICIKT_PCOA_MAX_BASIS 512
+int icikt_pcoa_f64(icikt_ctx *ctx, const double *X, int64_t n_feat, int64_t n_samp, int64_t ld, const double *global_na,
+                   int n_global_na, int perspective, int alternative, int continuity, uint32_t flags, int k, double tol,
+                   int max_basis, const double *start, int64_t *n_pairs, int64_t *q_total, int64_t *row_lo,
+                   int64_t *row_hi, double *eigenvalues, double *vectors, double *residuals, double *frobenius,
+                   double *min_ritz, int64_t *solver, double *gower, double *max_taumax, int64_t *reason_counts);
+/* The entry's hot kernel on DEVICE arrays, asynchronous on the context's stream (as icikt_convert_dev): d_W = d_G d_V
+ * for a row-major n_samp x n_samp table d_G and blocks of 1 <= b <= ICIKT_PCOA_MAX_K columns, column c of a block at
+ * [c n_samp, (c + 1) n_samp).  d_G is read once; every row's sum has a fixed order.  What tools/pcoa_time.py times and
+ * tests/test_gpu_pcoa.py holds against numpy for every block width's code path. */
+int icikt_pcoa_apply_dev(icikt_ctx *ctx, const double *d_G, const double *d_V, int64_t n_samp, int b, double *d_W);
+
 /* ---- query samples against a reference cohort: the query x reference rectangle ---------------------------------------
  *
  * Every column of Q (n_feat x n_query, leading dimension ld_query) with every column of R (n_feat x n_reference,
@@ -1031,6 +1084,11 @@ int icikt_permdisp_in(icikt_ctx *ctx, const icikt_input *X, int64_t n_feat, int6
                       int n_global_na, int perspective, int alternative, int continuity, uint32_t flags,
                       const int32_t *cls, int n_class, int64_t *n_pairs, int64_t *q_total, int64_t *t_lo,
                       int64_t *t_hi, double *max_taumax, int64_t *reason_counts);
+int icikt_pcoa_in(icikt_ctx *ctx, const icikt_input *X, int64_t n_feat, int64_t n_samp, const double *global_na,
+                  int n_global_na, int perspective, int alternative, int continuity, uint32_t flags, int k, double tol,
+                  int max_basis, const double *start, int64_t *n_pairs, int64_t *q_total, int64_t *row_lo,
+                  int64_t *row_hi, double *eigenvalues, double *vectors, double *residuals, double *frobenius,
+                  double *min_ritz, int64_t *solver, double *gower, double *max_taumax, int64_t *reason_counts);
 int icikt_matrix_in(icikt_ctx *ctx, const icikt_input *X, int64_t n_feat, int64_t n_samp, const double *global_na,
                     int n_global_na, const int32_t *pi, const int32_t *pj, int64_t n_pairs, int perspective,
                     int alternative, int continuity, uint32_t flags, int scale_max, int diag_good, double *out5,
@@ -1123,6 +1181,11 @@ int icikt_permdisp_csc(icikt_ctx *ctx, const icikt_csc_input *X, int64_t n_feat,
                        const double *global_na, int n_global_na, int perspective, int alternative, int continuity,
                        uint32_t flags, const int32_t *cls, int n_class, int64_t *n_pairs, int64_t *q_total,
                        int64_t *t_lo, int64_t *t_hi, double *max_taumax, int64_t *reason_counts);
+int icikt_pcoa_csc(icikt_ctx *ctx, const icikt_csc_input *X, int64_t n_feat, int64_t n_samp, const double *global_na,
+                   int n_global_na, int perspective, int alternative, int continuity, uint32_t flags, int k, double tol,
+                   int max_basis, const double *start, int64_t *n_pairs, int64_t *q_total, int64_t *row_lo,
+                   int64_t *row_hi, double *eigenvalues, double *vectors, double *residuals, double *frobenius,
+                   double *min_ritz, int64_t *solver, double *gower, double *max_taumax, int64_t *reason_counts);
 int icikt_missingness_csc(icikt_ctx *ctx, const icikt_csc_input *X, int64_t n_feat, int64_t n_samp, const int32_t *pi,
                           const int32_t *pj, int64_t n_pairs, int64_t *missingness);
 int icikt_col_medians_csc(icikt_ctx *ctx, const icikt_csc_input *X, int64_t n_feat, int64_t n_samp,
