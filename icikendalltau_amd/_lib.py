@@ -30,6 +30,7 @@ SOURCES = [os.path.join(_PKG, "csrc", f) for f in ("icikt_kernels.hip", "icikt_p
                                                        "icikt_permanova.hip", "icikt_capi_permanova.cpp",
                                                        "icikt_permdisp.hip", "icikt_capi_permdisp.cpp",
                                                        "icikt_pcoa.hip", "icikt_capi_pcoa.cpp",
+                                                       "icikt_mantel.hip", "icikt_capi_mantel.cpp",
                                                        "icikt_cross.hip", "icikt_capi_cross.cpp")]
 HEADERS = [os.path.join(_ROOT, "include", "icikt.h"), os.path.join(_PKG, "csrc", "icikt_device.h"),
            os.path.join(_PKG, "csrc", "icikt_wave.h"), os.path.join(_PKG, "csrc", "icikt_host.h"),
@@ -37,7 +38,8 @@ HEADERS = [os.path.join(_ROOT, "include", "icikt.h"), os.path.join(_PKG, "csrc",
            os.path.join(_PKG, "csrc", "icikt_blocks.h"), os.path.join(_PKG, "csrc", "icikt_select.h"),
            os.path.join(_PKG, "csrc", "icikt_keys.h"), os.path.join(_PKG, "csrc", "icikt_k0plan.h"),
            os.path.join(_PKG, "csrc", "icikt_k1plan.h"), os.path.join(_PKG, "csrc", "icikt_fixed.h"),
-           os.path.join(_PKG, "csrc", "icikt_labels.h"), os.path.join(_PKG, "csrc", "icikt_ritz.h")]
+           os.path.join(_PKG, "csrc", "icikt_labels.h"), os.path.join(_PKG, "csrc", "icikt_ritz.h"),
+           os.path.join(_PKG, "csrc", "icikt_mantel.h")]
 
 # include/icikt.h
 SUCCESS = 0
@@ -62,6 +64,8 @@ HCLUST = {"complete": 0, "average": 1, "single": 2}   # ICIKT_HCLUST_*: linkage 
 ANOSIM_MAX_PERM = 1000000     # ICIKT_ANOSIM_MAX_PERM: labellings per call of icikt_anosim_* beside the observed one
 PERMANOVA_MAX_CELLS = 1 << 26  # ICIKT_PERMANOVA_MAX_CELLS: (1 + n_perm) n_class of icikt_permanova_*
 PERMDISP_MAX_CELLS = 1 << 26   # ICIKT_PERMDISP_MAX_CELLS: n_samp n_class of icikt_permdisp_*
+MANTEL_MAX_PERM = 1000000      # ICIKT_MANTEL_MAX_PERM: permutations per call of icikt_mantel_*
+MANTEL = {"pearson": 0, "spearman": 1}   # ICIKT_MANTEL_*: how icikt_mantel_* turns the two vectors into integers
 PCOA_MAX_K = 64                # ICIKT_PCOA_MAX_K: eigenpairs per call of icikt_pcoa_*
 PCOA_MAX_BASIS = 512           # ICIKT_PCOA_MAX_BASIS: basis columns of icikt_pcoa_*
 MASK_VALS = 32                # distinct finite global_na values of the device-side exclusion rule (icikt_device.h)
@@ -106,6 +110,7 @@ EXPORTS = (
     "icikt_permanova_f64", "icikt_permanova_in", "icikt_permanova_csc",
     "icikt_permdisp_f64", "icikt_permdisp_in", "icikt_permdisp_csc",
     "icikt_pcoa_f64", "icikt_pcoa_in", "icikt_pcoa_csc", "icikt_pcoa_apply_dev",
+    "icikt_mantel_f64", "icikt_mantel_in", "icikt_mantel_csc",
     "icikt_cross_f64", "icikt_cross_in",
     "icikt_ref_prepare_f64", "icikt_ref_prepare_in", "icikt_ref_cross_f64", "icikt_ref_cross_in", "icikt_ref_info",
 )
@@ -412,6 +417,8 @@ def lib():
                                      c_int, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]
     L.icikt_pcoa_f64.argtypes = [c_vp, c_vp, c_i64, c_i64, c_i64, c_vp, c_int, c_int, c_int, c_int, c_u32, c_int,
                                  ctypes.c_double, c_int, c_vp] + [c_vp] * 13
+    L.icikt_mantel_f64.argtypes = [c_vp, c_vp, c_i64, c_i64, c_i64, c_vp, c_int, c_int, c_int, c_int, c_u32, c_vp, c_int,
+                                   c_vp, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]
     L.icikt_pcoa_apply_dev.argtypes = [c_vp, c_vp, c_vp, c_i64, c_int, c_vp]
     # (two matrices: the twins are spelled out)
     cross_tail = [c_i64, c_i64, c_i64, c_vp, c_int, c_int, c_int, c_int, c_int, c_u32, c_int, c_vp, c_vp, c_vp, c_vp, c_vp,
@@ -431,14 +438,14 @@ def lib():
     # the *_in twins: (ctx, const icikt_input*, n_feat, n_samp, ...) where the _f64 entry has (ctx, X, n_feat, n_samp, ld, ...)
     for nm in ("pairs", "matrix", "pairs_complete", "missingness", "cor_pairs", "col_medians", "censor_counts",
                "rank_order", "topk", "edges", "class_medians", "quantiles", "class_matrix", "padjust", "mst", "hclust", "anosim",
-               "permanova", "permdisp", "pcoa"):
+               "permanova", "permdisp", "pcoa", "mantel"):
         f64 = getattr(L, f"icikt_{nm}_f64").argtypes
         getattr(L, f"icikt_{nm}_in").argtypes = [c_vp, ctypes.POINTER(InputView), c_i64, c_i64] + list(f64[5:])
     L.icikt_convert_dev.argtypes = [c_vp, c_vp, c_int, c_int, c_i64, c_i64, c_i64, c_vp, c_i64]
     # the *_csc twins: (ctx, const icikt_csc_input*, n_feat, n_samp, ...)
     for nm in ("pairs", "matrix", "missingness", "col_medians", "censor_counts", "rank_order", "topk", "edges",
                "class_medians", "quantiles", "class_matrix", "padjust", "mst", "hclust", "anosim",
-               "permanova", "permdisp", "pcoa"):
+               "permanova", "permdisp", "pcoa", "mantel"):
         f64 = getattr(L, f"icikt_{nm}_f64").argtypes
         getattr(L, f"icikt_{nm}_csc").argtypes = [c_vp, ctypes.POINTER(CscInput), c_i64, c_i64] + list(f64[5:])
     L.icikt_scatter_csc_dev.argtypes = [c_vp, c_vp, c_vp, c_vp, c_int, c_int, ctypes.c_double, c_i64, c_i64, c_vp, c_i64]
@@ -507,8 +514,8 @@ def _matrix_call(fn, handle, chk, X, global_na, pi, pj, perspective, alternative
 
 
 class _SelectCall:
-    """What the thirteen selection entries (topk, cross, edges, class_medians, class_matrix, quantiles, padjust, mst, hclust,
-    anosim, permanova, permdisp, pcoa) share around their own arguments.  An instance holds a resolved entry (what Context._entry returns; the
+    """What the fourteen selection entries (topk, cross, edges, class_medians, class_matrix, quantiles, padjust, mst, hclust,
+    anosim, permanova, permdisp, pcoa, mantel) share around their own arguments.  An instance holds a resolved entry (what Context._entry returns; the
     array behind its arguments stays alive with it), n_samp and flags as that entry sees them, and alloc: the allocator
     of the result arrays that are pinned when the call says so.  Calling it makes the checked call fn(ctx, <X>,
     global_na, n_global_na, *before, perspective, alternative, continuity, flags[, scale_max], *after, max_taumax,
@@ -1111,6 +1118,46 @@ class Context:
         tail = sel(global_na, perspective, alternative, continuity, None, (),
                    (_ptr(cls_a), n_class, _ptr(n_pairs), _ptr(q_total), _ptr(t_lo), _ptr(t_hi)))
         return n_pairs, (int(q_total[1]) << 32) + int(q_total[0]), _limbs_to_ints(t_lo, t_hi), *tail
+
+    def mantel(self, X, other, method="pearson", perms=None, global_na=None, perspective="global",
+               alternative="two.sided", continuity=False, flags: int = 0):
+        """The Mantel test's integer sums of the dissimilarity 1 - raw against another matrix of the same samples, on
+        the device (icikt_mantel_f64): all pairs are computed and turned into integers below 2^32 -- their doubled ranks
+        (method "spearman") or fixed-point values (method "pearson", csrc/icikt_mantel.h) -- as `other` is, and
+        T = sum x_ij y_pi(i)pi(j) is summed there for the identity and every permutation.  other: [P] finite doubles,
+        one per pair i < j in combn order (scipy's squareform order); perms: [n_perm, S] sample indices, every row a
+        permutation of 0 .. S - 1 (None: none); X and global_na as matrix() takes them.  Returns (n_pairs [2] int64:
+        values, NA pairs; T [1 + n_perm] of Python ints (dtype object), index 0 the identity; moments: (Sx, Sxx, Sy,
+        Syy) as Python ints; n_ge, n_le: the permutations with T >= / <= T[0], compared exactly; max_taumax;
+        reason_counts [5]).  With an NA pair every T and moment is 0.  The limbs of the C ABI are combined here.
+        api.mantel_statistic turns (P, T, Sx, Sxx, Sy, Syy) into r.  The argument checks are the library's: a value of
+        other that is not finite, a row of perms that is no permutation or a bad method raises IciktError."""
+        sel = _SelectCall(self, self._entry("mantel", X, flags))
+        S = sel.n_samp
+        other_a = np.ascontiguousarray(other, dtype=np.float64)
+        if other_a.shape != (S * (S - 1) // 2 if S > 1 else 0,):
+            raise ValueError("other must be [S (S - 1) / 2]: one value per pair in combn order")
+        if perms is None:
+            perm_a, n_perm = None, 0
+        else:
+            perm_a = np.ascontiguousarray(perms, dtype=np.int32)
+            if perm_a.ndim != 2 or perm_a.shape[1] != S:
+                raise ValueError("perms must be [n_perm, S]: one sample index per column in every row")
+            n_perm = int(perm_a.shape[0])
+        n_lab = 1 + (n_perm if n_perm <= MANTEL_MAX_PERM else 0)
+        n_pairs = np.zeros(2, dtype=np.int64)
+        t_lo = np.zeros(n_lab, dtype=np.int64)
+        t_hi = np.zeros(n_lab, dtype=np.int64)
+        moments = np.zeros(8, dtype=np.int64)
+        n_ge = np.zeros(1, dtype=np.int64)
+        n_le = np.zeros(1, dtype=np.int64)
+        code = MANTEL.get(method, method if isinstance(method, int) else -1)
+        tail = sel(global_na, perspective, alternative, continuity, None, (),
+                   (_ptr(other_a) if other_a.size else None, code, _ptr(perm_a) if n_perm else None, n_perm, _ptr(n_pairs),
+                    _ptr(t_lo), _ptr(t_hi), _ptr(moments), _ptr(n_ge), _ptr(n_le)))
+        T = t_hi.astype(object) * (1 << 32) + t_lo.astype(object)
+        mom = tuple((int(moments[2 * k + 1]) << 32) + int(moments[2 * k]) for k in range(4))
+        return n_pairs, T, mom, int(n_ge[0]), int(n_le[0]), *tail
 
     def pcoa_apply_dev(self, d_G: int, d_V: int, n_samp: int, b: int, d_W: int):
         """icikt_pcoa_apply_dev: W = G V on DEVICE arrays (G row-major [S, S]; V and W [b, S], a block's column c in row

@@ -159,6 +159,13 @@ class HipEngine:
         return self._select_ctx().pcoa(data_matrix, k, tol, max_basis, seed, return_gower, global_na, perspective,
                                        alternative, continuity, self.flags | flags)
 
+    def mantel(self, data_matrix, other, method="pearson", perms=None, global_na=None, perspective="global",
+               alternative="two.sided", continuity=False, flags=0):
+        """The Mantel test's integer sums against another matrix, of the identity and of every permutation, on the
+        device (icikt_mantel_f64): Context.mantel's arguments and result."""
+        return self._select_ctx().mantel(data_matrix, other, method, perms, global_na, perspective, alternative,
+                                         continuity, self.flags | flags)
+
     def cor_pairs(self, X, pi, pj, method, pairwise, alternative, continuity):
         """cor_fast's pairs on the device (icikt_cor_pairs_f64): (out3: rho, p-value, n_values; reasons)."""
         return self.ctx.cor_pairs(X, pi, pj, method, pairwise, alternative, continuity)
@@ -2765,6 +2772,241 @@ def ici_kendalltau_pcoa(data_matrix, k=10, tol=1e-8, max_basis=None, seed=0, ret
         out["gower"] = G
     out.update({"sample_id": np.asarray(list(names), dtype=object), "max_taumax": max_taumax, "run_time": t_diff})
     return out
+
+
+# --------------------------------------------------------------------------------------------------
+# ici_kendalltau_mantel: the Mantel test (Mantel 1967; vegan::mantel, skbio.stats.distance.mantel) of the dissimilarity
+# 1 - raw against another matrix of the same samples, in integers (csrc/icikt_mantel.h)
+# --------------------------------------------------------------------------------------------------
+MANTEL_X_FRAC_BITS = 30   # mantel::X_FRAC_BITS: xv = (1 - raw) 2^30, rounded half to even
+MANTEL_Y_BITS = 31        # mantel::Y_BITS: yv = (y - lo) 2^(31 - e), (m, e) = frexp(hi - lo)
+
+
+def mantel_permutations(S, permutations=999, seed=None, strata=None):
+    """The permutations ``ici_kendalltau_mantel`` compares with, [n_perm, S] int32 sample indices:
+    ``anosim_permutations(numpy.arange(S), permutations, seed, strata)``.  Permutation t sends sample s to
+    ``perms[t, s]``, and ``codes[perms[t]]`` is the labelling ``ici_kendalltau_anosim``, ``ici_kendalltau_permanova``
+    and ``ici_kendalltau_permdisp`` draw for the same ``seed`` and ``strata``.  An integer array [n_perm, S] is returned
+    as given (as int32)."""
+    return anosim_permutations(np.arange(int(S), dtype=np.int32), permutations, seed, strata)
+
+
+def _sqrt_fraction(A, B):
+    """The correctly rounded double of sqrt(A / B) for integers A >= 0 and B > 0 (``permdisp_distance``'s recipe): e is
+    chosen so that N = floor((A / B) 4^e) has 127 or 128 bits and m is its integer square root (64 bits); m' = 2 m when
+    (A / B) 4^e is the integer m^2 and 2 m + 1 otherwise: the sticky bit makes the one conversion of m' / 2^(e + 1)
+    round correctly."""
+    A, B = int(A), int(B)
+    if A == 0:
+        return 0.0
+    e = (127 - (A.bit_length() - B.bit_length())) // 2
+    while True:
+        num, d = (A << (2 * e), B) if e >= 0 else (A, B << (-2 * e))
+        N, rest = divmod(num, d)
+        bits_n = N.bit_length()
+        if bits_n < 127:
+            e += 1
+        elif bits_n > 128:
+            e -= 1
+        else:
+            break
+    m = math.isqrt(N)
+    m2 = 2 * m if (rest == 0 and m * m == N) else 2 * m + 1
+    return float(Fraction(m2, 1 << (e + 1)) if e + 1 >= 0 else Fraction(m2 << -(e + 1)))
+
+
+def mantel_statistic(P, T, sx, sxx, sy, syy):
+    """The Mantel statistic r of one permutation as a correctly rounded double, from the integers of icikt_mantel_f64:
+    P pairs, T = sum x y, and the moments sum x, sum x^2, sum y, sum y^2.  With num = P T - sx sy and
+    den = (P sxx - sx^2)(P syy - sy^2), r = num / sqrt(den): the sign of num times the correctly rounded root of
+    num^2 / den.  None when a factor of den is 0 (x or y is constant, or P = 0): r is undefined."""
+    P, T, sx, sxx, sy, syy = (int(v) for v in (P, T, sx, sxx, sy, syy))
+    vx, vy = P * sxx - sx * sx, P * syy - sy * sy
+    if P <= 0 or vx <= 0 or vy <= 0:
+        return None
+    num = P * T - sx * sy
+    root = _sqrt_fraction(num * num, vx * vy)
+    return -root if num < 0 else root
+
+
+def _mantel_rank2(values, descending):
+    """The doubled average rank of every value among all of them, -0 as +0: ascending lo + hi + 1 (lo the values below,
+    hi those at or below), descending 2 M - lo - hi + 1, as int64."""
+    v = np.asarray(values, dtype=np.float64) + 0.0
+    asc = np.sort(v)
+    lo = np.searchsorted(asc, v, "left").astype(np.int64)
+    hi = np.searchsorted(asc, v, "right").astype(np.int64)
+    return 2 * v.shape[0] - lo - hi + 1 if descending else lo + hi + 1
+
+
+def _mantel_quantise_x(raw):
+    """mantel::quantise_x (csrc/icikt_mantel.h) on an array of raw values without NaN, as int64: -0 is +0, d = 1.0 - raw
+    in double, xv = rint(ldexp(d, 30))."""
+    return np.rint(np.ldexp(1.0 - (np.asarray(raw, dtype=np.float64) + 0.0), MANTEL_X_FRAC_BITS)).astype(np.int64)
+
+
+def _mantel_quantise_y(y):
+    """mantel::quantise_y on the finite doubles y, as int64: lo and hi the smallest and largest, span = hi - lo one
+    double operation, (m, e) = frexp(span), yv = rint(ldexp(y - lo, 31 - e)).  A span that is not finite is refused."""
+    y = np.asarray(y, dtype=np.float64)
+    if y.size == 0:
+        return np.zeros(0, dtype=np.int64)
+    lo, hi = y.min(), y.max()
+    with np.errstate(over="ignore"):
+        span = hi - lo
+    if not np.isfinite(span):
+        raise ValueError("the span of `other` (its largest minus its smallest value) is not finite")
+    e = int(np.frexp(span)[1])
+    return np.rint(np.ldexp(y - lo, MANTEL_Y_BITS - e)).astype(np.int64)
+
+
+def _mantel_dot(x, y):
+    """sum x y of two int64 arrays of values below 2^32, as a Python int: the four products of the 16-bit halves are
+    each below 2^32, and a sum of fewer than 2^31 of them stays in int64."""
+    xl, xh, yl, yh = x & 0xFFFF, x >> 16, y & 0xFFFF, y >> 16
+    ll, lh, hl, hh = (int(np.dot(a, b)) for a, b in ((xl, yl), (xl, yh), (xh, yl), (xh, yh)))
+    return ll + ((lh + hl) << 16) + (hh << 32)
+
+
+def _mantel_numpy(raw, other, method, perms):
+    """The integers of icikt_mantel_f64 from a full S x S raw matrix and the condensed `other`, for engines without a
+    mantel method (the CPU tests' checker engines): (n_pairs [2], T [1 + n_perm] of Python ints, (sx, sxx, sy, syy),
+    n_ge, n_le)."""
+    raw = np.asarray(raw, dtype=np.float64)
+    S = raw.shape[0]
+    iu, ju = np.triu_indices(S, k=1)
+    v = raw[iu, ju]
+    n_na = int(np.isnan(v).sum())
+    perms = np.asarray(perms, dtype=np.int64).reshape(-1, S)
+    T = np.zeros(1 + perms.shape[0], dtype=object)
+    n_pairs = np.array([v.shape[0] - n_na, n_na], dtype=np.int64)
+    if n_na > 0 or v.shape[0] == 0:
+        n_cmp = 0 if n_na > 0 else perms.shape[0]
+        return n_pairs, T, (0, 0, 0, 0), n_cmp, n_cmp
+    if method == "spearman":
+        xv, yv = _mantel_rank2(v, True), _mantel_rank2(other, False)
+    else:
+        xv, yv = _mantel_quantise_x(v), _mantel_quantise_y(other)
+    table = np.zeros((S, S), dtype=np.int64)
+    table[iu, ju] = yv
+    table[ju, iu] = yv
+    for t, pi in enumerate(np.vstack([np.arange(S, dtype=np.int64)[None, :], perms])):
+        T[t] = _mantel_dot(xv, table[pi[iu], pi[ju]])
+    n_ge = sum(1 for t in T[1:] if t >= T[0])
+    n_le = sum(1 for t in T[1:] if t <= T[0])
+    return n_pairs, T, (int(xv.sum()), _mantel_dot(xv, xv), int(yv.sum()), _mantel_dot(yv, yv)), n_ge, n_le
+
+
+def _mantel_other(other, S):
+    """`other` of ici_kendalltau_mantel as the condensed float64 vector of its P pairs in combn order."""
+    if _lib.is_sparse(other):
+        other = other.toarray()
+    a = np.asarray(other)
+    if a.dtype == object or not (np.issubdtype(a.dtype, np.number) or a.dtype == np.bool_):
+        raise ValueError("`other` must be numeric")
+    a = np.asarray(a, dtype=np.float64)
+    P = S * (S - 1) // 2
+    if a.ndim == 2 and a.shape == (S, S):
+        iu, ju = np.triu_indices(S, k=1)
+        upper, lower = a[iu, ju], a[ju, iu]
+        both_nan = np.isnan(upper) & np.isnan(lower)
+        differ = np.flatnonzero((upper != lower) & ~both_nan)
+        if differ.size:
+            i, j = int(iu[differ[0]]), int(ju[differ[0]])
+            raise ValueError(f"`other` must be exactly symmetric: other[{i}, {j}] = {float(a[i, j])!r} but "
+                             f"other[{j}, {i}] = {float(a[j, i])!r}")
+        vec = np.ascontiguousarray(upper)
+    elif a.ndim == 1 and a.shape[0] == P:
+        vec = np.ascontiguousarray(a)
+    else:
+        raise ValueError(f"`other` must be an S x S matrix or a condensed vector of length S (S - 1) / 2 "
+                         f"(S = {S}: {P}), not of shape {a.shape}")
+    bad = np.flatnonzero(~np.isfinite(vec))
+    if bad.size:
+        iu, ju = np.triu_indices(S, k=1)
+        raise ValueError(f"`other` must be finite: the value of pair ({int(iu[bad[0]])}, {int(ju[bad[0]])}) is "
+                         f"{float(vec[bad[0]])!r}")
+    return vec
+
+
+def ici_kendalltau_mantel(data_matrix, other, method="pearson", permutations=999, seed=None, strata=None,
+                          return_perms=True, global_na=(float("nan"), float("inf"), 0), perspective="global",
+                          alternative="two.sided", continuity=False, colnames=None, engine=None):
+    """Does the structure of the ICI-Kendall-tau correlations of the samples (columns) agree with ANOTHER matrix of the
+    same samples -- another omics layer, run order or collection time as ``|t_i - t_j|``, geographic distance, the
+    distances of ``cor_fast``, a 0/1 design matrix: the Mantel test (Mantel 1967; ``vegan::mantel``,
+    ``skbio.stats.distance.mantel``) of the dissimilarity ``1 - raw`` against ``other``, with its permutation test --
+    without the S x S matrices ``ici_kendalltau`` returns.
+
+    ``other`` is an S x S array (exactly symmetric; its diagonal is ignored) or a condensed vector with one value per
+    pair i < j (``scipy.spatial.distance.squareform`` order), every value finite.  ``statistic`` is the correlation r
+    of the two vectors of P = S (S - 1) / 2 pairs: Pearson's (``method="pearson"``, the default, as in vegan) or
+    Spearman's (``method="spearman"``: both vectors are replaced by their average ranks).  r is NA when either vector
+    is constant.
+
+    EXACTNESS.  Both vectors become integers below 2^32 by one fixed rule -- for spearman the doubled average ranks
+    (-0 equals +0), for pearson ``rint((1 - raw) 2^30)`` and ``rint((y - min) 2^(31 - e))`` with ``(m, e) =
+    frexp(max - min)``, which moves each value by at most 2^-31 of its range -- and everything after that is integer
+    arithmetic: T(pi) = sum x_ij y_pi(i)pi(j), the moments, and the comparison of T(pi) with the observed T.  The
+    result is a pure function of the input, ``other`` and the permutations; a 0/1 design matrix gives many exactly
+    equal T, and they compare as equal.  ``statistic`` and ``perm_statistic`` come from the integers by one correctly
+    rounded square root (``mantel_statistic``).
+
+    EVERY PAIR IS NEEDED.  With a pair whose ``raw`` is NA (``n_na > 0``) nothing is imputed and no pair is dropped:
+    every double of the result is NA, and one warning says so.  ``ici_kendalltau_medians`` gives ``n_valid`` per column,
+    which finds the columns to leave out.
+
+    THE PERMUTATIONS permute the samples of ``other`` (rows and columns together); they are fixed by (S, ``seed``,
+    ``strata``): ``mantel_permutations`` is the rule, and ``codes[perm_t]`` is the labelling ``ici_kendalltau_anosim``
+    draws for the same seed.  ``permutations`` is their number (999, at most 1 000 000) or an integer array [n_perm, S]
+    whose rows are permutations of 0 .. S - 1, used as given.  ``pvalue`` is ``(1 + n_ge) / (1 + n_perm)`` with
+    ``n_ge`` the permutations whose T is ``>=`` the observed T (vegan's one-sided test for a positive association);
+    ``n_le`` counts ``<=`` for the other side.  On the HIP engine everything up to the integers runs on the device
+    (icikt_mantel_f64); a matrix has at most 65 535 samples and the table of ``other`` takes 4 S^2 bytes there.  The
+    other arguments are ``ici_kendalltau``'s (column names are required).
+
+    Returns a dict: ``statistic``, ``pvalue``, ``n_permutations``, ``n_ge``, ``n_le``, ``n_valid``, ``n_na``,
+    ``perm_statistic`` ([n_perm]; only with ``return_perms``), ``method``, ``sums`` (the integers: ``T`` [1 + n_perm],
+    index 0 the observed one, ``sx``, ``sxx``, ``sy``, ``syy``), ``sample_id``, ``max_taumax`` and ``run_time``.
+    """
+    if method not in _lib.MANTEL:
+        raise ValueError('`method` must be "pearson" or "spearman"')
+    data_matrix, names, n_sample = _select_input(data_matrix, colnames)
+    _need_pairs(n_sample)
+    S = n_sample
+    vec = _mantel_other(other, S)
+    if method == "pearson":
+        _mantel_quantise_y(np.array([vec.min(), vec.max()]))   # (refuses a span that is not finite)
+    perms = mantel_permutations(S, permutations, seed, strata)
+    if perms.size and not np.array_equal(np.sort(perms, axis=1), np.broadcast_to(np.arange(S, dtype=np.int32), perms.shape)):
+        raise ValueError("every row of `permutations` must be a permutation of 0 .. S - 1")
+    n_perm = int(perms.shape[0])
+    eng = engine or _default_engine()
+    if hasattr(eng, "mantel"):
+        (n_pairs, T, mom, n_ge, n_le, max_taumax), t_diff = _on_device(
+            eng, data_matrix, global_na,
+            lambda X, gna: eng.mantel(X, vec, method, perms if n_perm else None, gna, perspective, alternative,
+                                      continuity, 0))
+    else:
+        mats5, t_diff, max_taumax = _from_full(eng, data_matrix, names, global_na, perspective, True, alternative,
+                                               continuity)
+        n_pairs, T, mom, n_ge, n_le = _mantel_numpy(mats5[1], vec, method, perms)
+    P, n_na = S * (S - 1) // 2, int(n_pairs[1])
+    if n_na > 0:
+        warnings.warn(f"The Mantel test needs every pair and {n_na} of them have no raw value: every statistic is NA.  "
+                      "`ici_kendalltau_medians` returns `n_valid` per column, which finds the columns to leave out.",
+                      RuntimeWarning, stacklevel=2)
+        obs, stats = None, [None] * n_perm
+    else:
+        obs = mantel_statistic(P, T[0], *mom)
+        stats = [mantel_statistic(P, t, *mom) for t in T[1:]] if return_perms else None
+    res = {"statistic": _as_float(obs), "pvalue": _na_real() if obs is None else float(Fraction(1 + int(n_ge), 1 + n_perm)),
+           "n_permutations": n_perm, "n_ge": int(n_ge), "n_le": int(n_le), "n_valid": int(n_pairs[0]), "n_na": n_na}
+    if return_perms:
+        res["perm_statistic"] = np.array([_as_float(f) for f in stats], dtype=np.float64)
+    res.update({"method": method, "sums": {"T": T, "sx": int(mom[0]), "sxx": int(mom[1]), "sy": int(mom[2]), "syy": int(mom[3])},
+                "sample_id": list(names), "max_taumax": max_taumax, "run_time": t_diff})
+    return res
 
 
 # --------------------------------------------------------------------------------------------------

@@ -318,6 +318,29 @@ hipError_t launch_pmv_perm(const unsigned long long* q, const uint16_t* labT, in
 hipError_t launch_pmv_classes(const uint16_t* labT, const unsigned long long* colsum_lo,
                               const unsigned long long* colsum_hi, int S, int n_class, long long n_lab,
                               unsigned long long* bins_lo, unsigned long long* bins_hi, hipStream_t s);
+// ---- Mantel: 1 - raw against another matrix of the same samples, with its permutation test (icikt_mantel.hip) ----
+// (the label plane -- a permutation is a labelling with S classes -- and the batch keys are icikt_labels.h's, the strip is ANOSIM's)
+constexpr int MANTEL_ROW_RUN = 1024;      // rows of a workgroup's run in k_mantel_perm
+constexpr int MANTEL_M_S_LO = 0, MANTEL_M_S_HI = 1, MANTEL_M_Q_LO = 2, MANTEL_M_Q_HI = 3, MANTEL_MOMENTS = 4;   // launch_mantel_moments' words
+// plane [n]: finite doubles y become the sortable keys of -y, in place
+hipError_t launch_mantel_ykeys(unsigned long long* plane, long long n, hipStream_t s);
+// yv[e] = mantel::quantise_y(y[e], lo, ex) (icikt_mantel.h) of the finite doubles y [n]; yv is another plane
+hipError_t launch_mantel_yquant(const unsigned long long* y, long long n, double lo, int ex, unsigned long long* yv,
+                                hipStream_t s);
+// plane: a value below 2^32 per pair of combn(S, 2).  tab [S][S] 32-bit words: tab[i][j] = tab[j][i] = the pair's value,
+// 0 on the diagonal; every cell written
+hipError_t launch_mantel_expand(const unsigned long long* plane, int S, uint32_t* tab, hipStream_t s);
+// kept: the whole combn plane launch_median_keep writes (n keys).  xv[e] = mantel::quantise_x of the key's double, 0 for
+// NA_KEY; *n_na (zeroed by the caller) += the NA_KEY pairs
+hipError_t launch_mantel_xquant(const unsigned long long* kept, long long n, unsigned long long* xv,
+                                unsigned long long* n_na, hipStream_t s);
+// out [MANTEL_MOMENTS] (zeroed by the caller) += the limbs of v and of v^2, v the low 32 bits of plane[e], e < n
+hipError_t launch_mantel_moments(const unsigned long long* plane, long long n, unsigned long long* out, hipStream_t s);
+// permT [n_groups][S][ANO_PB] halfwords as launch_anosim_perm's labT, every entry below S: permutation g * ANO_PB + p
+// sends sample s to permT[(g * S + s) * ANO_PB + p].  t_lo / t_hi [n_groups][ANO_PB] (zeroed by the caller) += the low 32
+// bits / the rest of xv[(i, j)] * tab[pi(i)][pi(j)] over the pairs i < j: T = hi 2^32 + lo.  strip as launch_anosim_perm
+hipError_t launch_mantel_perm(const unsigned long long* xv, const uint32_t* tab, const uint16_t* permT, int S, int n_groups,
+                              int strip, unsigned long long* t_lo, unsigned long long* t_hi, hipStream_t s);
 // ---- PERMDISP: every sample's sum of squared dissimilarities to every class (icikt_permdisp.hip) ----
 constexpr long long DISP_MAX_CELLS = 1ll << 26;   // == ICIKT_PERMDISP_MAX_CELLS: S n_class, 16 bytes a cell
 // kept: the whole combn(S, 2) plane launch_median_keep writes; cls [S]: a class in 0 .. n_class - 1 per sample (checked

@@ -228,6 +228,14 @@ struct icikt_ctx {
     DevBuf<unsigned long long> colsum_lo, colsum_hi, bins_lo, bins_hi, totals;
   } pmv;
 
+  // Mantel (icikt_mantel_f64): the symmetric S x S table of the other matrix's integers, the two limbs of T of a batch of
+  // permutations (the batch itself: labels), and the call's words (x's moments, y's moments, the NA pairs); `other`, its
+  // keys and ranks pass through sel (kept, plane_a, plane_b) before the first block, x's keys and integers after it
+  struct MantelBufs {
+    DevBuf<uint32_t> table;
+    DevBuf<unsigned long long> t_lo, t_hi, words;
+  } mantel;
+
   // PERMDISP (icikt_permdisp_f64): the class of every sample, the two limbs of the S x n_class table and the call's
   // totals (NA pairs, Q's limbs); the keys are in sel.kept
   struct PermdispBufs {

@@ -808,6 +808,55 @@ int icikt_pcoa_f64(icikt_ctx *ctx, const double *X, int64_t n_feat, int64_t n_sa
  * tests/test_gpu_pcoa.py holds against numpy for every block width's code path. */
 int icikt_pcoa_apply_dev(icikt_ctx *ctx, const double *d_G, const double *d_V, int64_t n_samp, int b, double *d_W);
 
+/* ---- the Mantel test: 1 - raw against another matrix of the same samples, with its permutation test --------------------
+ *
+ * Mantel 1967; vegan::mantel, skbio.stats.distance.mantel.  The triangle runs as in icikt_anosim_f64; a pair is a VALUE
+ * iff its raw is not NA.  x is the dissimilarity 1 - raw of the data matrix, y the caller's `other`: one finite double
+ * per pair i < j in combn order (scipy's squareform order).  Both vectors become unsigned integers below 2^32:
+ *   ICIKT_MANTEL_SPEARMAN   the doubled average rank among the P = n_samp (n_samp - 1) / 2 values, ascending in value:
+ *                for x icikt_anosim_f64's r2 with M = P, for y lo + hi + 1 (lo: the values below, hi: those at or below)
+ *   ICIKT_MANTEL_PEARSON    xv = llrint(ldexp(1.0 - raw, 30)), raw the double of the pair's key (-0 is +0), and
+ *                yv = llrint(ldexp(y - lo, 31 - e)) with lo and hi the smallest and largest y, span = hi - lo and
+ *                (m, e) = frexp(span): IEEE double, one rounding each, round half to even; both in 0 .. 2^31
+ *                (csrc/icikt_mantel.h).  A span that is not finite is ICIKT_E_INVALID
+ * For a permutation pi of the samples T(pi) = sum over i < j of xv_ij yv_{pi(i) pi(j)}; the observed T is that of the
+ * identity.  With M = P: r = (M T - Sx Sy) / sqrt((M Sxx - Sx^2)(M Syy - Sy^2)), undefined when a factor is 0.  This
+ * entry returns integers only; r is the caller's.
+ *   other        [P] doubles, every one finite (one that is not: ICIKT_E_INVALID, the message names its position)
+ *   perms        [n_perm][n_samp] row-major sample indices, 0 <= n_perm <= ICIKT_MANTEL_MAX_PERM; every row must be a
+ *                permutation of 0 .. n_samp - 1 (else ICIKT_E_INVALID: "perms[q][s] = v occurs twice" / "is outside
+ *                0 .. S - 1"); all rows are checked before anything is touched
+ *   n_pairs      [2] the values and the NA pairs
+ *   t_lo, t_hi   [1 + n_perm] T = t_hi 2^32 + t_lo, each limb a sum below 2^63 (t_lo may exceed 2^32); index 0 is the
+ *                identity, index 1 + t permutation t
+ *   moments      [8] Sx, Sxx, Sy, Syy as limbs: Sx = moments[1] 2^32 + moments[0], Sxx = moments[3] 2^32 + moments[2],
+ *                Sy = moments[5] 2^32 + moments[4], Syy = moments[7] 2^32 + moments[6]
+ *   n_ge, n_le   the permutations with T >= / <= the observed T, compared exactly as 128-bit integers: without an NA
+ *                pair the denominator of r does not depend on the permutation.  (1 + n_ge) / (1 + n_perm) is vegan's
+ *                p-value
+ * WITH AN NA PAIR (n_pairs[1] > 0) nothing is summed: every T and moment is 0 and n_ge = n_le = 0; the permutations
+ * are checked all the same.  n_samp of 0 or 1 gives zero sums; it is no error.
+ * All outputs but max_taumax and reason_counts (as icikt_topk_f64, over all pairs) are required.  A bad method, a bad
+ * n_perm, a null other or perms where one is needed, a null output, a value of other that is not finite, a row of perms
+ * that is no permutation: ICIKT_E_INVALID before anything -- the context or an output -- is touched.  n_samp <=
+ * ICIKT_TOPK_MAX_SAMPLES; n_feat, global_na and the state the call leaves behind (none): as icikt_topk_f64.  The result
+ * is a pure function of the input, other and the permutations: integer sums, counts and comparisons, whatever the
+ * block cut, the sort's tile, the batch, the strip or the grid.
+ * Device memory: the prepared matrix, one block's buffers, 24 bytes per pair of the triangle (16 for pearson) for the
+ * key planes, 4 n_samp^2 bytes for the table of y (n_samp = 65 535: 17 GB), and a batch of indices at two bytes each
+ * (64 MB unless the anoperms plan key says otherwise).  A failed allocation is ICIKT_E_HIP.  With ICIKT_FLAG_TIMING
+ * the kernels of y, the keep, the ranks or quantisation and the permutation kernel are accounted under
+ * ICIKT_K_EPILOGUE.
+ * icikt_mantel_in / icikt_mantel_csc: the same on a typed view / a CSC view of the matrix (below). */
+#define ICIKT_MANTEL_MAX_PERM 1000000
+#define ICIKT_MANTEL_PEARSON 0
+#define ICIKT_MANTEL_SPEARMAN 1
+int icikt_mantel_f64(icikt_ctx *ctx, const double *X, int64_t n_feat, int64_t n_samp, int64_t ld, const double *global_na,
+                     int n_global_na, int perspective, int alternative, int continuity, uint32_t flags,
+                     const double *other, int method, const int32_t *perms, int64_t n_perm, int64_t *n_pairs,
+                     int64_t *t_lo, int64_t *t_hi, int64_t *moments, int64_t *n_ge, int64_t *n_le, double *max_taumax,
+                     int64_t *reason_counts);
+
 /* ---- query samples against a reference cohort: the query x reference rectangle ---------------------------------------
  *
  * Every column of Q (n_feat x n_query, leading dimension ld_query) with every column of R (n_feat x n_reference,
@@ -1089,6 +1138,11 @@ int icikt_pcoa_in(icikt_ctx *ctx, const icikt_input *X, int64_t n_feat, int64_t 
                   int max_basis, const double *start, int64_t *n_pairs, int64_t *q_total, int64_t *row_lo,
                   int64_t *row_hi, double *eigenvalues, double *vectors, double *residuals, double *frobenius,
                   double *min_ritz, int64_t *solver, double *gower, double *max_taumax, int64_t *reason_counts);
+int icikt_mantel_in(icikt_ctx *ctx, const icikt_input *X, int64_t n_feat, int64_t n_samp, const double *global_na,
+                     int n_global_na, int perspective, int alternative, int continuity, uint32_t flags,
+                     const double *other, int method, const int32_t *perms, int64_t n_perm, int64_t *n_pairs,
+                     int64_t *t_lo, int64_t *t_hi, int64_t *moments, int64_t *n_ge, int64_t *n_le, double *max_taumax,
+                     int64_t *reason_counts);
 int icikt_matrix_in(icikt_ctx *ctx, const icikt_input *X, int64_t n_feat, int64_t n_samp, const double *global_na,
                     int n_global_na, const int32_t *pi, const int32_t *pj, int64_t n_pairs, int perspective,
                     int alternative, int continuity, uint32_t flags, int scale_max, int diag_good, double *out5,
@@ -1186,6 +1240,11 @@ int icikt_pcoa_csc(icikt_ctx *ctx, const icikt_csc_input *X, int64_t n_feat, int
                    int max_basis, const double *start, int64_t *n_pairs, int64_t *q_total, int64_t *row_lo,
                    int64_t *row_hi, double *eigenvalues, double *vectors, double *residuals, double *frobenius,
                    double *min_ritz, int64_t *solver, double *gower, double *max_taumax, int64_t *reason_counts);
+int icikt_mantel_csc(icikt_ctx *ctx, const icikt_csc_input *X, int64_t n_feat, int64_t n_samp, const double *global_na,
+                     int n_global_na, int perspective, int alternative, int continuity, uint32_t flags,
+                     const double *other, int method, const int32_t *perms, int64_t n_perm, int64_t *n_pairs,
+                     int64_t *t_lo, int64_t *t_hi, int64_t *moments, int64_t *n_ge, int64_t *n_le, double *max_taumax,
+                     int64_t *reason_counts);
 int icikt_missingness_csc(icikt_ctx *ctx, const icikt_csc_input *X, int64_t n_feat, int64_t n_samp, const int32_t *pi,
                           const int32_t *pj, int64_t n_pairs, int64_t *missingness);
 int icikt_col_medians_csc(icikt_ctx *ctx, const icikt_csc_input *X, int64_t n_feat, int64_t n_samp,
